@@ -13,7 +13,15 @@ all results visible to the host, i.e. H2D + kernels + D2H through ydc_dispatch â
 which is which, and `value_synchronous` / `value_pipelined` / `value_end_to_end` carry the
 three rates side by side.
 
-N = 1 (default cfg2): the line also carries `configs` â€” compact records of BASELINE.json
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps
+and prints the line: the contract keys (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...) and nothing that takes work of its own. `--full` adds everything below: the
+latency samples, the end-to-end, steady-state and per-kernel figures, the roofline, the CPU
+reference, the other configurations and the TaskDispatcher surface. `--dump-outputs DIR` writes
+what the timed path returned in its last timed step as DIR/<name>.npy (float64; the inputs are
+seeded, so two builds can be compared output for output).
+
+N = 1 (default cfg2, --full): the line also carries `configs` â€” compact records of BASELINE.json
 configs[2] (cfg3), configs[3]'s batch on one GPU (cfg4) and configs[4] (cfg5, streaming), each
 timed in this very run and pinned to the committed fixtures of the verbatim reference
 (tests/golden: first 50k placements / 200 ticks) â€” no CPU replay, a few seconds.
@@ -26,8 +34,8 @@ from the environment; `--gpus` must agree with WORLD_SIZE. torch.distributed (gl
 for the rendezvous, the barriers and the max-over-ranks of the wall time; the data path of
 the sharded batch is RCCL inside libydc.so. `--scaling weak` (default): G ranks place ONE
 global batch of G x (the config's requests) on a pool of G x (the config's servants);
-`--scaling strong`: the config's batch itself is cut into G rank ranges. For N > 1 the line
-also carries `strong_cfg4`: BASELINE.json configs[3] as specified (4M requests x 16k
+`--scaling strong`: the config's batch itself is cut into G rank ranges. For N > 1 and --full
+the line also carries `strong_cfg4`: BASELINE.json configs[3] as specified (4M requests x 16k
 servants cut over the N ranks), timed in the same run.
 Prints ONE JSON line on rank 0.
 """
@@ -50,6 +58,22 @@ METRIC = "task-to-servant assignments/sec on synthetic pool"
 def percentile(a, q):
     a = np.sort(np.asarray(a))
     return float(a[min(len(a) - 1, int(np.ceil(q * len(a))) - 1)]) if len(a) else 0.0
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, as float64 (exact for every uint32 servant
+    index, IDX_TIMEOUT and IDX_ENV_NOT_FOUND included). An array larger than its share of
+    DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its elements, kept in index order."""
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_LIMIT_BYTES // 8 // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        if len(a) > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), cap, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float64))
 
 
 def cpu_baseline(sv, tk, max_tasks=None):
@@ -138,26 +162,30 @@ def fixture_digests_ok(cfg, sv, tk, servant_idx):
     return bool(ok), n
 
 
-def stream_record(args, steps, warmup, ref_ticks, device=0):
+def stream_record(args, steps, warmup, ref_ticks, device=0, full=True, dump=None):
     """BASELINE.json configs[4]: 10k requests/tick x 2k servants with rolling heartbeats (10 % of
     the servants per tick) and 10k frees per tick; the whole tick is one replay of a captured
     hipGraph (ydc_stream_tick). A step is a tick; only the tick call is timed (the event
-    generator is host-side test scaffolding). Host buffers in, host results out. Every one of
-    the first 200 ticks is compared with what the verbatim reference answered on the same
-    stream (tests/golden/ref_cfg5_stream_200_ticks.npz); with ref_ticks > 0 the reference class
-    also replays the first ticks beside it (heartbeats, frees by grant id, sequential
-    WaitForStartingNewTask calls): cpu_baseline + per-tick parity."""
+    generator is host-side test scaffolding). Host buffers in, host results out. full: every one
+    of the first 200 ticks is compared with what the verbatim reference answered on the same
+    stream (tests/golden/ref_cfg5_stream_200_ticks.npz), and the same step is timed assembled in
+    place and enqueued eagerly (stream_variants); with ref_ticks > 0 the reference class also
+    replays the first ticks beside it (heartbeats, frees by grant id, sequential
+    WaitForStartingNewTask calls): cpu_baseline + per-tick parity. dump: --dump-outputs of the
+    last timed tick."""
     from yadcc_amd import binding, pack, streaming, synth
     sv, _ = synth.make_config("cfg5")
     es = streaming.EventStream(sv, 10_000, 10_000)
     ctx = binding.Context(device=device)
     ctx.upload_servants(pack.to_abi_columns(sv))
     ctx.stream_begin(es.hb + 8, 10_000, 10_000)
-    try:
-        fx = golden("ref_cfg5_stream_200_ticks.npz")
-        fx_ticks = int(fx["ticks"])
-    except OSError:
-        fx, fx_ticks = None, 0
+    fx, fx_ticks = None, 0
+    if full:
+        try:
+            fx = golden("ref_cfg5_stream_200_ticks.npz")
+            fx_ticks = int(fx["ticks"])
+        except OSError:
+            pass
     ref = ref_ids = None
     ref_secs, ref_granted, ref_lat, parity = 0.0, 0, [], True
     fx_ok, fx_seen = True, 0
@@ -195,7 +223,60 @@ def stream_record(args, steps, warmup, ref_ticks, device=0):
         if t >= warmup:
             lat.append(dt)
             granted += int((got < binding.IDX_ENV_NOT_FOUND).sum())
+    if dump:
+        dump_outputs(dump, {"servant_idx": got})
     st = ctx.stats()
+    out = {
+        "metric": METRIC,
+        "value": granted / sum(lat), "unit": "assignments/s", "n_gpus": 1,
+        "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * sum(lat) / len(lat),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+        "data": "synthetic",
+        "value_definition": "end to end per tick: host buffers in (one H2D copy), registry "
+                            "deltas + batch + commit, results back on the host (PCIe included)",
+        "config": {"workload": "cfg5 streaming: 10000 requests + 10000 frees + %d heartbeats per "
+                               "tick x %d servants, hipGraph-captured step" % (es.hb, es.n),
+                   "parallelism": "1 GPU", "inputs": "host buffers per tick (PCIe included)"},
+        "p99_dispatch_latency_ms": 1e3 * percentile(lat, 0.99),
+        "p50_dispatch_latency_ms": 1e3 * percentile(lat, 0.50),
+        "latency_samples": len(lat),
+        "stats": {k: v for k, v in st.items() if k != "stage_ms"},
+    }
+    if full:
+        out.update(stream_variants(ctx, es, sv, steps, fx, fx_ticks, device))
+        out["parity_vs_reference_fixture"] = bool(fx_ok) if fx_seen else None
+        out["fixture_ticks"] = fx_seen
+    # 16 B per request + 40 B per servant per tick (SURVEY.md Â§8d) over the whole tick: the
+    # captured step is one graph launch, so the "dominant kernel" is the step itself.
+    alg = 16 * 10_000 + 40 * es.n
+    tick_s = sum(lat) / len(lat)
+    out["roofline"] = {"bound": "hbm", "kernel": "captured step (one hipGraph launch)",
+                       "achieved": alg / tick_s / 1e9, "peak": 8000.0, "unit": "GB/s",
+                       "frac": alg / tick_s / 8e12, "traffic": None,
+                       "algorithmic_bytes_per_launch": alg, "avg_launch_us": tick_s * 1e6}
+    if ref is not None:
+        ref.close()
+        rl = np.concatenate(ref_lat)
+        out["cpu_baseline"] = {
+            "value": ref_granted / ref_secs, "unit": "assignments/s", "cores": 1,
+            "kind": "reference",
+            "sample": "the first %d ticks of the same stream replayed through the reference class "
+                      "(heartbeats, frees by grant id, %d sequential WaitForStartingNewTask calls, "
+                      "%.2f s inside them)" % (ref_ticks, len(rl), ref_secs),
+            "p99_latency_us": percentile(rl, 0.99) / 1e3,
+            "ms_per_tick": 1e3 * ref_secs / ref_ticks,
+            "host_cores_available": os.cpu_count()}
+        out["parity_vs_cpu_baseline"] = parity
+        out["parity_ticks"] = ref_ticks
+    ctx.stream_end()
+    ctx.close()
+    return out
+
+
+def stream_variants(ctx, es, sv, steps, fx, fx_ticks, device):
+    """--full, cfg5: the ticks that follow the timed ones assembled in place, and the same stream
+    from its start with the step enqueued eagerly -> the two records of stream_record."""
+    from yadcc_amd import binding, pack, streaming, synth
     # The same ticks assembled where the captured step reads them (ydc_stream_buffers_get): what
     # is left of a tick when nothing is copied on either side. Same stream, the next ticks.
     in_place = []
@@ -242,54 +323,11 @@ def stream_record(args, steps, warmup, ref_ticks, device=0):
         ctx2.stream_end()
     finally:
         ctx2.close()
-    out = {
-        "metric": METRIC,
-        "value": granted / sum(lat), "unit": "assignments/s", "n_gpus": 1,
-        "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * sum(lat) / len(lat),
-        "tick_enqueued_eagerly": eager,
-        "tick_assembled_in_place": {"ms_per_step": 1e3 * sum(in_place) / len(in_place),
-                                    "p99_ms": 1e3 * percentile(in_place, 0.99), "ticks": len(in_place),
-                                    "what": "the tick written into the library's page-locked arena by the caller "
-                                            "(ydc_stream_buffers_get): no staging copy on either side"},
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
-        "data": "synthetic",
-        "value_definition": "end to end per tick: host buffers in (one H2D copy), registry "
-                            "deltas + batch + commit, results back on the host (PCIe included)",
-        "config": {"workload": "cfg5 streaming: 10000 requests + 10000 frees + %d heartbeats per "
-                               "tick x %d servants, hipGraph-captured step" % (es.hb, es.n),
-                   "parallelism": "1 GPU", "inputs": "host buffers per tick (PCIe included)"},
-        "p99_dispatch_latency_ms": 1e3 * percentile(lat, 0.99),
-        "p50_dispatch_latency_ms": 1e3 * percentile(lat, 0.50),
-        "latency_samples": len(lat),
-        "stats": {k: v for k, v in st.items() if k != "stage_ms"},
-        "parity_vs_reference_fixture": bool(fx_ok) if fx_seen else None,
-        "fixture_ticks": fx_seen,
-    }
-    # 16 B per request + 40 B per servant per tick (SURVEY.md Â§8d) over the whole tick: the
-    # captured step is one graph launch, so the "dominant kernel" is the step itself.
-    alg = 16 * 10_000 + 40 * es.n
-    tick_s = sum(lat) / len(lat)
-    out["roofline"] = {"bound": "hbm", "kernel": "captured step (one hipGraph launch)",
-                       "achieved": alg / tick_s / 1e9, "peak": 8000.0, "unit": "GB/s",
-                       "frac": alg / tick_s / 8e12, "traffic": None,
-                       "algorithmic_bytes_per_launch": alg, "avg_launch_us": tick_s * 1e6}
-    if ref is not None:
-        ref.close()
-        rl = np.concatenate(ref_lat)
-        out["cpu_baseline"] = {
-            "value": ref_granted / ref_secs, "unit": "assignments/s", "cores": 1,
-            "kind": "reference",
-            "sample": "the first %d ticks of the same stream replayed through the reference class "
-                      "(heartbeats, frees by grant id, %d sequential WaitForStartingNewTask calls, "
-                      "%.2f s inside them)" % (ref_ticks, len(rl), ref_secs),
-            "p99_latency_us": percentile(rl, 0.99) / 1e3,
-            "ms_per_tick": 1e3 * ref_secs / ref_ticks,
-            "host_cores_available": os.cpu_count()}
-        out["parity_vs_cpu_baseline"] = parity
-        out["parity_ticks"] = ref_ticks
-    ctx.stream_end()
-    ctx.close()
-    return out
+    return {"tick_enqueued_eagerly": eager,
+            "tick_assembled_in_place": {"ms_per_step": 1e3 * sum(in_place) / len(in_place),
+                                        "p99_ms": 1e3 * percentile(in_place, 0.99), "ticks": len(in_place),
+                                        "what": "the tick written into the library's page-locked arena by the "
+                                                "caller (ydc_stream_buffers_get): no staging copy on either side"}}
 
 
 def td_surface(with_reference=True):
@@ -516,6 +554,12 @@ def parse_args(argv=None):
                          "(the default transport), and if its communicator does not come up in time "
                          "the RCCL-free mailbox transport of libydc.so (HIP IPC device memory, then "
                          "the shared host segment) instead of giving the sharded run up")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything, not only the timed steps: latency samples, end-to-end "
+                         "and steady-state loops, per-kernel times, roofline, CPU reference, parity against "
+                         "the committed fixtures, the other configurations and the TaskDispatcher surface")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -722,14 +766,16 @@ def setup(args):
 
 
 def measure_config(E, args, config, scaling, steps, warmup, detail, digests=0, cpu_prefix=0):
-    """Times `steps` batches of `config` on the run's context(s). detail "full": the driver's
-    line (end-to-end loops, CPU baseline, >= 100 latency samples); "compact": a sub-record of
-    it (resident loop, synchronous latencies, per-kernel events, parity against the committed
+    """Times `steps` batches of `config` on the run's context(s). detail "plain": the driver's
+    line of a plain run (the timed steps and nothing else); "full": the driver's line of --full
+    (end-to-end loops, CPU baseline, >= 100 latency samples); "compact": a sub-record of it
+    (resident loop, synchronous latencies, per-kernel events, parity against the committed
     fixture). Returns the record on rank 0, None elsewhere."""
     from yadcc_amd import binding, pack, synth
     dist, torch, ctx = E.dist, E.torch, E.ctx
     rank, world = E.rank, E.world
     full = detail == "full"
+    head = detail != "compact"  # (the run's own configuration: --digests / --shared-ip-frac apply)
 
     def barrier():
         if dist:
@@ -739,8 +785,8 @@ def measure_config(E, args, config, scaling, steps, warmup, detail, digests=0, c
     # Strong: the config's own batch and pool. Either way rank r owns the r-th range of the
     # batch (arrival order).
     n_cfg, s_cfg, n_envs, unk = synth.CONFIGS[config]
-    n_envs = (args.digests if full else digests) or n_envs
-    shared = args.shared_ip_frac if full else 0.0
+    n_envs = (args.digests if head else digests) or n_envs
+    shared = args.shared_ip_frac if head else 0.0
     mult = world if scaling == "weak" else 1
     n_all = n_cfg * mult
     sv = synth.make_servants(s_cfg * mult, n_tasks_hint=n_all, n_envs=n_envs, seed=42,
@@ -799,6 +845,70 @@ def measure_config(E, args, config, scaling, steps, warmup, detail, digests=0, c
     ctx.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if head and args.dump_outputs:
+        # What a caller of the timed path receives from its last step: the placement of the batch
+        # (every rank placed its own range of it) and the servants' running counts after it.
+        # (pipelined: an even number of steps ends in the second pair of result buffers)
+        last_out, last_run = (d_out2, d_run2) if pipelined and steps % 2 == 0 else (d_out, d_run)
+        placed = last_out.numpy()
+        if dist:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(placed, parts, dst=0)
+            placed = np.concatenate(parts) if rank == 0 else None
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"servant_idx": placed, "running_tasks": last_run.numpy()})
+
+    def over_ranks(elapsed, granted):
+        # -> (the slowest rank's timed region, the batch's grants over all ranks)
+        if not dist:
+            return elapsed, float(granted)
+        t = torch.tensor([elapsed], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        g = torch.tensor([float(granted)], dtype=torch.float64)
+        dist.all_reduce(g, op=dist.ReduceOp.SUM)
+        return float(t[0]), float(g[0])
+
+    def record(st, elapsed, granted_all):
+        # The contract keys and what says which batch was timed how.
+        shape = "%d pending requests x %d servants" % (n_all, n_serv)
+        return {
+            "metric": METRIC,
+            "value": granted_all * steps / elapsed,
+            "unit": "assignments/s",
+            "n_gpus": world, "steps": steps, "warmup": warmup,
+            "ms_per_step": 1e3 * elapsed / steps,
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+            "dtype": "u32" if st["key_bits"] <= 32 else "u64",
+            "data": "synthetic",
+            "value_definition": "HBM-resident: request columns, servant table and results stay in "
+                                "HBM (kernels + one 200-byte outcome read-back per batch)%s%s" % (
+                                    ", two batches in flight (ydc_dispatch_device_async: the next "
+                                    "batch is enqueued before the host reads the previous outcome%s)" % (
+                                        "; ms_per_step_synchronous = one batch at a time" if full else "")
+                                    if pipelined else "",
+                                    "; the host-buffer rate of SURVEY.md 8(d) is in end_to_end" if full else ""),
+            "pipeline_depth": 2 if pipelined else 1,
+            "config": {"workload": "%s%s%s: %s%s, %d classes" % (
+                           config, " with %d digests" % n_envs if (head and args.digests) or digests else "",
+                           "" if world == 1 else " (%s scaling)" % scaling, shape,
+                           ", %.0f %% of the servants on shared hosts" % (100 * shared) if shared else "",
+                           st["n_classes"]),
+                       "parallelism": "1 GPU" if world == 1 else
+                                      ("one global batch of %d requests x %d servants sharded by "
+                                       "rank range over %d ranks on %d GPU(s), %s all-gather of boundary "
+                                       "states and servant-slot deltas" % (
+                                           n_all, n_serv, world, min(world, max(E.n_dev, 1)),
+                                           "RCCL" if E.transport == "rccl" else "mailbox (%s)" % E.transport)
+                                       if sharded else E.group_note),
+                       "inputs": "request columns + servant table resident in HBM; results in HBM"},
+            "stats": {k: v for k, v in st.items() if k != "stage_ms"},
+            "granted_all_ranks": int(granted_all),
+        }
+
+    if detail == "plain":
+        st = ctx.stats()
+        elapsed, granted_all = over_ranks(elapsed, st["granted"])
+        return record(st, elapsed, granted_all) if rank == 0 else None
     # Per-batch latency (p50 / p99) and the synchronous rate: one batch in flight, a few untimed
     # calls first (the switch from the pipelined loop, a short run's clocks still settling), at
     # least n_lat samples whatever --steps is.
@@ -821,13 +931,7 @@ def measure_config(E, args, config, scaling, steps, warmup, detail, digests=0, c
             step()
             lat.append(time.perf_counter() - s0)
     st = ctx.stats()
-    granted_all = float(st["granted"])
-    if dist:
-        t = torch.tensor([elapsed], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        g = torch.tensor([granted_all], dtype=torch.float64)
-        dist.all_reduce(g, op=dist.ReduceOp.SUM)
-        elapsed, granted_all = float(t[0]), float(g[0])
+    elapsed, granted_all = over_ranks(elapsed, st["granted"])
     # p50 / p99 want >= 100 samples on the driver's line whatever --steps is (extra batches,
     # outside the timed region).
     lat_all = list(lat)
@@ -956,45 +1060,15 @@ def measure_config(E, args, config, scaling, steps, warmup, detail, digests=0, c
         return None
     host_idx = d_out.numpy()
     host_run = d_run.numpy()
-    shape = "%d pending requests x %d servants" % (n_all, n_serv)
-    out = {
-        "metric": METRIC,
-        "value": granted_all * steps / elapsed,
-        "unit": "assignments/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup,
-        "ms_per_step": 1e3 * elapsed / steps,
-        "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-        "dtype": "u32" if st["key_bits"] <= 32 else "u64",
-        "data": "synthetic",
-        "value_definition": "HBM-resident: request columns, servant table and results stay in "
-                            "HBM (kernels + one 200-byte outcome read-back per batch)%s; the "
-                            "host-buffer rate of SURVEY.md 8(d) is in end_to_end" % (
-                                ", two batches in flight (ydc_dispatch_device_async: the next "
-                                "batch is enqueued before the host reads the previous outcome; "
-                                "ms_per_step_synchronous = one batch at a time)" if pipelined else ""),
-        "pipeline_depth": 2 if pipelined else 1,
+    out = record(st, elapsed, granted_all)
+    out.update({
         "ms_per_step_synchronous": sync_ms,
-        "config": {"workload": "%s%s%s: %s%s, %d classes" % (
-                       config, " with %d digests" % n_envs if (full and args.digests) or digests else "",
-                       "" if world == 1 else " (%s scaling)" % scaling, shape,
-                       ", %.0f %% of the servants on shared hosts" % (100 * shared) if shared else "",
-                       st["n_classes"]),
-                   "parallelism": "1 GPU" if world == 1 else
-                                  ("one global batch of %d requests x %d servants sharded by "
-                                   "rank range over %d ranks on %d GPU(s), %s all-gather of boundary "
-                                   "states and servant-slot deltas" % (
-                                       n_all, n_serv, world, min(world, max(E.n_dev, 1)),
-                                       "RCCL" if E.transport == "rccl" else "mailbox (%s)" % E.transport)
-                                   if sharded else E.group_note),
-                   "inputs": "request columns + servant table resident in HBM; results in HBM"},
         "p99_dispatch_latency_ms": 1e3 * percentile(lat_all, 0.99),
         "p50_dispatch_latency_ms": 1e3 * percentile(lat_all, 0.50),
         "latency_samples": len(lat_all),
-        "stats": {k: v for k, v in st.items() if k != "stage_ms"},
-        "granted_all_ranks": int(granted_all),
         "kernels_us_per_step": {k: 1e3 * v[1] / n_prof for k, v in prof.items()},
         "kernel_launches_per_step": {k: v[0] / n_prof for k, v in prof.items()},
-    }
+    })
     # The three rates side by side, whichever of them `value` is.
     out["value_pipelined"] = out["value"] if pipelined else None
     out["value_synchronous"] = (st["granted"] / (sync_ms * 1e-3) if sync_ms else
@@ -1233,14 +1307,15 @@ def main():
         if world != 1:
             print("[bench] cfg5 (streaming) is a single-GPU configuration", file=sys.stderr)
             return 2
-        out = stream_record(args, args.steps, args.warmup, 0 if args.no_cpu_baseline else 30,
-                            device=int(os.environ.get("LOCAL_RANK", 0)))
+        out = stream_record(args, args.steps, args.warmup, 30 if args.full and not args.no_cpu_baseline else 0,
+                            device=int(os.environ.get("LOCAL_RANK", 0)), full=args.full, dump=args.dump_outputs)
         emit(out)
         return 0
 
     E = setup(args)
-    out = measure_config(E, args, args.config, args.scaling, args.steps, args.warmup, "full")
-    extra = not args.no_extra_configs and not args.digests and not args.shared_ip_frac
+    out = measure_config(E, args, args.config, args.scaling, args.steps, args.warmup,
+                         "full" if args.full else "plain")
+    extra = args.full and not args.no_extra_configs and not args.digests and not args.shared_ip_frac
     if extra and E.world > 1 and E.sharded and not (args.config == "cfg4" and args.scaling == "strong"):
         # BASELINE.json configs[3] as specified: 4M requests x 16k servants cut over the ranks.
         E.phase("%s (%s) timed; cfg4 strong next" % (args.config, args.scaling))

@@ -1,7 +1,7 @@
-"""The bench line the driver parses. The -m gpu tests RUN bench.py on the GPU box (a few steps
-of cfg2, the streaming ticks of cfg5, the group path of one rank) and validate the line that
-comes out — a change that breaks the contract fails here. The CPU part checks what can be
-checked without a device: BASELINE.json and the validator itself on the committed lines."""
+"""The bench line the driver parses. The -m gpu tests RUN bench.py on the GPU box (a plain run
+with its outputs dumped; with --full a few steps of cfg2, the streaming ticks of cfg5, the group
+path of one rank) and validate the line that comes out — a change that breaks the contract
+fails here. The CPU part checks what can be checked without a device: BASELINE.json and the validator itself on the committed lines."""
 import glob
 import json
 import os
@@ -52,7 +52,8 @@ def validate(j, steps=None, streaming=False, cpu_baseline=True):
         assert j["p99_dispatch_latency_ms"] >= j["p50_dispatch_latency_ms"] > 0
 
 
-def run_bench(*args, env=None, timeout=420):
+def bench_line(*args, env=None, timeout=420):
+    """Runs bench.py -> its ONE JSON line, parsed."""
     e = dict(os.environ)
     for k, v in (env or {}).items():
         if v is None:
@@ -67,7 +68,11 @@ def run_bench(*args, env=None, timeout=420):
     assert out.stdout.strip().splitlines()[-1] == lines[0]  # ... and it is the last thing on stdout
     # ... short enough for the driver to ingest (BENCH_r05: a 23.8 KB line came back "parsed": null)
     assert len(lines[0]) < 8192, len(lines[0])
-    line = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def run_bench(*args, env=None, timeout=420):
+    line = bench_line(*args, env=env, timeout=timeout)
     validate_line(line)
     # everything else that was measured is in the file the line names
     detail = json.load(open(os.path.join(ROOT, line["detail_file"])))
@@ -95,7 +100,7 @@ def validate_line(j, cpu_baseline=None):
 
 @pytest.mark.gpu
 def test_bench_cfg2_line():
-    j = run_bench("--steps", "3", "--warmup", "2")
+    j = run_bench("--full", "--steps", "3", "--warmup", "2")
     validate(j, steps=3)
     assert j["n_gpus"] == 1 and j["warmup"] == 2
     assert "cfg2: 100000 pending requests x 2000 servants" in j["config"]["workload"]
@@ -150,7 +155,7 @@ def test_bench_two_ranks_without_a_launcher():
     the gathered placement equal to the oracle's — and BASELINE.json configs[3] (cfg4, strong)
     timed beside the weak figure."""
     env = {k: None for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    j = run_bench("--gpus", "2", "--steps", "3", "--warmup", "2", env=env, timeout=900)
+    j = run_bench("--gpus", "2", "--full", "--steps", "3", "--warmup", "2", env=env, timeout=900)
     validate(j, steps=3, cpu_baseline=False)
     assert j["n_gpus"] == 2 and j["sharded"] is True and j["parity_vs_oracle"] is True
     assert j["transport"] in ("ipc", "ipc-device", "rccl"), j["transport_detail"]
@@ -159,6 +164,56 @@ def test_bench_two_ranks_without_a_launcher():
     assert s["n_gpus"] == 2 and s["scaling"] == "strong" and s["sharded"] is True
     assert "4000000 pending requests x 16000 servants" in s["workload"]
     assert s["parity_vs_oracle"] is True and s["value"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("config", ["cfg2", "cfg5"])
+def test_bench_plain_run_dumps_its_last_step(config, tmp_path):
+    """A plain run (no --full): the contract keys, exactly --steps timed steps, nothing measured
+    beside them; --dump-outputs writes what the timed path returned in its last step — cfg2: the
+    oracle's placement and running counts of the same seeded batch; cfg5: the verbatim
+    reference's answer to that tick (tests/golden)."""
+    import numpy as np
+    from yadcc_amd import synth
+    steps, warmup = 4, 2  # (an even count: the pipelined loop ends in its second result buffers)
+    j = bench_line("--config", config, "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path))
+    for k in REQUIRED:
+        assert k in j, k
+    assert j["steps"] == steps and j["warmup"] == warmup and j["n_gpus"] == 1 and j["higher_is_better"] is True
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["dtype"] in ("u32", "u64")
+    assert not {"cpu_baseline", "configs", "td_surface", "end_to_end_ms", "parity_vs_reference_fixture"} & set(j)
+    idx = np.load(tmp_path / "servant_idx.npy")
+    assert idx.dtype == np.float64
+    if config == "cfg2":
+        from oracle import oraclebind as O
+        assert abs(j["value"] - j["granted_all_ranks"] / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+        sv, tk = synth.make_config("cfg2")
+        want, _, wrun = O.dispatch(sv, tk, "sorted", want_util=False)
+        assert np.array_equal(idx, want.astype(np.float64))
+        assert np.array_equal(np.load(tmp_path / "running_tasks.npy"), wrun.astype(np.float64))
+    else:
+        fx = np.load(os.path.join(ROOT, "tests", "golden", "ref_cfg5_stream_200_ticks.npz"))
+        assert len(idx) == 10_000 and synth.placement_hash(idx.astype(np.uint32)) == int(fx["digest"][warmup + steps - 1])
+
+
+def test_dump_outputs_is_exact_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs' writer: float64 keeps every u32 (IDX_TIMEOUT / IDX_ENV_NOT_FOUND included);
+    an array over its share of the limit becomes the same seeded sample, in index order, every time."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = np.array([0, 1, 0xFFFFFFFE, 0xFFFFFFFF], np.uint32)
+    bench.dump_outputs(str(tmp_path / "a"), {"servant_idx": a})
+    got = np.load(tmp_path / "a" / "servant_idx.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), a)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 8 * 100)
+    big = np.arange(1000, dtype=np.uint32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"servant_idx": big, "running_tasks": big[:10]})
+    s = np.load(tmp_path / "b" / "servant_idx.npy")
+    assert len(s) == 100 and np.all(np.diff(s) > 0)
+    assert np.array_equal(s, np.load(tmp_path / "c" / "servant_idx.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "running_tasks.npy"), big[:10])
 
 
 def test_bench_refuses_a_world_size_that_is_not_gpus():
@@ -172,7 +227,7 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
 
 @pytest.mark.gpu
 def test_bench_cfg5_streaming_line():
-    j = run_bench("--config", "cfg5", "--steps", "40", "--warmup", "5")
+    j = run_bench("--config", "cfg5", "--full", "--steps", "40", "--warmup", "5")
     validate(j, steps=40, streaming=True)
     assert j["parity_ticks"] >= 20 and "hipGraph" in j["config"]["workload"]
     assert j["parity_vs_reference_fixture"] is True and j["fixture_ticks"] == 45
@@ -184,7 +239,7 @@ def test_bench_cfg5_streaming_line():
 def test_bench_group_of_one_rank_line():
     """The N > 1 code path of bench.py with one rank and the RCCL-free transport: the line says
     whether the batch went through ydc_dispatch_sharded and over which transport."""
-    j = run_bench("--steps", "3", "--warmup", "2", "--transport", "ipc", "--no-cpu-baseline",
+    j = run_bench("--full", "--steps", "3", "--warmup", "2", "--transport", "ipc", "--no-cpu-baseline",
                   env={"YDC_BENCH_FORCE_DIST": "1"})
     validate(j, steps=3, cpu_baseline=False)
     assert j["sharded"] is True and j["transport"] == "ipc" and j["parity_vs_oracle"] is True

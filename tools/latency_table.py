@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Renders td_surface.latency of a bench line (python bench.py's JSON) as the text table kept under
+"""Renders td_surface.latency of a bench line (python bench.py --full's JSON) as the text table kept under
 profiles/.   usage: python tools/latency_table.py profiles/r05_bench_driver_line.json"""
 import json
 import sys
@@ -9,7 +9,7 @@ def main():
     path = sys.argv[1]
     d = json.load(open(path))
     L = d["td_surface"]["latency"]
-    print("td_surface.latency of %s (python bench.py --steps %d --warmup %d, one MI355X box):" % (path, d["steps"], d["warmup"]))
+    print("td_surface.latency of %s (python bench.py --full --steps %d --warmup %d, one MI355X box):" % (path, d["steps"], d["warmup"]))
     print("microseconds per CALL, p50 / p99 — ydc_td_wait_for_starting_new_task(s), registry warm, grants freed between calls,")
     print("a heartbeat before every fourth call. tick = resident small-batch kernel (default); launch = one launch per call")
     print("(YDC_TUNE=resident=0); pipeline = the batch pipeline alone (small_batch=0, the round-4 path); reference = the verbatim")

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 cd /tmp
 for X in "$@"; do
   OUT=$ROOT/gpurun_out/$TAG/${CFG}_$(echo "$X" | tr ',= ' '___'); mkdir -p $OUT
-  YDC_TUNE="$X" timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/write" -- python "$ROOT/bench.py" --config $CFG --steps 10 --warmup 5 --no-cpu-baseline --resident-only --no-extra-configs > "$OUT/line.json" 2> "$OUT/write.log"
+  YDC_TUNE="$X" timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/write" -- python "$ROOT/bench.py" --full --config $CFG --steps 10 --warmup 5 --no-cpu-baseline --resident-only --no-extra-configs > "$OUT/line.json" 2> "$OUT/write.log"
   W=$(find "$OUT/write" -name "*.db" | head -1)
   echo "== $CFG YDC_TUNE=$X"
   python $ROOT/tools/rocprof_summary.py pmc "$W" | grep "k_match_pass\|kernel " | head -4

@@ -29,7 +29,7 @@ python tools/rocprof_summary.py hbmtable "cfg2 (100k requests x 2k servants)=pro
 run_bench() {  # <name> <timeout> <bench args...>
   local name=$1 t=$2; shift 2
   rm -f bench_detail.json
-  timeout $t python bench.py "$@" > $F/bench_$name.line 2> $F/bench_$name.err
+  timeout $t python bench.py --full "$@" > $F/bench_$name.line 2> $F/bench_$name.err
   if [ -s $F/bench_$name.line ] && tail -1 $F/bench_$name.line | python -c 'import json,sys; json.loads(sys.stdin.read())' 2>/dev/null \
      && [ -s bench_detail.json ]; then
     tail -1 $F/bench_$name.line > profiles/${R}_bench_${name}_line.json

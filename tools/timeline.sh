@@ -9,6 +9,6 @@ OUT=$ROOT/gpurun_out/timeline_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace -d "$OUT/trace" -- python "$ROOT/bench.py" --steps 12 --warmup 3 --no-cpu-baseline --resident-only --no-extra-configs --no-pipeline "$@" > "$OUT/bench.json" 2> "$OUT/trace.log"
+rocprofv3 --kernel-trace -d "$OUT/trace" -- python "$ROOT/bench.py" --full --steps 12 --warmup 3 --no-cpu-baseline --resident-only --no-extra-configs --no-pipeline "$@" > "$OUT/bench.json" 2> "$OUT/trace.log"
 cd "$ROOT"
 python tools/rocprof_summary.py timeline "$(find "$OUT/trace" -name "*.db" | head -1)" "$N" | tee "$OUT/timeline.txt"
