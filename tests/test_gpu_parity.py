@@ -121,14 +121,11 @@ def test_dispatch_device_caller_owned_outputs(ctx, shape):
         assert (want == O.IDX_TIMEOUT).sum() > 1000
 
 
-@pytest.mark.parametrize("host_in", ["map", "copy"])
-def test_dispatch_zero_copy_pinned_buffers(host_in, monkeypatch):
+def test_dispatch_zero_copy_pinned_buffers():
     """ydc_dispatch with page-locked caller buffers (ydc_host_alloc / ydc_host_register): the
     kernels read the request columns and write idx / utilisation / running_tasks through the
-    buffers' device addresses (YDC_HOST_IN=map), or DMA straight from them (copy) — no staging.
-    Same answers as with pageable buffers and as the oracle; mixed pinned / pageable arguments
-    take the staged path."""
-    monkeypatch.setenv("YDC_HOST_IN", host_in)
+    buffers' device addresses — no staging. Same answers as with pageable buffers and as the
+    oracle; mixed pinned / pageable arguments take the staged path."""
     c = binding.Context(device=0)
     sv, tk = cases.random_case(seed=93, n_tasks=70_001, n_servants=1500, n_envs=4, self_frac=0.2,
                                unknown_env_frac=0.002)
@@ -406,7 +403,7 @@ def test_many_classes_paths(ctx):
     assert st["n_classes"] > 256
 
 
-@pytest.mark.parametrize("wide", [1, 5, 4, 2, 3, 0])
+@pytest.mark.parametrize("wide", [1, 5, 4, 3, 0])
 def test_more_than_256_classes(wide, monkeypatch):
     """Pools whose machines advertise individual compiler sets (the reference has no limit on
     (environment set, version) combinations, task_dispatcher.h:93-94, .cc:316-344): 150 digests,
@@ -414,16 +411,14 @@ def test_more_than_256_classes(wide, monkeypatch):
     (k_sim_wide), a request's classes read from its (digest, version threshold) row — registries
     with such rows are walked 64 requests at a time from the first request on (k_walk_groups: head
     rank and class id in one word; wide=5: in two arrays, as registries with more slots need them);
-    wide=4: rounds of speculation and then the lone walker instead; wide=2: the walk with prefetch waves; wide=3: mask
-    scan instead of the rows; wide=0: the thread-per-chunk kernel. Plain, with traffic from the servants'
+    wide=4: rounds of speculation and then the lone walker instead; wide=3: mask scan instead of
+    the rows; wide=0: the thread-per-chunk kernel. Plain, with traffic from the servants'
     own hosts on shared hosts (holes, `self` resolved at replay time), and oversubscribed."""
     monkeypatch.setenv("YDC_WIDE", "1" if wide else "0")
-    if wide in (2, 4):
+    if wide == 4:
         monkeypatch.setenv("YDC_GROUP_WALK", "0")  # rounds, then one request at a time
     if wide == 5:
         monkeypatch.setenv("YDC_WALK_PACKED", "0")
-    if wide == 2:
-        monkeypatch.setenv("YDC_WALK_PREFETCH", "1")  # the walk with prefetch waves
     if wide == 3:
         monkeypatch.setenv("YDC_WIDE_LISTS", "0")  # mask scan instead of eligible-class lists
     c = binding.Context(device=0)

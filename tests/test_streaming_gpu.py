@@ -50,12 +50,12 @@ def test_stream_cfg5_shape():
     assert es.tick_no == 12 and len(es.live) > 0
 
 
-@pytest.mark.parametrize("zero_copy", ["1", "0"])
-def test_stream_multi_env_varying_counts(zero_copy, monkeypatch):
-    """zero_copy = 1: the captured step reads the tick's page-locked arena in place and k_finalize
-    stores placement and outcome to page-locked memory (no copy node); 0: three copy nodes."""
-    monkeypatch.setenv("YDC_STREAM_ZERO_COPY", zero_copy)
-    monkeypatch.setenv("YDC_OUTCOME_STORE", zero_copy)
+@pytest.mark.parametrize("outcome_store", ["1", "0"])
+def test_stream_multi_env_varying_counts(outcome_store, monkeypatch):
+    """The captured step reads the tick's page-locked arena in place and k_finalize stores the
+    placement to page-locked memory (no copy node); outcome_store = 1: the outcome block too,
+    0: the outcome block is copied."""
+    monkeypatch.setenv("YDC_OUTCOME_STORE", outcome_store)
     run_stream(600, 3000, 2500, ticks=15, n_envs=3, varying=True)
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """When the workgroups of k_slot_gen (radix path: slot tiles and request classification in one
 launch) start and finish, from the stamps of the measurement build (`make probe`).
-usage: python tools/gen_probe.py [cfg3|cfg4] [reps]   (YDC_SPLIT_GEN=1: the two halves apart)"""
+usage: python tools/gen_probe.py [cfg3|cfg4] [reps]"""
 import ctypes as C
 import os
 import sys
@@ -39,7 +39,6 @@ def main():
         n = -(-grid // stride)
         blk = np.arange(n) * stride
         rows.append((st[:n], blk < gen_blocks))
-    # (with YDC_SPLIT_GEN=1 the last launch stamped is the classification: gen_blocks == 0)
     print("%s: k_slot_gen grid %d = %d slot tiles + %d request blocks, every %d-th workgroup stamped; "
           "us after the first stamped start" % (cfg, grid, gen_blocks, grid - gen_blocks, stride))
     for name, want in (("slot tiles", True), ("request blocks", False)):

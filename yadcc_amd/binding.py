@@ -176,11 +176,11 @@ def _ptr(a):
 # into YDC_TUNE right before a context is created (and takes out again what it folded in last
 # time, so that a switch a test has dropped is gone). Not an interface of the package.
 _TUNE_KEYS = ("DEBUG_SIM", "CHUNK_SIZE", "TARGET_CHUNKS", "FUSED_CLASS", "OWN_GUESS", "PAIR", "RING_TOTAL",
-              "DENSE", "SPLIT_GEN", "XCD_TILES", "TILE_TAB", "GROUP_WALK", "WALK_PACKED", "ZONE_GUESS", "ZONE_LEAD", "ZONE_TRAIL", "ZONE_MAX_CHUNKS", "SCAN_MULTI", "CLASSIFY_PER_THREAD",
-              "PACKED_CLASS", "SHARD_SORT", "PACKED_SORT", "BINSORT", "FUSE_PASSES", "WARM_UP",
-              "HAND_TRIES", "CP_EVERY", "WALK_PARK", "LEVEL_TAB", "WIDE", "WALK_PREFETCH", "WIDE_LISTS", "GROUP_BINSORT",
-              "ZERO_COPY", "HOST_IN", "BINSORT_VERIFY", "BINSORT_MAX_SLOTS", "SHARD_MARGIN",
-              "ROUNDS_PER_CHECK", "WALK_AFTER", "OUTCOME_STORE", "STREAM_ZERO_COPY", "STREAM_GRAPH", "COMMIT_SWAP", "RELEASE_COUNTED", "SMALL_BATCH", "RESIDENT", "RESIDENT_IDLE_MS", "PACKED_TICK", "SORT_ITEMS", "IPC_SLOT_WORDS", "IPC_TIMEOUT_MS", "IPC_COARSE")
+              "GROUP_WALK", "WALK_PACKED", "ZONE_GUESS", "ZONE_LEAD", "ZONE_TRAIL", "ZONE_MAX_CHUNKS",
+              "PACKED_CLASS", "SHARD_SORT", "BINSORT", "FUSE_PASSES", "WARM_UP",
+              "HAND_TRIES", "CP_EVERY", "WALK_PARK", "WIDE", "WIDE_LISTS", "GROUP_BINSORT",
+              "BINSORT_VERIFY", "BINSORT_MAX_SLOTS", "SHARD_MARGIN",
+              "ROUNDS_PER_CHECK", "WALK_AFTER", "OUTCOME_STORE", "STREAM_GRAPH", "COMMIT_SWAP", "RELEASE_COUNTED", "SMALL_BATCH", "RESIDENT", "RESIDENT_IDLE_MS", "PACKED_TICK", "IPC_SLOT_WORDS", "IPC_TIMEOUT_MS", "IPC_COARSE")
 _tune_injected = ""
 
 

@@ -22,33 +22,14 @@ namespace ydc {
 
 constexpr uint32_t kMaxWideClasses = 3072;  // 36 B of class state + 8 B of staged mask words per class
 constexpr uint32_t kWideFields = 9;
-// The walk with prefetch waves keeps nine more words per class (a four-entry ring of upcoming list
-// entries + how far it is filled): 72 B + 8 B of mask words per class.
-constexpr uint32_t kMaxWalkPrefetchClasses = 1920;
-constexpr uint32_t kWalkRing = 4;
 constexpr size_t kGroupWalkMaxLds = 160 * 1024 - 512;  // k_walk_groups: one workgroup, a CU's LDS
-// Dynamic LDS of k_sim_wide for C classes: the nine state arrays + the class masks of a block of
-// 64 requests (64 x ceil(C / 64) 64-bit words).
-// Seven state arrays of C words, the two the scan reads (head rank, head slot) padded to a
-// multiple of 512 classes so that the scan needs no bounds tests; the class masks of a block of 64
-// requests (rows of W8 = ceil(W / 8) * 8 words) and the "has holes" / "one servant" bit rows.
-__host__ __device__ inline size_t wide_lds_bytes(uint32_t C, bool walk_prefetch = false) {
+// Dynamic LDS of k_sim_wide for C classes: seven state arrays of C words, the two the scan reads
+// (head rank, head slot) padded to a multiple of 512 classes so that the scan needs no bounds
+// tests; the class masks of a block of 64 requests (rows of W8 = ceil(W / 8) * 8 words) and the
+// "has holes" / "one servant" bit rows.
+__host__ __device__ inline size_t wide_lds_bytes(uint32_t C) {
   const size_t W = (C + 63) / 64, W8 = (W + 7) & ~(size_t)7;
-  return (size_t)(kWideFields - 2 + (walk_prefetch ? 1 + 2 * kWalkRing : 0)) * C * 4 + 2 * W8 * 64 * 4 + 16 +
-         (64 * W8 + 2 * W) * 8;
-}
-
-// LDS accesses of the walker / prefetcher protocol, as DS instructions on the LDS offset: a
-// `volatile` generic pointer makes the compiler emit FLAT loads, which count in vmcnt — every
-// protocol read then waits for the wave's outstanding global stores (measured: no faster than
-// fetching from memory). The "memory" clobber keeps the compiler from moving accesses across.
-__device__ __forceinline__ uint32_t lds_load_u32(const uint32_t* p) {
-  uint32_t v;
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"((uint32_t)(uintptr_t)p) : "memory");
-  return v;
-}
-__device__ __forceinline__ void lds_store_u32(uint32_t* p, uint32_t v) {
-  asm volatile("ds_write_b32 %0, %1" : : "v"((uint32_t)(uintptr_t)p), "v"(v) : "memory");
+  return (size_t)(kWideFields - 2) * C * 4 + 2 * W8 * 64 * 4 + 16 + (64 * W8 + 2 * W) * 8;
 }
 
 // Eligible-class lists (host_tables.h: elig_off / elig_cls, every row at most 64 classes) and the
@@ -202,12 +183,6 @@ __device__ __forceinline__ void wide_general_step(const ClassLists& L, const Wid
 // changed (everything before it is final: its guess IS its predecessor's final end state) and
 // walks from there to the end of the batch with the state in LDS, leaving guesses and end
 // states consistent behind it; the next k_update finds nothing to change.
-// walk == 2 (256 threads): waves 1-3 are PREFETCHERS. A lone walker that fetches the list entry
-// after next itself waits out a cold memory access per pick — a wave's vmcnt is wave-wide and in
-// order —, 3.5 us per request. Here the walker never touches memory for the lists: every class
-// has a four-entry ring of upcoming entries in LDS, which the prefetch waves keep filled behind
-// its cursor (single-writer counters: the walker owns `cur`, the prefetchers own `fill`; a slot
-// is position & 3, free once the walker has passed it; entries are written before `fill` moves).
 __global__ __launch_bounds__(256) void k_sim_wide(ClassLists L, TaskTable T, uint32_t n_tasks,
                                                  uint32_t chunk_size, uint32_t n_chunks,
                                                  ClassState* __restrict__ guess,
@@ -218,66 +193,19 @@ __global__ __launch_bounds__(256) void k_sim_wide(ClassLists L, TaskTable T, uin
   extern __shared__ uint32_t wsm[];
   if (blockIdx.x == 0 && threadIdx.x == 0) prm->n_changed[round & 63] = 0;
   uint32_t k = blockIdx.x;
-  const uint32_t lane = threadIdx.x & 63u, wave_id = threadIdx.x >> 6, C = L.n_classes, W = T.words;
-  const bool prefetched = walk == 2;
-  // walk == 2 only: [fill | ring_p[4] | ring_g[4]] behind the state arrays and the block's masks
-  // LDS: nine state arrays | "walk done" word | the block's class masks (8-byte aligned) | walk only:
+  const uint32_t lane = threadIdx.x & 63u, C = L.n_classes, W = T.words;
+  // LDS: nine state arrays | the block's class masks (8-byte aligned). mask_at leaves a spare word
+  // behind the state arrays: the layout k_walk_groups shares and wide_lds_bytes sizes.
   const uint32_t W8 = (W + 7u) & ~7u, Cpad = W8 * 64;
   const uint32_t state_words = (kWideFields - 2) * C + 2 * Cpad;
   const uint32_t mask_at = (state_words + 3u) & ~1u;
-  uint32_t* const wdone = wsm + (size_t)state_words;
-  uint32_t* const wfill = wsm + mask_at + (size_t)(64 * W8 + 2 * W) * 2;
-  uint32_t* const wring_p = wfill + C;
-  uint32_t* const wring_g = wring_p + (size_t)kWalkRing * C;
-  const uint32_t* const vcur = wsm;  // == S.cur
-  if (prefetched && wave_id != 0) {
-    // ---- prefetch waves: class c belongs to wave 1 + (c / 64) % 3, lane c % 64
-    __syncthreads();  // (the walker has set the state up)
-    const uint32_t* endv = wsm + 4 * C;  // == S.end
-    while (lds_load_u32(wdone) == 0) {
-      for (uint32_t c = (wave_id - 1) * 64 + lane; c < C; c += 192) {
-        const uint32_t cur = lds_load_u32(vcur + c), e = endv[c];
-        uint32_t pos = lds_load_u32(wfill + c);
-        pos = pos > cur + 2 ? pos : cur + 2;
-        const uint32_t lim = cur + 2 + kWalkRing < e ? cur + 2 + kWalkRing : e;
-        if (pos < lim) {
-          uint32_t tp[kWalkRing], tg[kWalkRing];
-#pragma unroll
-          for (uint32_t u = 0; u < kWalkRing; ++u) {
-            tp[u] = tg[u] = kNone;
-            if (pos + u < lim) {
-              tp[u] = list_rank(L, pos + u);
-              tg[u] = list_slot(L, pos + u);
-            }
-          }
-#pragma unroll
-          for (uint32_t u = 0; u < kWalkRing; ++u) {
-            if (pos + u < lim) {
-              lds_store_u32(wring_p + (size_t)((pos + u) & (kWalkRing - 1)) * C + c, tp[u]);
-              lds_store_u32(wring_g + (size_t)((pos + u) & (kWalkRing - 1)) * C + c, tg[u]);
-            }
-          }
-          // (DS operations of a wave execute in order: the entries are in before `fill` moves)
-          lds_store_u32(wfill + c, lim);
-        }
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    return;
-  }
   if (walk) {
     k = n_chunks;
     for (uint32_t base = 0; base < n_chunks && k == n_chunks; base += 64) {
       const uint64_t m = __ballot(base + lane < n_chunks && dirty[base + lane] != 0);
       if (m) k = base + (uint32_t)__builtin_ctzll(m);
     }
-    if (k >= n_chunks) {  // nothing left to walk (the prefetch waves are told, then let go)
-      if (prefetched) {
-        if (lane == 0) lds_store_u32(wdone, 1u);
-        __syncthreads();
-      }
-      return;
-    }
+    if (k >= n_chunks) return;  // nothing left to walk
   } else if (k >= n_chunks || !dirty[k]) {
     return;
   }
@@ -331,24 +259,6 @@ __global__ __launch_bounds__(256) void k_sim_wide(ClassLists L, TaskTable T, uin
   }
   (void)my_holes;
   __builtin_amdgcn_wave_barrier();
-  if (prefetched) {
-    for (uint32_t c = lane; c < C; c += 64) lds_store_u32(wfill + c, 0u);
-    if (lane == 0) lds_store_u32(wdone, 0u);
-    __syncthreads();  // the prefetch waves start
-  }
-  // The walker's "entry after next" of class c from the ring (waits for the prefetchers if the
-  // class was picked faster than they refill, which takes several picks within one of their sweeps).
-  auto ring_take = [&](uint32_t c, uint32_t pos, uint32_t& p, uint32_t& g) {
-    uint32_t spins = 0;
-    while (lds_load_u32(wfill + c) <= pos && ++spins < (1u << 20)) __builtin_amdgcn_s_sleep(1);
-    if (lds_load_u32(wfill + c) > pos) {
-      p = lds_load_u32(wring_p + (size_t)(pos & (kWalkRing - 1)) * C + c);
-      g = lds_load_u32(wring_g + (size_t)(pos & (kWalkRing - 1)) * C + c);
-    } else {  // (never expected: a prefetch wave that does not deliver; the walker fetches itself)
-      p = list_rank(L, pos);
-      g = list_slot(L, pos);
-    }
-  };
   // One fetch of "the entry after next" in flight per lane.
   uint32_t pend_c = 0, pend_p = kNone, pend_g = kNone;
   bool pend_on = false;
@@ -447,16 +357,13 @@ __global__ __launch_bounds__(256) void k_sim_wide(ClassLists L, TaskTable T, uin
             slot_of[t] = S.hg[c];
             flush();
             const uint32_t cur = S.cur[c] + 1;
-            uint32_t p2 = kNone, g2 = kNone;
-            const bool more_entries = cur + 1 < S.end[c];
-            if (prefetched && more_entries) ring_take(c, cur + 1, p2, g2);
             S.cur[c] = cur;
             S.lo[c] = cur;  // (none of the request's classes has holes on this path)
             S.hp[c] = S.np[c];
             S.hg[c] = S.ng[c];
-            if (!more_entries || prefetched) {
-              S.np[c] = p2;
-              S.ng[c] = g2;
+            if (cur + 1 >= S.end[c]) {
+              S.np[c] = kNone;
+              S.ng[c] = kNone;
             } else {
               pend_c = c;
               pend_p = list_rank(L, cur + 1);
@@ -524,18 +431,13 @@ __global__ __launch_bounds__(256) void k_sim_wide(ClassLists L, TaskTable T, uin
             slot_of[t] = S.hg[c];
             flush();
             const uint32_t cur = S.cur[c] + 1;
-            // (the prefetch waves fill positions [cursor + 2, cursor + 6): the entry after next is
-            // taken while the cursor still names the old head, or they would step over it)
-            uint32_t p2 = kNone, g2 = kNone;
-            const bool more_entries = cur + 1 < S.end[c];
-            if (prefetched && more_entries) ring_take(c, cur + 1, p2, g2);
             S.cur[c] = cur;
             S.lo[c] = cur;  // (no holes anywhere on this path)
             S.hp[c] = S.np[c];
             S.hg[c] = S.ng[c];
-            if (!more_entries || prefetched) {
-              S.np[c] = p2;
-              S.ng[c] = g2;
+            if (cur + 1 >= S.end[c]) {
+              S.np[c] = kNone;
+              S.ng[c] = kNone;
             } else {
               pend_c = c;
               pend_p = list_rank(L, cur + 1);
@@ -596,7 +498,6 @@ __global__ __launch_bounds__(256) void k_sim_wide(ClassLists L, TaskTable T, uin
     ydc_phase_probe[7] = wall_clock64() - pr_total0;
   }
 #endif
-  if (prefetched && lane == 0) lds_store_u32(wdone, 1u);
 }
 
 

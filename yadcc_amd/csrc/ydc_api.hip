@@ -219,8 +219,8 @@ struct ydc_context {
     bool active = false, stale = true;
     uint32_t max_upd = 0, max_rel = 0, max_tasks = 0, passes = 0;
     // One pinned staging arena for everything a tick brings (heartbeat indexes and rows,
-    // released slots, the three request columns) and its device mirror: one H2D copy per
-    // tick. The typed pointers below point into the two arenas.
+    // released slots, the three request columns) and its device mirror, which the ticks that
+    // run eagerly copy it to. The typed pointers below point into the two arenas.
     uint8_t* h_in = nullptr;
     DevBuf<uint8_t> d_in;
     size_t in_bytes = 0;
@@ -235,7 +235,6 @@ struct ydc_context {
     uint32_t *z_upd_idx = nullptr, *z_rel = nullptr, *z_env = nullptr, *z_minv = nullptr, *z_ip = nullptr,
              *z_out = nullptr;
     ServantRowDev* z_upd_rows = nullptr;
-    bool zero_copy = false;  // the captured step in use reads / writes the arenas in place
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     BatchPlan plan;
@@ -265,7 +264,6 @@ struct ydc_context {
   DeviceParams* finalize_outcome = nullptr;
   bool opt_outcome_store = true;  // (outcome_store=0: always the copy)
   bool opt_release_counted = true;  // long release lists counted in LDS first (release_counted=0: an atomic per slot)
-  bool opt_stream_zero_copy = true;  // streaming: the captured step reads / writes the page-locked arenas in place
 
   // Staging for the host-pointer entry point (ydc_dispatch): the three request columns in
   // one pinned arena and its device mirror (one H2D copy), the results (indexes |
@@ -287,7 +285,6 @@ struct ydc_context {
   // the H2D copy travels on a stream of its own (stage_host_requests).
   struct {
     bool active = false;
-    bool direct = false;  // the caller's columns are page-locked: DMA straight from them
     const ydc_task_soa* tk = nullptr;
     uint32_t n = 0;
     size_t col = 0, bytes = 0;
@@ -335,8 +332,6 @@ struct ydc_context {
   // 16 KB of LDS per matching wave = 10 waves per CU. Smaller rings (more waves per CU, shorter
   // chunks) were measured and bring nothing: the waves saturate VALU issue at ~2 per SIMD.
   uint32_t opt_ring_total = 0;  // entries of a matching wave's rings; 0: chosen per batch (YDC_RING_TOTAL)
-  uint32_t opt_xcd = 3;  // XCD-contiguous tile order: 1 slot generation, 2 histograms, 4 scatters (YDC_XCD_TILES)
-  bool opt_scan_multi = true;  // (scan_multi=0: one workgroup loops over the slabs)
   bool opt_group_walk = true;  // sparse eligibility: the walk in groups of 64 requests (YDC_GROUP_WALK=0: one at a time)
   uint32_t opt_zone_guess = 1;  // start guesses around the dedicated tier's end from a walk of that stretch: 1 where it pays, 2 always, 0 never
   // lead: where the walk starts, in levels before the tier's end (the first chunk boundary inside
@@ -360,16 +355,11 @@ struct ydc_context {
   uint32_t zone_since_probe = 0;
   uint64_t zone_shape = 0;       // the plans the figures above are about
   bool opt_walk_packed = true; // ... with head rank and class id in one word where they fit (walk_packed=0: two arrays)
-  bool opt_tile_tab = true;  // level searches narrowed by the class pass's histogram table (YDC_TILE_TAB=0)
-  bool opt_classify_multi = true;  // (YDC_CLASSIFY_PER_THREAD=1: one request per thread everywhere)
-  bool opt_split_gen = false;  // slot generation and request classification as two launches (YDC_SPLIT_GEN=1)
-  bool opt_dense = true;  // 4-waves-per-SIMD matching kernel and twice the chunks where it pays (YDC_DENSE=0)
   bool opt_fused_class = true;
   bool opt_own_guess = true;
   bool opt_pair = true;
   bool opt_packed_class = true;
   bool opt_shard_sort = true;
-  bool opt_packed_sort = true;  // 8-byte (key, value) sort records for 32-bit keys
   // Bin sort (three launches, bin_sort.h) for registries that offer at most this many slots;
   // a batch with a bin too large for LDS is repeated with the radix sort, which then stays
   // (binsort_blocked) until the registry changes structure.
@@ -381,16 +371,8 @@ struct ydc_context {
   bool opt_stream_graph = true;  // the streaming step is replayed from its hipGraph (0: enqueued eagerly)
   bool opt_walk_park = true;  // k_walk_groups parks its fetches in a254 / a255 (0: in plain variables)
   bool opt_group_binsort = true;  // multi-GPU: bin sort of the whole registry before windowed radix (YDC_GROUP_BINSORT=0)
-  // The walk of the wide kernel with prefetch waves (YDC_WALK_PREFETCH=1). Off: measured slower
-  // than the walker's own one-ahead fetch (57 against 35 ms of 100k picks; the scan was the cost).
-  bool opt_walk_prefetch = false;
   bool opt_wide_lists = true;  // eligible-class lists for the wide kernel where every row is short (YDC_WIDE_LISTS=0: masks)
   bool opt_wide = true;  // > 256 classes: wave-per-chunk replay (YDC_WIDE=0: thread per chunk)
-  bool opt_level_tab = true;  // bin sort leaves a level table for pass 0's guesses (YDC_LEVEL_TAB=0: search)
-  // ydc_dispatch with page-locked caller buffers: no staging (YDC_ZERO_COPY=0 switches it off);
-  // request columns read in place through the mapped pointer (YDC_HOST_IN=map) or copied by DMA
-  // from where they lie (YDC_HOST_IN=copy).
-  bool opt_zero_copy = true, opt_host_in_map = true;
   uint32_t opt_binsort_max_slots = 600000;
   bool binsort_blocked = false;
   bool debug_verify_binsort = false;  // YDC_BINSORT_VERIFY=1: check every bin sort against a host sort
@@ -487,7 +469,7 @@ void* pinned_device_pointer(const void* p, size_t bytes) {
 // Developer / test switchboard: ONE environment variable, YDC_TUNE="key=value,key=value", read
 // when a context is created. It forces code paths the planner would not choose on its own (the
 // parity tests cover the fallbacks with it: chunk and ring sizes, the radix pipeline on a
-// registry the bin sort would take, the lone walker, ...) and splits launches for measurements.
+// registry the bin sort would take, the lone walker, ...).
 // Not an interface: a scheduler never sets it, and nothing in it changes a placement.
 const char* tune_value(const char* key) {
   static thread_local std::string value;
@@ -662,8 +644,8 @@ int launch_sort_pass(ydc_context* c, const SortIn<KeyT>& in_, uint32_t n_tiles, 
                      bool out_u32, uint32_t* out_vals, const PrefixArgs* pa = nullptr,
                      bool have_hist = false) {
   SortIn<KeyT> in = in_;
-  in.xcd_hist = (c->opt_xcd >> 1) & 1;
-  in.xcd_scatter = (c->opt_xcd >> 2) & 1;
+  in.xcd_hist = 1;
+  in.xcd_scatter = 0;  // (XCD-contiguous order there too was measured and rejected)
   in.dbg = 0;
   const uint32_t radix = 1u << in.bits;
   if (!have_hist)  // (the first pass's tile histograms come out of k_slot_gen)
@@ -790,21 +772,14 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
   if (const char* s = tune_value("own_guess")) c->opt_own_guess = atoi(s) != 0;
   if (const char* s = tune_value("pair")) c->opt_pair = atoi(s) != 0;
   if (const char* s = tune_value("ring_total")) c->opt_ring_total = std::max(256u, (uint32_t)atoi(s));
-  if (const char* s = tune_value("dense")) c->opt_dense = atoi(s) != 0;
-  if (const char* s = tune_value("split_gen")) c->opt_split_gen = atoi(s) != 0;
-  if (const char* s = tune_value("xcd_tiles")) c->opt_xcd = (uint32_t)atoi(s);
-  if (const char* s = tune_value("tile_tab")) c->opt_tile_tab = atoi(s) != 0;
   if (const char* s = tune_value("group_walk")) c->opt_group_walk = atoi(s) != 0;
   if (const char* s = tune_value("walk_packed")) c->opt_walk_packed = atoi(s) != 0;
   if (const char* s = tune_value("zone_guess")) c->opt_zone_guess = (uint32_t)std::max(0, atoi(s));
   if (const char* s = tune_value("zone_lead")) c->opt_zone_lead = (uint32_t)atoi(s);
   if (const char* s = tune_value("zone_trail")) c->opt_zone_trail = (uint32_t)atoi(s);
   if (const char* s = tune_value("zone_max_chunks")) c->opt_zone_max_chunks = (uint32_t)atoi(s);
-  if (const char* s = tune_value("scan_multi")) c->opt_scan_multi = atoi(s) != 0;
-  if (const char* s = tune_value("classify_per_thread")) c->opt_classify_multi = atoi(s) != 1;
   if (const char* s = tune_value("packed_class")) c->opt_packed_class = atoi(s) != 0;
   if (const char* s = tune_value("shard_sort")) c->opt_shard_sort = atoi(s) != 0;
-  if (const char* s = tune_value("packed_sort")) c->opt_packed_sort = atoi(s) != 0;
   if (const char* s = tune_value("binsort")) c->opt_binsort = atoi(s) != 0;
   if (const char* s = tune_value("stream_graph")) c->opt_stream_graph = atoi(s) != 0;
   if (const char* s = tune_value("walk_park")) c->opt_walk_park = atoi(s) != 0;
@@ -816,13 +791,9 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
     while (p2 * 2 <= v && p2 < 1024) p2 *= 2;
     c->opt_cp_every = p2;
   }
-  if (const char* s = tune_value("level_tab")) c->opt_level_tab = atoi(s) != 0;
   if (const char* s = tune_value("wide")) c->opt_wide = atoi(s) != 0;
-  if (const char* s = tune_value("walk_prefetch")) c->opt_walk_prefetch = atoi(s) != 0;
   if (const char* s = tune_value("wide_lists")) c->opt_wide_lists = atoi(s) != 0;
   if (const char* s = tune_value("group_binsort")) c->opt_group_binsort = atoi(s) != 0;
-  if (const char* s = tune_value("zero_copy")) c->opt_zero_copy = atoi(s) != 0;
-  if (const char* s = tune_value("host_in")) c->opt_host_in_map = std::string(s) != "copy";
   if (const char* s = tune_value("binsort_verify")) c->debug_verify_binsort = atoi(s) != 0;
   if (const char* s = tune_value("binsort_max_slots")) c->opt_binsort_max_slots = (uint32_t)atoll(s);
   if (const char* s = tune_value("shard_margin")) c->opt_shard_margin = atoll(s);
@@ -832,7 +803,6 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
   if (const char* s = tune_value("resident_idle_ms")) c->opt_resident_idle_ms = (uint32_t)std::max(1, atoi(s));
   if (const char* s = tune_value("commit_swap")) c->opt_commit_swap = atoi(s) != 0;
   if (const char* s = tune_value("outcome_store")) c->opt_outcome_store = atoi(s) != 0;
-  if (const char* s = tune_value("stream_zero_copy")) c->opt_stream_zero_copy = atoi(s) != 0;
   if (const char* s = tune_value("release_counted")) c->opt_release_counted = atoi(s) != 0;
   if (const char* s = tune_value("walk_after")) c->opt_walk_after = (uint32_t)std::max(2, atoi(s));
   if (const char* s = tune_value("rounds_per_check"))
@@ -1215,7 +1185,6 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
   // Sort tiles: 256 threads x `items` elements; fewer elements per thread while that still
   // leaves the chip short of workgroups (the passes are latency-bound at this size).
   p.sort_items = p.slot_bound <= 300000 ? 2 : (p.slot_bound <= 700000 ? 4 : 8);
-  if (const char* e = tune_value("sort_items")) p.sort_items = std::min(8, std::max(1, atoi(e)));
   p.n_tiles = std::max<uint32_t>(1, ceil_div(p.slot_bound, kSortThreads * p.sort_items));
   p.any_shared = c->tables.any_shared_ip;
   p.use_generic = p.C > kMaxWaveClasses;
@@ -1229,7 +1198,7 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
     // SIMD instead of two (cfg4, 4M requests: k_match_pass 373 -> 294 us). Shorter chunks cost
     // more in wrong guesses and replays than the occupancy brings (cfg3 at 256 instead of 512
     // requests per chunk: 395 -> 465 us).
-    if (c->opt_dense && p.W == 1 && p.cs >= 2048) p.cs >>= 1;
+    if (p.W == 1 && p.cs >= 2048) p.cs >>= 1;
   }
   // The many-class kernels replay whole chunks per round (no checkpoints): chunks long enough
   // for a wrong start to heal inside them keep the rounds few (cfg2 with 10 digests, 947 classes:
@@ -1243,11 +1212,11 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
   // 32-bit keys: 8-byte (key, value) records in d_keys; 64-bit keys: keys there, values in d_vals.
   HIP_TRY(c, c->d_keys[0].reserve(slot_bound));
   HIP_TRY(c, c->d_keys[1].reserve(slot_bound));
-  if (!p.key32 || !c->opt_packed_sort) {
+  if (!p.key32) {
     HIP_TRY(c, c->d_vals[0].reserve(slot_bound));
     HIP_TRY(c, c->d_vals[1].reserve(slot_bound));
   }
-  p.packed = p.key32 && c->opt_packed_sort;
+  p.packed = p.key32;
   HIP_TRY(c, c->d_hist.reserve(((size_t)1 << kMaxRadixBits) * p.n_tiles));
   HIP_TRY(c, c->d_tile_first.reserve((size_t)p.n_tiles + 2));
   if (C > 1) HIP_TRY(c, c->d_cls_by_g.reserve(slot_bound));
@@ -1308,7 +1277,7 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
     HIP_TRY(c, c->d_binbase.reserve((size_t)(p.n_bins + 1) * (C + 1)));
     HIP_TRY(c, c->d_binruns.reserve((size_t)p.bin_tiles * p.n_bins));
     HIP_TRY(c, c->d_rank_to_g.reserve(slot_bound));
-    if (c->opt_level_tab) HIP_TRY(c, c->d_level_tab.reserve(((size_t)(slot_bound >> 6) + 2) * C));
+    HIP_TRY(c, c->d_level_tab.reserve(((size_t)(slot_bound >> 6) + 2) * C));
     // (consuming counts per wave of 64 requests instead of per chunk)
     HIP_TRY(c, c->d_chunk_consuming.reserve(((size_t)ceil_div(std::max(N, 1u), 64) + 1) * c->n_parts));
   }
@@ -1390,10 +1359,10 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
     p.mb.flags = c->d_prm.p->n_changed;
     p.mb.sampled = c->d_prm.p->n_sampled;
     p.mb.flag_mask = 63;
-    p.mb.level_tab = p.binsort && c->opt_level_tab && c->n_parts <= 1 ? c->d_level_tab.p : nullptr;
+    p.mb.level_tab = p.binsort && c->n_parts <= 1 ? c->d_level_tab.p : nullptr;
     // The class partition as a pass of its own leaves its scanned histogram table in d_hist:
     // digit == class, one column per sort tile (enqueue_sort; k_radix_scan).
-    if (!p.binsort && p.cls_passes == 1 && p.slot_bound && c->opt_tile_tab) {
+    if (!p.binsort && p.cls_passes == 1 && p.slot_bound) {
       p.mb.tile_tab = c->d_hist.p;
       p.mb.tile_tab_tiles = p.n_tiles;
       p.mb.tile_tab_elems = kSortThreads * p.sort_items;
@@ -1421,7 +1390,7 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
     // The 4-waves-per-SIMD build of the matching kernel for chunks long enough to amortise its
     // spills (cfg2's chunks of 64 requests: 22.7 -> 23.1 us with it; cfg3's of 512: 426 -> 395),
     // and rings small enough for all of a CU's waves to be resident (160 KB of LDS, 16 waves).
-    p.dense = c->opt_dense && p.W == 1 && p.cs >= 256;
+    p.dense = p.W == 1 && p.cs >= 256;
     if (p.dense && c->opt_ring_total == 0) {
       const uint32_t per_cu = std::min<uint32_t>(16, std::max<uint32_t>(1, ceil_div(p.K, 256)));
       p.ring_total = 2048;
@@ -1486,7 +1455,7 @@ void enqueue_scan(ydc_context* c, const BatchPlan& p, uint32_t* cls_begin) {
     return;
   }
   // (one workgroup per slab of 1024 servants from 4k servants on: kernels.h, servant_scan_multi)
-  const uint32_t scan_blocks = p.S > 4096 && c->opt_scan_multi ? ceil_div(p.S, 1024) : 1u;
+  const uint32_t scan_blocks = p.S > 4096 ? ceil_div(p.S, 1024) : 1u;
   YDC_LAUNCH(c, "k_servant_scan", k_servant_scan, dim3(scan_blocks), dim3(1024), (p.C + 1) * sizeof(uint32_t),
              c->stream, p.sv, p.C, p.slot_bound_glob, c->d_slot_base.p, cls_begin,
              c->d_chunk_consuming.p, p.K, PartTable{c->d_cls_comp.p, c->n_parts, c->d_part_base.p},
@@ -1515,7 +1484,7 @@ void enqueue_gen(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk, boo
   ca.n_ip = (uint32_t)c->tables.ip_sorted.size();
   ca.ip_hash = (const uint2*)c->d_ip_hash.p;
   ca.ip_hash_shift = c->tables.ip_hash_shift;
-  ca.xcd_gen = c->opt_xcd & 1;
+  ca.xcd_gen = 1;
   ca.ip_filter = c->d_ip_filter.p;
   ca.ip_filter_shift = c->tables.ip_filter_shift;
   ca.row_out = p.wide_lists && N && classify ? c->d_row_of.p : nullptr;
@@ -1526,9 +1495,9 @@ void enqueue_gen(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk, boo
   const uint32_t bits0 = std::min(bpp0, c->kf.key_bits) + fused0;
   const uint32_t gen_blocks = gen && p.slot_bound ? p.n_tiles : 0;
   // Large batches of the radix path: four requests per thread (kernels.h: task_classify_block_multi;
-  // the lookup form with one mask word). YDC_CLASSIFY_PER_THREAD=1 keeps one.
+  // the lookup form with one mask word).
   ca.per_thread = classify && !p.binsort && N >= (1u << 18) && !c->tables.env_ver_mask.empty() && W == 1 &&
-                          !ca.row_out && c->opt_classify_multi ? 4u : 1u;
+                          !ca.row_out ? 4u : 1u;
   const uint32_t cls_blocks = classify ? ceil_div(N, 256 * ca.per_thread) : 0;
   if (gen_blocks + cls_blocks == 0) return;
   const size_t lds0 = ((size_t)4 << bits0);
@@ -1588,7 +1557,7 @@ int enqueue_sort(ydc_context* c, const BatchPlan& p, bool prefix_pending) {
                             c->d_bin_tile_start.p, c->d_bin_tile_base.p},
                    p.C, p.gbits, p.bin_slot_bits, p.bin_cls_bits, c->d_slot_base.p, c->d_cls_begin.p,
                    (uint2*)c->d_keys[1].p, c->d_rank_to_g.p,
-                   c->opt_level_tab && c->n_parts <= 1 ? c->d_level_tab.p : nullptr};
+                   c->n_parts <= 1 ? c->d_level_tab.p : nullptr};
     YDC_LAUNCH(c, "k_bin_sort", k_bin_sort, dim3(p.n_bins + (pending_prefix ? 1 : 0)), dim3(kBinThreads),
                (size_t)kBinLdsWords * 4, c->stream, ba, c->d_prm.p, pending_prefix ? pa : PrefixArgs{});
     mark(c, 3);
@@ -1642,12 +1611,7 @@ int enqueue_sort(ydc_context* c, const BatchPlan& p, bool prefix_pending) {
 // Everything before the level guesses: slots, sort, class lists, request classification.
 int enqueue_front_a(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk) {
   enqueue_scan(c, p, c->d_cls_begin.p);
-  if (c->opt_split_gen) {  // (measurement: the two halves of the launch timed apart)
-    enqueue_gen(c, p, tk, true, false);
-    enqueue_gen(c, p, tk, false, true);
-  } else {
-    enqueue_gen(c, p, tk, true, true);
-  }
+  enqueue_gen(c, p, tk, true, true);
   return enqueue_sort(c, p, true);
 }
 
@@ -1681,17 +1645,10 @@ int enqueue_front_b(ydc_context* c, const BatchPlan& p, const uint32_t* d_base) 
 // for the copy (only the kernels behind this point read the columns).
 int stage_host_requests(ydc_context* c) {
   auto& h = c->host_in;
-  if (h.direct) {
-    const uint32_t* cols[3] = {h.tk->env_id, h.tk->min_version, h.tk->requestor_ip};
-    for (int k = 0; k < 3; ++k)
-      HIP_TRY(c, hipMemcpyAsync(c->d_in.p + k * h.col, cols[k], (size_t)h.n * 4, hipMemcpyHostToDevice,
-                                c->copy_stream));
-  } else {
-    std::memcpy(c->h_in, h.tk->env_id, (size_t)h.n * 4);
-    std::memcpy(c->h_in + h.col, h.tk->min_version, (size_t)h.n * 4);
-    std::memcpy(c->h_in + 2 * h.col, h.tk->requestor_ip, (size_t)h.n * 4);
-    HIP_TRY(c, hipMemcpyAsync(c->d_in.p, c->h_in, h.bytes, hipMemcpyHostToDevice, c->copy_stream));
-  }
+  std::memcpy(c->h_in, h.tk->env_id, (size_t)h.n * 4);
+  std::memcpy(c->h_in + h.col, h.tk->min_version, (size_t)h.n * 4);
+  std::memcpy(c->h_in + 2 * h.col, h.tk->requestor_ip, (size_t)h.n * 4);
+  HIP_TRY(c, hipMemcpyAsync(c->d_in.p, c->h_in, h.bytes, hipMemcpyHostToDevice, c->copy_stream));
   HIP_TRY(c, hipEventRecord(c->copy_ev, c->copy_stream));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_ev, 0));
   return YDC_OK;
@@ -2077,7 +2034,7 @@ int run_planned_batch(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk
       const bool wide = p.C <= kMaxWideClasses && c->opt_wide;
       if (wide)  // (above 64 KB of dynamic LDS the runtime wants to be told)
         HIP_TRY(c, hipFuncSetAttribute((const void*)k_sim_wide, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)std::max(wide_lds_bytes(kMaxWideClasses), wide_lds_bytes(kMaxWalkPrefetchClasses, true))));
+                                       (int)wide_lds_bytes(kMaxWideClasses)));
       // The walk in groups of 64 requests (k_walk_groups) where the registry has eligible-class
       // lists and they fit the LDS beside the class states (YDC_GROUP_WALK=0: the lone walker).
       const uint32_t n_rows = p.wide_lists ? (uint32_t)c->tables.elig_off.size() - 1 : 0;
@@ -2124,12 +2081,10 @@ int run_planned_batch(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk
           if (wide) {
             // One wave per chunk, the class states in LDS (wide_kernel.h) — or, once the rounds
             // have stopped making headway, one wave that walks the rest of the batch.
-            // (the walk: with prefetch waves while their rings fit the LDS, YDC_WALK_PREFETCH=0: alone)
-            const bool walk = walked, pf = walk && p.C <= kMaxWalkPrefetchClasses && c->opt_walk_prefetch;
+            const bool walk = walked;
             YDC_LAUNCH(c, walk ? "k_sim_wide(walk)" : "k_sim_wide", k_sim_wide, dim3(walk ? 1u : p.K),
-                       dim3(pf ? 256 : 64), wide_lds_bytes(p.C, pf), st, p.L, p.T, N, p.cs, p.K, gold,
-                       c->d_endst.p, c->d_dirty.p, c->d_slot_of.p, p.shared, rounds, prm,
-                       walk ? (pf ? 2u : 1u) : 0u,
+                       dim3(64), wide_lds_bytes(p.C), st, p.L, p.T, N, p.cs, p.K, gold,
+                       c->d_endst.p, c->d_dirty.p, c->d_slot_of.p, p.shared, rounds, prm, walk ? 1u : 0u,
                        p.wide_lists ? WideLists{c->d_row_of.p, c->d_elig_off.p, c->d_elig_cls.p}
                                     : WideLists{nullptr, nullptr, nullptr});
           } else {
@@ -2861,17 +2816,16 @@ int ydc_dispatch(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t fl
   // Page-locked caller buffers (ydc_host_register / ydc_host_alloc) are used as they are: the
   // classification reads the request columns and k_finalize writes the results through their
   // device addresses — no staging memcpy, no copy command on either side.
-  const bool zero_copy = c->opt_zero_copy;
   const uint32_t* m_in[3] = {nullptr, nullptr, nullptr};
-  if (zero_copy && N) {
+  if (N) {
     m_in[0] = (const uint32_t*)pinned_device_pointer(tk->env_id, (size_t)N * 4);
     m_in[1] = m_in[0] ? (const uint32_t*)pinned_device_pointer(tk->min_version, (size_t)N * 4) : nullptr;
     m_in[2] = m_in[1] ? (const uint32_t*)pinned_device_pointer(tk->requestor_ip, (size_t)N * 4) : nullptr;
   }
   const bool in_pinned = m_in[0] && m_in[1] && m_in[2];
-  uint32_t* m_idx = zero_copy && N ? (uint32_t*)pinned_device_pointer(out_idx, (size_t)N * 4) : nullptr;
-  uint32_t* m_run = zero_copy && out_running && S ? (uint32_t*)pinned_device_pointer(out_running, (size_t)S * 4) : nullptr;
-  double* m_util = zero_copy && out_util && N ? (double*)pinned_device_pointer(out_util, (size_t)N * 8) : nullptr;
+  uint32_t* m_idx = N ? (uint32_t*)pinned_device_pointer(out_idx, (size_t)N * 4) : nullptr;
+  uint32_t* m_run = out_running && S ? (uint32_t*)pinned_device_pointer(out_running, (size_t)S * 4) : nullptr;
+  double* m_util = out_util && N ? (double*)pinned_device_pointer(out_util, (size_t)N * 8) : nullptr;
   const bool out_pinned = (!N || m_idx) && (!(out_running && S) || m_run) && (!(out_util && N) || m_util);
   // in: env | min_version | requestor_ip        out: idx | running_tasks | utilisation
   const size_t col = pad((size_t)N * 4), in_bytes = 3 * col;
@@ -2887,23 +2841,20 @@ int ydc_dispatch(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t fl
     if (e == hipSuccess) *cap = want;
     return e;
   };
-  // Request columns: read in place (in_pinned, YDC_HOST_IN=map), copied by DMA straight from
-  // the caller's pinned columns (in_pinned, YDC_HOST_IN=copy), or staged through the context's
-  // own pinned arena (pageable caller memory).
-  const bool in_map = in_pinned && c->opt_host_in_map;
+  // Request columns: read in place (in_pinned), or staged through the context's own pinned arena
+  // (pageable caller memory).
   ydc_task_soa d{};
   c->host_in.active = false;
-  if (in_map) {
+  if (in_pinned) {
     d = ydc_task_soa{m_in[0], m_in[1], m_in[2]};
   } else if (N) {
-    if (!in_pinned) HIP_TRY(c, pinned(&c->h_in, &c->h_in_cap, in_bytes));
+    HIP_TRY(c, pinned(&c->h_in, &c->h_in_cap, in_bytes));
     HIP_TRY(c, c->d_in.reserve(std::max<size_t>(in_bytes, 256)));
     if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     if (!c->copy_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->copy_ev, hipEventDisableTiming));
     // The columns are staged and copied inside the batch, behind the launches that do not need
     // them (enqueue_front / stage_host_requests).
     c->host_in.active = true;
-    c->host_in.direct = in_pinned;
     c->host_in.tk = tk;
     c->host_in.n = N;
     c->host_in.col = col;
@@ -3860,34 +3811,29 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
     if (e != hipSuccess && rc == YDC_OK)
       rc = fail(c, YDC_ERR_HIP, "streaming step: %s", hipGetErrorString(e));
   };
-  const size_t T = sm.max_tasks;
-  // Round 5: no copy node. The tick's inputs are read where the host put them (k_apply_tick and
-  // the request classification read every word once), the placement is stored to the page-locked
-  // result array by k_finalize, and so is the outcome block (stream_zero_copy=0: three copies).
-  const bool zc = sm.zero_copy;
-  if (!zc) cap(hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, st));
+  // No copy node. The tick's inputs are read where the host put them (k_apply_tick and the request
+  // classification read every word once), the placement is stored to the page-locked result array
+  // by k_finalize, and so is the outcome block (outcome_store=0: copied).
   if (sm.max_upd + sm.max_rel) {
     const uint32_t upd_blocks = ceil_div(sm.max_upd, 256);
     hipLaunchKernelGGL(k_apply_tick, dim3(upd_blocks + ceil_div(sm.max_rel, 256)), dim3(256), 0, st,
-                       zc ? sm.z_upd_idx : sm.d_upd_idx, zc ? sm.z_upd_rows : sm.d_upd_rows, sm.max_upd, upd_blocks,
-                       zc ? sm.z_rel : sm.d_rel, sm.max_rel,
+                       sm.z_upd_idx, sm.z_upd_rows, sm.max_upd, upd_blocks, sm.z_rel, sm.max_rel,
                        c->n_servants, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p,
                        c->d_flags.p, c->d_running.p);
   }
-  ydc_task_soa d{zc ? sm.z_env : sm.d_env, zc ? sm.z_minv : sm.d_minv, zc ? sm.z_ip : sm.d_ip};
+  ydc_task_soa d{sm.z_env, sm.z_minv, sm.z_ip};
   if (rc == YDC_OK) rc = enqueue_front(c, plan, &d);
   if (rc == YDC_OK && plan.wave_path)
     for (uint32_t r = 0; r < sm.passes; ++r) enqueue_pass(c, plan, r, 1u);
-  const bool outcome_stored = zc && c->opt_outcome_store && plan.S != 0;
+  const bool outcome_stored = c->opt_outcome_store && plan.S != 0;
   if (rc == YDC_OK) {
     c->finalize_outcome = outcome_stored ? c->d_h_prm : nullptr;
     c->commit_by_swap = by_swap;
-    rc = enqueue_finalize(c, plan, YDC_DISPATCH_COMMIT, zc ? sm.z_out : c->d_out_idx.p, nullptr, nullptr,
+    rc = enqueue_finalize(c, plan, YDC_DISPATCH_COMMIT, sm.z_out, nullptr, nullptr,
                           plan.wave_path ? (sm.passes - 1) & 63 : kNone);
     c->commit_by_swap = false;
     c->finalize_outcome = nullptr;
   }
-  if (!zc) cap(hipMemcpyAsync(sm.h_out, c->d_out_idx.p, T * 4, hipMemcpyDeviceToHost, st));
   if (!outcome_stored) cap(hipMemcpyAsync(c->h_prm, c->d_prm.p, sizeof(DeviceParams), hipMemcpyDeviceToHost, st));
   return rc;
 }
@@ -3934,7 +3880,6 @@ int stream_capture(ydc_context* c) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   sm.passes = sm.want_passes ? sm.want_passes : std::max(2u, std::min(c->round_hint + 1, 12u));
   sm.window_max = sm.window_ticks = 0;
-  sm.zero_copy = c->opt_stream_zero_copy;
   sm.swaps = c->opt_commit_swap && sm.plan.S != 0;
   sm.run_a = c->d_running.p;
   int rc = stream_capture_one(c, sm.plan, sm.swaps, &sm.graph, &sm.exec);
@@ -4194,8 +4139,8 @@ int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_serv
     ++sm.eager_fallbacks;
     BatchPlan p2;
     if (int rc = fall_back_to_radix(c, sm.max_tasks, &p2)) return rc;
-    if (sm.zero_copy)  // (the captured step read the arena in place: the device copy is stale)
-      HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
+    // (the captured step read the arena in place: the device copy is stale)
+    HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
     ydc_task_soa d{sm.d_env, sm.d_minv, sm.d_ip};
     if (int rc = run_planned_batch(c, p2, &d, YDC_DISPATCH_COMMIT, c->d_out_idx.p, nullptr, nullptr, &rounds))
       return rc;
