@@ -27,6 +27,10 @@ extern "C" {
 /* ---- result sentinels (out_servant_idx) ---------------------------------- */
 #define YDC_IDX_TIMEOUT 0xFFFFFFFFu       /* WaitStatus::Timeout,             task_dispatcher.h:43 */
 #define YDC_IDX_ENV_NOT_FOUND 0xFFFFFFFEu /* WaitStatus::EnvironmentNotFound, task_dispatcher.h:42 */
+/* Streaming waiting mode only (ydc_stream_tick_waiting): no free servant yet, the request waits
+ * in the context's queue and is answered in a later tick's resolved list. No registry index
+ * ever has this value. */
+#define YDC_IDX_WAITING 0xFFFFFFFDu
 
 /* ---- error codes ---------------------------------------------------------- */
 #define YDC_OK 0
@@ -127,7 +131,8 @@ enum {
 
 const char* ydc_strerror(int code);
 const char* ydc_last_error(const ydc_context* ctx); /* ctx == NULL: last error outside a context */
-uint32_t ydc_abi_version(void);
+#define YDC_ABI_VERSION 7u
+uint32_t ydc_abi_version(void); /* YDC_ABI_VERSION */
 
 /* Number of usable devices (0 if the HIP runtime cannot see one). */
 int ydc_device_count(void);
@@ -283,7 +288,54 @@ typedef struct ydc_stream_buffers {
   uint32_t* out_servant_idx;
 } ydc_stream_buffers;
 int ydc_stream_buffers_get(ydc_context* ctx, ydc_stream_buffers* out);
+/* Discards the waiting queue of a context begun with ydc_stream_begin_waiting. */
 int ydc_stream_end(ydc_context* ctx);
+
+/* ---- streaming with a waiting queue --------------------------------------------
+ * The reference's grant call waits: WaitForStartingNewTask takes a deadline and, while no
+ * eligible servant has a free slot, sleeps on its condition variable and tries again on every
+ * wake-up, answering Timeout only once the deadline has passed (task_dispatcher.cc:93-118; the
+ * RPC handler passes max_wait of up to 10 s, scheduler_service_impl.cc:221-240). In waiting mode
+ * a streaming tick keeps such a request in a queue W on the device, in arrival order, and tries
+ * it again at the start of every later tick, ahead of that tick's new requests, until it is
+ * granted, gets EnvironmentNotFound or its deadline passes. max_waiting (> 0) bounds |W| plus a
+ * tick's new requests. Deadlines and the tick's `now` are int64 in any monotonic unit the caller
+ * chooses; a tag is a caller-chosen uint64, echoed back (need not be unique).
+ * One tick with clock value now and n_tasks new requests:
+ *   1. the heartbeats, then the releases, exactly as ydc_stream_tick_wide (structural heartbeats
+ *      are applied eagerly and the step is captured again);
+ *   2. every entry of W with deadline <= now resolves as Timeout without being tried (the
+ *      reference's wait_until returning timeout, :115-117);
+ *   3. the rest of W in queue order, then the new requests in array order, are placed as ONE
+ *      committed batch, identical to sequential WaitForStartingNewTask calls with timeout == now
+ *      (a retry per tick is a wake-up the reference's while (true) loop tolerates, :102-118);
+ *   4. an entry of W that is granted or gets EnvironmentNotFound is resolved; one that gets
+ *      Timeout stays, keeping its position. A new request's answer goes to out_servant_idx as in
+ *      ydc_stream_tick; a Timeout with deadline <= now is YDC_IDX_TIMEOUT, one with a deadline
+ *      ahead is YDC_IDX_WAITING and the request joins the end of W (array order).
+ * Outputs: out_servant_idx[n_tasks]; the resolved entries of W in queue order as
+ * (out_resolved_tags[i], out_resolved_idx[i]) — servant index, YDC_IDX_TIMEOUT or
+ * YDC_IDX_ENV_NOT_FOUND — at most max_waiting of them, *out_n_resolved of them; *out_n_waiting =
+ * |W| afterwards. ydc_get_stats().granted counts every grant of the tick, the queue's included.
+ * Refused with nothing applied: |W| + n_tasks > max_waiting (YDC_ERR_CAPACITY — |W| is the
+ * previous tick's *out_n_waiting), now before the previous tick's now (YDC_ERR_INVALID_ARGUMENT).
+ * ydc_stream_tick / _wide on a waiting context is YDC_ERR_INVALID_ARGUMENT. The whole tick —
+ * queue, expiry, compaction — is one captured step as in streaming mode (no extra host round
+ * trip); a context begun with ydc_stream_begin is not affected at all. upd_env_masks is nullable
+ * (rows' env_mask then, as ydc_stream_tick). The caller's arrays are copied into the context's
+ * page-locked arena. */
+int ydc_stream_begin_waiting(ydc_context* ctx, uint32_t max_updates, uint32_t max_releases,
+                             uint32_t max_tasks, uint32_t max_waiting);
+int ydc_stream_tick_waiting(ydc_context* ctx, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                            const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                            const uint32_t* release_servant_idx, uint32_t n_rel,
+                            const ydc_task_soa* tasks, const int64_t* deadlines, const uint64_t* tags,
+                            uint32_t n_tasks, int64_t now, uint32_t* out_servant_idx,
+                            uint64_t* out_resolved_tags, uint32_t* out_resolved_idx,
+                            uint32_t* out_n_resolved, uint32_t* out_n_waiting);
+/* Empties W and hands over its tags in queue order (*out_n of them), for a host that shuts down or
+ * answers the waiters itself. More than cap waiting: YDC_ERR_CAPACITY, *out_n = |W|, W kept. */
+int ydc_stream_waiting_take(ydc_context* ctx, uint64_t* out_tags, uint32_t cap, uint32_t* out_n);
 
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.

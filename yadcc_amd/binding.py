@@ -13,12 +13,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (YDC_LIB: a measurement build of the same library, e.g. libydc_probe.so — tools/phase_probe.py)
 LIB_PATH = os.environ.get("YDC_LIB") or os.path.join(_HERE, "libydc.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 IPC_HANDLE_BYTES = 256
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_LOCAL, TRANSPORT_IPC_DEVICE, TRANSPORT_IPC_HOST = range(5)
 TRANSPORT_NAMES = ("none", "rccl", "local", "ipc", "ipc-host")
 IDX_TIMEOUT = 0xFFFFFFFF
 IDX_ENV_NOT_FOUND = 0xFFFFFFFE
+IDX_WAITING = 0xFFFFFFFD  # streaming waiting mode: queued on the device, answered in a later tick
 DISPATCH_COMMIT = 1
 STAGES = ("servant_scan", "slot_gen", "sort", "class_lists", "task_classify", "match", "finalize",
           "total")
@@ -34,6 +35,7 @@ ABI_SYMBOLS = (
     "ydc_device_malloc", "ydc_device_free", "ydc_memcpy_h2d", "ydc_memcpy_d2h",
     "ydc_host_register", "ydc_host_unregister", "ydc_host_alloc", "ydc_host_free",
     "ydc_stream_begin", "ydc_stream_tick", "ydc_stream_tick_wide", "ydc_stream_buffers_get", "ydc_stream_end",
+    "ydc_stream_begin_waiting", "ydc_stream_tick_waiting", "ydc_stream_waiting_take",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -133,6 +135,13 @@ def lib():
                                            C.c_uint32, C.c_void_p]
         L.ydc_stream_buffers_get.argtypes = [C.c_void_p, C.c_void_p]
         L.ydc_stream_end.argtypes = [C.c_void_p]
+        L.ydc_stream_begin_waiting.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.ydc_stream_tick_waiting.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                              C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(TaskSoA),
+                                              C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_uint32)]
+        L.ydc_stream_waiting_take.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.ydc_group_unique_id.argtypes = [C.c_void_p]
         L.ydc_group_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ydc_group_init_local.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -314,6 +323,7 @@ class Context:
         self._h = h
         self.n_servants = 0
         self._stream_caps = (0, 0, 0)
+        self._max_waiting = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -524,10 +534,64 @@ class Context:
                     "ydc_dispatch_sharded")
 
     # -- streaming mode: one captured step per tick ---------------------------------
-    def stream_begin(self, max_updates, max_releases, max_tasks):
-        self._check(lib().ydc_stream_begin(self._h, max_updates, max_releases, max_tasks),
-                    "ydc_stream_begin")
+    def stream_begin(self, max_updates, max_releases, max_tasks, max_waiting=0):
+        """max_waiting > 0: waiting mode (ydc_stream_begin_waiting) — requests that find no free
+        servant wait in a queue on the device until granted, EnvironmentNotFound or their deadline
+        (stream_tick_waiting); max_waiting bounds the queue plus a tick's new requests."""
+        if max_waiting:
+            self._check(lib().ydc_stream_begin_waiting(self._h, max_updates, max_releases, max_tasks,
+                                                       max_waiting), "ydc_stream_begin_waiting")
+        else:
+            self._check(lib().ydc_stream_begin(self._h, max_updates, max_releases, max_tasks),
+                        "ydc_stream_begin")
         self._stream_caps = (int(max_updates), int(max_releases), int(max_tasks))
+        self._max_waiting = int(max_waiting)
+
+    def stream_tick_waiting(self, upd_idx, upd_rows, release_idx, tasks, deadlines, tags, now,
+                            env_masks=None):
+        """One tick of a context begun with max_waiting > 0 (ydc_stream_tick_waiting).
+        deadlines: int64 per request, tags: uint64 per request (echoed back), now: int64 clock of
+        the tick (never smaller than the previous tick's). Returns (out, resolved_tags,
+        resolved_idx, n_waiting): out[i] is the servant index, IDX_TIMEOUT, IDX_ENV_NOT_FOUND or
+        IDX_WAITING of request i; the resolved list holds the queued requests answered in this
+        tick, in queue order; n_waiting is the size of the queue afterwards."""
+        ui = np.ascontiguousarray(upd_idx, dtype=np.uint32)
+        if len(ui):
+            self.n_servants = max(self.n_servants, int(ui.max()) + 1)
+        ur = np.ascontiguousarray(upd_rows, dtype=ROW_DTYPE)
+        rel = np.ascontiguousarray(release_idx, dtype=np.uint32)
+        keep = [np.ascontiguousarray(tasks[k], dtype=np.uint32)
+                for k in ("env_id", "min_version", "requestor_ip")]
+        n = len(keep[0])
+        dl = np.ascontiguousarray(deadlines, dtype=np.int64)
+        tg = np.ascontiguousarray(tags, dtype=np.uint64)
+        assert len(dl) == n and len(tg) == n
+        soa = TaskSoA(*[a.ctypes.data for a in keep])
+        out = np.empty(n, np.uint32)
+        cap = max(self._max_waiting, 1)
+        res_tags = np.empty(cap, np.uint64)
+        res_idx = np.empty(cap, np.uint32)
+        n_res, n_wait = C.c_uint32(0), C.c_uint32(0)
+        if env_masks is None:
+            em, words = None, 1
+        else:
+            em = np.ascontiguousarray(env_masks, dtype=np.uint64).reshape(len(ui), -1)
+            words = em.shape[1]
+        self._check(lib().ydc_stream_tick_waiting(
+            self._h, ui.ctypes.data, ur.ctypes.data, None if em is None else em.ctypes.data, words,
+            len(ui), rel.ctypes.data, len(rel), C.byref(soa), dl.ctypes.data, tg.ctypes.data, n,
+            int(now), out.ctypes.data, res_tags.ctypes.data, res_idx.ctypes.data, C.byref(n_res),
+            C.byref(n_wait)), "ydc_stream_tick_waiting")
+        k = n_res.value
+        return out, res_tags[:k].copy(), res_idx[:k].copy(), int(n_wait.value)
+
+    def stream_waiting_take(self):
+        """Empties the waiting queue; returns its tags in queue order (ydc_stream_waiting_take)."""
+        n = C.c_uint32(0)
+        out = np.empty(max(self._max_waiting, 1), np.uint64)
+        self._check(lib().ydc_stream_waiting_take(self._h, out.ctypes.data, len(out), C.byref(n)),
+                    "ydc_stream_waiting_take")
+        return out[:n.value].copy()
 
     def stream_tick(self, upd_idx, upd_rows, release_idx, tasks, env_masks=None):
         """upd_rows: numpy structured array of ROW_DTYPE (one heartbeat per entry of upd_idx);
@@ -593,6 +657,7 @@ class Context:
 
     def stream_end(self):
         self._check(lib().ydc_stream_end(self._h), "ydc_stream_end")
+        self._max_waiting = 0
 
     def set_profiling(self, on):
         self._check(lib().ydc_set_profiling(self._h, int(on)), "ydc_set_profiling")

@@ -23,6 +23,7 @@
 #include "dispatch_core.h"
 #include "host_tables.h"
 #include "kernels.h"
+#include "wait_queue.h"
 #include "tick_kernel.h"
 
 using namespace ydc;
@@ -252,6 +253,25 @@ struct ydc_context {
     // ticks that all needed fewer, exactly the most any of them needed (a pre-launched pass
     // that finds nothing to do still costs a launch); more again after a tick that ran out.
     uint32_t want_passes = 0, window_max = 0, window_ticks = 0;
+    // Waiting mode (ydc_stream_begin_waiting; wait_queue.h): the queue W of requests that found
+    // no free servant, in HBM, and the tick's batch columns [max_waiting | max_tasks] the gather
+    // builds in front of the batch. max_waiting == 0: a plain context (none of this exists).
+    uint32_t max_waiting = 0;
+    uint32_t n_waiting = 0;  // |W| after the last tick (the outcome block's, kept here)
+    int64_t last_now = INT64_MIN;
+    int64_t *h_dl = nullptr, *h_now = nullptr, *d_dl = nullptr, *d_now = nullptr, *z_dl = nullptr,
+            *z_now = nullptr;
+    uint64_t *h_tag = nullptr, *d_tag = nullptr, *z_tag = nullptr;
+    DevBuf<uint8_t> d_wait;
+    WaitCols wq{}, wt{};  // W; the tick's batch
+    uint32_t* wt_out = nullptr;  // placement of the batch (k_finalize -> k_wait_compact)
+    WaitState* ws = nullptr;
+    unsigned long long* lookback = nullptr;
+    uint32_t lookback_n = 0;
+    uint8_t* h_wres = nullptr;  // page-locked: resolved tags | resolved answers | outcome
+    uint64_t *h_res_tag = nullptr, *z_res_tag = nullptr;
+    uint32_t *h_res_idx = nullptr, *z_res_idx = nullptr;
+    WaitOutcome *h_wout = nullptr, *z_wout = nullptr;
   } stream_mode;
   DevBuf<ClassRun> d_runs;
   DevBuf<uint8_t> d_dirty;
@@ -723,7 +743,7 @@ int ydc_memcpy_h2d(void* dst, const void* src, size_t bytes) {
 int ydc_memcpy_d2h(void* dst, const void* src, size_t bytes) {
   return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? YDC_OK : YDC_ERR_HIP;
 }
-uint32_t ydc_abi_version(void) { return 6; }
+uint32_t ydc_abi_version(void) { return YDC_ABI_VERSION; }
 
 int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t max_slots,
                void* stream, ydc_context** out) {
@@ -3798,8 +3818,44 @@ void stream_release(ydc_context* c) {
   sm.h_upd_idx = sm.h_rel = sm.h_env = sm.h_minv = sm.h_ip = sm.h_out = nullptr;
   sm.h_upd_rows = nullptr;
   sm.d_in.release();
+  if (sm.h_wres) (void)hipHostFree(sm.h_wres);
+  sm.h_wres = nullptr;
+  sm.d_wait.release();  // (ydc_stream_end discards W)
+  sm.max_waiting = sm.n_waiting = 0;
+  sm.last_now = INT64_MIN;
+  sm.h_dl = sm.h_now = sm.d_dl = sm.d_now = sm.z_dl = sm.z_now = nullptr;
+  sm.h_tag = sm.d_tag = sm.z_tag = nullptr;
+  sm.wq = sm.wt = WaitCols{};
+  sm.wt_out = nullptr;
+  sm.ws = nullptr;
+  sm.lookback = nullptr;
+  sm.h_res_tag = sm.z_res_tag = nullptr;
+  sm.h_res_idx = sm.z_res_idx = nullptr;
+  sm.h_wout = sm.z_wout = nullptr;
   sm.active = false;
   sm.stale = true;
+}
+
+// Requests one streaming batch places: the new ones, behind W's region in waiting mode.
+uint32_t stream_batch_n(const ydc_context::Stream& sm) { return sm.max_tasks + sm.max_waiting; }
+
+// Waiting mode: the tick's batch columns from W and the new requests (wait_queue.h). `in`: the
+// staged tick as the launch reads it (page-locked arena in place, or its device copy).
+void enqueue_wait_gather(ydc_context* c, const WaitNew& in) {
+  auto& sm = c->stream_mode;
+  const uint32_t N = stream_batch_n(sm);
+  YDC_LAUNCH(c, "k_wait_gather", k_wait_gather, dim3(ceil_div(std::max(N, sm.lookback_n), 256)), dim3(256), 0,
+             c->stream, sm.wq, sm.wt, in, sm.max_waiting, N, sm.ws, sm.lookback, sm.lookback_n);
+}
+
+// ... and behind the batch: new W, resolved list, the new requests' answers. prm: gated on the
+// batch having become final (the captured step); NULL: the host has just placed it itself.
+void enqueue_wait_compact(ydc_context* c, const int64_t* now, const DeviceParams* prm, uint32_t check_slot) {
+  auto& sm = c->stream_mode;
+  const uint32_t N = stream_batch_n(sm);
+  YDC_LAUNCH(c, "k_wait_compact", k_wait_compact, dim3(ceil_div(N, kWaitTile)), dim3(256), 0, c->stream, sm.wt,
+             sm.wt_out, now, sm.max_waiting, N, sm.wq, sm.ws, sm.lookback, sm.z_out, sm.z_res_tag,
+             sm.z_res_idx, sm.z_wout, prm, check_slot);
 }
 
 // The step itself, enqueued on the context's stream (inside a capture, or — stream_graph=0 — as it is).
@@ -3821,19 +3877,27 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
                        c->n_servants, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p,
                        c->d_flags.p, c->d_running.p);
   }
+  // Waiting mode: the batch is W's region and the new requests, gathered into HBM; its placement
+  // stays there for k_wait_compact, which answers the caller.
+  const bool waiting = sm.max_waiting != 0;
+  if (waiting)
+    enqueue_wait_gather(c, WaitNew{sm.z_env, sm.z_minv, sm.z_ip, sm.z_dl, sm.z_tag, sm.z_now});
   ydc_task_soa d{sm.z_env, sm.z_minv, sm.z_ip};
+  if (waiting) d = ydc_task_soa{sm.wt.env, sm.wt.minv, sm.wt.ip};
   if (rc == YDC_OK) rc = enqueue_front(c, plan, &d);
   if (rc == YDC_OK && plan.wave_path)
     for (uint32_t r = 0; r < sm.passes; ++r) enqueue_pass(c, plan, r, 1u);
   const bool outcome_stored = c->opt_outcome_store && plan.S != 0;
+  const uint32_t check_slot = plan.wave_path ? (sm.passes - 1) & 63 : kNone;
   if (rc == YDC_OK) {
     c->finalize_outcome = outcome_stored ? c->d_h_prm : nullptr;
     c->commit_by_swap = by_swap;
-    rc = enqueue_finalize(c, plan, YDC_DISPATCH_COMMIT, sm.z_out, nullptr, nullptr,
-                          plan.wave_path ? (sm.passes - 1) & 63 : kNone);
+    rc = enqueue_finalize(c, plan, YDC_DISPATCH_COMMIT, waiting ? sm.wt_out : sm.z_out, nullptr, nullptr,
+                          check_slot);
     c->commit_by_swap = false;
     c->finalize_outcome = nullptr;
   }
+  if (rc == YDC_OK && waiting) enqueue_wait_compact(c, sm.z_now, c->d_prm.p, check_slot);
   if (!outcome_stored) cap(hipMemcpyAsync(c->h_prm, c->d_prm.p, sizeof(DeviceParams), hipMemcpyDeviceToHost, st));
   return rc;
 }
@@ -3867,7 +3931,7 @@ int stream_capture(ydc_context* c) {
   const bool was_profiling = c->profiling;
   c->profiling = false;  // no event pairs inside a capture
   // Sizes and workspace first (allocations and table uploads cannot be captured).
-  if (int rc = plan_batch(c, sm.max_tasks, &sm.plan)) return rc;
+  if (int rc = plan_batch(c, stream_batch_n(sm), &sm.plan)) return rc;
   if (sm.plan.use_generic) {
     // More than 256 servant classes: the rounds of that path are checked by the host, which a
     // captured step cannot do — such ticks run eagerly (ydc_stream_tick_wide, below).
@@ -3887,7 +3951,7 @@ int stream_capture(ydc_context* c) {
     // ... and once more with the two columns in each other's role.
     std::swap(c->d_running, c->d_running_out);
     sm.run_b = c->d_running.p;
-    rc = plan_batch(c, sm.max_tasks, &sm.plan_b);
+    rc = plan_batch(c, stream_batch_n(sm), &sm.plan_b);
     if (rc == YDC_OK) rc = stream_capture_one(c, sm.plan_b, true, &sm.graph_b, &sm.exec_b);
     std::swap(c->d_running, c->d_running_out);
   }
@@ -3898,13 +3962,22 @@ int stream_capture(ydc_context* c) {
   return YDC_OK;
 }
 
-}  // namespace
+// A waiting tick's own arguments (ydc_stream_tick_waiting).
+struct WaitTick {
+  const int64_t* deadlines;
+  const uint64_t* tags;
+  int64_t now;
+  uint64_t* out_resolved_tags;
+  uint32_t* out_resolved_idx;
+  uint32_t* out_n_resolved;
+  uint32_t* out_n_waiting;
+};
 
-extern "C" {
-
-int ydc_stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases,
-                     uint32_t max_tasks) {
+int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
+                 uint32_t max_waiting) {
   if (!c || !max_tasks) return YDC_ERR_INVALID_ARGUMENT;
+  if ((uint64_t)max_tasks + max_waiting > 0x7FFFFFFFull)
+    return fail(c, YDC_ERR_CAPACITY, "max_tasks %u + max_waiting %u too large", max_tasks, max_waiting);
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   stream_release(c);
@@ -3925,6 +3998,10 @@ int ydc_stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases
   const size_t o_env = section((size_t)max_tasks * 4);
   const size_t o_minv = section((size_t)max_tasks * 4);
   const size_t o_ip = section((size_t)max_tasks * 4);
+  // Waiting mode: the new requests' deadlines and tags, and the tick's clock, in the same arena.
+  const size_t o_dl = max_waiting ? section((size_t)max_tasks * 8) : 0;
+  const size_t o_tag = max_waiting ? section((size_t)max_tasks * 8) : 0;
+  const size_t o_now = max_waiting ? section(8) : 0;
   sm.in_bytes = off;
   HIP_TRY(c, hipHostMalloc((void**)&sm.h_in, sm.in_bytes, hipHostMallocCoherent | hipHostMallocMapped));
   HIP_TRY(c, hipHostMalloc((void**)&sm.h_out, std::max<size_t>((size_t)max_tasks * 4, 16),
@@ -3954,9 +4031,94 @@ int ydc_stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases
   sm.d_minv = (uint32_t*)(sm.d_in.p + o_minv);
   sm.d_ip = (uint32_t*)(sm.d_in.p + o_ip);
   HIP_TRY(c, c->d_out_idx.reserve(max_tasks));
+  if (max_waiting) {
+    sm.max_waiting = max_waiting;
+    uint8_t* z_in = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&z_in, sm.h_in, 0));
+    sm.h_dl = (int64_t*)(sm.h_in + o_dl);
+    sm.h_tag = (uint64_t*)(sm.h_in + o_tag);
+    sm.h_now = (int64_t*)(sm.h_in + o_now);
+    sm.d_dl = (int64_t*)(sm.d_in.p + o_dl);
+    sm.d_tag = (uint64_t*)(sm.d_in.p + o_tag);
+    sm.d_now = (int64_t*)(sm.d_in.p + o_now);
+    sm.z_dl = (int64_t*)(z_in + o_dl);
+    sm.z_tag = (uint64_t*)(z_in + o_tag);
+    sm.z_now = (int64_t*)(z_in + o_now);
+    // HBM: W (max_waiting entries), the tick's batch (max_waiting + max_tasks) with its placement,
+    // the queue's counters and k_wait_compact's look-back words.
+    const size_t NB = (size_t)max_tasks + max_waiting;
+    sm.lookback_n = (uint32_t)((NB + kWaitTile - 1) / kWaitTile);
+    size_t w_off = 0;
+    auto wsec = [&](size_t bytes) {
+      const size_t at = w_off;
+      w_off += (std::max<size_t>(bytes, 16) + 255) & ~(size_t)255;
+      return at;
+    };
+    const size_t o_wq[5] = {wsec(max_waiting * 4ull), wsec(max_waiting * 4ull), wsec(max_waiting * 4ull),
+                            wsec(max_waiting * 8ull), wsec(max_waiting * 8ull)};
+    const size_t o_wt[5] = {wsec(NB * 4), wsec(NB * 4), wsec(NB * 4), wsec(NB * 8), wsec(NB * 8)};
+    const size_t o_wout = wsec(NB * 4), o_ws = wsec(sizeof(WaitState)), o_lb = wsec((size_t)sm.lookback_n * 8);
+    HIP_TRY(c, sm.d_wait.reserve(w_off));
+    uint8_t* b = sm.d_wait.p;
+    sm.wq = WaitCols{(uint32_t*)(b + o_wq[0]), (uint32_t*)(b + o_wq[1]), (uint32_t*)(b + o_wq[2]),
+                     (int64_t*)(b + o_wq[3]), (uint64_t*)(b + o_wq[4])};
+    sm.wt = WaitCols{(uint32_t*)(b + o_wt[0]), (uint32_t*)(b + o_wt[1]), (uint32_t*)(b + o_wt[2]),
+                     (int64_t*)(b + o_wt[3]), (uint64_t*)(b + o_wt[4])};
+    sm.wt_out = (uint32_t*)(b + o_wout);
+    sm.ws = (WaitState*)(b + o_ws);
+    sm.lookback = (unsigned long long*)(b + o_lb);
+    HIP_TRY(c, hipMemsetAsync(sm.ws, 0, sizeof(WaitState), c->stream));  // W empty
+    // Page-locked results: resolved tags | resolved answers | outcome block.
+    const size_t r_tag = 0, r_idx = ((size_t)max_waiting * 8 + 255) & ~(size_t)255;
+    const size_t r_out = r_idx + (((size_t)max_waiting * 4 + 255) & ~(size_t)255);
+    HIP_TRY(c, hipHostMalloc((void**)&sm.h_wres, r_out + sizeof(WaitOutcome),
+                             hipHostMallocCoherent | hipHostMallocMapped));
+    uint8_t* z_res = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&z_res, sm.h_wres, 0));
+    sm.h_res_tag = (uint64_t*)(sm.h_wres + r_tag);
+    sm.h_res_idx = (uint32_t*)(sm.h_wres + r_idx);
+    sm.h_wout = (WaitOutcome*)(sm.h_wres + r_out);
+    sm.z_res_tag = (uint64_t*)(z_res + r_tag);
+    sm.z_res_idx = (uint32_t*)(z_res + r_idx);
+    sm.z_wout = (WaitOutcome*)(z_res + r_out);
+    std::memset(sm.h_wout, 0, sizeof(WaitOutcome));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
   sm.active = true;
   sm.stale = true;
+  return YDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ydc_stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases,
+                     uint32_t max_tasks) {
+  return stream_begin(c, max_updates, max_releases, max_tasks, 0);
+}
+
+int ydc_stream_begin_waiting(ydc_context* c, uint32_t max_updates, uint32_t max_releases,
+                             uint32_t max_tasks, uint32_t max_waiting) {
+  if (!c || !max_waiting) return YDC_ERR_INVALID_ARGUMENT;
+  return stream_begin(c, max_updates, max_releases, max_tasks, max_waiting);
+}
+
+int ydc_stream_waiting_take(ydc_context* c, uint64_t* out_tags, uint32_t cap, uint32_t* out_n) {
+  if (!c || !out_n || !c->stream_mode.active || !c->stream_mode.max_waiting) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint32_t n = 0;
+  HIP_TRY(c, hipMemcpy(&n, &sm.ws->count, 4, hipMemcpyDeviceToHost));
+  *out_n = n;
+  if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u waiting requests > cap %u", n, cap);
+  if (n && !out_tags) return YDC_ERR_INVALID_ARGUMENT;
+  if (n) HIP_TRY(c, hipMemcpy(out_tags, sm.wq.tag, (size_t)n * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemsetAsync(&sm.ws->count, 0, 4, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  sm.n_waiting = 0;
   return YDC_OK;
 }
 
@@ -3988,12 +4150,42 @@ int ydc_stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_r
                               n_tasks, out_servant_idx);
 }
 
-int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
-                         const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
-                         const uint32_t* release_servant_idx, uint32_t n_rel, const ydc_task_soa* tasks,
-                         uint32_t n_tasks, uint32_t* out_servant_idx) {
+// Waiting mode, after the step: the resolved list to the caller, the host's mirror of |W| and the
+// statistics (padding — W's unused or expired slots, the new region's tail — counts nowhere).
+static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tasks) {
+  auto& sm = c->stream_mode;
+  const uint32_t n_res = std::min(sm.h_wout->n_resolved, sm.max_waiting);
+  const uint32_t n_wait = sm.h_wout->n_waiting;
+  if (n_wait > sm.max_waiting)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u > max_waiting %u", n_wait, sm.max_waiting);
+  uint32_t expired = 0;  // (a resolved Timeout is an expired entry: a live one that timed out stays)
+  for (uint32_t i = 0; i < n_res; ++i) expired += sm.h_res_idx[i] == YDC_IDX_TIMEOUT;
+  if (n_res && wt->out_resolved_tags != sm.h_res_tag)
+    std::memcpy(wt->out_resolved_tags, sm.h_res_tag, (size_t)n_res * 8);
+  if (n_res && wt->out_resolved_idx != sm.h_res_idx)
+    std::memcpy(wt->out_resolved_idx, sm.h_res_idx, (size_t)n_res * 4);
+  *wt->out_n_resolved = n_res;
+  *wt->out_n_waiting = n_wait;
+  const uint32_t live = sm.n_waiting - std::min(sm.n_waiting, expired);
+  c->stats.n_tasks = n_tasks + live;
+  // (the new region's padding is taken off by the caller, as in a plain tick; W's here)
+  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_waiting - live);
+  sm.n_waiting = n_wait;
+  sm.last_now = wt->now;
+  return YDC_OK;
+}
+
+static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                       const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                       const uint32_t* release_servant_idx, uint32_t n_rel, const ydc_task_soa* tasks,
+                       uint32_t n_tasks, uint32_t* out_servant_idx, const WaitTick* wt) {
   if (!c || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
+  if (wt && !sm.max_waiting)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_waiting on a context begun without a waiting queue");
+  if (!wt && sm.max_waiting)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_waiting takes "
+                "ydc_stream_tick_waiting");
   if (n_upd > sm.max_upd || n_rel > sm.max_rel || n_tasks > sm.max_tasks)
     return fail(c, YDC_ERR_CAPACITY, "tick (%u updates, %u releases, %u tasks) exceeds the capacity "
                 "given to ydc_stream_begin (%u, %u, %u)", n_upd, n_rel, n_tasks, sm.max_upd,
@@ -4001,6 +4193,18 @@ int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_serv
   if ((n_upd && (!upd_idx || !upd_rows)) || (n_rel && !release_servant_idx) ||
       (n_tasks && (!tasks || !out_servant_idx)))
     return YDC_ERR_INVALID_ARGUMENT;
+  if (wt) {
+    // (nothing is applied unless the whole tick is acceptable)
+    if ((uint64_t)sm.n_waiting + n_tasks > sm.max_waiting)
+      return fail(c, YDC_ERR_CAPACITY, "%u waiting + %u new requests > max_waiting %u", sm.n_waiting, n_tasks,
+                  sm.max_waiting);
+    if (wt->now < sm.last_now)
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "now %lld is before the previous tick's %lld", (long long)wt->now,
+                  (long long)sm.last_now);
+    if ((n_tasks && (!wt->deadlines || !wt->tags)) || !wt->out_n_resolved || !wt->out_n_waiting ||
+        !wt->out_resolved_tags || !wt->out_resolved_idx)
+      return YDC_ERR_INVALID_ARGUMENT;
+  }
   if (upd_env_masks && (env_words == 0 || env_words > YDC_MAX_ENV_WORDS))
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "env_words %u out of range", env_words);
   HIP_TRY(c, hipSetDevice(c->device));
@@ -4082,6 +4286,17 @@ int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_serv
     sm.h_minv[i] = 0;
     sm.h_ip[i] = 0;
   }
+  if (wt) {
+    if (n_tasks && wt->deadlines != sm.h_dl) std::memcpy(sm.h_dl, wt->deadlines, (size_t)n_tasks * 8);
+    if (n_tasks && wt->tags != sm.h_tag) std::memcpy(sm.h_tag, wt->tags, (size_t)n_tasks * 8);
+    *sm.h_now = wt->now;
+  }
+  // Waiting mode: the batch is W's region + the new requests in HBM (k_wait_gather), its placement
+  // goes to wt_out and k_wait_compact answers the caller.
+  const ydc_task_soa batch_dev = wt ? ydc_task_soa{sm.wt.env, sm.wt.minv, sm.wt.ip}
+                                    : ydc_task_soa{sm.d_env, sm.d_minv, sm.d_ip};
+  uint32_t* const batch_out = wt ? sm.wt_out : c->d_out_idx.p;
+  const uint32_t NB = stream_batch_n(sm);
   if (sm.eager_only) {
     // The same step, enqueued instead of replayed: staging copy, registry deltas, the batch with
     // its host-checked rounds, COMMIT, results back.
@@ -4094,17 +4309,26 @@ int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_serv
                          c->n_servants, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p,
                          c->d_flags.p, c->d_running.p);
     }
+    if (wt) enqueue_wait_gather(c, WaitNew{sm.d_env, sm.d_minv, sm.d_ip, sm.d_dl, sm.d_tag, sm.d_now});
     BatchPlan pe;
-    if (int rc = plan_batch(c, sm.max_tasks, &pe)) return rc;
-    ydc_task_soa d{sm.d_env, sm.d_minv, sm.d_ip};
+    if (int rc = plan_batch(c, NB, &pe)) return rc;
+    ydc_task_soa d = batch_dev;
     uint32_t rounds_e = 0;
-    if (int rc = run_planned_batch(c, pe, &d, YDC_DISPATCH_COMMIT, c->d_out_idx.p, nullptr, nullptr, &rounds_e))
+    if (int rc = run_planned_batch(c, pe, &d, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &rounds_e))
       return rc;
-    HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
+    if (wt) {
+      enqueue_wait_compact(c, sm.d_now, nullptr, kNone);
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      HIP_TRY(c, hipGetLastError());
+    } else {
+      HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
+    }
     ++sm.ticks;
     fill_stats(c, pe, rounds_e);
     c->stats.n_tasks = n_tasks;
     c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
+    if (wt)
+      if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
     if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
     return YDC_OK;
   }
@@ -4138,16 +4362,25 @@ int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_serv
     // again, without the bin sort, on the next tick.
     ++sm.eager_fallbacks;
     BatchPlan p2;
-    if (int rc = fall_back_to_radix(c, sm.max_tasks, &p2)) return rc;
-    // (the captured step read the arena in place: the device copy is stale)
+    if (int rc = fall_back_to_radix(c, NB, &p2)) return rc;
+    // (the captured step read the arena in place: the device copy is stale; in waiting mode the
+    // gathered batch in HBM is what is placed again, and W is still as the gather read it)
     HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
-    ydc_task_soa d{sm.d_env, sm.d_minv, sm.d_ip};
-    if (int rc = run_planned_batch(c, p2, &d, YDC_DISPATCH_COMMIT, c->d_out_idx.p, nullptr, nullptr, &rounds))
+    ydc_task_soa d = batch_dev;
+    if (int rc = run_planned_batch(c, p2, &d, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &rounds))
       return rc;
-    HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
+    if (wt) {
+      enqueue_wait_compact(c, sm.d_now, nullptr, kNone);
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      HIP_TRY(c, hipGetLastError());
+    } else {
+      HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
+    }
     fill_stats(c, p2, rounds);
     c->stats.n_tasks = n_tasks;
     c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
+    if (wt)
+      if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
     if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
     return YDC_OK;
   }
@@ -4156,10 +4389,16 @@ int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_serv
       // The captured passes were not enough (rare): finish eagerly and capture a longer
       // step next time.
       ++sm.eager_fallbacks;
-      if (int rc = run_passes_until_consistent(c, p, sm.passes, YDC_DISPATCH_COMMIT, c->d_out_idx.p,
+      if (int rc = run_passes_until_consistent(c, p, sm.passes, YDC_DISPATCH_COMMIT, batch_out,
                                                nullptr, nullptr, &rounds))
         return rc;
-      HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
+      if (wt) {
+        enqueue_wait_compact(c, sm.z_now, nullptr, kNone);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+      } else {
+        HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
+      }
       c->round_hint = rounds;
       sm.want_passes = std::min(rounds + 1, 12u);
       sm.stale = true;
@@ -4182,8 +4421,29 @@ int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_serv
   fill_stats(c, p, rounds);
   c->stats.n_tasks = n_tasks;
   c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
+  if (wt)
+    if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
   if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
   return YDC_OK;
+}
+
+int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                         const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                         const uint32_t* release_servant_idx, uint32_t n_rel, const ydc_task_soa* tasks,
+                         uint32_t n_tasks, uint32_t* out_servant_idx) {
+  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
+                     n_tasks, out_servant_idx, nullptr);
+}
+
+int ydc_stream_tick_waiting(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                            const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                            const uint32_t* release_servant_idx, uint32_t n_rel, const ydc_task_soa* tasks,
+                            const int64_t* deadlines, const uint64_t* tags, uint32_t n_tasks, int64_t now,
+                            uint32_t* out_servant_idx, uint64_t* out_resolved_tags, uint32_t* out_resolved_idx,
+                            uint32_t* out_n_resolved, uint32_t* out_n_waiting) {
+  const WaitTick wt{deadlines, tags, now, out_resolved_tags, out_resolved_idx, out_n_resolved, out_n_waiting};
+  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
+                     n_tasks, out_servant_idx, &wt);
 }
 
 }  // extern "C"
