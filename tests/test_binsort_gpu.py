@@ -9,7 +9,9 @@ import pytest
 
 from oracle import oraclebind as O
 from tests import cases
+from tests import stream_wait_model as M
 from tests.test_gpu_parity import check
+from tests.test_stream_waiting_gpu import drive
 from yadcc_amd import binding, pack, streaming, synth
 
 pytestmark = pytest.mark.gpu
@@ -127,10 +129,21 @@ def test_bin_overflow_repeats_the_batch_with_the_radix_sort():
         c.close()
 
 
+def _crowded_bin_pool():
+    """4096 idle servants (the bin sort's limit; _tied_pool's sizes are beyond it): 4000 with one
+    slot and 96 with 2047. Every first slot has the same key and the large servants add 8 slots
+    each next to it: one bin holds 4768 slots, more than its LDS buffer (bin_sort.h: kBinCap)."""
+    sv = _tied_pool(4096)
+    for k in ("num_processors", "max_tasks"):
+        sv[k][:] = 1
+        sv[k][:96] = 2047
+    return sv
+
+
 def test_bin_overflow_inside_a_streaming_tick():
     """The captured step uses the bin sort; a tick whose bins overflow is placed eagerly with the
     radix sort (its registry deltas are already applied) and the step is captured again."""
-    sv = _tied_pool(5000)
+    sv = _crowded_bin_pool()
     es = streaming.EventStream(sv, 3000, 1000)
     c = _context(True)
     try:
@@ -141,8 +154,28 @@ def test_bin_overflow_inside_a_streaming_tick():
             want, _, wrun = O.dispatch(es.registry_snapshot(), tk, "sorted")
             got = c.stream_tick(who, rows, rel, tk)
             assert np.array_equal(got, want), t
+            if t == 0:
+                assert c.stats()["radix_passes"] >= 1  # (placed again with the radix sort)
             es.commit(got)
             assert np.array_equal(c.get_running(), wrun), t
+        c.stream_end()
+    finally:
+        c.close()
+
+
+def test_bin_overflow_inside_a_waiting_streaming_tick():
+    """The same in waiting mode: the overflowing tick places the gathered batch (W's region and the
+    new requests, in HBM) again with the radix sort and compacts it. Every tick is checked against
+    the model (tests/stream_wait_model.py)."""
+    ws = M.WaitingStream(_crowded_bin_pool(), 3000, 1000, 6000)
+    q = M.WaitQueue(6000)
+    c = _context(True)
+    try:
+        c.upload_servants(pack.to_abi_columns(ws.es.sv))
+        c.stream_begin(ws.es.hb + 8, 1000, 3000, max_waiting=6000)
+        drive(c, ws, q, 1)
+        assert c.stats()["radix_passes"] >= 1  # (placed again with the radix sort)
+        drive(c, ws, q, 3)
         c.stream_end()
     finally:
         c.close()

@@ -102,6 +102,19 @@ struct BatchPlan {
   uint32_t rank_stride = 1;             // 2: rank_to_g are the values of 8-byte sort records
   SharedIpTable shared{};  // pos_last != NULL: some host runs several servants
 };
+
+// The sections of a streaming tick's staging arena (stream_begin lays them out): heartbeat
+// indexes and rows, released slots, the three request columns and, in waiting mode, the new
+// requests' deadlines and tags and the tick's clock (NULL in a plain context).
+struct TickArena {
+  uint32_t* upd_idx;
+  ydc_servant_row* upd_rows;
+  uint32_t* rel;
+  uint32_t *env, *minv, *ip;
+  int64_t* dl;
+  uint64_t* tag;
+  int64_t* now;
+};
 }  // namespace
 
 struct ydc_context {
@@ -219,23 +232,15 @@ struct ydc_context {
   struct Stream {
     bool active = false, stale = true;
     uint32_t max_upd = 0, max_rel = 0, max_tasks = 0, passes = 0;
-    // One pinned staging arena for everything a tick brings (heartbeat indexes and rows,
-    // released slots, the three request columns) and its device mirror, which the ticks that
-    // run eagerly copy it to. The typed pointers below point into the two arenas.
+    // One pinned staging arena for everything a tick brings (TickArena) and its device mirror,
+    // which the ticks that run eagerly copy it to. Its sections three times: at their host
+    // addresses, in the mirror, and as the kernels of the captured step see the page-locked
+    // arena when they read it in place (no H2D copy node).
     uint8_t* h_in = nullptr;
     DevBuf<uint8_t> d_in;
     size_t in_bytes = 0;
-    uint32_t *h_upd_idx = nullptr, *h_rel = nullptr, *h_env = nullptr, *h_minv = nullptr,
-             *h_ip = nullptr, *h_out = nullptr;
-    ydc_servant_row* h_upd_rows = nullptr;
-    uint32_t *d_upd_idx = nullptr, *d_rel = nullptr, *d_env = nullptr, *d_minv = nullptr,
-             *d_ip = nullptr;
-    ServantRowDev* d_upd_rows = nullptr;
-    // The same sections as the kernels of the captured step see them when they read the
-    // page-locked arena in place (no H2D copy node), and the result array likewise.
-    uint32_t *z_upd_idx = nullptr, *z_rel = nullptr, *z_env = nullptr, *z_minv = nullptr, *z_ip = nullptr,
-             *z_out = nullptr;
-    ServantRowDev* z_upd_rows = nullptr;
+    TickArena h{}, d{}, z{};
+    uint32_t *h_out = nullptr, *z_out = nullptr;  // the placement (page-locked), host and device addresses
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     BatchPlan plan;
@@ -247,7 +252,6 @@ struct ydc_context {
     BatchPlan plan_b;
     const uint32_t *run_a = nullptr, *run_b = nullptr;
     bool swaps = false;
-    uint64_t ticks = 0, recaptures = 0, eager_fallbacks = 0;
     bool eager_only = false;  // the registry's batches cannot be captured (> 256 classes): every tick runs eagerly
     // Passes to capture: one more than the last eager batch needed, to begin with; after 64
     // ticks that all needed fewer, exactly the most any of them needed (a pre-launched pass
@@ -259,9 +263,6 @@ struct ydc_context {
     uint32_t max_waiting = 0;
     uint32_t n_waiting = 0;  // |W| after the last tick (the outcome block's, kept here)
     int64_t last_now = INT64_MIN;
-    int64_t *h_dl = nullptr, *h_now = nullptr, *d_dl = nullptr, *d_now = nullptr, *z_dl = nullptr,
-            *z_now = nullptr;
-    uint64_t *h_tag = nullptr, *d_tag = nullptr, *z_tag = nullptr;
     DevBuf<uint8_t> d_wait;
     WaitCols wq{}, wt{};  // W; the tick's batch
     uint32_t* wt_out = nullptr;  // placement of the batch (k_finalize -> k_wait_compact)
@@ -2153,12 +2154,25 @@ int run_planned_batch(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk
 }
 
 // A bin of the bin sort overflowed: from now on (until the registry changes structure) the
-// radix sort; `p` is planned again accordingly.
-int fall_back_to_radix(ydc_context* c, uint32_t N, BatchPlan* p) {
+// radix sort — batches planned after this take it.
+void note_bin_overflow(ydc_context* c) {
   c->binsort_blocked = true;
   ++c->binsort_misses;
   c->stream_mode.stale = true;
-  return plan_batch(c, N, p);
+}
+
+// Plans a batch and places it, host-checked (*p: the plan it was placed with); a bin overflow
+// places it once more with the radix sort.
+int place_batch(ydc_context* c, uint32_t N, const ydc_task_soa* tk, uint32_t flags, uint32_t* d_out_idx,
+                double* d_out_util, uint32_t* d_out_running, BatchPlan* p, uint32_t* rounds_out) {
+  if (int rc = plan_batch(c, N, p)) return rc;
+  int rc = run_planned_batch(c, *p, tk, flags, d_out_idx, d_out_util, d_out_running, rounds_out);
+  if (rc == kRetryRadix) {
+    note_bin_overflow(c);
+    if (int rc2 = plan_batch(c, N, p)) return rc2;
+    rc = run_planned_batch(c, *p, tk, flags, d_out_idx, d_out_util, d_out_running, rounds_out);
+  }
+  return rc;
 }
 
 }  // namespace
@@ -2199,20 +2213,38 @@ bool tick_takes(const ydc_context* c, uint32_t n_tasks, bool same = false) {
 }
 
 // A heartbeat row that changes what the derived tables are built from (classes, the ip table,
-// the slot bound): same test as ydc_update_servants_wide.
+// the slot bound): a new servant, another version / host / capacity bound, or (row i of
+// env_masks, env_words words each) another environment set, the shorter of the two masks
+// extended with zero words. A row without masks on a table of several mask words cannot say what
+// the servant advertises: it keeps its environments.
 bool row_is_structural(const ydc_context* c, uint32_t s, const ydc_servant_row& r, const uint64_t* env_masks,
                        uint32_t env_words, uint32_t i) {
-  if (s >= c->n_servants) return true;  // a new servant
+  if (s >= c->n_servants) return true;
   const uint32_t EW = c->env_words;
-  if (env_masks && env_words > EW) return true;
-  if (!env_masks && EW > 1) return true;  // (refused by ydc_update_servants_wide: let it say so)
-  const uint64_t* env = &c->h_env[(size_t)s * EW];
-  for (uint32_t w = 0; w < EW; ++w) {
-    const uint64_t m = env_masks ? (w < env_words ? env_masks[(size_t)i * env_words + w] : 0) : (w == 0 ? r.env_mask : 0);
-    if (env[w] != m) return true;
+  bool env_changed = false;
+  if (env_masks) {
+    for (uint32_t w = 0; w < std::max(EW, env_words); ++w) {
+      const uint64_t have = w < EW ? c->h_env[(size_t)s * EW + w] : 0;
+      const uint64_t want = w < env_words ? env_masks[(size_t)i * env_words + w] : 0;
+      env_changed |= have != want;
+    }
+  } else if (EW == 1) {
+    env_changed = c->h_env[s] != r.env_mask;
   }
-  return c->h_version[s] != r.version || c->h_ip[s] != r.ip_id || (c->h_max_tasks[s] == 0) != (r.max_tasks == 0) ||
+  return env_changed || c->h_version[s] != r.version || c->h_ip[s] != r.ip_id ||
+         (c->h_max_tasks[s] == 0) != (r.max_tasks == 0) ||
          std::min(c->h_max_tasks[s], c->h_nproc[s]) != std::min(r.max_tasks, r.num_processors);
+}
+
+// The host mirror of the columns that heartbeat rows which change no structure replace.
+void mirror_rows(ydc_context* c, const uint32_t* idx, const ydc_servant_row* rows, uint32_t n) {
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t s = idx[i];
+    c->h_nproc[s] = rows[i].num_processors;
+    c->h_load[s] = rows[i].current_load;
+    c->h_max_tasks[s] = rows[i].max_tasks;
+    c->h_flags[s] = rows[i].flags;
+  }
 }
 
 // ---- the resident kernel (tick_kernel.h: TickBox) ----
@@ -2655,14 +2687,8 @@ int ydc_dispatch_device(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint
   }
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   BatchPlan p;
-  if (int rc = plan_batch(c, N, &p)) return rc;
   uint32_t rounds = 0;
-  int rc = run_planned_batch(c, p, tk, flags, d_out_idx, d_out_util, d_out_running, &rounds);
-  if (rc == kRetryRadix) {
-    if (int rc2 = fall_back_to_radix(c, N, &p)) return rc2;
-    rc = run_planned_batch(c, p, tk, flags, d_out_idx, d_out_util, d_out_running, &rounds);
-  }
-  if (rc) return rc;
+  if (int rc = place_batch(c, N, tk, flags, d_out_idx, d_out_util, d_out_running, &p, &rounds)) return rc;
   fill_stats(c, p, rounds);
   ydc_stats& s = c->stats;
   if (c->profiling) {
@@ -2921,10 +2947,13 @@ int ydc_dispatch_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant
   HIP_TRY(c, hipSetDevice(c->device));
   // Heartbeats that change structure (a new servant, other environments / version / host /
   // capacity bound) take the general path, derived tables and all; so does a tick the kernel
-  // does not take (a large batch, a registry beyond its limits).
+  // does not take (a large batch, a registry beyond its limits). So do mask words beyond the
+  // table's width and rows without masks on a table of several words (ydc_update_servants_wide
+  // refuses those: let it say so).
+  const bool wider = upd_env_masks ? env_words > c->env_words : c->env_words > 1;
   bool structural = false;
   for (uint32_t i = 0; i < n_upd && !structural; ++i)
-    structural = row_is_structural(c, upd_idx[i], upd_rows[i], upd_env_masks, env_words, i);
+    structural = wider || row_is_structural(c, upd_idx[i], upd_rows[i], upd_env_masks, env_words, i);
   if (!structural && c->tables_dirty)
     if (int rc = rebuild_tables(c)) return rc;
   // (registry deltas ride in the launch only with COMMIT: running_tasks goes back once, into the
@@ -2945,13 +2974,7 @@ int ydc_dispatch_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant
       return ydc_dispatch(c, tasks, n_tasks, flags, out_servant_idx, out_utilization, nullptr);
     }
   }
-  for (uint32_t i = 0; i < n_upd; ++i) {  // host mirror of the columns the rows replace
-    const uint32_t s = upd_idx[i];
-    c->h_nproc[s] = upd_rows[i].num_processors;
-    c->h_load[s] = upd_rows[i].current_load;
-    c->h_max_tasks[s] = upd_rows[i].max_tasks;
-    c->h_flags[s] = upd_rows[i].flags;
-  }
+  mirror_rows(c, upd_idx, upd_rows, n_upd);
   TickCall io;
   io.tasks = tasks;
   io.n_tasks = n_tasks;
@@ -3770,7 +3793,8 @@ int ydc_dispatch_sharded(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uin
     if (!windowed && p.binsort) {
       // A bin of the bin sort overflowed (bin_sort.h; the registry decides, so every rank met
       // the same): once more with the radix pipeline, which then stays.
-      if (int rc = fall_back_to_radix(c, N, &full_plan)) return rc;
+      note_bin_overflow(c);
+      if (int rc = plan_batch(c, N, &full_plan)) return rc;
       continue;
     }
     if (!windowed) return fail(c, YDC_ERR_NOT_CONVERGED, "window miss flagged without a window");
@@ -3804,48 +3828,53 @@ int ydc_dispatch_sharded(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uin
 // ---------------------------------------------------------------------------
 namespace {
 
-void stream_release(ydc_context* c) {
-  auto& sm = c->stream_mode;
+void stream_drop_graphs(ydc_context::Stream& sm) {
   if (sm.exec) (void)hipGraphExecDestroy(sm.exec);
   if (sm.graph) (void)hipGraphDestroy(sm.graph);
   if (sm.exec_b) (void)hipGraphExecDestroy(sm.exec_b);
   if (sm.graph_b) (void)hipGraphDestroy(sm.graph_b);
   sm.exec = sm.exec_b = nullptr;
   sm.graph = sm.graph_b = nullptr;
-  if (sm.h_in) (void)hipHostFree(sm.h_in);
-  if (sm.h_out) (void)hipHostFree(sm.h_out);
-  sm.h_in = nullptr;
-  sm.h_upd_idx = sm.h_rel = sm.h_env = sm.h_minv = sm.h_ip = sm.h_out = nullptr;
-  sm.h_upd_rows = nullptr;
-  sm.d_in.release();
-  if (sm.h_wres) (void)hipHostFree(sm.h_wres);
-  sm.h_wres = nullptr;
-  sm.d_wait.release();  // (ydc_stream_end discards W)
-  sm.max_waiting = sm.n_waiting = 0;
-  sm.last_now = INT64_MIN;
-  sm.h_dl = sm.h_now = sm.d_dl = sm.d_now = sm.z_dl = sm.z_now = nullptr;
-  sm.h_tag = sm.d_tag = sm.z_tag = nullptr;
-  sm.wq = sm.wt = WaitCols{};
-  sm.wt_out = nullptr;
-  sm.ws = nullptr;
-  sm.lookback = nullptr;
-  sm.h_res_tag = sm.z_res_tag = nullptr;
-  sm.h_res_idx = sm.z_res_idx = nullptr;
-  sm.h_wout = sm.z_wout = nullptr;
-  sm.active = false;
-  sm.stale = true;
+}
+
+void stream_release(ydc_context* c) {
+  auto& sm = c->stream_mode;
+  stream_drop_graphs(sm);
+  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres})
+    if (h) (void)hipHostFree(h);
+  sm = ydc_context::Stream{};  // (frees the device buffers: ydc_stream_end discards W)
+}
+
+// Offset of the next 256 B aligned section of an arena that is `*off` bytes long so far.
+size_t section(size_t* off, size_t bytes) {
+  const size_t at = *off;
+  *off += (std::max<size_t>(bytes, 16) + 255) & ~(size_t)255;
+  return at;
 }
 
 // Requests one streaming batch places: the new ones, behind W's region in waiting mode.
 uint32_t stream_batch_n(const ydc_context::Stream& sm) { return sm.max_tasks + sm.max_waiting; }
 
-// Waiting mode: the tick's batch columns from W and the new requests (wait_queue.h). `in`: the
-// staged tick as the launch reads it (page-locked arena in place, or its device copy).
-void enqueue_wait_gather(ydc_context* c, const WaitNew& in) {
+// The tick's heartbeats and frees applied to the registry's device columns, from the arena as
+// `a` sees it (in place, or its device mirror).
+void enqueue_apply_tick(ydc_context* c, const TickArena& a) {
+  auto& sm = c->stream_mode;
+  if (!(sm.max_upd + sm.max_rel)) return;
+  const uint32_t upd_blocks = ceil_div(sm.max_upd, 256);
+  hipLaunchKernelGGL(k_apply_tick, dim3(upd_blocks + ceil_div(sm.max_rel, 256)), dim3(256), 0, c->stream,
+                     a.upd_idx, (ServantRowDev*)a.upd_rows, sm.max_upd, upd_blocks, a.rel, sm.max_rel,
+                     c->n_servants, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p, c->d_flags.p,
+                     c->d_running.p);
+}
+
+// Waiting mode: the tick's batch columns from W and the new requests (wait_queue.h), which the
+// launch reads from the arena as `a` sees it.
+void enqueue_wait_gather(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
   const uint32_t N = stream_batch_n(sm);
   YDC_LAUNCH(c, "k_wait_gather", k_wait_gather, dim3(ceil_div(std::max(N, sm.lookback_n), 256)), dim3(256), 0,
-             c->stream, sm.wq, sm.wt, in, sm.max_waiting, N, sm.ws, sm.lookback, sm.lookback_n);
+             c->stream, sm.wq, sm.wt, WaitNew{a.env, a.minv, a.ip, a.dl, a.tag, a.now}, sm.max_waiting, N, sm.ws,
+             sm.lookback, sm.lookback_n);
 }
 
 // ... and behind the batch: new W, resolved list, the new requests' answers. prm: gated on the
@@ -3870,19 +3899,12 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
   // No copy node. The tick's inputs are read where the host put them (k_apply_tick and the request
   // classification read every word once), the placement is stored to the page-locked result array
   // by k_finalize, and so is the outcome block (outcome_store=0: copied).
-  if (sm.max_upd + sm.max_rel) {
-    const uint32_t upd_blocks = ceil_div(sm.max_upd, 256);
-    hipLaunchKernelGGL(k_apply_tick, dim3(upd_blocks + ceil_div(sm.max_rel, 256)), dim3(256), 0, st,
-                       sm.z_upd_idx, sm.z_upd_rows, sm.max_upd, upd_blocks, sm.z_rel, sm.max_rel,
-                       c->n_servants, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p,
-                       c->d_flags.p, c->d_running.p);
-  }
+  enqueue_apply_tick(c, sm.z);
   // Waiting mode: the batch is W's region and the new requests, gathered into HBM; its placement
   // stays there for k_wait_compact, which answers the caller.
   const bool waiting = sm.max_waiting != 0;
-  if (waiting)
-    enqueue_wait_gather(c, WaitNew{sm.z_env, sm.z_minv, sm.z_ip, sm.z_dl, sm.z_tag, sm.z_now});
-  ydc_task_soa d{sm.z_env, sm.z_minv, sm.z_ip};
+  if (waiting) enqueue_wait_gather(c, sm.z);
+  ydc_task_soa d{sm.z.env, sm.z.minv, sm.z.ip};
   if (waiting) d = ydc_task_soa{sm.wt.env, sm.wt.minv, sm.wt.ip};
   if (rc == YDC_OK) rc = enqueue_front(c, plan, &d);
   if (rc == YDC_OK && plan.wave_path)
@@ -3897,7 +3919,7 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
     c->commit_by_swap = false;
     c->finalize_outcome = nullptr;
   }
-  if (rc == YDC_OK && waiting) enqueue_wait_compact(c, sm.z_now, c->d_prm.p, check_slot);
+  if (rc == YDC_OK && waiting) enqueue_wait_compact(c, sm.z.now, c->d_prm.p, check_slot);
   if (!outcome_stored) cap(hipMemcpyAsync(c->h_prm, c->d_prm.p, sizeof(DeviceParams), hipMemcpyDeviceToHost, st));
   return rc;
 }
@@ -3922,12 +3944,7 @@ int stream_capture_one(ydc_context* c, const BatchPlan& plan, bool by_swap, hipG
 
 int stream_capture(ydc_context* c) {
   auto& sm = c->stream_mode;
-  if (sm.exec) (void)hipGraphExecDestroy(sm.exec);
-  if (sm.graph) (void)hipGraphDestroy(sm.graph);
-  if (sm.exec_b) (void)hipGraphExecDestroy(sm.exec_b);
-  if (sm.graph_b) (void)hipGraphDestroy(sm.graph_b);
-  sm.exec = sm.exec_b = nullptr;
-  sm.graph = sm.graph_b = nullptr;
+  stream_drop_graphs(sm);
   const bool was_profiling = c->profiling;
   c->profiling = false;  // no event pairs inside a capture
   // Sizes and workspace first (allocations and table uploads cannot be captured).
@@ -3958,7 +3975,6 @@ int stream_capture(ydc_context* c) {
   c->profiling = was_profiling;
   if (rc != YDC_OK) return rc;
   sm.stale = false;
-  ++sm.recaptures;
   return YDC_OK;
 }
 
@@ -3985,75 +4001,44 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
   sm.max_upd = max_updates;
   sm.max_rel = max_releases;
   sm.max_tasks = max_tasks;
-  // Arena layout (256 B aligned sections).
+  // Arena layout (256 B aligned sections); waiting mode adds the new requests' deadlines and tags,
+  // and the tick's clock.
   size_t off = 0;
-  auto section = [&](size_t bytes) {
-    const size_t at = off;
-    off += (std::max<size_t>(bytes, 16) + 255) & ~(size_t)255;
-    return at;
+  const size_t o_idx = section(&off, (size_t)max_updates * 4);
+  const size_t o_rows = section(&off, (size_t)max_updates * sizeof(ydc_servant_row));
+  const size_t o_rel = section(&off, (size_t)max_releases * 4);
+  const size_t o_env = section(&off, (size_t)max_tasks * 4);
+  const size_t o_minv = section(&off, (size_t)max_tasks * 4);
+  const size_t o_ip = section(&off, (size_t)max_tasks * 4);
+  const size_t o_dl = max_waiting ? section(&off, (size_t)max_tasks * 8) : 0;
+  const size_t o_tag = max_waiting ? section(&off, (size_t)max_tasks * 8) : 0;
+  const size_t o_now = max_waiting ? section(&off, 8) : 0;
+  auto arena_at = [&](uint8_t* b) {
+    return TickArena{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
+                     (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
+                     max_waiting ? (int64_t*)(b + o_dl) : nullptr, max_waiting ? (uint64_t*)(b + o_tag) : nullptr,
+                     max_waiting ? (int64_t*)(b + o_now) : nullptr};
   };
-  const size_t o_idx = section((size_t)max_updates * 4);
-  const size_t o_rows = section((size_t)max_updates * sizeof(ydc_servant_row));
-  const size_t o_rel = section((size_t)max_releases * 4);
-  const size_t o_env = section((size_t)max_tasks * 4);
-  const size_t o_minv = section((size_t)max_tasks * 4);
-  const size_t o_ip = section((size_t)max_tasks * 4);
-  // Waiting mode: the new requests' deadlines and tags, and the tick's clock, in the same arena.
-  const size_t o_dl = max_waiting ? section((size_t)max_tasks * 8) : 0;
-  const size_t o_tag = max_waiting ? section((size_t)max_tasks * 8) : 0;
-  const size_t o_now = max_waiting ? section(8) : 0;
   sm.in_bytes = off;
   HIP_TRY(c, hipHostMalloc((void**)&sm.h_in, sm.in_bytes, hipHostMallocCoherent | hipHostMallocMapped));
   HIP_TRY(c, hipHostMalloc((void**)&sm.h_out, std::max<size_t>((size_t)max_tasks * 4, 16),
                            hipHostMallocCoherent | hipHostMallocMapped));
-  {
-    uint8_t* z_in = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&z_in, sm.h_in, 0));
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&sm.z_out, sm.h_out, 0));
-    sm.z_upd_idx = (uint32_t*)(z_in + o_idx);
-    sm.z_upd_rows = (ServantRowDev*)(z_in + o_rows);
-    sm.z_rel = (uint32_t*)(z_in + o_rel);
-    sm.z_env = (uint32_t*)(z_in + o_env);
-    sm.z_minv = (uint32_t*)(z_in + o_minv);
-    sm.z_ip = (uint32_t*)(z_in + o_ip);
-  }
+  uint8_t* z_in = nullptr;
+  HIP_TRY(c, hipHostGetDevicePointer((void**)&z_in, sm.h_in, 0));
+  HIP_TRY(c, hipHostGetDevicePointer((void**)&sm.z_out, sm.h_out, 0));
   HIP_TRY(c, sm.d_in.reserve(sm.in_bytes));
-  sm.h_upd_idx = (uint32_t*)(sm.h_in + o_idx);
-  sm.h_upd_rows = (ydc_servant_row*)(sm.h_in + o_rows);
-  sm.h_rel = (uint32_t*)(sm.h_in + o_rel);
-  sm.h_env = (uint32_t*)(sm.h_in + o_env);
-  sm.h_minv = (uint32_t*)(sm.h_in + o_minv);
-  sm.h_ip = (uint32_t*)(sm.h_in + o_ip);
-  sm.d_upd_idx = (uint32_t*)(sm.d_in.p + o_idx);
-  sm.d_upd_rows = (ServantRowDev*)(sm.d_in.p + o_rows);
-  sm.d_rel = (uint32_t*)(sm.d_in.p + o_rel);
-  sm.d_env = (uint32_t*)(sm.d_in.p + o_env);
-  sm.d_minv = (uint32_t*)(sm.d_in.p + o_minv);
-  sm.d_ip = (uint32_t*)(sm.d_in.p + o_ip);
+  sm.h = arena_at(sm.h_in);
+  sm.d = arena_at(sm.d_in.p);
+  sm.z = arena_at(z_in);
   HIP_TRY(c, c->d_out_idx.reserve(max_tasks));
   if (max_waiting) {
     sm.max_waiting = max_waiting;
-    uint8_t* z_in = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&z_in, sm.h_in, 0));
-    sm.h_dl = (int64_t*)(sm.h_in + o_dl);
-    sm.h_tag = (uint64_t*)(sm.h_in + o_tag);
-    sm.h_now = (int64_t*)(sm.h_in + o_now);
-    sm.d_dl = (int64_t*)(sm.d_in.p + o_dl);
-    sm.d_tag = (uint64_t*)(sm.d_in.p + o_tag);
-    sm.d_now = (int64_t*)(sm.d_in.p + o_now);
-    sm.z_dl = (int64_t*)(z_in + o_dl);
-    sm.z_tag = (uint64_t*)(z_in + o_tag);
-    sm.z_now = (int64_t*)(z_in + o_now);
     // HBM: W (max_waiting entries), the tick's batch (max_waiting + max_tasks) with its placement,
     // the queue's counters and k_wait_compact's look-back words.
     const size_t NB = (size_t)max_tasks + max_waiting;
     sm.lookback_n = (uint32_t)((NB + kWaitTile - 1) / kWaitTile);
     size_t w_off = 0;
-    auto wsec = [&](size_t bytes) {
-      const size_t at = w_off;
-      w_off += (std::max<size_t>(bytes, 16) + 255) & ~(size_t)255;
-      return at;
-    };
+    auto wsec = [&](size_t bytes) { return section(&w_off, bytes); };
     const size_t o_wq[5] = {wsec(max_waiting * 4ull), wsec(max_waiting * 4ull), wsec(max_waiting * 4ull),
                             wsec(max_waiting * 8ull), wsec(max_waiting * 8ull)};
     const size_t o_wt[5] = {wsec(NB * 4), wsec(NB * 4), wsec(NB * 4), wsec(NB * 8), wsec(NB * 8)};
@@ -4069,10 +4054,10 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     sm.lookback = (unsigned long long*)(b + o_lb);
     HIP_TRY(c, hipMemsetAsync(sm.ws, 0, sizeof(WaitState), c->stream));  // W empty
     // Page-locked results: resolved tags | resolved answers | outcome block.
-    const size_t r_tag = 0, r_idx = ((size_t)max_waiting * 8 + 255) & ~(size_t)255;
-    const size_t r_out = r_idx + (((size_t)max_waiting * 4 + 255) & ~(size_t)255);
-    HIP_TRY(c, hipHostMalloc((void**)&sm.h_wres, r_out + sizeof(WaitOutcome),
-                             hipHostMallocCoherent | hipHostMallocMapped));
+    size_t r_off = 0;
+    const size_t r_tag = section(&r_off, (size_t)max_waiting * 8), r_idx = section(&r_off, (size_t)max_waiting * 4);
+    const size_t r_out = section(&r_off, sizeof(WaitOutcome));
+    HIP_TRY(c, hipHostMalloc((void**)&sm.h_wres, r_off, hipHostMallocCoherent | hipHostMallocMapped));
     uint8_t* z_res = nullptr;
     HIP_TRY(c, hipHostGetDevicePointer((void**)&z_res, sm.h_wres, 0));
     sm.h_res_tag = (uint64_t*)(sm.h_wres + r_tag);
@@ -4125,12 +4110,12 @@ int ydc_stream_waiting_take(ydc_context* c, uint64_t* out_tags, uint32_t cap, ui
 int ydc_stream_buffers_get(ydc_context* c, ydc_stream_buffers* out) {
   if (!c || !out || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  out->upd_idx = sm.h_upd_idx;
-  out->upd_rows = sm.h_upd_rows;
-  out->release_servant_idx = sm.h_rel;
-  out->env_id = sm.h_env;
-  out->min_version = sm.h_minv;
-  out->requestor_ip = sm.h_ip;
+  out->upd_idx = sm.h.upd_idx;
+  out->upd_rows = sm.h.upd_rows;
+  out->release_servant_idx = sm.h.rel;
+  out->env_id = sm.h.env;
+  out->min_version = sm.h.minv;
+  out->requestor_ip = sm.h.ip;
   out->out_servant_idx = sm.h_out;
   return YDC_OK;
 }
@@ -4172,6 +4157,37 @@ static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tas
   c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_waiting - live);
   sm.n_waiting = n_wait;
   sm.last_now = wt->now;
+  return YDC_OK;
+}
+
+// After a placement the host ran itself: the answers into the page-locked result array — in
+// waiting mode by k_wait_compact (ungated), otherwise by a copy. `now`: the tick's clock where
+// the step read it. That is the device mirror (d.now) when the tick copied the arena there, and
+// the page-locked arena in place (z.now) when it did not: the mirror then still holds an older
+// tick's clock.
+static int stream_answer_eager(ydc_context* c, const int64_t* now) {
+  auto& sm = c->stream_mode;
+  if (sm.max_waiting) {
+    enqueue_wait_compact(c, now, nullptr, kNone);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+  } else {
+    HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
+  }
+  return YDC_OK;
+}
+
+// The end of every tick: the statistics of the placement (p, rounds) without the padding, waiting
+// mode's resolved list, the answers to the caller.
+static int stream_tick_finish(ydc_context* c, const BatchPlan& p, uint32_t rounds, uint32_t n_tasks,
+                              uint32_t* out_servant_idx, const WaitTick* wt) {
+  auto& sm = c->stream_mode;
+  fill_stats(c, p, rounds);
+  c->stats.n_tasks = n_tasks;
+  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
+  if (wt)
+    if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
+  if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
   return YDC_OK;
 }
 
@@ -4219,27 +4235,8 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       if (upd_idx[i] >= c->n_servants)
         return fail(c, YDC_ERR_INVALID_ARGUMENT, "a tick that adds a servant to a table with %u mask "
                     "words needs its environments: use ydc_stream_tick_wide", EW);
-  for (uint32_t i = 0; i < n_upd && !structural; ++i) {
-    const uint32_t s = upd_idx[i];
-    if (s >= c->n_servants) {
-      structural = true;
-      break;
-    }
-    const ydc_servant_row& r = upd_rows[i];
-    bool env_changed = false;
-    if (upd_env_masks) {
-      for (uint32_t w = 0; w < std::max(EW, env_words); ++w) {
-        const uint64_t have = w < EW ? c->h_env[(size_t)s * EW + w] : 0;
-        const uint64_t want = w < env_words ? upd_env_masks[(size_t)i * env_words + w] : 0;
-        env_changed |= have != want;
-      }
-    } else if (EW == 1) {
-      env_changed = c->h_env[s] != r.env_mask;
-    }
-    structural = c->h_version[s] != r.version || env_changed ||
-                 c->h_ip[s] != r.ip_id || (c->h_max_tasks[s] == 0) != (r.max_tasks == 0) ||
-                 std::min(c->h_max_tasks[s], c->h_nproc[s]) != std::min(r.max_tasks, r.num_processors);
-  }
+  for (uint32_t i = 0; i < n_upd && !structural; ++i)
+    structural = row_is_structural(c, upd_idx[i], upd_rows[i], upd_env_masks, env_words, i);
   uint32_t graph_upd = n_upd;
   if (structural) {
     if (upd_env_masks) {
@@ -4256,81 +4253,55 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     }
     graph_upd = 0;
   } else {
-    for (uint32_t i = 0; i < n_upd; ++i) {
-      const uint32_t s = upd_idx[i];
-      const ydc_servant_row& r = upd_rows[i];
-      c->h_nproc[s] = r.num_processors;
-      c->h_load[s] = r.current_load;
-      c->h_max_tasks[s] = r.max_tasks;
-      c->h_flags[s] = r.flags;
-    }
+    mirror_rows(c, upd_idx, upd_rows, n_upd);
   }
   if (sm.stale || c->tables_dirty)
     if (int rc = stream_capture(c)) return rc;
   // Stage the tick (padding = no-ops).
   // (a caller that filled the arena itself — ydc_stream_buffers_get — has nothing to copy)
+  const TickArena& h = sm.h;
   if (graph_upd) {
-    if (upd_idx != sm.h_upd_idx) std::memcpy(sm.h_upd_idx, upd_idx, (size_t)graph_upd * 4);
-    if (upd_rows != sm.h_upd_rows) std::memcpy(sm.h_upd_rows, upd_rows, (size_t)graph_upd * sizeof(ydc_servant_row));
+    if (upd_idx != h.upd_idx) std::memcpy(h.upd_idx, upd_idx, (size_t)graph_upd * 4);
+    if (upd_rows != h.upd_rows) std::memcpy(h.upd_rows, upd_rows, (size_t)graph_upd * sizeof(ydc_servant_row));
   }
-  for (uint32_t i = graph_upd; i < sm.max_upd; ++i) sm.h_upd_idx[i] = 0xFFFFFFFFu;
-  if (n_rel && release_servant_idx != sm.h_rel) std::memcpy(sm.h_rel, release_servant_idx, (size_t)n_rel * 4);
-  for (uint32_t i = n_rel; i < sm.max_rel; ++i) sm.h_rel[i] = 0xFFFFFFFFu;
+  for (uint32_t i = graph_upd; i < sm.max_upd; ++i) h.upd_idx[i] = 0xFFFFFFFFu;
+  if (n_rel && release_servant_idx != h.rel) std::memcpy(h.rel, release_servant_idx, (size_t)n_rel * 4);
+  for (uint32_t i = n_rel; i < sm.max_rel; ++i) h.rel[i] = 0xFFFFFFFFu;
   if (n_tasks) {
-    if (tasks->env_id != sm.h_env) std::memcpy(sm.h_env, tasks->env_id, (size_t)n_tasks * 4);
-    if (tasks->min_version != sm.h_minv) std::memcpy(sm.h_minv, tasks->min_version, (size_t)n_tasks * 4);
-    if (tasks->requestor_ip != sm.h_ip) std::memcpy(sm.h_ip, tasks->requestor_ip, (size_t)n_tasks * 4);
+    if (tasks->env_id != h.env) std::memcpy(h.env, tasks->env_id, (size_t)n_tasks * 4);
+    if (tasks->min_version != h.minv) std::memcpy(h.minv, tasks->min_version, (size_t)n_tasks * 4);
+    if (tasks->requestor_ip != h.ip) std::memcpy(h.ip, tasks->requestor_ip, (size_t)n_tasks * 4);
   }
   for (uint32_t i = n_tasks; i < sm.max_tasks; ++i) {
-    sm.h_env[i] = 0xFFFFFFFFu;  // a digest nobody has: EnvironmentNotFound, consumes nothing
-    sm.h_minv[i] = 0;
-    sm.h_ip[i] = 0;
+    h.env[i] = 0xFFFFFFFFu;  // a digest nobody has: EnvironmentNotFound, consumes nothing
+    h.minv[i] = 0;
+    h.ip[i] = 0;
   }
   if (wt) {
-    if (n_tasks && wt->deadlines != sm.h_dl) std::memcpy(sm.h_dl, wt->deadlines, (size_t)n_tasks * 8);
-    if (n_tasks && wt->tags != sm.h_tag) std::memcpy(sm.h_tag, wt->tags, (size_t)n_tasks * 8);
-    *sm.h_now = wt->now;
+    if (n_tasks && wt->deadlines != h.dl) std::memcpy(h.dl, wt->deadlines, (size_t)n_tasks * 8);
+    if (n_tasks && wt->tags != h.tag) std::memcpy(h.tag, wt->tags, (size_t)n_tasks * 8);
+    *h.now = wt->now;
   }
-  // Waiting mode: the batch is W's region + the new requests in HBM (k_wait_gather), its placement
-  // goes to wt_out and k_wait_compact answers the caller.
+  // The ticks placed eagerly place this batch from the arena's device mirror. Waiting mode: the
+  // batch is W's region + the new requests in HBM (k_wait_gather), its placement goes to wt_out
+  // and k_wait_compact answers the caller.
   const ydc_task_soa batch_dev = wt ? ydc_task_soa{sm.wt.env, sm.wt.minv, sm.wt.ip}
-                                    : ydc_task_soa{sm.d_env, sm.d_minv, sm.d_ip};
+                                    : ydc_task_soa{sm.d.env, sm.d.minv, sm.d.ip};
   uint32_t* const batch_out = wt ? sm.wt_out : c->d_out_idx.p;
   const uint32_t NB = stream_batch_n(sm);
   if (sm.eager_only) {
-    // The same step, enqueued instead of replayed: staging copy, registry deltas, the batch with
-    // its host-checked rounds, COMMIT, results back.
-    ++sm.eager_fallbacks;
+    // The same step, enqueued instead of replayed: mirror the arena, apply, gather, place, answer.
+    // (> kMaxWaveClasses classes: the bin sort, which needs at most that many, is never planned,
+    // so place_batch never repeats the batch here)
     HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (sm.max_upd + sm.max_rel) {
-      const uint32_t upd_blocks = ceil_div(sm.max_upd, 256);
-      hipLaunchKernelGGL(k_apply_tick, dim3(upd_blocks + ceil_div(sm.max_rel, 256)), dim3(256), 0, c->stream,
-                         sm.d_upd_idx, sm.d_upd_rows, sm.max_upd, upd_blocks, sm.d_rel, sm.max_rel,
-                         c->n_servants, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p,
-                         c->d_flags.p, c->d_running.p);
-    }
-    if (wt) enqueue_wait_gather(c, WaitNew{sm.d_env, sm.d_minv, sm.d_ip, sm.d_dl, sm.d_tag, sm.d_now});
+    enqueue_apply_tick(c, sm.d);
+    if (wt) enqueue_wait_gather(c, sm.d);
     BatchPlan pe;
-    if (int rc = plan_batch(c, NB, &pe)) return rc;
-    ydc_task_soa d = batch_dev;
     uint32_t rounds_e = 0;
-    if (int rc = run_planned_batch(c, pe, &d, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &rounds_e))
+    if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &pe, &rounds_e))
       return rc;
-    if (wt) {
-      enqueue_wait_compact(c, sm.d_now, nullptr, kNone);
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      HIP_TRY(c, hipGetLastError());
-    } else {
-      HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
-    }
-    ++sm.ticks;
-    fill_stats(c, pe, rounds_e);
-    c->stats.n_tasks = n_tasks;
-    c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
-    if (wt)
-      if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
-    if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
-    return YDC_OK;
+    if (int rc = stream_answer_eager(c, sm.d.now)) return rc;
+    return stream_tick_finish(c, pe, rounds_e, n_tasks, out_servant_idx, wt);
   }
   const bool second = sm.swaps && c->d_running.p == sm.run_b;
   if (sm.swaps && !second && c->d_running.p != sm.run_a)
@@ -4347,7 +4318,6 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
-  ++sm.ticks;
   const BatchPlan& p = second ? sm.plan_b : sm.plan;
   // (a step that took effect left the registry's running_tasks in its output column)
   if (sm.swaps && !c->h_prm->overflow && !(p.binsort && c->h_prm->window_miss) &&
@@ -4357,48 +4327,27 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     return fail(c, YDC_ERR_CAPACITY, "slot workspace overflow (bound %u)", p.slot_bound);
   uint32_t rounds = sm.passes;
   if (p.binsort && c->h_prm->window_miss) {
-    // A bin of the bin sort overflowed (bin_sort.h): the tick's registry deltas are applied,
-    // its batch was gated out. Place it eagerly with the radix sort; the step is captured
-    // again, without the bin sort, on the next tick.
-    ++sm.eager_fallbacks;
-    BatchPlan p2;
-    if (int rc = fall_back_to_radix(c, NB, &p2)) return rc;
+    // A bin of the bin sort overflowed (bin_sort.h): the tick's registry deltas are applied, its
+    // batch was gated out. Place it eagerly with the radix sort; the step is captured again,
+    // without the bin sort, on the next tick.
+    note_bin_overflow(c);
     // (the captured step read the arena in place: the device copy is stale; in waiting mode the
     // gathered batch in HBM is what is placed again, and W is still as the gather read it)
     HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
-    ydc_task_soa d = batch_dev;
-    if (int rc = run_planned_batch(c, p2, &d, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &rounds))
+    BatchPlan p2;
+    if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &p2, &rounds))
       return rc;
-    if (wt) {
-      enqueue_wait_compact(c, sm.d_now, nullptr, kNone);
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      HIP_TRY(c, hipGetLastError());
-    } else {
-      HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
-    }
-    fill_stats(c, p2, rounds);
-    c->stats.n_tasks = n_tasks;
-    c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
-    if (wt)
-      if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
-    if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
-    return YDC_OK;
+    if (int rc = stream_answer_eager(c, sm.d.now)) return rc;
+    return stream_tick_finish(c, p2, rounds, n_tasks, out_servant_idx, wt);
   }
   if (p.wave_path) {
     if (c->h_prm->n_changed[(sm.passes - 1) & 63] != 0) {
       // The captured passes were not enough (rare): finish eagerly and capture a longer
       // step next time.
-      ++sm.eager_fallbacks;
       if (int rc = run_passes_until_consistent(c, p, sm.passes, YDC_DISPATCH_COMMIT, batch_out,
                                                nullptr, nullptr, &rounds))
         return rc;
-      if (wt) {
-        enqueue_wait_compact(c, sm.z_now, nullptr, kNone);
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipGetLastError());
-      } else {
-        HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
-      }
+      if (int rc = stream_answer_eager(c, sm.z.now)) return rc;
       c->round_hint = rounds;
       sm.want_passes = std::min(rounds + 1, 12u);
       sm.stale = true;
@@ -4418,13 +4367,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       }
     }
   }
-  fill_stats(c, p, rounds);
-  c->stats.n_tasks = n_tasks;
-  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
-  if (wt)
-    if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
-  if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
-  return YDC_OK;
+  return stream_tick_finish(c, p, rounds, n_tasks, out_servant_idx, wt);
 }
 
 int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
