@@ -117,6 +117,9 @@ typedef struct ydc_stats {
    * by a launched tick kernel, and batches placed by the batch pipeline */
   uint32_t tick_resident_calls, tick_launched_calls, pipeline_batches;
   float stage_ms[16];      /* per-stage GPU time when profiling is on (ydc_set_profiling) */
+  /* of the most recent ydc_stream_tick_leased: leases that became zombies, zombies freed by a
+   * servant's report, leases freed by id, renewals answered 0 */
+  uint32_t leases_expired, leases_swept, leases_freed, renewals_refused;
 } ydc_stats;
 
 /* stage indices of ydc_stats::stage_ms */
@@ -131,7 +134,7 @@ enum {
 
 const char* ydc_strerror(int code);
 const char* ydc_last_error(const ydc_context* ctx); /* ctx == NULL: last error outside a context */
-#define YDC_ABI_VERSION 7u
+#define YDC_ABI_VERSION 8u
 uint32_t ydc_abi_version(void); /* YDC_ABI_VERSION */
 
 /* Number of usable devices (0 if the HIP runtime cannot see one). */
@@ -288,7 +291,8 @@ typedef struct ydc_stream_buffers {
   uint32_t* out_servant_idx;
 } ydc_stream_buffers;
 int ydc_stream_buffers_get(ydc_context* ctx, ydc_stream_buffers* out);
-/* Discards the waiting queue of a context begun with ydc_stream_begin_waiting. */
+/* Discards the waiting queue of a context begun with ydc_stream_begin_waiting and the lease table
+ * of one begun with ydc_stream_begin_leased. */
 int ydc_stream_end(ydc_context* ctx);
 
 /* ---- streaming with a waiting queue --------------------------------------------
@@ -336,6 +340,59 @@ int ydc_stream_tick_waiting(ydc_context* ctx, const uint32_t* upd_idx, const ydc
 /* Empties W and hands over its tags in queue order (*out_n of them), for a host that shuts down or
  * answers the waiters itself. More than cap waiting: YDC_ERR_CAPACITY, *out_n = |W|, W kept. */
 int ydc_stream_waiting_take(ydc_context* ctx, uint64_t* out_tags, uint32_t cap, uint32_t* out_n);
+
+/* ---- streaming with leases ---------------------------------------------------------
+ * The reference remembers every grant in tasks_: a task id from next_task_id, the servant,
+ * expires_at, the zombie flag (task_dispatcher.cc:127-135). A leased context keeps that table L
+ * (at most max_leases entries) and the counter next_id on the device, both reset by
+ * ydc_stream_begin_leased; next_id starts at 0. Clock values are int64 in any monotonic unit.
+ * One tick with clock value now applies, in this order, each step as the named reference calls
+ * made one after another in array order:
+ *   1. the heartbeats, exactly as ydc_stream_tick_wide (upd_env_masks nullable);
+ *   2. renewals (renew_task_id[i], renew_expires_at[i]) = KeepTaskAlive (:142-167): an unknown id
+ *      (never granted, already freed, >= next_id) or a zombie: out_renewed[i] = 0 and nothing
+ *      changes; otherwise expires_at = renew_expires_at[i], out_renewed[i] = 1. An overdue lease
+ *      that is not a zombie yet is renewed; the zombie flag is stored, never derived from the clock;
+ *   3. free_task_id[i] = one FreeTask each (:169-188): unknown id: ignored; known id, zombie or
+ *      not: the servant's running_tasks - 1 and the lease erased (the same id again: unknown);
+ *   4. release_servant_idx as in ydc_stream_tick (slots the caller tracks itself; no lease touched);
+ *   5. expiry = the task loop of OnExpirationTimer (:522-535): every lease with expires_at < now
+ *      becomes a zombie and keeps its slot;
+ *   6. servant reports in CSR form = NotifyServantRunningTasks (:225-275) per reporting servant,
+ *      a servant at most once per tick: report r is servant report_servant_idx[r] listing
+ *      report_task_id[report_off[r] .. report_off[r + 1]). Every zombie of that servant whose id is
+ *      not listed is freed (running_tasks - 1, lease erased); out_report_unknown[k] = 1 unless
+ *      report_task_id[k] is a non-zombie lease of that very servant. Servants that do not report
+ *      keep their zombies;
+ *   7. the requests, placed and committed as one batch exactly as ydc_stream_tick; each grant, in
+ *      array order, takes the next id: out_task_id[i] = next_id++ (undefined where
+ *      out_servant_idx[i] is no servant), expires_at = lease_expires_at[i], not a zombie.
+ * *out_n_leases = |L| afterwards, zombies included. Refused with nothing applied: |L| (the
+ * previous tick's *out_n_leases) + n_tasks > max_leases and counts above the capacities given at
+ * begin (YDC_ERR_CAPACITY); now before the previous tick's now, a servant twice in
+ * report_servant_idx or one the registry does not have, a report_off that decreases
+ * (YDC_ERR_INVALID_ARGUMENT). ydc_stream_tick / _wide / _waiting on a leased context, and this
+ * call on any other, are YDC_ERR_INVALID_ARGUMENT. ydc_remove_servants while the stream is open
+ * drops the leases of the removed rows (UnsafeSweepOrphans, :478-496) and renumbers the others'
+ * servants with the registry. All of it runs inside the captured step; plain and waiting contexts
+ * are not affected. ydc_get_stats().leases_* / renewals_refused count the tick's events. */
+int ydc_stream_begin_leased(ydc_context* ctx, uint32_t max_updates, uint32_t max_releases,
+                            uint32_t max_tasks, uint32_t max_leases, uint32_t max_renewals,
+                            uint32_t max_frees, uint32_t max_reports, uint32_t max_report_ids);
+int ydc_stream_tick_leased(ydc_context* ctx, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                           const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                           const uint32_t* release_servant_idx, uint32_t n_rel,
+                           const uint64_t* renew_task_id, const int64_t* renew_expires_at, uint32_t n_renew,
+                           const uint64_t* free_task_id, uint32_t n_free,
+                           const uint32_t* report_servant_idx, const uint32_t* report_off,
+                           const uint64_t* report_task_id, uint32_t n_rep,
+                           const ydc_task_soa* tasks, const int64_t* lease_expires_at, uint32_t n_tasks,
+                           int64_t now, uint32_t* out_servant_idx, uint64_t* out_task_id,
+                           uint8_t* out_renewed, uint8_t* out_report_unknown, uint32_t* out_n_leases);
+/* Snapshot of L in id order (tests, DumpInternals, shutdown): *out_n leases; more than cap:
+ * YDC_ERR_CAPACITY with *out_n = |L| and nothing written. */
+int ydc_stream_leases_get(ydc_context* ctx, uint64_t* out_task_id, uint32_t* out_servant_idx,
+                          int64_t* out_expires_at, uint8_t* out_zombie, uint32_t cap, uint32_t* out_n);
 
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.

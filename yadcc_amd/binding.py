@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (YDC_LIB: a measurement build of the same library, e.g. libydc_probe.so — tools/phase_probe.py)
 LIB_PATH = os.environ.get("YDC_LIB") or os.path.join(_HERE, "libydc.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 IPC_HANDLE_BYTES = 256
 TRANSPORT_NONE, TRANSPORT_RCCL, TRANSPORT_LOCAL, TRANSPORT_IPC_DEVICE, TRANSPORT_IPC_HOST = range(5)
 TRANSPORT_NAMES = ("none", "rccl", "local", "ipc", "ipc-host")
@@ -36,6 +36,7 @@ ABI_SYMBOLS = (
     "ydc_host_register", "ydc_host_unregister", "ydc_host_alloc", "ydc_host_free",
     "ydc_stream_begin", "ydc_stream_tick", "ydc_stream_tick_wide", "ydc_stream_buffers_get", "ydc_stream_end",
     "ydc_stream_begin_waiting", "ydc_stream_tick_waiting", "ydc_stream_waiting_take",
+    "ydc_stream_begin_leased", "ydc_stream_tick_leased", "ydc_stream_leases_get",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -76,7 +77,8 @@ class Stats(C.Structure):
         "rounds", "chunk_sims", "granted", "timeouts", "env_not_found", "shard_sort_batches",
         "shard_sort_misses", "small_batch", "zone_rows", "tick_resident_calls", "tick_launched_calls",
         "pipeline_batches")] + [
-            ("stage_ms", C.c_float * 16)]
+            ("stage_ms", C.c_float * 16)] + [(k, C.c_uint32) for k in (
+                "leases_expired", "leases_swept", "leases_freed", "renewals_refused")]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "stage_ms"}
@@ -142,6 +144,17 @@ def lib():
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32)]
         L.ydc_stream_waiting_take.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.ydc_stream_begin_leased.argtypes = [C.c_void_p] + [C.c_uint32] * 8
+        L.ydc_stream_tick_leased.argtypes = [
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,  # heartbeats
+            C.c_void_p, C.c_uint32,                                                  # releases by servant
+            C.c_void_p, C.c_void_p, C.c_uint32,                                      # renewals
+            C.c_void_p, C.c_uint32,                                                  # frees by id
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,                          # reports (CSR)
+            C.POINTER(TaskSoA), C.c_void_p, C.c_uint32, C.c_int64,                   # requests, clock
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.ydc_stream_leases_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint32, C.POINTER(C.c_uint32)]
         L.ydc_group_unique_id.argtypes = [C.c_void_p]
         L.ydc_group_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ydc_group_init_local.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -584,6 +597,75 @@ class Context:
             C.byref(n_wait)), "ydc_stream_tick_waiting")
         k = n_res.value
         return out, res_tags[:k].copy(), res_idx[:k].copy(), int(n_wait.value)
+
+    def stream_begin_leased(self, max_updates, max_releases, max_tasks, max_leases, max_renewals,
+                            max_frees, max_reports, max_report_ids):
+        """Leased mode (ydc_stream_begin_leased): the context remembers every grant in a lease table
+        on the device (task id, servant, expiry, zombie flag); ticks go through stream_tick_leased."""
+        self._check(lib().ydc_stream_begin_leased(self._h, max_updates, max_releases, max_tasks, max_leases,
+                                                  max_renewals, max_frees, max_reports, max_report_ids),
+                    "ydc_stream_begin_leased")
+        self._stream_caps = (int(max_updates), int(max_releases), int(max_tasks))
+        self._max_waiting = 0
+        self._max_leases = int(max_leases)
+
+    def stream_tick_leased(self, upd_idx, upd_rows, release_idx, renew_ids, renew_expires_at, free_ids,
+                           report_servants, report_off, report_ids, tasks, lease_expires_at, now,
+                           env_masks=None):
+        """One tick of a context begun with stream_begin_leased (ydc_stream_tick_leased): heartbeats,
+        renewals (uint64 ids, int64 new expiries), frees by id, releases by servant index, expiry at
+        clock `now`, servant reports in CSR form (report_off has len(report_servants) + 1 entries),
+        then the requests with their per-request lease_expires_at. Returns (out, task_ids, renewed,
+        report_unknown, n_leases): out[i] as stream_tick, task_ids[i] the grant's id (only where
+        out[i] is a servant), renewed[i] / report_unknown[k] as uint8 flags, n_leases = |L| afterwards."""
+        ui = np.ascontiguousarray(upd_idx, dtype=np.uint32)
+        if len(ui):
+            self.n_servants = max(self.n_servants, int(ui.max()) + 1)
+        ur = np.ascontiguousarray(upd_rows, dtype=ROW_DTYPE)
+        rel = np.ascontiguousarray(release_idx, dtype=np.uint32)
+        rid = np.ascontiguousarray(renew_ids, dtype=np.uint64)
+        rex = np.ascontiguousarray(renew_expires_at, dtype=np.int64)
+        fid = np.ascontiguousarray(free_ids, dtype=np.uint64)
+        rs = np.ascontiguousarray(report_servants, dtype=np.uint32)
+        ro = np.ascontiguousarray(report_off, dtype=np.uint32)
+        ri = np.ascontiguousarray(report_ids, dtype=np.uint64)
+        assert len(rid) == len(rex) and (len(rs) == 0 or len(ro) == len(rs) + 1)
+        assert len(rs) == 0 or int(ro[-1]) == len(ri)
+        keep = [np.ascontiguousarray(tasks[k], dtype=np.uint32)
+                for k in ("env_id", "min_version", "requestor_ip")]
+        n = len(keep[0])
+        lex = np.ascontiguousarray(lease_expires_at, dtype=np.int64)
+        assert len(lex) == n
+        soa = TaskSoA(*[a.ctypes.data for a in keep])
+        out = np.empty(n, np.uint32)
+        ids = np.empty(n, np.uint64)
+        renewed = np.zeros(len(rid), np.uint8)
+        unknown = np.zeros(len(ri), np.uint8)
+        n_leases = C.c_uint32(0)
+        if env_masks is None:
+            em, words = None, 1
+        else:
+            em = np.ascontiguousarray(env_masks, dtype=np.uint64).reshape(len(ui), -1)
+            words = em.shape[1]
+        self._check(lib().ydc_stream_tick_leased(
+            self._h, ui.ctypes.data, ur.ctypes.data, None if em is None else em.ctypes.data, words, len(ui),
+            rel.ctypes.data, len(rel), rid.ctypes.data, rex.ctypes.data, len(rid), fid.ctypes.data, len(fid),
+            rs.ctypes.data, ro.ctypes.data, ri.ctypes.data, len(rs), C.byref(soa), lex.ctypes.data, n, int(now),
+            out.ctypes.data, ids.ctypes.data, renewed.ctypes.data, unknown.ctypes.data, C.byref(n_leases)),
+            "ydc_stream_tick_leased")
+        return out, ids, renewed, unknown, int(n_leases.value)
+
+    def stream_leases(self):
+        """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,
+        servant_idx uint32, expires_at int64, zombie uint8)."""
+        cap = max(self._max_leases, 1)
+        ids, srv = np.empty(cap, np.uint64), np.empty(cap, np.uint32)
+        exp, zom = np.empty(cap, np.int64), np.empty(cap, np.uint8)
+        n = C.c_uint32(0)
+        self._check(lib().ydc_stream_leases_get(self._h, ids.ctypes.data, srv.ctypes.data, exp.ctypes.data,
+                                                zom.ctypes.data, cap, C.byref(n)), "ydc_stream_leases_get")
+        k = n.value
+        return ids[:k].copy(), srv[:k].copy(), exp[:k].copy(), zom[:k].copy()
 
     def stream_waiting_take(self):
         """Empties the waiting queue; returns its tags in queue order (ydc_stream_waiting_take)."""

@@ -24,6 +24,7 @@
 #include "host_tables.h"
 #include "kernels.h"
 #include "wait_queue.h"
+#include "lease_table.h"
 #include "tick_kernel.h"
 
 using namespace ydc;
@@ -105,7 +106,9 @@ struct BatchPlan {
 
 // The sections of a streaming tick's staging arena (stream_begin lays them out): heartbeat
 // indexes and rows, released slots, the three request columns and, in waiting mode, the new
-// requests' deadlines and tags and the tick's clock (NULL in a plain context).
+// requests' deadlines and tags and the tick's clock (NULL in a plain context); in leased mode the
+// requests' lease expiries, the renewals, the frees by id, the servant reports (CSR) and the
+// tick's scalars (NULL in any other context).
 struct TickArena {
   uint32_t* upd_idx;
   ydc_servant_row* upd_rows;
@@ -114,6 +117,13 @@ struct TickArena {
   int64_t* dl;
   uint64_t* tag;
   int64_t* now;
+  int64_t* lexp;
+  unsigned long long* ren_id;
+  int64_t* ren_exp;
+  unsigned long long* free_id;
+  uint32_t *rep_srv, *rep_off;
+  unsigned long long* rep_id;
+  LeaseHdr* lh;
 };
 }  // namespace
 
@@ -273,6 +283,24 @@ struct ydc_context {
     uint64_t *h_res_tag = nullptr, *z_res_tag = nullptr;
     uint32_t *h_res_idx = nullptr, *z_res_idx = nullptr;
     WaitOutcome *h_wout = nullptr, *z_wout = nullptr;
+    // Leased mode (ydc_stream_begin_leased; lease_table.h): the lease table L in HBM, the placement
+    // of the tick's batch in front of k_lease_grant, and the page-locked results. max_leases == 0:
+    // not a leased context (none of this exists). lookback / lookback_n above serve k_lease_grant.
+    uint32_t max_leases = 0, max_renew = 0, max_free = 0, max_rep = 0, max_rep_ids = 0;
+    uint32_t n_leases = 0;    // |L| after the last tick (the outcome block's, kept here)
+    uint32_t lease_tick = 0;  // number of the last tick that was staged
+    DevBuf<uint8_t> d_lease;
+    LeaseCols lt{};
+    LeaseState* ls = nullptr;
+    uint32_t* ren_slot = nullptr;
+    uint32_t* lt_out = nullptr;     // placement of the batch (k_finalize -> k_lease_grant)
+    DevBuf<uint32_t> d_rep_tick;    // per servant: the last tick it reported in
+    uint8_t* h_lres = nullptr;      // page-locked: task ids | renewed | report_unknown | outcome
+    unsigned long long *h_task_id = nullptr, *z_task_id = nullptr;
+    uint8_t *h_renewed = nullptr, *z_renewed = nullptr, *h_unknown = nullptr, *z_unknown = nullptr;
+    LeaseOutcome *h_lout = nullptr, *z_lout = nullptr;
+    std::vector<uint32_t> rep_seen;  // per servant: rep_mark of the last report list that named it (host check)
+    uint32_t rep_mark = 0;
   } stream_mode;
   DevBuf<ClassRun> d_runs;
   DevBuf<uint8_t> d_dirty;
@@ -1070,8 +1098,16 @@ int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
                    c->d_spare[5].p}};
   hipLaunchKernelGGL(k_compact_rows, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, in, out,
                      c->d_upd_idx.p, n, S);
+  // A leased stream: the leases of the removed rows vanish (UnsafeSweepOrphans), the others follow
+  // the compaction.
+  auto& sm = c->stream_mode;
+  const bool leased = sm.active && sm.max_leases;
+  if (leased)
+    hipLaunchKernelGGL(k_lease_remap, dim3(ceil_div(sm.lt.mask + 1, 256)), dim3(256), 0, c->stream, sm.lt, sm.ls,
+                       c->d_upd_idx.p, n);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (idx is pageable; the swap below retires the old columns)
+  if (leased) HIP_TRY(c, hipMemcpy(&sm.n_leases, &sm.ls->n_leases, 4, hipMemcpyDeviceToHost));
   DevBuf<uint32_t>* cols[6] = {&c->d_version, &c->d_nproc, &c->d_load, &c->d_max_tasks, &c->d_running,
                                &c->d_flags};
   for (int k = 0; k < 6; ++k) std::swap(*cols[k], c->d_spare[k]);
@@ -3840,7 +3876,7 @@ void stream_drop_graphs(ydc_context::Stream& sm) {
 void stream_release(ydc_context* c) {
   auto& sm = c->stream_mode;
   stream_drop_graphs(sm);
-  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres})
+  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres})
     if (h) (void)hipHostFree(h);
   sm = ydc_context::Stream{};  // (frees the device buffers: ydc_stream_end discards W)
 }
@@ -3887,6 +3923,40 @@ void enqueue_wait_compact(ydc_context* c, const int64_t* now, const DeviceParams
              sm.z_res_idx, sm.z_wout, prm, check_slot);
 }
 
+LeaseIn lease_in(const TickArena& a) {
+  return LeaseIn{a.lh, a.ren_id, a.ren_exp, a.free_id, a.rep_srv, a.rep_off, a.rep_id, a.lexp};
+}
+
+// Leased mode, in front of the batch: renewals, frees by id, report marks, expiry + sweep
+// (lease_table.h), reading the tick from the arena as `a` sees it.
+void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
+  auto& sm = c->stream_mode;
+  const LeaseIn in = lease_in(a);
+  const uint32_t S = c->n_servants;
+  const uint32_t ren_blocks = ceil_div(sm.max_renew, 256), rep_blocks = ceil_div(sm.max_rep, 256);
+  YDC_LAUNCH(c, "k_lease_renew", k_lease_renew, dim3(std::max(1u, ceil_div(std::max(sm.max_renew, sm.lookback_n), 256))),
+             dim3(256), 0, c->stream, sm.lt, sm.ls, in, sm.max_renew, sm.ren_slot, sm.z_renewed, sm.lookback,
+             sm.lookback_n);
+  if (sm.max_renew + sm.max_free)
+    YDC_LAUNCH(c, "k_lease_free", k_lease_free, dim3(ren_blocks + ceil_div(sm.max_free, 256)), dim3(256), 0, c->stream,
+               sm.lt, sm.ls, in, sm.max_renew, ren_blocks, sm.ren_slot, sm.max_free, S, c->d_running.p);
+  if (sm.max_rep)
+    YDC_LAUNCH(c, "k_lease_report", k_lease_report, dim3(rep_blocks + ceil_div(sm.max_rep_ids, 256)), dim3(256), 0,
+               c->stream, sm.lt, sm.ls, in, sm.max_rep, rep_blocks, sm.max_rep_ids, S, sm.d_rep_tick.p,
+               sm.z_unknown);
+  YDC_LAUNCH(c, "k_lease_sweep", k_lease_sweep, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
+             sm.lt, sm.ls, a.lh, S, sm.d_rep_tick.p, c->d_running.p);
+}
+
+// ... and behind the batch: ids for the grants, their leases, the answers, the outcome block. prm:
+// gated on the batch having become final (the captured step); NULL: the host has just placed it.
+void enqueue_lease_grant(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
+  auto& sm = c->stream_mode;
+  YDC_LAUNCH(c, "k_lease_grant", k_lease_grant, dim3(ceil_div(sm.max_tasks, kLeaseTile)), dim3(256), 0, c->stream,
+             sm.lt_out, sm.max_tasks, a.lexp, a.lh, sm.lt, sm.ls, sm.lookback, sm.z_out, sm.z_task_id, sm.z_lout,
+             prm, check_slot);
+}
+
 // The step itself, enqueued on the context's stream (inside a capture, or — stream_graph=0 — as it is).
 int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
   auto& sm = c->stream_mode;
@@ -3899,6 +3969,11 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
   // No copy node. The tick's inputs are read where the host put them (k_apply_tick and the request
   // classification read every word once), the placement is stored to the page-locked result array
   // by k_finalize, and so is the outcome block (outcome_store=0: copied).
+  // Leased mode: the lease kernels of the tick's renewals, frees, reports and expiry come first
+  // (their decrements of running_tasks and k_apply_tick's commute); the placement stays in HBM
+  // for k_lease_grant, which answers the caller.
+  const bool leased = sm.max_leases != 0;
+  if (leased) enqueue_lease_pre(c, sm.z);
   enqueue_apply_tick(c, sm.z);
   // Waiting mode: the batch is W's region and the new requests, gathered into HBM; its placement
   // stays there for k_wait_compact, which answers the caller.
@@ -3914,12 +3989,13 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
   if (rc == YDC_OK) {
     c->finalize_outcome = outcome_stored ? c->d_h_prm : nullptr;
     c->commit_by_swap = by_swap;
-    rc = enqueue_finalize(c, plan, YDC_DISPATCH_COMMIT, waiting ? sm.wt_out : sm.z_out, nullptr, nullptr,
-                          check_slot);
+    rc = enqueue_finalize(c, plan, YDC_DISPATCH_COMMIT, waiting ? sm.wt_out : leased ? sm.lt_out : sm.z_out,
+                          nullptr, nullptr, check_slot);
     c->commit_by_swap = false;
     c->finalize_outcome = nullptr;
   }
   if (rc == YDC_OK && waiting) enqueue_wait_compact(c, sm.z.now, c->d_prm.p, check_slot);
+  if (rc == YDC_OK && leased) enqueue_lease_grant(c, sm.z, c->d_prm.p, check_slot);
   if (!outcome_stored) cap(hipMemcpyAsync(c->h_prm, c->d_prm.p, sizeof(DeviceParams), hipMemcpyDeviceToHost, st));
   return rc;
 }
@@ -3948,6 +4024,12 @@ int stream_capture(ydc_context* c) {
   const bool was_profiling = c->profiling;
   c->profiling = false;  // no event pairs inside a capture
   // Sizes and workspace first (allocations and table uploads cannot be captured).
+  if (sm.max_leases && sm.d_rep_tick.cap < c->n_servants) {
+    // (a tick number is never 0, and a servant's stamp matters within its tick only)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, sm.d_rep_tick.reserve((size_t)c->n_servants + 1024));
+    HIP_TRY(c, hipMemset(sm.d_rep_tick.p, 0, sm.d_rep_tick.cap * 4));
+  }
   if (int rc = plan_batch(c, stream_batch_n(sm), &sm.plan)) return rc;
   if (sm.plan.use_generic) {
     // More than 256 servant classes: the rounds of that path are checked by the host, which a
@@ -3989,9 +4071,33 @@ struct WaitTick {
   uint32_t* out_n_waiting;
 };
 
+// A leased tick's own arguments (ydc_stream_tick_leased).
+struct LeaseTick {
+  const uint64_t* renew_id;
+  const int64_t* renew_exp;
+  uint32_t n_renew;
+  const uint64_t* free_id;
+  uint32_t n_free;
+  const uint32_t *rep_srv, *rep_off;
+  const uint64_t* rep_id;
+  uint32_t n_rep;
+  const int64_t* lease_exp;
+  int64_t now;
+  uint64_t* out_task_id;
+  uint8_t *out_renewed, *out_unknown;
+  uint32_t* out_n_leases;
+};
+
+// Capacities of a leased context (ydc_stream_begin_leased).
+struct LeaseCaps {
+  uint32_t max_leases, max_renew, max_free, max_rep, max_rep_ids;
+};
+
 int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
-                 uint32_t max_waiting) {
+                 uint32_t max_waiting, const LeaseCaps* lc = nullptr) {
   if (!c || !max_tasks) return YDC_ERR_INVALID_ARGUMENT;
+  if (lc && (!lc->max_leases || lc->max_leases > (1u << 30) || lc->max_rep_ids > 0x7FFFFFFFu))
+    return fail(c, YDC_ERR_CAPACITY, "max_leases %u out of range (1 .. 2^30)", lc->max_leases);
   if ((uint64_t)max_tasks + max_waiting > 0x7FFFFFFFull)
     return fail(c, YDC_ERR_CAPACITY, "max_tasks %u + max_waiting %u too large", max_tasks, max_waiting);
   HIP_TRY(c, hipSetDevice(c->device));
@@ -4013,11 +4119,31 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
   const size_t o_dl = max_waiting ? section(&off, (size_t)max_tasks * 8) : 0;
   const size_t o_tag = max_waiting ? section(&off, (size_t)max_tasks * 8) : 0;
   const size_t o_now = max_waiting ? section(&off, 8) : 0;
+  // ... leased mode the requests' expiries, renewals, frees by id, reports (CSR) and the scalars.
+  const size_t o_lexp = lc ? section(&off, (size_t)max_tasks * 8) : 0;
+  const size_t o_ren_id = lc ? section(&off, (size_t)lc->max_renew * 8) : 0;
+  const size_t o_ren_exp = lc ? section(&off, (size_t)lc->max_renew * 8) : 0;
+  const size_t o_free_id = lc ? section(&off, (size_t)lc->max_free * 8) : 0;
+  const size_t o_rep_srv = lc ? section(&off, (size_t)lc->max_rep * 4) : 0;
+  const size_t o_rep_off = lc ? section(&off, ((size_t)lc->max_rep + 1) * 4) : 0;
+  const size_t o_rep_id = lc ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
+  const size_t o_lh = lc ? section(&off, sizeof(LeaseHdr)) : 0;
   auto arena_at = [&](uint8_t* b) {
-    return TickArena{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
-                     (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
-                     max_waiting ? (int64_t*)(b + o_dl) : nullptr, max_waiting ? (uint64_t*)(b + o_tag) : nullptr,
-                     max_waiting ? (int64_t*)(b + o_now) : nullptr};
+    TickArena a{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
+                (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
+                max_waiting ? (int64_t*)(b + o_dl) : nullptr, max_waiting ? (uint64_t*)(b + o_tag) : nullptr,
+                max_waiting ? (int64_t*)(b + o_now) : nullptr};
+    if (lc) {
+      a.lexp = (int64_t*)(b + o_lexp);
+      a.ren_id = (unsigned long long*)(b + o_ren_id);
+      a.ren_exp = (int64_t*)(b + o_ren_exp);
+      a.free_id = (unsigned long long*)(b + o_free_id);
+      a.rep_srv = (uint32_t*)(b + o_rep_srv);
+      a.rep_off = (uint32_t*)(b + o_rep_off);
+      a.rep_id = (unsigned long long*)(b + o_rep_id);
+      a.lh = (LeaseHdr*)(b + o_lh);
+    }
+    return a;
   };
   sm.in_bytes = off;
   HIP_TRY(c, hipHostMalloc((void**)&sm.h_in, sm.in_bytes, hipHostMallocCoherent | hipHostMallocMapped));
@@ -4067,6 +4193,52 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     sm.z_res_idx = (uint32_t*)(z_res + r_idx);
     sm.z_wout = (WaitOutcome*)(z_res + r_out);
     std::memset(sm.h_wout, 0, sizeof(WaitOutcome));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (lc) {
+    sm.max_leases = lc->max_leases;
+    sm.max_renew = lc->max_renew;
+    sm.max_free = lc->max_free;
+    sm.max_rep = lc->max_rep;
+    sm.max_rep_ids = lc->max_rep_ids;
+    // HBM: the table (cap = 2^k >= 2 * max_leases slots, five columns), its bookkeeping, the
+    // renewals' slots, the placement of the tick's batch and k_lease_grant's look-back words.
+    size_t cap = 1024;
+    uint32_t cap_bits = 10;
+    while (cap < 2 * (size_t)lc->max_leases) cap <<= 1, ++cap_bits;
+    sm.lookback_n = ceil_div(max_tasks, kLeaseTile);
+    size_t l_off = 0;
+    auto lsec = [&](size_t bytes) { return section(&l_off, bytes); };
+    const size_t o_key = lsec(cap * 8), o_exp = lsec(cap * 8), o_srv = lsec(cap * 4), o_st = lsec(cap * 4);
+    const size_t o_win = lsec(cap * 4), o_ls = lsec(sizeof(LeaseState)), o_rs = lsec((size_t)lc->max_renew * 4);
+    const size_t o_out = lsec((size_t)max_tasks * 4), o_lb = lsec((size_t)sm.lookback_n * 8);
+    HIP_TRY(c, sm.d_lease.reserve(l_off));
+    uint8_t* b = sm.d_lease.p;
+    sm.lt = LeaseCols{(unsigned long long*)(b + o_key), (int64_t*)(b + o_exp), (uint32_t*)(b + o_srv),
+                      (uint32_t*)(b + o_st), (uint32_t*)(b + o_win), (uint32_t)(cap - 1), 64 - cap_bits};
+    sm.ls = (LeaseState*)(b + o_ls);
+    sm.ren_slot = (uint32_t*)(b + o_rs);
+    sm.lt_out = (uint32_t*)(b + o_out);
+    sm.lookback = (unsigned long long*)(b + o_lb);
+    // L empty, next_id 0 (the reference's next_task_id{}).
+    HIP_TRY(c, hipMemsetAsync(b, 0, l_off, c->stream));
+    HIP_TRY(c, hipMemsetAsync(sm.lt.key, 0xFF, cap * 8, c->stream));
+    // Page-locked results: task ids | renewed | report_unknown | outcome block.
+    size_t r_off = 0;
+    const size_t r_id = section(&r_off, (size_t)max_tasks * 8), r_ren = section(&r_off, lc->max_renew);
+    const size_t r_unk = section(&r_off, lc->max_rep_ids), r_out = section(&r_off, sizeof(LeaseOutcome));
+    HIP_TRY(c, hipHostMalloc((void**)&sm.h_lres, r_off, hipHostMallocCoherent | hipHostMallocMapped));
+    uint8_t* z_res = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&z_res, sm.h_lres, 0));
+    sm.h_task_id = (unsigned long long*)(sm.h_lres + r_id);
+    sm.h_renewed = sm.h_lres + r_ren;
+    sm.h_unknown = sm.h_lres + r_unk;
+    sm.h_lout = (LeaseOutcome*)(sm.h_lres + r_out);
+    sm.z_task_id = (unsigned long long*)(z_res + r_id);
+    sm.z_renewed = z_res + r_ren;
+    sm.z_unknown = z_res + r_unk;
+    sm.z_lout = (LeaseOutcome*)(z_res + r_out);
+    std::memset(sm.h_lout, 0, sizeof(LeaseOutcome));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
@@ -4160,15 +4332,41 @@ static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tas
   return YDC_OK;
 }
 
+// Leased mode, after the step: ids, renewal and report answers to the caller, the host's mirror
+// of |L| and the statistics.
+static int stream_lease_finish(ydc_context* c, const LeaseTick* lt, uint32_t n_tasks) {
+  auto& sm = c->stream_mode;
+  const LeaseOutcome& o = *sm.h_lout;
+  if (o.tick_no != sm.lease_tick || o.n_leases > sm.max_leases)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: outcome of tick %u (expected %u), %u leases of %u",
+                o.tick_no, sm.lease_tick, o.n_leases, sm.max_leases);
+  if (n_tasks) std::memcpy(lt->out_task_id, sm.h_task_id, (size_t)n_tasks * 8);
+  if (lt->n_renew) std::memcpy(lt->out_renewed, sm.h_renewed, lt->n_renew);
+  const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
+  if (n_ids) std::memcpy(lt->out_unknown, sm.h_unknown, n_ids);
+  *lt->out_n_leases = o.n_leases;
+  c->stats.leases_expired = o.expired;
+  c->stats.leases_swept = o.swept;
+  c->stats.leases_freed = o.freed;
+  c->stats.renewals_refused = o.renew_refused;
+  sm.n_leases = o.n_leases;
+  sm.last_now = lt->now;
+  return YDC_OK;
+}
+
 // After a placement the host ran itself: the answers into the page-locked result array — in
-// waiting mode by k_wait_compact (ungated), otherwise by a copy. `now`: the tick's clock where
-// the step read it. That is the device mirror (d.now) when the tick copied the arena there, and
-// the page-locked arena in place (z.now) when it did not: the mirror then still holds an older
+// waiting mode by k_wait_compact (ungated), otherwise by a copy. `a`: the arena where the step
+// read the tick's clock. That is the device mirror (d) when the tick copied the arena there, and
+// the page-locked arena in place (z) when it did not: the mirror then still holds an older
 // tick's clock.
-static int stream_answer_eager(ydc_context* c, const int64_t* now) {
+static int stream_answer_eager(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
   if (sm.max_waiting) {
-    enqueue_wait_compact(c, now, nullptr, kNone);
+    enqueue_wait_compact(c, a.now, nullptr, kNone);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+  } else if (sm.max_leases) {  // (leased mode: by k_lease_grant, ungated, with the ids and the leases)
+    enqueue_lease_grant(c, a, nullptr, kNone);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
   } else {
@@ -4180,13 +4378,15 @@ static int stream_answer_eager(ydc_context* c, const int64_t* now) {
 // The end of every tick: the statistics of the placement (p, rounds) without the padding, waiting
 // mode's resolved list, the answers to the caller.
 static int stream_tick_finish(ydc_context* c, const BatchPlan& p, uint32_t rounds, uint32_t n_tasks,
-                              uint32_t* out_servant_idx, const WaitTick* wt) {
+                              uint32_t* out_servant_idx, const WaitTick* wt, const LeaseTick* lt) {
   auto& sm = c->stream_mode;
   fill_stats(c, p, rounds);
   c->stats.n_tasks = n_tasks;
   c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
   if (wt)
     if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
+  if (lt)
+    if (int rc = stream_lease_finish(c, lt, n_tasks)) return rc;
   if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
   return YDC_OK;
 }
@@ -4194,9 +4394,15 @@ static int stream_tick_finish(ydc_context* c, const BatchPlan& p, uint32_t round
 static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
                        const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
                        const uint32_t* release_servant_idx, uint32_t n_rel, const ydc_task_soa* tasks,
-                       uint32_t n_tasks, uint32_t* out_servant_idx, const WaitTick* wt) {
+                       uint32_t n_tasks, uint32_t* out_servant_idx, const WaitTick* wt,
+                       const LeaseTick* lt = nullptr) {
   if (!c || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
+  if (lt && !sm.max_leases)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_leased on a context begun without a lease table");
+  if (!lt && sm.max_leases)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_leased takes "
+                "ydc_stream_tick_leased");
   if (wt && !sm.max_waiting)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_waiting on a context begun without a waiting queue");
   if (!wt && sm.max_waiting)
@@ -4220,6 +4426,51 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     if ((n_tasks && (!wt->deadlines || !wt->tags)) || !wt->out_n_resolved || !wt->out_n_waiting ||
         !wt->out_resolved_tags || !wt->out_resolved_idx)
       return YDC_ERR_INVALID_ARGUMENT;
+  }
+  if (lt) {
+    // (nothing is applied unless the whole tick is acceptable)
+    if (lt->n_renew > sm.max_renew || lt->n_free > sm.max_free || lt->n_rep > sm.max_rep)
+      return fail(c, YDC_ERR_CAPACITY, "tick (%u renewals, %u frees by id, %u reports) exceeds the capacity given "
+                  "to ydc_stream_begin_leased (%u, %u, %u)", lt->n_renew, lt->n_free, lt->n_rep, sm.max_renew,
+                  sm.max_free, sm.max_rep);
+    if ((lt->n_renew && (!lt->renew_id || !lt->renew_exp || !lt->out_renewed)) || (lt->n_free && !lt->free_id) ||
+        (lt->n_rep && (!lt->rep_srv || !lt->rep_off)) || (n_tasks && (!lt->lease_exp || !lt->out_task_id)) ||
+        !lt->out_n_leases)
+      return YDC_ERR_INVALID_ARGUMENT;
+    if ((uint64_t)sm.n_leases + n_tasks > sm.max_leases)
+      return fail(c, YDC_ERR_CAPACITY, "%u leases + %u new requests > max_leases %u", sm.n_leases, n_tasks,
+                  sm.max_leases);
+    if (lt->now < sm.last_now)
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "now %lld is before the previous tick's %lld", (long long)lt->now,
+                  (long long)sm.last_now);
+    if (lt->n_rep) {
+      if (lt->rep_off[0] != 0) return fail(c, YDC_ERR_INVALID_ARGUMENT, "report_off[0] must be 0");
+      for (uint32_t r = 0; r < lt->n_rep; ++r)
+        if (lt->rep_off[r + 1] < lt->rep_off[r])
+          return fail(c, YDC_ERR_INVALID_ARGUMENT, "report_off must not decrease (entry %u)", r + 1);
+      const uint32_t n_ids = lt->rep_off[lt->n_rep];
+      if (n_ids > sm.max_rep_ids)
+        return fail(c, YDC_ERR_CAPACITY, "%u reported ids > max_report_ids %u", n_ids, sm.max_rep_ids);
+      if (n_ids && (!lt->rep_id || !lt->out_unknown)) return YDC_ERR_INVALID_ARGUMENT;
+      // A servant reports at most once per tick (a servant this tick's heartbeats add may report too).
+      uint32_t S = c->n_servants;
+      for (uint32_t i = 0; i < n_upd; ++i) S = std::max(S, upd_idx[i] + 1);
+      if (sm.rep_seen.size() < S) sm.rep_seen.resize(S, 0);
+      if (++sm.rep_mark == 0) {  // (a mark per look at a report list, refused ticks included)
+        std::fill(sm.rep_seen.begin(), sm.rep_seen.end(), 0u);
+        sm.rep_mark = 1;
+      }
+      uint32_t bad = kNone;
+      for (uint32_t r = 0; r < lt->n_rep && bad == kNone; ++r) {
+        const uint32_t s = lt->rep_srv[r];
+        if (s >= S || sm.rep_seen[s] == sm.rep_mark) bad = r;
+        else sm.rep_seen[s] = sm.rep_mark;
+      }
+      if (bad != kNone) {
+        return fail(c, YDC_ERR_INVALID_ARGUMENT, "report %u names servant %u, which is unknown or reports twice", bad,
+                    lt->rep_srv[bad]);
+      }
+    }
   }
   if (upd_env_masks && (env_words == 0 || env_words > YDC_MAX_ENV_WORDS))
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "env_words %u out of range", env_words);
@@ -4282,26 +4533,44 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     if (n_tasks && wt->tags != h.tag) std::memcpy(h.tag, wt->tags, (size_t)n_tasks * 8);
     *h.now = wt->now;
   }
+  if (lt) {
+    if (n_tasks) std::memcpy(h.lexp, lt->lease_exp, (size_t)n_tasks * 8);
+    if (lt->n_renew) {
+      std::memcpy(h.ren_id, lt->renew_id, (size_t)lt->n_renew * 8);
+      std::memcpy(h.ren_exp, lt->renew_exp, (size_t)lt->n_renew * 8);
+    }
+    if (lt->n_free) std::memcpy(h.free_id, lt->free_id, (size_t)lt->n_free * 8);
+    const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
+    if (lt->n_rep) {
+      std::memcpy(h.rep_srv, lt->rep_srv, (size_t)lt->n_rep * 4);
+      std::memcpy(h.rep_off, lt->rep_off, ((size_t)lt->n_rep + 1) * 4);
+    }
+    if (n_ids) std::memcpy(h.rep_id, lt->rep_id, (size_t)n_ids * 8);
+    // (the counts make the unused capacity a no-op; a tick number's low 30 bits are never 0)
+    if ((++sm.lease_tick & kLeaseStamp) == 0) ++sm.lease_tick;
+    *h.lh = LeaseHdr{lt->now, lt->n_renew, lt->n_free, lt->n_rep, n_ids, sm.lease_tick, 0};
+  }
   // The ticks placed eagerly place this batch from the arena's device mirror. Waiting mode: the
   // batch is W's region + the new requests in HBM (k_wait_gather), its placement goes to wt_out
   // and k_wait_compact answers the caller.
   const ydc_task_soa batch_dev = wt ? ydc_task_soa{sm.wt.env, sm.wt.minv, sm.wt.ip}
                                     : ydc_task_soa{sm.d.env, sm.d.minv, sm.d.ip};
-  uint32_t* const batch_out = wt ? sm.wt_out : c->d_out_idx.p;
+  uint32_t* const batch_out = wt ? sm.wt_out : lt ? sm.lt_out : c->d_out_idx.p;
   const uint32_t NB = stream_batch_n(sm);
   if (sm.eager_only) {
     // The same step, enqueued instead of replayed: mirror the arena, apply, gather, place, answer.
     // (> kMaxWaveClasses classes: the bin sort, which needs at most that many, is never planned,
     // so place_batch never repeats the batch here)
     HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
+    if (lt) enqueue_lease_pre(c, sm.d);
     enqueue_apply_tick(c, sm.d);
     if (wt) enqueue_wait_gather(c, sm.d);
     BatchPlan pe;
     uint32_t rounds_e = 0;
     if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &pe, &rounds_e))
       return rc;
-    if (int rc = stream_answer_eager(c, sm.d.now)) return rc;
-    return stream_tick_finish(c, pe, rounds_e, n_tasks, out_servant_idx, wt);
+    if (int rc = stream_answer_eager(c, sm.d)) return rc;
+    return stream_tick_finish(c, pe, rounds_e, n_tasks, out_servant_idx, wt, lt);
   }
   const bool second = sm.swaps && c->d_running.p == sm.run_b;
   if (sm.swaps && !second && c->d_running.p != sm.run_a)
@@ -4337,8 +4606,8 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     BatchPlan p2;
     if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &p2, &rounds))
       return rc;
-    if (int rc = stream_answer_eager(c, sm.d.now)) return rc;
-    return stream_tick_finish(c, p2, rounds, n_tasks, out_servant_idx, wt);
+    if (int rc = stream_answer_eager(c, sm.d)) return rc;
+    return stream_tick_finish(c, p2, rounds, n_tasks, out_servant_idx, wt, lt);
   }
   if (p.wave_path) {
     if (c->h_prm->n_changed[(sm.passes - 1) & 63] != 0) {
@@ -4347,7 +4616,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       if (int rc = run_passes_until_consistent(c, p, sm.passes, YDC_DISPATCH_COMMIT, batch_out,
                                                nullptr, nullptr, &rounds))
         return rc;
-      if (int rc = stream_answer_eager(c, sm.z.now)) return rc;
+      if (int rc = stream_answer_eager(c, sm.z)) return rc;
       c->round_hint = rounds;
       sm.want_passes = std::min(rounds + 1, 12u);
       sm.stale = true;
@@ -4367,7 +4636,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       }
     }
   }
-  return stream_tick_finish(c, p, rounds, n_tasks, out_servant_idx, wt);
+  return stream_tick_finish(c, p, rounds, n_tasks, out_servant_idx, wt, lt);
 }
 
 int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
@@ -4376,6 +4645,63 @@ int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_serv
                          uint32_t n_tasks, uint32_t* out_servant_idx) {
   return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
                      n_tasks, out_servant_idx, nullptr);
+}
+
+int ydc_stream_begin_leased(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
+                            uint32_t max_leases, uint32_t max_renewals, uint32_t max_frees, uint32_t max_reports,
+                            uint32_t max_report_ids) {
+  if (!c || !max_leases) return YDC_ERR_INVALID_ARGUMENT;
+  const LeaseCaps lc{max_leases, max_renewals, max_frees, max_reports, max_report_ids};
+  return stream_begin(c, max_updates, max_releases, max_tasks, 0, &lc);
+}
+
+int ydc_stream_tick_leased(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                           const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                           const uint32_t* release_servant_idx, uint32_t n_rel, const uint64_t* renew_task_id,
+                           const int64_t* renew_expires_at, uint32_t n_renew, const uint64_t* free_task_id,
+                           uint32_t n_free, const uint32_t* report_servant_idx, const uint32_t* report_off,
+                           const uint64_t* report_task_id, uint32_t n_rep, const ydc_task_soa* tasks,
+                           const int64_t* lease_expires_at, uint32_t n_tasks, int64_t now,
+                           uint32_t* out_servant_idx, uint64_t* out_task_id, uint8_t* out_renewed,
+                           uint8_t* out_report_unknown, uint32_t* out_n_leases) {
+  const LeaseTick lt{renew_task_id, renew_expires_at, n_renew, free_task_id, n_free, report_servant_idx,
+                     report_off, report_task_id, n_rep, lease_expires_at, now, out_task_id, out_renewed,
+                     out_report_unknown, out_n_leases};
+  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
+                     n_tasks, out_servant_idx, nullptr, &lt);
+}
+
+// The table as it is, in id order: one copy of the columns, the live slots picked and sorted here.
+int ydc_stream_leases_get(ydc_context* c, uint64_t* out_task_id, uint32_t* out_servant_idx,
+                          int64_t* out_expires_at, uint8_t* out_zombie, uint32_t cap, uint32_t* out_n) {
+  if (!c || !out_n || !c->stream_mode.active || !c->stream_mode.max_leases) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const size_t slots = (size_t)sm.lt.mask + 1;
+  std::vector<unsigned long long> key(slots);
+  std::vector<int64_t> exp(slots);
+  std::vector<uint32_t> srv(slots), st(slots);
+  HIP_TRY(c, hipMemcpy(key.data(), sm.lt.key, slots * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(exp.data(), sm.lt.expires, slots * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(srv.data(), sm.lt.servant, slots * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(st.data(), sm.lt.state, slots * 4, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> live;
+  for (size_t i = 0; i < slots; ++i)
+    if (st[i] & kLeaseLive) live.push_back((uint32_t)i);
+  std::sort(live.begin(), live.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+  *out_n = (uint32_t)live.size();
+  if (live.size() > cap) return fail(c, YDC_ERR_CAPACITY, "%zu leases > cap %u", live.size(), cap);
+  if (!live.empty() && (!out_task_id || !out_servant_idx || !out_expires_at || !out_zombie))
+    return YDC_ERR_INVALID_ARGUMENT;
+  for (size_t k = 0; k < live.size(); ++k) {
+    const uint32_t i = live[k];
+    out_task_id[k] = key[i];
+    out_servant_idx[k] = srv[i];
+    out_expires_at[k] = exp[i];
+    out_zombie[k] = (st[i] & kLeaseZombie) ? 1 : 0;
+  }
+  return YDC_OK;
 }
 
 int ydc_stream_tick_waiting(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
