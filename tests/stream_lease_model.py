@@ -21,8 +21,9 @@ of their grants plus foreign and invented ids; ticks with none of each. The cloc
 number.
 
 `place` decides a batch: the plain-C oracle (oracle.oraclebind.dispatch on the stream's registry
-snapshot) for the model; run_reference replays the same stream through the verbatim reference
-class (oracle.refbind) and records the reference's own answers.
+snapshot) for the model; ReferenceReplay puts one given tick at a time through the verbatim
+reference class (oracle.refbind) and records the reference's own answers (run_reference: the same
+seeded stream; tests/stream_lease_cases.py: ticks written by hand).
 """
 import numpy as np
 
@@ -263,69 +264,88 @@ def location(sv, s):
     return "%u.%u.%u.%u:%u" % (ip >> 24, (ip >> 16) & 255, (ip >> 8) & 255, ip & 255, port)
 
 
+class ReferenceReplay:
+    """One GIVEN tick at a time through the VERBATIM reference class (oracle/_ref), one clock unit =
+    1 ms: clock to `now`, heartbeats as KeepServantAlive, renewals as KeepTaskAlive, frees as
+    FreeTask, fire_timers (OnExpirationTimer), reports as NotifyServantRunningTasks, the batch as
+    sequential WaitForStartingNewTask calls. Servants live 30 s there and a run's clock stays far
+    below 30000, so the timer removes none. refbind's batch call grants with a fixed lease; each
+    grant's own expiry is set right behind it with KeepTaskAlive. `ls`: the stream the ticks come
+    from (drawn by it or written by hand on top of its heartbeats and requests); its table is the
+    shadow that follows the reference's placement. Every recorded field is the reference's own
+    answer (running_tasks from DumpInternals); the counts it does not report are the shadow's."""
+
+    def __init__(self, ls):
+        from oracle import refbind as R
+        self.R, self.ls = R, ls
+        sv = ls.es.sv
+        self.ref = R.RefDispatcher()
+        self.ref.load_servants(sv)
+        self.base = int(np.asarray(sv["running_tasks"], np.int64).sum())  # ids the priming grants took
+        self.loc = [location(sv, s) for s in range(ls.es.n)]
+        self.row_of = {l: s for s, l in enumerate(self.loc)}
+        self.clock = None
+
+    def close(self):
+        self.ref.close()
+
+    def _id(self, t):
+        """A task id of the stream as the reference numbers it (ids are 64 bit there too)."""
+        return (int(t) + self.base) & NO_ID
+
+    def tick(self, ev):
+        """-> dict of FIELDS, as model_tick."""
+        ref, ls, es = self.ref, self.ls, self.ls.es
+        now = int(ev["now"])
+        if self.clock is not None and now > self.clock:
+            self.R.clock_advance_ms(now - self.clock)
+        self.clock = now
+        hb = {k: v[ev["upd_idx"]] for k, v in es.sv.items()}
+        hb["running_tasks"] = np.zeros(len(ev["upd_idx"]), np.uint32)  # (kept by a renewal anyway)
+        ref.load_servants(hb)
+        renewed = np.array([ref.keep_task_alive(self._id(t), int(e) - now)
+                            for t, e in zip(ev["renew_ids"], ev["renew_expires_at"])], np.uint8)
+        for t in ev["free_ids"].tolist():
+            ref.free_task(self._id(t))
+        self.R.fire_timers()
+        unknown = np.zeros(len(ev["report_ids"]), np.uint8)
+        off = ev["report_off"]
+        for r, s in enumerate(ev["report_servants"].tolist()):
+            listed = ev["report_ids"][off[r]:off[r + 1]].tolist()
+            unk = set(ref.notify_servant_running_tasks(
+                self.loc[s], np.array([self._id(t) for t in listed], np.uint64)))
+            unknown[off[r]:off[r + 1]] = [self._id(t) in unk for t in listed]
+        got = {}
+
+        def place(batch):
+            ridx, rids, _, _ = ref.dispatch_batch(batch)
+            got["ids"] = rids
+            return ridx
+
+        before = set(ls.table.L)
+        r = ls.table.tick(es.running, ev, place)
+        ls.commit(before, r["out"])
+        granted = r["out"] < IDX_ENV_NOT_FOUND
+        ids = np.full(len(granted), NO_ID, np.uint64)
+        if granted.any():
+            ids[granted] = got["ids"][granted] - np.uint64(self.base)
+            for t, e in zip(got["ids"][granted].tolist(), ev["lease_expires_at"][granted].tolist()):
+                assert ref.keep_task_alive(t, e - now)
+        dump = ref.dump_internals()
+        running = np.zeros(es.n, np.uint32)
+        for s in dump["servants"]:
+            running[self.row_of[s["location"]]] = s["running_tasks"]
+        r.update(task_id=ids, renewed=renewed, report_unknown=unknown, running=running,
+                 renew_refused=int((renewed == 0).sum()), unknown_reported=int(unknown.sum()))
+        return r
+
+
 def run_reference(sv, tasks, frees, renewals, ticks, n_envs=1, seed=83):
-    """The same stream through the VERBATIM reference class (oracle/_ref), one clock tick = 1 ms:
-    clock to `now`, heartbeats as KeepServantAlive, renewals as KeepTaskAlive, frees as FreeTask,
-    fire_timers (OnExpirationTimer), reports as NotifyServantRunningTasks, the batch as sequential
-    WaitForStartingNewTask calls. Servants live 30 s there and a run has far fewer ticks than 30000,
-    so the timer removes none. refbind's batch call grants with a fixed lease; each grant's own
-    expiry is set right behind it with KeepTaskAlive. The traffic is drawn from a shadow table that
-    follows the reference's placement; every recorded field is the reference's own answer
-    (running_tasks from DumpInternals). Same record as run_model."""
-    from oracle import refbind as R
-    shadow = LeaseTable()
-    ls = LeaseStream(sv, tasks, frees, renewals, shadow, n_envs=n_envs, seed=seed)
-    es = ls.es
-    ref = R.RefDispatcher()
-    ref.load_servants(sv)
-    base = int(np.asarray(sv["running_tasks"], np.int64).sum())  # ids the priming grants took
-    loc = [location(sv, s) for s in range(es.n)]
-    row_of = {l: s for s, l in enumerate(loc)}
-    rec = []
+    """The seeded stream of run_model through ReferenceReplay: the traffic is drawn from the shadow
+    table. Same record as run_model."""
+    ls = LeaseStream(sv, tasks, frees, renewals, LeaseTable(), n_envs=n_envs, seed=seed)
+    ref = ReferenceReplay(ls)
     try:
-        for _ in range(ticks):
-            ev = ls.next_tick()
-            now = ev["now"]
-            if rec:
-                R.clock_advance_ms(1)
-            hb = {k: v[ev["upd_idx"]] for k, v in es.sv.items()}
-            hb["running_tasks"] = np.zeros(len(ev["upd_idx"]), np.uint32)  # (kept by a renewal anyway)
-            ref.load_servants(hb)
-            renewed = np.array([ref.keep_task_alive(int(t) + base, int(e) - now)
-                                for t, e in zip(ev["renew_ids"], ev["renew_expires_at"])], np.uint8)
-            for t in ev["free_ids"].tolist():
-                ref.free_task(t + base)
-            R.fire_timers()
-            unknown = np.zeros(len(ev["report_ids"]), np.uint8)
-            off = ev["report_off"]
-            for r, s in enumerate(ev["report_servants"].tolist()):
-                listed = ev["report_ids"][off[r]:off[r + 1]]
-                unk = set(ref.notify_servant_running_tasks(loc[s], listed + np.uint64(base)))
-                unknown[off[r]:off[r + 1]] = [int(t) + base in unk for t in listed.tolist()]
-            got = {}
-
-            def place(batch):
-                ridx, rids, _, _ = ref.dispatch_batch(batch)
-                got["ids"] = rids
-                return ridx
-
-            before = set(shadow.L)
-            r = shadow.tick(es.running, ev, place)
-            ls.commit(before, r["out"])
-            granted = r["out"] < IDX_ENV_NOT_FOUND
-            ids = np.full(len(granted), NO_ID, np.uint64)
-            if granted.any():
-                ids[granted] = got["ids"][granted] - np.uint64(base)
-                for t, e in zip(got["ids"][granted].tolist(), ev["lease_expires_at"][granted].tolist()):
-                    assert ref.keep_task_alive(t, e - now)
-            dump = ref.dump_internals()
-            running = np.zeros(es.n, np.uint32)
-            for s in dump["servants"]:
-                running[row_of[s["location"]]] = s["running_tasks"]
-            # the reference's own answers; the counts it does not report are the shadow's
-            r.update(task_id=ids, renewed=renewed, report_unknown=unknown, running=running,
-                     renew_refused=int((renewed == 0).sum()), unknown_reported=int(unknown.sum()))
-            rec.append(r)
+        return [ref.tick(ls.next_tick()) for _ in range(ticks)]
     finally:
         ref.close()
-    return rec

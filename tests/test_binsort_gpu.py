@@ -9,8 +9,10 @@ import pytest
 
 from oracle import oraclebind as O
 from tests import cases
+from tests import stream_lease_model as LM
 from tests import stream_wait_model as M
 from tests.test_gpu_parity import check
+from tests.test_stream_lease_gpu import check_tick as lease_check_tick, drive as lease_drive, gpu_tick as lease_gpu_tick
 from tests.test_stream_waiting_gpu import drive
 from yadcc_amd import binding, pack, streaming, synth
 
@@ -176,6 +178,53 @@ def test_bin_overflow_inside_a_waiting_streaming_tick():
         drive(c, ws, q, 1)
         assert c.stats()["radix_passes"] >= 1  # (placed again with the radix sort)
         drive(c, ws, q, 3)
+        c.stream_end()
+    finally:
+        c.close()
+
+
+def test_bin_overflow_inside_a_leased_streaming_tick():
+    """The same in leased mode, where the exit is the delicate one: the captured step has applied
+    the tick's renewals, frees by id, report stamps and the sweep before its gated k_lease_grant
+    returned, and the host then places the batch again and runs k_lease_grant from the arena's
+    device mirror. The overflowing tick must carry real lease traffic, so it cannot be the first of
+    an empty table. The batch of a captured step always has max_tasks positions, so a smaller batch
+    would not keep the crowded pool from overflowing; instead the stream begins on a pool that does
+    not overflow (only the first 48 large servants offer slots and take every lease), runs four
+    ordinary ticks, and in tick 4 the heartbeats of all the others bring their slots in: 4000 small
+    servants with one slot and 48 idle large ones whose first 8 slots have the same key, 4384 in
+    one bin. (The large servants that hold leases no longer have slots in that bin, which is why
+    half of them are kept idle until then.) Servants 0 .. 408 report in that tick, the lease
+    holders among them. Every
+    output, running_tasks, the counts and the lease snapshot are compared with the model in every
+    tick."""
+    sv = _crowded_bin_pool()
+    sv["max_tasks"][48:] = 0
+    ls = LM.LeaseStream(sv, 3000, 1000, 200, LM.LeaseTable())
+    c = _context(True)
+    try:
+        c.upload_servants(pack.to_abi_columns(sv))
+        c.stream_begin_leased(4096 + 8, 16, 3000, 1 << 15, 4096, 8192, ls.n_rep, 1 << 17)
+        lease_drive(c, ls, 4)
+        assert c.stats()["radix_passes"] == 0  # (so far the bin sort placed the slots)
+        ls.rep_pos = 0
+        ev = ls.next_tick()
+        es = ls.es
+        es.sv["max_tasks"][48:96], es.sv["max_tasks"][96:] = 2047, 1
+        es.abi = pack.to_abi_columns(es.sv)
+        who = np.union1d(ev["upd_idx"], np.arange(48, 4096)).astype(np.uint32)
+        rows = np.zeros(len(who), dtype=binding.ROW_DTYPE)
+        for k in ("version", "num_processors", "current_load", "max_tasks"):
+            rows[k] = es.sv[k][who]
+        rows["flags"], rows["ip_id"], rows["env_mask"] = es.abi["flags"][who], es.abi["ip_id"][who], es.abi["env_mask"][who]
+        ev = dict(ev, upd_idx=who, upd_rows=rows)
+        assert len(ev["renew_ids"]) and len(ev["free_ids"]) and len(ev["report_ids"]) and len(ev["tasks"]["env_id"])
+        want = LM.model_tick(ls, ev)
+        assert want["freed"] and want["swept"] and want["expired"] and int(want["renewed"].sum())
+        assert int(((want["out"] >= 96) & (want["out"] < LM.IDX_ENV_NOT_FOUND)).sum()) > 1000  # (the small servants take requests now)
+        lease_check_tick(4, c, ls, lease_gpu_tick(c, ls, ev), want)
+        assert c.stats()["radix_passes"] >= 1  # (placed again with the radix sort)
+        lease_drive(c, ls, 3, t0=5)
         c.stream_end()
     finally:
         c.close()

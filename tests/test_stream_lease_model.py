@@ -3,7 +3,8 @@ yardstick of tests/test_stream_lease_gpu.py pinned on the CPU. Tick by tick and 
 model (plain-C oracle placement, plain dict for the lease table) and the reference replay
 (KeepTaskAlive, FreeTask, OnExpirationTimer, NotifyServantRunningTasks, WaitForStartingNewTask of
 oracle/_ref) agree on small seeded streams; the model reproduces the committed cfg5 fixture; hand
-cases with literal values pin the semantics to the reference lines; the ABI carries the feature."""
+cases with literal values pin the semantics to the reference lines; the hand-written ticks of
+tests/stream_lease_cases.py (same-tick interactions) go through the verbatim class tick by tick; the ABI carries the feature."""
 import os
 import re
 
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import refbind as R
+from tests import stream_lease_cases as cases
 from tests import stream_lease_model as M
 from tests.conftest import ROOT
 from yadcc_amd import binding, synth
@@ -117,6 +119,37 @@ def test_model_semantics_by_hand():
     # ydc_remove_servants: the leases of the removed row vanish, the others' rows move up.
     T.remove_servants([0])
     assert [list(c) for c in T.snapshot()][:2] == [[3], [0]]
+
+
+@needs_ref
+@pytest.mark.parametrize("case", cases.CASES, ids=[c.__name__ for c in cases.CASES])
+def test_hand_written_ticks_model_against_the_reference_replay(case):
+    """The same-tick interactions of tests/stream_lease_cases.py: every tick through the model and
+    through the verbatim class, field by field; each step's own expectations are asserted on both
+    records."""
+    got, want = [], []
+    ls = cases.small_stream()
+    cases.play(ls, case(), lambda ev: got.append(M.model_tick(ls, ev)) or got[-1])
+    snap = ls.table.snapshot()
+    ls = cases.small_stream()
+    ref = M.ReferenceReplay(ls)
+    try:
+        cases.play(ls, case(), lambda ev: want.append(ref.tick(ev)) or want[-1])
+    finally:
+        ref.close()
+    assert len(got) == len(want) == len(case())
+    for t, (x, y) in enumerate(zip(got, want)):
+        for k in M.FIELDS:
+            assert np.array_equal(np.asarray(x[k]), np.asarray(y[k])), "tick %d: %s differs" % (t, k)
+    for a, b in zip(snap, ls.table.snapshot()):
+        assert np.array_equal(a, b)
+
+
+def test_hand_written_ticks_on_the_model_alone():
+    """Without oracle/_ref the cases still hold their own expectations on the model."""
+    for case in cases.CASES:
+        ls = cases.small_stream()
+        cases.play(ls, case(), lambda ev: M.model_tick(ls, ev))
 
 
 def test_abi_carries_the_leased_stream():
