@@ -292,7 +292,7 @@ typedef struct ydc_stream_buffers {
 } ydc_stream_buffers;
 int ydc_stream_buffers_get(ydc_context* ctx, ydc_stream_buffers* out);
 /* Discards the waiting queue of a context begun with ydc_stream_begin_waiting and the lease table
- * of one begun with ydc_stream_begin_leased. */
+ * of one begun with ydc_stream_begin_leased (both of one begun with ydc_stream_begin_waiting_leased). */
 int ydc_stream_end(ydc_context* ctx);
 
 /* ---- streaming with a waiting queue --------------------------------------------
@@ -393,6 +393,50 @@ int ydc_stream_tick_leased(ydc_context* ctx, const uint32_t* upd_idx, const ydc_
  * YDC_ERR_CAPACITY with *out_n = |L| and nothing written. */
 int ydc_stream_leases_get(ydc_context* ctx, uint64_t* out_task_id, uint32_t* out_servant_idx,
                           int64_t* out_expires_at, uint8_t* out_zombie, uint32_t cap, uint32_t* out_n);
+
+/* ---- streaming with a waiting queue and leases at once ------------------------------
+ * The reference's grant call does both in one step (task_dispatcher.cc:93-140): it waits until a
+ * servant has a free slot or the deadline passes, and when it grants it records the lease with
+ * task_id = next_task_id++ and expires_at = the clock at the moment of the grant + expires_in. A
+ * context begun with ydc_stream_begin_waiting_leased (max_waiting > 0, max_leases > 0, otherwise as
+ * the two begin calls above; W, L and next_id are reset) keeps W and L on the device together. A
+ * request carries lease_for[i], its lease's DURATION in the caller's clock unit (expires_in), in
+ * place of an absolute expiry: it may be granted in a later tick than it was submitted in.
+ * One tick with clock value now, in this order:
+ *   1. - 6. exactly steps 1 - 6 of ydc_stream_tick_leased;
+ *   7. every entry of W with deadline <= now resolves as Timeout without being tried;
+ *   8. the rest of W in queue order, then the new requests in array order, are placed as ONE
+ *      committed batch (steps 3 - 4 of ydc_stream_tick_waiting);
+ *   9. every grant of that batch, in batch order (the queue's first), takes next_id++ and enters L
+ *      with expires_at = now + lease_for of that request, not a zombie. A queue entry's id is
+ *      out_resolved_task_id[i] beside out_resolved_idx[i], a new request's is out_task_id[i];
+ *      undefined where no servant was granted.
+ * Refused with nothing applied: |W| + n_tasks > max_waiting; |L| + |W| + n_tasks > max_leases
+ * (every waiting entry may be granted in this tick) — both YDC_ERR_CAPACITY — and every refusal of
+ * the two ticks above. ydc_stream_tick / _wide / _waiting / _leased on such a context, and this
+ * call on any other, are YDC_ERR_INVALID_ARGUMENT. ydc_stream_waiting_take, ydc_stream_leases_get,
+ * ydc_remove_servants (W holds no servant index and is untouched) and ydc_stream_end work on it.
+ * ydc_get_stats(): granted counts the queue's grants too; leases_* / renewals_refused as in leased
+ * mode. Behind the batch one kernel does the compaction of W, the resolved list, the ids and the
+ * leases in a single pass; plain, waiting and leased contexts are not affected. */
+int ydc_stream_begin_waiting_leased(ydc_context* ctx, uint32_t max_updates, uint32_t max_releases,
+                                    uint32_t max_tasks, uint32_t max_waiting, uint32_t max_leases,
+                                    uint32_t max_renewals, uint32_t max_frees, uint32_t max_reports,
+                                    uint32_t max_report_ids);
+int ydc_stream_tick_waiting_leased(ydc_context* ctx, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                                   const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                                   const uint32_t* release_servant_idx, uint32_t n_rel,
+                                   const uint64_t* renew_task_id, const int64_t* renew_expires_at,
+                                   uint32_t n_renew, const uint64_t* free_task_id, uint32_t n_free,
+                                   const uint32_t* report_servant_idx, const uint32_t* report_off,
+                                   const uint64_t* report_task_id, uint32_t n_rep,
+                                   const ydc_task_soa* tasks, const int64_t* lease_for,
+                                   const int64_t* deadlines, const uint64_t* tags, uint32_t n_tasks,
+                                   int64_t now, uint32_t* out_servant_idx, uint64_t* out_task_id,
+                                   uint8_t* out_renewed, uint8_t* out_report_unknown, uint32_t* out_n_leases,
+                                   uint64_t* out_resolved_tags, uint32_t* out_resolved_idx,
+                                   uint64_t* out_resolved_task_id, uint32_t* out_n_resolved,
+                                   uint32_t* out_n_waiting);
 
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.

@@ -37,6 +37,7 @@ ABI_SYMBOLS = (
     "ydc_stream_begin", "ydc_stream_tick", "ydc_stream_tick_wide", "ydc_stream_buffers_get", "ydc_stream_end",
     "ydc_stream_begin_waiting", "ydc_stream_tick_waiting", "ydc_stream_waiting_take",
     "ydc_stream_begin_leased", "ydc_stream_tick_leased", "ydc_stream_leases_get",
+    "ydc_stream_begin_waiting_leased", "ydc_stream_tick_waiting_leased",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -153,6 +154,16 @@ def lib():
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,                          # reports (CSR)
             C.POINTER(TaskSoA), C.c_void_p, C.c_uint32, C.c_int64,                   # requests, clock
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.ydc_stream_begin_waiting_leased.argtypes = [C.c_void_p] + [C.c_uint32] * 9
+        L.ydc_stream_tick_waiting_leased.argtypes = [
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,  # heartbeats
+            C.c_void_p, C.c_uint32,                                                  # releases by servant
+            C.c_void_p, C.c_void_p, C.c_uint32,                                      # renewals
+            C.c_void_p, C.c_uint32,                                                  # frees by id
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,                          # reports (CSR)
+            C.POINTER(TaskSoA), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64,  # requests, clock
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),   # as a leased tick
+            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]  # resolved list
         L.ydc_stream_leases_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.POINTER(C.c_uint32)]
         L.ydc_group_unique_id.argtypes = [C.c_void_p]
@@ -654,6 +665,73 @@ class Context:
             out.ctypes.data, ids.ctypes.data, renewed.ctypes.data, unknown.ctypes.data, C.byref(n_leases)),
             "ydc_stream_tick_leased")
         return out, ids, renewed, unknown, int(n_leases.value)
+
+    def stream_begin_waiting_leased(self, max_updates, max_releases, max_tasks, max_waiting, max_leases,
+                                    max_renewals, max_frees, max_reports, max_report_ids):
+        """Waiting queue and lease table at once (ydc_stream_begin_waiting_leased): requests that find
+        no free servant wait on the device, and every grant, a waiter's included, takes its task id
+        and its lease there; ticks go through stream_tick_waiting_leased."""
+        self._check(lib().ydc_stream_begin_waiting_leased(
+            self._h, max_updates, max_releases, max_tasks, max_waiting, max_leases, max_renewals, max_frees,
+            max_reports, max_report_ids), "ydc_stream_begin_waiting_leased")
+        self._stream_caps = (int(max_updates), int(max_releases), int(max_tasks))
+        self._max_waiting = int(max_waiting)
+        self._max_leases = int(max_leases)
+
+    def stream_tick_waiting_leased(self, upd_idx, upd_rows, release_idx, renew_ids, renew_expires_at, free_ids,
+                                   report_servants, report_off, report_ids, tasks, lease_for, deadlines, tags,
+                                   now, env_masks=None):
+        """One tick of a context begun with stream_begin_waiting_leased
+        (ydc_stream_tick_waiting_leased): the arguments of stream_tick_leased with lease_for (int64
+        duration per request; a lease runs from its grant: expires_at = now of the granting tick +
+        lease_for) in place of lease_expires_at, plus deadlines and tags as stream_tick_waiting.
+        Returns (out, task_ids, renewed, report_unknown, n_leases, resolved_tags, resolved_idx,
+        resolved_task_ids, n_waiting): the resolved list holds the queued requests answered in this
+        tick in queue order, resolved_task_ids[i] the id of a queued request's grant (only where
+        resolved_idx[i] is a servant); ids go to the queue's grants first, then to the new ones."""
+        ui = np.ascontiguousarray(upd_idx, dtype=np.uint32)
+        if len(ui):
+            self.n_servants = max(self.n_servants, int(ui.max()) + 1)
+        ur = np.ascontiguousarray(upd_rows, dtype=ROW_DTYPE)
+        rel = np.ascontiguousarray(release_idx, dtype=np.uint32)
+        rid = np.ascontiguousarray(renew_ids, dtype=np.uint64)
+        rex = np.ascontiguousarray(renew_expires_at, dtype=np.int64)
+        fid = np.ascontiguousarray(free_ids, dtype=np.uint64)
+        rs = np.ascontiguousarray(report_servants, dtype=np.uint32)
+        ro = np.ascontiguousarray(report_off, dtype=np.uint32)
+        ri = np.ascontiguousarray(report_ids, dtype=np.uint64)
+        assert len(rid) == len(rex) and (len(rs) == 0 or len(ro) == len(rs) + 1)
+        assert len(rs) == 0 or int(ro[-1]) == len(ri)
+        keep = [np.ascontiguousarray(tasks[k], dtype=np.uint32)
+                for k in ("env_id", "min_version", "requestor_ip")]
+        n = len(keep[0])
+        lfor = np.ascontiguousarray(lease_for, dtype=np.int64)
+        dl = np.ascontiguousarray(deadlines, dtype=np.int64)
+        tg = np.ascontiguousarray(tags, dtype=np.uint64)
+        assert len(lfor) == n and len(dl) == n and len(tg) == n
+        soa = TaskSoA(*[a.ctypes.data for a in keep])
+        out = np.empty(n, np.uint32)
+        ids = np.empty(n, np.uint64)
+        renewed = np.zeros(len(rid), np.uint8)
+        unknown = np.zeros(len(ri), np.uint8)
+        cap = max(self._max_waiting, 1)
+        res_tags, res_idx, res_ids = np.empty(cap, np.uint64), np.empty(cap, np.uint32), np.empty(cap, np.uint64)
+        n_leases, n_res, n_wait = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        if env_masks is None:
+            em, words = None, 1
+        else:
+            em = np.ascontiguousarray(env_masks, dtype=np.uint64).reshape(len(ui), -1)
+            words = em.shape[1]
+        self._check(lib().ydc_stream_tick_waiting_leased(
+            self._h, ui.ctypes.data, ur.ctypes.data, None if em is None else em.ctypes.data, words, len(ui),
+            rel.ctypes.data, len(rel), rid.ctypes.data, rex.ctypes.data, len(rid), fid.ctypes.data, len(fid),
+            rs.ctypes.data, ro.ctypes.data, ri.ctypes.data, len(rs), C.byref(soa), lfor.ctypes.data,
+            dl.ctypes.data, tg.ctypes.data, n, int(now), out.ctypes.data, ids.ctypes.data, renewed.ctypes.data,
+            unknown.ctypes.data, C.byref(n_leases), res_tags.ctypes.data, res_idx.ctypes.data,
+            res_ids.ctypes.data, C.byref(n_res), C.byref(n_wait)), "ydc_stream_tick_waiting_leased")
+        k = n_res.value
+        return (out, ids, renewed, unknown, int(n_leases.value), res_tags[:k].copy(), res_idx[:k].copy(),
+                res_ids[:k].copy(), int(n_wait.value))
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

@@ -73,10 +73,19 @@ struct WaitOutcome {
 constexpr unsigned long long kLbAggregate = 1ull << 62, kLbInclusive = 2ull << 62;
 constexpr unsigned long long kLbValue = (1ull << 62) - 1;
 
+// A further int64 column that travels with the entries where the context has one (wait_lease.h:
+// the lease durations); all NULL otherwise.
+struct WaitExtra {
+  const int64_t* w;   // W's column
+  int64_t* t;         // the batch's
+  const int64_t* nw;  // the new requests'
+};
+
 // Thread per batch position j in [0, max_waiting + max_tasks).
 __global__ __launch_bounds__(256) void k_wait_gather(WaitCols w, WaitCols t, WaitNew nw, uint32_t MW,
                                                      uint32_t N, WaitState* ws,
-                                                     unsigned long long* lookback, uint32_t n_lookback) {
+                                                     unsigned long long* lookback, uint32_t n_lookback,
+                                                     WaitExtra x) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t cnt = ws->count;
   if (j == 0) {
@@ -91,6 +100,7 @@ __global__ __launch_bounds__(256) void k_wait_gather(WaitCols w, WaitCols t, Wai
       const int64_t dl = w.deadline[j];
       t.deadline[j] = dl;
       t.tag[j] = w.tag[j];
+      if (x.t) x.t[j] = x.w[j];
       if (dl > *nw.now) {  // (deadline <= now: expired, resolved as Timeout without being tried)
         e = w.env[j];
         mv = w.minv[j];
@@ -107,6 +117,7 @@ __global__ __launch_bounds__(256) void k_wait_gather(WaitCols w, WaitCols t, Wai
     t.ip[j] = nw.ip[k];
     t.deadline[j] = nw.deadline[k];
     t.tag[j] = nw.tag[k];
+    if (x.t) x.t[j] = x.nw[k];
   }
 }
 

@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "wait_queue.h"
 #include "lease_table.h"
+#include "wait_lease.h"
 #include "tick_kernel.h"
 
 using namespace ydc;
@@ -107,8 +108,8 @@ struct BatchPlan {
 // The sections of a streaming tick's staging arena (stream_begin lays them out): heartbeat
 // indexes and rows, released slots, the three request columns and, in waiting mode, the new
 // requests' deadlines and tags and the tick's clock (NULL in a plain context); in leased mode the
-// requests' lease expiries, the renewals, the frees by id, the servant reports (CSR) and the
-// tick's scalars (NULL in any other context).
+// requests' lease expiries (with a waiting queue as well: their lease durations), the renewals,
+// the frees by id, the servant reports (CSR) and the tick's scalars (NULL in any other context).
 struct TickArena {
   uint32_t* upd_idx;
   ydc_servant_row* upd_rows;
@@ -283,6 +284,11 @@ struct ydc_context {
     uint64_t *h_res_tag = nullptr, *z_res_tag = nullptr;
     uint32_t *h_res_idx = nullptr, *z_res_idx = nullptr;
     WaitOutcome *h_wout = nullptr, *z_wout = nullptr;
+    // Waiting and leased at once (ydc_stream_begin_waiting_leased; wait_lease.h): both of the above
+    // and below exist, plus the lease durations of W and of the batch and the resolved entries' task
+    // ids (page-locked, beside the resolved tags). wl.t_for == NULL: not such a context.
+    WaitLeaseCols wl{};
+    unsigned long long* h_res_id = nullptr;
     // Leased mode (ydc_stream_begin_leased; lease_table.h): the lease table L in HBM, the placement
     // of the tick's batch in front of k_lease_grant, and the page-locked results. max_leases == 0:
     // not a leased context (none of this exists). lookback / lookback_n above serve k_lease_grant.
@@ -3910,7 +3916,8 @@ void enqueue_wait_gather(ydc_context* c, const TickArena& a) {
   const uint32_t N = stream_batch_n(sm);
   YDC_LAUNCH(c, "k_wait_gather", k_wait_gather, dim3(ceil_div(std::max(N, sm.lookback_n), 256)), dim3(256), 0,
              c->stream, sm.wq, sm.wt, WaitNew{a.env, a.minv, a.ip, a.dl, a.tag, a.now}, sm.max_waiting, N, sm.ws,
-             sm.lookback, sm.lookback_n);
+             sm.lookback, sm.max_leases ? 0u : sm.lookback_n,  // (with leases: k_lease_renew has cleared the words)
+             WaitExtra{sm.wl.w_for, sm.wl.t_for, sm.wl.t_for ? a.lexp : nullptr});
 }
 
 // ... and behind the batch: new W, resolved list, the new requests' answers. prm: gated on the
@@ -3957,6 +3964,24 @@ void enqueue_lease_grant(ydc_context* c, const TickArena& a, const DeviceParams*
              prm, check_slot);
 }
 
+// Waiting and leased at once, behind the batch: the one pass of wait_lease.h instead of the two
+// above. prm as there.
+void enqueue_wait_lease_commit(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
+  auto& sm = c->stream_mode;
+  const uint32_t N = stream_batch_n(sm);
+  YDC_LAUNCH(c, "k_wait_lease_commit", k_wait_lease_commit, dim3(ceil_div(N, kWaitTile)), dim3(256), 0, c->stream,
+             sm.wt, sm.wl, sm.wt_out, a.lh, sm.max_waiting, N, sm.wq, sm.ws, sm.lt, sm.ls, sm.lookback, sm.z_out,
+             sm.z_task_id, sm.z_res_tag, sm.z_res_idx, sm.z_wout, sm.z_lout, prm, check_slot);
+}
+
+// The kernel behind the batch that answers the caller in the context's mode (none: a plain one).
+void enqueue_stream_answer(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
+  auto& sm = c->stream_mode;
+  if (sm.max_waiting && sm.max_leases) enqueue_wait_lease_commit(c, a, prm, check_slot);
+  else if (sm.max_waiting) enqueue_wait_compact(c, a.now, prm, check_slot);
+  else if (sm.max_leases) enqueue_lease_grant(c, a, prm, check_slot);
+}
+
 // The step itself, enqueued on the context's stream (inside a capture, or — stream_graph=0 — as it is).
 int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
   auto& sm = c->stream_mode;
@@ -3994,8 +4019,7 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
     c->commit_by_swap = false;
     c->finalize_outcome = nullptr;
   }
-  if (rc == YDC_OK && waiting) enqueue_wait_compact(c, sm.z.now, c->d_prm.p, check_slot);
-  if (rc == YDC_OK && leased) enqueue_lease_grant(c, sm.z, c->d_prm.p, check_slot);
+  if (rc == YDC_OK) enqueue_stream_answer(c, sm.z, c->d_prm.p, check_slot);
   if (!outcome_stored) cap(hipMemcpyAsync(c->h_prm, c->d_prm.p, sizeof(DeviceParams), hipMemcpyDeviceToHost, st));
   return rc;
 }
@@ -4069,6 +4093,7 @@ struct WaitTick {
   uint32_t* out_resolved_idx;
   uint32_t* out_n_resolved;
   uint32_t* out_n_waiting;
+  uint64_t* out_resolved_task_id;  // waiting and leased at once; NULL otherwise
 };
 
 // A leased tick's own arguments (ydc_stream_tick_leased).
@@ -4169,8 +4194,11 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
                             wsec(max_waiting * 8ull), wsec(max_waiting * 8ull)};
     const size_t o_wt[5] = {wsec(NB * 4), wsec(NB * 4), wsec(NB * 4), wsec(NB * 8), wsec(NB * 8)};
     const size_t o_wout = wsec(NB * 4), o_ws = wsec(sizeof(WaitState)), o_lb = wsec((size_t)sm.lookback_n * 8);
+    // ... with leases: W's sixth column and the batch's, the lease durations (wait_lease.h).
+    const size_t o_wfor = lc ? wsec(max_waiting * 8ull) : 0, o_tfor = lc ? wsec(NB * 8) : 0;
     HIP_TRY(c, sm.d_wait.reserve(w_off));
     uint8_t* b = sm.d_wait.p;
+    if (lc) sm.wl = WaitLeaseCols{(int64_t*)(b + o_wfor), (int64_t*)(b + o_tfor), nullptr};
     sm.wq = WaitCols{(uint32_t*)(b + o_wq[0]), (uint32_t*)(b + o_wq[1]), (uint32_t*)(b + o_wq[2]),
                      (int64_t*)(b + o_wq[3]), (uint64_t*)(b + o_wq[4])};
     sm.wt = WaitCols{(uint32_t*)(b + o_wt[0]), (uint32_t*)(b + o_wt[1]), (uint32_t*)(b + o_wt[2]),
@@ -4183,9 +4211,14 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     size_t r_off = 0;
     const size_t r_tag = section(&r_off, (size_t)max_waiting * 8), r_idx = section(&r_off, (size_t)max_waiting * 4);
     const size_t r_out = section(&r_off, sizeof(WaitOutcome));
+    const size_t r_id = lc ? section(&r_off, (size_t)max_waiting * 8) : 0;  // (with leases: the resolved ids)
     HIP_TRY(c, hipHostMalloc((void**)&sm.h_wres, r_off, hipHostMallocCoherent | hipHostMallocMapped));
     uint8_t* z_res = nullptr;
     HIP_TRY(c, hipHostGetDevicePointer((void**)&z_res, sm.h_wres, 0));
+    if (lc) {
+      sm.h_res_id = (unsigned long long*)(sm.h_wres + r_id);
+      sm.wl.res_id = (unsigned long long*)(z_res + r_id);
+    }
     sm.h_res_tag = (uint64_t*)(sm.h_wres + r_tag);
     sm.h_res_idx = (uint32_t*)(sm.h_wres + r_idx);
     sm.h_wout = (WaitOutcome*)(sm.h_wres + r_out);
@@ -4206,7 +4239,8 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     size_t cap = 1024;
     uint32_t cap_bits = 10;
     while (cap < 2 * (size_t)lc->max_leases) cap <<= 1, ++cap_bits;
-    sm.lookback_n = ceil_div(max_tasks, kLeaseTile);
+    // (with a waiting queue: two words per tile of the whole batch, wait_lease.h)
+    sm.lookback_n = max_waiting ? 2 * ceil_div(max_tasks + max_waiting, kWaitTile) : ceil_div(max_tasks, kLeaseTile);
     size_t l_off = 0;
     auto lsec = [&](size_t bytes) { return section(&l_off, bytes); };
     const size_t o_key = lsec(cap * 8), o_exp = lsec(cap * 8), o_srv = lsec(cap * 4), o_st = lsec(cap * 4);
@@ -4321,6 +4355,7 @@ static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tas
     std::memcpy(wt->out_resolved_tags, sm.h_res_tag, (size_t)n_res * 8);
   if (n_res && wt->out_resolved_idx != sm.h_res_idx)
     std::memcpy(wt->out_resolved_idx, sm.h_res_idx, (size_t)n_res * 4);
+  if (n_res && wt->out_resolved_task_id) std::memcpy(wt->out_resolved_task_id, sm.h_res_id, (size_t)n_res * 8);
   *wt->out_n_resolved = n_res;
   *wt->out_n_waiting = n_wait;
   const uint32_t live = sm.n_waiting - std::min(sm.n_waiting, expired);
@@ -4355,18 +4390,15 @@ static int stream_lease_finish(ydc_context* c, const LeaseTick* lt, uint32_t n_t
 }
 
 // After a placement the host ran itself: the answers into the page-locked result array — in
-// waiting mode by k_wait_compact (ungated), otherwise by a copy. `a`: the arena where the step
+// waiting mode by k_wait_compact, in leased mode by k_lease_grant, with both by
+// k_wait_lease_commit (ungated), otherwise by a copy. `a`: the arena where the step
 // read the tick's clock. That is the device mirror (d) when the tick copied the arena there, and
 // the page-locked arena in place (z) when it did not: the mirror then still holds an older
 // tick's clock.
 static int stream_answer_eager(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
-  if (sm.max_waiting) {
-    enqueue_wait_compact(c, a.now, nullptr, kNone);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-  } else if (sm.max_leases) {  // (leased mode: by k_lease_grant, ungated, with the ids and the leases)
-    enqueue_lease_grant(c, a, nullptr, kNone);
+  if (sm.max_waiting || sm.max_leases) {  // (ungated; in leased mode with the ids and the leases)
+    enqueue_stream_answer(c, a, nullptr, kNone);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
   } else {
@@ -4398,6 +4430,12 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
                        const LeaseTick* lt = nullptr) {
   if (!c || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
+  if (sm.max_leases && sm.max_waiting && !(wt && lt))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_waiting_leased takes "
+                "ydc_stream_tick_waiting_leased");
+  if (wt && lt && !(sm.max_leases && sm.max_waiting))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_waiting_leased on a context begun without a waiting "
+                "queue and a lease table");
   if (lt && !sm.max_leases)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_leased on a context begun without a lease table");
   if (!lt && sm.max_leases)
@@ -4424,7 +4462,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       return fail(c, YDC_ERR_INVALID_ARGUMENT, "now %lld is before the previous tick's %lld", (long long)wt->now,
                   (long long)sm.last_now);
     if ((n_tasks && (!wt->deadlines || !wt->tags)) || !wt->out_n_resolved || !wt->out_n_waiting ||
-        !wt->out_resolved_tags || !wt->out_resolved_idx)
+        !wt->out_resolved_tags || !wt->out_resolved_idx || (lt && !wt->out_resolved_task_id))
       return YDC_ERR_INVALID_ARGUMENT;
   }
   if (lt) {
@@ -4437,6 +4475,10 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
         (lt->n_rep && (!lt->rep_srv || !lt->rep_off)) || (n_tasks && (!lt->lease_exp || !lt->out_task_id)) ||
         !lt->out_n_leases)
       return YDC_ERR_INVALID_ARGUMENT;
+    // (with a waiting queue: every waiting entry may be granted in this tick)
+    if (wt && (uint64_t)sm.n_leases + sm.n_waiting + n_tasks > sm.max_leases)
+      return fail(c, YDC_ERR_CAPACITY, "%u leases + %u waiting + %u new requests > max_leases %u", sm.n_leases,
+                  sm.n_waiting, n_tasks, sm.max_leases);
     if ((uint64_t)sm.n_leases + n_tasks > sm.max_leases)
       return fail(c, YDC_ERR_CAPACITY, "%u leases + %u new requests > max_leases %u", sm.n_leases, n_tasks,
                   sm.max_leases);
@@ -4671,6 +4713,37 @@ int ydc_stream_tick_leased(ydc_context* c, const uint32_t* upd_idx, const ydc_se
                      n_tasks, out_servant_idx, nullptr, &lt);
 }
 
+int ydc_stream_begin_waiting_leased(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
+                                    uint32_t max_waiting, uint32_t max_leases, uint32_t max_renewals,
+                                    uint32_t max_frees, uint32_t max_reports, uint32_t max_report_ids) {
+  if (!c || !max_waiting || !max_leases) return YDC_ERR_INVALID_ARGUMENT;
+  const LeaseCaps lc{max_leases, max_renewals, max_frees, max_reports, max_report_ids};
+  return stream_begin(c, max_updates, max_releases, max_tasks, max_waiting, &lc);
+}
+
+int ydc_stream_tick_waiting_leased(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                                   const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                                   const uint32_t* release_servant_idx, uint32_t n_rel,
+                                   const uint64_t* renew_task_id, const int64_t* renew_expires_at, uint32_t n_renew,
+                                   const uint64_t* free_task_id, uint32_t n_free,
+                                   const uint32_t* report_servant_idx, const uint32_t* report_off,
+                                   const uint64_t* report_task_id, uint32_t n_rep, const ydc_task_soa* tasks,
+                                   const int64_t* lease_for, const int64_t* deadlines, const uint64_t* tags,
+                                   uint32_t n_tasks, int64_t now, uint32_t* out_servant_idx, uint64_t* out_task_id,
+                                   uint8_t* out_renewed, uint8_t* out_report_unknown, uint32_t* out_n_leases,
+                                   uint64_t* out_resolved_tags, uint32_t* out_resolved_idx,
+                                   uint64_t* out_resolved_task_id, uint32_t* out_n_resolved,
+                                   uint32_t* out_n_waiting) {
+  // (lease_for travels where a leased tick's absolute expiries do: the arena's per-request column)
+  const LeaseTick lt{renew_task_id, renew_expires_at, n_renew, free_task_id, n_free, report_servant_idx,
+                     report_off, report_task_id, n_rep, lease_for, now, out_task_id, out_renewed,
+                     out_report_unknown, out_n_leases};
+  const WaitTick wt{deadlines, tags, now, out_resolved_tags, out_resolved_idx, out_n_resolved, out_n_waiting,
+                    out_resolved_task_id};
+  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
+                     n_tasks, out_servant_idx, &wt, &lt);
+}
+
 // The table as it is, in id order: one copy of the columns, the live slots picked and sorted here.
 int ydc_stream_leases_get(ydc_context* c, uint64_t* out_task_id, uint32_t* out_servant_idx,
                           int64_t* out_expires_at, uint8_t* out_zombie, uint32_t cap, uint32_t* out_n) {
@@ -4710,7 +4783,8 @@ int ydc_stream_tick_waiting(ydc_context* c, const uint32_t* upd_idx, const ydc_s
                             const int64_t* deadlines, const uint64_t* tags, uint32_t n_tasks, int64_t now,
                             uint32_t* out_servant_idx, uint64_t* out_resolved_tags, uint32_t* out_resolved_idx,
                             uint32_t* out_n_resolved, uint32_t* out_n_waiting) {
-  const WaitTick wt{deadlines, tags, now, out_resolved_tags, out_resolved_idx, out_n_resolved, out_n_waiting};
+  const WaitTick wt{deadlines, tags, now, out_resolved_tags, out_resolved_idx, out_n_resolved, out_n_waiting,
+                    nullptr};
   return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
                      n_tasks, out_servant_idx, &wt);
 }
