@@ -438,6 +438,60 @@ int ydc_stream_tick_waiting_leased(ydc_context* ctx, const uint32_t* upd_idx, co
                                    uint64_t* out_resolved_task_id, uint32_t* out_n_resolved,
                                    uint32_t* out_n_waiting);
 
+/* ---- streaming, one request row per RPC ---------------------------------------------
+ * The unit a scheduler receives is one WaitForStartingTask RPC (scheduler_service_impl.cc:209-271):
+ * one personality asking for n_immediate + n_prefetch grants. Only the first grant may wait until
+ * the deadline; the rest are tried at the moment the first is granted; the loops stop at the first
+ * failure; EnvironmentNotFound fails the RPC only inside the immediate loop; an RPC that ends
+ * without a grant is NO_QUOTA. A context begun with ydc_stream_begin_rpc is a waiting and leased
+ * one (above; W, L and next_id are reset) whose request rows and entries of W are RPCs:
+ * max_requests bounds a tick's new requests, max_rows the expanded batch (the rows of W's entries
+ * plus the rows of the tick's new requests), max_waiting the blocked RPCs.
+ * A request is (env_id, min_version, requestor_ip, n_immediate, n_prefetch, lease_for, deadline,
+ * tag); rows = n_immediate + n_prefetch, rows == 0 is YDC_ERR_INVALID_ARGUMENT. One tick:
+ *   1. - 6. exactly steps 1 - 6 of ydc_stream_tick_leased;
+ *   7. every entry of W with deadline <= now resolves as YDC_IDX_TIMEOUT, untried, with 0 grants;
+ *   8. the remaining entries of W in queue order, then the new requests in array order, each
+ *      expand into rows consecutive identical batch rows; the expansion is placed as ONE committed
+ *      batch (the handler's sequential calls with timeout == now; nothing frees between identical
+ *      consecutive rows, so the granted rows of a request are a prefix of its rows);
+ *   9. granted rows in batch order take next_id++ and enter L with expires_at = now + lease_for.
+ * A request with g granted rows: g > 0: granted (status 0), the rows beyond g are dropped, never
+ * queued. g == 0 and EnvironmentNotFound: YDC_IDX_ENV_NOT_FOUND if n_immediate > 0, otherwise
+ * YDC_IDX_TIMEOUT (the prefetch loop only breaks; the RPC ends as NO_QUOTA). g == 0, Timeout,
+ * deadline > now: it waits as ONE entry of W keeping both counts (a new request: YDC_IDX_WAITING);
+ * deadline <= now: YDC_IDX_TIMEOUT. Whether a row is a prefetch is not stored (the reference uses
+ * is_prefetch for log text only).
+ * New requests: out_status[n_req], out_n_granted[n_req]; out_servant_idx[] / out_task_id[] in
+ * EXPANDED layout: request i's rows start at the sum of the rows of the requests before it, the
+ * first out_n_granted[i] of them are defined. W's entries answered in this tick, in queue order:
+ * out_resolved_tags / _status / _n_granted / _first [max_waiting]; entry j's grants are
+ * out_resolved_servant_idx / out_resolved_task_id [first_j, first_j + n_granted_j) (packed, at most
+ * max_rows). *out_n_waiting = |W|, *out_n_waiting_rows = the rows W's entries stand for.
+ * Refused with nothing applied (YDC_ERR_CAPACITY): |W| + n_req > max_waiting; rows(W) + rows(new) >
+ * max_rows; |L| + rows(W) + rows(new) > max_leases; and every refusal of the ticks above. Any other
+ * tick call on an rpc context, and this call on any other, are YDC_ERR_INVALID_ARGUMENT.
+ * ydc_stream_waiting_take (one tag per RPC), ydc_stream_leases_get, ydc_remove_servants and
+ * ydc_stream_end work on it. ydc_get_stats(): n_tasks counts the batch's rows, granted and the
+ * lease counters as in waiting-and-leased mode. */
+int ydc_stream_begin_rpc(ydc_context* ctx, uint32_t max_updates, uint32_t max_releases, uint32_t max_requests,
+                         uint32_t max_rows, uint32_t max_waiting, uint32_t max_leases, uint32_t max_renewals,
+                         uint32_t max_frees, uint32_t max_reports, uint32_t max_report_ids);
+int ydc_stream_tick_rpc(ydc_context* ctx, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                        const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                        const uint32_t* release_servant_idx, uint32_t n_rel, const uint64_t* renew_task_id,
+                        const int64_t* renew_expires_at, uint32_t n_renew, const uint64_t* free_task_id,
+                        uint32_t n_free, const uint32_t* report_servant_idx, const uint32_t* report_off,
+                        const uint64_t* report_task_id, uint32_t n_rep, const ydc_task_soa* requests,
+                        const uint32_t* n_immediate, const uint32_t* n_prefetch, const int64_t* lease_for,
+                        const int64_t* deadlines, const uint64_t* tags, uint32_t n_req, int64_t now,
+                        uint32_t* out_status, uint32_t* out_n_granted, uint32_t* out_servant_idx,
+                        uint64_t* out_task_id, uint8_t* out_renewed, uint8_t* out_report_unknown,
+                        uint32_t* out_n_leases, uint64_t* out_resolved_tags, uint32_t* out_resolved_status,
+                        uint32_t* out_resolved_n_granted, uint32_t* out_resolved_first,
+                        uint32_t* out_resolved_servant_idx, uint64_t* out_resolved_task_id,
+                        uint32_t* out_n_resolved, uint32_t* out_n_waiting, uint32_t* out_n_waiting_rows);
+
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.
  * Rank 0 gets a 128-byte id (ncclGetUniqueId), the launcher hands it to every rank (any

@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "ydc_stream_begin_waiting", "ydc_stream_tick_waiting", "ydc_stream_waiting_take",
     "ydc_stream_begin_leased", "ydc_stream_tick_leased", "ydc_stream_leases_get",
     "ydc_stream_begin_waiting_leased", "ydc_stream_tick_waiting_leased",
+    "ydc_stream_begin_rpc", "ydc_stream_tick_rpc",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -164,6 +165,19 @@ def lib():
             C.POINTER(TaskSoA), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64,  # requests, clock
             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),   # as a leased tick
             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]  # resolved list
+        L.ydc_stream_begin_rpc.argtypes = [C.c_void_p] + [C.c_uint32] * 10
+        L.ydc_stream_tick_rpc.argtypes = [
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,  # heartbeats
+            C.c_void_p, C.c_uint32,                                                  # releases by servant
+            C.c_void_p, C.c_void_p, C.c_uint32,                                      # renewals
+            C.c_void_p, C.c_uint32,                                                  # frees by id
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,                          # reports (CSR)
+            C.POINTER(TaskSoA), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,  # requests
+            C.c_uint32, C.c_int64,                                                   # n_req, clock
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,                          # status, count, rows
+            C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),                           # as a leased tick
+            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,  # resolved list, its grants
+            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.ydc_stream_leases_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.POINTER(C.c_uint32)]
         L.ydc_group_unique_id.argtypes = [C.c_void_p]
@@ -348,6 +362,7 @@ class Context:
         self.n_servants = 0
         self._stream_caps = (0, 0, 0)
         self._max_waiting = 0
+        self._max_rows = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -732,6 +747,85 @@ class Context:
         k = n_res.value
         return (out, ids, renewed, unknown, int(n_leases.value), res_tags[:k].copy(), res_idx[:k].copy(),
                 res_ids[:k].copy(), int(n_wait.value))
+
+    def stream_begin_rpc(self, max_updates, max_releases, max_requests, max_rows, max_waiting, max_leases,
+                         max_renewals, max_frees, max_reports, max_report_ids):
+        """One request row per WaitForStartingTask RPC (ydc_stream_begin_rpc): a waiting and leased
+        context whose requests ask for n_immediate + n_prefetch grants each; max_rows bounds the
+        expanded batch. Ticks go through stream_tick_rpc."""
+        self._check(lib().ydc_stream_begin_rpc(
+            self._h, max_updates, max_releases, max_requests, max_rows, max_waiting, max_leases, max_renewals,
+            max_frees, max_reports, max_report_ids), "ydc_stream_begin_rpc")
+        self._stream_caps = (int(max_updates), int(max_releases), int(max_requests))
+        self._max_waiting = int(max_waiting)
+        self._max_leases = int(max_leases)
+        self._max_rows = int(max_rows)
+
+    def stream_tick_rpc(self, upd_idx, upd_rows, release_idx, renew_ids, renew_expires_at, free_ids,
+                        report_servants, report_off, report_ids, requests, n_immediate, n_prefetch, lease_for,
+                        deadlines, tags, now, env_masks=None):
+        """One tick of a context begun with stream_begin_rpc (ydc_stream_tick_rpc): the arguments of
+        stream_tick_waiting_leased with the two counts per request. Returns a dict: status and
+        n_granted per request; servants and task_ids in expanded layout (request i's rows at
+        row_off[i], the first n_granted[i] defined); renewed, report_unknown, n_leases; the resolved
+        list res_tags, res_status, res_n_granted, res_first with its grants packed in res_servants /
+        res_task_ids; n_waiting, n_waiting_rows."""
+        ui = np.ascontiguousarray(upd_idx, dtype=np.uint32)
+        if len(ui):
+            self.n_servants = max(self.n_servants, int(ui.max()) + 1)
+        ur = np.ascontiguousarray(upd_rows, dtype=ROW_DTYPE)
+        rel = np.ascontiguousarray(release_idx, dtype=np.uint32)
+        rid = np.ascontiguousarray(renew_ids, dtype=np.uint64)
+        rex = np.ascontiguousarray(renew_expires_at, dtype=np.int64)
+        fid = np.ascontiguousarray(free_ids, dtype=np.uint64)
+        rs = np.ascontiguousarray(report_servants, dtype=np.uint32)
+        ro = np.ascontiguousarray(report_off, dtype=np.uint32)
+        ri = np.ascontiguousarray(report_ids, dtype=np.uint64)
+        assert len(rid) == len(rex) and (len(rs) == 0 or len(ro) == len(rs) + 1)
+        assert len(rs) == 0 or int(ro[-1]) == len(ri)
+        keep = [np.ascontiguousarray(requests[k], dtype=np.uint32)
+                for k in ("env_id", "min_version", "requestor_ip")]
+        n = len(keep[0])
+        ni = np.ascontiguousarray(n_immediate, dtype=np.uint32)
+        npf = np.ascontiguousarray(n_prefetch, dtype=np.uint32)
+        lfor = np.ascontiguousarray(lease_for, dtype=np.int64)
+        dl = np.ascontiguousarray(deadlines, dtype=np.int64)
+        tg = np.ascontiguousarray(tags, dtype=np.uint64)
+        assert len(ni) == n and len(npf) == n and len(lfor) == n and len(dl) == n and len(tg) == n
+        soa = TaskSoA(*[a.ctypes.data for a in keep])
+        row_off = np.concatenate([[0], np.cumsum(ni.astype(np.int64) + npf)]).astype(np.int64)
+        rows = max(int(row_off[-1]), 1)
+        status, n_granted = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        out, ids = np.empty(rows, np.uint32), np.empty(rows, np.uint64)
+        renewed = np.zeros(len(rid), np.uint8)
+        unknown = np.zeros(len(ri), np.uint8)
+        cap, rcap = max(self._max_waiting, 1), max(self._max_rows, 1)
+        res_tags, res_status = np.empty(cap, np.uint64), np.empty(cap, np.uint32)
+        res_n, res_first = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+        res_srv, res_ids = np.empty(rcap, np.uint32), np.empty(rcap, np.uint64)
+        n_leases, n_res, n_wait, n_wrows = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        if env_masks is None:
+            em, words = None, 1
+        else:
+            em = np.ascontiguousarray(env_masks, dtype=np.uint64).reshape(len(ui), -1)
+            words = em.shape[1]
+        self._check(lib().ydc_stream_tick_rpc(
+            self._h, ui.ctypes.data, ur.ctypes.data, None if em is None else em.ctypes.data, words, len(ui),
+            rel.ctypes.data, len(rel), rid.ctypes.data, rex.ctypes.data, len(rid), fid.ctypes.data, len(fid),
+            rs.ctypes.data, ro.ctypes.data, ri.ctypes.data, len(rs), C.byref(soa), ni.ctypes.data, npf.ctypes.data,
+            lfor.ctypes.data, dl.ctypes.data, tg.ctypes.data, n, int(now), status.ctypes.data, n_granted.ctypes.data,
+            out.ctypes.data, ids.ctypes.data, renewed.ctypes.data, unknown.ctypes.data, C.byref(n_leases),
+            res_tags.ctypes.data, res_status.ctypes.data, res_n.ctypes.data, res_first.ctypes.data,
+            res_srv.ctypes.data, res_ids.ctypes.data, C.byref(n_res), C.byref(n_wait), C.byref(n_wrows)),
+            "ydc_stream_tick_rpc")
+        k = n_res.value
+        g = int((res_first[:k].astype(np.int64) + res_n[:k]).max()) if k else 0
+        return {"status": status, "n_granted": n_granted, "row_off": row_off, "servants": out[:int(row_off[-1])],
+                "task_ids": ids[:int(row_off[-1])], "renewed": renewed, "report_unknown": unknown,
+                "n_leases": int(n_leases.value), "res_tags": res_tags[:k].copy(), "res_status": res_status[:k].copy(),
+                "res_n_granted": res_n[:k].copy(), "res_first": res_first[:k].copy(),
+                "res_servants": res_srv[:g].copy(), "res_task_ids": res_ids[:g].copy(),
+                "n_waiting": int(n_wait.value), "n_waiting_rows": int(n_wrows.value)}
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "wait_queue.h"
 #include "lease_table.h"
+#include "rpc_stream.h"
 #include "wait_lease.h"
 #include "tick_kernel.h"
 
@@ -125,6 +126,7 @@ struct TickArena {
   uint32_t *rep_srv, *rep_off;
   unsigned long long* rep_id;
   LeaseHdr* lh;
+  uint32_t *nimm, *npre;  // rpc mode: grants asked for per request (NULL in any other context)
 };
 }  // namespace
 
@@ -307,6 +309,20 @@ struct ydc_context {
     LeaseOutcome *h_lout = nullptr, *z_lout = nullptr;
     std::vector<uint32_t> rep_seen;  // per servant: rep_mark of the last report list that named it (host check)
     uint32_t rep_mark = 0;
+    // RPC mode (ydc_stream_begin_rpc; rpc_stream.h): a waiting and leased context whose request rows
+    // and entries of W are RPCs asking for several grants. max_tasks is max_requests there; the
+    // batch is the max_rows expanded rows (wt, wl.t_for, wt_out hold that many), W gains two count
+    // columns, and the answers have their own page-locked block. max_rows == 0: not such a context.
+    uint32_t max_rows = 0;
+    uint32_t n_wait_rows = 0;  // rows W's entries stand for after the last tick
+    uint32_t rows_new = 0;     // rows of the tick in flight's new requests
+    DevBuf<uint8_t> d_rpc;
+    RpcEntryCols rw{}, rp{};   // W; the tick's positions [max_waiting | max_requests]
+    RpcBatch rb{};
+    RpcState* rs = nullptr;
+    unsigned long long *lb_scan = nullptr, *lb_settle = nullptr, *lb_grant = nullptr;
+    uint8_t* h_rres = nullptr;  // page-locked: the RpcOut sections
+    RpcOut rh{}, rz{};          // ... at their host and device addresses
   } stream_mode;
   DevBuf<ClassRun> d_runs;
   DevBuf<uint8_t> d_dirty;
@@ -3882,7 +3898,7 @@ void stream_drop_graphs(ydc_context::Stream& sm) {
 void stream_release(ydc_context* c) {
   auto& sm = c->stream_mode;
   stream_drop_graphs(sm);
-  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres})
+  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres, sm.h_rres})
     if (h) (void)hipHostFree(h);
   sm = ydc_context::Stream{};  // (frees the device buffers: ydc_stream_end discards W)
 }
@@ -3894,8 +3910,11 @@ size_t section(size_t* off, size_t bytes) {
   return at;
 }
 
-// Requests one streaming batch places: the new ones, behind W's region in waiting mode.
-uint32_t stream_batch_n(const ydc_context::Stream& sm) { return sm.max_tasks + sm.max_waiting; }
+// Requests one streaming batch places: the new ones, behind W's region in waiting mode; the
+// expanded rows in rpc mode.
+uint32_t stream_batch_n(const ydc_context::Stream& sm) {
+  return sm.max_rows ? sm.max_rows : sm.max_tasks + sm.max_waiting;
+}
 
 // The tick's heartbeats and frees applied to the registry's device columns, from the arena as
 // `a` sees it (in place, or its device mirror).
@@ -3918,6 +3937,23 @@ void enqueue_wait_gather(ydc_context* c, const TickArena& a) {
              c->stream, sm.wq, sm.wt, WaitNew{a.env, a.minv, a.ip, a.dl, a.tag, a.now}, sm.max_waiting, N, sm.ws,
              sm.lookback, sm.max_leases ? 0u : sm.lookback_n,  // (with leases: k_lease_renew has cleared the words)
              WaitExtra{sm.wl.w_for, sm.wl.t_for, sm.wl.t_for ? a.lexp : nullptr});
+}
+
+// RPC mode: W's entries and the new requests expanded into the batch's rows (rpc_stream.h).
+void enqueue_rpc_expand(ydc_context* c, const TickArena& a) {
+  auto& sm = c->stream_mode;
+  const uint32_t P = sm.max_waiting + sm.max_tasks, NR = sm.max_rows;
+  YDC_LAUNCH(c, "k_rpc_scan", k_rpc_scan, dim3(ceil_div(P, kRpcTile)), dim3(256), 0, c->stream, sm.rw,
+             RpcNew{a.env, a.minv, a.ip, a.dl, a.tag, a.lexp, a.nimm, a.npre}, sm.rp, a.lh, sm.max_waiting, P, sm.ws,
+             sm.rs, sm.lb_scan, sm.rb.row_start);
+  YDC_LAUNCH(c, "k_rpc_expand", k_rpc_expand, dim3(ceil_div(NR, 256)), dim3(256), 0, c->stream, sm.rp, P, NR, sm.rb,
+             sm.rs);
+}
+
+// The tick's batch columns in HBM, in the context's mode.
+void enqueue_stream_gather(ydc_context* c, const TickArena& a) {
+  if (c->stream_mode.max_rows) enqueue_rpc_expand(c, a);
+  else enqueue_wait_gather(c, a);
 }
 
 // ... and behind the batch: new W, resolved list, the new requests' answers. prm: gated on the
@@ -3974,10 +4010,22 @@ void enqueue_wait_lease_commit(ydc_context* c, const TickArena& a, const DeviceP
              sm.z_task_id, sm.z_res_tag, sm.z_res_idx, sm.z_wout, sm.z_lout, prm, check_slot);
 }
 
+// RPC mode, behind the batch: ids and leases per granted row, then every RPC settled. prm as above.
+void enqueue_rpc_answer(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
+  auto& sm = c->stream_mode;
+  const uint32_t P = sm.max_waiting + sm.max_tasks, NR = sm.max_rows;
+  YDC_LAUNCH(c, "k_rpc_grant", k_rpc_grant, dim3(ceil_div(NR, kRpcTile)), dim3(256), 0, c->stream, sm.rb, NR,
+             sm.max_waiting, a.lh, sm.lt, sm.ls, sm.rs, sm.lb_grant, sm.rz, prm, check_slot);
+  YDC_LAUNCH(c, "k_rpc_settle", k_rpc_settle, dim3(ceil_div(P, kRpcTile)), dim3(256), 0, c->stream, sm.rp, sm.rb,
+             sm.max_waiting, P, NR, a.lh, sm.rw, sm.ws, sm.rs, sm.ls, sm.lb_settle, sm.rz, sm.z_lout, prm,
+             check_slot);
+}
+
 // The kernel behind the batch that answers the caller in the context's mode (none: a plain one).
 void enqueue_stream_answer(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
   auto& sm = c->stream_mode;
-  if (sm.max_waiting && sm.max_leases) enqueue_wait_lease_commit(c, a, prm, check_slot);
+  if (sm.max_rows) enqueue_rpc_answer(c, a, prm, check_slot);
+  else if (sm.max_waiting && sm.max_leases) enqueue_wait_lease_commit(c, a, prm, check_slot);
   else if (sm.max_waiting) enqueue_wait_compact(c, a.now, prm, check_slot);
   else if (sm.max_leases) enqueue_lease_grant(c, a, prm, check_slot);
 }
@@ -4003,7 +4051,7 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
   // Waiting mode: the batch is W's region and the new requests, gathered into HBM; its placement
   // stays there for k_wait_compact, which answers the caller.
   const bool waiting = sm.max_waiting != 0;
-  if (waiting) enqueue_wait_gather(c, sm.z);
+  if (waiting) enqueue_stream_gather(c, sm.z);
   ydc_task_soa d{sm.z.env, sm.z.minv, sm.z.ip};
   if (waiting) d = ydc_task_soa{sm.wt.env, sm.wt.minv, sm.wt.ip};
   if (rc == YDC_OK) rc = enqueue_front(c, plan, &d);
@@ -4113,14 +4161,25 @@ struct LeaseTick {
   uint32_t* out_n_leases;
 };
 
+// An rpc tick's own arguments (ydc_stream_tick_rpc), beside a waiting and a leased tick's.
+struct RpcTick {
+  const uint32_t *n_imm, *n_pre;
+  uint32_t *out_status, *out_n_granted;
+  uint32_t *out_resolved_n_granted, *out_resolved_first, *out_resolved_servant_idx;
+  uint32_t* out_n_waiting_rows;
+};
+
 // Capacities of a leased context (ydc_stream_begin_leased).
 struct LeaseCaps {
   uint32_t max_leases, max_renew, max_free, max_rep, max_rep_ids;
 };
 
 int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
-                 uint32_t max_waiting, const LeaseCaps* lc = nullptr) {
+                 uint32_t max_waiting, const LeaseCaps* lc = nullptr, uint32_t max_rows = 0) {
   if (!c || !max_tasks) return YDC_ERR_INVALID_ARGUMENT;
+  // (rpc mode: max_tasks is max_requests, the batch is the max_rows expanded rows)
+  if (max_rows && (max_rows > (1u << 30) || max_rows < max_tasks))
+    return fail(c, YDC_ERR_CAPACITY, "max_rows %u out of range (max_requests %u .. 2^30)", max_rows, max_tasks);
   if (lc && (!lc->max_leases || lc->max_leases > (1u << 30) || lc->max_rep_ids > 0x7FFFFFFFu))
     return fail(c, YDC_ERR_CAPACITY, "max_leases %u out of range (1 .. 2^30)", lc->max_leases);
   if ((uint64_t)max_tasks + max_waiting > 0x7FFFFFFFull)
@@ -4153,6 +4212,8 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
   const size_t o_rep_off = lc ? section(&off, ((size_t)lc->max_rep + 1) * 4) : 0;
   const size_t o_rep_id = lc ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
   const size_t o_lh = lc ? section(&off, sizeof(LeaseHdr)) : 0;
+  const size_t o_nimm = max_rows ? section(&off, (size_t)max_tasks * 4) : 0;
+  const size_t o_npre = max_rows ? section(&off, (size_t)max_tasks * 4) : 0;
   auto arena_at = [&](uint8_t* b) {
     TickArena a{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
                 (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
@@ -4168,11 +4229,16 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
       a.rep_id = (unsigned long long*)(b + o_rep_id);
       a.lh = (LeaseHdr*)(b + o_lh);
     }
+    if (max_rows) {
+      a.nimm = (uint32_t*)(b + o_nimm);
+      a.npre = (uint32_t*)(b + o_npre);
+    }
     return a;
   };
   sm.in_bytes = off;
   HIP_TRY(c, hipHostMalloc((void**)&sm.h_in, sm.in_bytes, hipHostMallocCoherent | hipHostMallocMapped));
-  HIP_TRY(c, hipHostMalloc((void**)&sm.h_out, std::max<size_t>((size_t)max_tasks * 4, 16),
+  const size_t n_out = max_rows ? max_rows : max_tasks;  // answers per tick (rpc mode: one per row)
+  HIP_TRY(c, hipHostMalloc((void**)&sm.h_out, std::max<size_t>(n_out * 4, 16),
                            hipHostMallocCoherent | hipHostMallocMapped));
   uint8_t* z_in = nullptr;
   HIP_TRY(c, hipHostGetDevicePointer((void**)&z_in, sm.h_in, 0));
@@ -4186,7 +4252,7 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     sm.max_waiting = max_waiting;
     // HBM: W (max_waiting entries), the tick's batch (max_waiting + max_tasks) with its placement,
     // the queue's counters and k_wait_compact's look-back words.
-    const size_t NB = (size_t)max_tasks + max_waiting;
+    const size_t NB = max_rows ? (size_t)max_rows : (size_t)max_tasks + max_waiting;
     sm.lookback_n = (uint32_t)((NB + kWaitTile - 1) / kWaitTile);
     size_t w_off = 0;
     auto wsec = [&](size_t bytes) { return section(&w_off, bytes); };
@@ -4241,6 +4307,8 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     while (cap < 2 * (size_t)lc->max_leases) cap <<= 1, ++cap_bits;
     // (with a waiting queue: two words per tile of the whole batch, wait_lease.h)
     sm.lookback_n = max_waiting ? 2 * ceil_div(max_tasks + max_waiting, kWaitTile) : ceil_div(max_tasks, kLeaseTile);
+    // (rpc mode: the scan's and the settling's words per tile of positions, the grants' per tile of rows)
+    if (max_rows) sm.lookback_n = 2 * ceil_div(max_tasks + max_waiting, kRpcTile) + ceil_div(max_rows, kRpcTile);
     size_t l_off = 0;
     auto lsec = [&](size_t bytes) { return section(&l_off, bytes); };
     const size_t o_key = lsec(cap * 8), o_exp = lsec(cap * 8), o_srv = lsec(cap * 4), o_st = lsec(cap * 4);
@@ -4259,7 +4327,7 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     HIP_TRY(c, hipMemsetAsync(sm.lt.key, 0xFF, cap * 8, c->stream));
     // Page-locked results: task ids | renewed | report_unknown | outcome block.
     size_t r_off = 0;
-    const size_t r_id = section(&r_off, (size_t)max_tasks * 8), r_ren = section(&r_off, lc->max_renew);
+    const size_t r_id = section(&r_off, n_out * 8), r_ren = section(&r_off, lc->max_renew);
     const size_t r_unk = section(&r_off, lc->max_rep_ids), r_out = section(&r_off, sizeof(LeaseOutcome));
     HIP_TRY(c, hipHostMalloc((void**)&sm.h_lres, r_off, hipHostMallocCoherent | hipHostMallocMapped));
     uint8_t* z_res = nullptr;
@@ -4273,6 +4341,51 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     sm.z_unknown = z_res + r_unk;
     sm.z_lout = (LeaseOutcome*)(z_res + r_out);
     std::memset(sm.h_lout, 0, sizeof(LeaseOutcome));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  if (max_rows) {
+    sm.max_rows = max_rows;
+    const size_t MW = max_waiting, P = MW + max_tasks, NR = max_rows;
+    const uint32_t tiles_p = ceil_div((uint32_t)P, kRpcTile);
+    sm.lb_scan = sm.lookback;
+    sm.lb_settle = sm.lookback + tiles_p;
+    sm.lb_grant = sm.lookback + 2 * (size_t)tiles_p;
+    // HBM: W's two count columns, the positions' eight columns, row_start, rank, the tickets.
+    size_t d_off = 0;
+    auto dsec = [&](size_t bytes) { return section(&d_off, bytes); };
+    const size_t o_wi = dsec(MW * 4), o_wp = dsec(MW * 4);
+    const size_t o_p4[5] = {dsec(P * 4), dsec(P * 4), dsec(P * 4), dsec(P * 4), dsec(P * 4)};
+    const size_t o_p8[3] = {dsec(P * 8), dsec(P * 8), dsec(P * 8)};
+    const size_t o_rs = dsec((P + 1) * 4), o_rk = dsec((NR + 1) * 4), o_st = dsec(sizeof(RpcState));
+    HIP_TRY(c, sm.d_rpc.reserve(d_off));
+    uint8_t* b = sm.d_rpc.p;
+    HIP_TRY(c, hipMemsetAsync(b, 0, d_off, c->stream));
+    sm.rw = RpcEntryCols{sm.wq.env, sm.wq.minv, sm.wq.ip, sm.wq.deadline, sm.wq.tag, sm.wl.w_for,
+                         (uint32_t*)(b + o_wi), (uint32_t*)(b + o_wp)};
+    sm.rp = RpcEntryCols{(uint32_t*)(b + o_p4[0]), (uint32_t*)(b + o_p4[1]), (uint32_t*)(b + o_p4[2]),
+                         (int64_t*)(b + o_p8[0]), (uint64_t*)(b + o_p8[1]), (int64_t*)(b + o_p8[2]),
+                         (uint32_t*)(b + o_p4[3]), (uint32_t*)(b + o_p4[4])};
+    sm.rb = RpcBatch{sm.wt.env, sm.wt.minv, sm.wt.ip, sm.wl.t_for, sm.wt_out, (uint32_t*)(b + o_rk),
+                     (uint32_t*)(b + o_rs)};
+    sm.rs = (RpcState*)(b + o_st);
+    // Page-locked results beside h_out / h_task_id (the new requests' rows): status and count per
+    // request, the resolved list, W's grants packed, the outcome block.
+    size_t r_off = 0;
+    auto rsec = [&](size_t bytes) { return section(&r_off, bytes); };
+    const size_t r_st = rsec((size_t)max_tasks * 4), r_ng = rsec((size_t)max_tasks * 4);
+    const size_t r_tag = rsec(MW * 8), r_rs = rsec(MW * 4), r_rn = rsec(MW * 4), r_rf = rsec(MW * 4);
+    const size_t r_srv = rsec(NR * 4), r_id = rsec(NR * 8), r_out = rsec(sizeof(RpcOutcome));
+    HIP_TRY(c, hipHostMalloc((void**)&sm.h_rres, r_off, hipHostMallocCoherent | hipHostMallocMapped));
+    uint8_t* z = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&z, sm.h_rres, 0));
+    auto out_at = [&](uint8_t* q, uint32_t* srv, unsigned long long* id) {
+      return RpcOut{srv, id, (uint32_t*)(q + r_st), (uint32_t*)(q + r_ng), (uint64_t*)(q + r_tag),
+                    (uint32_t*)(q + r_rs), (uint32_t*)(q + r_rn), (uint32_t*)(q + r_rf), (uint32_t*)(q + r_srv),
+                    (unsigned long long*)(q + r_id), (RpcOutcome*)(q + r_out)};
+    };
+    sm.rh = out_at(sm.h_rres, sm.h_out, sm.h_task_id);
+    sm.rz = out_at(z, sm.z_out, sm.z_task_id);
+    std::memset(sm.rh.outcome, 0, sizeof(RpcOutcome));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
@@ -4309,7 +4422,7 @@ int ydc_stream_waiting_take(ydc_context* c, uint64_t* out_tags, uint32_t cap, ui
   if (n) HIP_TRY(c, hipMemcpy(out_tags, sm.wq.tag, (size_t)n * 8, hipMemcpyDeviceToHost));
   HIP_TRY(c, hipMemsetAsync(&sm.ws->count, 0, 4, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  sm.n_waiting = 0;
+  sm.n_waiting = sm.n_wait_rows = 0;
   return YDC_OK;
 }
 
@@ -4389,6 +4502,55 @@ static int stream_lease_finish(ydc_context* c, const LeaseTick* lt, uint32_t n_t
   return YDC_OK;
 }
 
+// RPC mode, after the step: every list to the caller, the host's mirrors of |W|, rows(W) and |L|,
+// and the statistics (n_tasks counts the batch's rows; padding counts nowhere).
+static int stream_rpc_finish(ydc_context* c, const WaitTick* wt, const LeaseTick* lt, const RpcTick* rt,
+                             uint32_t n_req, uint32_t* out_servant_idx) {
+  auto& sm = c->stream_mode;
+  const LeaseOutcome& lo = *sm.h_lout;
+  const RpcOutcome& o = *sm.rh.outcome;
+  if (lo.tick_no != sm.lease_tick || lo.n_leases > sm.max_leases || o.n_waiting > sm.max_waiting ||
+      o.n_resolved > sm.max_waiting || o.n_rows > sm.max_rows || o.n_res_grants > sm.max_rows)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "rpc stream: outcome of tick %u (expected %u), %u leases, %u waiting, %u rows",
+                lo.tick_no, sm.lease_tick, lo.n_leases, o.n_waiting, o.n_rows);
+  if (sm.rows_new) {
+    std::memcpy(out_servant_idx, sm.rh.new_srv, (size_t)sm.rows_new * 4);
+    std::memcpy(lt->out_task_id, sm.rh.new_id, (size_t)sm.rows_new * 8);
+  }
+  if (n_req) {
+    std::memcpy(rt->out_status, sm.rh.status, (size_t)n_req * 4);
+    std::memcpy(rt->out_n_granted, sm.rh.n_granted, (size_t)n_req * 4);
+  }
+  if (o.n_resolved) {
+    std::memcpy(wt->out_resolved_tags, sm.rh.res_tag, (size_t)o.n_resolved * 8);
+    std::memcpy(wt->out_resolved_idx, sm.rh.res_status, (size_t)o.n_resolved * 4);
+    std::memcpy(rt->out_resolved_n_granted, sm.rh.res_n, (size_t)o.n_resolved * 4);
+    std::memcpy(rt->out_resolved_first, sm.rh.res_first, (size_t)o.n_resolved * 4);
+  }
+  if (o.n_res_grants) {
+    std::memcpy(rt->out_resolved_servant_idx, sm.rh.res_srv, (size_t)o.n_res_grants * 4);
+    std::memcpy(wt->out_resolved_task_id, sm.rh.res_id, (size_t)o.n_res_grants * 8);
+  }
+  if (lt->n_renew) std::memcpy(lt->out_renewed, sm.h_renewed, lt->n_renew);
+  const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
+  if (n_ids) std::memcpy(lt->out_unknown, sm.h_unknown, n_ids);
+  *wt->out_n_resolved = o.n_resolved;
+  *wt->out_n_waiting = o.n_waiting;
+  *rt->out_n_waiting_rows = o.n_waiting_rows;
+  *lt->out_n_leases = lo.n_leases;
+  c->stats.n_tasks = o.n_rows;
+  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_rows - o.n_rows);  // padding
+  c->stats.leases_expired = lo.expired;
+  c->stats.leases_swept = lo.swept;
+  c->stats.leases_freed = lo.freed;
+  c->stats.renewals_refused = lo.renew_refused;
+  sm.n_waiting = o.n_waiting;
+  sm.n_wait_rows = o.n_waiting_rows;
+  sm.n_leases = lo.n_leases;
+  sm.last_now = lt->now;
+  return YDC_OK;
+}
+
 // After a placement the host ran itself: the answers into the page-locked result array — in
 // waiting mode by k_wait_compact, in leased mode by k_lease_grant, with both by
 // k_wait_lease_commit (ungated), otherwise by a copy. `a`: the arena where the step
@@ -4410,9 +4572,11 @@ static int stream_answer_eager(ydc_context* c, const TickArena& a) {
 // The end of every tick: the statistics of the placement (p, rounds) without the padding, waiting
 // mode's resolved list, the answers to the caller.
 static int stream_tick_finish(ydc_context* c, const BatchPlan& p, uint32_t rounds, uint32_t n_tasks,
-                              uint32_t* out_servant_idx, const WaitTick* wt, const LeaseTick* lt) {
+                              uint32_t* out_servant_idx, const WaitTick* wt, const LeaseTick* lt,
+                              const RpcTick* rt) {
   auto& sm = c->stream_mode;
   fill_stats(c, p, rounds);
+  if (rt) return stream_rpc_finish(c, wt, lt, rt, n_tasks, out_servant_idx);
   c->stats.n_tasks = n_tasks;
   c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
   if (wt)
@@ -4427,9 +4591,13 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
                        const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
                        const uint32_t* release_servant_idx, uint32_t n_rel, const ydc_task_soa* tasks,
                        uint32_t n_tasks, uint32_t* out_servant_idx, const WaitTick* wt,
-                       const LeaseTick* lt = nullptr) {
+                       const LeaseTick* lt = nullptr, const RpcTick* rt = nullptr) {
   if (!c || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
+  if (sm.max_rows && !rt)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_rpc takes ydc_stream_tick_rpc");
+  if (rt && !sm.max_rows)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_rpc on a context begun without ydc_stream_begin_rpc");
   if (sm.max_leases && sm.max_waiting && !(wt && lt))
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_waiting_leased takes "
                 "ydc_stream_tick_waiting_leased");
@@ -4476,12 +4644,32 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
         !lt->out_n_leases)
       return YDC_ERR_INVALID_ARGUMENT;
     // (with a waiting queue: every waiting entry may be granted in this tick)
-    if (wt && (uint64_t)sm.n_leases + sm.n_waiting + n_tasks > sm.max_leases)
+    if (!rt && wt && (uint64_t)sm.n_leases + sm.n_waiting + n_tasks > sm.max_leases)
       return fail(c, YDC_ERR_CAPACITY, "%u leases + %u waiting + %u new requests > max_leases %u", sm.n_leases,
                   sm.n_waiting, n_tasks, sm.max_leases);
-    if ((uint64_t)sm.n_leases + n_tasks > sm.max_leases)
+    if (!rt && (uint64_t)sm.n_leases + n_tasks > sm.max_leases)
       return fail(c, YDC_ERR_CAPACITY, "%u leases + %u new requests > max_leases %u", sm.n_leases, n_tasks,
                   sm.max_leases);
+    if (rt) {
+      // (every row of W's entries and of the new requests may be granted in this tick)
+      if ((n_tasks && (!rt->n_imm || !rt->n_pre || !rt->out_status || !rt->out_n_granted)) ||
+          !rt->out_resolved_n_granted || !rt->out_resolved_first || !rt->out_resolved_servant_idx ||
+          !rt->out_n_waiting_rows)
+        return YDC_ERR_INVALID_ARGUMENT;
+      uint64_t rows = 0;
+      for (uint32_t i = 0; i < n_tasks; ++i) {
+        const uint64_t r = (uint64_t)rt->n_imm[i] + rt->n_pre[i];
+        if (!r) return fail(c, YDC_ERR_INVALID_ARGUMENT, "request %u asks for no grant (n_immediate + n_prefetch == 0)", i);
+        rows += r;
+      }
+      if (sm.n_wait_rows + rows > sm.max_rows)
+        return fail(c, YDC_ERR_CAPACITY, "%u waiting rows + %llu new rows > max_rows %u", sm.n_wait_rows,
+                    (unsigned long long)rows, sm.max_rows);
+      if ((uint64_t)sm.n_leases + sm.n_wait_rows + rows > sm.max_leases)
+        return fail(c, YDC_ERR_CAPACITY, "%u leases + %u waiting rows + %llu new rows > max_leases %u", sm.n_leases,
+                    sm.n_wait_rows, (unsigned long long)rows, sm.max_leases);
+      sm.rows_new = (uint32_t)rows;
+    }
     if (lt->now < sm.last_now)
       return fail(c, YDC_ERR_INVALID_ARGUMENT, "now %lld is before the previous tick's %lld", (long long)lt->now,
                   (long long)sm.last_now);
@@ -4592,6 +4780,13 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     if ((++sm.lease_tick & kLeaseStamp) == 0) ++sm.lease_tick;
     *h.lh = LeaseHdr{lt->now, lt->n_renew, lt->n_free, lt->n_rep, n_ids, sm.lease_tick, 0};
   }
+  if (rt) {
+    if (n_tasks) {
+      std::memcpy(h.nimm, rt->n_imm, (size_t)n_tasks * 4);
+      std::memcpy(h.npre, rt->n_pre, (size_t)n_tasks * 4);
+    }
+    for (uint32_t i = n_tasks; i < sm.max_tasks; ++i) h.nimm[i] = h.npre[i] = 0;  // (no rows: padding)
+  }
   // The ticks placed eagerly place this batch from the arena's device mirror. Waiting mode: the
   // batch is W's region + the new requests in HBM (k_wait_gather), its placement goes to wt_out
   // and k_wait_compact answers the caller.
@@ -4606,13 +4801,13 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
     if (lt) enqueue_lease_pre(c, sm.d);
     enqueue_apply_tick(c, sm.d);
-    if (wt) enqueue_wait_gather(c, sm.d);
+    if (wt) enqueue_stream_gather(c, sm.d);
     BatchPlan pe;
     uint32_t rounds_e = 0;
     if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &pe, &rounds_e))
       return rc;
     if (int rc = stream_answer_eager(c, sm.d)) return rc;
-    return stream_tick_finish(c, pe, rounds_e, n_tasks, out_servant_idx, wt, lt);
+    return stream_tick_finish(c, pe, rounds_e, n_tasks, out_servant_idx, wt, lt, rt);
   }
   const bool second = sm.swaps && c->d_running.p == sm.run_b;
   if (sm.swaps && !second && c->d_running.p != sm.run_a)
@@ -4649,7 +4844,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &p2, &rounds))
       return rc;
     if (int rc = stream_answer_eager(c, sm.d)) return rc;
-    return stream_tick_finish(c, p2, rounds, n_tasks, out_servant_idx, wt, lt);
+    return stream_tick_finish(c, p2, rounds, n_tasks, out_servant_idx, wt, lt, rt);
   }
   if (p.wave_path) {
     if (c->h_prm->n_changed[(sm.passes - 1) & 63] != 0) {
@@ -4678,7 +4873,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       }
     }
   }
-  return stream_tick_finish(c, p, rounds, n_tasks, out_servant_idx, wt, lt);
+  return stream_tick_finish(c, p, rounds, n_tasks, out_servant_idx, wt, lt, rt);
 }
 
 int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
@@ -4742,6 +4937,39 @@ int ydc_stream_tick_waiting_leased(ydc_context* c, const uint32_t* upd_idx, cons
                     out_resolved_task_id};
   return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
                      n_tasks, out_servant_idx, &wt, &lt);
+}
+
+int ydc_stream_begin_rpc(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_requests,
+                         uint32_t max_rows, uint32_t max_waiting, uint32_t max_leases, uint32_t max_renewals,
+                         uint32_t max_frees, uint32_t max_reports, uint32_t max_report_ids) {
+  if (!c || !max_requests || !max_rows || !max_waiting || !max_leases) return YDC_ERR_INVALID_ARGUMENT;
+  const LeaseCaps lc{max_leases, max_renewals, max_frees, max_reports, max_report_ids};
+  return stream_begin(c, max_updates, max_releases, max_requests, max_waiting, &lc, max_rows);
+}
+
+int ydc_stream_tick_rpc(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
+                        const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
+                        const uint32_t* release_servant_idx, uint32_t n_rel, const uint64_t* renew_task_id,
+                        const int64_t* renew_expires_at, uint32_t n_renew, const uint64_t* free_task_id,
+                        uint32_t n_free, const uint32_t* report_servant_idx, const uint32_t* report_off,
+                        const uint64_t* report_task_id, uint32_t n_rep, const ydc_task_soa* requests,
+                        const uint32_t* n_immediate, const uint32_t* n_prefetch, const int64_t* lease_for,
+                        const int64_t* deadlines, const uint64_t* tags, uint32_t n_req, int64_t now,
+                        uint32_t* out_status, uint32_t* out_n_granted, uint32_t* out_servant_idx,
+                        uint64_t* out_task_id, uint8_t* out_renewed, uint8_t* out_report_unknown,
+                        uint32_t* out_n_leases, uint64_t* out_resolved_tags, uint32_t* out_resolved_status,
+                        uint32_t* out_resolved_n_granted, uint32_t* out_resolved_first,
+                        uint32_t* out_resolved_servant_idx, uint64_t* out_resolved_task_id,
+                        uint32_t* out_n_resolved, uint32_t* out_n_waiting, uint32_t* out_n_waiting_rows) {
+  const LeaseTick lt{renew_task_id, renew_expires_at, n_renew, free_task_id, n_free, report_servant_idx,
+                     report_off, report_task_id, n_rep, lease_for, now, out_task_id, out_renewed,
+                     out_report_unknown, out_n_leases};
+  const WaitTick wt{deadlines, tags, now, out_resolved_tags, out_resolved_status, out_n_resolved, out_n_waiting,
+                    out_resolved_task_id};
+  const RpcTick rt{n_immediate, n_prefetch, out_status, out_n_granted, out_resolved_n_granted, out_resolved_first,
+                   out_resolved_servant_idx, out_n_waiting_rows};
+  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, requests,
+                     n_req, out_servant_idx, &wt, &lt, &rt);
 }
 
 // The table as it is, in id order: one copy of the columns, the live slots picked and sorted here.

@@ -65,3 +65,18 @@ class EventStream:
         sv = {k: v.copy() for k, v in self.sv.items()}
         sv["running_tasks"] = self.running.astype(np.uint32)
         return sv
+
+
+def rpc_grants(result, i):
+    """Views of a stream_tick_rpc result (binding.Context.stream_tick_rpc): the (servants, task ids)
+    granted to new request i: the first n_granted[i] rows at its offset in the expanded layout."""
+    a = int(result["row_off"][i])
+    b = a + int(result["n_granted"][i])
+    return result["servants"][a:b], result["task_ids"][a:b]
+
+
+def rpc_resolved_grants(result, j):
+    """... and of the j-th waiting RPC answered in that tick (packed behind res_first[j])."""
+    a = int(result["res_first"][j])
+    b = a + int(result["res_n_granted"][j])
+    return result["res_servants"][a:b], result["res_task_ids"][a:b]
