@@ -88,6 +88,16 @@ struct DeviceParams {
   uint32_t t_begin_lo, t_begin_hi, t_end_lo, t_end_hi;
 };
 
+// The gates of what is pre-launched behind the matching passes. passes_final: the passes converged
+// (check_slot: the last pass's n_changed slot, kNone: nothing to check) and every rank's key window
+// covered what its requests reached. batch_is_final: and the bin sort's workspace held every slot.
+__device__ __forceinline__ bool passes_final(const DeviceParams* prm, uint32_t check_slot) {
+  return (check_slot == kNone || prm->n_changed[check_slot] == 0) && !prm->window_miss;
+}
+__device__ __forceinline__ bool batch_is_final(const DeviceParams* prm, uint32_t check_slot) {
+  return passes_final(prm, check_slot) && !prm->overflow;
+}
+
 // Measurement builds only (`make probe`): wall-clock stamps the kernels leave behind
 // (match_kernel.h: k_match_pass phases per chunk; bin_sort.h: the front's workgroups and
 // k_bin_sort's phases; wide_kernel.h: the walk's accumulators). Compiled out of the product.
@@ -1346,8 +1356,7 @@ __global__ __launch_bounds__(256) void k_finalize(ServantTable sv, const uint32_
                                                   uint32_t rank_stride) {
   // Pre-launched behind the matching passes: only takes effect once they have converged (and,
   // with a sharded sort, only if every rank's key window covered what its requests reached).
-  const bool final = (check_slot == kNone || prm->n_changed[check_slot] == 0) && !prm->window_miss &&
-                     !(ra.pipelined && (prm->pipeline_broken || prm->overflow));
+  const bool final = passes_final(prm, check_slot) && !(ra.pipelined && (prm->pipeline_broken || prm->overflow));
   if (ra.pipelined && !final && blockIdx.x == req_blocks && threadIdx.x == 0)
     __hip_atomic_store(&prm->pipeline_broken, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (blockIdx.x < req_blocks) {

@@ -19,10 +19,9 @@
 //   k_lease_sweep    one pass over the table: overdue -> zombie; zombie whose servant reported
 //                    this tick without listing it -> freed.
 //   (k_apply_tick, front, passes, k_finalize place the tick's requests as in a plain tick)
-//   k_lease_grant    gated like k_finalize: a stable scan of "granted" over the placed batch
-//                    (decoupled look-back, as k_wait_compact), out_task_id[i] = next_id + rank,
-//                    the lease inserted; the last workgroup bumps next_id and |L| and stores the
-//                    tick's outcome block to page-locked memory.
+//   k_lease_grant    the commit pass of wait_lease.h in its form without a queue: out_task_id[i]
+//                    = next_id + rank among the granted, the lease inserted; the last workgroup
+//                    bumps next_id and |L| and stores the tick's outcome block to page-locked memory.
 //
 // running_tasks: the decrements of frees and sweeps are atomicSub on the column k_apply_tick's
 // releases decrement too (the same instruction, the same column; the kernels run one after another
@@ -44,7 +43,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
-#include "wait_queue.h"
+#include "stream_tile.h"
 
 namespace ydc {
 
@@ -52,7 +51,7 @@ constexpr unsigned long long kLeaseEmpty = ~0ull;
 constexpr uint32_t kLeaseLive = 1u << 31, kLeaseZombie = 1u << 30;
 // Tick number of the last report that listed the lease (mod 2^30; a tick number is never 0 there).
 constexpr uint32_t kLeaseStamp = kLeaseZombie - 1;
-constexpr uint32_t kLeaseTile = 1024;  // positions per workgroup of k_lease_sweep / k_lease_grant (256 x 4)
+constexpr uint32_t kLeaseTile = 1024;  // positions per workgroup of k_lease_sweep and the commit pass (256 x 4)
 
 struct LeaseCols {
   unsigned long long* key;  // task id, kLeaseEmpty: free slot
@@ -73,8 +72,8 @@ struct LeaseState {
   unsigned long long next_id;
   uint32_t n_leases;  // |L|
   uint32_t max_disp;  // largest displacement from the home slot any insert has used
-  uint32_t ticket;    // k_lease_grant workgroups started
-  uint32_t expired, swept, freed, renew_refused;  // of the tick in flight (k_lease_grant clears them)
+  uint32_t ticket;    // workgroups of the commit pass started
+  uint32_t expired, swept, freed, renew_refused;  // of the tick in flight (lease_close_tick clears them)
   uint32_t pad;
 };
 
@@ -86,7 +85,7 @@ struct LeaseHdr {
   uint32_t pad;
 };
 
-// Page-locked: what the host reads after the tick (stored by the last k_lease_grant workgroup).
+// Page-locked: what the host reads after the tick (lease_close_tick).
 struct LeaseOutcome {
   unsigned long long next_id;
   uint32_t n_leases, expired, swept, freed, renew_refused;
@@ -115,13 +114,48 @@ __device__ __forceinline__ uint32_t lease_find(const LeaseCols& L, const LeaseSt
   return kNone;
 }
 
+// A new lease in the first free slot from its home on. Always ends: the host checks before the tick
+// that |L| plus everything the tick can grant is <= max_leases <= cap / 2.
+__device__ __forceinline__ void lease_insert(const LeaseCols& L, LeaseState* st, unsigned long long id,
+                                             int64_t expires, uint32_t servant) {
+  const uint32_t h = lease_home(L, id);
+  for (uint32_t d = 0; d <= L.mask; ++d) {
+    const uint32_t slot = (h + d) & L.mask;
+    if (L.key[slot] != kLeaseEmpty || atomicCAS(&L.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
+    L.expires[slot] = expires;
+    L.servant[slot] = servant;
+    L.state[slot] = kLeaseLive;
+    if (d) atomicMax(&st->max_disp, d);
+    return;
+  }
+}
+
+// The last workgroup of the last kernel of a leased tick: |L|, the outcome block, the tick's
+// counters cleared. Returns the new next_id, which the caller stores to LeaseState.
+__device__ __forceinline__ unsigned long long lease_close_tick(LeaseState* st, const LeaseHdr* hdr, LeaseOutcome* lout,
+                                                               uint32_t granted, unsigned long long next_id_before) {
+  const uint32_t n = st->n_leases - st->freed - st->swept + granted;
+  const unsigned long long next = next_id_before + granted;
+  lout->next_id = next;
+  lout->n_leases = n;
+  lout->expired = st->expired;
+  lout->swept = st->swept;
+  lout->freed = st->freed;
+  lout->renew_refused = st->renew_refused;
+  lout->tick_no = hdr->tick_no;
+  st->n_leases = n;
+  st->expired = st->swept = st->freed = st->renew_refused = 0;
+  return next;
+}
+
 // One atomicAdd per wave for a per-lane 0/1.
 __device__ __forceinline__ void wave_count(uint32_t* counter, bool flag) {
   const unsigned long long m = __ballot(flag);
   if (m && lane_id() == (uint32_t)__builtin_ctzll(m)) atomicAdd(counter, (uint32_t)__popcll(m));
 }
 
-// Thread per renewal (and per look-back word of k_lease_grant, which this first launch clears).
+// Thread per renewal (and per look-back word of the kernels behind the batch, which this first
+// launch clears).
 __global__ __launch_bounds__(256) void k_lease_renew(LeaseCols L, LeaseState* st, LeaseIn in, uint32_t max_renew,
                                                      uint32_t* ren_slot, uint8_t* out_renewed,
                                                      unsigned long long* lookback, uint32_t n_lookback) {
@@ -252,117 +286,6 @@ __global__ __launch_bounds__(256) void k_lease_sweep(LeaseCols L, LeaseState* st
   __syncthreads();
   if (threadIdx.x == 0 && s_cnt[0]) atomicAdd(&st->expired, s_cnt[0]);
   if (threadIdx.x == 1 && s_cnt[1]) atomicAdd(&st->swept, s_cnt[1]);
-}
-
-// ceil(N / kLeaseTile) workgroups of 256 threads over the positions of a placed batch; thread i of
-// a workgroup owns four consecutive positions. prm == NULL: ungated (the host has just placed the
-// batch itself). The answers and ids go to page-locked memory once, 16 / 32 bytes per thread.
-__global__ __launch_bounds__(256) void k_lease_grant(const uint32_t* placed, uint32_t N, const int64_t* lease_exp,
-                                                     const LeaseHdr* hdr, LeaseCols L, LeaseState* st,
-                                                     unsigned long long* lookback, uint32_t* out_idx,
-                                                     unsigned long long* out_task_id, LeaseOutcome* outcome,
-                                                     const DeviceParams* prm, uint32_t check_slot) {
-  if (prm) {
-    const bool final = (check_slot == kNone || prm->n_changed[check_slot] == 0) && !prm->window_miss &&
-                       !prm->overflow;
-    if (!final) return;  // (every workgroup alike: L and next_id stay as they are)
-  }
-  __shared__ uint32_t s_bid, s_pre;
-  __shared__ unsigned long long s_next;
-  __shared__ uint32_t lds[17];
-  if (threadIdx.x == 0) {
-    // next_id is read before this workgroup publishes anything; the last workgroup changes it only
-    // after every other one has published.
-    s_next = __hip_atomic_load(&st->next_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_bid = atomicAdd(&st->ticket, 1u);
-  }
-  __syncthreads();
-  const uint32_t bid = s_bid;
-  const uint32_t j0 = bid * kLeaseTile + threadIdx.x * 4;
-  uint32_t r[4];
-  uint32_t n_gr = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    r[i] = j0 + i < N ? placed[j0 + i] : kIdxEnvNotFound;
-    n_gr += r[i] < kIdxWaiting;
-  }
-  uint32_t tot;
-  const uint32_t ex = block_exclusive_scan(n_gr, lds, &tot);
-  if (threadIdx.x < 64) {
-    // Decoupled look-back by wave 0 (the words of wait_queue.h with one count in them).
-    const uint32_t lane = threadIdx.x;
-    uint32_t pre = 0;
-    if (bid == 0) {
-      if (lane == 0) __hip_atomic_store(&lookback[0], kLbInclusive | tot, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      if (lane == 0) __hip_atomic_store(&lookback[bid], kLbAggregate | tot, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      int look = (int)bid - 1;
-      while (true) {
-        const int q = look - (int)lane;
-        unsigned long long w = kLbInclusive;  // (before block 0: an empty inclusive prefix)
-        while (true) {
-          if (q >= 0) w = __hip_atomic_load(&lookback[q], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-          if (__ballot((w >> 62) == 0) == 0) break;
-          __builtin_amdgcn_s_sleep(1);
-        }
-        const unsigned long long incl = __ballot((w >> 62) == 2);
-        const uint32_t upto = incl ? (uint32_t)__builtin_ctzll(incl) : 63u;
-        pre += wave_sum_u32(lane <= upto ? (uint32_t)(w & 0xFFFFFFFFull) : 0u);
-        if (incl) break;
-        look -= 64;
-      }
-      if (lane == 0)
-        __hip_atomic_store(&lookback[bid], kLbInclusive | (unsigned long long)(pre + tot), __ATOMIC_RELEASE,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (lane == 0) {
-      s_pre = pre;
-      if (bid == gridDim.x - 1) {  // the last workgroup: the totals
-        const uint32_t granted = pre + tot;
-        const uint32_t n = st->n_leases - st->freed - st->swept + granted;
-        const unsigned long long next = s_next + granted;
-        outcome->next_id = next;
-        outcome->n_leases = n;
-        outcome->expired = st->expired;
-        outcome->swept = st->swept;
-        outcome->freed = st->freed;
-        outcome->renew_refused = st->renew_refused;
-        outcome->tick_no = hdr->tick_no;
-        st->n_leases = n;
-        st->expired = st->swept = st->freed = st->renew_refused = 0;
-        __hip_atomic_store(&st->next_id, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  }
-  __syncthreads();
-  unsigned long long id = s_next + s_pre + ex;
-  unsigned long long ids[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ids[i] = kLeaseEmpty;
-    if (r[i] >= kIdxWaiting) continue;
-    ids[i] = id++;
-    const uint32_t h = lease_home(L, ids[i]);
-    for (uint32_t d = 0; d <= L.mask; ++d) {  // (always ends: |L| + n <= max_leases <= cap / 2 is checked before the tick)
-      const uint32_t slot = (h + d) & L.mask;
-      if (L.key[slot] != kLeaseEmpty || atomicCAS(&L.key[slot], kLeaseEmpty, ids[i]) != kLeaseEmpty) continue;
-      L.expires[slot] = lease_exp[j0 + i];
-      L.servant[slot] = r[i];
-      L.state[slot] = kLeaseLive;
-      if (d) atomicMax(&st->max_disp, d);
-      break;
-    }
-  }
-  if (j0 + 3 < N) {
-    *reinterpret_cast<uint4*>(out_idx + j0) = make_uint4(r[0], r[1], r[2], r[3]);
-    *reinterpret_cast<ulonglong2*>(out_task_id + j0) = make_ulonglong2(ids[0], ids[1]);
-    *reinterpret_cast<ulonglong2*>(out_task_id + j0 + 2) = make_ulonglong2(ids[2], ids[3]);
-  } else {
-    for (int i = 0; i < 4 && j0 + i < N; ++i) {
-      out_idx[j0 + i] = r[i];
-      out_task_id[j0 + i] = ids[i];
-    }
-  }
 }
 
 // ydc_remove_servants with a leased stream open (UnsafeSweepOrphans, task_dispatcher.cc:478-496):

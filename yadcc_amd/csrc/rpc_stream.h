@@ -17,7 +17,7 @@
 //                  the tick's total up to max_rows are a digest nobody has.
 //   (front, passes, k_finalize place the max_rows rows as one batch)
 //   k_rpc_grant    thread per row, gated like k_finalize: stable scan of "granted", id = next_id +
-//                  rank, the lease (lease_home, CAS probe, max_disp of lease_table.h), the exclusive
+//                  rank, the lease (lease_insert of lease_table.h), the exclusive
 //                  rank per row to HBM, servants and ids to page-locked memory: W's region packed by
 //                  rank (it leads the batch, so an entry's first grant is the rank of its first
 //                  row), the new requests' rows at row - rows(W).
@@ -29,15 +29,16 @@
 // Whether a row is a prefetch (rank within its RPC >= n_immediate) is not stored: the reference
 // uses is_prefetch for log text only (task_dispatcher.cc:464,531).
 //
-// Look-back: the words of wait_queue.h (flag | hi 31 bits | lo 31 bits), three arrays (scan,
-// settle, grant). k_lease_renew, the step's first launch, clears them; k_rpc_expand, which runs
-// when the scan is complete and before the other two start, resets the three tickets.
+// Look-back (stream_tile.h): one word per tile, three arrays (scan, settle, grant). k_lease_renew,
+// the step's first launch, clears them; k_rpc_expand, which runs when the scan is complete and
+// before the other two start, resets the three tickets.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels.h"
 #include "lease_table.h"
+#include "stream_tile.h"
 #include "wait_queue.h"
 
 namespace ydc {
@@ -98,7 +99,9 @@ struct RpcOut {
   RpcOutcome* outcome;
 };
 
-// Wave 0 of the workgroup with ticket `bid`: publishes the workgroup's two totals (each < 2^31,
+// k_rpc_scan's own look-back, the form it was timed with (tile_lookback<1> of stream_tile.h is the
+// same protocol; under it the compiler schedules the scan's column copies differently, and that was
+// measured 1.5 us slower). Wave 0 of the workgroup with ticket `bid`: publishes the workgroup's two totals (each < 2^31,
 // sums too) and returns the sums over the workgroups in front (every lane gets them).
 __device__ __forceinline__ void rpc_lookback(unsigned long long* lookback, uint32_t bid, uint32_t lane,
                                              uint32_t tot_lo, uint32_t tot_hi, uint32_t* pre_lo, uint32_t* pre_hi) {
@@ -242,11 +245,7 @@ __global__ __launch_bounds__(256) void k_rpc_grant(RpcBatch b, uint32_t NR, uint
                                                    LeaseCols L, LeaseState* st, RpcState* rs,
                                                    unsigned long long* lookback, RpcOut o,
                                                    const DeviceParams* prm, uint32_t check_slot) {
-  if (prm) {
-    const bool final = (check_slot == kNone || prm->n_changed[check_slot] == 0) && !prm->window_miss &&
-                       !prm->overflow;
-    if (!final) return;  // (every workgroup alike: L stays as it is)
-  }
+  if (prm && !batch_is_final(prm, check_slot)) return;  // (every workgroup alike: L stays as it is)
   __shared__ uint32_t s_bid, s_pre;
   __shared__ uint32_t lds[17];
   if (threadIdx.x == 0) s_bid = atomicAdd(&rs->t_grant, 1u);
@@ -266,8 +265,7 @@ __global__ __launch_bounds__(256) void k_rpc_grant(RpcBatch b, uint32_t NR, uint
   uint32_t tot;
   const uint32_t ex = block_exclusive_scan(n_gr, lds, &tot);
   if (threadIdx.x < 64) {
-    uint32_t pre, unused;
-    rpc_lookback(lookback, bid, threadIdx.x, tot, 0u, &pre, &unused);
+    const uint32_t pre = lb_lo(tile_lookback<1>(lookback, bid, threadIdx.x, {{lb_pack(tot)}}).w[0]);
     if (threadIdx.x == 0) {
       s_pre = pre;
       if (bid == gridDim.x - 1) b.rank[NR] = pre + tot;  // the last workgroup: the tick's grants
@@ -283,38 +281,15 @@ __global__ __launch_bounds__(256) void k_rpc_grant(RpcBatch b, uint32_t NR, uint
     if (j < NR) b.rank[j] = rk;
     if (r[i] >= kIdxWaiting) continue;
     ids[i] = next + rk;
-    const uint32_t h = lease_home(L, ids[i]);
-    // (always ends: |L| + rows(W) + rows(new) <= max_leases <= cap / 2 is checked before the tick)
-    for (uint32_t d = 0; d <= L.mask; ++d) {
-      const uint32_t slot = (h + d) & L.mask;
-      if (L.key[slot] != kLeaseEmpty || atomicCAS(&L.key[slot], kLeaseEmpty, ids[i]) != kLeaseEmpty) continue;
-      L.expires[slot] = now + b.lease_for[j];  // the lease runs from the grant
-      L.servant[slot] = r[i];
-      L.state[slot] = kLeaseLive;
-      if (d) atomicMax(&st->max_disp, d);
-      break;
-    }
+    lease_insert(L, st, ids[i], now + b.lease_for[j], r[i]);  // the lease runs from the grant
     if (j < w_rows) {  // a waiting RPC's grant: packed by rank (rk <= j < NR)
       o.res_srv[rk] = r[i];
       o.res_id[rk] = ids[i];
     }
     ++rk;
   }
-  // The new requests' rows go to page-locked memory once, 16 / 32 bytes per thread where the
-  // thread's four rows are four whole, aligned answers (rows(W) a multiple of 4).
-  if (j0 >= w_rows && ((j0 - w_rows) & 3) == 0 && j0 + 3 < NR) {
-    const uint32_t k = j0 - w_rows;
-    *reinterpret_cast<uint4*>(o.new_srv + k) = make_uint4(r[0], r[1], r[2], r[3]);
-    *reinterpret_cast<ulonglong2*>(o.new_id + k) = make_ulonglong2(ids[0], ids[1]);
-    *reinterpret_cast<ulonglong2*>(o.new_id + k + 2) = make_ulonglong2(ids[2], ids[3]);
-  } else {
-    for (int i = 0; i < 4; ++i) {
-      const uint32_t j = j0 + i;
-      if (j < w_rows || j >= NR) continue;
-      o.new_srv[j - w_rows] = r[i];
-      o.new_id[j - w_rows] = ids[i];
-    }
-  }
+  // The new requests' rows to page-locked memory (vector stores where rows(W) is a multiple of 4).
+  store_answers(o.new_srv, o.new_id, j0, w_rows, NR, r, ids);
 }
 
 // ceil(P / kRpcTile) workgroups of 256 threads over the positions; thread i of a workgroup owns
@@ -324,11 +299,7 @@ __global__ __launch_bounds__(256) void k_rpc_settle(RpcEntryCols p, RpcBatch b, 
                                                     RpcState* rs, LeaseState* st, unsigned long long* lookback,
                                                     RpcOut o, LeaseOutcome* lout, const DeviceParams* prm,
                                                     uint32_t check_slot) {
-  if (prm) {
-    const bool final = (check_slot == kNone || prm->n_changed[check_slot] == 0) && !prm->window_miss &&
-                       !prm->overflow;
-    if (!final) return;  // (every workgroup alike: W, L and next_id stay as they are)
-  }
+  if (prm && !batch_is_final(prm, check_slot)) return;  // (every workgroup alike: W, L and next_id stay as they are)
   __shared__ uint32_t s_bid, s_pre_surv, s_pre_res;
   __shared__ uint32_t lds[17];
   if (threadIdx.x == 0) s_bid = atomicAdd(&rs->t_settle, 1u);
@@ -379,8 +350,8 @@ __global__ __launch_bounds__(256) void k_rpc_settle(RpcEntryCols p, RpcBatch b, 
     const uint32_t lane = threadIdx.x;
     // (before the workgroup's word is published: the last workgroup reads the sum behind it)
     if (lane == 0 && tot_rows) atomicAdd(&rs->w_rows, tot_rows);
-    uint32_t pre_s, pre_r;
-    rpc_lookback(lookback, bid, lane, tot & 0xFFFFu, tot >> 16, &pre_s, &pre_r);
+    const LbWords<1> pre = tile_lookback<1>(lookback, bid, lane, {{lb_pack(tot & 0xFFFFu, tot >> 16)}});
+    const uint32_t pre_s = lb_lo(pre.w[0]), pre_r = lb_hi(pre.w[0]);
     if (lane == 0) {
       s_pre_surv = pre_s;
       s_pre_res = pre_r;
@@ -395,18 +366,7 @@ __global__ __launch_bounds__(256) void k_rpc_settle(RpcEntryCols p, RpcBatch b, 
         o.outcome->n_rows = b.row_start[P];
         o.outcome->n_res_grants = b.rank[b.row_start[MW]];
         o.outcome->granted = granted;
-        const uint32_t n = st->n_leases - st->freed - st->swept + granted;
-        const unsigned long long next = st->next_id + granted;
-        lout->next_id = next;
-        lout->n_leases = n;
-        lout->expired = st->expired;
-        lout->swept = st->swept;
-        lout->freed = st->freed;
-        lout->renew_refused = st->renew_refused;
-        lout->tick_no = hdr->tick_no;
-        st->n_leases = n;
-        st->expired = st->swept = st->freed = st->renew_refused = 0;
-        st->next_id = next;
+        st->next_id = lease_close_tick(st, hdr, lout, granted, st->next_id);
       }
     }
   }
@@ -417,11 +377,7 @@ __global__ __launch_bounds__(256) void k_rpc_settle(RpcEntryCols p, RpcBatch b, 
     const uint32_t j = j0 + i;
     if (kind[i] == 1) {
       if (ps < MW) {  // (always: |W| + n_req <= max_waiting is checked before the tick)
-        w.env[ps] = p.env[j];
-        w.minv[ps] = p.minv[j];
-        w.ip[ps] = p.ip[j];
-        w.deadline[ps] = p.deadline[j];
-        w.tag[ps] = p.tag[j];
+        copy_entry(w, ps, p, j);
         w.lease_for[ps] = p.lease_for[j];
         w.n_imm[ps] = p.n_imm[j];
         w.n_pre[ps] = p.n_pre[j];

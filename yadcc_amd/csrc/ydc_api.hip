@@ -4480,15 +4480,16 @@ static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tas
   return YDC_OK;
 }
 
-// Leased mode, after the step: ids, renewal and report answers to the caller, the host's mirror
-// of |L| and the statistics.
-static int stream_lease_finish(ydc_context* c, const LeaseTick* lt, uint32_t n_tasks) {
+// The lease outcome block is this tick's and |L| is in range.
+static bool stream_lease_outcome_ok(const ydc_context::Stream& sm) {
+  return sm.h_lout->tick_no == sm.lease_tick && sm.h_lout->n_leases <= sm.max_leases;
+}
+
+// The lease part of a tick's ending, once the outcome is known to be good: renewal and report
+// answers to the caller, the host's mirror of |L| and the statistics.
+static void stream_lease_apply(ydc_context* c, const LeaseTick* lt) {
   auto& sm = c->stream_mode;
   const LeaseOutcome& o = *sm.h_lout;
-  if (o.tick_no != sm.lease_tick || o.n_leases > sm.max_leases)
-    return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: outcome of tick %u (expected %u), %u leases of %u",
-                o.tick_no, sm.lease_tick, o.n_leases, sm.max_leases);
-  if (n_tasks) std::memcpy(lt->out_task_id, sm.h_task_id, (size_t)n_tasks * 8);
   if (lt->n_renew) std::memcpy(lt->out_renewed, sm.h_renewed, lt->n_renew);
   const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
   if (n_ids) std::memcpy(lt->out_unknown, sm.h_unknown, n_ids);
@@ -4499,6 +4500,16 @@ static int stream_lease_finish(ydc_context* c, const LeaseTick* lt, uint32_t n_t
   c->stats.renewals_refused = o.renew_refused;
   sm.n_leases = o.n_leases;
   sm.last_now = lt->now;
+}
+
+// Leased mode, after the step: the ids and the lease part.
+static int stream_lease_finish(ydc_context* c, const LeaseTick* lt, uint32_t n_tasks) {
+  auto& sm = c->stream_mode;
+  if (!stream_lease_outcome_ok(sm))
+    return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: outcome of tick %u (expected %u), %u leases of %u",
+                sm.h_lout->tick_no, sm.lease_tick, sm.h_lout->n_leases, sm.max_leases);
+  stream_lease_apply(c, lt);
+  if (n_tasks) std::memcpy(lt->out_task_id, sm.h_task_id, (size_t)n_tasks * 8);
   return YDC_OK;
 }
 
@@ -4509,8 +4520,8 @@ static int stream_rpc_finish(ydc_context* c, const WaitTick* wt, const LeaseTick
   auto& sm = c->stream_mode;
   const LeaseOutcome& lo = *sm.h_lout;
   const RpcOutcome& o = *sm.rh.outcome;
-  if (lo.tick_no != sm.lease_tick || lo.n_leases > sm.max_leases || o.n_waiting > sm.max_waiting ||
-      o.n_resolved > sm.max_waiting || o.n_rows > sm.max_rows || o.n_res_grants > sm.max_rows)
+  if (!stream_lease_outcome_ok(sm) || o.n_waiting > sm.max_waiting || o.n_resolved > sm.max_waiting ||
+      o.n_rows > sm.max_rows || o.n_res_grants > sm.max_rows)
     return fail(c, YDC_ERR_NOT_CONVERGED, "rpc stream: outcome of tick %u (expected %u), %u leases, %u waiting, %u rows",
                 lo.tick_no, sm.lease_tick, lo.n_leases, o.n_waiting, o.n_rows);
   if (sm.rows_new) {
@@ -4531,23 +4542,14 @@ static int stream_rpc_finish(ydc_context* c, const WaitTick* wt, const LeaseTick
     std::memcpy(rt->out_resolved_servant_idx, sm.rh.res_srv, (size_t)o.n_res_grants * 4);
     std::memcpy(wt->out_resolved_task_id, sm.rh.res_id, (size_t)o.n_res_grants * 8);
   }
-  if (lt->n_renew) std::memcpy(lt->out_renewed, sm.h_renewed, lt->n_renew);
-  const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
-  if (n_ids) std::memcpy(lt->out_unknown, sm.h_unknown, n_ids);
+  stream_lease_apply(c, lt);
   *wt->out_n_resolved = o.n_resolved;
   *wt->out_n_waiting = o.n_waiting;
   *rt->out_n_waiting_rows = o.n_waiting_rows;
-  *lt->out_n_leases = lo.n_leases;
   c->stats.n_tasks = o.n_rows;
   c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_rows - o.n_rows);  // padding
-  c->stats.leases_expired = lo.expired;
-  c->stats.leases_swept = lo.swept;
-  c->stats.leases_freed = lo.freed;
-  c->stats.renewals_refused = lo.renew_refused;
   sm.n_waiting = o.n_waiting;
   sm.n_wait_rows = o.n_waiting_rows;
-  sm.n_leases = lo.n_leases;
-  sm.last_now = lt->now;
   return YDC_OK;
 }
 
