@@ -292,7 +292,8 @@ typedef struct ydc_stream_buffers {
 } ydc_stream_buffers;
 int ydc_stream_buffers_get(ydc_context* ctx, ydc_stream_buffers* out);
 /* Discards the waiting queue of a context begun with ydc_stream_begin_waiting and the lease table
- * of one begun with ydc_stream_begin_leased (both of one begun with ydc_stream_begin_waiting_leased). */
+ * of one begun with ydc_stream_begin_leased (both of one begun with ydc_stream_begin_waiting_leased).
+ * A stream that has merely become too small is grown, state kept, with ydc_stream_reserve (below). */
 int ydc_stream_end(ydc_context* ctx);
 
 /* ---- streaming with a waiting queue --------------------------------------------
@@ -491,6 +492,43 @@ int ydc_stream_tick_rpc(ydc_context* ctx, const uint32_t* upd_idx, const ydc_ser
                         uint32_t* out_resolved_n_granted, uint32_t* out_resolved_first,
                         uint32_t* out_resolved_servant_idx, uint64_t* out_resolved_task_id,
                         uint32_t* out_n_resolved, uint32_t* out_n_waiting, uint32_t* out_n_waiting_rows);
+
+/* ---- growing an open stream's capacities ---------------------------------------------
+ * Every bound of a waiting, leased, waiting-and-leased or rpc stream is given at its begin call, and
+ * a tick that would cross one is refused with YDC_ERR_CAPACITY. ydc_stream_reserve makes the bounds
+ * larger while the stream stays open and keeps its state, which lives on the device only; a caller
+ * may begin small and reserve when a tick is refused, or ahead of that from *out_n_waiting,
+ * *out_n_waiting_rows and *out_n_leases. ydc_stream_caps_get reports the open stream's bounds
+ * (max_tasks is an rpc stream's max_requests; what the mode does not have is 0).
+ *   Growth only: every bound becomes max(current, want); nothing shrinks. A want that changes
+ *     nothing returns YDC_OK and does nothing (the captured step stays).
+ *   The mode is fixed: a non-zero field of a part the stream was begun without (max_waiting on a
+ *     leased stream, a lease bound on a waiting one, max_rows outside rpc mode) is
+ *     YDC_ERR_INVALID_ARGUMENT. So is a call with no stream open or on a plain ydc_stream_begin
+ *     stream — that one keeps no state on the device, and its ydc_stream_buffers_get pointers are
+ *     promised to stay valid until ydc_stream_end — and so are bounds beyond the limits of the begin
+ *     calls (max_tasks + max_waiting <= 0x7FFFFFFF, max_leases and max_rows <= 2^30,
+ *     max_report_ids <= 0x7FFFFFFF, max_rows >= max_requests), checked before anything is touched.
+ *   Carried over — everything the next tick can observe: L entry by entry (id, servant, expires_at
+ *     and the whole state: live, zombie, the tick number of the last report that listed it), next_id
+ *     and |L|; W in queue order with all its columns (deadline, tag, the request, lease_for with
+ *     leases, both counts in rpc mode), |W| and rows(W); the previous tick's now (an earlier one is
+ *     still refused); the tick number the report stamps are taken from. From the call on, every
+ *     tick's outputs, ydc_stream_leases_get, ydc_stream_waiting_take, ydc_get_running and
+ *     ydc_get_stats() are those of a stream begun with the larger bounds and fed the same ticks; a
+ *     tick that was refused with YDC_ERR_CAPACITY is accepted when given again after the call.
+ *   All or nothing: the larger buffers are allocated and filled before the old ones are released.
+ *     When an allocation fails (YDC_ERR_HIP), or the number of leases moved differs from |L|
+ *     (YDC_ERR_NOT_CONVERGED), the stream is as it was and stays usable.
+ * The lease table is filed again into its larger array in one pass (its bound on probe lengths
+ * starts afresh), W is copied, the step is captured again at the next tick. The cost is that of a
+ * begin call plus one pass over the old table: for the moment of a burst, not for every tick. */
+typedef struct ydc_stream_caps {
+  uint32_t max_updates, max_releases, max_tasks /* rpc: max_requests */, max_rows,
+           max_waiting, max_leases, max_renewals, max_frees, max_reports, max_report_ids;
+} ydc_stream_caps;
+int ydc_stream_caps_get(ydc_context* ctx, ydc_stream_caps* out);
+int ydc_stream_reserve(ydc_context* ctx, const ydc_stream_caps* want);
 
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.

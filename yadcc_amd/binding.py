@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "ydc_stream_begin_waiting", "ydc_stream_tick_waiting", "ydc_stream_waiting_take",
     "ydc_stream_begin_leased", "ydc_stream_tick_leased", "ydc_stream_leases_get",
     "ydc_stream_begin_waiting_leased", "ydc_stream_tick_waiting_leased",
-    "ydc_stream_begin_rpc", "ydc_stream_tick_rpc",
+    "ydc_stream_begin_rpc", "ydc_stream_tick_rpc", "ydc_stream_caps_get", "ydc_stream_reserve",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -86,6 +86,13 @@ class Stats(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "stage_ms"}
         d["stage_ms"] = {name: float(self.stage_ms[i]) for i, name in enumerate(STAGES)}
         return d
+
+
+class StreamCaps(C.Structure):
+    """ydc_stream_caps: the bounds of an open stream, in the header's field order."""
+    _fields_ = [(k, C.c_uint32) for k in (
+        "max_updates", "max_releases", "max_tasks", "max_rows", "max_waiting", "max_leases",
+        "max_renewals", "max_frees", "max_reports", "max_report_ids")]
 
 
 _lib = None
@@ -180,6 +187,8 @@ def lib():
             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.ydc_stream_leases_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_uint32, C.POINTER(C.c_uint32)]
+        L.ydc_stream_caps_get.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
+        L.ydc_stream_reserve.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
         L.ydc_group_unique_id.argtypes = [C.c_void_p]
         L.ydc_group_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ydc_group_init_local.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -826,6 +835,31 @@ class Context:
                 "res_n_granted": res_n[:k].copy(), "res_first": res_first[:k].copy(),
                 "res_servants": res_srv[:g].copy(), "res_task_ids": res_ids[:g].copy(),
                 "n_waiting": int(n_wait.value), "n_waiting_rows": int(n_wrows.value)}
+
+    def stream_caps(self):
+        """The open stream's bounds (ydc_stream_caps_get) as a dict; max_tasks is an rpc stream's
+        max_requests, and what the stream's mode does not have is 0."""
+        caps = StreamCaps()
+        self._check(lib().ydc_stream_caps_get(self._h, C.byref(caps)), "ydc_stream_caps_get")
+        return {k: int(getattr(caps, k)) for k, _ in StreamCaps._fields_}
+
+    def stream_reserve(self, **caps):
+        """Grows the open stream's bounds to max(current, given) with its waiting queue and lease
+        table kept (ydc_stream_reserve); keywords as the keys of stream_caps(), max_requests for
+        max_tasks accepted. Returns the bounds afterwards."""
+        if "max_requests" in caps:
+            caps["max_tasks"] = max(int(caps.pop("max_requests")), int(caps.get("max_tasks", 0)))
+        want = StreamCaps()
+        for k, v in caps.items():
+            if k not in dict(StreamCaps._fields_):
+                raise TypeError("stream_reserve: unknown capacity %r" % k)
+            setattr(want, k, int(v))
+        self._check(lib().ydc_stream_reserve(self._h, C.byref(want)), "ydc_stream_reserve")
+        now = self.stream_caps()
+        # (the result arrays of the tick calls are sized by these)
+        self._stream_caps = (now["max_updates"], now["max_releases"], now["max_tasks"])
+        self._max_waiting, self._max_leases, self._max_rows = now["max_waiting"], now["max_leases"], now["max_rows"]
+        return now
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

@@ -22,6 +22,8 @@
 //   k_lease_grant    the commit pass of wait_lease.h in its form without a queue: out_task_id[i]
 //                    = next_id + rank among the granted, the lease inserted; the last workgroup
 //                    bumps next_id and |L| and stores the tick's outcome block to page-locked memory.
+// Outside the tick: k_lease_remap (ydc_remove_servants) and k_lease_rehash (ydc_stream_reserve: the
+// table filed again into a larger one).
 //
 // running_tasks: the decrements of frees and sweeps are atomicSub on the column k_apply_tick's
 // releases decrement too (the same instruction, the same column; the kernels run one after another
@@ -308,6 +310,59 @@ __global__ __launch_bounds__(256) void k_lease_remap(LeaseCols L, LeaseState* st
   }
   const unsigned long long m = __ballot(gone);
   if (m && lane_id() == (uint32_t)__builtin_ctzll(m)) atomicSub(&st->n_leases, (uint32_t)__popcll(m));
+}
+
+// ydc_stream_reserve: every lease of the table `o` filed into the larger, empty table `n` by
+// lease_insert's rule (multiplicative home, linear probing, one CAS on the key), its state word
+// stored as it is: live, zombie and the report stamp. One pass shaped like k_lease_sweep:
+// ceil(old cap / kLeaseTile) workgroups, thread i owns four consecutive slots of `o`. n's
+// bookkeeping starts cleared: n_leases counts what was filed (the host compares it with |L|),
+// max_disp is that of the new table alone (the bound is tightened again), next_id is o's.
+// No order is kept and none is needed: a slot's place depends on its key and on which of the
+// probing inserts came first, and every reader finds a key by probing up to max_disp.
+__global__ __launch_bounds__(256) void k_lease_rehash(LeaseCols o, const LeaseState* ost, LeaseCols n,
+                                                      LeaseState* nst) {
+  const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  uint32_t moved = 0;
+  if (i0 <= o.mask) {  // (cap is a multiple of 4)
+    const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(o.key + i0);
+    const ulonglong2 k23 = *reinterpret_cast<const ulonglong2*>(o.key + i0 + 2);
+    const unsigned long long k4[4] = {k01.x, k01.y, k23.x, k23.y};
+    if ((k4[0] & k4[1] & k4[2] & k4[3]) != kLeaseEmpty) {
+      const uint4 sv = *reinterpret_cast<const uint4*>(o.state + i0);
+      const uint4 srv = *reinterpret_cast<const uint4*>(o.servant + i0);
+      const longlong2 e01 = *reinterpret_cast<const longlong2*>(o.expires + i0);
+      const longlong2 e23 = *reinterpret_cast<const longlong2*>(o.expires + i0 + 2);
+      const uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
+      const uint32_t s4[4] = {srv.x, srv.y, srv.z, srv.w};
+      const int64_t e4[4] = {e01.x, e01.y, e23.x, e23.y};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const unsigned long long id = k4[k];
+        if (id == kLeaseEmpty) continue;
+        const uint32_t h = lease_home(n, id);
+        for (uint32_t d = 0; d <= n.mask; ++d) {
+          const uint32_t slot = (h + d) & n.mask;
+          if (n.key[slot] != kLeaseEmpty || atomicCAS(&n.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
+          n.expires[slot] = e4[k];
+          n.servant[slot] = s4[k];
+          n.state[slot] = st4[k];
+          if (d) atomicMax(&nst->max_disp, d);
+          ++moved;
+          break;
+        }
+      }
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) nst->next_id = ost->next_id;
+  // One atomic per workgroup.
+  __shared__ uint32_t s_cnt;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  const uint32_t wm = wave_sum_u32(moved);
+  if ((threadIdx.x & 63) == 0 && wm) atomicAdd(&s_cnt, wm);
+  __syncthreads();
+  if (threadIdx.x == 0 && s_cnt) atomicAdd(&nst->n_leases, s_cnt);
 }
 
 }  // namespace ydc

@@ -3895,13 +3895,14 @@ void stream_drop_graphs(ydc_context::Stream& sm) {
   sm.graph = sm.graph_b = nullptr;
 }
 
-void stream_release(ydc_context* c) {
-  auto& sm = c->stream_mode;
+void stream_release(ydc_context::Stream& sm) {
   stream_drop_graphs(sm);
   for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres, sm.h_rres})
     if (h) (void)hipHostFree(h);
   sm = ydc_context::Stream{};  // (frees the device buffers: ydc_stream_end discards W)
 }
+
+void stream_release(ydc_context* c) { stream_release(c->stream_mode); }
 
 // Offset of the next 256 B aligned section of an arena that is `*off` bytes long so far.
 size_t section(size_t* off, size_t bytes) {
@@ -4174,20 +4175,23 @@ struct LeaseCaps {
   uint32_t max_leases, max_renew, max_free, max_rep, max_rep_ids;
 };
 
-int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
-                 uint32_t max_waiting, const LeaseCaps* lc = nullptr, uint32_t max_rows = 0) {
-  if (!c || !max_tasks) return YDC_ERR_INVALID_ARGUMENT;
+// The limits of a stream's capacities; `code`: what going beyond them is to the caller.
+int stream_caps_check(ydc_context* c, int code, uint32_t max_tasks, uint32_t max_waiting, const LeaseCaps* lc,
+                      uint32_t max_rows) {
   // (rpc mode: max_tasks is max_requests, the batch is the max_rows expanded rows)
   if (max_rows && (max_rows > (1u << 30) || max_rows < max_tasks))
-    return fail(c, YDC_ERR_CAPACITY, "max_rows %u out of range (max_requests %u .. 2^30)", max_rows, max_tasks);
+    return fail(c, code, "max_rows %u out of range (max_requests %u .. 2^30)", max_rows, max_tasks);
   if (lc && (!lc->max_leases || lc->max_leases > (1u << 30) || lc->max_rep_ids > 0x7FFFFFFFu))
-    return fail(c, YDC_ERR_CAPACITY, "max_leases %u out of range (1 .. 2^30)", lc->max_leases);
+    return fail(c, code, "max_leases %u out of range (1 .. 2^30)", lc->max_leases);
   if ((uint64_t)max_tasks + max_waiting > 0x7FFFFFFFull)
-    return fail(c, YDC_ERR_CAPACITY, "max_tasks %u + max_waiting %u too large", max_tasks, max_waiting);
-  HIP_TRY(c, hipSetDevice(c->device));
-  resident_stop(c);  // (the registry leaves the resident kernel's registers)
-  stream_release(c);
-  auto& sm = c->stream_mode;
+    return fail(c, code, "max_tasks %u + max_waiting %u too large", max_tasks, max_waiting);
+  return YDC_OK;
+}
+
+// Layout and allocation of everything a stream of these capacities has, into `sm` (released, or
+// fresh). Its contents are not defined before stream_reset; after a failure the caller releases it.
+int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, uint32_t max_releases,
+                 uint32_t max_tasks, uint32_t max_waiting, const LeaseCaps* lc, uint32_t max_rows) {
   sm.max_upd = max_updates;
   sm.max_rel = max_releases;
   sm.max_tasks = max_tasks;
@@ -4272,7 +4276,6 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     sm.wt_out = (uint32_t*)(b + o_wout);
     sm.ws = (WaitState*)(b + o_ws);
     sm.lookback = (unsigned long long*)(b + o_lb);
-    HIP_TRY(c, hipMemsetAsync(sm.ws, 0, sizeof(WaitState), c->stream));  // W empty
     // Page-locked results: resolved tags | resolved answers | outcome block.
     size_t r_off = 0;
     const size_t r_tag = section(&r_off, (size_t)max_waiting * 8), r_idx = section(&r_off, (size_t)max_waiting * 4);
@@ -4291,8 +4294,6 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     sm.z_res_tag = (uint64_t*)(z_res + r_tag);
     sm.z_res_idx = (uint32_t*)(z_res + r_idx);
     sm.z_wout = (WaitOutcome*)(z_res + r_out);
-    std::memset(sm.h_wout, 0, sizeof(WaitOutcome));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   if (lc) {
     sm.max_leases = lc->max_leases;
@@ -4322,9 +4323,6 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     sm.ren_slot = (uint32_t*)(b + o_rs);
     sm.lt_out = (uint32_t*)(b + o_out);
     sm.lookback = (unsigned long long*)(b + o_lb);
-    // L empty, next_id 0 (the reference's next_task_id{}).
-    HIP_TRY(c, hipMemsetAsync(b, 0, l_off, c->stream));
-    HIP_TRY(c, hipMemsetAsync(sm.lt.key, 0xFF, cap * 8, c->stream));
     // Page-locked results: task ids | renewed | report_unknown | outcome block.
     size_t r_off = 0;
     const size_t r_id = section(&r_off, n_out * 8), r_ren = section(&r_off, lc->max_renew);
@@ -4340,8 +4338,6 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     sm.z_renewed = z_res + r_ren;
     sm.z_unknown = z_res + r_unk;
     sm.z_lout = (LeaseOutcome*)(z_res + r_out);
-    std::memset(sm.h_lout, 0, sizeof(LeaseOutcome));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   if (max_rows) {
     sm.max_rows = max_rows;
@@ -4359,7 +4355,6 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     const size_t o_rs = dsec((P + 1) * 4), o_rk = dsec((NR + 1) * 4), o_st = dsec(sizeof(RpcState));
     HIP_TRY(c, sm.d_rpc.reserve(d_off));
     uint8_t* b = sm.d_rpc.p;
-    HIP_TRY(c, hipMemsetAsync(b, 0, d_off, c->stream));
     sm.rw = RpcEntryCols{sm.wq.env, sm.wq.minv, sm.wq.ip, sm.wq.deadline, sm.wq.tag, sm.wl.w_for,
                          (uint32_t*)(b + o_wi), (uint32_t*)(b + o_wp)};
     sm.rp = RpcEntryCols{(uint32_t*)(b + o_p4[0]), (uint32_t*)(b + o_p4[1]), (uint32_t*)(b + o_p4[2]),
@@ -4385,13 +4380,97 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     };
     sm.rh = out_at(sm.h_rres, sm.h_out, sm.h_task_id);
     sm.rz = out_at(z, sm.z_out, sm.z_task_id);
-    std::memset(sm.rh.outcome, 0, sizeof(RpcOutcome));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
-  sm.active = true;
   sm.stale = true;
   return YDC_OK;
+}
+
+// The state of a stream that has just been begun, in the buffers stream_alloc made: W empty, L
+// empty with next_id 0 (the reference's next_task_id{}), the rpc columns and every outcome block
+// cleared.
+int stream_reset(ydc_context* c, ydc_context::Stream& sm) {
+  if (sm.max_waiting) {
+    HIP_TRY(c, hipMemsetAsync(sm.ws, 0, sizeof(WaitState), c->stream));
+    std::memset(sm.h_wout, 0, sizeof(WaitOutcome));
+  }
+  if (sm.max_leases) {
+    HIP_TRY(c, hipMemsetAsync(sm.d_lease.p, 0, sm.d_lease.cap, c->stream));
+    HIP_TRY(c, hipMemsetAsync(sm.lt.key, 0xFF, ((size_t)sm.lt.mask + 1) * 8, c->stream));
+    std::memset(sm.h_lout, 0, sizeof(LeaseOutcome));
+  }
+  if (sm.max_rows) {
+    HIP_TRY(c, hipMemsetAsync(sm.d_rpc.p, 0, sm.d_rpc.cap, c->stream));
+    std::memset(sm.rh.outcome, 0, sizeof(RpcOutcome));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  sm.active = true;
+  return YDC_OK;
+}
+
+// ydc_stream_reserve: what the next tick can observe of the stream `o`, carried into the freshly
+// reset, larger `n`. L is filed again slot by slot (k_lease_rehash: the new table has other home
+// slots); W is compact between ticks (k_wait_compact / k_rpc_settle leave it packed), so entries
+// [0, |W|) of every column are copied as they lie; of the small state blocks only |W| and next_id
+// outlive a tick (tickets, snapshots and the tick's counters are cleared by the tick that uses
+// them). Nothing of `o` is written.
+int stream_migrate(ydc_context* c, const ydc_context::Stream& o, ydc_context::Stream& n) {
+  hipStream_t st = c->stream;
+  LeaseState ls_old{}, ls_new{};
+  if (o.max_leases) {
+    YDC_LAUNCH(c, "k_lease_rehash", k_lease_rehash, dim3(ceil_div(o.lt.mask + 1, kLeaseTile)), dim3(256), 0, st,
+               o.lt, o.ls, n.lt, n.ls);
+    HIP_TRY(c, hipGetLastError());
+  }
+  if (o.max_waiting) {
+    uint32_t cnt = 0;
+    HIP_TRY(c, hipMemcpy(&cnt, &o.ws->count, 4, hipMemcpyDeviceToHost));
+    if (cnt > o.max_waiting)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u > max_waiting %u", cnt, o.max_waiting);
+    auto carry = [&](void* dst, const void* src, size_t width) {
+      return cnt && src ? hipMemcpyAsync(dst, src, cnt * width, hipMemcpyDeviceToDevice, st) : hipSuccess;
+    };
+    HIP_TRY(c, carry(n.wq.env, o.wq.env, 4));
+    HIP_TRY(c, carry(n.wq.minv, o.wq.minv, 4));
+    HIP_TRY(c, carry(n.wq.ip, o.wq.ip, 4));
+    HIP_TRY(c, carry(n.wq.deadline, o.wq.deadline, 8));
+    HIP_TRY(c, carry(n.wq.tag, o.wq.tag, 8));
+    HIP_TRY(c, carry(n.wl.w_for, o.wl.w_for, 8));  // (with leases)
+    HIP_TRY(c, carry(n.rw.n_imm, o.rw.n_imm, 4));  // (rpc mode)
+    HIP_TRY(c, carry(n.rw.n_pre, o.rw.n_pre, 4));
+    HIP_TRY(c, hipMemcpyAsync(&n.ws->count, &o.ws->count, 4, hipMemcpyDeviceToDevice, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (o.max_leases) {
+    HIP_TRY(c, hipMemcpy(&ls_old, o.ls, sizeof ls_old, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&ls_new, n.ls, sizeof ls_new, hipMemcpyDeviceToHost));
+    if (ls_new.n_leases != ls_old.n_leases || ls_new.next_id != ls_old.next_id)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: %u of %u leases moved (next_id %llu of %llu)",
+                  ls_new.n_leases, ls_old.n_leases, ls_new.next_id, ls_old.next_id);
+  }
+  // The host's mirrors: |W|, rows(W), |L|, the last tick's clock, the tick number the report stamps
+  // are taken from, the servants' report marks, and what the stream has learnt about its passes.
+  n.n_waiting = o.n_waiting;
+  n.n_wait_rows = o.n_wait_rows;
+  n.n_leases = o.n_leases;
+  n.last_now = o.last_now;
+  n.lease_tick = o.lease_tick;
+  n.rep_seen = o.rep_seen;
+  n.rep_mark = o.rep_mark;
+  n.want_passes = o.want_passes;
+  return YDC_OK;
+}
+
+int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
+                 uint32_t max_waiting, const LeaseCaps* lc = nullptr, uint32_t max_rows = 0) {
+  if (!c || !max_tasks) return YDC_ERR_INVALID_ARGUMENT;
+  if (int rc = stream_caps_check(c, YDC_ERR_CAPACITY, max_tasks, max_waiting, lc, max_rows)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  stream_release(c);
+  if (int rc = stream_alloc(c, c->stream_mode, max_updates, max_releases, max_tasks, max_waiting, lc, max_rows))
+    return rc;
+  return stream_reset(c, c->stream_mode);
 }
 
 }  // namespace
@@ -4407,6 +4486,61 @@ int ydc_stream_begin_waiting(ydc_context* c, uint32_t max_updates, uint32_t max_
                              uint32_t max_tasks, uint32_t max_waiting) {
   if (!c || !max_waiting) return YDC_ERR_INVALID_ARGUMENT;
   return stream_begin(c, max_updates, max_releases, max_tasks, max_waiting);
+}
+
+int ydc_stream_caps_get(ydc_context* c, ydc_stream_caps* out) {
+  if (!c || !out || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
+  const auto& sm = c->stream_mode;
+  *out = ydc_stream_caps{sm.max_upd,    sm.max_rel,   sm.max_tasks, sm.max_rows, sm.max_waiting,
+                         sm.max_leases, sm.max_renew, sm.max_free,  sm.max_rep,  sm.max_rep_ids};
+  return YDC_OK;
+}
+
+int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
+  if (!c || !want) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: no stream is open");
+  if (!sm.max_waiting && !sm.max_leases)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: a stream begun with ydc_stream_begin keeps no state "
+                "on the device, and its ydc_stream_buffers_get pointers stay valid until ydc_stream_end");
+  // The mode is fixed: no capacity of a part the stream was begun without.
+  if (!sm.max_waiting && want->max_waiting)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: max_waiting on a stream without a waiting queue");
+  if (!sm.max_leases && (want->max_leases | want->max_renewals | want->max_frees | want->max_reports |
+                         want->max_report_ids))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: lease capacities on a stream without a lease table");
+  if (!sm.max_rows && want->max_rows)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: max_rows on a stream not begun with ydc_stream_begin_rpc");
+  // Growth only.
+  const uint32_t max_upd = std::max(sm.max_upd, want->max_updates), max_rel = std::max(sm.max_rel, want->max_releases);
+  const uint32_t max_tasks = std::max(sm.max_tasks, want->max_tasks), max_rows = std::max(sm.max_rows, want->max_rows);
+  const uint32_t max_waiting = std::max(sm.max_waiting, want->max_waiting);
+  const LeaseCaps lc{std::max(sm.max_leases, want->max_leases), std::max(sm.max_renew, want->max_renewals),
+                     std::max(sm.max_free, want->max_frees), std::max(sm.max_rep, want->max_reports),
+                     std::max(sm.max_rep_ids, want->max_report_ids)};
+  const LeaseCaps* lcp = sm.max_leases ? &lc : nullptr;
+  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, max_tasks, max_waiting, lcp, max_rows)) return rc;
+  if (max_upd == sm.max_upd && max_rel == sm.max_rel && max_tasks == sm.max_tasks && max_rows == sm.max_rows &&
+      max_waiting == sm.max_waiting && lc.max_leases == sm.max_leases && lc.max_renew == sm.max_renew &&
+      lc.max_free == sm.max_free && lc.max_rep == sm.max_rep && lc.max_rep_ids == sm.max_rep_ids)
+    return YDC_OK;  // (nothing to do: the captured step stays)
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // A second set of buffers, filled from the first, which is released only once that has worked:
+  // after any failure the stream is as it was.
+  ydc_context::Stream grown;
+  int rc = stream_alloc(c, grown, max_upd, max_rel, max_tasks, max_waiting, lcp, max_rows);
+  if (rc == YDC_OK) rc = stream_reset(c, grown);
+  if (rc == YDC_OK) rc = stream_migrate(c, sm, grown);
+  if (rc != YDC_OK) {
+    stream_release(grown);
+    return rc;
+  }
+  grown.d_rep_tick = std::move(sm.d_rep_tick);  // (sized by the registry, not by the stream)
+  std::swap(sm, grown);
+  stream_release(grown);  // (the old buffers and the old captures; sm.stale: the step is captured again)
+  return YDC_OK;
 }
 
 int ydc_stream_waiting_take(ydc_context* c, uint64_t* out_tags, uint32_t cap, uint32_t* out_n) {
