@@ -530,6 +530,45 @@ typedef struct ydc_stream_caps {
 int ydc_stream_caps_get(ydc_context* ctx, ydc_stream_caps* out);
 int ydc_stream_reserve(ydc_context* ctx, const ydc_stream_caps* want);
 
+/* ---- the servants' running-task book (GetRunningTasks) --------------------------------
+ * The reference's NotifyServantRunningTasks (task_dispatcher.cc:222-277) answers unknown_tasks —
+ * out_report_unknown of the leased ticks — and hands the report minus the unknown ids to
+ * RunningTaskBookkeeper::SetServantRunningTasks; servant expiry calls DropServant and
+ * GetRunningTasks flattens what is left (running_task_bookkeeper.cc:24-43). A leased,
+ * waiting-and-leased or rpc stream keeps that flattened list B on the device once
+ * ydc_stream_book_begin was called, so a scheduler need not wait for out_report_unknown to filter
+ * its reports, renumber its copy on ydc_remove_servants or rebuild it across ydc_stream_reserve.
+ * An entry is four columns: servant_idx u32 | task_grant_id u64 (the reported id) |
+ * servant_task_id u64 | digest_key u64, a caller-chosen handle for the task_digest string, echoed
+ * back as a tag is (strings stay on the host).
+ *   ydc_stream_book_begin: the first call on an open stream switches B on, empty, with room for
+ *     max_book entries; a later call with a larger max_book grows it, entries and order kept; a
+ *     smaller or equal one returns YDC_OK and does nothing. An effective call allocates a second
+ *     set of the stream's buffers, copies, then swaps, all or nothing as ydc_stream_reserve does
+ *     (pointers of ydc_stream_buffers_get change), and the step is captured again at the next
+ *     tick. No open leased stream, max_book == 0, max_book > 2^30 or max_book + max_report_ids >=
+ *     2^31: YDC_ERR_INVALID_ARGUMENT. The next begin call of a stream and ydc_stream_end switch B
+ *     off and free it.
+ *   ydc_stream_book_stage: servant_task_id[k] and digest_key[k] for report_task_id[k] of the next
+ *     accepted tick; either pointer may be NULL (zeros); nothing staged: zeros. A tick whose
+ *     report-id count differs from a staged n_ids is refused with YDC_ERR_INVALID_ARGUMENT, nothing
+ *     applied, the staging left in place; an accepted tick consumes it.
+ *   A tick with B on (step 6 of a leased tick, for B): every entry of a servant that reports in the
+ *     tick is dropped; every reported id k with out_report_unknown[k] == 0 becomes a new entry (an
+ *     id listed twice gives two); an empty report only clears; servants that do not report keep
+ *     theirs. B's order: the surviving entries in their previous order, then the tick's permitted ids
+ *     in report order. A tick with |B| + reported ids > max_book is refused with YDC_ERR_CAPACITY and
+ *     nothing applied (conservative, like the bound on |L|).
+ *   ydc_stream_book_get: synchronises and copies B in its order; more than cap entries:
+ *     YDC_ERR_CAPACITY with *out_n = |B| and nothing written. B off: YDC_ERR_INVALID_ARGUMENT.
+ *   ydc_remove_servants drops the entries of removed rows (DropServant) and renumbers the others
+ *     with the registry; ydc_stream_reserve carries B over, max_book unchanged. */
+int ydc_stream_book_begin(ydc_context* ctx, uint32_t max_book);
+int ydc_stream_book_stage(ydc_context* ctx, const uint64_t* servant_task_id, const uint64_t* digest_key,
+                          uint32_t n_ids);
+int ydc_stream_book_get(ydc_context* ctx, uint32_t* out_servant_idx, uint64_t* out_task_grant_id,
+                        uint64_t* out_servant_task_id, uint64_t* out_digest_key, uint32_t cap, uint32_t* out_n);
+
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.
  * Rank 0 gets a 128-byte id (ncclGetUniqueId), the launcher hands it to every rank (any

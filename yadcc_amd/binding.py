@@ -39,6 +39,7 @@ ABI_SYMBOLS = (
     "ydc_stream_begin_leased", "ydc_stream_tick_leased", "ydc_stream_leases_get",
     "ydc_stream_begin_waiting_leased", "ydc_stream_tick_waiting_leased",
     "ydc_stream_begin_rpc", "ydc_stream_tick_rpc", "ydc_stream_caps_get", "ydc_stream_reserve",
+    "ydc_stream_book_begin", "ydc_stream_book_stage", "ydc_stream_book_get",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -189,6 +190,10 @@ def lib():
                                             C.c_uint32, C.POINTER(C.c_uint32)]
         L.ydc_stream_caps_get.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
         L.ydc_stream_reserve.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
+        L.ydc_stream_book_begin.argtypes = [C.c_void_p, C.c_uint32]
+        L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_uint32, C.POINTER(C.c_uint32)]
         L.ydc_group_unique_id.argtypes = [C.c_void_p]
         L.ydc_group_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ydc_group_init_local.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -860,6 +865,37 @@ class Context:
         self._stream_caps = (now["max_updates"], now["max_releases"], now["max_tasks"])
         self._max_waiting, self._max_leases, self._max_rows = now["max_waiting"], now["max_leases"], now["max_rows"]
         return now
+
+    def stream_book_begin(self, max_book):
+        """Switches the running-task book of the open leased, waiting-and-leased or rpc stream on,
+        or grows it with its entries kept (ydc_stream_book_begin)."""
+        self._check(lib().ydc_stream_book_begin(self._h, int(max_book)), "ydc_stream_book_begin")
+
+    def stream_book_stage(self, servant_task_ids=None, digest_keys=None, n_ids=None):
+        """The payload columns of the next accepted tick's reports, parallel to its report_ids
+        (ydc_stream_book_stage); a column left out is zeros."""
+        st = None if servant_task_ids is None else np.ascontiguousarray(servant_task_ids, dtype=np.uint64)
+        dk = None if digest_keys is None else np.ascontiguousarray(digest_keys, dtype=np.uint64)
+        if n_ids is None:
+            n_ids = len(st) if st is not None else len(dk) if dk is not None else 0
+        assert all(a is None or len(a) == n_ids for a in (st, dk))
+        self._check(lib().ydc_stream_book_stage(self._h, _ptr(st), _ptr(dk), int(n_ids)), "ydc_stream_book_stage")
+
+    def stream_book(self):
+        """The running-task book in its order (ydc_stream_book_get): (servant_idx uint32,
+        task_grant_id, servant_task_id, digest_key uint64)."""
+        n = C.c_uint32(0)
+        rc = lib().ydc_stream_book_get(self._h, None, None, None, None, 0, C.byref(n))
+        if rc == 0:
+            return np.empty(0, np.uint32), np.empty(0, np.uint64), np.empty(0, np.uint64), np.empty(0, np.uint64)
+        cap = int(n.value)
+        if cap == 0:
+            self._check(rc, "ydc_stream_book_get")
+        srv = np.empty(cap, np.uint32)
+        gid, stid, dkey = np.empty(cap, np.uint64), np.empty(cap, np.uint64), np.empty(cap, np.uint64)
+        self._check(lib().ydc_stream_book_get(self._h, srv.ctypes.data, gid.ctypes.data, stid.ctypes.data,
+                                              dkey.ctypes.data, cap, C.byref(n)), "ydc_stream_book_get")
+        return srv, gid, stid, dkey
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

@@ -27,6 +27,7 @@
 #include "lease_table.h"
 #include "rpc_stream.h"
 #include "wait_lease.h"
+#include "running_book.h"
 #include "tick_kernel.h"
 
 using namespace ydc;
@@ -127,6 +128,7 @@ struct TickArena {
   unsigned long long* rep_id;
   LeaseHdr* lh;
   uint32_t *nimm, *npre;  // rpc mode: grants asked for per request (NULL in any other context)
+  unsigned long long *bk_stid, *bk_dkey;  // with a running-task book: the reports' payload columns, beside rep_id
 };
 }  // namespace
 
@@ -323,6 +325,20 @@ struct ydc_context {
     unsigned long long *lb_scan = nullptr, *lb_settle = nullptr, *lb_grant = nullptr;
     uint8_t* h_rres = nullptr;  // page-locked: the RpcOut sections
     RpcOut rh{}, rz{};          // ... at their host and device addresses
+    // The running-task book B of a leased stream (ydc_stream_book_begin; running_book.h): its four
+    // columns and its bookkeeping in HBM, its look-back words at the tail of `lookback`, the
+    // page-locked outcome block. max_book == 0: no book (none of this exists).
+    uint32_t max_book = 0;
+    uint32_t n_book = 0;  // |B| after the last tick (the outcome block's, kept here)
+    DevBuf<uint8_t> d_book;
+    BookCols bk{};
+    BookState* bks = nullptr;
+    unsigned long long* lb_book = nullptr;
+    uint8_t* h_bres = nullptr;  // page-locked: the outcome block
+    BookOutcome *h_bout = nullptr, *z_bout = nullptr;
+    // ydc_stream_book_stage: the payload columns of the next accepted tick's reports.
+    bool book_staged = false;
+    std::vector<uint64_t> stage_stid, stage_dkey;
   } stream_mode;
   DevBuf<ClassRun> d_runs;
   DevBuf<uint8_t> d_dirty;
@@ -1127,9 +1143,18 @@ int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
   if (leased)
     hipLaunchKernelGGL(k_lease_remap, dim3(ceil_div(sm.lt.mask + 1, 256)), dim3(256), 0, c->stream, sm.lt, sm.ls,
                        c->d_upd_idx.p, n);
+  // ... and with a running-task book the entries of the removed rows (DropServant).
+  const bool booked = leased && sm.max_book;
+  if (booked) {
+    const uint32_t tiles = ceil_div(sm.max_book, kBookTile);
+    HIP_TRY(c, hipMemsetAsync(sm.lb_book, 0, (size_t)tiles * 8, c->stream));
+    hipLaunchKernelGGL(k_book_remap, dim3(tiles), dim3(256), 0, c->stream, sm.bk, sm.bks, sm.max_book,
+                       c->d_upd_idx.p, n, sm.lb_book);
+  }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (idx is pageable; the swap below retires the old columns)
   if (leased) HIP_TRY(c, hipMemcpy(&sm.n_leases, &sm.ls->n_leases, 4, hipMemcpyDeviceToHost));
+  if (booked) HIP_TRY(c, hipMemcpy(&sm.n_book, &sm.bks->n_entries, 4, hipMemcpyDeviceToHost));
   DevBuf<uint32_t>* cols[6] = {&c->d_version, &c->d_nproc, &c->d_load, &c->d_max_tasks, &c->d_running,
                                &c->d_flags};
   for (int k = 0; k < 6; ++k) std::swap(*cols[k], c->d_spare[k]);
@@ -3897,7 +3922,7 @@ void stream_drop_graphs(ydc_context::Stream& sm) {
 
 void stream_release(ydc_context::Stream& sm) {
   stream_drop_graphs(sm);
-  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres, sm.h_rres})
+  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres, sm.h_rres, sm.h_bres})
     if (h) (void)hipHostFree(h);
   sm = ydc_context::Stream{};  // (frees the device buffers: ydc_stream_end discards W)
 }
@@ -3988,6 +4013,13 @@ void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
     YDC_LAUNCH(c, "k_lease_report", k_lease_report, dim3(rep_blocks + ceil_div(sm.max_rep_ids, 256)), dim3(256), 0,
                c->stream, sm.lt, sm.ls, in, sm.max_rep, rep_blocks, sm.max_rep_ids, S, sm.d_rep_tick.p,
                sm.z_unknown);
+  // With a running-task book: the reports' permitted ids replace their servants' entries. Here and
+  // nowhere else: this part of the step runs once per tick on every path, and the eager exits
+  // place it no second time.
+  if (sm.max_book)
+    YDC_LAUNCH(c, "k_book_commit", k_book_commit, dim3(ceil_div(sm.max_book + sm.max_rep_ids, kBookTile)), dim3(256),
+               0, c->stream, sm.bk, sm.bks, sm.max_book, in, a.bk_stid, a.bk_dkey, sm.max_rep, sm.max_rep_ids, S,
+               sm.d_rep_tick.p, sm.z_unknown, sm.lb_book, sm.z_bout);
   YDC_LAUNCH(c, "k_lease_sweep", k_lease_sweep, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
              sm.lt, sm.ls, a.lh, S, sm.d_rep_tick.p, c->d_running.p);
 }
@@ -4177,7 +4209,10 @@ struct LeaseCaps {
 
 // The limits of a stream's capacities; `code`: what going beyond them is to the caller.
 int stream_caps_check(ydc_context* c, int code, uint32_t max_tasks, uint32_t max_waiting, const LeaseCaps* lc,
-                      uint32_t max_rows) {
+                      uint32_t max_rows, uint32_t max_book = 0) {
+  // (the book's pass is over max_book + max_report_ids positions, one 31-bit count)
+  if (max_book && (!lc || max_book > (1u << 30) || (uint64_t)max_book + lc->max_rep_ids > 0x7FFFFFFFull))
+    return fail(c, code, "max_book %u out of range (1 .. 2^30, max_book + max_report_ids < 2^31)", max_book);
   // (rpc mode: max_tasks is max_requests, the batch is the max_rows expanded rows)
   if (max_rows && (max_rows > (1u << 30) || max_rows < max_tasks))
     return fail(c, code, "max_rows %u out of range (max_requests %u .. 2^30)", max_rows, max_tasks);
@@ -4191,7 +4226,8 @@ int stream_caps_check(ydc_context* c, int code, uint32_t max_tasks, uint32_t max
 // Layout and allocation of everything a stream of these capacities has, into `sm` (released, or
 // fresh). Its contents are not defined before stream_reset; after a failure the caller releases it.
 int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, uint32_t max_releases,
-                 uint32_t max_tasks, uint32_t max_waiting, const LeaseCaps* lc, uint32_t max_rows) {
+                 uint32_t max_tasks, uint32_t max_waiting, const LeaseCaps* lc, uint32_t max_rows,
+                 uint32_t max_book = 0) {
   sm.max_upd = max_updates;
   sm.max_rel = max_releases;
   sm.max_tasks = max_tasks;
@@ -4218,6 +4254,9 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
   const size_t o_lh = lc ? section(&off, sizeof(LeaseHdr)) : 0;
   const size_t o_nimm = max_rows ? section(&off, (size_t)max_tasks * 4) : 0;
   const size_t o_npre = max_rows ? section(&off, (size_t)max_tasks * 4) : 0;
+  // ... a running-task book the reports' two payload columns.
+  const size_t o_bstid = max_book ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
+  const size_t o_bdkey = max_book ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
   auto arena_at = [&](uint8_t* b) {
     TickArena a{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
                 (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
@@ -4236,6 +4275,10 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     if (max_rows) {
       a.nimm = (uint32_t*)(b + o_nimm);
       a.npre = (uint32_t*)(b + o_npre);
+    }
+    if (max_book) {
+      a.bk_stid = (unsigned long long*)(b + o_bstid);
+      a.bk_dkey = (unsigned long long*)(b + o_bdkey);
     }
     return a;
   };
@@ -4310,6 +4353,9 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     sm.lookback_n = max_waiting ? 2 * ceil_div(max_tasks + max_waiting, kWaitTile) : ceil_div(max_tasks, kLeaseTile);
     // (rpc mode: the scan's and the settling's words per tile of positions, the grants' per tile of rows)
     if (max_rows) sm.lookback_n = 2 * ceil_div(max_tasks + max_waiting, kRpcTile) + ceil_div(max_rows, kRpcTile);
+    // (a running-task book: one word per tile of its pass, behind the others; k_lease_renew clears them all)
+    const uint32_t lb_own = sm.lookback_n;
+    if (max_book) sm.lookback_n += ceil_div(max_book + lc->max_rep_ids, kBookTile);
     size_t l_off = 0;
     auto lsec = [&](size_t bytes) { return section(&l_off, bytes); };
     const size_t o_key = lsec(cap * 8), o_exp = lsec(cap * 8), o_srv = lsec(cap * 4), o_st = lsec(cap * 4);
@@ -4323,6 +4369,7 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     sm.ren_slot = (uint32_t*)(b + o_rs);
     sm.lt_out = (uint32_t*)(b + o_out);
     sm.lookback = (unsigned long long*)(b + o_lb);
+    sm.lb_book = max_book ? sm.lookback + lb_own : nullptr;
     // Page-locked results: task ids | renewed | report_unknown | outcome block.
     size_t r_off = 0;
     const size_t r_id = section(&r_off, n_out * 8), r_ren = section(&r_off, lc->max_renew);
@@ -4381,6 +4428,24 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     sm.rh = out_at(sm.h_rres, sm.h_out, sm.h_task_id);
     sm.rz = out_at(z, sm.z_out, sm.z_task_id);
   }
+  if (max_book) {
+    sm.max_book = max_book;
+    // HBM: B's four columns and its bookkeeping. Page-locked: the outcome block.
+    size_t b_off = 0;
+    auto bsec = [&](size_t bytes) { return section(&b_off, bytes); };
+    const size_t o_srv = bsec((size_t)max_book * 4), o_gr = bsec((size_t)max_book * 8);
+    const size_t o_st = bsec((size_t)max_book * 8), o_dk = bsec((size_t)max_book * 8), o_bs = bsec(sizeof(BookState));
+    HIP_TRY(c, sm.d_book.reserve(b_off));
+    uint8_t* b = sm.d_book.p;
+    sm.bk = BookCols{(uint32_t*)(b + o_srv), (unsigned long long*)(b + o_gr), (unsigned long long*)(b + o_st),
+                     (unsigned long long*)(b + o_dk)};
+    sm.bks = (BookState*)(b + o_bs);
+    HIP_TRY(c, hipHostMalloc((void**)&sm.h_bres, 256, hipHostMallocCoherent | hipHostMallocMapped));
+    uint8_t* z = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&z, sm.h_bres, 0));
+    sm.h_bout = (BookOutcome*)sm.h_bres;
+    sm.z_bout = (BookOutcome*)z;
+  }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
   sm.stale = true;
   return YDC_OK;
@@ -4402,6 +4467,11 @@ int stream_reset(ydc_context* c, ydc_context::Stream& sm) {
   if (sm.max_rows) {
     HIP_TRY(c, hipMemsetAsync(sm.d_rpc.p, 0, sm.d_rpc.cap, c->stream));
     std::memset(sm.rh.outcome, 0, sizeof(RpcOutcome));
+  }
+  if (sm.max_book) {  // (B empty, the ticket 0)
+    HIP_TRY(c, hipMemsetAsync(sm.bks, 0, sizeof(BookState), c->stream));
+    std::memset(sm.h_bout, 0, sizeof(BookOutcome));
+    sm.n_book = 0;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   sm.active = true;
@@ -4440,6 +4510,19 @@ int stream_migrate(ydc_context* c, const ydc_context::Stream& o, ydc_context::St
     HIP_TRY(c, carry(n.rw.n_pre, o.rw.n_pre, 4));
     HIP_TRY(c, hipMemcpyAsync(&n.ws->count, &o.ws->count, 4, hipMemcpyDeviceToDevice, st));
   }
+  if (o.max_book && n.max_book) {
+    // B is compact between ticks: entries [0, |B|) of its columns as they lie, and |B|.
+    if (o.n_book > n.max_book)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "running-task book of %u > max_book %u", o.n_book, n.max_book);
+    auto carry = [&](void* dst, const void* src, size_t width) {
+      return o.n_book ? hipMemcpyAsync(dst, src, o.n_book * width, hipMemcpyDeviceToDevice, st) : hipSuccess;
+    };
+    HIP_TRY(c, carry(n.bk.servant, o.bk.servant, 4));
+    HIP_TRY(c, carry(n.bk.grant, o.bk.grant, 8));
+    HIP_TRY(c, carry(n.bk.stid, o.bk.stid, 8));
+    HIP_TRY(c, carry(n.bk.dkey, o.bk.dkey, 8));
+    HIP_TRY(c, hipMemcpyAsync(&n.bks->n_entries, &o.bks->n_entries, 4, hipMemcpyDeviceToDevice, st));
+  }
   HIP_TRY(c, hipStreamSynchronize(st));
   if (o.max_leases) {
     HIP_TRY(c, hipMemcpy(&ls_old, o.ls, sizeof ls_old, hipMemcpyDeviceToHost));
@@ -4458,6 +4541,12 @@ int stream_migrate(ydc_context* c, const ydc_context::Stream& o, ydc_context::St
   n.rep_seen = o.rep_seen;
   n.rep_mark = o.rep_mark;
   n.want_passes = o.want_passes;
+  if (o.max_book && n.max_book) {
+    n.n_book = o.n_book;
+    n.book_staged = o.book_staged;
+    n.stage_stid = o.stage_stid;
+    n.stage_dkey = o.stage_dkey;
+  }
   return YDC_OK;
 }
 
@@ -4472,6 +4561,9 @@ int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, ui
     return rc;
   return stream_reset(c, c->stream_mode);
 }
+
+int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t max_tasks, uint32_t max_waiting,
+                  const LeaseCaps* lcp, uint32_t max_rows, uint32_t max_book);
 
 }  // namespace
 
@@ -4519,18 +4611,30 @@ int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
                      std::max(sm.max_free, want->max_frees), std::max(sm.max_rep, want->max_reports),
                      std::max(sm.max_rep_ids, want->max_report_ids)};
   const LeaseCaps* lcp = sm.max_leases ? &lc : nullptr;
-  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, max_tasks, max_waiting, lcp, max_rows)) return rc;
+  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, max_tasks, max_waiting, lcp, max_rows, sm.max_book))
+    return rc;
   if (max_upd == sm.max_upd && max_rel == sm.max_rel && max_tasks == sm.max_tasks && max_rows == sm.max_rows &&
       max_waiting == sm.max_waiting && lc.max_leases == sm.max_leases && lc.max_renew == sm.max_renew &&
       lc.max_free == sm.max_free && lc.max_rep == sm.max_rep && lc.max_rep_ids == sm.max_rep_ids)
     return YDC_OK;  // (nothing to do: the captured step stays)
+  return stream_regrow(c, max_upd, max_rel, max_tasks, max_waiting, lcp, max_rows, sm.max_book);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The open stream in a second, larger set of buffers (ydc_stream_reserve, ydc_stream_book_begin).
+int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t max_tasks, uint32_t max_waiting,
+                  const LeaseCaps* lcp, uint32_t max_rows, uint32_t max_book) {
+  auto& sm = c->stream_mode;
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   // A second set of buffers, filled from the first, which is released only once that has worked:
   // after any failure the stream is as it was.
   ydc_context::Stream grown;
-  int rc = stream_alloc(c, grown, max_upd, max_rel, max_tasks, max_waiting, lcp, max_rows);
+  int rc = stream_alloc(c, grown, max_upd, max_rel, max_tasks, max_waiting, lcp, max_rows, max_book);
   if (rc == YDC_OK) rc = stream_reset(c, grown);
   if (rc == YDC_OK) rc = stream_migrate(c, sm, grown);
   if (rc != YDC_OK) {
@@ -4540,6 +4644,60 @@ int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
   grown.d_rep_tick = std::move(sm.d_rep_tick);  // (sized by the registry, not by the stream)
   std::swap(sm, grown);
   stream_release(grown);  // (the old buffers and the old captures; sm.stale: the step is captured again)
+  return YDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ydc_stream_book_begin(ydc_context* c, uint32_t max_book) {
+  if (!c || !max_book) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_leases)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_begin: no leased, waiting-and-leased or rpc stream is open");
+  const LeaseCaps lc{sm.max_leases, sm.max_renew, sm.max_free, sm.max_rep, sm.max_rep_ids};
+  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, sm.max_tasks, sm.max_waiting, &lc, sm.max_rows, max_book))
+    return rc;
+  if (max_book <= sm.max_book) return YDC_OK;  // (nothing to do: the captured step stays)
+  return stream_regrow(c, sm.max_upd, sm.max_rel, sm.max_tasks, sm.max_waiting, &lc, sm.max_rows, max_book);
+}
+
+int ydc_stream_book_stage(ydc_context* c, const uint64_t* servant_task_id, const uint64_t* digest_key,
+                          uint32_t n_ids) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_book)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_stage: the stream has no running-task book");
+  if (n_ids > sm.max_rep_ids)
+    return fail(c, YDC_ERR_CAPACITY, "%u staged ids > max_report_ids %u", n_ids, sm.max_rep_ids);
+  sm.stage_stid.assign(n_ids, 0);
+  sm.stage_dkey.assign(n_ids, 0);
+  if (servant_task_id) std::copy_n(servant_task_id, n_ids, sm.stage_stid.begin());
+  if (digest_key) std::copy_n(digest_key, n_ids, sm.stage_dkey.begin());
+  sm.book_staged = true;
+  return YDC_OK;
+}
+
+int ydc_stream_book_get(ydc_context* c, uint32_t* out_servant_idx, uint64_t* out_task_grant_id,
+                        uint64_t* out_servant_task_id, uint64_t* out_digest_key, uint32_t cap, uint32_t* out_n) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_book)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_get: the stream has no running-task book");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t n = sm.n_book;
+  *out_n = n;
+  if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u book entries > cap %u", n, cap);
+  if (n && (!out_servant_idx || !out_task_grant_id || !out_servant_task_id || !out_digest_key))
+    return YDC_ERR_INVALID_ARGUMENT;
+  if (n) {
+    HIP_TRY(c, hipMemcpy(out_servant_idx, sm.bk.servant, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_task_grant_id, sm.bk.grant, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_servant_task_id, sm.bk.stid, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_digest_key, sm.bk.dkey, (size_t)n * 8, hipMemcpyDeviceToHost));
+  }
   return YDC_OK;
 }
 
@@ -4616,6 +4774,7 @@ static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tas
 
 // The lease outcome block is this tick's and |L| is in range.
 static bool stream_lease_outcome_ok(const ydc_context::Stream& sm) {
+  if (sm.max_book && (sm.h_bout->tick_no != sm.lease_tick || sm.h_bout->n_entries > sm.max_book)) return false;
   return sm.h_lout->tick_no == sm.lease_tick && sm.h_lout->n_leases <= sm.max_leases;
 }
 
@@ -4633,6 +4792,7 @@ static void stream_lease_apply(ydc_context* c, const LeaseTick* lt) {
   c->stats.leases_freed = o.freed;
   c->stats.renewals_refused = o.renew_refused;
   sm.n_leases = o.n_leases;
+  if (sm.max_book) sm.n_book = sm.h_bout->n_entries;
   sm.last_now = lt->now;
 }
 
@@ -4837,6 +4997,16 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
                     lt->rep_srv[bad]);
       }
     }
+    if (sm.max_book) {
+      // (conservative like the |L| bound: every reported id may be permitted, no entry dropped)
+      const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
+      if (sm.book_staged && sm.stage_stid.size() != n_ids)
+        return fail(c, YDC_ERR_INVALID_ARGUMENT, "%zu ids staged with ydc_stream_book_stage, %u reported",
+                    sm.stage_stid.size(), n_ids);
+      if ((uint64_t)sm.n_book + n_ids > sm.max_book)
+        return fail(c, YDC_ERR_CAPACITY, "%u book entries + %u reported ids > max_book %u", sm.n_book, n_ids,
+                    sm.max_book);
+    }
   }
   if (upd_env_masks && (env_words == 0 || env_words > YDC_MAX_ENV_WORDS))
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "env_words %u out of range", env_words);
@@ -4912,6 +5082,16 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       std::memcpy(h.rep_off, lt->rep_off, ((size_t)lt->n_rep + 1) * 4);
     }
     if (n_ids) std::memcpy(h.rep_id, lt->rep_id, (size_t)n_ids * 8);
+    if (sm.max_book) {  // (the staged payload columns, consumed; nothing staged: zeros)
+      if (n_ids && sm.book_staged) {
+        std::memcpy(h.bk_stid, sm.stage_stid.data(), (size_t)n_ids * 8);
+        std::memcpy(h.bk_dkey, sm.stage_dkey.data(), (size_t)n_ids * 8);
+      } else if (n_ids) {
+        std::memset(h.bk_stid, 0, (size_t)n_ids * 8);
+        std::memset(h.bk_dkey, 0, (size_t)n_ids * 8);
+      }
+      sm.book_staged = false;
+    }
     // (the counts make the unused capacity a no-op; a tick number's low 30 bits are never 0)
     if ((++sm.lease_tick & kLeaseStamp) == 0) ++sm.lease_tick;
     *h.lh = LeaseHdr{lt->now, lt->n_renew, lt->n_free, lt->n_rep, n_ids, sm.lease_tick, 0};
