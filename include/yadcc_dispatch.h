@@ -569,6 +569,51 @@ int ydc_stream_book_stage(ydc_context* ctx, const uint64_t* servant_task_id, con
 int ydc_stream_book_get(ydc_context* ctx, uint32_t* out_servant_idx, uint64_t* out_task_grant_id,
                         uint64_t* out_servant_task_id, uint64_t* out_digest_key, uint32_t cap, uint32_t* out_n);
 
+/* ---- the servants' expiry on the device: KeepServantAlive's expires_in and the servant half of
+ * OnExpirationTimer (task_dispatcher.cc:190-220, :498-520) inside the tick -------------------------
+ * With aliveness on, every servant has an expires_at (int64, on the clock the ticks carry as `now`)
+ * in HBM, and step 5 of a leased, waiting-and-leased or rpc tick is the WHOLE of OnExpirationTimer, in
+ * the reference's order:
+ *   - heartbeat i of the tick (step 1) also sets expires_at[upd_idx[i]] = upd_expires_at[i]; a servant
+ *     the tick appends gets its value the same way;
+ *   - steps 2 - 4 (renewals, frees by id, releases) run on the numbering the caller used;
+ *   - step 5: every servant with expires_at < now (strict) is erased — the survivors keep their order,
+ *     their running_tasks and their host aliases —, its book entries are dropped (DropServant), every
+ *     lease on it is erased as an orphan without the zombie stage (UnsafeSweepOrphans), and only then
+ *     do leases with expires_at < now become zombies;
+ *   - steps 6 onward run on the compacted registry: a report of a servant that was just erased answers
+ *     out_report_unknown = 1 for all its ids and touches neither leases nor book; out_servant_idx, the
+ *     lease snapshot and the book are in the new numbering.
+ * So a renewal (step 2) of a lease that is orphaned in step 5 answers 1, a free of it counts in
+ * leases_freed, an orphan is never counted in leases_expired or leases_swept, *out_n_leases excludes
+ * the orphans, and the waiting queue (which holds no servant index) is untouched. A heartbeat whose own
+ * upd_expires_at is already < now files the row, and the servant is erased in the same tick.
+ *   ydc_stream_alive_begin: switches aliveness on for the open leased, waiting-and-leased or rpc stream
+ *     (any other context or mode: YDC_ERR_INVALID_ARGUMENT). n must be the registry's servant count;
+ *     expires_at == NULL: "never" (INT64_MAX) until a heartbeat says otherwise. A second call replaces
+ *     the column. The stream's next begin call and ydc_stream_end switch it off.
+ *   ydc_stream_alive_stage: the expiries of the NEXT accepted tick's heartbeats, parallel to its
+ *     upd_idx. With aliveness on, a tick whose n_upd differs from the staged count (nothing staged
+ *     counts as 0) or that names a servant twice in upd_idx is refused with YDC_ERR_INVALID_ARGUMENT,
+ *     nothing applied, the staging kept. An accepted tick consumes the staging.
+ *   ydc_stream_alive_removed: the rows the most recent accepted tick erased, strictly ascending, in
+ *     the numbering BEFORE that tick's removal (rows the tick itself appended included), and how many
+ *     leases went with them as orphans; *out_n == 0 after an ordinary tick. More than cap rows:
+ *     YDC_ERR_CAPACITY with *out_n set and nothing written. A caller renumbers its own location table
+ *     by dropping these rows in order.
+ *   ydc_stream_alive_get: synchronises and copies the column (DumpInternals, tests).
+ *   ydc_remove_servants by the caller compacts the column with the registry; ydc_stream_reserve and
+ *     ydc_stream_book_begin carry it over. No tick signature changes; a stream without aliveness
+ *     launches what it launched before.
+ *   A tick that erased servants and then fails (capacity of the slot workspace, a placement that does
+ *     not converge) has still erased them, their book entries and their leases: ydc_stream_alive_removed
+ *     names the rows as after a successful tick, and the caller renumbers before it tries again. */
+int ydc_stream_alive_begin(ydc_context* ctx, const int64_t* expires_at, uint32_t n);
+int ydc_stream_alive_stage(ydc_context* ctx, const int64_t* upd_expires_at, uint32_t n_upd);
+int ydc_stream_alive_removed(ydc_context* ctx, uint32_t* out_idx, uint32_t cap, uint32_t* out_n,
+                             uint32_t* out_n_orphans);
+int ydc_stream_alive_get(ydc_context* ctx, int64_t* out_expires_at, uint32_t cap, uint32_t* out_n);
+
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.
  * Rank 0 gets a 128-byte id (ncclGetUniqueId), the launcher hands it to every rank (any

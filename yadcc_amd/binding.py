@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "ydc_stream_begin_waiting_leased", "ydc_stream_tick_waiting_leased",
     "ydc_stream_begin_rpc", "ydc_stream_tick_rpc", "ydc_stream_caps_get", "ydc_stream_reserve",
     "ydc_stream_book_begin", "ydc_stream_book_stage", "ydc_stream_book_get",
+    "ydc_stream_alive_begin", "ydc_stream_alive_stage", "ydc_stream_alive_removed", "ydc_stream_alive_get",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -190,6 +191,11 @@ def lib():
                                             C.c_uint32, C.POINTER(C.c_uint32)]
         L.ydc_stream_caps_get.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
         L.ydc_stream_reserve.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
+        L.ydc_stream_alive_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ydc_stream_alive_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ydc_stream_alive_removed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.ydc_stream_alive_get.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ydc_debug_alive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ydc_stream_book_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -377,6 +383,8 @@ class Context:
         self._stream_caps = (0, 0, 0)
         self._max_waiting = 0
         self._max_rows = 0
+        self._alive = False
+        self._alive_removals = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -598,6 +606,7 @@ class Context:
             self._check(lib().ydc_stream_begin(self._h, max_updates, max_releases, max_tasks),
                         "ydc_stream_begin")
         self._stream_caps = (int(max_updates), int(max_releases), int(max_tasks))
+        self._alive = False
         self._max_waiting = int(max_waiting)
 
     def stream_tick_waiting(self, upd_idx, upd_rows, release_idx, tasks, deadlines, tags, now,
@@ -646,6 +655,7 @@ class Context:
                                                   max_renewals, max_frees, max_reports, max_report_ids),
                     "ydc_stream_begin_leased")
         self._stream_caps = (int(max_updates), int(max_releases), int(max_tasks))
+        self._alive = False
         self._max_waiting = 0
         self._max_leases = int(max_leases)
 
@@ -693,6 +703,7 @@ class Context:
             rs.ctypes.data, ro.ctypes.data, ri.ctypes.data, len(rs), C.byref(soa), lex.ctypes.data, n, int(now),
             out.ctypes.data, ids.ctypes.data, renewed.ctypes.data, unknown.ctypes.data, C.byref(n_leases)),
             "ydc_stream_tick_leased")
+        self._alive_shrink()
         return out, ids, renewed, unknown, int(n_leases.value)
 
     def stream_begin_waiting_leased(self, max_updates, max_releases, max_tasks, max_waiting, max_leases,
@@ -704,6 +715,7 @@ class Context:
             self._h, max_updates, max_releases, max_tasks, max_waiting, max_leases, max_renewals, max_frees,
             max_reports, max_report_ids), "ydc_stream_begin_waiting_leased")
         self._stream_caps = (int(max_updates), int(max_releases), int(max_tasks))
+        self._alive = False
         self._max_waiting = int(max_waiting)
         self._max_leases = int(max_leases)
 
@@ -758,6 +770,7 @@ class Context:
             dl.ctypes.data, tg.ctypes.data, n, int(now), out.ctypes.data, ids.ctypes.data, renewed.ctypes.data,
             unknown.ctypes.data, C.byref(n_leases), res_tags.ctypes.data, res_idx.ctypes.data,
             res_ids.ctypes.data, C.byref(n_res), C.byref(n_wait)), "ydc_stream_tick_waiting_leased")
+        self._alive_shrink()
         k = n_res.value
         return (out, ids, renewed, unknown, int(n_leases.value), res_tags[:k].copy(), res_idx[:k].copy(),
                 res_ids[:k].copy(), int(n_wait.value))
@@ -771,6 +784,7 @@ class Context:
             self._h, max_updates, max_releases, max_requests, max_rows, max_waiting, max_leases, max_renewals,
             max_frees, max_reports, max_report_ids), "ydc_stream_begin_rpc")
         self._stream_caps = (int(max_updates), int(max_releases), int(max_requests))
+        self._alive = False
         self._max_waiting = int(max_waiting)
         self._max_leases = int(max_leases)
         self._max_rows = int(max_rows)
@@ -832,6 +846,7 @@ class Context:
             res_tags.ctypes.data, res_status.ctypes.data, res_n.ctypes.data, res_first.ctypes.data,
             res_srv.ctypes.data, res_ids.ctypes.data, C.byref(n_res), C.byref(n_wait), C.byref(n_wrows)),
             "ydc_stream_tick_rpc")
+        self._alive_shrink()
         k = n_res.value
         g = int((res_first[:k].astype(np.int64) + res_n[:k]).max()) if k else 0
         return {"status": status, "n_granted": n_granted, "row_off": row_off, "servants": out[:int(row_off[-1])],
@@ -896,6 +911,64 @@ class Context:
         self._check(lib().ydc_stream_book_get(self._h, srv.ctypes.data, gid.ctypes.data, stid.ctypes.data,
                                               dkey.ctypes.data, cap, C.byref(n)), "ydc_stream_book_get")
         return srv, gid, stid, dkey
+
+    def stream_alive_begin(self, expires_at=None, n=None):
+        """Switches the servants' expiry column of the open leased, waiting-and-leased or rpc stream
+        on (ydc_stream_alive_begin): one expires_at (int64, the ticks' clock) per servant of the
+        registry; None: `n` servants that never expire until a heartbeat says otherwise."""
+        e = None if expires_at is None else np.ascontiguousarray(expires_at, dtype=np.int64)
+        if n is None:
+            n = len(e) if e is not None else 0
+        assert e is None or len(e) == n
+        self._check(lib().ydc_stream_alive_begin(self._h, _ptr(e), int(n)), "ydc_stream_alive_begin")
+        if not self._alive:
+            self._alive_removals = 0
+        self._alive = True
+
+    def _alive_shrink(self):
+        """With aliveness on, a tick may have erased servants: the row count follows (from the
+        stream's running count of erased rows, a call that cannot fail)."""
+        if self._alive:
+            total = self.debug_alive()[2]
+            self.n_servants -= total - self._alive_removals
+            self._alive_removals = total
+
+    def stream_alive_stage(self, upd_expires_at):
+        """The expiries of the next accepted tick's heartbeats, parallel to its upd_idx
+        (ydc_stream_alive_stage)."""
+        e = np.ascontiguousarray(upd_expires_at, dtype=np.int64)
+        self._check(lib().ydc_stream_alive_stage(self._h, _ptr(e) if len(e) else None, len(e)), "ydc_stream_alive_stage")
+
+    def stream_alive_removed(self):
+        """(rows the most recent accepted tick erased — ascending, in the numbering before its
+        removal —, leases that went with them as orphans) (ydc_stream_alive_removed)."""
+        n, orphans = C.c_uint32(0), C.c_uint32(0)
+        rc = lib().ydc_stream_alive_removed(self._h, None, 0, C.byref(n), C.byref(orphans))
+        if n.value == 0:
+            self._check(rc, "ydc_stream_alive_removed")
+            return np.empty(0, np.uint32), int(orphans.value)
+        idx = np.empty(n.value, np.uint32)
+        self._check(lib().ydc_stream_alive_removed(self._h, idx.ctypes.data, len(idx), C.byref(n), C.byref(orphans)),
+                    "ydc_stream_alive_removed")
+        return idx, int(orphans.value)
+
+    def stream_alive(self):
+        """The servants' expiry column (ydc_stream_alive_get): int64 per servant."""
+        n = C.c_uint32(0)
+        rc = lib().ydc_stream_alive_get(self._h, None, 0, C.byref(n))
+        if n.value == 0:
+            self._check(rc, "ydc_stream_alive_get")
+            return np.empty(0, np.int64)
+        out = np.empty(n.value, np.int64)
+        self._check(lib().ydc_stream_alive_get(self._h, out.ctypes.data, len(out), C.byref(n)), "ydc_stream_alive_get")
+        return out
+
+    def debug_alive(self):
+        """Tests and tools: (the host's lower bound of the smallest expires_at, ticks that asked the
+        device who is due so far, servants the ticks removed so far)."""
+        b, a, r = C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().ydc_debug_alive(self._h, C.byref(b), C.byref(a), C.byref(r)), "ydc_debug_alive")
+        return int(b.value), int(a.value), int(r.value)
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,
@@ -982,6 +1055,7 @@ class Context:
     def stream_end(self):
         self._check(lib().ydc_stream_end(self._h), "ydc_stream_end")
         self._max_waiting = 0
+        self._alive = False
 
     def set_profiling(self, on):
         self._check(lib().ydc_set_profiling(self._h, int(on)), "ydc_set_profiling")

@@ -28,6 +28,7 @@
 #include "rpc_stream.h"
 #include "wait_lease.h"
 #include "running_book.h"
+#include "servant_alive.h"
 #include "tick_kernel.h"
 
 using namespace ydc;
@@ -129,6 +130,7 @@ struct TickArena {
   LeaseHdr* lh;
   uint32_t *nimm, *npre;  // rpc mode: grants asked for per request (NULL in any other context)
   unsigned long long *bk_stid, *bk_dkey;  // with a running-task book: the reports' payload columns, beside rep_id
+  int64_t* upd_exp;  // leased modes: the heartbeats' expiries, beside upd_idx (read only with aliveness on)
 };
 }  // namespace
 
@@ -339,6 +341,28 @@ struct ydc_context {
     // ydc_stream_book_stage: the payload columns of the next accepted tick's reports.
     bool book_staged = false;
     std::vector<uint64_t> stage_stid, stage_dkey;
+    // The servants' expiry column E of a leased stream (ydc_stream_alive_begin; servant_alive.h): sized
+    // by the registry like d_rep_tick, with a spare the removal route compacts into. alive == false:
+    // no aliveness (none of this exists, and the step launches what it launches without it).
+    bool alive = false;
+    uint32_t alive_n = 0;  // rows of E that are filed (the registry's servant count, between ticks)
+    DevBuf<int64_t> d_alive, d_alive_spare, d_alive_stage;
+    DevBuf<uint32_t> d_alive_idx;
+    DevBuf<AliveState> d_alive_state;
+    uint32_t* h_alive_list = nullptr;  // page-locked: k_alive_due's list
+    uint32_t* z_alive_list = nullptr;  // ... its device address
+    size_t alive_list_cap = 0;
+    int64_t alive_bound = INT64_MAX;  // <= min(E): only errs low; k_alive_due makes it exact
+    uint64_t alive_alarms = 0, alive_removals = 0;  // ticks that launched k_alive_due; ... and removed rows
+    // ydc_stream_alive_stage: the expiries of the next accepted tick's heartbeats.
+    bool alive_staged = false;
+    std::vector<int64_t> alive_stage;
+    // What the most recent accepted tick erased (ydc_stream_alive_removed).
+    std::vector<uint32_t> alive_removed;
+    uint32_t alive_orphans = 0;
+    std::vector<uint32_t> alive_seen;  // per servant: alive_mark of the last heartbeat list that named it
+    uint32_t alive_mark = 0;
+    std::vector<uint32_t> alive_rel, alive_rep;  // the removal route's rewritten releases and report servants
   } stream_mode;
   DevBuf<ClassRun> d_runs;
   DevBuf<uint8_t> d_dirty;
@@ -496,6 +520,7 @@ struct ydc_context {
 namespace {
 
 void stream_release(ydc_context* c);  // streaming mode, defined further down
+int alive_fit(ydc_context* c);         // ... its servants' expiry column, defined further down
 void resident_stop(ydc_context* c);   // small-batch path's resident kernel, defined further down
 void group_release(ydc_context* c);   // multi-GPU group, defined further down
 
@@ -1117,19 +1142,27 @@ int ydc_set_host_aliases(ydc_context* c, const uint32_t* ip_id, const uint32_t* 
   return rebuild_tables(c);
 }
 
-int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
-  if (!c || (n && !idx)) return YDC_ERR_INVALID_ARGUMENT;
-  if (!n) return YDC_OK;
-  for (uint32_t i = 0; i < n; ++i)
-    if (idx[i] >= c->n_servants || (i && idx[i] <= idx[i - 1]))
-      return fail(c, YDC_ERR_INVALID_ARGUMENT, "removed rows must be ascending and < %u", c->n_servants);
+// The body of ydc_remove_servants (idx: checked, ascending). in_tick: the removal route of a tick with
+// aliveness on (servant_alive.h) — the leases of removed rows are parked for the tick's own steps
+// instead of erased, and the host aliases of the survivors are kept and renumbered (the caller
+// cannot set them again in the middle of a tick).
+static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_tick) {
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   const uint32_t S = c->n_servants, kept = S - n, EW = c->env_words;
-  // Device: order-preserving compaction of the six resident columns into spare buffers,
-  // which then take their place (running_tasks of the survivors never leaves the device).
+  auto& sm = c->stream_mode;
+  const bool leased = sm.active && sm.max_leases;
+  const bool alive = leased && sm.alive;
+  // Everything that can fail for want of memory comes before the first launch: a removal is applied
+  // to registry, leases, book and expiry column together or not at all.
   HIP_TRY(c, c->d_upd_idx.reserve(n));
   for (auto& b : c->d_spare) HIP_TRY(c, b.reserve(c->d_version.cap));
+  if (alive) {
+    if (int rc = alive_fit(c)) return rc;  // (rows the registry gained outside a tick: "never")
+    HIP_TRY(c, sm.d_alive_spare.reserve(sm.d_alive.cap));
+  }
+  // Device: order-preserving compaction of the six resident columns into spare buffers,
+  // which then take their place (running_tasks of the survivors never leaves the device).
   HIP_TRY(c, hipMemcpyAsync(c->d_upd_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   CompactCols in{{c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p, c->d_running.p, c->d_flags.p}};
   CompactCols out{{c->d_spare[0].p, c->d_spare[1].p, c->d_spare[2].p, c->d_spare[3].p, c->d_spare[4].p,
@@ -1138,11 +1171,16 @@ int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
                      c->d_upd_idx.p, n, S);
   // A leased stream: the leases of the removed rows vanish (UnsafeSweepOrphans), the others follow
   // the compaction.
-  auto& sm = c->stream_mode;
-  const bool leased = sm.active && sm.max_leases;
-  if (leased)
+  if (leased && in_tick)
+    hipLaunchKernelGGL(k_alive_remap, dim3(ceil_div(sm.lt.mask + 1, 256)), dim3(256), 0, c->stream, sm.lt,
+                       c->d_upd_idx.p, n);
+  else if (leased)
     hipLaunchKernelGGL(k_lease_remap, dim3(ceil_div(sm.lt.mask + 1, 256)), dim3(256), 0, c->stream, sm.lt, sm.ls,
                        c->d_upd_idx.p, n);
+  // ... and with aliveness the expiry column follows the registry's columns.
+  if (alive)
+    hipLaunchKernelGGL(k_alive_compact, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, sm.d_alive.p,
+                       sm.d_alive_spare.p, c->d_upd_idx.p, n, S);
   // ... and with a running-task book the entries of the removed rows (DropServant).
   const bool booked = leased && sm.max_book;
   if (booked) {
@@ -1158,6 +1196,10 @@ int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
   DevBuf<uint32_t>* cols[6] = {&c->d_version, &c->d_nproc, &c->d_load, &c->d_max_tasks, &c->d_running,
                                &c->d_flags};
   for (int k = 0; k < 6; ++k) std::swap(*cols[k], c->d_spare[k]);
+  if (alive) {
+    std::swap(sm.d_alive, sm.d_alive_spare);
+    sm.alive_n = kept;
+  }
   // Host mirror.
   uint32_t w = 0, next = 0;
   for (uint32_t s = 0; s < S; ++s) {
@@ -1177,8 +1219,21 @@ int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
     ++w;
   }
   c->n_servants = kept;
-  c->h_alias_ip.clear();  // (row numbers moved)
-  c->h_alias_servant.clear();
+  if (in_tick) {  // (the survivors' entries, in the new numbering)
+    size_t wa = 0;
+    for (size_t a = 0; a < c->h_alias_servant.size(); ++a) {
+      const uint32_t s = c->h_alias_servant[a];
+      const uint32_t before = (uint32_t)(std::lower_bound(idx, idx + n, s) - idx);
+      if (before < n && idx[before] == s) continue;
+      c->h_alias_ip[wa] = c->h_alias_ip[a];
+      c->h_alias_servant[wa++] = s - before;
+    }
+    c->h_alias_ip.resize(wa);
+    c->h_alias_servant.resize(wa);
+  } else {
+    c->h_alias_ip.clear();  // (row numbers moved)
+    c->h_alias_servant.clear();
+  }
   c->h_version.resize(kept);
   c->h_nproc.resize(kept);
   c->h_load.resize(kept);
@@ -1187,6 +1242,15 @@ int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
   c->h_ip.resize(kept);
   c->h_env.resize((size_t)kept * EW);
   return rebuild_tables(c);  // classes, the ip table and the slot bound follow the registry
+}
+
+int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
+  if (!c || (n && !idx)) return YDC_ERR_INVALID_ARGUMENT;
+  if (!n) return YDC_OK;
+  for (uint32_t i = 0; i < n; ++i)
+    if (idx[i] >= c->n_servants || (i && idx[i] <= idx[i - 1]))
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "removed rows must be ascending and < %u", c->n_servants);
+  return remove_rows(c, idx, n, false);
 }
 
 // FreeTask's --running_tasks for a list of grants (servant indexes on the device).
@@ -3922,7 +3986,7 @@ void stream_drop_graphs(ydc_context::Stream& sm) {
 
 void stream_release(ydc_context::Stream& sm) {
   stream_drop_graphs(sm);
-  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres, sm.h_rres, sm.h_bres})
+  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres, sm.h_rres, sm.h_bres, (uint8_t*)sm.h_alive_list})
     if (h) (void)hipHostFree(h);
   sm = ydc_context::Stream{};  // (frees the device buffers: ydc_stream_end discards W)
 }
@@ -4003,6 +4067,11 @@ void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
   const LeaseIn in = lease_in(a);
   const uint32_t S = c->n_servants;
   const uint32_t ren_blocks = ceil_div(sm.max_renew, 256), rep_blocks = ceil_div(sm.max_rep, 256);
+  // With aliveness: the heartbeats' expiries into E (servant_alive.h). Here for the reason the book's
+  // pass is here: once per tick on every path.
+  if (sm.alive && sm.max_upd)
+    YDC_LAUNCH(c, "k_alive_beat", k_alive_beat, dim3(ceil_div(sm.max_upd, 256)), dim3(256), 0, c->stream, a.upd_idx,
+               a.upd_exp, sm.max_upd, std::min(S, sm.alive_n), sm.d_alive.p);
   YDC_LAUNCH(c, "k_lease_renew", k_lease_renew, dim3(std::max(1u, ceil_div(std::max(sm.max_renew, sm.lookback_n), 256))),
              dim3(256), 0, c->stream, sm.lt, sm.ls, in, sm.max_renew, sm.ren_slot, sm.z_renewed, sm.lookback,
              sm.lookback_n);
@@ -4257,6 +4326,8 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
   // ... a running-task book the reports' two payload columns.
   const size_t o_bstid = max_book ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
   const size_t o_bdkey = max_book ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
+  // ... and, last (no other section moves), the heartbeats' expiries of a leased stream.
+  const size_t o_uexp = lc ? section(&off, (size_t)max_updates * 8) : 0;
   auto arena_at = [&](uint8_t* b) {
     TickArena a{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
                 (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
@@ -4271,6 +4342,7 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
       a.rep_off = (uint32_t*)(b + o_rep_off);
       a.rep_id = (unsigned long long*)(b + o_rep_id);
       a.lh = (LeaseHdr*)(b + o_lh);
+      a.upd_exp = (int64_t*)(b + o_uexp);
     }
     if (max_rows) {
       a.nimm = (uint32_t*)(b + o_nimm);
@@ -4624,6 +4696,139 @@ int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
 
 namespace {
 
+// ---- the servants' expiry column (servant_alive.h) ----
+
+// Everything aliveness keeps, from the stream `o` to the one that takes its place.
+void alive_carry(ydc_context::Stream& o, ydc_context::Stream& n) {
+  n.alive = o.alive;
+  n.alive_n = o.alive_n;
+  n.d_alive = std::move(o.d_alive);
+  n.d_alive_spare = std::move(o.d_alive_spare);
+  n.d_alive_stage = std::move(o.d_alive_stage);
+  n.d_alive_idx = std::move(o.d_alive_idx);
+  n.d_alive_state = std::move(o.d_alive_state);
+  n.h_alive_list = o.h_alive_list;
+  n.z_alive_list = o.z_alive_list;
+  n.alive_list_cap = o.alive_list_cap;
+  o.h_alive_list = o.z_alive_list = nullptr;
+  o.alive_list_cap = 0;
+  n.alive_bound = o.alive_bound;
+  n.alive_alarms = o.alive_alarms;
+  n.alive_removals = o.alive_removals;
+  n.alive_staged = o.alive_staged;
+  n.alive_stage = o.alive_stage;
+  n.alive_removed = o.alive_removed;
+  n.alive_orphans = o.alive_orphans;
+}
+
+// E has a row for every servant of the registry; rows it gains start at "never".
+int alive_fit(ydc_context* c) {
+  auto& sm = c->stream_mode;
+  const uint32_t S = c->n_servants;
+  if (S < sm.alive_n) sm.alive_n = S;
+  if (S == sm.alive_n) return YDC_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (S > sm.d_alive.cap) {
+    DevBuf<int64_t> bigger;
+    HIP_TRY(c, bigger.reserve((size_t)S + S / 2 + 1024));
+    if (sm.alive_n) {
+      HIP_TRY(c, hipMemcpyAsync(bigger.p, sm.d_alive.p, (size_t)sm.alive_n * 8, hipMemcpyDeviceToDevice, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    sm.d_alive = std::move(bigger);
+    sm.stale = true;  // (a captured step holds the column's address)
+  }
+  const std::vector<int64_t> never(S - sm.alive_n, kAliveNever);
+  HIP_TRY(c, hipMemcpy(sm.d_alive.p + sm.alive_n, never.data(), never.size() * 8, hipMemcpyHostToDevice));
+  sm.alive_n = S;
+  return YDC_OK;
+}
+
+// n heartbeats' expiries into E now (k_alive_beat on a device copy of the two columns).
+int alive_file(ydc_context* c, const uint32_t* idx, const int64_t* expires, uint32_t n) {
+  auto& sm = c->stream_mode;
+  if (!n) return YDC_OK;
+  HIP_TRY(c, sm.d_alive_idx.reserve(n));
+  HIP_TRY(c, sm.d_alive_stage.reserve(n));
+  HIP_TRY(c, hipMemcpy(sm.d_alive_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(sm.d_alive_stage.p, expires, (size_t)n * 8, hipMemcpyHostToDevice));
+  YDC_LAUNCH(c, "k_alive_beat", k_alive_beat, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, sm.d_alive_idx.p,
+             sm.d_alive_stage.p, n, sm.alive_n, sm.d_alive.p);
+  HIP_TRY(c, hipGetLastError());
+  return YDC_OK;
+}
+
+// The alarm: the rows with E < now, ascending, in h_alive_list[0, *n_due); alive_bound exact (the
+// minimum over the rows that stay).
+int alive_due(ydc_context* c, int64_t now, uint32_t* n_due) {
+  auto& sm = c->stream_mode;
+  *n_due = 0;
+  ++sm.alive_alarms;
+  if (!sm.alive_n) {
+    sm.alive_bound = kAliveNever;
+    return YDC_OK;
+  }
+  HIP_TRY(c, sm.d_alive_state.reserve(1));
+  if (sm.alive_list_cap < sm.alive_n) {
+    if (sm.h_alive_list) (void)hipHostFree(sm.h_alive_list);
+    sm.h_alive_list = sm.z_alive_list = nullptr;
+    sm.alive_list_cap = 0;
+    const size_t want = (size_t)sm.alive_n + sm.alive_n / 2 + 1024;
+    HIP_TRY(c, hipHostMalloc((void**)&sm.h_alive_list, want * 4, hipHostMallocCoherent | hipHostMallocMapped));
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&sm.z_alive_list, sm.h_alive_list, 0));
+    sm.alive_list_cap = want;
+  }
+  AliveState st{kAliveNever, 0, 0, 0, 0};
+  HIP_TRY(c, hipMemcpy(sm.d_alive_state.p, &st, sizeof st, hipMemcpyHostToDevice));
+  YDC_LAUNCH(c, "k_alive_due", k_alive_due, dim3(ceil_div(sm.alive_n, 256)), dim3(256), 0, c->stream, sm.d_alive.p,
+             sm.alive_n, now, sm.d_alive_state.p, sm.z_alive_list);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(&st, sm.d_alive_state.p, sizeof st, hipMemcpyDeviceToHost));
+  if (st.n_due > sm.alive_n) return fail(c, YDC_ERR_NOT_CONVERGED, "%u of %u servants due", st.n_due, sm.alive_n);
+  std::sort(sm.h_alive_list, sm.h_alive_list + st.n_due);
+  sm.alive_bound = st.min_expires;
+  *n_due = st.n_due;
+  return YDC_OK;
+}
+
+// Behind the step of a tick that took the removal route: the parked leases erased, and the tick's
+// outcome block corrected — an orphan is neither a lease any more nor one that expired.
+int alive_orphans(ydc_context* c) {
+  auto& sm = c->stream_mode;
+  YDC_LAUNCH(c, "k_alive_orphans", k_alive_orphans, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
+             sm.lt, sm.ls, sm.d_alive_state.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  AliveState st{};
+  HIP_TRY(c, hipMemcpy(&st, sm.d_alive_state.p, sizeof st, hipMemcpyDeviceToHost));
+  sm.h_lout->n_leases -= std::min(sm.h_lout->n_leases, st.n_orphans);
+  sm.h_lout->expired -= std::min(sm.h_lout->expired, st.n_late);
+  sm.alive_orphans = st.n_orphans;
+  return YDC_OK;
+}
+
+// A removal tick that ends in an error before its ending ran: the parked leases must not outlive it
+// (they would count in |L| and show in ydc_stream_leases_get with a servant no registry has). The
+// error that is being returned keeps its text; |L| is read back from the device.
+void alive_orphans_after_error(ydc_context* c) {
+  auto& sm = c->stream_mode;
+  if (!sm.d_alive_state.p) return;
+  (void)hipStreamSynchronize(c->stream);
+  hipLaunchKernelGGL(k_alive_orphans, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream, sm.lt, sm.ls,
+                     sm.d_alive_state.p);
+  (void)hipStreamSynchronize(c->stream);
+  AliveState st{};
+  if (hipMemcpy(&st, sm.d_alive_state.p, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) sm.alive_orphans = st.n_orphans;
+  (void)hipMemcpy(&sm.n_leases, &sm.ls->n_leases, 4, hipMemcpyDeviceToHost);
+}
+
+// A row number after the removal of removed[0, n) (ascending); a removed row itself: kRemovedRow.
+uint32_t alive_renumber(const uint32_t* removed, uint32_t n, uint32_t s) {
+  const uint32_t before = (uint32_t)(std::lower_bound(removed, removed + n, s) - removed);
+  return before < n && removed[before] == s ? kRemovedRow : s - before;
+}
+
 // The open stream in a second, larger set of buffers (ydc_stream_reserve, ydc_stream_book_begin).
 int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t max_tasks, uint32_t max_waiting,
                   const LeaseCaps* lcp, uint32_t max_rows, uint32_t max_book) {
@@ -4642,6 +4847,7 @@ int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t m
     return rc;
   }
   grown.d_rep_tick = std::move(sm.d_rep_tick);  // (sized by the registry, not by the stream)
+  alive_carry(sm, grown);                       // (so is the expiry column; a pending staging goes along)
   std::swap(sm, grown);
   stream_release(grown);  // (the old buffers and the old captures; sm.stale: the step is captured again)
   return YDC_OK;
@@ -4698,6 +4904,81 @@ int ydc_stream_book_get(ydc_context* c, uint32_t* out_servant_idx, uint64_t* out
     HIP_TRY(c, hipMemcpy(out_servant_task_id, sm.bk.stid, (size_t)n * 8, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(out_digest_key, sm.bk.dkey, (size_t)n * 8, hipMemcpyDeviceToHost));
   }
+  return YDC_OK;
+}
+
+int ydc_stream_alive_begin(ydc_context* c, const int64_t* expires_at, uint32_t n) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_leases)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_begin: no leased, waiting-and-leased or rpc stream is open");
+  if (n != c->n_servants)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_begin: %u expiries for %u servants", n, c->n_servants);
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const int64_t* old = sm.d_alive.p;
+  HIP_TRY(c, sm.d_alive.reserve((size_t)n + n / 2 + 1024));
+  std::vector<int64_t> col(n, kAliveNever);
+  if (expires_at) std::copy_n(expires_at, n, col.begin());
+  if (n) HIP_TRY(c, hipMemcpy(sm.d_alive.p, col.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  sm.alive_bound = kAliveNever;
+  for (int64_t e : col) sm.alive_bound = std::min(sm.alive_bound, e);
+  sm.alive_n = n;
+  if (!sm.alive || old != sm.d_alive.p) sm.stale = true;  // (the step gains k_alive_beat: captured again)
+  sm.alive = true;
+  return YDC_OK;
+}
+
+int ydc_stream_alive_stage(ydc_context* c, const int64_t* upd_expires_at, uint32_t n_upd) {
+  if (!c || (n_upd && !upd_expires_at)) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.alive)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_stage: the stream keeps no servant expiries");
+  if (n_upd > sm.max_upd) return fail(c, YDC_ERR_CAPACITY, "%u staged expiries > max_updates %u", n_upd, sm.max_upd);
+  sm.alive_stage.assign(upd_expires_at, upd_expires_at + n_upd);
+  sm.alive_staged = true;
+  return YDC_OK;
+}
+
+int ydc_stream_alive_removed(ydc_context* c, uint32_t* out_idx, uint32_t cap, uint32_t* out_n,
+                             uint32_t* out_n_orphans) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.alive)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_removed: the stream keeps no servant expiries");
+  const uint32_t n = (uint32_t)sm.alive_removed.size();
+  *out_n = n;
+  if (out_n_orphans) *out_n_orphans = sm.alive_orphans;
+  if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u removed servants > cap %u", n, cap);
+  if (n && !out_idx) return YDC_ERR_INVALID_ARGUMENT;
+  if (n) std::memcpy(out_idx, sm.alive_removed.data(), (size_t)n * 4);
+  return YDC_OK;
+}
+
+int ydc_stream_alive_get(ydc_context* c, int64_t* out_expires_at, uint32_t cap, uint32_t* out_n) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.alive)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_get: the stream keeps no servant expiries");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = alive_fit(c)) return rc;
+  const uint32_t n = sm.alive_n;
+  *out_n = n;
+  if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u servant expiries > cap %u", n, cap);
+  if (n && !out_expires_at) return YDC_ERR_INVALID_ARGUMENT;
+  if (n) HIP_TRY(c, hipMemcpy(out_expires_at, sm.d_alive.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return YDC_OK;
+}
+
+// Tests and tools (not part of the ABI): the host's lower bound of min(E), the ticks that launched
+// k_alive_due so far and the servants the ticks removed so far.
+int ydc_debug_alive(ydc_context* c, int64_t* out_bound, uint64_t* out_alarms, uint64_t* out_removals) {
+  if (!c || !c->stream_mode.active || !c->stream_mode.alive) return YDC_ERR_INVALID_ARGUMENT;
+  if (out_bound) *out_bound = c->stream_mode.alive_bound;
+  if (out_alarms) *out_alarms = c->stream_mode.alive_alarms;
+  if (out_removals) *out_removals = c->stream_mode.alive_removals;
   return YDC_OK;
 }
 
@@ -5008,6 +5289,26 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
                     sm.max_book);
     }
   }
+  if (sm.alive) {
+    // Every heartbeat brings its expiry, and a servant at most one (k_apply_tick leaves the winner of
+    // two rows for one servant undefined; an expiry cannot be).
+    if (sm.alive_staged ? sm.alive_stage.size() != n_upd : n_upd != 0)
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "%u heartbeats, %zu expiries staged with ydc_stream_alive_stage", n_upd,
+                  sm.alive_staged ? sm.alive_stage.size() : (size_t)0);
+    const uint64_t S = (uint64_t)c->n_servants + n_upd;  // (the tick's heartbeats may add that many rows)
+    if (sm.alive_seen.size() < S) sm.alive_seen.resize(S, 0);
+    if (++sm.alive_mark == 0) {
+      std::fill(sm.alive_seen.begin(), sm.alive_seen.end(), 0u);
+      sm.alive_mark = 1;
+    }
+    for (uint32_t i = 0; i < n_upd; ++i) {
+      const uint32_t s = upd_idx[i];
+      if (s >= S) return fail(c, YDC_ERR_INVALID_ARGUMENT, "servant index %u out of order", s);
+      if (sm.alive_seen[s] == sm.alive_mark)
+        return fail(c, YDC_ERR_INVALID_ARGUMENT, "heartbeat %u names servant %u a second time", i, s);
+      sm.alive_seen[s] = sm.alive_mark;
+    }
+  }
   if (upd_env_masks && (env_words == 0 || env_words > YDC_MAX_ENV_WORDS))
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "env_words %u out of range", env_words);
   HIP_TRY(c, hipSetDevice(c->device));
@@ -5025,23 +5326,82 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
   for (uint32_t i = 0; i < n_upd && !structural; ++i)
     structural = row_is_structural(c, upd_idx[i], upd_rows[i], upd_env_masks, env_words, i);
   uint32_t graph_upd = n_upd;
+  auto apply_eager = [&]() -> int {
+    if (upd_env_masks) return ydc_update_servants_wide(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd);
+    if (EW == 1) return ydc_update_servants(c, upd_idx, upd_rows, n_upd);
+    // Rows without masks on a wide table: the (known) servants keep their environments.
+    std::vector<uint64_t> env((size_t)n_upd * EW, 0);
+    for (uint32_t i = 0; i < n_upd; ++i)
+      if (upd_idx[i] < c->n_servants)  // (new servants were refused above)
+        std::copy_n(&c->h_env[(size_t)upd_idx[i] * EW], EW, &env[(size_t)i * EW]);
+    return ydc_update_servants_wide(c, upd_idx, upd_rows, env.data(), EW, n_upd);
+  };
   if (structural) {
-    if (upd_env_masks) {
-      if (int rc = ydc_update_servants_wide(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd)) return rc;
-    } else if (EW == 1) {
-      if (int rc = ydc_update_servants(c, upd_idx, upd_rows, n_upd)) return rc;
-    } else {
-      // Rows without masks on a wide table: the (known) servants keep their environments.
-      std::vector<uint64_t> env((size_t)n_upd * EW, 0);
-      for (uint32_t i = 0; i < n_upd; ++i)
-        if (upd_idx[i] < c->n_servants)  // (new servants were refused above)
-          std::copy_n(&c->h_env[(size_t)upd_idx[i] * EW], EW, &env[(size_t)i * EW]);
-      if (int rc = ydc_update_servants_wide(c, upd_idx, upd_rows, env.data(), EW, n_upd)) return rc;
-    }
+    if (int rc = apply_eager()) return rc;
     graph_upd = 0;
   } else {
     mirror_rows(c, upd_idx, upd_rows, n_upd);
   }
+  // Aliveness (servant_alive.h): step 5 is the whole of OnExpirationTimer. No servant can be due while
+  // the host's bound of min(E) is not below the clock; when it is, k_alive_due says who is, and a tick
+  // in which somebody is takes the removal route here, in front of the step.
+  bool removal = false;
+  struct ParkedGuard {  // (every return between the parking and the tick's ending sweeps the parked leases)
+    ydc_context* c;
+    bool armed = false;
+    ~ParkedGuard() {
+      if (armed) alive_orphans_after_error(c);
+    }
+  } parked{c};
+  LeaseTick lt_alive;
+  if (sm.alive) {
+    const int64_t now = lt->now;
+    if (int rc = alive_fit(c)) return rc;  // (rows the heartbeats added: "never" until filed below)
+    const int64_t* stage = sm.alive_stage.data();
+    bool filed = false;
+    if (structural) {  // (heartbeats that took the eager path: so do their expiries)
+      if (int rc = alive_file(c, upd_idx, stage, n_upd)) return rc;
+      filed = true;
+    }
+    for (uint32_t i = 0; i < n_upd; ++i) sm.alive_bound = std::min(sm.alive_bound, stage[i]);
+    sm.alive_removed.clear();
+    sm.alive_orphans = 0;
+    uint32_t n_due = 0;
+    if (sm.alive_bound < now) {
+      if (!filed)
+        if (int rc = alive_file(c, upd_idx, stage, n_upd)) return rc;  // (again inside the step: idempotent)
+      if (int rc = alive_due(c, now, &n_due)) return rc;
+    }
+    if (n_due) {
+      if (!structural) {  // (all of the tick's heartbeats eagerly, as the structural branch does)
+        if (int rc = apply_eager()) return rc;
+        graph_upd = 0;
+      }
+      sm.alive_removed.assign(sm.h_alive_list, sm.h_alive_list + n_due);
+      const uint32_t* gone = sm.alive_removed.data();
+      parked.armed = true;
+      if (int rc = remove_rows(c, gone, n_due, true)) return rc;
+      sm.alive_removals += n_due;
+      // The staged tick in the new numbering (the reports were validated on the caller's, above).
+      sm.alive_rel.assign(release_servant_idx, release_servant_idx + n_rel);
+      for (uint32_t& s : sm.alive_rel) s = alive_renumber(gone, n_due, s);
+      release_servant_idx = sm.alive_rel.data();
+      sm.alive_rep.assign(lt->rep_srv, lt->rep_srv + lt->n_rep);
+      for (uint32_t& s : sm.alive_rep) s = alive_renumber(gone, n_due, s);
+      lt_alive = *lt;
+      lt_alive.rep_srv = sm.alive_rep.data();
+      lt = &lt_alive;
+      removal = true;
+    }
+  }
+  // The end of the tick; behind a removal the parked leases go first.
+  auto finish = [&](const BatchPlan& fp, uint32_t frounds) -> int {
+    if (removal) {
+      parked.armed = false;
+      if (int rc = alive_orphans(c)) return rc;
+    }
+    return stream_tick_finish(c, fp, frounds, n_tasks, out_servant_idx, wt, lt, rt);
+  };
   if (sm.stale || c->tables_dirty)
     if (int rc = stream_capture(c)) return rc;
   // Stage the tick (padding = no-ops).
@@ -5052,6 +5412,11 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     if (upd_rows != h.upd_rows) std::memcpy(h.upd_rows, upd_rows, (size_t)graph_upd * sizeof(ydc_servant_row));
   }
   for (uint32_t i = graph_upd; i < sm.max_upd; ++i) h.upd_idx[i] = 0xFFFFFFFFu;
+  if (sm.alive) {  // (the staged expiries, consumed)
+    if (graph_upd) std::memcpy(h.upd_exp, sm.alive_stage.data(), (size_t)graph_upd * 8);
+    sm.alive_staged = false;
+    sm.alive_stage.clear();
+  }
   if (n_rel && release_servant_idx != h.rel) std::memcpy(h.rel, release_servant_idx, (size_t)n_rel * 4);
   for (uint32_t i = n_rel; i < sm.max_rel; ++i) h.rel[i] = 0xFFFFFFFFu;
   if (n_tasks) {
@@ -5123,7 +5488,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &pe, &rounds_e))
       return rc;
     if (int rc = stream_answer_eager(c, sm.d)) return rc;
-    return stream_tick_finish(c, pe, rounds_e, n_tasks, out_servant_idx, wt, lt, rt);
+    return finish(pe, rounds_e);
   }
   const bool second = sm.swaps && c->d_running.p == sm.run_b;
   if (sm.swaps && !second && c->d_running.p != sm.run_a)
@@ -5160,7 +5525,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &p2, &rounds))
       return rc;
     if (int rc = stream_answer_eager(c, sm.d)) return rc;
-    return stream_tick_finish(c, p2, rounds, n_tasks, out_servant_idx, wt, lt, rt);
+    return finish(p2, rounds);
   }
   if (p.wave_path) {
     if (c->h_prm->n_changed[(sm.passes - 1) & 63] != 0) {
@@ -5189,7 +5554,7 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       }
     }
   }
-  return stream_tick_finish(c, p, rounds, n_tasks, out_servant_idx, wt, lt, rt);
+  return finish(p, rounds);
 }
 
 int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
