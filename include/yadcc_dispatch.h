@@ -614,6 +614,35 @@ int ydc_stream_alive_removed(ydc_context* ctx, uint32_t* out_idx, uint32_t cap, 
                              uint32_t* out_n_orphans);
 int ydc_stream_alive_get(ydc_context* ctx, int64_t* out_expires_at, uint32_t cap, uint32_t* out_n);
 
+/* ---- snapshot and restore of an open stream --------------------------------------------
+ * Everything an open waiting, leased, waiting-and-leased or rpc stream keeps on the device (L with
+ * next_id and the report stamps, W, B, E, running_tasks, the registry's columns, the clock and the
+ * tick number) leaves the context as one block of bytes and enters another one — a restarted
+ * scheduler, another GPU, a standby — so that the two give identical results for identical ticks
+ * and calls from then on. The format is DESIGN 3.3.8: self-describing, little-endian, no pointers,
+ * nothing of the lease table's geometry; two contexts in the same state give the same bytes. The
+ * blob holds ids only: the caller persists its own row -> location table and its intern tables
+ * for digests and hosts beside it.
+ *   - ydc_stream_snapshot: between ticks. cap too small: YDC_ERR_CAPACITY, *out_bytes the size
+ *     needed, nothing written (out may be NULL then). Refused with YDC_ERR_INVALID_ARGUMENT: no
+ *     stream open, a plain ydc_stream_begin stream (it keeps no state on the device), a context in
+ *     a group, pipelined batches outstanding, a ydc_stream_book_stage or ydc_stream_alive_stage
+ *     that no tick has consumed yet. The stream is not changed.
+ *   - ydc_stream_restore: ctx becomes what the snapshotted context was: registry (as by
+ *     ydc_upload_servants), running_tasks, host aliases and the open stream. Its bounds are
+ *     max(blob's, *want) field by field (want may be NULL); a want that names a part the blob's
+ *     mode lacks is YDC_ERR_INVALID_ARGUMENT. Whatever stream ctx had open is ended. The bytes are
+ *     untrusted: magic, version, size, checksum, every section's place and size, the bounds, and
+ *     the contents (ids ascending and < next_id, servant indexes < n_servants, rows(W)) are all
+ *     checked BEFORE anything of ctx is touched; a blob that fails is YDC_ERR_INVALID_ARGUMENT
+ *     (more servants than ydc_create's max_servants: YDC_ERR_CAPACITY) and ctx, an open stream
+ *     included, is exactly as it was. A failure after that (YDC_ERR_HIP; a load that does not file
+ *     every lease: YDC_ERR_NOT_CONVERGED) leaves ctx with the blob's registry and NO open stream.
+ *     Not state, so not restored: cumulative statistics, the last tick's result lists
+ *     (ydc_stream_alive_removed reports none), what the stream had learnt about its passes. */
+int ydc_stream_snapshot(ydc_context* ctx, void* out, size_t cap, size_t* out_bytes);
+int ydc_stream_restore(ydc_context* ctx, const void* blob, size_t bytes, const ydc_stream_caps* want);
+
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.
  * Rank 0 gets a 128-byte id (ncclGetUniqueId), the launcher hands it to every rank (any

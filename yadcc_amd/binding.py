@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "ydc_stream_begin_rpc", "ydc_stream_tick_rpc", "ydc_stream_caps_get", "ydc_stream_reserve",
     "ydc_stream_book_begin", "ydc_stream_book_stage", "ydc_stream_book_get",
     "ydc_stream_alive_begin", "ydc_stream_alive_stage", "ydc_stream_alive_removed", "ydc_stream_alive_get",
+    "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -191,6 +192,8 @@ def lib():
                                             C.c_uint32, C.POINTER(C.c_uint32)]
         L.ydc_stream_caps_get.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
         L.ydc_stream_reserve.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
+        L.ydc_stream_snapshot.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ydc_stream_restore.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(StreamCaps)]
         L.ydc_stream_alive_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_alive_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_alive_removed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -877,6 +880,41 @@ class Context:
         self._check(lib().ydc_stream_reserve(self._h, C.byref(want)), "ydc_stream_reserve")
         now = self.stream_caps()
         # (the result arrays of the tick calls are sized by these)
+        self._stream_caps = (now["max_updates"], now["max_releases"], now["max_tasks"])
+        self._max_waiting, self._max_leases, self._max_rows = now["max_waiting"], now["max_leases"], now["max_rows"]
+        return now
+
+    def stream_snapshot(self):
+        """Everything the open stream keeps on the device, and the registry, as one block of bytes
+        (ydc_stream_snapshot; the format: yadcc_amd/snapshot.py)."""
+        need = C.c_size_t(0)
+        rc = lib().ydc_stream_snapshot(self._h, None, C.c_size_t(0), C.byref(need))
+        if rc != -4:  # (YDC_ERR_CAPACITY with the size needed is the expected answer)
+            self._check(rc or -1, "ydc_stream_snapshot")
+        buf = C.create_string_buffer(need.value)
+        self._check(lib().ydc_stream_snapshot(self._h, buf, C.c_size_t(need.value), C.byref(need)), "ydc_stream_snapshot")
+        return buf.raw[:need.value]
+
+    def stream_restore(self, blob, **want):
+        """Makes this context what the snapshotted one was (ydc_stream_restore): registry, running_tasks,
+        host aliases and the open stream, its bounds max(blob's, want) — keywords as stream_reserve's.
+        Returns the bounds."""
+        from . import snapshot
+        if "max_requests" in want:
+            want["max_tasks"] = max(int(want.pop("max_requests")), int(want.get("max_tasks", 0)))
+        caps = StreamCaps()
+        for k, v in want.items():
+            if k not in dict(StreamCaps._fields_):
+                raise TypeError("stream_restore: unknown capacity %r" % k)
+            setattr(caps, k, int(v))
+        blob = bytes(blob)
+        self._check(lib().ydc_stream_restore(self._h, blob, C.c_size_t(len(blob)), C.byref(caps) if want else None),
+                    "ydc_stream_restore")
+        head = snapshot.HEADER.unpack_from(blob)
+        self.n_servants = int(head[7])
+        self._alive = bool(head[5] & 16)
+        self._alive_removals = 0
+        now = self.stream_caps()
         self._stream_caps = (now["max_updates"], now["max_releases"], now["max_tasks"])
         self._max_waiting, self._max_leases, self._max_rows = now["max_waiting"], now["max_leases"], now["max_rows"]
         return now

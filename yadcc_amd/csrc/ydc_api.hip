@@ -29,6 +29,8 @@
 #include "wait_lease.h"
 #include "running_book.h"
 #include "servant_alive.h"
+#include "stream_snapshot.h"
+#include "stream_snapshot_codec.h"
 #include "tick_kernel.h"
 
 using namespace ydc;
@@ -364,6 +366,12 @@ struct ydc_context {
     uint32_t alive_mark = 0;
     std::vector<uint32_t> alive_rel, alive_rep;  // the removal route's rewritten releases and report servants
   } stream_mode;
+  // ydc_stream_snapshot: the packed columns of L with their count on the device, and the page-locked
+  // block they cross the bus into. Kept for the next snapshot (a standby is fed periodically, and
+  // the two allocations cost more than everything else the call does).
+  DevBuf<uint8_t> d_snap;
+  uint8_t* h_snap = nullptr;
+  size_t h_snap_cap = 0;
   DevBuf<ClassRun> d_runs;
   DevBuf<uint8_t> d_dirty;
   bool debug_sim = false;
@@ -960,6 +968,7 @@ int ydc_destroy(ydc_context* c) {
     if (pd.ev) (void)hipEventDestroy(pd.ev);
   }
   if (c->h_in) (void)hipHostFree(c->h_in);
+  if (c->h_snap) (void)hipHostFree(c->h_snap);
   if (c->h_rel) (void)hipHostFree(c->h_rel);
   if (c->h_rel_ev) (void)hipEventDestroy(c->h_rel_ev);
   if (c->copy_ev) (void)hipEventDestroy(c->copy_ev);
@@ -5696,6 +5705,345 @@ int ydc_stream_tick_waiting(ydc_context* c, const uint32_t* upd_idx, const ydc_s
                     nullptr};
   return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
                      n_tasks, out_servant_idx, &wt);
+}
+
+}  // extern "C"
+
+// ---- snapshot and restore of an open stream (stream_snapshot.h, stream_snapshot_codec.h) ----
+namespace {
+
+// What the open stream holds, from the host's mirrors alone: mode, bounds, counts and with them the
+// blob's layout. next_id and alive_bound are the device's to say (stream_snapshot fills them in).
+void snap_describe(const ydc_context* c, snap::Header* h) {
+  const auto& sm = c->stream_mode;
+  std::memset(h, 0, sizeof *h);
+  h->magic = snap::kMagic;
+  h->version = snap::kVersion;
+  h->mode = (sm.max_waiting ? snap::kModeWaiting : 0) | (sm.max_leases ? snap::kModeLeased : 0) |
+            (sm.max_rows ? snap::kModeRpc : 0) | (sm.max_book ? snap::kModeBook : 0) | (sm.alive ? snap::kModeAlive : 0);
+  h->env_words = c->env_words;
+  h->n_servants = c->n_servants;
+  h->n_alias = (uint32_t)c->h_alias_ip.size();
+  const uint32_t caps[snap::kCaps] = {sm.max_upd,    sm.max_rel,   sm.max_tasks, sm.max_rows, sm.max_waiting,
+                                      sm.max_leases, sm.max_renew, sm.max_free,  sm.max_rep,  sm.max_rep_ids};
+  std::copy_n(caps, (size_t)snap::kCaps, h->caps);
+  h->max_book = sm.max_book;
+  h->n_leases = sm.max_leases ? sm.n_leases : 0;
+  h->n_waiting = sm.max_waiting ? sm.n_waiting : 0;
+  h->n_wait_rows = sm.max_rows ? sm.n_wait_rows : 0;
+  h->n_book = sm.max_book ? sm.n_book : 0;
+  h->lease_tick = sm.max_leases ? sm.lease_tick : 0;
+  h->last_now = sm.last_now;
+  h->alive_bound = INT64_MAX;
+  snap::layout(h);
+}
+
+// The four packed columns of L on the device, `cap` records each.
+struct PackedBufs {
+  DevBuf<unsigned long long> id;
+  DevBuf<int64_t> exp;
+  DevBuf<uint32_t> srv, st, count;
+  LeasePacked cols{};
+  hipError_t reserve(uint32_t cap) {
+    for (hipError_t e : {id.reserve(cap), exp.reserve(cap), srv.reserve(cap), st.reserve(cap), count.reserve(1)})
+      if (e != hipSuccess) return e;
+    cols = LeasePacked{id.p, exp.p, srv.p, st.p, cap};
+    return hipSuccess;
+  }
+};
+
+int stream_snapshot(ydc_context* c, uint8_t* out, const snap::Header& h0) {
+  auto& sm = c->stream_mode;
+  snap::Header h = h0;
+  snap::View v{};
+  v.h = h;
+  snap::place(&v, out);
+  auto at = [](const uint8_t* col) { return const_cast<uint8_t*>(col); };  // (the view's columns lie in `out`)
+  std::memset(out, 0, (size_t)h.total_bytes);
+  hipStream_t st = c->stream;
+  const uint32_t n = h.n_servants;
+  // The registry: the device's columns are the truth for everything a heartbeat row replaces inside a
+  // step (k_apply_tick leaves the winner of two rows for one servant undefined; mirror_rows takes the
+  // last) and for running_tasks. ip_id and the environment masks change on the structural path only,
+  // which writes the host's copy first; per servant, the device holds neither.
+  if (n) {
+    std::memcpy(at(v.env_mask), c->h_env.data(), (size_t)n * h.env_words * 8);
+    std::memcpy(at(v.ip), c->h_ip.data(), (size_t)n * 4);
+    const std::pair<const uint8_t*, const uint32_t*> cols[] = {
+        {v.version, c->d_version.p}, {v.nproc, c->d_nproc.p}, {v.load, c->d_load.p},
+        {v.max_tasks, c->d_max_tasks.p}, {v.flags, c->d_flags.p}, {v.running, c->d_running.p}};
+    for (auto& col : cols) HIP_TRY(c, hipMemcpyAsync(at(col.first), col.second, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    // (rows behind the column's end have not reported yet: 0, which no tick number is)
+    const uint32_t have = (uint32_t)std::min<size_t>(n, sm.d_rep_tick.cap);
+    if (have) HIP_TRY(c, hipMemcpyAsync(at(v.rep_tick), sm.d_rep_tick.p, (size_t)have * 4, hipMemcpyDeviceToHost, st));
+  }
+  if (h.n_alias) {
+    std::memcpy(at(v.alias_ip), c->h_alias_ip.data(), (size_t)h.n_alias * 4);
+    std::memcpy(at(v.alias_servant), c->h_alias_servant.data(), (size_t)h.n_alias * 4);
+  }
+  // W, B, E: compact between ticks, [0, n) of every column as it lies.
+  if (sm.max_waiting) {
+    uint32_t cnt = 0;
+    HIP_TRY(c, hipMemcpy(&cnt, &sm.ws->count, 4, hipMemcpyDeviceToHost));
+    if (cnt != h.n_waiting)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u on the device, %u on the host", cnt, h.n_waiting);
+    auto carry = [&](const uint8_t* dst, const void* src, size_t width) {
+      return cnt && src ? hipMemcpyAsync(at(dst), src, cnt * width, hipMemcpyDeviceToHost, st) : hipSuccess;
+    };
+    HIP_TRY(c, carry(v.w_deadline, sm.wq.deadline, 8));
+    HIP_TRY(c, carry(v.w_tag, sm.wq.tag, 8));
+    HIP_TRY(c, carry(v.w_for, sm.wl.w_for, 8));  // (with leases)
+    HIP_TRY(c, carry(v.w_env, sm.wq.env, 4));
+    HIP_TRY(c, carry(v.w_minv, sm.wq.minv, 4));
+    HIP_TRY(c, carry(v.w_ip, sm.wq.ip, 4));
+    HIP_TRY(c, carry(v.w_nimm, sm.rw.n_imm, 4));  // (rpc mode)
+    HIP_TRY(c, carry(v.w_npre, sm.rw.n_pre, 4));
+  }
+  if (h.n_book) {
+    const size_t nb = h.n_book;
+    HIP_TRY(c, hipMemcpyAsync(at(v.b_grant), sm.bk.grant, nb * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(at(v.b_stid), sm.bk.stid, nb * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(at(v.b_dkey), sm.bk.dkey, nb * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(at(v.b_srv), sm.bk.servant, nb * 4, hipMemcpyDeviceToHost, st));
+  }
+  if (sm.alive && n) HIP_TRY(c, hipMemcpyAsync(at(v.e_exp), sm.d_alive.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  // L: packed on the device, brought over through one page-locked block (the four columns behind each
+  // other), sorted by id here.
+  if (sm.max_leases) {
+    const uint32_t nl = h.n_leases;
+    const size_t cap = std::max(nl, 1u);
+    HIP_TRY(c, c->d_snap.reserve(cap * 24 + 16));
+    if (c->h_snap_cap < cap * 24) {
+      if (c->h_snap) (void)hipHostFree(c->h_snap);
+      c->h_snap = nullptr;
+      c->h_snap_cap = 0;
+      const size_t want = cap * 24 + cap * 6;  // (a quarter more: |L| moves from snapshot to snapshot)
+      HIP_TRY(c, hipHostMalloc((void**)&c->h_snap, want, hipHostMallocDefault));
+      c->h_snap_cap = want;
+    }
+    uint8_t* d = c->d_snap.p;
+    const LeasePacked pk{(unsigned long long*)d, (int64_t*)(d + cap * 8), (uint32_t*)(d + cap * 16),
+                         (uint32_t*)(d + cap * 20), (uint32_t)cap};
+    uint32_t* d_count = (uint32_t*)(d + cap * 24);
+    const uint8_t* stage = c->h_snap;
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, 4, st));
+    YDC_LAUNCH(c, "k_lease_pack", k_lease_pack, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, st, sm.lt,
+               pk, d_count);
+    HIP_TRY(c, hipGetLastError());
+    // (the copies of all |L| records are enqueued before the count is known to be |L|: the packed
+    // columns hold that many, and a count that differs fails the call below)
+    const unsigned long long* id = (const unsigned long long*)stage;
+    const int64_t* exp = (const int64_t*)(stage + (size_t)nl * 8);
+    const uint32_t* srv = (const uint32_t*)(stage + (size_t)nl * 16);
+    const uint32_t* state = (const uint32_t*)(stage + (size_t)nl * 20);
+    if (nl) {
+      HIP_TRY(c, hipMemcpyAsync((void*)id, pk.id, (size_t)nl * 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync((void*)exp, pk.expires, (size_t)nl * 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync((void*)srv, pk.servant, (size_t)nl * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync((void*)state, pk.state, (size_t)nl * 4, hipMemcpyDeviceToHost, st));
+    }
+    LeaseState ls{};
+    uint32_t packed = 0;
+    HIP_TRY(c, hipMemcpyAsync(&packed, d_count, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&ls, sm.ls, sizeof ls, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (packed != nl || ls.n_leases != nl)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: %u live slots, |L| %u on the device, %u on the host", packed,
+                  ls.n_leases, nl);
+    h.next_id = ls.next_id;
+    std::vector<std::pair<unsigned long long, uint32_t>> order(nl);  // (id, packed position)
+    for (uint32_t i = 0; i < nl; ++i) order[i] = {id[i], i};
+    std::sort(order.begin(), order.end());
+    for (uint32_t k = 0; k < nl; ++k) {
+      const uint32_t i = order[k].second;
+      // (between ticks no lease is parked: servant_alive.h)
+      if (srv[i] >= n || id[i] >= ls.next_id)
+        return fail(c, YDC_ERR_NOT_CONVERGED, "lease %llu names servant %u of %u (next_id %llu)", id[i], srv[i], n,
+                    ls.next_id);
+      std::memcpy(at(v.l_id) + (size_t)k * 8, &id[i], 8);
+      std::memcpy(at(v.l_exp) + (size_t)k * 8, &exp[i], 8);
+      std::memcpy(at(v.l_srv) + (size_t)k * 4, &srv[i], 4);
+      std::memcpy(at(v.l_state) + (size_t)k * 4, &state[i], 4);
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  // alive_bound: the column's minimum itself (the host's bound only errs low, by what it has seen).
+  for (uint32_t s = 0; sm.alive && s < n; ++s) h.alive_bound = std::min(h.alive_bound, snap::get<int64_t>(v.e_exp, s));
+  std::memcpy(out, &h, sizeof h);
+  h.checksum = snap::checksum(out, h.total_bytes);
+  std::memcpy(out, &h, sizeof h);
+  return YDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ydc_stream_snapshot(ydc_context* c, void* out, size_t cap, size_t* out_bytes) {
+  if (!c || !out_bytes) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: no stream is open");
+  if (!sm.max_waiting && !sm.max_leases)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: a stream begun with ydc_stream_begin keeps no state "
+                "on the device");
+  if (c->group.n_ranks) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: the context is in a group");
+  if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: pipelined batches are outstanding");
+  if (sm.book_staged || sm.alive_staged)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: a staging for the next tick is pending (a snapshot "
+                "is taken between ticks)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (sm.alive)
+    if (int rc = alive_fit(c)) return rc;  // (rows the registry gained outside a tick: "never")
+  snap::Header h;
+  snap_describe(c, &h);
+  *out_bytes = (size_t)h.total_bytes;
+  if (cap < h.total_bytes)
+    return fail(c, YDC_ERR_CAPACITY, "a snapshot of %llu bytes > cap %zu", (unsigned long long)h.total_bytes, cap);
+  if (!out) return YDC_ERR_INVALID_ARGUMENT;
+  return stream_snapshot(c, (uint8_t*)out, h);
+}
+
+int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc_stream_caps* want) {
+  if (!c || !blob) return YDC_ERR_INVALID_ARGUMENT;
+  if (c->group.n_ranks) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: the context is in a group");
+  if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: pipelined batches are outstanding");
+  // Everything that can be wrong with the bytes, before anything of the context is touched.
+  snap::View v{};
+  if (const char* why = snap::validate(blob, bytes, &v)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: %s", why);
+  const snap::Header& h = v.h;
+  if (h.env_words > YDC_MAX_ENV_WORDS)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: env_words %u > %u", h.env_words, YDC_MAX_ENV_WORDS);
+  const ydc_stream_caps none{};
+  const ydc_stream_caps& w = want ? *want : none;
+  if (!(h.mode & snap::kModeWaiting) && w.max_waiting)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: max_waiting for a stream without a waiting queue");
+  if (!(h.mode & snap::kModeLeased) && (w.max_leases | w.max_renewals | w.max_frees | w.max_reports | w.max_report_ids))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: lease capacities for a stream without a lease table");
+  if (!(h.mode & snap::kModeRpc) && w.max_rows)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: max_rows for a stream that is not an rpc stream");
+  const uint32_t max_upd = std::max(h.caps[snap::kUpdates], w.max_updates);
+  const uint32_t max_rel = std::max(h.caps[snap::kReleases], w.max_releases);
+  const uint32_t max_tasks = std::max(h.caps[snap::kTasks], w.max_tasks), max_rows = std::max(h.caps[snap::kRows], w.max_rows);
+  const uint32_t max_waiting = std::max(h.caps[snap::kWaiting], w.max_waiting);
+  const LeaseCaps lc{std::max(h.caps[snap::kLeases], w.max_leases), std::max(h.caps[snap::kRenewals], w.max_renewals),
+                     std::max(h.caps[snap::kFrees], w.max_frees), std::max(h.caps[snap::kReports], w.max_reports),
+                     std::max(h.caps[snap::kReportIds], w.max_report_ids)};
+  const LeaseCaps* lcp = (h.mode & snap::kModeLeased) ? &lc : nullptr;
+  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, max_tasks, max_waiting, lcp, max_rows, h.max_book)) return rc;
+  if (c->max_servants && h.n_servants > c->max_servants)
+    return fail(c, YDC_ERR_CAPACITY, "ydc_stream_restore: %u servants > max_servants %u", h.n_servants, c->max_servants);
+  if (c->max_tasks && max_tasks > c->max_tasks)
+    return fail(c, YDC_ERR_CAPACITY, "ydc_stream_restore: max_tasks %u > the context's %u", max_tasks, c->max_tasks);
+  // The blob is good. From here on a failure is the device's (YDC_ERR_HIP, or a load that lost
+  // records: YDC_ERR_NOT_CONVERGED) and leaves the blob's registry and no open stream.
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  stream_release(c);
+  const uint32_t n = h.n_servants;
+  // (aligned copies of the columns: the block's base may be any address)
+  auto col32 = [&](const uint8_t* p, size_t k) {
+    std::vector<uint32_t> a(k);
+    if (k) std::memcpy(a.data(), p, k * 4);
+    return a;
+  };
+  auto col64 = [&](const uint8_t* p, size_t k) {
+    std::vector<uint64_t> a(k);
+    if (k) std::memcpy(a.data(), p, k * 8);
+    return a;
+  };
+  {
+    const auto version = col32(v.version, n), nproc = col32(v.nproc, n), load = col32(v.load, n);
+    const auto maxt = col32(v.max_tasks, n), flags = col32(v.flags, n), ip = col32(v.ip, n), run = col32(v.running, n);
+    const auto env = col64(v.env_mask, (size_t)n * h.env_words);
+    const ydc_servant_soa sv{version.data(), nproc.data(), load.data(), maxt.data(), run.data(),
+                             flags.data(), env.data(),  ip.data(),   h.env_words};
+    if (int rc = ydc_upload_servants(c, &sv, n)) return rc;  // (registry and running_tasks; the aliases cleared)
+    if (h.n_alias) {
+      const auto aip = col32(v.alias_ip, h.n_alias), asv = col32(v.alias_servant, h.n_alias);
+      if (int rc = ydc_set_host_aliases(c, aip.data(), asv.data(), h.n_alias)) return rc;
+    }
+  }
+  // A second stream, complete before it becomes the context's.
+  ydc_context::Stream fresh;
+  auto load = [&]() -> int {
+    if (int rc = stream_alloc(c, fresh, max_upd, max_rel, max_tasks, max_waiting, lcp, max_rows, h.max_book)) return rc;
+    if (int rc = stream_reset(c, fresh)) return rc;
+    hipStream_t st = c->stream;
+    if (lcp) {
+      const uint32_t nl = h.n_leases;
+      PackedBufs pk;
+      HIP_TRY(c, pk.reserve(std::max(nl, 1u)));
+      if (nl) {
+        HIP_TRY(c, hipMemcpy(pk.id.p, col64(v.l_id, nl).data(), (size_t)nl * 8, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(pk.exp.p, col64(v.l_exp, nl).data(), (size_t)nl * 8, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(pk.srv.p, col32(v.l_srv, nl).data(), (size_t)nl * 4, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(pk.st.p, col32(v.l_state, nl).data(), (size_t)nl * 4, hipMemcpyHostToDevice));
+      }
+      YDC_LAUNCH(c, "k_lease_load", k_lease_load, dim3(ceil_div(std::max(nl, 1u), 256)), dim3(256), 0, st, fresh.lt,
+                 fresh.ls, pk.cols, nl, (unsigned long long)h.next_id);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipStreamSynchronize(st));
+      LeaseState ls{};
+      HIP_TRY(c, hipMemcpy(&ls, fresh.ls, sizeof ls, hipMemcpyDeviceToHost));
+      if (ls.n_leases != nl || ls.next_id != h.next_id)
+        return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: %u of %u leases filed (next_id %llu of %llu)", ls.n_leases,
+                    nl, ls.next_id, (unsigned long long)h.next_id);
+      // (sized by the registry, as stream_capture sizes it; rows that never reported: 0)
+      HIP_TRY(c, fresh.d_rep_tick.reserve((size_t)n + 1024));
+      HIP_TRY(c, hipMemset(fresh.d_rep_tick.p, 0, fresh.d_rep_tick.cap * 4));
+      if (n) HIP_TRY(c, hipMemcpy(fresh.d_rep_tick.p, col32(v.rep_tick, n).data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    if (h.n_waiting) {
+      const size_t cnt = h.n_waiting;
+      auto carry = [&](void* dst, const uint8_t* src, size_t width) {
+        // (pageable and unaligned source: a synchronous copy)
+        return dst ? hipMemcpy(dst, src, cnt * width, hipMemcpyHostToDevice) : hipSuccess;
+      };
+      HIP_TRY(c, carry(fresh.wq.deadline, v.w_deadline, 8));
+      HIP_TRY(c, carry(fresh.wq.tag, v.w_tag, 8));
+      HIP_TRY(c, carry(fresh.wl.w_for, v.w_for, 8));  // (with leases)
+      HIP_TRY(c, carry(fresh.wq.env, v.w_env, 4));
+      HIP_TRY(c, carry(fresh.wq.minv, v.w_minv, 4));
+      HIP_TRY(c, carry(fresh.wq.ip, v.w_ip, 4));
+      HIP_TRY(c, carry(fresh.rw.n_imm, v.w_nimm, 4));  // (rpc mode)
+      HIP_TRY(c, carry(fresh.rw.n_pre, v.w_npre, 4));
+      HIP_TRY(c, hipMemcpy(&fresh.ws->count, &h.n_waiting, 4, hipMemcpyHostToDevice));
+    }
+    if (h.n_book) {
+      const size_t nb = h.n_book;
+      HIP_TRY(c, hipMemcpy(fresh.bk.grant, v.b_grant, nb * 8, hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemcpy(fresh.bk.stid, v.b_stid, nb * 8, hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemcpy(fresh.bk.dkey, v.b_dkey, nb * 8, hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemcpy(fresh.bk.servant, v.b_srv, nb * 4, hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemcpy(&fresh.bks->n_entries, &h.n_book, 4, hipMemcpyHostToDevice));
+    }
+    if (h.mode & snap::kModeAlive) {  // (ydc_stream_alive_begin's allocation)
+      HIP_TRY(c, fresh.d_alive.reserve((size_t)n + n / 2 + 1024));
+      if (n) HIP_TRY(c, hipMemcpy(fresh.d_alive.p, v.e_exp, (size_t)n * 8, hipMemcpyHostToDevice));
+      fresh.alive = true;
+      fresh.alive_n = n;
+      fresh.alive_bound = h.alive_bound;
+    }
+    // The host's mirrors. What a stream learns (want_passes and its window) and the per-tick marks
+    // (rep_seen / rep_mark, alive_seen / alive_mark) start fresh: none of them outlives a tick in
+    // anything a tick returns.
+    fresh.n_waiting = h.n_waiting;
+    fresh.n_wait_rows = h.n_wait_rows;
+    fresh.n_leases = h.n_leases;
+    fresh.n_book = h.n_book;
+    fresh.last_now = h.last_now;
+    fresh.lease_tick = h.lease_tick;
+    return YDC_OK;
+  };
+  if (int rc = load()) {
+    stream_release(fresh);
+    return rc;
+  }
+  std::swap(c->stream_mode, fresh);  // (stale: the next tick captures its step)
+  return YDC_OK;
 }
 
 }  // extern "C"
