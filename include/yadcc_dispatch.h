@@ -614,6 +614,64 @@ int ydc_stream_alive_removed(ydc_context* ctx, uint32_t* out_idx, uint32_t cap, 
                              uint32_t* out_n_orphans);
 int ydc_stream_alive_get(ydc_context* ctx, int64_t* out_expires_at, uint32_t cap, uint32_t* out_n);
 
+/* ---- inspection: DumpInternals (task_dispatcher.cc:538-614) answered from an open stream --------
+ * Opt-in, like the book and aliveness. With inspection on, the device keeps beside every lease a
+ * detail record (started_at, env_id, requestor_ip, prefetch) and per servant discovered_at and
+ * ever_assigned, so a scheduler needs no host-side shadow of the grants to answer /inspect.
+ *   What a tick does with inspection on: every grant of the committed batch, the queue's grants
+ *     included, adds 1 to its servant's ever_assigned (:124) and stores started_at = the GRANTING tick's
+ *     now (:133: the clock at the grant, not at submission), the request's env_id and requestor_ip, and
+ *     prefetch = 1 iff, in rpc mode, the row's rank inside its RPC is >= n_immediate
+ *     (scheduler_service_impl.cc:234-264); the leased and waiting-and-leased modes store 0. A servant
+ *     the tick's heartbeats append gets discovered_at = that tick's now and ever_assigned = 0 (:208); a
+ *     servant that returns after it was erased is a new row. An erased lease (free, sweep, orphan)
+ *     loses its record with it. A tick that is refused, or whose batch takes no effect, counts and
+ *     stores nothing.
+ *   ydc_stream_inspect_begin: switches inspection on for the open leased, waiting-and-leased or rpc
+ *     stream (any other context or mode: YDC_ERR_INVALID_ARGUMENT). n must be the registry's servant
+ *     count. A NULL column: discovered_at = the previous accepted tick's now (0 before the first
+ *     tick), ever_assigned = 0. Leases L holds already get env_id = requestor_ip = YDC_INSPECT_NO_ID,
+ *     started_at = YDC_INSPECT_NO_TIME, prefetch = 0. A second call replaces the two servant columns
+ *     and leaves the task details alone. The stream's next begin call, ydc_stream_end and
+ *     ydc_stream_restore switch it off.
+ *   ydc_stream_inspect_load: files details for n leases that exist, by id (a NULL column: the
+ *     sentinel / 0). Checked before anything is touched: every id is a lease of L, no id appears
+ *     twice, n <= |L|; otherwise YDC_ERR_INVALID_ARGUMENT and nothing is applied. The snapshot blob
+ *     says nothing about inspection; a restart persists the two get calls' columns beside it and runs
+ *     ydc_stream_restore, ydc_stream_inspect_begin(columns), ydc_stream_inspect_load(columns).
+ *   ydc_stream_inspect_servants: between ticks; synchronises. Per servant the two columns,
+ *     running_tasks and capacity_available = GetCapacityAvailable (:283-313): a YDC_SERVANT_LOW_MEMORY
+ *     servant reports its running_tasks, any other min(max_tasks, max(num_processors -
+ *     max(current_load - running_tasks, 0), 0)) in signed 64-bit arithmetic. The totals as :541-612
+ *     computes them, in u64 arithmetic modulo 2^64: capacity = sum of max_tasks; capacity_unavailable
+ *     = sum of (max_tasks - capacity_available) (a low-memory servant running more than max_tasks makes
+ *     a term wrap, as the reference's does); capacity_available = max((int64)(capacity - running_tasks -
+ *     capacity_unavailable), 0).
+ *   ydc_stream_inspect_tasks: L in ascending id order, as ydc_stream_leases_get returns it, with the
+ *     details beside it.
+ *   Both get calls: more than cap rows is YDC_ERR_CAPACITY with *out_n set and nothing written; any
+ *     output pointer may be NULL; inspection off is YDC_ERR_INVALID_ARGUMENT.
+ *   ydc_remove_servants and aliveness's removal compact the two servant columns, order kept;
+ *     ydc_stream_reserve and ydc_stream_book_begin carry everything over. No tick signature changes; a
+ *     stream without inspection launches what it launched before. */
+#define YDC_INSPECT_NO_ID 0xFFFFFFFFu /* env_id / requestor_ip of a lease granted while inspection was off */
+#define YDC_INSPECT_NO_TIME INT64_MIN /* its started_at */
+typedef struct ydc_stream_totals {
+  uint64_t servants_up, running_tasks, capacity, capacity_available, capacity_unavailable;
+} ydc_stream_totals;
+int ydc_stream_inspect_begin(ydc_context* ctx, const int64_t* discovered_at, const uint64_t* ever_assigned,
+                             uint32_t n);
+int ydc_stream_inspect_load(ydc_context* ctx, const uint64_t* task_id, const int64_t* started_at,
+                            const uint32_t* env_id, const uint32_t* requestor_ip, const uint8_t* prefetch,
+                            uint32_t n);
+int ydc_stream_inspect_servants(ydc_context* ctx, int64_t* out_discovered_at, uint64_t* out_ever_assigned,
+                                uint32_t* out_running_tasks, uint32_t* out_capacity_available, uint32_t cap,
+                                uint32_t* out_n, ydc_stream_totals* out_totals);
+int ydc_stream_inspect_tasks(ydc_context* ctx, uint64_t* out_task_id, uint32_t* out_servant_idx,
+                             int64_t* out_expires_at, uint8_t* out_zombie, int64_t* out_started_at,
+                             uint32_t* out_env_id, uint32_t* out_requestor_ip, uint8_t* out_prefetch,
+                             uint32_t cap, uint32_t* out_n);
+
 /* ---- snapshot and restore of an open stream --------------------------------------------
  * Everything an open waiting, leased, waiting-and-leased or rpc stream keeps on the device (L with
  * next_id and the report stamps, W, B, E, running_tasks, the registry's columns, the clock and the

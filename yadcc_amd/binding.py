@@ -20,6 +20,8 @@ TRANSPORT_NAMES = ("none", "rccl", "local", "ipc", "ipc-host")
 IDX_TIMEOUT = 0xFFFFFFFF
 IDX_ENV_NOT_FOUND = 0xFFFFFFFE
 IDX_WAITING = 0xFFFFFFFD  # streaming waiting mode: queued on the device, answered in a later tick
+INSPECT_NO_ID = 0xFFFFFFFF  # env_id / requestor_ip of a lease granted while inspection was off
+INSPECT_NO_TIME = -(1 << 63)  # ... its started_at
 DISPATCH_COMMIT = 1
 STAGES = ("servant_scan", "slot_gen", "sort", "class_lists", "task_classify", "match", "finalize",
           "total")
@@ -41,6 +43,7 @@ ABI_SYMBOLS = (
     "ydc_stream_begin_rpc", "ydc_stream_tick_rpc", "ydc_stream_caps_get", "ydc_stream_reserve",
     "ydc_stream_book_begin", "ydc_stream_book_stage", "ydc_stream_book_get",
     "ydc_stream_alive_begin", "ydc_stream_alive_stage", "ydc_stream_alive_removed", "ydc_stream_alive_get",
+    "ydc_stream_inspect_begin", "ydc_stream_inspect_load", "ydc_stream_inspect_servants", "ydc_stream_inspect_tasks",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
@@ -59,6 +62,12 @@ class ServantSoA(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("version", "num_processors", "current_load",
                                            "max_tasks", "running_tasks", "flags", "env_mask",
                                            "ip_id")] + [("env_words", C.c_uint32)]
+
+
+class StreamTotals(C.Structure):
+    """ydc_stream_totals."""
+    _fields_ = [(k, C.c_uint64) for k in ("servants_up", "running_tasks", "capacity", "capacity_available",
+                                          "capacity_unavailable")]
 
 
 # numpy view of ydc_servant_row (32 bytes)
@@ -199,6 +208,10 @@ def lib():
         L.ydc_stream_alive_removed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.ydc_stream_alive_get.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.ydc_debug_alive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ydc_stream_inspect_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ydc_stream_inspect_load.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_uint32]
+        L.ydc_stream_inspect_servants.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_void_p]
+        L.ydc_stream_inspect_tasks.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
         L.ydc_stream_book_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1007,6 +1020,58 @@ class Context:
         b, a, r = C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
         self._check(lib().ydc_debug_alive(self._h, C.byref(b), C.byref(a), C.byref(r)), "ydc_debug_alive")
         return int(b.value), int(a.value), int(r.value)
+
+    def stream_inspect_begin(self, discovered_at=None, ever_assigned=None):
+        """Switches inspection of the open leased, waiting-and-leased or rpc stream on
+        (ydc_stream_inspect_begin): per servant discovered_at (int64, the ticks' clock; None: the
+        previous tick's now) and ever_assigned (uint64; None: 0)."""
+        d = None if discovered_at is None else np.ascontiguousarray(discovered_at, dtype=np.int64)
+        e = None if ever_assigned is None else np.ascontiguousarray(ever_assigned, dtype=np.uint64)
+        n = len(d) if d is not None else len(e) if e is not None else self.n_servants
+        assert all(a is None or len(a) == n for a in (d, e))
+        self._check(lib().ydc_stream_inspect_begin(self._h, _ptr(d), _ptr(e), int(n)), "ydc_stream_inspect_begin")
+
+    def stream_inspect_load(self, task_id, started_at=None, env_id=None, requestor_ip=None, prefetch=None, **_):
+        """Files the details of leases that exist, by id (ydc_stream_inspect_load); takes the dict
+        stream_inspect_tasks returns as keywords. A column left out: the sentinel / 0."""
+        ids = np.ascontiguousarray(task_id, dtype=np.uint64)
+        cols = [None if a is None else np.ascontiguousarray(a, dtype=t) for a, t in
+                ((started_at, np.int64), (env_id, np.uint32), (requestor_ip, np.uint32), (prefetch, np.uint8))]
+        assert all(a is None or len(a) == len(ids) for a in cols)
+        self._check(lib().ydc_stream_inspect_load(self._h, _ptr(ids), *[_ptr(a) for a in cols], len(ids)),
+                    "ydc_stream_inspect_load")
+
+    def stream_inspect_servants(self):
+        """Per servant discovered_at, ever_assigned, running_tasks, capacity_available, and the
+        cluster's "totals" (dict of the five numbers DumpInternals prints) (ydc_stream_inspect_servants)."""
+        n = C.c_uint32(0)
+        rc = lib().ydc_stream_inspect_servants(self._h, None, None, None, None, 0, C.byref(n), None)
+        if rc != -4:  # (YDC_ERR_CAPACITY with the count is the expected answer; no servants: 0)
+            self._check(rc, "ydc_stream_inspect_servants")
+        k = int(n.value)
+        disc, ever = np.empty(k, np.int64), np.empty(k, np.uint64)
+        run, avail = np.empty(k, np.uint32), np.empty(k, np.uint32)
+        tot = StreamTotals()
+        self._check(lib().ydc_stream_inspect_servants(self._h, _ptr(disc), _ptr(ever), _ptr(run), _ptr(avail), k,
+                                                      C.byref(n), C.byref(tot)), "ydc_stream_inspect_servants")
+        return {"discovered_at": disc, "ever_assigned": ever, "running_tasks": run, "capacity_available": avail,
+                "totals": {f: int(getattr(tot, f)) for f, _ in StreamTotals._fields_}}
+
+    def stream_inspect_tasks(self):
+        """The lease table in id order with every lease's details (ydc_stream_inspect_tasks): dict of
+        task_id, servant_idx, expires_at, zombie, started_at, env_id, requestor_ip, prefetch."""
+        n = C.c_uint32(0)
+        rc = lib().ydc_stream_inspect_tasks(self._h, *([None] * 8), 0, C.byref(n))
+        if rc != -4:
+            self._check(rc, "ydc_stream_inspect_tasks")
+        k = int(n.value)
+        cols = {"task_id": np.empty(k, np.uint64), "servant_idx": np.empty(k, np.uint32),
+                "expires_at": np.empty(k, np.int64), "zombie": np.empty(k, np.uint8),
+                "started_at": np.empty(k, np.int64), "env_id": np.empty(k, np.uint32),
+                "requestor_ip": np.empty(k, np.uint32), "prefetch": np.empty(k, np.uint8)}
+        self._check(lib().ydc_stream_inspect_tasks(self._h, *[_ptr(a) for a in cols.values()], k, C.byref(n)),
+                    "ydc_stream_inspect_tasks")
+        return cols
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

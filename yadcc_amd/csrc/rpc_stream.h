@@ -26,8 +26,9 @@
 //                  the new W, the resolved list, the new requests' status and count. The last
 //                  workgroup stores |W|, rows(W), |L|, next_id and the outcome blocks.
 //
-// Whether a row is a prefetch (rank within its RPC >= n_immediate) is not stored: the reference
-// uses is_prefetch for log text only (task_dispatcher.cc:464,531).
+// Whether a row is a prefetch (rank within its RPC >= n_immediate) is stored only with inspection on
+// (stream_inspect.h): the reference logs is_prefetch (task_dispatcher.cc:464,531) and DumpInternals
+// prints it as prefetched_task (:598).
 //
 // Look-back (stream_tile.h): one word per tile, three arrays (scan, settle, grant). k_lease_renew,
 // the step's first launch, clears them; k_rpc_expand, which runs when the scan is complete and
@@ -38,6 +39,7 @@
 
 #include "kernels.h"
 #include "lease_table.h"
+#include "stream_inspect.h"
 #include "stream_tile.h"
 #include "wait_queue.h"
 
@@ -240,7 +242,7 @@ __global__ __launch_bounds__(256) void k_rpc_expand(RpcEntryCols p, uint32_t P, 
 
 // ceil(NR / kRpcTile) workgroups of 256 threads over the rows of the placed batch; thread i of a
 // workgroup owns four consecutive rows. prm == NULL: ungated (the host has just placed the batch
-// itself).
+// itself). k_rpc_grant_inspect below is this kernel's twin: a change here belongs there as well.
 __global__ __launch_bounds__(256) void k_rpc_grant(RpcBatch b, uint32_t NR, uint32_t MW, const LeaseHdr* hdr,
                                                    LeaseCols L, LeaseState* st, RpcState* rs,
                                                    unsigned long long* lookback, RpcOut o,
@@ -282,6 +284,71 @@ __global__ __launch_bounds__(256) void k_rpc_grant(RpcBatch b, uint32_t NR, uint
     if (r[i] >= kIdxWaiting) continue;
     ids[i] = next + rk;
     lease_insert(L, st, ids[i], now + b.lease_for[j], r[i]);  // the lease runs from the grant
+    if (j < w_rows) {  // a waiting RPC's grant: packed by rank (rk <= j < NR)
+      o.res_srv[rk] = r[i];
+      o.res_id[rk] = ids[i];
+    }
+    ++rk;
+  }
+  // The new requests' rows to page-locked memory (vector stores where rows(W) is a multiple of 4).
+  store_answers(o.new_srv, o.new_id, j0, w_rows, NR, r, ids);
+}
+
+// k_rpc_grant with inspection on (stream_inspect.h): the inserting thread also files the grant's
+// detail record (started_at = the granting tick's now; the row is a prefetch iff its rank inside its
+// RPC is >= n_immediate) and counts it for its servant. A kernel of its own, not a shared pass with a
+// compile-time flag as in wait_lease.h: moving k_rpc_grant's body into a function both kernels call
+// changed k_rpc_grant's register allocation (its assembly was compared), and a stream without
+// inspection launches the code it launched before.
+__global__ __launch_bounds__(256) void k_rpc_grant_inspect(RpcBatch b, uint32_t NR, uint32_t MW, const LeaseHdr* hdr,
+                                                           LeaseCols L, LeaseState* st, RpcState* rs,
+                                                           unsigned long long* lookback, RpcOut o,
+                                                           const DeviceParams* prm, uint32_t check_slot,
+                                                           InspectIn ins) {
+  if (prm && !batch_is_final(prm, check_slot)) return;  // (every workgroup alike: L stays as it is)
+  __shared__ uint32_t s_bid, s_pre;
+  __shared__ uint32_t lds[17];
+  if (threadIdx.x == 0) s_bid = atomicAdd(&rs->t_grant, 1u);
+  __syncthreads();
+  const uint32_t bid = s_bid;
+  const unsigned long long next = st->next_id;  // (k_rpc_settle's last workgroup changes it, a launch later)
+  const int64_t now = hdr->now;
+  const uint32_t w_rows = b.row_start[MW];  // W's region leads the batch
+  const uint32_t j0 = bid * kRpcTile + threadIdx.x * 4;
+  uint32_t r[4];
+  uint32_t n_gr = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    r[i] = j0 + i < NR ? b.placed[j0 + i] : kIdxEnvNotFound;
+    n_gr += r[i] < kIdxWaiting;
+  }
+  uint32_t tot;
+  const uint32_t ex = block_exclusive_scan(n_gr, lds, &tot);
+  if (threadIdx.x < 64) {
+    const uint32_t pre = lb_lo(tile_lookback<1>(lookback, bid, threadIdx.x, {{lb_pack(tot)}}).w[0]);
+    if (threadIdx.x == 0) {
+      s_pre = pre;
+      if (bid == gridDim.x - 1) b.rank[NR] = pre + tot;  // the last workgroup: the tick's grants
+    }
+  }
+  __syncthreads();
+  uint32_t rk = s_pre + ex;
+  unsigned long long ids[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t j = j0 + i;
+    ids[i] = kLeaseEmpty;
+    if (j < NR) b.rank[j] = rk;
+    if (r[i] >= kIdxWaiting) continue;
+    ids[i] = next + rk;
+    // The position row j belongs to (k_rpc_expand's search), and with it the row's rank in its RPC.
+    uint32_t lo = 0, hi = ins.P;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (b.row_start[mid] <= j) lo = mid; else hi = mid;
+    }
+    lease_insert_inspected(L, st, ins, ids[i], now + b.lease_for[j], r[i], now, j,
+                           j - b.row_start[lo] >= ins.n_imm[lo]);  // the lease runs from the grant
     if (j < w_rows) {  // a waiting RPC's grant: packed by rank (rk <= j < NR)
       o.res_srv[rk] = r[i];
       o.res_id[rk] = ids[i];

@@ -31,6 +31,7 @@
 
 #include "kernels.h"
 #include "lease_table.h"
+#include "stream_inspect.h"
 #include "stream_tile.h"
 #include "wait_queue.h"
 
@@ -47,14 +48,16 @@ struct WaitLeaseCols {
 // positions. What a mode does not have is NULL / 0: !kWait: t, lf, MW, w, ws, res_*, wout;
 // !kLease: lf, hdr, lease_exp, L, st, out_task_id, lout. now_p: the clock without leases (with
 // them: hdr->now). lease_exp: the requests' absolute expiries without a queue (with one: lf).
-template <bool kWait, bool kLease>
+// kInspect (stream_inspect.h; needs kLease): the inserting thread also files the grant's detail
+// record and counts it for its servant; ins: empty without.
+template <bool kWait, bool kLease, bool kInspect = false>
 __device__ __forceinline__ void commit_pass(WaitCols t, WaitLeaseCols lf, const uint32_t* placed, const int64_t* now_p,
                                             const int64_t* lease_exp, const LeaseHdr* hdr, uint32_t MW, uint32_t N,
                                             WaitCols w, WaitState* ws, LeaseCols L, LeaseState* st,
                                             unsigned long long* lookback, uint32_t* out_new,
                                             unsigned long long* out_task_id, uint64_t* res_tag, uint32_t* res_idx,
                                             WaitOutcome* wout, LeaseOutcome* lout, const DeviceParams* prm,
-                                            uint32_t check_slot) {
+                                            uint32_t check_slot, const InspectIn& ins = InspectIn{}) {
   if (prm && !batch_is_final(prm, check_slot)) return;  // (every workgroup alike)
   __shared__ uint32_t s_bid, s_pre_surv, s_pre_res, s_pre_gr;
   __shared__ unsigned long long s_next;
@@ -162,7 +165,12 @@ __device__ __forceinline__ void commit_pass(WaitCols t, WaitLeaseCols lf, const 
         int64_t expires;
         if constexpr (kWait) expires = now + lf.t_for[j];  // the lease runs from the grant
         else expires = lease_exp[j];
-        lease_insert(L, st, ids[i], expires, r[i]);
+        if constexpr (kInspect) {
+          // (started_at: the clock at the grant, task_dispatcher.cc:133; no prefetch in these modes)
+          lease_insert_inspected(L, st, ins, ids[i], expires, r[i], hdr->now, j, false);
+        } else {
+          lease_insert(L, st, ids[i], expires, r[i]);
+        }
       }
     }
     if constexpr (kWait) {
@@ -223,6 +231,29 @@ __global__ __launch_bounds__(256) void k_wait_lease_commit(
     const DeviceParams* prm, uint32_t check_slot) {
   commit_pass<true, true>(t, lf, placed, /*now_p=*/nullptr, /*lease_exp=*/nullptr, hdr, MW, N, w, ws, L, st, lookback, out_new, out_task_id,
                           res_tag, res_idx, wout, lout, prm, check_slot);
+}
+
+// The two leased forms with inspection on (stream_inspect.h): the same pass, the detail record and
+// the servant's count at the insert.
+__global__ __launch_bounds__(256) void k_lease_grant_inspect(const uint32_t* placed, uint32_t N,
+                                                             const int64_t* lease_exp, const LeaseHdr* hdr, LeaseCols L,
+                                                             LeaseState* st, unsigned long long* lookback,
+                                                             uint32_t* out_idx, unsigned long long* out_task_id,
+                                                             LeaseOutcome* outcome, const DeviceParams* prm,
+                                                             uint32_t check_slot, InspectIn ins) {
+  commit_pass<false, true, true>(/*t=*/WaitCols{}, /*lf=*/WaitLeaseCols{}, placed, /*now_p=*/nullptr, lease_exp, hdr,
+                                 /*MW=*/0, N, /*w=*/WaitCols{}, /*ws=*/nullptr, L, st, lookback, out_idx, out_task_id,
+                                 /*res_tag=*/nullptr, /*res_idx=*/nullptr, /*wout=*/nullptr, outcome, prm, check_slot,
+                                 ins);
+}
+
+__global__ __launch_bounds__(256) void k_wait_lease_commit_inspect(
+    WaitCols t, WaitLeaseCols lf, const uint32_t* placed, const LeaseHdr* hdr, uint32_t MW, uint32_t N, WaitCols w,
+    WaitState* ws, LeaseCols L, LeaseState* st, unsigned long long* lookback, uint32_t* out_new,
+    unsigned long long* out_task_id, uint64_t* res_tag, uint32_t* res_idx, WaitOutcome* wout, LeaseOutcome* lout,
+    const DeviceParams* prm, uint32_t check_slot, InspectIn ins) {
+  commit_pass<true, true, true>(t, lf, placed, /*now_p=*/nullptr, /*lease_exp=*/nullptr, hdr, MW, N, w, ws, L, st,
+                                lookback, out_new, out_task_id, res_tag, res_idx, wout, lout, prm, check_slot, ins);
 }
 
 }  // namespace ydc

@@ -29,6 +29,7 @@
 #include "wait_lease.h"
 #include "running_book.h"
 #include "servant_alive.h"
+#include "stream_inspect.h"
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
 #include "tick_kernel.h"
@@ -365,6 +366,20 @@ struct ydc_context {
     std::vector<uint32_t> alive_seen;  // per servant: alive_mark of the last heartbeat list that named it
     uint32_t alive_mark = 0;
     std::vector<uint32_t> alive_rel, alive_rep;  // the removal route's rewritten releases and report servants
+    // Inspection (ydc_stream_inspect_begin; stream_inspect.h): the detail records beside L's slots (a
+    // 16-byte record and a prefetch byte per slot) and the servants' discovered_at / ever_assigned
+    // columns, sized by the registry like E, each with a spare the removal route compacts into.
+    // inspect == false: no inspection (none of this exists, and the step launches what it launches
+    // without it).
+    bool inspect = false;
+    uint32_t inspect_n = 0;  // rows of the two servant columns that are filed
+    DevBuf<uint4> d_insp_rec;
+    DevBuf<uint8_t> d_insp_pre;
+    DevBuf<int64_t> d_insp_disc, d_insp_disc_spare;
+    DevBuf<unsigned long long> d_insp_ever, d_insp_ever_spare;
+    DevBuf<uint32_t> d_insp_avail;   // k_inspect_servants' per-servant result
+    DevBuf<InspectSums> d_insp_sums;
+    DevBuf<uint8_t> d_insp_pack;     // k_inspect_pack's columns and their count
   } stream_mode;
   // ydc_stream_snapshot: the packed columns of L with their count on the device, and the page-locked
   // block they cross the bus into. Kept for the next snapshot (a standby is fed periodically, and
@@ -529,6 +544,7 @@ namespace {
 
 void stream_release(ydc_context* c);  // streaming mode, defined further down
 int alive_fit(ydc_context* c);         // ... its servants' expiry column, defined further down
+int inspect_fit(ydc_context* c, int64_t when);  // ... its inspection's servant columns, defined further down
 void resident_stop(ydc_context* c);   // small-batch path's resident kernel, defined further down
 void group_release(ydc_context* c);   // multi-GPU group, defined further down
 
@@ -1162,6 +1178,7 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
   auto& sm = c->stream_mode;
   const bool leased = sm.active && sm.max_leases;
   const bool alive = leased && sm.alive;
+  const bool inspect = leased && sm.inspect;
   // Everything that can fail for want of memory comes before the first launch: a removal is applied
   // to registry, leases, book and expiry column together or not at all.
   HIP_TRY(c, c->d_upd_idx.reserve(n));
@@ -1169,6 +1186,12 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
   if (alive) {
     if (int rc = alive_fit(c)) return rc;  // (rows the registry gained outside a tick: "never")
     HIP_TRY(c, sm.d_alive_spare.reserve(sm.d_alive.cap));
+  }
+  if (inspect) {
+    // (rows the registry gained outside a tick: discovered at the last tick's clock)
+    if (int rc = inspect_fit(c, sm.last_now == INT64_MIN ? 0 : sm.last_now)) return rc;
+    HIP_TRY(c, sm.d_insp_disc_spare.reserve(sm.d_insp_disc.cap));
+    HIP_TRY(c, sm.d_insp_ever_spare.reserve(sm.d_insp_ever.cap));
   }
   // Device: order-preserving compaction of the six resident columns into spare buffers,
   // which then take their place (running_tasks of the survivors never leaves the device).
@@ -1190,6 +1213,10 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
   if (alive)
     hipLaunchKernelGGL(k_alive_compact, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, sm.d_alive.p,
                        sm.d_alive_spare.p, c->d_upd_idx.p, n, S);
+  // ... and with inspection discovered_at and ever_assigned do.
+  if (inspect)
+    hipLaunchKernelGGL(k_inspect_compact, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, sm.d_insp_disc.p,
+                       sm.d_insp_ever.p, sm.d_insp_disc_spare.p, sm.d_insp_ever_spare.p, c->d_upd_idx.p, n, S);
   // ... and with a running-task book the entries of the removed rows (DropServant).
   const bool booked = leased && sm.max_book;
   if (booked) {
@@ -1208,6 +1235,12 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
   if (alive) {
     std::swap(sm.d_alive, sm.d_alive_spare);
     sm.alive_n = kept;
+  }
+  if (inspect) {
+    std::swap(sm.d_insp_disc, sm.d_insp_disc_spare);
+    std::swap(sm.d_insp_ever, sm.d_insp_ever_spare);
+    sm.inspect_n = kept;
+    sm.stale = true;  // (a captured step holds the count column's address)
   }
   // Host mirror.
   uint32_t w = 0, next = 0;
@@ -4102,10 +4135,24 @@ void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
              sm.lt, sm.ls, a.lh, S, sm.d_rep_tick.p, c->d_running.p);
 }
 
+// With inspection on: what the granting pass files beside a lease (stream_inspect.h). env / ip: the
+// placed batch's columns as the pass indexes them.
+InspectIn inspect_in(ydc_context* c, const uint32_t* env, const uint32_t* ip) {
+  auto& sm = c->stream_mode;
+  return InspectIn{sm.d_insp_rec.p, sm.d_insp_pre.p, sm.d_insp_ever.p, std::min(sm.inspect_n, c->n_servants),
+                   env,             ip,              sm.rp.n_imm,      sm.max_rows ? sm.max_waiting + sm.max_tasks : 0};
+}
+
 // ... and behind the batch: ids for the grants, their leases, the answers, the outcome block. prm:
 // gated on the batch having become final (the captured step); NULL: the host has just placed it.
 void enqueue_lease_grant(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
   auto& sm = c->stream_mode;
+  if (sm.inspect) {
+    YDC_LAUNCH(c, "k_lease_grant_inspect", k_lease_grant_inspect, dim3(ceil_div(sm.max_tasks, kLeaseTile)), dim3(256),
+               0, c->stream, sm.lt_out, sm.max_tasks, a.lexp, a.lh, sm.lt, sm.ls, sm.lookback, sm.z_out, sm.z_task_id,
+               sm.z_lout, prm, check_slot, inspect_in(c, a.env, a.ip));
+    return;
+  }
   YDC_LAUNCH(c, "k_lease_grant", k_lease_grant, dim3(ceil_div(sm.max_tasks, kLeaseTile)), dim3(256), 0, c->stream,
              sm.lt_out, sm.max_tasks, a.lexp, a.lh, sm.lt, sm.ls, sm.lookback, sm.z_out, sm.z_task_id, sm.z_lout,
              prm, check_slot);
@@ -4116,6 +4163,13 @@ void enqueue_lease_grant(ydc_context* c, const TickArena& a, const DeviceParams*
 void enqueue_wait_lease_commit(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
   auto& sm = c->stream_mode;
   const uint32_t N = stream_batch_n(sm);
+  if (sm.inspect) {
+    YDC_LAUNCH(c, "k_wait_lease_commit_inspect", k_wait_lease_commit_inspect, dim3(ceil_div(N, kWaitTile)), dim3(256),
+               0, c->stream, sm.wt, sm.wl, sm.wt_out, a.lh, sm.max_waiting, N, sm.wq, sm.ws, sm.lt, sm.ls, sm.lookback,
+               sm.z_out, sm.z_task_id, sm.z_res_tag, sm.z_res_idx, sm.z_wout, sm.z_lout, prm, check_slot,
+               inspect_in(c, sm.wt.env, sm.wt.ip));
+    return;
+  }
   YDC_LAUNCH(c, "k_wait_lease_commit", k_wait_lease_commit, dim3(ceil_div(N, kWaitTile)), dim3(256), 0, c->stream,
              sm.wt, sm.wl, sm.wt_out, a.lh, sm.max_waiting, N, sm.wq, sm.ws, sm.lt, sm.ls, sm.lookback, sm.z_out,
              sm.z_task_id, sm.z_res_tag, sm.z_res_idx, sm.z_wout, sm.z_lout, prm, check_slot);
@@ -4125,8 +4179,13 @@ void enqueue_wait_lease_commit(ydc_context* c, const TickArena& a, const DeviceP
 void enqueue_rpc_answer(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
   auto& sm = c->stream_mode;
   const uint32_t P = sm.max_waiting + sm.max_tasks, NR = sm.max_rows;
-  YDC_LAUNCH(c, "k_rpc_grant", k_rpc_grant, dim3(ceil_div(NR, kRpcTile)), dim3(256), 0, c->stream, sm.rb, NR,
-             sm.max_waiting, a.lh, sm.lt, sm.ls, sm.rs, sm.lb_grant, sm.rz, prm, check_slot);
+  if (sm.inspect)
+    YDC_LAUNCH(c, "k_rpc_grant_inspect", k_rpc_grant_inspect, dim3(ceil_div(NR, kRpcTile)), dim3(256), 0, c->stream,
+               sm.rb, NR, sm.max_waiting, a.lh, sm.lt, sm.ls, sm.rs, sm.lb_grant, sm.rz, prm, check_slot,
+               inspect_in(c, sm.rb.env, sm.rb.ip));
+  else
+    YDC_LAUNCH(c, "k_rpc_grant", k_rpc_grant, dim3(ceil_div(NR, kRpcTile)), dim3(256), 0, c->stream, sm.rb, NR,
+               sm.max_waiting, a.lh, sm.lt, sm.ls, sm.rs, sm.lb_grant, sm.rz, prm, check_slot);
   YDC_LAUNCH(c, "k_rpc_settle", k_rpc_settle, dim3(ceil_div(P, kRpcTile)), dim3(256), 0, c->stream, sm.rp, sm.rb,
              sm.max_waiting, P, NR, a.lh, sm.rw, sm.ws, sm.rs, sm.ls, sm.lb_settle, sm.rz, sm.z_lout, prm,
              check_slot);
@@ -4568,7 +4627,15 @@ int stream_reset(ydc_context* c, ydc_context::Stream& sm) {
 int stream_migrate(ydc_context* c, const ydc_context::Stream& o, ydc_context::Stream& n) {
   hipStream_t st = c->stream;
   LeaseState ls_old{}, ls_new{};
-  if (o.max_leases) {
+  if (o.max_leases && o.inspect) {
+    // With inspection: the detail records move with their leases into columns of the new table's size.
+    const size_t slots = (size_t)n.lt.mask + 1;
+    HIP_TRY(c, n.d_insp_rec.reserve(slots));
+    HIP_TRY(c, n.d_insp_pre.reserve(slots));
+    YDC_LAUNCH(c, "k_inspect_rehash", k_inspect_rehash, dim3(ceil_div(o.lt.mask + 1, 256)), dim3(256), 0, st, o.lt, o.ls,
+               o.d_insp_rec.p, o.d_insp_pre.p, n.lt, n.ls, n.d_insp_rec.p, n.d_insp_pre.p);
+    HIP_TRY(c, hipGetLastError());
+  } else if (o.max_leases) {
     YDC_LAUNCH(c, "k_lease_rehash", k_lease_rehash, dim3(ceil_div(o.lt.mask + 1, kLeaseTile)), dim3(256), 0, st,
                o.lt, o.ls, n.lt, n.ls);
     HIP_TRY(c, hipGetLastError());
@@ -4730,6 +4797,48 @@ void alive_carry(ydc_context::Stream& o, ydc_context::Stream& n) {
   n.alive_orphans = o.alive_orphans;
 }
 
+// Inspection's servant columns and scratch, from the stream `o` to the one that takes its place (the
+// detail records have moved already: stream_migrate).
+void inspect_carry(ydc_context::Stream& o, ydc_context::Stream& n) {
+  n.inspect = o.inspect;
+  n.inspect_n = o.inspect_n;
+  n.d_insp_disc = std::move(o.d_insp_disc);
+  n.d_insp_disc_spare = std::move(o.d_insp_disc_spare);
+  n.d_insp_ever = std::move(o.d_insp_ever);
+  n.d_insp_ever_spare = std::move(o.d_insp_ever_spare);
+  n.d_insp_avail = std::move(o.d_insp_avail);
+  n.d_insp_sums = std::move(o.d_insp_sums);
+  n.d_insp_pack = std::move(o.d_insp_pack);
+}
+
+// discovered_at and ever_assigned have a row for every servant of the registry; rows they gain were
+// discovered at `when` and have been assigned nothing (task_dispatcher.cc:208).
+int inspect_fit(ydc_context* c, int64_t when) {
+  auto& sm = c->stream_mode;
+  const uint32_t S = c->n_servants;
+  if (S < sm.inspect_n) sm.inspect_n = S;
+  if (S == sm.inspect_n) return YDC_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (S > sm.d_insp_disc.cap || S > sm.d_insp_ever.cap) {
+    DevBuf<int64_t> disc;
+    DevBuf<unsigned long long> ever;
+    HIP_TRY(c, disc.reserve((size_t)S + S / 2 + 1024));
+    HIP_TRY(c, ever.reserve((size_t)S + S / 2 + 1024));
+    if (sm.inspect_n) {
+      HIP_TRY(c, hipMemcpy(disc.p, sm.d_insp_disc.p, (size_t)sm.inspect_n * 8, hipMemcpyDeviceToDevice));
+      HIP_TRY(c, hipMemcpy(ever.p, sm.d_insp_ever.p, (size_t)sm.inspect_n * 8, hipMemcpyDeviceToDevice));
+    }
+    sm.d_insp_disc = std::move(disc);
+    sm.d_insp_ever = std::move(ever);
+  }
+  const std::vector<int64_t> at(S - sm.inspect_n, when);
+  HIP_TRY(c, hipMemcpy(sm.d_insp_disc.p + sm.inspect_n, at.data(), at.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemset(sm.d_insp_ever.p + sm.inspect_n, 0, at.size() * 8));
+  sm.inspect_n = S;
+  sm.stale = true;  // (a captured step holds the count column's address and its row count)
+  return YDC_OK;
+}
+
 // E has a row for every servant of the registry; rows it gains start at "never".
 int alive_fit(ydc_context* c) {
   auto& sm = c->stream_mode;
@@ -4857,6 +4966,7 @@ int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t m
   }
   grown.d_rep_tick = std::move(sm.d_rep_tick);  // (sized by the registry, not by the stream)
   alive_carry(sm, grown);                       // (so is the expiry column; a pending staging goes along)
+  inspect_carry(sm, grown);                     // (so are inspection's servant columns)
   std::swap(sm, grown);
   stream_release(grown);  // (the old buffers and the old captures; sm.stale: the step is captured again)
   return YDC_OK;
@@ -4988,6 +5098,192 @@ int ydc_debug_alive(ydc_context* c, int64_t* out_bound, uint64_t* out_alarms, ui
   if (out_bound) *out_bound = c->stream_mode.alive_bound;
   if (out_alarms) *out_alarms = c->stream_mode.alive_alarms;
   if (out_removals) *out_removals = c->stream_mode.alive_removals;
+  return YDC_OK;
+}
+
+// ---- inspection (stream_inspect.h) ----
+
+int ydc_stream_inspect_begin(ydc_context* c, const int64_t* discovered_at, const uint64_t* ever_assigned, uint32_t n) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_leases)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_begin: no leased, waiting-and-leased or rpc stream is open");
+  if (n != c->n_servants)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_begin: %u rows for %u servants", n, c->n_servants);
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, sm.d_insp_disc.reserve((size_t)n + n / 2 + 1024));
+  HIP_TRY(c, sm.d_insp_ever.reserve((size_t)n + n / 2 + 1024));
+  const size_t slots = (size_t)sm.lt.mask + 1;
+  if (!sm.inspect) {
+    HIP_TRY(c, sm.d_insp_rec.reserve(slots));
+    HIP_TRY(c, sm.d_insp_pre.reserve(slots));
+  }
+  std::vector<int64_t> disc(n, sm.last_now == INT64_MIN ? 0 : sm.last_now);
+  std::vector<unsigned long long> ever(n, 0);
+  if (discovered_at) std::copy_n(discovered_at, n, disc.begin());
+  if (ever_assigned) std::copy_n(ever_assigned, n, ever.begin());
+  if (n) {
+    HIP_TRY(c, hipMemcpy(sm.d_insp_disc.p, disc.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(sm.d_insp_ever.p, ever.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  }
+  if (!sm.inspect) {  // (the leases L holds were granted without details)
+    YDC_LAUNCH(c, "k_inspect_fill", k_inspect_fill, dim3(ceil_div((uint32_t)slots, 256)), dim3(256), 0, c->stream,
+               sm.d_insp_rec.p, sm.d_insp_pre.p, (uint32_t)slots);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  sm.inspect_n = n;
+  sm.inspect = true;
+  sm.stale = true;  // (the step's granting pass changes, and it holds the columns' addresses: captured again)
+  return YDC_OK;
+}
+
+int ydc_stream_inspect_load(ydc_context* c, const uint64_t* task_id, const int64_t* started_at, const uint32_t* env_id,
+                            const uint32_t* requestor_ip, const uint8_t* prefetch, uint32_t n) {
+  if (!c || (n && !task_id)) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.inspect)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_load: the stream has no inspection");
+  if (n > sm.n_leases) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_load: %u records for %u leases", n, sm.n_leases);
+  if (!n) return YDC_OK;
+  {
+    std::vector<uint64_t> sorted(task_id, task_id + n);
+    std::sort(sorted.begin(), sorted.end());
+    const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+    if (dup != sorted.end())
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_load: task %llu appears twice", (unsigned long long)*dup);
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevBuf<unsigned long long> d_id;
+  DevBuf<int64_t> d_at;
+  DevBuf<uint32_t> d_slot, d_env, d_ip, d_miss;
+  DevBuf<uint8_t> d_pre;
+  HIP_TRY(c, d_id.reserve(n));
+  HIP_TRY(c, d_slot.reserve(n));
+  HIP_TRY(c, d_miss.reserve(1));
+  HIP_TRY(c, hipMemcpy(d_id.p, task_id, (size_t)n * 8, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemset(d_miss.p, 0, 4));
+  YDC_LAUNCH(c, "k_inspect_find", k_inspect_find, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, sm.lt, sm.ls, d_id.p, n,
+             d_slot.p, d_miss.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint32_t missing = 0;
+  HIP_TRY(c, hipMemcpy(&missing, d_miss.p, 4, hipMemcpyDeviceToHost));
+  if (missing) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_load: %u of %u ids are no lease", missing, n);
+  if (started_at) {
+    HIP_TRY(c, d_at.reserve(n));
+    HIP_TRY(c, hipMemcpy(d_at.p, started_at, (size_t)n * 8, hipMemcpyHostToDevice));
+  }
+  if (env_id) {
+    HIP_TRY(c, d_env.reserve(n));
+    HIP_TRY(c, hipMemcpy(d_env.p, env_id, (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  if (requestor_ip) {
+    HIP_TRY(c, d_ip.reserve(n));
+    HIP_TRY(c, hipMemcpy(d_ip.p, requestor_ip, (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  if (prefetch) {
+    HIP_TRY(c, d_pre.reserve(n));
+    HIP_TRY(c, hipMemcpy(d_pre.p, prefetch, n, hipMemcpyHostToDevice));
+  }
+  YDC_LAUNCH(c, "k_inspect_file", k_inspect_file, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, d_slot.p, n,
+             sm.lt.mask + 1, d_at.p, d_env.p, d_ip.p, d_pre.p, sm.d_insp_rec.p, sm.d_insp_pre.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return YDC_OK;
+}
+
+int ydc_stream_inspect_servants(ydc_context* c, int64_t* out_discovered_at, uint64_t* out_ever_assigned,
+                                uint32_t* out_running_tasks, uint32_t* out_capacity_available, uint32_t cap,
+                                uint32_t* out_n, ydc_stream_totals* out_totals) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.inspect)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_servants: the stream has no inspection");
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = inspect_fit(c, sm.last_now == INT64_MIN ? 0 : sm.last_now)) return rc;
+  const uint32_t n = sm.inspect_n;
+  *out_n = n;
+  if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u servants > cap %u", n, cap);
+  HIP_TRY(c, sm.d_insp_avail.reserve(n));
+  HIP_TRY(c, sm.d_insp_sums.reserve(1));
+  InspectSums sums{0, 0, 0};
+  HIP_TRY(c, hipMemcpy(sm.d_insp_sums.p, &sums, sizeof sums, hipMemcpyHostToDevice));
+  if (n) {
+    YDC_LAUNCH(c, "k_inspect_servants", k_inspect_servants, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, c->d_nproc.p,
+               c->d_load.p, c->d_max_tasks.p, c->d_running.p, c->d_flags.p, n, sm.d_insp_avail.p, sm.d_insp_sums.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (out_discovered_at) HIP_TRY(c, hipMemcpy(out_discovered_at, sm.d_insp_disc.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (out_ever_assigned) HIP_TRY(c, hipMemcpy(out_ever_assigned, sm.d_insp_ever.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (out_running_tasks) HIP_TRY(c, hipMemcpy(out_running_tasks, c->d_running.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (out_capacity_available)
+      HIP_TRY(c, hipMemcpy(out_capacity_available, sm.d_insp_avail.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&sums, sm.d_insp_sums.p, sizeof sums, hipMemcpyDeviceToHost));
+  }
+  if (out_totals) {
+    // (task_dispatcher.cc:604-612, u64 arithmetic modulo 2^64)
+    const uint64_t left = (uint64_t)sums.capacity - (uint64_t)sums.running - (uint64_t)sums.unavailable;
+    *out_totals = ydc_stream_totals{n, sums.running, sums.capacity, (uint64_t)std::max<int64_t>((int64_t)left, 0),
+                                    sums.unavailable};
+  }
+  return YDC_OK;
+}
+
+int ydc_stream_inspect_tasks(ydc_context* c, uint64_t* out_task_id, uint32_t* out_servant_idx, int64_t* out_expires_at,
+                             uint8_t* out_zombie, int64_t* out_started_at, uint32_t* out_env_id,
+                             uint32_t* out_requestor_ip, uint8_t* out_prefetch, uint32_t cap, uint32_t* out_n) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.inspect)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_tasks: the stream has no inspection");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t nl = sm.n_leases;
+  *out_n = nl;
+  if (nl > cap) return fail(c, YDC_ERR_CAPACITY, "%u leases > cap %u", nl, cap);
+  // One pass over the table; |L| records cross the bus, not 2^k slots; sorted by id here.
+  const size_t pc = std::max(nl, 1u), o_cnt = (pc * 41 + 3) & ~(size_t)3;
+  HIP_TRY(c, sm.d_insp_pack.reserve(o_cnt + 4));
+  uint8_t* d = sm.d_insp_pack.p;
+  const InspectPacked pk{(unsigned long long*)(d + pc * 16), (int64_t*)(d + pc * 24), (uint4*)d,
+                         (uint32_t*)(d + pc * 32),            (uint32_t*)(d + pc * 36), d + pc * 40, (uint32_t)pc};
+  HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, 4, c->stream));
+  YDC_LAUNCH(c, "k_inspect_pack", k_inspect_pack, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
+             sm.lt, sm.d_insp_rec.p, sm.d_insp_pre.p, pk, (uint32_t*)(d + o_cnt));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<uint8_t> h(o_cnt + 4);
+  HIP_TRY(c, hipMemcpy(h.data(), d, h.size(), hipMemcpyDeviceToHost));
+  uint32_t packed = 0;
+  std::memcpy(&packed, h.data() + o_cnt, 4);
+  if (packed != nl) return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: %u live slots, |L| %u on the host", packed, nl);
+  auto at = [&](size_t off, size_t width, uint32_t i, void* out) { std::memcpy(out, h.data() + off + (size_t)i * width, width); };
+  std::vector<std::pair<unsigned long long, uint32_t>> order(nl);  // (id, packed position)
+  for (uint32_t i = 0; i < nl; ++i) {
+    at(pc * 16, 8, i, &order[i].first);
+    order[i].second = i;
+  }
+  std::sort(order.begin(), order.end());
+  for (uint32_t k = 0; k < nl; ++k) {
+    const uint32_t i = order[k].second;
+    uint32_t rec[4], state = 0;
+    at(0, 16, i, rec);
+    at(pc * 36, 4, i, &state);
+    if (out_task_id) out_task_id[k] = order[k].first;
+    if (out_servant_idx) at(pc * 32, 4, i, &out_servant_idx[k]);
+    if (out_expires_at) at(pc * 24, 8, i, &out_expires_at[k]);
+    if (out_zombie) out_zombie[k] = (state & kLeaseZombie) ? 1 : 0;
+    if (out_started_at) out_started_at[k] = (int64_t)((uint64_t)rec[0] | ((uint64_t)rec[1] << 32));
+    if (out_env_id) out_env_id[k] = rec[2];
+    if (out_requestor_ip) out_requestor_ip[k] = rec[3];
+    if (out_prefetch) out_prefetch[k] = h[pc * 40 + i];
+  }
   return YDC_OK;
 }
 
@@ -5351,6 +5647,9 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
   } else {
     mirror_rows(c, upd_idx, upd_rows, n_upd);
   }
+  // Inspection (stream_inspect.h): a servant this tick's heartbeats appended was discovered now.
+  if (sm.inspect)
+    if (int rc = inspect_fit(c, lt->now)) return rc;
   // Aliveness (servant_alive.h): step 5 is the whole of OnExpirationTimer. No servant can be due while
   // the host's bound of min(E) is not below the clock; when it is, k_alive_due says who is, and a tick
   // in which somebody is takes the removal route here, in front of the step.

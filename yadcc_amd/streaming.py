@@ -80,3 +80,76 @@ def rpc_resolved_grants(result, j):
     a = int(result["res_first"][j])
     b = a + int(result["res_n_granted"][j])
     return result["res_servants"][a:b], result["res_task_ids"][a:b]
+
+
+PRIORITY_NAMES = {0: "SERVANT_PRIORITY_UNKNOWN", 1: "SERVANT_PRIORITY_DEDICATED", 2: "SERVANT_PRIORITY_USER"}
+REASON_NAMES = {0: "NOT_ACCEPTING_TASK_REASON_UNKNOWN", 1: "NOT_ACCEPTING_TASK_REASON_USER_INSTRUCTED",
+                2: "NOT_ACCEPTING_TASK_REASON_POOR_MACHINE", 3: "NOT_ACCEPTING_TASK_REASON_CGROUPS_PRESENT",
+                4: "NOT_ACCEPTING_TASK_REASON_BEHIND_NAT", 100: "NOT_ACCEPTING_TASK_REASON_NOT_VERIFIED"}
+
+
+def format_time(t, unit_s=1e-3):
+    """A clock reading of the ticks (`unit_s` seconds per unit) as the reference's FormatTime prints it."""
+    import time
+    return time.strftime("%Y-%m-%d %H:%M:%S", time.gmtime(int(t) * unit_s))
+
+
+def dump_internals(servants, tasks, sv, locations, digest_names, host_names, expires_at=None, fmt=format_time):
+    """The reference's DumpInternals (task_dispatcher.cc:538-614) as a dict of the JSON's shape, from
+    what an open stream with inspection answers and the tables a scheduler owns anyway. No compute:
+    every number is one of the two get calls' (binding.Context.stream_inspect_servants / _tasks).
+
+    servants, tasks: the two dicts. sv: the registry's columns as the scheduler keeps them (version,
+    num_processors, current_load, max_tasks, priority, total_memory, memory_available, env_mask;
+    optionally not_accepting_task_reason). locations: per servant row its observed location, or
+    (observed, reported). digest_names: env_id -> compiler digest; host_names: requestor_ip id -> the
+    requestor's address (a lease granted while inspection was off has neither: None). expires_at: the
+    servants' expiry column where aliveness keeps one (ydc_stream_alive_get). Times go through fmt."""
+    out = {}
+    em = sv["env_mask"]
+    reason = sv.get("not_accepting_task_reason")
+    for s in range(len(servants["running_tasks"])):
+        item = {"version": int(sv["version"][s])}
+        loc = locations[s]
+        observed, reported = (loc, loc) if isinstance(loc, str) else loc
+        if observed != reported:
+            item["observed_location"], item["reported_location"] = observed, reported
+        else:
+            item["location"] = observed
+        item["discovered_at"] = fmt(servants["discovered_at"][s])
+        item["expires_at"] = fmt(expires_at[s]) if expires_at is not None else None
+        words = [int(em[s])] if em.ndim == 1 else [int(w) for w in em[s]]
+        envs = [digest_names[64 * k + b] for k, w in enumerate(words) for b in range(64) if w >> b & 1]
+        if envs:
+            item["environments"] = envs
+        item["priority"] = PRIORITY_NAMES[int(sv["priority"][s])]
+        if int(sv["max_tasks"][s]):
+            item["max_tasks"] = int(sv["max_tasks"][s])
+        else:
+            item["not_accepting_task_reason"] = REASON_NAMES[int(reason[s]) if reason is not None else 0]
+        item["num_processors"] = int(sv["num_processors"][s])
+        item["current_load"] = int(sv["current_load"][s])
+        item["capacity_available"] = int(servants["capacity_available"][s])
+        item["total_memory_mb"] = int(sv["total_memory"][s]) >> 20
+        item["memory_available_mb"] = int(sv["memory_available"][s]) >> 20
+        item["running_tasks"] = int(servants["running_tasks"][s])
+        item["ever_assigned_tasks"] = int(servants["ever_assigned"][s])
+        out.setdefault("servants", []).append(item)
+    for k in range(len(tasks["task_id"])):
+        tid, env, ip = int(tasks["task_id"][k]), int(tasks["env_id"][k]), int(tasks["requestor_ip"][k])
+        loc = locations[int(tasks["servant_idx"][k])]
+        known = env != binding.INSPECT_NO_ID
+        out.setdefault("tasks", {})[str(tid)] = {
+            "task_id": tid,
+            "requestor_ip": host_names[ip] if known else None,
+            "compiler_digest": digest_names[env] if known else None,
+            "started_at": fmt(tasks["started_at"][k]) if known else None,
+            "expires_at": fmt(tasks["expires_at"][k]),
+            "prefetched_task": bool(tasks["prefetch"][k]),
+            "servant_location": loc if isinstance(loc, str) else loc[0],
+            "zombie": bool(tasks["zombie"][k]),
+        }
+    tot = servants["totals"]
+    for k in ("servants_up", "running_tasks", "capacity", "capacity_available", "capacity_unavailable"):
+        out[k] = int(tot[k])
+    return out
