@@ -672,6 +672,55 @@ int ydc_stream_inspect_tasks(ydc_context* ctx, uint64_t* out_task_id, uint32_t* 
                              uint32_t* out_env_id, uint32_t* out_requestor_ip, uint8_t* out_prefetch,
                              uint32_t cap, uint32_t* out_n);
 
+/* ---- the outlook per request personality, and a view of the waiting queue ----------------------
+ * The operator's first question when builds stall: for THIS compiler digest at THIS minimum version,
+ * how many servants are eligible, how many are free, how many grants could be given right now, and
+ * how many RPCs are blocked on it. Both calls answer from what an open waiting, leased,
+ * waiting-and-leased or rpc stream keeps on the device; they run between ticks and synchronise.
+ *   ydc_stream_outlook_get: out[i] for the personality (env_id[i], min_version[i]), n of them; queries
+ *     may repeat; n == 0 is YDC_OK (NULL columns allowed then).
+ *     Supply columns: a servant counts if max_tasks != 0, its environment set has bit env_id and
+ *     version >= min_version (UnsafeEnumerateEligibleServants, task_dispatcher.cc:316-344) — exactly
+ *     the class test the batch pipeline applies. free_servants are the eligible ones with
+ *     running_tasks < GetCapacityAvailable (:346-360). grants_available is what N identical requests
+ *     from a host that owns no eligible servant are granted by the next tick (a requestor's own
+ *     servant is its last resort and counts as well). All sums are 64-bit.
+ *     Demand columns: waiting, waiting_rows, leases and zombies depend on env_id ONLY. An entry of W
+ *     counts for its digest whatever min_version it carries itself, and a lease's record does not
+ *     keep the version. Without W (a leased stream) waiting = waiting_rows = 0. leases / zombies need
+ *     inspection and are YDC_OUTLOOK_UNKNOWN without it (nothing else here needs it); a lease granted
+ *     while inspection was off (YDC_INSPECT_NO_ID) is counted for no digest; zombies uses the zombie
+ *     bit as ydc_stream_inspect_tasks reports it, and a zombie is counted in leases too.
+ *     An env_id >= 64 * env_words of the resident table is a digest nobody has: its row is all zeros
+ *     (leases / zombies YDC_OUTLOOK_UNKNOWN with inspection off).
+ *   ydc_stream_inspect_waiting: W in queue order, *out_n entries, W kept (ydc_stream_waiting_take is
+ *     the destructive one). Columns the mode lacks come back 0: lease_for on a waiting stream, both
+ *     counts outside rpc mode, where n_immediate is reported as 1. Any output pointer may be NULL.
+ *     More than cap entries: YDC_ERR_CAPACITY with *out_n = |W| and nothing written. A leased stream
+ *     (no W) answers *out_n = 0.
+ *   Both: no stream open, a plain ydc_stream_begin stream, or pipelined batches outstanding is
+ *     YDC_ERR_INVALID_ARGUMENT. Like every other entry point they end a resident tick kernel first.
+ *     They change nothing: the next tick's results are those of a twin context that never called
+ *     them, no tick launches anything else because of them, and nothing of theirs is carried by
+ *     ydc_stream_reserve, ydc_stream_snapshot or ydc_stream_restore. */
+#define YDC_OUTLOOK_UNKNOWN 0xFFFFFFFFu
+typedef struct ydc_stream_outlook {
+  uint32_t eligible;           /* servants UnsafeEnumerateEligibleServants lists for (env_id, min_version) */
+  uint32_t free_servants;      /* of those, the ones UnsafeEnumerateFreeServants keeps (:350-358) */
+  uint64_t grants_available;   /* sum of servant_slot_count over the eligible: grants N identical requests get now */
+  uint64_t running_tasks;      /* sums over the eligible servants */
+  uint64_t max_tasks;
+  uint64_t capacity_available; /* sum of GetCapacityAvailable (:283-313), as ydc_stream_inspect_servants computes it */
+  uint32_t waiting, waiting_rows;  /* entries of W with this env_id, and their rows (rpc: n_immediate + n_prefetch; else = waiting) */
+  uint32_t leases, zombies;    /* leases whose inspection record has this env_id; YDC_OUTLOOK_UNKNOWN with inspection off */
+} ydc_stream_outlook;
+int ydc_stream_outlook_get(ydc_context* ctx, const uint32_t* env_id, const uint32_t* min_version,
+                           uint32_t n, ydc_stream_outlook* out);
+int ydc_stream_inspect_waiting(ydc_context* ctx, uint64_t* out_tag, uint32_t* out_env_id,
+                               uint32_t* out_min_version, uint32_t* out_requestor_ip, int64_t* out_deadline,
+                               int64_t* out_lease_for, uint32_t* out_n_immediate, uint32_t* out_n_prefetch,
+                               uint32_t cap, uint32_t* out_n);
+
 /* ---- snapshot and restore of an open stream --------------------------------------------
  * Everything an open waiting, leased, waiting-and-leased or rpc stream keeps on the device (L with
  * next_id and the report stamps, W, B, E, running_tasks, the registry's columns, the clock and the

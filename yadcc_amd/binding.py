@@ -22,6 +22,7 @@ IDX_ENV_NOT_FOUND = 0xFFFFFFFE
 IDX_WAITING = 0xFFFFFFFD  # streaming waiting mode: queued on the device, answered in a later tick
 INSPECT_NO_ID = 0xFFFFFFFF  # env_id / requestor_ip of a lease granted while inspection was off
 INSPECT_NO_TIME = -(1 << 63)  # ... its started_at
+OUTLOOK_UNKNOWN = 0xFFFFFFFF  # leases / zombies of an outlook row while inspection is off
 DISPATCH_COMMIT = 1
 STAGES = ("servant_scan", "slot_gen", "sort", "class_lists", "task_classify", "match", "finalize",
           "total")
@@ -44,6 +45,7 @@ ABI_SYMBOLS = (
     "ydc_stream_book_begin", "ydc_stream_book_stage", "ydc_stream_book_get",
     "ydc_stream_alive_begin", "ydc_stream_alive_stage", "ydc_stream_alive_removed", "ydc_stream_alive_get",
     "ydc_stream_inspect_begin", "ydc_stream_inspect_load", "ydc_stream_inspect_servants", "ydc_stream_inspect_tasks",
+    "ydc_stream_outlook_get", "ydc_stream_inspect_waiting",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
@@ -68,6 +70,20 @@ class StreamTotals(C.Structure):
     """ydc_stream_totals."""
     _fields_ = [(k, C.c_uint64) for k in ("servants_up", "running_tasks", "capacity", "capacity_available",
                                           "capacity_unavailable")]
+
+
+class StreamOutlook(C.Structure):
+    """ydc_stream_outlook."""
+    _fields_ = [("eligible", C.c_uint32), ("free_servants", C.c_uint32), ("grants_available", C.c_uint64),
+                ("running_tasks", C.c_uint64), ("max_tasks", C.c_uint64), ("capacity_available", C.c_uint64),
+                ("waiting", C.c_uint32), ("waiting_rows", C.c_uint32), ("leases", C.c_uint32),
+                ("zombies", C.c_uint32)]
+
+
+# numpy view of ydc_stream_outlook (56 bytes)
+OUTLOOK_DTYPE = np.dtype([("eligible", "<u4"), ("free_servants", "<u4"), ("grants_available", "<u8"),
+                          ("running_tasks", "<u8"), ("max_tasks", "<u8"), ("capacity_available", "<u8"),
+                          ("waiting", "<u4"), ("waiting_rows", "<u4"), ("leases", "<u4"), ("zombies", "<u4")])
 
 
 # numpy view of ydc_servant_row (32 bytes)
@@ -212,6 +228,8 @@ def lib():
         L.ydc_stream_inspect_load.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_uint32]
         L.ydc_stream_inspect_servants.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_void_p]
         L.ydc_stream_inspect_tasks.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
+        L.ydc_stream_outlook_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ydc_stream_inspect_waiting.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
         L.ydc_stream_book_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1072,6 +1090,37 @@ class Context:
         self._check(lib().ydc_stream_inspect_tasks(self._h, *[_ptr(a) for a in cols.values()], k, C.byref(n)),
                     "ydc_stream_inspect_tasks")
         return cols
+
+    def stream_outlook(self, env_id, min_version):
+        """The outlook of every personality (env_id[i], min_version[i]) (ydc_stream_outlook_get): dict
+        of arrays eligible, free_servants, grants_available, running_tasks, max_tasks,
+        capacity_available, waiting, waiting_rows, leases, zombies (the last two OUTLOOK_UNKNOWN while
+        inspection is off)."""
+        env = np.ascontiguousarray(env_id, dtype=np.uint32)
+        minv = np.ascontiguousarray(min_version, dtype=np.uint32)
+        assert env.ndim == 1 and env.shape == minv.shape
+        out = np.zeros(len(env), OUTLOOK_DTYPE)
+        self._check(lib().ydc_stream_outlook_get(self._h, _ptr(env), _ptr(minv), len(env), _ptr(out)),
+                    "ydc_stream_outlook_get")
+        return {k: out[k].copy() for k in OUTLOOK_DTYPE.names}
+
+    def stream_waiting(self, cap=None):
+        """The waiting queue in queue order, left as it is (ydc_stream_inspect_waiting): dict of tag,
+        env_id, min_version, requestor_ip, deadline, lease_for, n_immediate, n_prefetch. cap: the
+        room offered (None: asked for first)."""
+        n = C.c_uint32(0)
+        if cap is None:
+            rc = lib().ydc_stream_inspect_waiting(self._h, *([None] * 8), 0, C.byref(n))
+            if rc != -4:  # (YDC_ERR_CAPACITY with the count is the expected answer; an empty queue: 0)
+                self._check(rc, "ydc_stream_inspect_waiting")
+            cap = int(n.value)
+        cols = {"tag": np.empty(cap, np.uint64), "env_id": np.empty(cap, np.uint32),
+                "min_version": np.empty(cap, np.uint32), "requestor_ip": np.empty(cap, np.uint32),
+                "deadline": np.empty(cap, np.int64), "lease_for": np.empty(cap, np.int64),
+                "n_immediate": np.empty(cap, np.uint32), "n_prefetch": np.empty(cap, np.uint32)}
+        self._check(lib().ydc_stream_inspect_waiting(self._h, *[_ptr(a) for a in cols.values()], cap, C.byref(n)),
+                    "ydc_stream_inspect_waiting")
+        return {k: a[:n.value].copy() for k, a in cols.items()}
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

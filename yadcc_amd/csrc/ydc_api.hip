@@ -30,6 +30,7 @@
 #include "running_book.h"
 #include "servant_alive.h"
 #include "stream_inspect.h"
+#include "stream_outlook.h"
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
 #include "tick_kernel.h"
@@ -380,6 +381,10 @@ struct ydc_context {
     DevBuf<uint32_t> d_insp_avail;   // k_inspect_servants' per-servant result
     DevBuf<InspectSums> d_insp_sums;
     DevBuf<uint8_t> d_insp_pack;     // k_inspect_pack's columns and their count
+    // ydc_stream_outlook_get (stream_outlook.h): scratch only, reserved at the first call and
+    // released with the stream; nothing of it is state, so reserve / restore carry nothing over.
+    DevBuf<unsigned long long> d_outlook_agg, d_outlook_res;  // per class; per query (kOutlookCols each)
+    DevBuf<uint32_t> d_outlook_q, d_outlook_hist;             // queries (env | minv); W's and L's histograms
   } stream_mode;
   // ydc_stream_snapshot: the packed columns of L with their count on the device, and the page-locked
   // block they cross the bus into. Kept for the next snapshot (a standby is fed periodically, and
@@ -5284,6 +5289,114 @@ int ydc_stream_inspect_tasks(ydc_context* c, uint64_t* out_task_id, uint32_t* ou
     if (out_requestor_ip) out_requestor_ip[k] = rec[3];
     if (out_prefetch) out_prefetch[k] = h[pc * 40 + i];
   }
+  return YDC_OK;
+}
+
+// What both read calls of the outlook refuse, and what every entry point does before it reads the
+// registry: the resident kernel ended, the stream's work drained.
+static int outlook_enter(ydc_context* c, const char* who) {
+  auto& sm = c->stream_mode;
+  if (!sm.active) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: no stream is open", who);
+  if (!sm.max_waiting && !sm.max_leases)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: a stream begun with ydc_stream_begin keeps no state on the device", who);
+  if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: pipelined batches are outstanding", who);
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return YDC_OK;
+}
+
+int ydc_stream_outlook_get(ydc_context* c, const uint32_t* env_id, const uint32_t* min_version, uint32_t n,
+                           ydc_stream_outlook* out) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (n && (!env_id || !min_version || !out))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_outlook_get: %u queries without their columns", n);
+  if (int rc = outlook_enter(c, "ydc_stream_outlook_get")) return rc;
+  if (!n) return YDC_OK;
+  auto& sm = c->stream_mode;
+  if (c->tables_dirty)
+    if (int rc = rebuild_tables(c)) return rc;  // (what the next tick would do first)
+  const uint32_t S = c->n_servants, C = c->tables.n_classes(), EW = c->env_words, bins = 64 * EW + 1;
+  const bool with_w = sm.max_waiting != 0, with_l = sm.max_leases != 0 && sm.inspect;
+  const size_t n_agg = (size_t)std::max(C, 1u) * kOutlookCols, n_res = (size_t)n * kOutlookCols;
+  HIP_TRY(c, sm.d_outlook_agg.reserve(n_agg));
+  HIP_TRY(c, sm.d_outlook_res.reserve(n_res));
+  HIP_TRY(c, sm.d_outlook_q.reserve((size_t)n * 2));
+  HIP_TRY(c, sm.d_outlook_hist.reserve((size_t)bins * 4));
+  uint32_t *d_env = sm.d_outlook_q.p, *d_minv = d_env + n;
+  uint32_t *d_hw = sm.d_outlook_hist.p, *d_hl = d_hw + (size_t)bins * 2;
+  HIP_TRY(c, hipMemcpy(d_env, env_id, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_minv, min_version, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemsetAsync(sm.d_outlook_agg.p, 0, n_agg * 8, c->stream));
+  HIP_TRY(c, hipMemsetAsync(d_hw, 0, (size_t)bins * 16, c->stream));
+  if (S && C)
+    YDC_LAUNCH(c, "k_outlook_classes", k_outlook_classes, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, c->d_nproc.p,
+               c->d_load.p, c->d_max_tasks.p, c->d_running.p, c->d_flags.p, c->d_class_of.p, S, C, sm.d_outlook_agg.p);
+  YDC_LAUNCH(c, "k_outlook_queries", k_outlook_queries, dim3(ceil_div(n, 4)), dim3(256), 0, c->stream, d_env, d_minv, n,
+             c->d_cls_env.p, c->d_cls_ver.p, C, EW, sm.d_outlook_agg.p, sm.d_outlook_res.p);
+  if (with_w)
+    YDC_LAUNCH(c, "k_outlook_waiting", k_outlook_waiting, dim3(std::max(ceil_div(sm.n_waiting, 256), 1u)), dim3(256), 0,
+               c->stream, sm.wq.env, sm.rw.n_imm, sm.rw.n_pre, sm.ws, sm.max_waiting, bins, d_hw);
+  if (with_l)
+    YDC_LAUNCH(c, "k_outlook_leases", k_outlook_leases, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0,
+               c->stream, sm.lt, sm.d_insp_rec.p, bins, d_hl);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<unsigned long long> res(n_res);
+  std::vector<uint32_t> hist((size_t)bins * 4);
+  HIP_TRY(c, hipMemcpy(res.data(), sm.d_outlook_res.p, n_res * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(hist.data(), sm.d_outlook_hist.p, (size_t)bins * 16, hipMemcpyDeviceToHost));
+  // The per-digest histograms fanned out to the queries (the last bin is nobody's).
+  for (uint32_t q = 0; q < n; ++q) {
+    const unsigned long long* r = &res[(size_t)q * kOutlookCols];
+    const uint32_t e = env_id[q];
+    const bool known = e < bins - 1;
+    ydc_stream_outlook o{};
+    o.eligible = (uint32_t)r[0];
+    o.free_servants = (uint32_t)r[1];
+    o.grants_available = r[2];
+    o.running_tasks = r[3];
+    o.max_tasks = r[4];
+    o.capacity_available = r[5];
+    o.waiting = with_w && known ? hist[e] : 0;
+    o.waiting_rows = with_w && known ? hist[bins + e] : 0;
+    o.leases = !with_l ? YDC_OUTLOOK_UNKNOWN : known ? hist[(size_t)bins * 2 + e] : 0;
+    o.zombies = !with_l ? YDC_OUTLOOK_UNKNOWN : known ? hist[(size_t)bins * 3 + e] : 0;
+    out[q] = o;
+  }
+  return YDC_OK;
+}
+
+int ydc_stream_inspect_waiting(ydc_context* c, uint64_t* out_tag, uint32_t* out_env_id, uint32_t* out_min_version,
+                               uint32_t* out_requestor_ip, int64_t* out_deadline, int64_t* out_lease_for,
+                               uint32_t* out_n_immediate, uint32_t* out_n_prefetch, uint32_t cap, uint32_t* out_n) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  if (int rc = outlook_enter(c, "ydc_stream_inspect_waiting")) return rc;
+  auto& sm = c->stream_mode;
+  uint32_t n = 0;
+  if (sm.max_waiting) {
+    HIP_TRY(c, hipMemcpy(&n, &sm.ws->count, 4, hipMemcpyDeviceToHost));
+    if (n > sm.max_waiting)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u on the device, room for %u", n, sm.max_waiting);
+  }
+  *out_n = n;
+  if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u waiting requests > cap %u", n, cap);
+  // Entries [0, |W|) of the mode's own columns; what the mode lacks: 0 (one immediate row outside rpc mode).
+  auto column = [&](void* dst, const void* src, size_t width) {
+    if (!dst || !n) return hipSuccess;
+    if (src) return hipMemcpy(dst, src, n * width, hipMemcpyDeviceToHost);
+    std::memset(dst, 0, n * width);
+    return hipSuccess;
+  };
+  HIP_TRY(c, column(out_tag, sm.wq.tag, 8));
+  HIP_TRY(c, column(out_env_id, sm.wq.env, 4));
+  HIP_TRY(c, column(out_min_version, sm.wq.minv, 4));
+  HIP_TRY(c, column(out_requestor_ip, sm.wq.ip, 4));
+  HIP_TRY(c, column(out_deadline, sm.wq.deadline, 8));
+  HIP_TRY(c, column(out_lease_for, sm.wl.w_for, 8));
+  HIP_TRY(c, column(out_n_immediate, sm.rw.n_imm, 4));
+  HIP_TRY(c, column(out_n_prefetch, sm.rw.n_pre, 4));
+  if (!sm.rw.n_imm && out_n_immediate) std::fill(out_n_immediate, out_n_immediate + n, 1u);
   return YDC_OK;
 }
 

@@ -153,3 +153,30 @@ def dump_internals(servants, tasks, sv, locations, digest_names, host_names, exp
     for k in ("servants_up", "running_tasks", "capacity", "capacity_available", "capacity_unavailable"):
         out[k] = int(tot[k])
     return out
+
+
+OUTLOOK_COLUMNS = ("eligible", "free_servants", "grants_available", "running_tasks", "max_tasks",
+                   "capacity_available", "waiting", "waiting_rows", "leases", "zombies")
+
+
+def outlook_table(outlook, digest_names, env_id=None, min_version=None):
+    """The per-digest table /inspect gains: one line per row of a binding.Context.stream_outlook result,
+    named by compiler digest. No compute: every number is the call's. digest_names: env_id -> digest,
+    indexed by env_id[i] (without env_id: by the row number); an id without a name prints as "#id";
+    a column that is OUTLOOK_UNKNOWN (leases / zombies while inspection is off) prints as "-"."""
+    n = len(outlook["eligible"])
+    ids = list(range(n)) if env_id is None else [int(e) for e in env_id]
+    names = []
+    for i, e in enumerate(ids):
+        name = digest_names[e] if e < len(digest_names) and digest_names[e] is not None else "#%d" % e
+        names.append(name if min_version is None else "%s >= %d" % (name, int(min_version[i])))
+    rows = [("digest",) + OUTLOOK_COLUMNS]
+    for i in range(n):
+        cells = []
+        for k in OUTLOOK_COLUMNS:
+            v = int(outlook[k][i])
+            cells.append("-" if k in ("leases", "zombies") and v == binding.OUTLOOK_UNKNOWN else str(v))
+        rows.append((names[i],) + tuple(cells))
+    width = [max(len(r[c]) for r in rows) for c in range(len(rows[0]))]
+    return "\n".join("  ".join(cell.ljust(width[c]) if c == 0 else cell.rjust(width[c])
+                               for c, cell in enumerate(r)).rstrip() for r in rows)
