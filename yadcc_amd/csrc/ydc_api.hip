@@ -9,6 +9,7 @@
 #include <rccl/rccl.h>  // types and prototypes only: librccl is resolved with dlopen at ydc_group_init
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -17,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/yadcc_dispatch.h"
@@ -76,6 +78,42 @@ struct DevBuf {
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;
+    cap = 0;
+  }
+};
+
+// Owns one page-locked allocation in the same way. z: the block's device address where it is
+// mapped (the default flags), NULL where it is not.
+struct PinnedBuf {
+  uint8_t *p = nullptr, *z = nullptr;
+  size_t cap = 0;  // bytes
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  PinnedBuf(PinnedBuf&& o) noexcept { *this = std::move(o); }
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr), z = std::exchange(o.z, nullptr), cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~PinnedBuf() { release(); }
+  // Grow only; the contents are not kept.
+  hipError_t reserve(size_t bytes, unsigned flags = hipHostMallocCoherent | hipHostMallocMapped) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    const size_t want = std::max<size_t>(bytes, 16);
+    hipError_t e = hipHostMalloc((void**)&p, want, flags);
+    if (e != hipSuccess) p = nullptr;
+    else if (flags & hipHostMallocMapped) e = hipHostGetDevicePointer((void**)&z, p, 0);
+    if (e == hipSuccess) cap = want;
+    else release();
+    return e;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = z = nullptr;
     cap = 0;
   }
 };
@@ -252,16 +290,27 @@ struct ydc_context {
   // committed batch, replayed from a captured graph.
   struct Stream {
     bool active = false, stale = true;
-    uint32_t max_upd = 0, max_rel = 0, max_tasks = 0, passes = 0;
+    // The stream's bounds, once. A part the mode lacks has 0 everywhere, so they say the mode as
+    // well (rpc mode: max_tasks is max_requests). max_book: the running-task book's (0: none).
+    ydc_stream_caps caps{};
+    uint32_t max_book = 0;
+    bool waiting() const { return caps.max_waiting != 0; }
+    bool leased() const { return caps.max_leases != 0; }
+    bool rpc() const { return caps.max_rows != 0; }
+    uint32_t passes = 0;
+    // What is sized by the bounds is laid out by stream_alloc and, when the stream grows, filled
+    // by stream_migrate from the old one; what is sized by the registry (d_rep_tick, `alive`,
+    // `inspect`) moves to the grown stream as it is (stream_regrow).
     // One pinned staging arena for everything a tick brings (TickArena) and its device mirror,
     // which the ticks that run eagerly copy it to. Its sections three times: at their host
     // addresses, in the mirror, and as the kernels of the captured step see the page-locked
     // arena when they read it in place (no H2D copy node).
-    uint8_t* h_in = nullptr;
+    PinnedBuf h_in;
     DevBuf<uint8_t> d_in;
     size_t in_bytes = 0;
     TickArena h{}, d{}, z{};
-    uint32_t *h_out = nullptr, *z_out = nullptr;  // the placement (page-locked), host and device addresses
+    PinnedBuf h_place;                            // the placement, page-locked
+    uint32_t *h_out = nullptr, *z_out = nullptr;  // ... at its host and device addresses
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     BatchPlan plan;
@@ -280,8 +329,7 @@ struct ydc_context {
     uint32_t want_passes = 0, window_max = 0, window_ticks = 0;
     // Waiting mode (ydc_stream_begin_waiting; wait_queue.h): the queue W of requests that found
     // no free servant, in HBM, and the tick's batch columns [max_waiting | max_tasks] the gather
-    // builds in front of the batch. max_waiting == 0: a plain context (none of this exists).
-    uint32_t max_waiting = 0;
+    // builds in front of the batch. !waiting(): a plain context (none of this exists).
     uint32_t n_waiting = 0;  // |W| after the last tick (the outcome block's, kept here)
     int64_t last_now = INT64_MIN;
     DevBuf<uint8_t> d_wait;
@@ -290,7 +338,7 @@ struct ydc_context {
     WaitState* ws = nullptr;
     unsigned long long* lookback = nullptr;
     uint32_t lookback_n = 0;
-    uint8_t* h_wres = nullptr;  // page-locked: resolved tags | resolved answers | outcome
+    PinnedBuf h_wres;  // page-locked: resolved tags | resolved answers | outcome
     uint64_t *h_res_tag = nullptr, *z_res_tag = nullptr;
     uint32_t *h_res_idx = nullptr, *z_res_idx = nullptr;
     WaitOutcome *h_wout = nullptr, *z_wout = nullptr;
@@ -300,9 +348,8 @@ struct ydc_context {
     WaitLeaseCols wl{};
     unsigned long long* h_res_id = nullptr;
     // Leased mode (ydc_stream_begin_leased; lease_table.h): the lease table L in HBM, the placement
-    // of the tick's batch in front of k_lease_grant, and the page-locked results. max_leases == 0:
-    // not a leased context (none of this exists). lookback / lookback_n above serve k_lease_grant.
-    uint32_t max_leases = 0, max_renew = 0, max_free = 0, max_rep = 0, max_rep_ids = 0;
+    // of the tick's batch in front of k_lease_grant, and the page-locked results. !leased(): not a
+    // leased context (none of this exists). lookback / lookback_n above serve k_lease_grant.
     uint32_t n_leases = 0;    // |L| after the last tick (the outcome block's, kept here)
     uint32_t lease_tick = 0;  // number of the last tick that was staged
     DevBuf<uint8_t> d_lease;
@@ -311,87 +358,105 @@ struct ydc_context {
     uint32_t* ren_slot = nullptr;
     uint32_t* lt_out = nullptr;     // placement of the batch (k_finalize -> k_lease_grant)
     DevBuf<uint32_t> d_rep_tick;    // per servant: the last tick it reported in
-    uint8_t* h_lres = nullptr;      // page-locked: task ids | renewed | report_unknown | outcome
+    PinnedBuf h_lres;               // page-locked: task ids | renewed | report_unknown | outcome
     unsigned long long *h_task_id = nullptr, *z_task_id = nullptr;
     uint8_t *h_renewed = nullptr, *z_renewed = nullptr, *h_unknown = nullptr, *z_unknown = nullptr;
     LeaseOutcome *h_lout = nullptr, *z_lout = nullptr;
-    std::vector<uint32_t> rep_seen;  // per servant: rep_mark of the last report list that named it (host check)
-    uint32_t rep_mark = 0;
+    // "Each servant at most once per list", checked by the host: a stamp per servant and the stamp
+    // of the list being looked at (one more per look, refused ticks included).
+    struct OnceMarks {
+      std::vector<uint32_t> seen;
+      uint32_t mark = 0;
+      void begin(size_t n_servants) {
+        if (seen.size() < n_servants) seen.resize(n_servants, 0);
+        if (++mark == 0) {
+          std::fill(seen.begin(), seen.end(), 0u);
+          mark = 1;
+        }
+      }
+      bool first(uint32_t s) { return std::exchange(seen[s], mark) != mark; }
+    };
+    OnceMarks rep_once;  // over a tick's report list
+    // With inspection: the detail records beside L's slots (stream_inspect.h: a 16-byte record and a
+    // prefetch byte per slot). Sized by the table: stream_migrate files them again with their leases.
+    DevBuf<uint4> d_insp_rec;
+    DevBuf<uint8_t> d_insp_pre;
     // RPC mode (ydc_stream_begin_rpc; rpc_stream.h): a waiting and leased context whose request rows
     // and entries of W are RPCs asking for several grants. max_tasks is max_requests there; the
     // batch is the max_rows expanded rows (wt, wl.t_for, wt_out hold that many), W gains two count
-    // columns, and the answers have their own page-locked block. max_rows == 0: not such a context.
-    uint32_t max_rows = 0;
+    // columns, and the answers have their own page-locked block. !rpc(): not such a context.
     uint32_t n_wait_rows = 0;  // rows W's entries stand for after the last tick
-    uint32_t rows_new = 0;     // rows of the tick in flight's new requests
     DevBuf<uint8_t> d_rpc;
     RpcEntryCols rw{}, rp{};   // W; the tick's positions [max_waiting | max_requests]
     RpcBatch rb{};
     RpcState* rs = nullptr;
     unsigned long long *lb_scan = nullptr, *lb_settle = nullptr, *lb_grant = nullptr;
-    uint8_t* h_rres = nullptr;  // page-locked: the RpcOut sections
-    RpcOut rh{}, rz{};          // ... at their host and device addresses
+    PinnedBuf h_rres;   // page-locked: the RpcOut sections
+    RpcOut rh{}, rz{};  // ... at their host and device addresses
     // The running-task book B of a leased stream (ydc_stream_book_begin; running_book.h): its four
     // columns and its bookkeeping in HBM, its look-back words at the tail of `lookback`, the
-    // page-locked outcome block. max_book == 0: no book (none of this exists).
-    uint32_t max_book = 0;
-    uint32_t n_book = 0;  // |B| after the last tick (the outcome block's, kept here)
-    DevBuf<uint8_t> d_book;
-    BookCols bk{};
-    BookState* bks = nullptr;
-    unsigned long long* lb_book = nullptr;
-    uint8_t* h_bres = nullptr;  // page-locked: the outcome block
-    BookOutcome *h_bout = nullptr, *z_bout = nullptr;
-    // ydc_stream_book_stage: the payload columns of the next accepted tick's reports.
-    bool book_staged = false;
-    std::vector<uint64_t> stage_stid, stage_dkey;
+    // page-locked outcome block. max_book == 0: no book (none of this exists). Sized by max_book,
+    // except `staged`, which moves to a grown stream as it is.
+    struct Book {
+      uint32_t n = 0;  // |B| after the last tick (the outcome block's, kept here)
+      DevBuf<uint8_t> d;
+      BookCols bk{};
+      BookState* bks = nullptr;
+      unsigned long long* lb = nullptr;
+      PinnedBuf h_res;  // page-locked: the outcome block
+      BookOutcome *h_bout = nullptr, *z_bout = nullptr;
+      // ydc_stream_book_stage: the payload columns of the next accepted tick's reports.
+      struct Staged {
+        bool on = false;
+        std::vector<uint64_t> stid, dkey;
+      } staged;
+    } book;
     // The servants' expiry column E of a leased stream (ydc_stream_alive_begin; servant_alive.h): sized
-    // by the registry like d_rep_tick, with a spare the removal route compacts into. alive == false:
-    // no aliveness (none of this exists, and the step launches what it launches without it).
-    bool alive = false;
-    uint32_t alive_n = 0;  // rows of E that are filed (the registry's servant count, between ticks)
-    DevBuf<int64_t> d_alive, d_alive_spare, d_alive_stage;
-    DevBuf<uint32_t> d_alive_idx;
-    DevBuf<AliveState> d_alive_state;
-    uint32_t* h_alive_list = nullptr;  // page-locked: k_alive_due's list
-    uint32_t* z_alive_list = nullptr;  // ... its device address
-    size_t alive_list_cap = 0;
-    int64_t alive_bound = INT64_MAX;  // <= min(E): only errs low; k_alive_due makes it exact
-    uint64_t alive_alarms = 0, alive_removals = 0;  // ticks that launched k_alive_due; ... and removed rows
-    // ydc_stream_alive_stage: the expiries of the next accepted tick's heartbeats.
-    bool alive_staged = false;
-    std::vector<int64_t> alive_stage;
-    // What the most recent accepted tick erased (ydc_stream_alive_removed).
-    std::vector<uint32_t> alive_removed;
-    uint32_t alive_orphans = 0;
-    std::vector<uint32_t> alive_seen;  // per servant: alive_mark of the last heartbeat list that named it
-    uint32_t alive_mark = 0;
-    std::vector<uint32_t> alive_rel, alive_rep;  // the removal route's rewritten releases and report servants
-    // Inspection (ydc_stream_inspect_begin; stream_inspect.h): the detail records beside L's slots (a
-    // 16-byte record and a prefetch byte per slot) and the servants' discovered_at / ever_assigned
-    // columns, sized by the registry like E, each with a spare the removal route compacts into.
-    // inspect == false: no inspection (none of this exists, and the step launches what it launches
-    // without it).
-    bool inspect = false;
-    uint32_t inspect_n = 0;  // rows of the two servant columns that are filed
-    DevBuf<uint4> d_insp_rec;
-    DevBuf<uint8_t> d_insp_pre;
-    DevBuf<int64_t> d_insp_disc, d_insp_disc_spare;
-    DevBuf<unsigned long long> d_insp_ever, d_insp_ever_spare;
-    DevBuf<uint32_t> d_insp_avail;   // k_inspect_servants' per-servant result
-    DevBuf<InspectSums> d_insp_sums;
-    DevBuf<uint8_t> d_insp_pack;     // k_inspect_pack's columns and their count
+    // by the registry like d_rep_tick, with a spare the removal route compacts into. !alive.on: no
+    // aliveness (none of this exists, and the step launches what it launches without it).
+    struct Alive {
+      bool on = false;
+      uint32_t n = 0;  // rows of E that are filed (the registry's servant count, between ticks)
+      DevBuf<int64_t> col, spare, d_stage;
+      DevBuf<uint32_t> d_idx;
+      DevBuf<AliveState> d_state;
+      PinnedBuf due;  // page-locked: k_alive_due's list (uint32_t each)
+      int64_t bound = INT64_MAX;  // <= min(E): only errs low; k_alive_due makes it exact
+      uint64_t alarms = 0, removals = 0;  // ticks that launched k_alive_due; ... and removed rows
+      // ydc_stream_alive_stage: the expiries of the next accepted tick's heartbeats.
+      bool staged = false;
+      std::vector<int64_t> stage;
+      // What the most recent accepted tick erased (ydc_stream_alive_removed).
+      std::vector<uint32_t> removed;
+      uint32_t orphans = 0;
+      OnceMarks once;  // over a tick's heartbeat list
+      std::vector<uint32_t> rel, rep;  // the removal route's rewritten releases and report servants
+    } alive;
+    // Inspection (ydc_stream_inspect_begin; stream_inspect.h), beside the detail records above: the
+    // servants' discovered_at / ever_assigned columns, sized by the registry like E, each with a spare
+    // the removal route compacts into, and the read calls' scratch. !inspect.on: no inspection (none
+    // of this exists, and the step launches what it launches without it).
+    struct Inspect {
+      bool on = false;
+      uint32_t n = 0;  // rows of the two servant columns that are filed
+      DevBuf<int64_t> disc, disc_spare;
+      DevBuf<unsigned long long> ever, ever_spare;
+      DevBuf<uint32_t> avail;   // k_inspect_servants' per-servant result
+      DevBuf<InspectSums> sums;
+      DevBuf<uint8_t> pack;     // k_inspect_pack's columns and their count
+    } inspect;
     // ydc_stream_outlook_get (stream_outlook.h): scratch only, reserved at the first call and
     // released with the stream; nothing of it is state, so reserve / restore carry nothing over.
-    DevBuf<unsigned long long> d_outlook_agg, d_outlook_res;  // per class; per query (kOutlookCols each)
-    DevBuf<uint32_t> d_outlook_q, d_outlook_hist;             // queries (env | minv); W's and L's histograms
+    struct Outlook {
+      DevBuf<unsigned long long> agg, res;  // per class; per query (kOutlookCols each)
+      DevBuf<uint32_t> q, hist;             // queries (env | minv); W's and L's histograms
+    } outlook;
   } stream_mode;
   // ydc_stream_snapshot: the packed columns of L with their count on the device, and the page-locked
   // block they cross the bus into. Kept for the next snapshot (a standby is fed periodically, and
   // the two allocations cost more than everything else the call does).
   DevBuf<uint8_t> d_snap;
-  uint8_t* h_snap = nullptr;
-  size_t h_snap_cap = 0;
+  PinnedBuf h_snap;
   DevBuf<ClassRun> d_runs;
   DevBuf<uint8_t> d_dirty;
   bool debug_sim = false;
@@ -989,7 +1054,6 @@ int ydc_destroy(ydc_context* c) {
     if (pd.ev) (void)hipEventDestroy(pd.ev);
   }
   if (c->h_in) (void)hipHostFree(c->h_in);
-  if (c->h_snap) (void)hipHostFree(c->h_snap);
   if (c->h_rel) (void)hipHostFree(c->h_rel);
   if (c->h_rel_ev) (void)hipEventDestroy(c->h_rel_ev);
   if (c->copy_ev) (void)hipEventDestroy(c->copy_ev);
@@ -1181,22 +1245,22 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   const uint32_t S = c->n_servants, kept = S - n, EW = c->env_words;
   auto& sm = c->stream_mode;
-  const bool leased = sm.active && sm.max_leases;
-  const bool alive = leased && sm.alive;
-  const bool inspect = leased && sm.inspect;
+  const bool leased = sm.active && sm.leased();
+  const bool alive = leased && sm.alive.on;
+  const bool inspect = leased && sm.inspect.on;
   // Everything that can fail for want of memory comes before the first launch: a removal is applied
   // to registry, leases, book and expiry column together or not at all.
   HIP_TRY(c, c->d_upd_idx.reserve(n));
   for (auto& b : c->d_spare) HIP_TRY(c, b.reserve(c->d_version.cap));
   if (alive) {
     if (int rc = alive_fit(c)) return rc;  // (rows the registry gained outside a tick: "never")
-    HIP_TRY(c, sm.d_alive_spare.reserve(sm.d_alive.cap));
+    HIP_TRY(c, sm.alive.spare.reserve(sm.alive.col.cap));
   }
   if (inspect) {
     // (rows the registry gained outside a tick: discovered at the last tick's clock)
     if (int rc = inspect_fit(c, sm.last_now == INT64_MIN ? 0 : sm.last_now)) return rc;
-    HIP_TRY(c, sm.d_insp_disc_spare.reserve(sm.d_insp_disc.cap));
-    HIP_TRY(c, sm.d_insp_ever_spare.reserve(sm.d_insp_ever.cap));
+    HIP_TRY(c, sm.inspect.disc_spare.reserve(sm.inspect.disc.cap));
+    HIP_TRY(c, sm.inspect.ever_spare.reserve(sm.inspect.ever.cap));
   }
   // Device: order-preserving compaction of the six resident columns into spare buffers,
   // which then take their place (running_tasks of the survivors never leaves the device).
@@ -1216,35 +1280,35 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
                        c->d_upd_idx.p, n);
   // ... and with aliveness the expiry column follows the registry's columns.
   if (alive)
-    hipLaunchKernelGGL(k_alive_compact, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, sm.d_alive.p,
-                       sm.d_alive_spare.p, c->d_upd_idx.p, n, S);
+    hipLaunchKernelGGL(k_alive_compact, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, sm.alive.col.p,
+                       sm.alive.spare.p, c->d_upd_idx.p, n, S);
   // ... and with inspection discovered_at and ever_assigned do.
   if (inspect)
-    hipLaunchKernelGGL(k_inspect_compact, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, sm.d_insp_disc.p,
-                       sm.d_insp_ever.p, sm.d_insp_disc_spare.p, sm.d_insp_ever_spare.p, c->d_upd_idx.p, n, S);
+    hipLaunchKernelGGL(k_inspect_compact, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, sm.inspect.disc.p,
+                       sm.inspect.ever.p, sm.inspect.disc_spare.p, sm.inspect.ever_spare.p, c->d_upd_idx.p, n, S);
   // ... and with a running-task book the entries of the removed rows (DropServant).
   const bool booked = leased && sm.max_book;
   if (booked) {
     const uint32_t tiles = ceil_div(sm.max_book, kBookTile);
-    HIP_TRY(c, hipMemsetAsync(sm.lb_book, 0, (size_t)tiles * 8, c->stream));
-    hipLaunchKernelGGL(k_book_remap, dim3(tiles), dim3(256), 0, c->stream, sm.bk, sm.bks, sm.max_book,
-                       c->d_upd_idx.p, n, sm.lb_book);
+    HIP_TRY(c, hipMemsetAsync(sm.book.lb, 0, (size_t)tiles * 8, c->stream));
+    hipLaunchKernelGGL(k_book_remap, dim3(tiles), dim3(256), 0, c->stream, sm.book.bk, sm.book.bks, sm.max_book,
+                       c->d_upd_idx.p, n, sm.book.lb);
   }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (idx is pageable; the swap below retires the old columns)
   if (leased) HIP_TRY(c, hipMemcpy(&sm.n_leases, &sm.ls->n_leases, 4, hipMemcpyDeviceToHost));
-  if (booked) HIP_TRY(c, hipMemcpy(&sm.n_book, &sm.bks->n_entries, 4, hipMemcpyDeviceToHost));
+  if (booked) HIP_TRY(c, hipMemcpy(&sm.book.n, &sm.book.bks->n_entries, 4, hipMemcpyDeviceToHost));
   DevBuf<uint32_t>* cols[6] = {&c->d_version, &c->d_nproc, &c->d_load, &c->d_max_tasks, &c->d_running,
                                &c->d_flags};
   for (int k = 0; k < 6; ++k) std::swap(*cols[k], c->d_spare[k]);
   if (alive) {
-    std::swap(sm.d_alive, sm.d_alive_spare);
-    sm.alive_n = kept;
+    std::swap(sm.alive.col, sm.alive.spare);
+    sm.alive.n = kept;
   }
   if (inspect) {
-    std::swap(sm.d_insp_disc, sm.d_insp_disc_spare);
-    std::swap(sm.d_insp_ever, sm.d_insp_ever_spare);
-    sm.inspect_n = kept;
+    std::swap(sm.inspect.disc, sm.inspect.disc_spare);
+    std::swap(sm.inspect.ever, sm.inspect.ever_spare);
+    sm.inspect.n = kept;
     sm.stale = true;  // (a captured step holds the count column's address)
   }
   // Host mirror.
@@ -4033,9 +4097,7 @@ void stream_drop_graphs(ydc_context::Stream& sm) {
 
 void stream_release(ydc_context::Stream& sm) {
   stream_drop_graphs(sm);
-  for (uint8_t* h : {sm.h_in, (uint8_t*)sm.h_out, sm.h_wres, sm.h_lres, sm.h_rres, sm.h_bres, (uint8_t*)sm.h_alive_list})
-    if (h) (void)hipHostFree(h);
-  sm = ydc_context::Stream{};  // (frees the device buffers: ydc_stream_end discards W)
+  sm = ydc_context::Stream{};  // (frees every buffer the stream owns: ydc_stream_end discards W)
 }
 
 void stream_release(ydc_context* c) { stream_release(c->stream_mode); }
@@ -4050,17 +4112,17 @@ size_t section(size_t* off, size_t bytes) {
 // Requests one streaming batch places: the new ones, behind W's region in waiting mode; the
 // expanded rows in rpc mode.
 uint32_t stream_batch_n(const ydc_context::Stream& sm) {
-  return sm.max_rows ? sm.max_rows : sm.max_tasks + sm.max_waiting;
+  return sm.rpc() ? sm.caps.max_rows : sm.caps.max_tasks + sm.caps.max_waiting;
 }
 
 // The tick's heartbeats and frees applied to the registry's device columns, from the arena as
 // `a` sees it (in place, or its device mirror).
 void enqueue_apply_tick(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
-  if (!(sm.max_upd + sm.max_rel)) return;
-  const uint32_t upd_blocks = ceil_div(sm.max_upd, 256);
-  hipLaunchKernelGGL(k_apply_tick, dim3(upd_blocks + ceil_div(sm.max_rel, 256)), dim3(256), 0, c->stream,
-                     a.upd_idx, (ServantRowDev*)a.upd_rows, sm.max_upd, upd_blocks, a.rel, sm.max_rel,
+  if (!(sm.caps.max_updates + sm.caps.max_releases)) return;
+  const uint32_t upd_blocks = ceil_div(sm.caps.max_updates, 256);
+  hipLaunchKernelGGL(k_apply_tick, dim3(upd_blocks + ceil_div(sm.caps.max_releases, 256)), dim3(256), 0, c->stream,
+                     a.upd_idx, (ServantRowDev*)a.upd_rows, sm.caps.max_updates, upd_blocks, a.rel, sm.caps.max_releases,
                      c->n_servants, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p, c->d_flags.p,
                      c->d_running.p);
 }
@@ -4071,17 +4133,17 @@ void enqueue_wait_gather(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
   const uint32_t N = stream_batch_n(sm);
   YDC_LAUNCH(c, "k_wait_gather", k_wait_gather, dim3(ceil_div(std::max(N, sm.lookback_n), 256)), dim3(256), 0,
-             c->stream, sm.wq, sm.wt, WaitNew{a.env, a.minv, a.ip, a.dl, a.tag, a.now}, sm.max_waiting, N, sm.ws,
-             sm.lookback, sm.max_leases ? 0u : sm.lookback_n,  // (with leases: k_lease_renew has cleared the words)
+             c->stream, sm.wq, sm.wt, WaitNew{a.env, a.minv, a.ip, a.dl, a.tag, a.now}, sm.caps.max_waiting, N, sm.ws,
+             sm.lookback, sm.leased() ? 0u : sm.lookback_n,  // (with leases: k_lease_renew has cleared the words)
              WaitExtra{sm.wl.w_for, sm.wl.t_for, sm.wl.t_for ? a.lexp : nullptr});
 }
 
 // RPC mode: W's entries and the new requests expanded into the batch's rows (rpc_stream.h).
 void enqueue_rpc_expand(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
-  const uint32_t P = sm.max_waiting + sm.max_tasks, NR = sm.max_rows;
+  const uint32_t P = sm.caps.max_waiting + sm.caps.max_tasks, NR = sm.caps.max_rows;
   YDC_LAUNCH(c, "k_rpc_scan", k_rpc_scan, dim3(ceil_div(P, kRpcTile)), dim3(256), 0, c->stream, sm.rw,
-             RpcNew{a.env, a.minv, a.ip, a.dl, a.tag, a.lexp, a.nimm, a.npre}, sm.rp, a.lh, sm.max_waiting, P, sm.ws,
+             RpcNew{a.env, a.minv, a.ip, a.dl, a.tag, a.lexp, a.nimm, a.npre}, sm.rp, a.lh, sm.caps.max_waiting, P, sm.ws,
              sm.rs, sm.lb_scan, sm.rb.row_start);
   YDC_LAUNCH(c, "k_rpc_expand", k_rpc_expand, dim3(ceil_div(NR, 256)), dim3(256), 0, c->stream, sm.rp, P, NR, sm.rb,
              sm.rs);
@@ -4089,7 +4151,7 @@ void enqueue_rpc_expand(ydc_context* c, const TickArena& a) {
 
 // The tick's batch columns in HBM, in the context's mode.
 void enqueue_stream_gather(ydc_context* c, const TickArena& a) {
-  if (c->stream_mode.max_rows) enqueue_rpc_expand(c, a);
+  if (c->stream_mode.rpc()) enqueue_rpc_expand(c, a);
   else enqueue_wait_gather(c, a);
 }
 
@@ -4099,7 +4161,7 @@ void enqueue_wait_compact(ydc_context* c, const int64_t* now, const DeviceParams
   auto& sm = c->stream_mode;
   const uint32_t N = stream_batch_n(sm);
   YDC_LAUNCH(c, "k_wait_compact", k_wait_compact, dim3(ceil_div(N, kWaitTile)), dim3(256), 0, c->stream, sm.wt,
-             sm.wt_out, now, sm.max_waiting, N, sm.wq, sm.ws, sm.lookback, sm.z_out, sm.z_res_tag,
+             sm.wt_out, now, sm.caps.max_waiting, N, sm.wq, sm.ws, sm.lookback, sm.z_out, sm.z_res_tag,
              sm.z_res_idx, sm.z_wout, prm, check_slot);
 }
 
@@ -4111,31 +4173,31 @@ LeaseIn lease_in(const TickArena& a) {
 // (lease_table.h), reading the tick from the arena as `a` sees it.
 void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
+  const ydc_stream_caps& k = sm.caps;
   const LeaseIn in = lease_in(a);
   const uint32_t S = c->n_servants;
-  const uint32_t ren_blocks = ceil_div(sm.max_renew, 256), rep_blocks = ceil_div(sm.max_rep, 256);
+  const uint32_t ren_blocks = ceil_div(k.max_renewals, 256), rep_blocks = ceil_div(k.max_reports, 256);
   // With aliveness: the heartbeats' expiries into E (servant_alive.h). Here for the reason the book's
   // pass is here: once per tick on every path.
-  if (sm.alive && sm.max_upd)
-    YDC_LAUNCH(c, "k_alive_beat", k_alive_beat, dim3(ceil_div(sm.max_upd, 256)), dim3(256), 0, c->stream, a.upd_idx,
-               a.upd_exp, sm.max_upd, std::min(S, sm.alive_n), sm.d_alive.p);
-  YDC_LAUNCH(c, "k_lease_renew", k_lease_renew, dim3(std::max(1u, ceil_div(std::max(sm.max_renew, sm.lookback_n), 256))),
-             dim3(256), 0, c->stream, sm.lt, sm.ls, in, sm.max_renew, sm.ren_slot, sm.z_renewed, sm.lookback,
+  if (sm.alive.on && k.max_updates)
+    YDC_LAUNCH(c, "k_alive_beat", k_alive_beat, dim3(ceil_div(k.max_updates, 256)), dim3(256), 0, c->stream, a.upd_idx,
+               a.upd_exp, k.max_updates, std::min(S, sm.alive.n), sm.alive.col.p);
+  YDC_LAUNCH(c, "k_lease_renew", k_lease_renew, dim3(std::max(1u, ceil_div(std::max(k.max_renewals, sm.lookback_n), 256))),
+             dim3(256), 0, c->stream, sm.lt, sm.ls, in, k.max_renewals, sm.ren_slot, sm.z_renewed, sm.lookback,
              sm.lookback_n);
-  if (sm.max_renew + sm.max_free)
-    YDC_LAUNCH(c, "k_lease_free", k_lease_free, dim3(ren_blocks + ceil_div(sm.max_free, 256)), dim3(256), 0, c->stream,
-               sm.lt, sm.ls, in, sm.max_renew, ren_blocks, sm.ren_slot, sm.max_free, S, c->d_running.p);
-  if (sm.max_rep)
-    YDC_LAUNCH(c, "k_lease_report", k_lease_report, dim3(rep_blocks + ceil_div(sm.max_rep_ids, 256)), dim3(256), 0,
-               c->stream, sm.lt, sm.ls, in, sm.max_rep, rep_blocks, sm.max_rep_ids, S, sm.d_rep_tick.p,
-               sm.z_unknown);
+  if (k.max_renewals + k.max_frees)
+    YDC_LAUNCH(c, "k_lease_free", k_lease_free, dim3(ren_blocks + ceil_div(k.max_frees, 256)), dim3(256), 0, c->stream,
+               sm.lt, sm.ls, in, k.max_renewals, ren_blocks, sm.ren_slot, k.max_frees, S, c->d_running.p);
+  if (k.max_reports)
+    YDC_LAUNCH(c, "k_lease_report", k_lease_report, dim3(rep_blocks + ceil_div(k.max_report_ids, 256)), dim3(256), 0,
+               c->stream, sm.lt, sm.ls, in, k.max_reports, rep_blocks, k.max_report_ids, S, sm.d_rep_tick.p, sm.z_unknown);
   // With a running-task book: the reports' permitted ids replace their servants' entries. Here and
   // nowhere else: this part of the step runs once per tick on every path, and the eager exits
   // place it no second time.
   if (sm.max_book)
-    YDC_LAUNCH(c, "k_book_commit", k_book_commit, dim3(ceil_div(sm.max_book + sm.max_rep_ids, kBookTile)), dim3(256),
-               0, c->stream, sm.bk, sm.bks, sm.max_book, in, a.bk_stid, a.bk_dkey, sm.max_rep, sm.max_rep_ids, S,
-               sm.d_rep_tick.p, sm.z_unknown, sm.lb_book, sm.z_bout);
+    YDC_LAUNCH(c, "k_book_commit", k_book_commit, dim3(ceil_div(sm.max_book + k.max_report_ids, kBookTile)), dim3(256),
+               0, c->stream, sm.book.bk, sm.book.bks, sm.max_book, in, a.bk_stid, a.bk_dkey, k.max_reports, k.max_report_ids,
+               S, sm.d_rep_tick.p, sm.z_unknown, sm.book.lb, sm.book.z_bout);
   YDC_LAUNCH(c, "k_lease_sweep", k_lease_sweep, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
              sm.lt, sm.ls, a.lh, S, sm.d_rep_tick.p, c->d_running.p);
 }
@@ -4144,22 +4206,22 @@ void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
 // placed batch's columns as the pass indexes them.
 InspectIn inspect_in(ydc_context* c, const uint32_t* env, const uint32_t* ip) {
   auto& sm = c->stream_mode;
-  return InspectIn{sm.d_insp_rec.p, sm.d_insp_pre.p, sm.d_insp_ever.p, std::min(sm.inspect_n, c->n_servants),
-                   env,             ip,              sm.rp.n_imm,      sm.max_rows ? sm.max_waiting + sm.max_tasks : 0};
+  return InspectIn{sm.d_insp_rec.p, sm.d_insp_pre.p, sm.inspect.ever.p, std::min(sm.inspect.n, c->n_servants),
+                   env,             ip,              sm.rp.n_imm,      sm.rpc() ? sm.caps.max_waiting + sm.caps.max_tasks : 0};
 }
 
 // ... and behind the batch: ids for the grants, their leases, the answers, the outcome block. prm:
 // gated on the batch having become final (the captured step); NULL: the host has just placed it.
 void enqueue_lease_grant(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
   auto& sm = c->stream_mode;
-  if (sm.inspect) {
-    YDC_LAUNCH(c, "k_lease_grant_inspect", k_lease_grant_inspect, dim3(ceil_div(sm.max_tasks, kLeaseTile)), dim3(256),
-               0, c->stream, sm.lt_out, sm.max_tasks, a.lexp, a.lh, sm.lt, sm.ls, sm.lookback, sm.z_out, sm.z_task_id,
+  if (sm.inspect.on) {
+    YDC_LAUNCH(c, "k_lease_grant_inspect", k_lease_grant_inspect, dim3(ceil_div(sm.caps.max_tasks, kLeaseTile)), dim3(256),
+               0, c->stream, sm.lt_out, sm.caps.max_tasks, a.lexp, a.lh, sm.lt, sm.ls, sm.lookback, sm.z_out, sm.z_task_id,
                sm.z_lout, prm, check_slot, inspect_in(c, a.env, a.ip));
     return;
   }
-  YDC_LAUNCH(c, "k_lease_grant", k_lease_grant, dim3(ceil_div(sm.max_tasks, kLeaseTile)), dim3(256), 0, c->stream,
-             sm.lt_out, sm.max_tasks, a.lexp, a.lh, sm.lt, sm.ls, sm.lookback, sm.z_out, sm.z_task_id, sm.z_lout,
+  YDC_LAUNCH(c, "k_lease_grant", k_lease_grant, dim3(ceil_div(sm.caps.max_tasks, kLeaseTile)), dim3(256), 0, c->stream,
+             sm.lt_out, sm.caps.max_tasks, a.lexp, a.lh, sm.lt, sm.ls, sm.lookback, sm.z_out, sm.z_task_id, sm.z_lout,
              prm, check_slot);
 }
 
@@ -4168,41 +4230,41 @@ void enqueue_lease_grant(ydc_context* c, const TickArena& a, const DeviceParams*
 void enqueue_wait_lease_commit(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
   auto& sm = c->stream_mode;
   const uint32_t N = stream_batch_n(sm);
-  if (sm.inspect) {
+  if (sm.inspect.on) {
     YDC_LAUNCH(c, "k_wait_lease_commit_inspect", k_wait_lease_commit_inspect, dim3(ceil_div(N, kWaitTile)), dim3(256),
-               0, c->stream, sm.wt, sm.wl, sm.wt_out, a.lh, sm.max_waiting, N, sm.wq, sm.ws, sm.lt, sm.ls, sm.lookback,
+               0, c->stream, sm.wt, sm.wl, sm.wt_out, a.lh, sm.caps.max_waiting, N, sm.wq, sm.ws, sm.lt, sm.ls, sm.lookback,
                sm.z_out, sm.z_task_id, sm.z_res_tag, sm.z_res_idx, sm.z_wout, sm.z_lout, prm, check_slot,
                inspect_in(c, sm.wt.env, sm.wt.ip));
     return;
   }
   YDC_LAUNCH(c, "k_wait_lease_commit", k_wait_lease_commit, dim3(ceil_div(N, kWaitTile)), dim3(256), 0, c->stream,
-             sm.wt, sm.wl, sm.wt_out, a.lh, sm.max_waiting, N, sm.wq, sm.ws, sm.lt, sm.ls, sm.lookback, sm.z_out,
+             sm.wt, sm.wl, sm.wt_out, a.lh, sm.caps.max_waiting, N, sm.wq, sm.ws, sm.lt, sm.ls, sm.lookback, sm.z_out,
              sm.z_task_id, sm.z_res_tag, sm.z_res_idx, sm.z_wout, sm.z_lout, prm, check_slot);
 }
 
 // RPC mode, behind the batch: ids and leases per granted row, then every RPC settled. prm as above.
 void enqueue_rpc_answer(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
   auto& sm = c->stream_mode;
-  const uint32_t P = sm.max_waiting + sm.max_tasks, NR = sm.max_rows;
-  if (sm.inspect)
+  const uint32_t P = sm.caps.max_waiting + sm.caps.max_tasks, NR = sm.caps.max_rows;
+  if (sm.inspect.on)
     YDC_LAUNCH(c, "k_rpc_grant_inspect", k_rpc_grant_inspect, dim3(ceil_div(NR, kRpcTile)), dim3(256), 0, c->stream,
-               sm.rb, NR, sm.max_waiting, a.lh, sm.lt, sm.ls, sm.rs, sm.lb_grant, sm.rz, prm, check_slot,
+               sm.rb, NR, sm.caps.max_waiting, a.lh, sm.lt, sm.ls, sm.rs, sm.lb_grant, sm.rz, prm, check_slot,
                inspect_in(c, sm.rb.env, sm.rb.ip));
   else
     YDC_LAUNCH(c, "k_rpc_grant", k_rpc_grant, dim3(ceil_div(NR, kRpcTile)), dim3(256), 0, c->stream, sm.rb, NR,
-               sm.max_waiting, a.lh, sm.lt, sm.ls, sm.rs, sm.lb_grant, sm.rz, prm, check_slot);
+               sm.caps.max_waiting, a.lh, sm.lt, sm.ls, sm.rs, sm.lb_grant, sm.rz, prm, check_slot);
   YDC_LAUNCH(c, "k_rpc_settle", k_rpc_settle, dim3(ceil_div(P, kRpcTile)), dim3(256), 0, c->stream, sm.rp, sm.rb,
-             sm.max_waiting, P, NR, a.lh, sm.rw, sm.ws, sm.rs, sm.ls, sm.lb_settle, sm.rz, sm.z_lout, prm,
+             sm.caps.max_waiting, P, NR, a.lh, sm.rw, sm.ws, sm.rs, sm.ls, sm.lb_settle, sm.rz, sm.z_lout, prm,
              check_slot);
 }
 
 // The kernel behind the batch that answers the caller in the context's mode (none: a plain one).
 void enqueue_stream_answer(ydc_context* c, const TickArena& a, const DeviceParams* prm, uint32_t check_slot) {
   auto& sm = c->stream_mode;
-  if (sm.max_rows) enqueue_rpc_answer(c, a, prm, check_slot);
-  else if (sm.max_waiting && sm.max_leases) enqueue_wait_lease_commit(c, a, prm, check_slot);
-  else if (sm.max_waiting) enqueue_wait_compact(c, a.now, prm, check_slot);
-  else if (sm.max_leases) enqueue_lease_grant(c, a, prm, check_slot);
+  if (sm.rpc()) enqueue_rpc_answer(c, a, prm, check_slot);
+  else if (sm.waiting() && sm.leased()) enqueue_wait_lease_commit(c, a, prm, check_slot);
+  else if (sm.waiting()) enqueue_wait_compact(c, a.now, prm, check_slot);
+  else if (sm.leased()) enqueue_lease_grant(c, a, prm, check_slot);
 }
 
 // The step itself, enqueued on the context's stream (inside a capture, or — stream_graph=0 — as it is).
@@ -4220,12 +4282,12 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
   // Leased mode: the lease kernels of the tick's renewals, frees, reports and expiry come first
   // (their decrements of running_tasks and k_apply_tick's commute); the placement stays in HBM
   // for k_lease_grant, which answers the caller.
-  const bool leased = sm.max_leases != 0;
+  const bool leased = sm.leased();
   if (leased) enqueue_lease_pre(c, sm.z);
   enqueue_apply_tick(c, sm.z);
   // Waiting mode: the batch is W's region and the new requests, gathered into HBM; its placement
   // stays there for k_wait_compact, which answers the caller.
-  const bool waiting = sm.max_waiting != 0;
+  const bool waiting = sm.waiting();
   if (waiting) enqueue_stream_gather(c, sm.z);
   ydc_task_soa d{sm.z.env, sm.z.minv, sm.z.ip};
   if (waiting) d = ydc_task_soa{sm.wt.env, sm.wt.minv, sm.wt.ip};
@@ -4271,7 +4333,7 @@ int stream_capture(ydc_context* c) {
   const bool was_profiling = c->profiling;
   c->profiling = false;  // no event pairs inside a capture
   // Sizes and workspace first (allocations and table uploads cannot be captured).
-  if (sm.max_leases && sm.d_rep_tick.cap < c->n_servants) {
+  if (sm.leased() && sm.d_rep_tick.cap < c->n_servants) {
     // (a tick number is never 0, and a servant's stamp matters within its tick only)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, sm.d_rep_tick.reserve((size_t)c->n_servants + 1024));
@@ -4344,35 +4406,72 @@ struct RpcTick {
   uint32_t* out_n_waiting_rows;
 };
 
-// Capacities of a leased context (ydc_stream_begin_leased).
-struct LeaseCaps {
-  uint32_t max_leases, max_renew, max_free, max_rep, max_rep_ids;
+// What a tick brings, whichever entry point took it: the heartbeats (with their environment masks
+// in the wide form), the releases, the requests, where the placement goes, and the mode's own
+// arguments (NULL: not a tick of that mode).
+struct StreamCall {
+  const uint32_t* upd_idx;
+  const ydc_servant_row* upd_rows;
+  const uint64_t* upd_env_masks;
+  uint32_t env_words, n_upd;
+  const uint32_t* rel;
+  uint32_t n_rel;
+  const ydc_task_soa* tasks;
+  uint32_t n_tasks;
+  uint32_t* out_servant_idx;
+  const WaitTick* wt;
+  const LeaseTick* lt;
+  const RpcTick* rt;
 };
 
-// The limits of a stream's capacities; `code`: what going beyond them is to the caller.
-int stream_caps_check(ydc_context* c, int code, uint32_t max_tasks, uint32_t max_waiting, const LeaseCaps* lc,
-                      uint32_t max_rows, uint32_t max_book = 0) {
+// The limits of a stream's bounds; `code`: what going beyond them is to the caller.
+int stream_caps_check(ydc_context* c, int code, const ydc_stream_caps& k, uint32_t max_book) {
   // (the book's pass is over max_book + max_report_ids positions, one 31-bit count)
-  if (max_book && (!lc || max_book > (1u << 30) || (uint64_t)max_book + lc->max_rep_ids > 0x7FFFFFFFull))
+  if (max_book && (!k.max_leases || max_book > (1u << 30) || (uint64_t)max_book + k.max_report_ids > 0x7FFFFFFFull))
     return fail(c, code, "max_book %u out of range (1 .. 2^30, max_book + max_report_ids < 2^31)", max_book);
   // (rpc mode: max_tasks is max_requests, the batch is the max_rows expanded rows)
-  if (max_rows && (max_rows > (1u << 30) || max_rows < max_tasks))
-    return fail(c, code, "max_rows %u out of range (max_requests %u .. 2^30)", max_rows, max_tasks);
-  if (lc && (!lc->max_leases || lc->max_leases > (1u << 30) || lc->max_rep_ids > 0x7FFFFFFFu))
-    return fail(c, code, "max_leases %u out of range (1 .. 2^30)", lc->max_leases);
-  if ((uint64_t)max_tasks + max_waiting > 0x7FFFFFFFull)
-    return fail(c, code, "max_tasks %u + max_waiting %u too large", max_tasks, max_waiting);
+  if (k.max_rows && (k.max_rows > (1u << 30) || k.max_rows < k.max_tasks))
+    return fail(c, code, "max_rows %u out of range (max_requests %u .. 2^30)", k.max_rows, k.max_tasks);
+  if (k.max_leases && (k.max_leases > (1u << 30) || k.max_report_ids > 0x7FFFFFFFu))
+    return fail(c, code, "max_leases %u out of range (1 .. 2^30)", k.max_leases);
+  if ((uint64_t)k.max_tasks + k.max_waiting > 0x7FFFFFFFull)
+    return fail(c, code, "max_tasks %u + max_waiting %u too large", k.max_tasks, k.max_waiting);
   return YDC_OK;
 }
 
-// Layout and allocation of everything a stream of these capacities has, into `sm` (released, or
+// The record's bounds, listed once, in the order the snapshot codec numbers them (snap::Cap).
+constexpr uint32_t ydc_stream_caps::*kCapFields[snap::kCaps] = {
+    &ydc_stream_caps::max_updates, &ydc_stream_caps::max_releases, &ydc_stream_caps::max_tasks,
+    &ydc_stream_caps::max_rows,    &ydc_stream_caps::max_waiting,  &ydc_stream_caps::max_leases,
+    &ydc_stream_caps::max_renewals, &ydc_stream_caps::max_frees,   &ydc_stream_caps::max_reports,
+    &ydc_stream_caps::max_report_ids};
+
+// `have` grown to what `want` asks for: no bound shrinks.
+ydc_stream_caps stream_caps_grown(const ydc_stream_caps& have, const ydc_stream_caps& want) {
+  ydc_stream_caps k{};
+  for (auto f : kCapFields) k.*f = std::max(have.*f, want.*f);
+  return k;
+}
+
+// The mode of a stream is fixed: what `want` asks of a part that a stream with the bounds `have`
+// was begun without, or NULL.
+const char* stream_caps_foreign(const ydc_stream_caps& have, const ydc_stream_caps& want) {
+  if (!have.max_waiting && want.max_waiting) return "max_waiting for a stream without a waiting queue";
+  if (!have.max_leases &&
+      (want.max_leases | want.max_renewals | want.max_frees | want.max_reports | want.max_report_ids))
+    return "lease capacities for a stream without a lease table";
+  if (!have.max_rows && want.max_rows) return "max_rows for a stream that is not an rpc stream";
+  return nullptr;
+}
+
+// Layout and allocation of everything a stream of these bounds has, into `sm` (released, or
 // fresh). Its contents are not defined before stream_reset; after a failure the caller releases it.
-int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, uint32_t max_releases,
-                 uint32_t max_tasks, uint32_t max_waiting, const LeaseCaps* lc, uint32_t max_rows,
-                 uint32_t max_book = 0) {
-  sm.max_upd = max_updates;
-  sm.max_rel = max_releases;
-  sm.max_tasks = max_tasks;
+int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps& k, uint32_t max_book) {
+  sm.caps = k;
+  sm.max_book = max_book;
+  const uint32_t max_updates = k.max_updates, max_releases = k.max_releases, max_tasks = k.max_tasks;
+  const uint32_t max_waiting = k.max_waiting, max_rows = k.max_rows;
+  const bool leased = sm.leased();
   // Arena layout (256 B aligned sections); waiting mode adds the new requests' deadlines and tags,
   // and the tick's clock.
   size_t off = 0;
@@ -4386,27 +4485,27 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
   const size_t o_tag = max_waiting ? section(&off, (size_t)max_tasks * 8) : 0;
   const size_t o_now = max_waiting ? section(&off, 8) : 0;
   // ... leased mode the requests' expiries, renewals, frees by id, reports (CSR) and the scalars.
-  const size_t o_lexp = lc ? section(&off, (size_t)max_tasks * 8) : 0;
-  const size_t o_ren_id = lc ? section(&off, (size_t)lc->max_renew * 8) : 0;
-  const size_t o_ren_exp = lc ? section(&off, (size_t)lc->max_renew * 8) : 0;
-  const size_t o_free_id = lc ? section(&off, (size_t)lc->max_free * 8) : 0;
-  const size_t o_rep_srv = lc ? section(&off, (size_t)lc->max_rep * 4) : 0;
-  const size_t o_rep_off = lc ? section(&off, ((size_t)lc->max_rep + 1) * 4) : 0;
-  const size_t o_rep_id = lc ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
-  const size_t o_lh = lc ? section(&off, sizeof(LeaseHdr)) : 0;
+  const size_t o_lexp = leased ? section(&off, (size_t)max_tasks * 8) : 0;
+  const size_t o_ren_id = leased ? section(&off, (size_t)k.max_renewals * 8) : 0;
+  const size_t o_ren_exp = leased ? section(&off, (size_t)k.max_renewals * 8) : 0;
+  const size_t o_free_id = leased ? section(&off, (size_t)k.max_frees * 8) : 0;
+  const size_t o_rep_srv = leased ? section(&off, (size_t)k.max_reports * 4) : 0;
+  const size_t o_rep_off = leased ? section(&off, ((size_t)k.max_reports + 1) * 4) : 0;
+  const size_t o_rep_id = leased ? section(&off, (size_t)k.max_report_ids * 8) : 0;
+  const size_t o_lh = leased ? section(&off, sizeof(LeaseHdr)) : 0;
   const size_t o_nimm = max_rows ? section(&off, (size_t)max_tasks * 4) : 0;
   const size_t o_npre = max_rows ? section(&off, (size_t)max_tasks * 4) : 0;
   // ... a running-task book the reports' two payload columns.
-  const size_t o_bstid = max_book ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
-  const size_t o_bdkey = max_book ? section(&off, (size_t)lc->max_rep_ids * 8) : 0;
+  const size_t o_bstid = max_book ? section(&off, (size_t)k.max_report_ids * 8) : 0;
+  const size_t o_bdkey = max_book ? section(&off, (size_t)k.max_report_ids * 8) : 0;
   // ... and, last (no other section moves), the heartbeats' expiries of a leased stream.
-  const size_t o_uexp = lc ? section(&off, (size_t)max_updates * 8) : 0;
+  const size_t o_uexp = leased ? section(&off, (size_t)max_updates * 8) : 0;
   auto arena_at = [&](uint8_t* b) {
     TickArena a{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
                 (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
                 max_waiting ? (int64_t*)(b + o_dl) : nullptr, max_waiting ? (uint64_t*)(b + o_tag) : nullptr,
                 max_waiting ? (int64_t*)(b + o_now) : nullptr};
-    if (lc) {
+    if (leased) {
       a.lexp = (int64_t*)(b + o_lexp);
       a.ren_id = (unsigned long long*)(b + o_ren_id);
       a.ren_exp = (int64_t*)(b + o_ren_exp);
@@ -4428,20 +4527,17 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     return a;
   };
   sm.in_bytes = off;
-  HIP_TRY(c, hipHostMalloc((void**)&sm.h_in, sm.in_bytes, hipHostMallocCoherent | hipHostMallocMapped));
+  HIP_TRY(c, sm.h_in.reserve(sm.in_bytes));
   const size_t n_out = max_rows ? max_rows : max_tasks;  // answers per tick (rpc mode: one per row)
-  HIP_TRY(c, hipHostMalloc((void**)&sm.h_out, std::max<size_t>(n_out * 4, 16),
-                           hipHostMallocCoherent | hipHostMallocMapped));
-  uint8_t* z_in = nullptr;
-  HIP_TRY(c, hipHostGetDevicePointer((void**)&z_in, sm.h_in, 0));
-  HIP_TRY(c, hipHostGetDevicePointer((void**)&sm.z_out, sm.h_out, 0));
+  HIP_TRY(c, sm.h_place.reserve(n_out * 4));
+  sm.h_out = (uint32_t*)sm.h_place.p;
+  sm.z_out = (uint32_t*)sm.h_place.z;
   HIP_TRY(c, sm.d_in.reserve(sm.in_bytes));
-  sm.h = arena_at(sm.h_in);
+  sm.h = arena_at(sm.h_in.p);
   sm.d = arena_at(sm.d_in.p);
-  sm.z = arena_at(z_in);
+  sm.z = arena_at(sm.h_in.z);
   HIP_TRY(c, c->d_out_idx.reserve(max_tasks));
   if (max_waiting) {
-    sm.max_waiting = max_waiting;
     // HBM: W (max_waiting entries), the tick's batch (max_waiting + max_tasks) with its placement,
     // the queue's counters and k_wait_compact's look-back words.
     const size_t NB = max_rows ? (size_t)max_rows : (size_t)max_tasks + max_waiting;
@@ -4453,10 +4549,10 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     const size_t o_wt[5] = {wsec(NB * 4), wsec(NB * 4), wsec(NB * 4), wsec(NB * 8), wsec(NB * 8)};
     const size_t o_wout = wsec(NB * 4), o_ws = wsec(sizeof(WaitState)), o_lb = wsec((size_t)sm.lookback_n * 8);
     // ... with leases: W's sixth column and the batch's, the lease durations (wait_lease.h).
-    const size_t o_wfor = lc ? wsec(max_waiting * 8ull) : 0, o_tfor = lc ? wsec(NB * 8) : 0;
+    const size_t o_wfor = leased ? wsec(max_waiting * 8ull) : 0, o_tfor = leased ? wsec(NB * 8) : 0;
     HIP_TRY(c, sm.d_wait.reserve(w_off));
     uint8_t* b = sm.d_wait.p;
-    if (lc) sm.wl = WaitLeaseCols{(int64_t*)(b + o_wfor), (int64_t*)(b + o_tfor), nullptr};
+    if (leased) sm.wl = WaitLeaseCols{(int64_t*)(b + o_wfor), (int64_t*)(b + o_tfor), nullptr};
     sm.wq = WaitCols{(uint32_t*)(b + o_wq[0]), (uint32_t*)(b + o_wq[1]), (uint32_t*)(b + o_wq[2]),
                      (int64_t*)(b + o_wq[3]), (uint64_t*)(b + o_wq[4])};
     sm.wt = WaitCols{(uint32_t*)(b + o_wt[0]), (uint32_t*)(b + o_wt[1]), (uint32_t*)(b + o_wt[2]),
@@ -4468,43 +4564,37 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     size_t r_off = 0;
     const size_t r_tag = section(&r_off, (size_t)max_waiting * 8), r_idx = section(&r_off, (size_t)max_waiting * 4);
     const size_t r_out = section(&r_off, sizeof(WaitOutcome));
-    const size_t r_id = lc ? section(&r_off, (size_t)max_waiting * 8) : 0;  // (with leases: the resolved ids)
-    HIP_TRY(c, hipHostMalloc((void**)&sm.h_wres, r_off, hipHostMallocCoherent | hipHostMallocMapped));
-    uint8_t* z_res = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&z_res, sm.h_wres, 0));
-    if (lc) {
-      sm.h_res_id = (unsigned long long*)(sm.h_wres + r_id);
+    const size_t r_id = leased ? section(&r_off, (size_t)max_waiting * 8) : 0;  // (with leases: the resolved ids)
+    HIP_TRY(c, sm.h_wres.reserve(r_off));
+    uint8_t *h_res = sm.h_wres.p, *z_res = sm.h_wres.z;
+    if (leased) {
+      sm.h_res_id = (unsigned long long*)(h_res + r_id);
       sm.wl.res_id = (unsigned long long*)(z_res + r_id);
     }
-    sm.h_res_tag = (uint64_t*)(sm.h_wres + r_tag);
-    sm.h_res_idx = (uint32_t*)(sm.h_wres + r_idx);
-    sm.h_wout = (WaitOutcome*)(sm.h_wres + r_out);
+    sm.h_res_tag = (uint64_t*)(h_res + r_tag);
+    sm.h_res_idx = (uint32_t*)(h_res + r_idx);
+    sm.h_wout = (WaitOutcome*)(h_res + r_out);
     sm.z_res_tag = (uint64_t*)(z_res + r_tag);
     sm.z_res_idx = (uint32_t*)(z_res + r_idx);
     sm.z_wout = (WaitOutcome*)(z_res + r_out);
   }
-  if (lc) {
-    sm.max_leases = lc->max_leases;
-    sm.max_renew = lc->max_renew;
-    sm.max_free = lc->max_free;
-    sm.max_rep = lc->max_rep;
-    sm.max_rep_ids = lc->max_rep_ids;
+  if (leased) {
     // HBM: the table (cap = 2^k >= 2 * max_leases slots, five columns), its bookkeeping, the
     // renewals' slots, the placement of the tick's batch and k_lease_grant's look-back words.
     size_t cap = 1024;
     uint32_t cap_bits = 10;
-    while (cap < 2 * (size_t)lc->max_leases) cap <<= 1, ++cap_bits;
+    while (cap < 2 * (size_t)k.max_leases) cap <<= 1, ++cap_bits;
     // (with a waiting queue: two words per tile of the whole batch, wait_lease.h)
     sm.lookback_n = max_waiting ? 2 * ceil_div(max_tasks + max_waiting, kWaitTile) : ceil_div(max_tasks, kLeaseTile);
     // (rpc mode: the scan's and the settling's words per tile of positions, the grants' per tile of rows)
     if (max_rows) sm.lookback_n = 2 * ceil_div(max_tasks + max_waiting, kRpcTile) + ceil_div(max_rows, kRpcTile);
     // (a running-task book: one word per tile of its pass, behind the others; k_lease_renew clears them all)
     const uint32_t lb_own = sm.lookback_n;
-    if (max_book) sm.lookback_n += ceil_div(max_book + lc->max_rep_ids, kBookTile);
+    if (max_book) sm.lookback_n += ceil_div(max_book + k.max_report_ids, kBookTile);
     size_t l_off = 0;
     auto lsec = [&](size_t bytes) { return section(&l_off, bytes); };
     const size_t o_key = lsec(cap * 8), o_exp = lsec(cap * 8), o_srv = lsec(cap * 4), o_st = lsec(cap * 4);
-    const size_t o_win = lsec(cap * 4), o_ls = lsec(sizeof(LeaseState)), o_rs = lsec((size_t)lc->max_renew * 4);
+    const size_t o_win = lsec(cap * 4), o_ls = lsec(sizeof(LeaseState)), o_rs = lsec((size_t)k.max_renewals * 4);
     const size_t o_out = lsec((size_t)max_tasks * 4), o_lb = lsec((size_t)sm.lookback_n * 8);
     HIP_TRY(c, sm.d_lease.reserve(l_off));
     uint8_t* b = sm.d_lease.p;
@@ -4514,25 +4604,23 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     sm.ren_slot = (uint32_t*)(b + o_rs);
     sm.lt_out = (uint32_t*)(b + o_out);
     sm.lookback = (unsigned long long*)(b + o_lb);
-    sm.lb_book = max_book ? sm.lookback + lb_own : nullptr;
+    sm.book.lb = max_book ? sm.lookback + lb_own : nullptr;
     // Page-locked results: task ids | renewed | report_unknown | outcome block.
     size_t r_off = 0;
-    const size_t r_id = section(&r_off, n_out * 8), r_ren = section(&r_off, lc->max_renew);
-    const size_t r_unk = section(&r_off, lc->max_rep_ids), r_out = section(&r_off, sizeof(LeaseOutcome));
-    HIP_TRY(c, hipHostMalloc((void**)&sm.h_lres, r_off, hipHostMallocCoherent | hipHostMallocMapped));
-    uint8_t* z_res = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&z_res, sm.h_lres, 0));
-    sm.h_task_id = (unsigned long long*)(sm.h_lres + r_id);
-    sm.h_renewed = sm.h_lres + r_ren;
-    sm.h_unknown = sm.h_lres + r_unk;
-    sm.h_lout = (LeaseOutcome*)(sm.h_lres + r_out);
+    const size_t r_id = section(&r_off, n_out * 8), r_ren = section(&r_off, k.max_renewals);
+    const size_t r_unk = section(&r_off, k.max_report_ids), r_out = section(&r_off, sizeof(LeaseOutcome));
+    HIP_TRY(c, sm.h_lres.reserve(r_off));
+    uint8_t *h_res = sm.h_lres.p, *z_res = sm.h_lres.z;
+    sm.h_task_id = (unsigned long long*)(h_res + r_id);
+    sm.h_renewed = h_res + r_ren;
+    sm.h_unknown = h_res + r_unk;
+    sm.h_lout = (LeaseOutcome*)(h_res + r_out);
     sm.z_task_id = (unsigned long long*)(z_res + r_id);
     sm.z_renewed = z_res + r_ren;
     sm.z_unknown = z_res + r_unk;
     sm.z_lout = (LeaseOutcome*)(z_res + r_out);
   }
   if (max_rows) {
-    sm.max_rows = max_rows;
     const size_t MW = max_waiting, P = MW + max_tasks, NR = max_rows;
     const uint32_t tiles_p = ceil_div((uint32_t)P, kRpcTile);
     sm.lb_scan = sm.lookback;
@@ -4562,34 +4650,29 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
     const size_t r_st = rsec((size_t)max_tasks * 4), r_ng = rsec((size_t)max_tasks * 4);
     const size_t r_tag = rsec(MW * 8), r_rs = rsec(MW * 4), r_rn = rsec(MW * 4), r_rf = rsec(MW * 4);
     const size_t r_srv = rsec(NR * 4), r_id = rsec(NR * 8), r_out = rsec(sizeof(RpcOutcome));
-    HIP_TRY(c, hipHostMalloc((void**)&sm.h_rres, r_off, hipHostMallocCoherent | hipHostMallocMapped));
-    uint8_t* z = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&z, sm.h_rres, 0));
+    HIP_TRY(c, sm.h_rres.reserve(r_off));
     auto out_at = [&](uint8_t* q, uint32_t* srv, unsigned long long* id) {
       return RpcOut{srv, id, (uint32_t*)(q + r_st), (uint32_t*)(q + r_ng), (uint64_t*)(q + r_tag),
                     (uint32_t*)(q + r_rs), (uint32_t*)(q + r_rn), (uint32_t*)(q + r_rf), (uint32_t*)(q + r_srv),
                     (unsigned long long*)(q + r_id), (RpcOutcome*)(q + r_out)};
     };
-    sm.rh = out_at(sm.h_rres, sm.h_out, sm.h_task_id);
-    sm.rz = out_at(z, sm.z_out, sm.z_task_id);
+    sm.rh = out_at(sm.h_rres.p, sm.h_out, sm.h_task_id);
+    sm.rz = out_at(sm.h_rres.z, sm.z_out, sm.z_task_id);
   }
   if (max_book) {
-    sm.max_book = max_book;
     // HBM: B's four columns and its bookkeeping. Page-locked: the outcome block.
     size_t b_off = 0;
     auto bsec = [&](size_t bytes) { return section(&b_off, bytes); };
     const size_t o_srv = bsec((size_t)max_book * 4), o_gr = bsec((size_t)max_book * 8);
     const size_t o_st = bsec((size_t)max_book * 8), o_dk = bsec((size_t)max_book * 8), o_bs = bsec(sizeof(BookState));
-    HIP_TRY(c, sm.d_book.reserve(b_off));
-    uint8_t* b = sm.d_book.p;
-    sm.bk = BookCols{(uint32_t*)(b + o_srv), (unsigned long long*)(b + o_gr), (unsigned long long*)(b + o_st),
+    HIP_TRY(c, sm.book.d.reserve(b_off));
+    uint8_t* b = sm.book.d.p;
+    sm.book.bk = BookCols{(uint32_t*)(b + o_srv), (unsigned long long*)(b + o_gr), (unsigned long long*)(b + o_st),
                      (unsigned long long*)(b + o_dk)};
-    sm.bks = (BookState*)(b + o_bs);
-    HIP_TRY(c, hipHostMalloc((void**)&sm.h_bres, 256, hipHostMallocCoherent | hipHostMallocMapped));
-    uint8_t* z = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&z, sm.h_bres, 0));
-    sm.h_bout = (BookOutcome*)sm.h_bres;
-    sm.z_bout = (BookOutcome*)z;
+    sm.book.bks = (BookState*)(b + o_bs);
+    HIP_TRY(c, sm.book.h_res.reserve(256));
+    sm.book.h_bout = (BookOutcome*)sm.book.h_res.p;
+    sm.book.z_bout = (BookOutcome*)sm.book.h_res.z;
   }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
   sm.stale = true;
@@ -4600,39 +4683,59 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, uint32_t max_updates, 
 // empty with next_id 0 (the reference's next_task_id{}), the rpc columns and every outcome block
 // cleared.
 int stream_reset(ydc_context* c, ydc_context::Stream& sm) {
-  if (sm.max_waiting) {
+  if (sm.waiting()) {
     HIP_TRY(c, hipMemsetAsync(sm.ws, 0, sizeof(WaitState), c->stream));
     std::memset(sm.h_wout, 0, sizeof(WaitOutcome));
   }
-  if (sm.max_leases) {
+  if (sm.leased()) {
     HIP_TRY(c, hipMemsetAsync(sm.d_lease.p, 0, sm.d_lease.cap, c->stream));
     HIP_TRY(c, hipMemsetAsync(sm.lt.key, 0xFF, ((size_t)sm.lt.mask + 1) * 8, c->stream));
     std::memset(sm.h_lout, 0, sizeof(LeaseOutcome));
   }
-  if (sm.max_rows) {
+  if (sm.rpc()) {
     HIP_TRY(c, hipMemsetAsync(sm.d_rpc.p, 0, sm.d_rpc.cap, c->stream));
     std::memset(sm.rh.outcome, 0, sizeof(RpcOutcome));
   }
   if (sm.max_book) {  // (B empty, the ticket 0)
-    HIP_TRY(c, hipMemsetAsync(sm.bks, 0, sizeof(BookState), c->stream));
-    std::memset(sm.h_bout, 0, sizeof(BookOutcome));
-    sm.n_book = 0;
+    HIP_TRY(c, hipMemsetAsync(sm.book.bks, 0, sizeof(BookState), c->stream));
+    std::memset(sm.book.h_bout, 0, sizeof(BookOutcome));
+    sm.book.n = 0;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   sm.active = true;
   return YDC_OK;
 }
 
+// The columns of W and of B as the open stream holds them, listed once: device address (NULL: the
+// mode has no such column) and width in bytes. Both are compact between ticks (k_wait_compact /
+// k_rpc_settle and k_book_commit leave them packed), so whoever carries them copies entries [0, n) of
+// every column as they lie. The order is the snapshot's; the other side of a pairing lists the same.
+struct StateCol {
+  void* p;
+  size_t width;
+};
+constexpr size_t kWCols = 8, kBCols = 4;
+std::array<StateCol, kWCols> w_cols(const ydc_context::Stream& sm) {
+  return {{{sm.wq.deadline, 8}, {sm.wq.tag, 8}, {sm.wl.w_for, 8} /* with leases */, {sm.wq.env, 4}, {sm.wq.minv, 4},
+           {sm.wq.ip, 4}, {sm.rw.n_imm, 4} /* rpc mode */, {sm.rw.n_pre, 4}}};
+}
+std::array<StateCol, kBCols> b_cols(const ydc_context::Stream& sm) {
+  return {{{sm.book.bk.grant, 8}, {sm.book.bk.stid, 8}, {sm.book.bk.dkey, 8}, {sm.book.bk.servant, 4}}};
+}
+std::array<const uint8_t*, kWCols> w_cols(const snap::View& v) {
+  return {{v.w_deadline, v.w_tag, v.w_for, v.w_env, v.w_minv, v.w_ip, v.w_nimm, v.w_npre}};
+}
+std::array<const uint8_t*, kBCols> b_cols(const snap::View& v) { return {{v.b_grant, v.b_stid, v.b_dkey, v.b_srv}}; }
+
 // ydc_stream_reserve: what the next tick can observe of the stream `o`, carried into the freshly
 // reset, larger `n`. L is filed again slot by slot (k_lease_rehash: the new table has other home
-// slots); W is compact between ticks (k_wait_compact / k_rpc_settle leave it packed), so entries
-// [0, |W|) of every column are copied as they lie; of the small state blocks only |W| and next_id
+// slots); W and B are copied as they lie; of the small state blocks only |W|, |B| and next_id
 // outlive a tick (tickets, snapshots and the tick's counters are cleared by the tick that uses
-// them). Nothing of `o` is written.
+// them). Nothing of `o` is written: what simply moves to `n` is stream_regrow's.
 int stream_migrate(ydc_context* c, const ydc_context::Stream& o, ydc_context::Stream& n) {
   hipStream_t st = c->stream;
   LeaseState ls_old{}, ls_new{};
-  if (o.max_leases && o.inspect) {
+  if (o.leased() && o.inspect.on) {
     // With inspection: the detail records move with their leases into columns of the new table's size.
     const size_t slots = (size_t)n.lt.mask + 1;
     HIP_TRY(c, n.d_insp_rec.reserve(slots));
@@ -4640,44 +4743,33 @@ int stream_migrate(ydc_context* c, const ydc_context::Stream& o, ydc_context::St
     YDC_LAUNCH(c, "k_inspect_rehash", k_inspect_rehash, dim3(ceil_div(o.lt.mask + 1, 256)), dim3(256), 0, st, o.lt, o.ls,
                o.d_insp_rec.p, o.d_insp_pre.p, n.lt, n.ls, n.d_insp_rec.p, n.d_insp_pre.p);
     HIP_TRY(c, hipGetLastError());
-  } else if (o.max_leases) {
+  } else if (o.leased()) {
     YDC_LAUNCH(c, "k_lease_rehash", k_lease_rehash, dim3(ceil_div(o.lt.mask + 1, kLeaseTile)), dim3(256), 0, st,
                o.lt, o.ls, n.lt, n.ls);
     HIP_TRY(c, hipGetLastError());
   }
-  if (o.max_waiting) {
+  if (o.waiting()) {
     uint32_t cnt = 0;
     HIP_TRY(c, hipMemcpy(&cnt, &o.ws->count, 4, hipMemcpyDeviceToHost));
-    if (cnt > o.max_waiting)
-      return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u > max_waiting %u", cnt, o.max_waiting);
-    auto carry = [&](void* dst, const void* src, size_t width) {
-      return cnt && src ? hipMemcpyAsync(dst, src, cnt * width, hipMemcpyDeviceToDevice, st) : hipSuccess;
-    };
-    HIP_TRY(c, carry(n.wq.env, o.wq.env, 4));
-    HIP_TRY(c, carry(n.wq.minv, o.wq.minv, 4));
-    HIP_TRY(c, carry(n.wq.ip, o.wq.ip, 4));
-    HIP_TRY(c, carry(n.wq.deadline, o.wq.deadline, 8));
-    HIP_TRY(c, carry(n.wq.tag, o.wq.tag, 8));
-    HIP_TRY(c, carry(n.wl.w_for, o.wl.w_for, 8));  // (with leases)
-    HIP_TRY(c, carry(n.rw.n_imm, o.rw.n_imm, 4));  // (rpc mode)
-    HIP_TRY(c, carry(n.rw.n_pre, o.rw.n_pre, 4));
+    if (cnt > o.caps.max_waiting)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u > max_waiting %u", cnt, o.caps.max_waiting);
+    const auto from = w_cols(o), to = w_cols(n);
+    for (size_t k = 0; k < kWCols; ++k)
+      if (cnt && from[k].p)
+        HIP_TRY(c, hipMemcpyAsync(to[k].p, from[k].p, cnt * from[k].width, hipMemcpyDeviceToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(&n.ws->count, &o.ws->count, 4, hipMemcpyDeviceToDevice, st));
   }
   if (o.max_book && n.max_book) {
-    // B is compact between ticks: entries [0, |B|) of its columns as they lie, and |B|.
-    if (o.n_book > n.max_book)
-      return fail(c, YDC_ERR_NOT_CONVERGED, "running-task book of %u > max_book %u", o.n_book, n.max_book);
-    auto carry = [&](void* dst, const void* src, size_t width) {
-      return o.n_book ? hipMemcpyAsync(dst, src, o.n_book * width, hipMemcpyDeviceToDevice, st) : hipSuccess;
-    };
-    HIP_TRY(c, carry(n.bk.servant, o.bk.servant, 4));
-    HIP_TRY(c, carry(n.bk.grant, o.bk.grant, 8));
-    HIP_TRY(c, carry(n.bk.stid, o.bk.stid, 8));
-    HIP_TRY(c, carry(n.bk.dkey, o.bk.dkey, 8));
-    HIP_TRY(c, hipMemcpyAsync(&n.bks->n_entries, &o.bks->n_entries, 4, hipMemcpyDeviceToDevice, st));
+    if (o.book.n > n.max_book)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "running-task book of %u > max_book %u", o.book.n, n.max_book);
+    const auto from = b_cols(o), to = b_cols(n);
+    for (size_t k = 0; o.book.n && k < kBCols; ++k)
+      HIP_TRY(c, hipMemcpyAsync(to[k].p, from[k].p, o.book.n * from[k].width, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(&n.book.bks->n_entries, &o.book.bks->n_entries, 4, hipMemcpyDeviceToDevice, st));
+    n.book.n = o.book.n;
   }
   HIP_TRY(c, hipStreamSynchronize(st));
-  if (o.max_leases) {
+  if (o.leased()) {
     HIP_TRY(c, hipMemcpy(&ls_old, o.ls, sizeof ls_old, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(&ls_new, n.ls, sizeof ls_new, hipMemcpyDeviceToHost));
     if (ls_new.n_leases != ls_old.n_leases || ls_new.next_id != ls_old.next_id)
@@ -4691,270 +4783,23 @@ int stream_migrate(ydc_context* c, const ydc_context::Stream& o, ydc_context::St
   n.n_leases = o.n_leases;
   n.last_now = o.last_now;
   n.lease_tick = o.lease_tick;
-  n.rep_seen = o.rep_seen;
-  n.rep_mark = o.rep_mark;
+  n.rep_once = o.rep_once;
   n.want_passes = o.want_passes;
-  if (o.max_book && n.max_book) {
-    n.n_book = o.n_book;
-    n.book_staged = o.book_staged;
-    n.stage_stid = o.stage_stid;
-    n.stage_dkey = o.stage_dkey;
-  }
   return YDC_OK;
 }
 
-int stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
-                 uint32_t max_waiting, const LeaseCaps* lc = nullptr, uint32_t max_rows = 0) {
-  if (!c || !max_tasks) return YDC_ERR_INVALID_ARGUMENT;
-  if (int rc = stream_caps_check(c, YDC_ERR_CAPACITY, max_tasks, max_waiting, lc, max_rows)) return rc;
+int stream_begin(ydc_context* c, const ydc_stream_caps& k) {
+  if (!c || !k.max_tasks) return YDC_ERR_INVALID_ARGUMENT;
+  if (int rc = stream_caps_check(c, YDC_ERR_CAPACITY, k, 0)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   stream_release(c);
-  if (int rc = stream_alloc(c, c->stream_mode, max_updates, max_releases, max_tasks, max_waiting, lc, max_rows))
-    return rc;
+  if (int rc = stream_alloc(c, c->stream_mode, k, 0)) return rc;
   return stream_reset(c, c->stream_mode);
 }
 
-int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t max_tasks, uint32_t max_waiting,
-                  const LeaseCaps* lcp, uint32_t max_rows, uint32_t max_book);
-
-}  // namespace
-
-extern "C" {
-
-int ydc_stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases,
-                     uint32_t max_tasks) {
-  return stream_begin(c, max_updates, max_releases, max_tasks, 0);
-}
-
-int ydc_stream_begin_waiting(ydc_context* c, uint32_t max_updates, uint32_t max_releases,
-                             uint32_t max_tasks, uint32_t max_waiting) {
-  if (!c || !max_waiting) return YDC_ERR_INVALID_ARGUMENT;
-  return stream_begin(c, max_updates, max_releases, max_tasks, max_waiting);
-}
-
-int ydc_stream_caps_get(ydc_context* c, ydc_stream_caps* out) {
-  if (!c || !out || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
-  const auto& sm = c->stream_mode;
-  *out = ydc_stream_caps{sm.max_upd,    sm.max_rel,   sm.max_tasks, sm.max_rows, sm.max_waiting,
-                         sm.max_leases, sm.max_renew, sm.max_free,  sm.max_rep,  sm.max_rep_ids};
-  return YDC_OK;
-}
-
-int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
-  if (!c || !want) return YDC_ERR_INVALID_ARGUMENT;
-  auto& sm = c->stream_mode;
-  if (!sm.active) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: no stream is open");
-  if (!sm.max_waiting && !sm.max_leases)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: a stream begun with ydc_stream_begin keeps no state "
-                "on the device, and its ydc_stream_buffers_get pointers stay valid until ydc_stream_end");
-  // The mode is fixed: no capacity of a part the stream was begun without.
-  if (!sm.max_waiting && want->max_waiting)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: max_waiting on a stream without a waiting queue");
-  if (!sm.max_leases && (want->max_leases | want->max_renewals | want->max_frees | want->max_reports |
-                         want->max_report_ids))
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: lease capacities on a stream without a lease table");
-  if (!sm.max_rows && want->max_rows)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: max_rows on a stream not begun with ydc_stream_begin_rpc");
-  // Growth only.
-  const uint32_t max_upd = std::max(sm.max_upd, want->max_updates), max_rel = std::max(sm.max_rel, want->max_releases);
-  const uint32_t max_tasks = std::max(sm.max_tasks, want->max_tasks), max_rows = std::max(sm.max_rows, want->max_rows);
-  const uint32_t max_waiting = std::max(sm.max_waiting, want->max_waiting);
-  const LeaseCaps lc{std::max(sm.max_leases, want->max_leases), std::max(sm.max_renew, want->max_renewals),
-                     std::max(sm.max_free, want->max_frees), std::max(sm.max_rep, want->max_reports),
-                     std::max(sm.max_rep_ids, want->max_report_ids)};
-  const LeaseCaps* lcp = sm.max_leases ? &lc : nullptr;
-  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, max_tasks, max_waiting, lcp, max_rows, sm.max_book))
-    return rc;
-  if (max_upd == sm.max_upd && max_rel == sm.max_rel && max_tasks == sm.max_tasks && max_rows == sm.max_rows &&
-      max_waiting == sm.max_waiting && lc.max_leases == sm.max_leases && lc.max_renew == sm.max_renew &&
-      lc.max_free == sm.max_free && lc.max_rep == sm.max_rep && lc.max_rep_ids == sm.max_rep_ids)
-    return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, max_upd, max_rel, max_tasks, max_waiting, lcp, max_rows, sm.max_book);
-}
-
-}  // extern "C"
-
-namespace {
-
-// ---- the servants' expiry column (servant_alive.h) ----
-
-// Everything aliveness keeps, from the stream `o` to the one that takes its place.
-void alive_carry(ydc_context::Stream& o, ydc_context::Stream& n) {
-  n.alive = o.alive;
-  n.alive_n = o.alive_n;
-  n.d_alive = std::move(o.d_alive);
-  n.d_alive_spare = std::move(o.d_alive_spare);
-  n.d_alive_stage = std::move(o.d_alive_stage);
-  n.d_alive_idx = std::move(o.d_alive_idx);
-  n.d_alive_state = std::move(o.d_alive_state);
-  n.h_alive_list = o.h_alive_list;
-  n.z_alive_list = o.z_alive_list;
-  n.alive_list_cap = o.alive_list_cap;
-  o.h_alive_list = o.z_alive_list = nullptr;
-  o.alive_list_cap = 0;
-  n.alive_bound = o.alive_bound;
-  n.alive_alarms = o.alive_alarms;
-  n.alive_removals = o.alive_removals;
-  n.alive_staged = o.alive_staged;
-  n.alive_stage = o.alive_stage;
-  n.alive_removed = o.alive_removed;
-  n.alive_orphans = o.alive_orphans;
-}
-
-// Inspection's servant columns and scratch, from the stream `o` to the one that takes its place (the
-// detail records have moved already: stream_migrate).
-void inspect_carry(ydc_context::Stream& o, ydc_context::Stream& n) {
-  n.inspect = o.inspect;
-  n.inspect_n = o.inspect_n;
-  n.d_insp_disc = std::move(o.d_insp_disc);
-  n.d_insp_disc_spare = std::move(o.d_insp_disc_spare);
-  n.d_insp_ever = std::move(o.d_insp_ever);
-  n.d_insp_ever_spare = std::move(o.d_insp_ever_spare);
-  n.d_insp_avail = std::move(o.d_insp_avail);
-  n.d_insp_sums = std::move(o.d_insp_sums);
-  n.d_insp_pack = std::move(o.d_insp_pack);
-}
-
-// discovered_at and ever_assigned have a row for every servant of the registry; rows they gain were
-// discovered at `when` and have been assigned nothing (task_dispatcher.cc:208).
-int inspect_fit(ydc_context* c, int64_t when) {
-  auto& sm = c->stream_mode;
-  const uint32_t S = c->n_servants;
-  if (S < sm.inspect_n) sm.inspect_n = S;
-  if (S == sm.inspect_n) return YDC_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (S > sm.d_insp_disc.cap || S > sm.d_insp_ever.cap) {
-    DevBuf<int64_t> disc;
-    DevBuf<unsigned long long> ever;
-    HIP_TRY(c, disc.reserve((size_t)S + S / 2 + 1024));
-    HIP_TRY(c, ever.reserve((size_t)S + S / 2 + 1024));
-    if (sm.inspect_n) {
-      HIP_TRY(c, hipMemcpy(disc.p, sm.d_insp_disc.p, (size_t)sm.inspect_n * 8, hipMemcpyDeviceToDevice));
-      HIP_TRY(c, hipMemcpy(ever.p, sm.d_insp_ever.p, (size_t)sm.inspect_n * 8, hipMemcpyDeviceToDevice));
-    }
-    sm.d_insp_disc = std::move(disc);
-    sm.d_insp_ever = std::move(ever);
-  }
-  const std::vector<int64_t> at(S - sm.inspect_n, when);
-  HIP_TRY(c, hipMemcpy(sm.d_insp_disc.p + sm.inspect_n, at.data(), at.size() * 8, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemset(sm.d_insp_ever.p + sm.inspect_n, 0, at.size() * 8));
-  sm.inspect_n = S;
-  sm.stale = true;  // (a captured step holds the count column's address and its row count)
-  return YDC_OK;
-}
-
-// E has a row for every servant of the registry; rows it gains start at "never".
-int alive_fit(ydc_context* c) {
-  auto& sm = c->stream_mode;
-  const uint32_t S = c->n_servants;
-  if (S < sm.alive_n) sm.alive_n = S;
-  if (S == sm.alive_n) return YDC_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (S > sm.d_alive.cap) {
-    DevBuf<int64_t> bigger;
-    HIP_TRY(c, bigger.reserve((size_t)S + S / 2 + 1024));
-    if (sm.alive_n) {
-      HIP_TRY(c, hipMemcpyAsync(bigger.p, sm.d_alive.p, (size_t)sm.alive_n * 8, hipMemcpyDeviceToDevice, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    sm.d_alive = std::move(bigger);
-    sm.stale = true;  // (a captured step holds the column's address)
-  }
-  const std::vector<int64_t> never(S - sm.alive_n, kAliveNever);
-  HIP_TRY(c, hipMemcpy(sm.d_alive.p + sm.alive_n, never.data(), never.size() * 8, hipMemcpyHostToDevice));
-  sm.alive_n = S;
-  return YDC_OK;
-}
-
-// n heartbeats' expiries into E now (k_alive_beat on a device copy of the two columns).
-int alive_file(ydc_context* c, const uint32_t* idx, const int64_t* expires, uint32_t n) {
-  auto& sm = c->stream_mode;
-  if (!n) return YDC_OK;
-  HIP_TRY(c, sm.d_alive_idx.reserve(n));
-  HIP_TRY(c, sm.d_alive_stage.reserve(n));
-  HIP_TRY(c, hipMemcpy(sm.d_alive_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(sm.d_alive_stage.p, expires, (size_t)n * 8, hipMemcpyHostToDevice));
-  YDC_LAUNCH(c, "k_alive_beat", k_alive_beat, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, sm.d_alive_idx.p,
-             sm.d_alive_stage.p, n, sm.alive_n, sm.d_alive.p);
-  HIP_TRY(c, hipGetLastError());
-  return YDC_OK;
-}
-
-// The alarm: the rows with E < now, ascending, in h_alive_list[0, *n_due); alive_bound exact (the
-// minimum over the rows that stay).
-int alive_due(ydc_context* c, int64_t now, uint32_t* n_due) {
-  auto& sm = c->stream_mode;
-  *n_due = 0;
-  ++sm.alive_alarms;
-  if (!sm.alive_n) {
-    sm.alive_bound = kAliveNever;
-    return YDC_OK;
-  }
-  HIP_TRY(c, sm.d_alive_state.reserve(1));
-  if (sm.alive_list_cap < sm.alive_n) {
-    if (sm.h_alive_list) (void)hipHostFree(sm.h_alive_list);
-    sm.h_alive_list = sm.z_alive_list = nullptr;
-    sm.alive_list_cap = 0;
-    const size_t want = (size_t)sm.alive_n + sm.alive_n / 2 + 1024;
-    HIP_TRY(c, hipHostMalloc((void**)&sm.h_alive_list, want * 4, hipHostMallocCoherent | hipHostMallocMapped));
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&sm.z_alive_list, sm.h_alive_list, 0));
-    sm.alive_list_cap = want;
-  }
-  AliveState st{kAliveNever, 0, 0, 0, 0};
-  HIP_TRY(c, hipMemcpy(sm.d_alive_state.p, &st, sizeof st, hipMemcpyHostToDevice));
-  YDC_LAUNCH(c, "k_alive_due", k_alive_due, dim3(ceil_div(sm.alive_n, 256)), dim3(256), 0, c->stream, sm.d_alive.p,
-             sm.alive_n, now, sm.d_alive_state.p, sm.z_alive_list);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(&st, sm.d_alive_state.p, sizeof st, hipMemcpyDeviceToHost));
-  if (st.n_due > sm.alive_n) return fail(c, YDC_ERR_NOT_CONVERGED, "%u of %u servants due", st.n_due, sm.alive_n);
-  std::sort(sm.h_alive_list, sm.h_alive_list + st.n_due);
-  sm.alive_bound = st.min_expires;
-  *n_due = st.n_due;
-  return YDC_OK;
-}
-
-// Behind the step of a tick that took the removal route: the parked leases erased, and the tick's
-// outcome block corrected — an orphan is neither a lease any more nor one that expired.
-int alive_orphans(ydc_context* c) {
-  auto& sm = c->stream_mode;
-  YDC_LAUNCH(c, "k_alive_orphans", k_alive_orphans, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
-             sm.lt, sm.ls, sm.d_alive_state.p);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  AliveState st{};
-  HIP_TRY(c, hipMemcpy(&st, sm.d_alive_state.p, sizeof st, hipMemcpyDeviceToHost));
-  sm.h_lout->n_leases -= std::min(sm.h_lout->n_leases, st.n_orphans);
-  sm.h_lout->expired -= std::min(sm.h_lout->expired, st.n_late);
-  sm.alive_orphans = st.n_orphans;
-  return YDC_OK;
-}
-
-// A removal tick that ends in an error before its ending ran: the parked leases must not outlive it
-// (they would count in |L| and show in ydc_stream_leases_get with a servant no registry has). The
-// error that is being returned keeps its text; |L| is read back from the device.
-void alive_orphans_after_error(ydc_context* c) {
-  auto& sm = c->stream_mode;
-  if (!sm.d_alive_state.p) return;
-  (void)hipStreamSynchronize(c->stream);
-  hipLaunchKernelGGL(k_alive_orphans, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream, sm.lt, sm.ls,
-                     sm.d_alive_state.p);
-  (void)hipStreamSynchronize(c->stream);
-  AliveState st{};
-  if (hipMemcpy(&st, sm.d_alive_state.p, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) sm.alive_orphans = st.n_orphans;
-  (void)hipMemcpy(&sm.n_leases, &sm.ls->n_leases, 4, hipMemcpyDeviceToHost);
-}
-
-// A row number after the removal of removed[0, n) (ascending); a removed row itself: kRemovedRow.
-uint32_t alive_renumber(const uint32_t* removed, uint32_t n, uint32_t s) {
-  const uint32_t before = (uint32_t)(std::lower_bound(removed, removed + n, s) - removed);
-  return before < n && removed[before] == s ? kRemovedRow : s - before;
-}
-
 // The open stream in a second, larger set of buffers (ydc_stream_reserve, ydc_stream_book_begin).
-int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t max_tasks, uint32_t max_waiting,
-                  const LeaseCaps* lcp, uint32_t max_rows, uint32_t max_book) {
+int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book) {
   auto& sm = c->stream_mode;
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
@@ -4962,16 +4807,18 @@ int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t m
   // A second set of buffers, filled from the first, which is released only once that has worked:
   // after any failure the stream is as it was.
   ydc_context::Stream grown;
-  int rc = stream_alloc(c, grown, max_upd, max_rel, max_tasks, max_waiting, lcp, max_rows, max_book);
+  int rc = stream_alloc(c, grown, k, max_book);
   if (rc == YDC_OK) rc = stream_reset(c, grown);
   if (rc == YDC_OK) rc = stream_migrate(c, sm, grown);
   if (rc != YDC_OK) {
     stream_release(grown);
     return rc;
   }
-  grown.d_rep_tick = std::move(sm.d_rep_tick);  // (sized by the registry, not by the stream)
-  alive_carry(sm, grown);                       // (so is the expiry column; a pending staging goes along)
-  inspect_carry(sm, grown);                     // (so are inspection's servant columns)
+  // What is sized by the registry, not by the stream, moves as it is.
+  grown.d_rep_tick = std::move(sm.d_rep_tick);
+  grown.alive = std::move(sm.alive);      // (a pending staging goes along)
+  grown.inspect = std::move(sm.inspect);  // (the detail records have moved already: stream_migrate)
+  grown.book.staged = std::move(sm.book.staged);
   std::swap(sm, grown);
   stream_release(grown);  // (the old buffers and the old captures; sm.stale: the step is captured again)
   return YDC_OK;
@@ -4981,16 +4828,181 @@ int stream_regrow(ydc_context* c, uint32_t max_upd, uint32_t max_rel, uint32_t m
 
 extern "C" {
 
+int ydc_stream_begin(ydc_context* c, uint32_t max_updates, uint32_t max_releases,
+                     uint32_t max_tasks) {
+  return stream_begin(c, ydc_stream_caps{max_updates, max_releases, max_tasks, 0, 0, 0, 0, 0, 0, 0});
+}
+
+int ydc_stream_begin_waiting(ydc_context* c, uint32_t max_updates, uint32_t max_releases,
+                             uint32_t max_tasks, uint32_t max_waiting) {
+  if (!c || !max_waiting) return YDC_ERR_INVALID_ARGUMENT;
+  return stream_begin(c, ydc_stream_caps{max_updates, max_releases, max_tasks, 0, max_waiting, 0, 0, 0, 0, 0});
+}
+
+int ydc_stream_caps_get(ydc_context* c, ydc_stream_caps* out) {
+  if (!c || !out || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
+  *out = c->stream_mode.caps;
+  return YDC_OK;
+}
+
+int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
+  if (!c || !want) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: no stream is open");
+  if (!sm.waiting() && !sm.leased())
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: a stream begun with ydc_stream_begin keeps no state "
+                "on the device, and its ydc_stream_buffers_get pointers stay valid until ydc_stream_end");
+  if (const char* why = stream_caps_foreign(sm.caps, *want))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_reserve: %s", why);
+  const ydc_stream_caps k = stream_caps_grown(sm.caps, *want);  // (growth only)
+  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, k, sm.max_book)) return rc;
+  if (!std::memcmp(&k, &sm.caps, sizeof k)) return YDC_OK;  // (nothing to do: the captured step stays)
+  return stream_regrow(c, k, sm.max_book);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- the servants' expiry column (servant_alive.h) ----
+
+// A device column with a row per servant of the registry, `have` of them filed: room for `want`
+// rows, the filed ones kept, the rows it gains set to `fill`. The context's stream is idle.
+template <typename T>
+int fit_rows(ydc_context* c, DevBuf<T>& col, uint32_t have, uint32_t want, T fill) {
+  if (want > col.cap) {
+    DevBuf<T> bigger;
+    HIP_TRY(c, bigger.reserve((size_t)want + want / 2 + 1024));
+    if (have) HIP_TRY(c, hipMemcpy(bigger.p, col.p, (size_t)have * sizeof(T), hipMemcpyDeviceToDevice));
+    col = std::move(bigger);
+  }
+  const std::vector<T> rows(want - have, fill);
+  HIP_TRY(c, hipMemcpy(col.p + have, rows.data(), rows.size() * sizeof(T), hipMemcpyHostToDevice));
+  return YDC_OK;
+}
+
+// discovered_at and ever_assigned have a row for every servant of the registry; rows they gain were
+// discovered at `when` and have been assigned nothing (task_dispatcher.cc:208).
+int inspect_fit(ydc_context* c, int64_t when) {
+  auto& sm = c->stream_mode;
+  auto& in = sm.inspect;
+  const uint32_t S = c->n_servants;
+  if (S < in.n) in.n = S;
+  if (S == in.n) return YDC_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (int rc = fit_rows(c, in.disc, in.n, S, when)) return rc;
+  if (int rc = fit_rows(c, in.ever, in.n, S, 0ull)) return rc;
+  in.n = S;
+  sm.stale = true;  // (a captured step holds the count column's address and its row count)
+  return YDC_OK;
+}
+
+// E has a row for every servant of the registry; rows it gains start at "never".
+int alive_fit(ydc_context* c) {
+  auto& sm = c->stream_mode;
+  auto& al = sm.alive;
+  const uint32_t S = c->n_servants;
+  if (S < al.n) al.n = S;
+  if (S == al.n) return YDC_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const int64_t* was = al.col.p;
+  if (int rc = fit_rows(c, al.col, al.n, S, kAliveNever)) return rc;
+  if (al.col.p != was) sm.stale = true;  // (a captured step holds the column's address)
+  al.n = S;
+  return YDC_OK;
+}
+
+// n heartbeats' expiries into E now (k_alive_beat on a device copy of the two columns).
+int alive_file(ydc_context* c, const uint32_t* idx, const int64_t* expires, uint32_t n) {
+  auto& sm = c->stream_mode;
+  if (!n) return YDC_OK;
+  HIP_TRY(c, sm.alive.d_idx.reserve(n));
+  HIP_TRY(c, sm.alive.d_stage.reserve(n));
+  HIP_TRY(c, hipMemcpy(sm.alive.d_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(sm.alive.d_stage.p, expires, (size_t)n * 8, hipMemcpyHostToDevice));
+  YDC_LAUNCH(c, "k_alive_beat", k_alive_beat, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, sm.alive.d_idx.p,
+             sm.alive.d_stage.p, n, sm.alive.n, sm.alive.col.p);
+  HIP_TRY(c, hipGetLastError());
+  return YDC_OK;
+}
+
+// The alarm: the rows with E < now, ascending, in alive.due[0, *n_due); alive.bound exact (the
+// minimum over the rows that stay).
+int alive_due(ydc_context* c, int64_t now, uint32_t* n_due) {
+  auto& sm = c->stream_mode;
+  *n_due = 0;
+  ++sm.alive.alarms;
+  if (!sm.alive.n) {
+    sm.alive.bound = kAliveNever;
+    return YDC_OK;
+  }
+  HIP_TRY(c, sm.alive.d_state.reserve(1));
+  if (sm.alive.due.cap < (size_t)sm.alive.n * 4)
+    HIP_TRY(c, sm.alive.due.reserve(((size_t)sm.alive.n + sm.alive.n / 2 + 1024) * 4));
+  AliveState st{kAliveNever, 0, 0, 0, 0};
+  HIP_TRY(c, hipMemcpy(sm.alive.d_state.p, &st, sizeof st, hipMemcpyHostToDevice));
+  YDC_LAUNCH(c, "k_alive_due", k_alive_due, dim3(ceil_div(sm.alive.n, 256)), dim3(256), 0, c->stream, sm.alive.col.p,
+             sm.alive.n, now, sm.alive.d_state.p, (uint32_t*)sm.alive.due.z);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(&st, sm.alive.d_state.p, sizeof st, hipMemcpyDeviceToHost));
+  if (st.n_due > sm.alive.n) return fail(c, YDC_ERR_NOT_CONVERGED, "%u of %u servants due", st.n_due, sm.alive.n);
+  uint32_t* due = (uint32_t*)sm.alive.due.p;
+  std::sort(due, due + st.n_due);
+  sm.alive.bound = st.min_expires;
+  *n_due = st.n_due;
+  return YDC_OK;
+}
+
+// Behind the step of a tick that took the removal route: the parked leases erased, and the tick's
+// outcome block corrected — an orphan is neither a lease any more nor one that expired.
+int alive_orphans(ydc_context* c) {
+  auto& sm = c->stream_mode;
+  YDC_LAUNCH(c, "k_alive_orphans", k_alive_orphans, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
+             sm.lt, sm.ls, sm.alive.d_state.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  AliveState st{};
+  HIP_TRY(c, hipMemcpy(&st, sm.alive.d_state.p, sizeof st, hipMemcpyDeviceToHost));
+  sm.h_lout->n_leases -= std::min(sm.h_lout->n_leases, st.n_orphans);
+  sm.h_lout->expired -= std::min(sm.h_lout->expired, st.n_late);
+  sm.alive.orphans = st.n_orphans;
+  return YDC_OK;
+}
+
+// A removal tick that ends in an error before its ending ran: the parked leases must not outlive it
+// (they would count in |L| and show in ydc_stream_leases_get with a servant no registry has). The
+// error that is being returned keeps its text; |L| is read back from the device.
+void alive_orphans_after_error(ydc_context* c) {
+  auto& sm = c->stream_mode;
+  if (!sm.alive.d_state.p) return;
+  (void)hipStreamSynchronize(c->stream);
+  hipLaunchKernelGGL(k_alive_orphans, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream, sm.lt, sm.ls,
+                     sm.alive.d_state.p);
+  (void)hipStreamSynchronize(c->stream);
+  AliveState st{};
+  if (hipMemcpy(&st, sm.alive.d_state.p, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) sm.alive.orphans = st.n_orphans;
+  (void)hipMemcpy(&sm.n_leases, &sm.ls->n_leases, 4, hipMemcpyDeviceToHost);
+}
+
+// A row number after the removal of removed[0, n) (ascending); a removed row itself: kRemovedRow.
+uint32_t alive_renumber(const uint32_t* removed, uint32_t n, uint32_t s) {
+  const uint32_t before = (uint32_t)(std::lower_bound(removed, removed + n, s) - removed);
+  return before < n && removed[before] == s ? kRemovedRow : s - before;
+}
+
+}  // namespace
+
+extern "C" {
+
 int ydc_stream_book_begin(ydc_context* c, uint32_t max_book) {
   if (!c || !max_book) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.max_leases)
+  if (!sm.active || !sm.leased())
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_begin: no leased, waiting-and-leased or rpc stream is open");
-  const LeaseCaps lc{sm.max_leases, sm.max_renew, sm.max_free, sm.max_rep, sm.max_rep_ids};
-  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, sm.max_tasks, sm.max_waiting, &lc, sm.max_rows, max_book))
-    return rc;
+  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, sm.caps, max_book)) return rc;
   if (max_book <= sm.max_book) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, sm.max_upd, sm.max_rel, sm.max_tasks, sm.max_waiting, &lc, sm.max_rows, max_book);
+  return stream_regrow(c, ydc_stream_caps(sm.caps), max_book);  // (a copy: regrow replaces the stream)
 }
 
 int ydc_stream_book_stage(ydc_context* c, const uint64_t* servant_task_id, const uint64_t* digest_key,
@@ -4999,13 +5011,13 @@ int ydc_stream_book_stage(ydc_context* c, const uint64_t* servant_task_id, const
   auto& sm = c->stream_mode;
   if (!sm.active || !sm.max_book)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_stage: the stream has no running-task book");
-  if (n_ids > sm.max_rep_ids)
-    return fail(c, YDC_ERR_CAPACITY, "%u staged ids > max_report_ids %u", n_ids, sm.max_rep_ids);
-  sm.stage_stid.assign(n_ids, 0);
-  sm.stage_dkey.assign(n_ids, 0);
-  if (servant_task_id) std::copy_n(servant_task_id, n_ids, sm.stage_stid.begin());
-  if (digest_key) std::copy_n(digest_key, n_ids, sm.stage_dkey.begin());
-  sm.book_staged = true;
+  if (n_ids > sm.caps.max_report_ids)
+    return fail(c, YDC_ERR_CAPACITY, "%u staged ids > max_report_ids %u", n_ids, sm.caps.max_report_ids);
+  sm.book.staged.stid.assign(n_ids, 0);
+  sm.book.staged.dkey.assign(n_ids, 0);
+  if (servant_task_id) std::copy_n(servant_task_id, n_ids, sm.book.staged.stid.begin());
+  if (digest_key) std::copy_n(digest_key, n_ids, sm.book.staged.dkey.begin());
+  sm.book.staged.on = true;
   return YDC_OK;
 }
 
@@ -5017,51 +5029,49 @@ int ydc_stream_book_get(ydc_context* c, uint32_t* out_servant_idx, uint64_t* out
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_get: the stream has no running-task book");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const uint32_t n = sm.n_book;
+  const uint32_t n = sm.book.n;
   *out_n = n;
   if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u book entries > cap %u", n, cap);
   if (n && (!out_servant_idx || !out_task_grant_id || !out_servant_task_id || !out_digest_key))
     return YDC_ERR_INVALID_ARGUMENT;
-  if (n) {
-    HIP_TRY(c, hipMemcpy(out_servant_idx, sm.bk.servant, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(out_task_grant_id, sm.bk.grant, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(out_servant_task_id, sm.bk.stid, (size_t)n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(out_digest_key, sm.bk.dkey, (size_t)n * 8, hipMemcpyDeviceToHost));
-  }
+  const auto from = b_cols(sm);
+  void* const to[kBCols] = {out_task_grant_id, out_servant_task_id, out_digest_key, out_servant_idx};
+  for (size_t k = 0; n && k < kBCols; ++k) HIP_TRY(c, hipMemcpy(to[k], from[k].p, n * from[k].width, hipMemcpyDeviceToHost));
   return YDC_OK;
 }
 
 int ydc_stream_alive_begin(ydc_context* c, const int64_t* expires_at, uint32_t n) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.max_leases)
+  if (!sm.active || !sm.leased())
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_begin: no leased, waiting-and-leased or rpc stream is open");
   if (n != c->n_servants)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_begin: %u expiries for %u servants", n, c->n_servants);
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const int64_t* old = sm.d_alive.p;
-  HIP_TRY(c, sm.d_alive.reserve((size_t)n + n / 2 + 1024));
+  const int64_t* old = sm.alive.col.p;
+  HIP_TRY(c, sm.alive.col.reserve((size_t)n + n / 2 + 1024));
   std::vector<int64_t> col(n, kAliveNever);
   if (expires_at) std::copy_n(expires_at, n, col.begin());
-  if (n) HIP_TRY(c, hipMemcpy(sm.d_alive.p, col.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-  sm.alive_bound = kAliveNever;
-  for (int64_t e : col) sm.alive_bound = std::min(sm.alive_bound, e);
-  sm.alive_n = n;
-  if (!sm.alive || old != sm.d_alive.p) sm.stale = true;  // (the step gains k_alive_beat: captured again)
-  sm.alive = true;
+  if (n) HIP_TRY(c, hipMemcpy(sm.alive.col.p, col.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+  sm.alive.bound = kAliveNever;
+  for (int64_t e : col) sm.alive.bound = std::min(sm.alive.bound, e);
+  sm.alive.n = n;
+  if (!sm.alive.on || old != sm.alive.col.p) sm.stale = true;  // (the step gains k_alive_beat: captured again)
+  sm.alive.on = true;
   return YDC_OK;
 }
 
 int ydc_stream_alive_stage(ydc_context* c, const int64_t* upd_expires_at, uint32_t n_upd) {
   if (!c || (n_upd && !upd_expires_at)) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.alive)
+  if (!sm.active || !sm.alive.on)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_stage: the stream keeps no servant expiries");
-  if (n_upd > sm.max_upd) return fail(c, YDC_ERR_CAPACITY, "%u staged expiries > max_updates %u", n_upd, sm.max_upd);
-  sm.alive_stage.assign(upd_expires_at, upd_expires_at + n_upd);
-  sm.alive_staged = true;
+  if (n_upd > sm.caps.max_updates)
+    return fail(c, YDC_ERR_CAPACITY, "%u staged expiries > max_updates %u", n_upd, sm.caps.max_updates);
+  sm.alive.stage.assign(upd_expires_at, upd_expires_at + n_upd);
+  sm.alive.staged = true;
   return YDC_OK;
 }
 
@@ -5069,40 +5079,40 @@ int ydc_stream_alive_removed(ydc_context* c, uint32_t* out_idx, uint32_t cap, ui
                              uint32_t* out_n_orphans) {
   if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.alive)
+  if (!sm.active || !sm.alive.on)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_removed: the stream keeps no servant expiries");
-  const uint32_t n = (uint32_t)sm.alive_removed.size();
+  const uint32_t n = (uint32_t)sm.alive.removed.size();
   *out_n = n;
-  if (out_n_orphans) *out_n_orphans = sm.alive_orphans;
+  if (out_n_orphans) *out_n_orphans = sm.alive.orphans;
   if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u removed servants > cap %u", n, cap);
   if (n && !out_idx) return YDC_ERR_INVALID_ARGUMENT;
-  if (n) std::memcpy(out_idx, sm.alive_removed.data(), (size_t)n * 4);
+  if (n) std::memcpy(out_idx, sm.alive.removed.data(), (size_t)n * 4);
   return YDC_OK;
 }
 
 int ydc_stream_alive_get(ydc_context* c, int64_t* out_expires_at, uint32_t cap, uint32_t* out_n) {
   if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.alive)
+  if (!sm.active || !sm.alive.on)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_get: the stream keeps no servant expiries");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (int rc = alive_fit(c)) return rc;
-  const uint32_t n = sm.alive_n;
+  const uint32_t n = sm.alive.n;
   *out_n = n;
   if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u servant expiries > cap %u", n, cap);
   if (n && !out_expires_at) return YDC_ERR_INVALID_ARGUMENT;
-  if (n) HIP_TRY(c, hipMemcpy(out_expires_at, sm.d_alive.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (n) HIP_TRY(c, hipMemcpy(out_expires_at, sm.alive.col.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   return YDC_OK;
 }
 
 // Tests and tools (not part of the ABI): the host's lower bound of min(E), the ticks that launched
 // k_alive_due so far and the servants the ticks removed so far.
 int ydc_debug_alive(ydc_context* c, int64_t* out_bound, uint64_t* out_alarms, uint64_t* out_removals) {
-  if (!c || !c->stream_mode.active || !c->stream_mode.alive) return YDC_ERR_INVALID_ARGUMENT;
-  if (out_bound) *out_bound = c->stream_mode.alive_bound;
-  if (out_alarms) *out_alarms = c->stream_mode.alive_alarms;
-  if (out_removals) *out_removals = c->stream_mode.alive_removals;
+  if (!c || !c->stream_mode.active || !c->stream_mode.alive.on) return YDC_ERR_INVALID_ARGUMENT;
+  if (out_bound) *out_bound = c->stream_mode.alive.bound;
+  if (out_alarms) *out_alarms = c->stream_mode.alive.alarms;
+  if (out_removals) *out_removals = c->stream_mode.alive.removals;
   return YDC_OK;
 }
 
@@ -5111,17 +5121,17 @@ int ydc_debug_alive(ydc_context* c, int64_t* out_bound, uint64_t* out_alarms, ui
 int ydc_stream_inspect_begin(ydc_context* c, const int64_t* discovered_at, const uint64_t* ever_assigned, uint32_t n) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.max_leases)
+  if (!sm.active || !sm.leased())
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_begin: no leased, waiting-and-leased or rpc stream is open");
   if (n != c->n_servants)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_begin: %u rows for %u servants", n, c->n_servants);
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, sm.d_insp_disc.reserve((size_t)n + n / 2 + 1024));
-  HIP_TRY(c, sm.d_insp_ever.reserve((size_t)n + n / 2 + 1024));
+  HIP_TRY(c, sm.inspect.disc.reserve((size_t)n + n / 2 + 1024));
+  HIP_TRY(c, sm.inspect.ever.reserve((size_t)n + n / 2 + 1024));
   const size_t slots = (size_t)sm.lt.mask + 1;
-  if (!sm.inspect) {
+  if (!sm.inspect.on) {
     HIP_TRY(c, sm.d_insp_rec.reserve(slots));
     HIP_TRY(c, sm.d_insp_pre.reserve(slots));
   }
@@ -5130,17 +5140,17 @@ int ydc_stream_inspect_begin(ydc_context* c, const int64_t* discovered_at, const
   if (discovered_at) std::copy_n(discovered_at, n, disc.begin());
   if (ever_assigned) std::copy_n(ever_assigned, n, ever.begin());
   if (n) {
-    HIP_TRY(c, hipMemcpy(sm.d_insp_disc.p, disc.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(sm.d_insp_ever.p, ever.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(sm.inspect.disc.p, disc.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(sm.inspect.ever.p, ever.data(), (size_t)n * 8, hipMemcpyHostToDevice));
   }
-  if (!sm.inspect) {  // (the leases L holds were granted without details)
+  if (!sm.inspect.on) {  // (the leases L holds were granted without details)
     YDC_LAUNCH(c, "k_inspect_fill", k_inspect_fill, dim3(ceil_div((uint32_t)slots, 256)), dim3(256), 0, c->stream,
                sm.d_insp_rec.p, sm.d_insp_pre.p, (uint32_t)slots);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
-  sm.inspect_n = n;
-  sm.inspect = true;
+  sm.inspect.n = n;
+  sm.inspect.on = true;
   sm.stale = true;  // (the step's granting pass changes, and it holds the columns' addresses: captured again)
   return YDC_OK;
 }
@@ -5149,7 +5159,7 @@ int ydc_stream_inspect_load(ydc_context* c, const uint64_t* task_id, const int64
                             const uint32_t* requestor_ip, const uint8_t* prefetch, uint32_t n) {
   if (!c || (n && !task_id)) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.inspect)
+  if (!sm.active || !sm.inspect.on)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_load: the stream has no inspection");
   if (n > sm.n_leases) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_load: %u records for %u leases", n, sm.n_leases);
   if (!n) return YDC_OK;
@@ -5206,30 +5216,30 @@ int ydc_stream_inspect_servants(ydc_context* c, int64_t* out_discovered_at, uint
                                 uint32_t* out_n, ydc_stream_totals* out_totals) {
   if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.inspect)
+  if (!sm.active || !sm.inspect.on)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_servants: the stream has no inspection");
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (int rc = inspect_fit(c, sm.last_now == INT64_MIN ? 0 : sm.last_now)) return rc;
-  const uint32_t n = sm.inspect_n;
+  const uint32_t n = sm.inspect.n;
   *out_n = n;
   if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u servants > cap %u", n, cap);
-  HIP_TRY(c, sm.d_insp_avail.reserve(n));
-  HIP_TRY(c, sm.d_insp_sums.reserve(1));
+  HIP_TRY(c, sm.inspect.avail.reserve(n));
+  HIP_TRY(c, sm.inspect.sums.reserve(1));
   InspectSums sums{0, 0, 0};
-  HIP_TRY(c, hipMemcpy(sm.d_insp_sums.p, &sums, sizeof sums, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(sm.inspect.sums.p, &sums, sizeof sums, hipMemcpyHostToDevice));
   if (n) {
     YDC_LAUNCH(c, "k_inspect_servants", k_inspect_servants, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, c->d_nproc.p,
-               c->d_load.p, c->d_max_tasks.p, c->d_running.p, c->d_flags.p, n, sm.d_insp_avail.p, sm.d_insp_sums.p);
+               c->d_load.p, c->d_max_tasks.p, c->d_running.p, c->d_flags.p, n, sm.inspect.avail.p, sm.inspect.sums.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (out_discovered_at) HIP_TRY(c, hipMemcpy(out_discovered_at, sm.d_insp_disc.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-    if (out_ever_assigned) HIP_TRY(c, hipMemcpy(out_ever_assigned, sm.d_insp_ever.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (out_discovered_at) HIP_TRY(c, hipMemcpy(out_discovered_at, sm.inspect.disc.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (out_ever_assigned) HIP_TRY(c, hipMemcpy(out_ever_assigned, sm.inspect.ever.p, (size_t)n * 8, hipMemcpyDeviceToHost));
     if (out_running_tasks) HIP_TRY(c, hipMemcpy(out_running_tasks, c->d_running.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (out_capacity_available)
-      HIP_TRY(c, hipMemcpy(out_capacity_available, sm.d_insp_avail.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(&sums, sm.d_insp_sums.p, sizeof sums, hipMemcpyDeviceToHost));
+      HIP_TRY(c, hipMemcpy(out_capacity_available, sm.inspect.avail.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&sums, sm.inspect.sums.p, sizeof sums, hipMemcpyDeviceToHost));
   }
   if (out_totals) {
     // (task_dispatcher.cc:604-612, u64 arithmetic modulo 2^64)
@@ -5245,7 +5255,7 @@ int ydc_stream_inspect_tasks(ydc_context* c, uint64_t* out_task_id, uint32_t* ou
                              uint32_t* out_requestor_ip, uint8_t* out_prefetch, uint32_t cap, uint32_t* out_n) {
   if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
-  if (!sm.active || !sm.inspect)
+  if (!sm.active || !sm.inspect.on)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_tasks: the stream has no inspection");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -5254,8 +5264,8 @@ int ydc_stream_inspect_tasks(ydc_context* c, uint64_t* out_task_id, uint32_t* ou
   if (nl > cap) return fail(c, YDC_ERR_CAPACITY, "%u leases > cap %u", nl, cap);
   // One pass over the table; |L| records cross the bus, not 2^k slots; sorted by id here.
   const size_t pc = std::max(nl, 1u), o_cnt = (pc * 41 + 3) & ~(size_t)3;
-  HIP_TRY(c, sm.d_insp_pack.reserve(o_cnt + 4));
-  uint8_t* d = sm.d_insp_pack.p;
+  HIP_TRY(c, sm.inspect.pack.reserve(o_cnt + 4));
+  uint8_t* d = sm.inspect.pack.p;
   const InspectPacked pk{(unsigned long long*)(d + pc * 16), (int64_t*)(d + pc * 24), (uint4*)d,
                          (uint32_t*)(d + pc * 32),            (uint32_t*)(d + pc * 36), d + pc * 40, (uint32_t)pc};
   HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, 4, c->stream));
@@ -5297,7 +5307,7 @@ int ydc_stream_inspect_tasks(ydc_context* c, uint64_t* out_task_id, uint32_t* ou
 static int outlook_enter(ydc_context* c, const char* who) {
   auto& sm = c->stream_mode;
   if (!sm.active) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: no stream is open", who);
-  if (!sm.max_waiting && !sm.max_leases)
+  if (!sm.waiting() && !sm.leased())
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: a stream begun with ydc_stream_begin keeps no state on the device", who);
   if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: pipelined batches are outstanding", who);
   HIP_TRY(c, hipSetDevice(c->device));
@@ -5317,26 +5327,26 @@ int ydc_stream_outlook_get(ydc_context* c, const uint32_t* env_id, const uint32_
   if (c->tables_dirty)
     if (int rc = rebuild_tables(c)) return rc;  // (what the next tick would do first)
   const uint32_t S = c->n_servants, C = c->tables.n_classes(), EW = c->env_words, bins = 64 * EW + 1;
-  const bool with_w = sm.max_waiting != 0, with_l = sm.max_leases != 0 && sm.inspect;
+  const bool with_w = sm.waiting(), with_l = sm.leased() && sm.inspect.on;
   const size_t n_agg = (size_t)std::max(C, 1u) * kOutlookCols, n_res = (size_t)n * kOutlookCols;
-  HIP_TRY(c, sm.d_outlook_agg.reserve(n_agg));
-  HIP_TRY(c, sm.d_outlook_res.reserve(n_res));
-  HIP_TRY(c, sm.d_outlook_q.reserve((size_t)n * 2));
-  HIP_TRY(c, sm.d_outlook_hist.reserve((size_t)bins * 4));
-  uint32_t *d_env = sm.d_outlook_q.p, *d_minv = d_env + n;
-  uint32_t *d_hw = sm.d_outlook_hist.p, *d_hl = d_hw + (size_t)bins * 2;
+  HIP_TRY(c, sm.outlook.agg.reserve(n_agg));
+  HIP_TRY(c, sm.outlook.res.reserve(n_res));
+  HIP_TRY(c, sm.outlook.q.reserve((size_t)n * 2));
+  HIP_TRY(c, sm.outlook.hist.reserve((size_t)bins * 4));
+  uint32_t *d_env = sm.outlook.q.p, *d_minv = d_env + n;
+  uint32_t *d_hw = sm.outlook.hist.p, *d_hl = d_hw + (size_t)bins * 2;
   HIP_TRY(c, hipMemcpy(d_env, env_id, (size_t)n * 4, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(d_minv, min_version, (size_t)n * 4, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemsetAsync(sm.d_outlook_agg.p, 0, n_agg * 8, c->stream));
+  HIP_TRY(c, hipMemsetAsync(sm.outlook.agg.p, 0, n_agg * 8, c->stream));
   HIP_TRY(c, hipMemsetAsync(d_hw, 0, (size_t)bins * 16, c->stream));
   if (S && C)
     YDC_LAUNCH(c, "k_outlook_classes", k_outlook_classes, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, c->d_nproc.p,
-               c->d_load.p, c->d_max_tasks.p, c->d_running.p, c->d_flags.p, c->d_class_of.p, S, C, sm.d_outlook_agg.p);
+               c->d_load.p, c->d_max_tasks.p, c->d_running.p, c->d_flags.p, c->d_class_of.p, S, C, sm.outlook.agg.p);
   YDC_LAUNCH(c, "k_outlook_queries", k_outlook_queries, dim3(ceil_div(n, 4)), dim3(256), 0, c->stream, d_env, d_minv, n,
-             c->d_cls_env.p, c->d_cls_ver.p, C, EW, sm.d_outlook_agg.p, sm.d_outlook_res.p);
+             c->d_cls_env.p, c->d_cls_ver.p, C, EW, sm.outlook.agg.p, sm.outlook.res.p);
   if (with_w)
     YDC_LAUNCH(c, "k_outlook_waiting", k_outlook_waiting, dim3(std::max(ceil_div(sm.n_waiting, 256), 1u)), dim3(256), 0,
-               c->stream, sm.wq.env, sm.rw.n_imm, sm.rw.n_pre, sm.ws, sm.max_waiting, bins, d_hw);
+               c->stream, sm.wq.env, sm.rw.n_imm, sm.rw.n_pre, sm.ws, sm.caps.max_waiting, bins, d_hw);
   if (with_l)
     YDC_LAUNCH(c, "k_outlook_leases", k_outlook_leases, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0,
                c->stream, sm.lt, sm.d_insp_rec.p, bins, d_hl);
@@ -5344,8 +5354,8 @@ int ydc_stream_outlook_get(ydc_context* c, const uint32_t* env_id, const uint32_
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   std::vector<unsigned long long> res(n_res);
   std::vector<uint32_t> hist((size_t)bins * 4);
-  HIP_TRY(c, hipMemcpy(res.data(), sm.d_outlook_res.p, n_res * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(hist.data(), sm.d_outlook_hist.p, (size_t)bins * 16, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(res.data(), sm.outlook.res.p, n_res * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(hist.data(), sm.outlook.hist.p, (size_t)bins * 16, hipMemcpyDeviceToHost));
   // The per-digest histograms fanned out to the queries (the last bin is nobody's).
   for (uint32_t q = 0; q < n; ++q) {
     const unsigned long long* r = &res[(size_t)q * kOutlookCols];
@@ -5374,34 +5384,28 @@ int ydc_stream_inspect_waiting(ydc_context* c, uint64_t* out_tag, uint32_t* out_
   if (int rc = outlook_enter(c, "ydc_stream_inspect_waiting")) return rc;
   auto& sm = c->stream_mode;
   uint32_t n = 0;
-  if (sm.max_waiting) {
+  if (sm.waiting()) {
     HIP_TRY(c, hipMemcpy(&n, &sm.ws->count, 4, hipMemcpyDeviceToHost));
-    if (n > sm.max_waiting)
-      return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u on the device, room for %u", n, sm.max_waiting);
+    if (n > sm.caps.max_waiting)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u on the device, room for %u", n, sm.caps.max_waiting);
   }
   *out_n = n;
   if (n > cap) return fail(c, YDC_ERR_CAPACITY, "%u waiting requests > cap %u", n, cap);
   // Entries [0, |W|) of the mode's own columns; what the mode lacks: 0 (one immediate row outside rpc mode).
-  auto column = [&](void* dst, const void* src, size_t width) {
-    if (!dst || !n) return hipSuccess;
-    if (src) return hipMemcpy(dst, src, n * width, hipMemcpyDeviceToHost);
-    std::memset(dst, 0, n * width);
-    return hipSuccess;
-  };
-  HIP_TRY(c, column(out_tag, sm.wq.tag, 8));
-  HIP_TRY(c, column(out_env_id, sm.wq.env, 4));
-  HIP_TRY(c, column(out_min_version, sm.wq.minv, 4));
-  HIP_TRY(c, column(out_requestor_ip, sm.wq.ip, 4));
-  HIP_TRY(c, column(out_deadline, sm.wq.deadline, 8));
-  HIP_TRY(c, column(out_lease_for, sm.wl.w_for, 8));
-  HIP_TRY(c, column(out_n_immediate, sm.rw.n_imm, 4));
-  HIP_TRY(c, column(out_n_prefetch, sm.rw.n_pre, 4));
-  if (!sm.rw.n_imm && out_n_immediate) std::fill(out_n_immediate, out_n_immediate + n, 1u);
+  const auto from = w_cols(sm);
+  void* const to[kWCols] = {out_deadline,     out_tag,         out_lease_for,  out_env_id, out_min_version,
+                            out_requestor_ip, out_n_immediate, out_n_prefetch};
+  for (size_t k = 0; n && k < kWCols; ++k) {
+    if (!to[k]) continue;
+    if (from[k].p) HIP_TRY(c, hipMemcpy(to[k], from[k].p, n * from[k].width, hipMemcpyDeviceToHost));
+    else std::memset(to[k], 0, n * from[k].width);
+  }
+  if (!sm.rpc() && out_n_immediate) std::fill(out_n_immediate, out_n_immediate + n, 1u);
   return YDC_OK;
 }
 
 int ydc_stream_waiting_take(ydc_context* c, uint64_t* out_tags, uint32_t cap, uint32_t* out_n) {
-  if (!c || !out_n || !c->stream_mode.active || !c->stream_mode.max_waiting) return YDC_ERR_INVALID_ARGUMENT;
+  if (!c || !out_n || !c->stream_mode.active || !c->stream_mode.waiting()) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -5449,10 +5453,10 @@ int ydc_stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_r
 // statistics (padding — W's unused or expired slots, the new region's tail — counts nowhere).
 static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tasks) {
   auto& sm = c->stream_mode;
-  const uint32_t n_res = std::min(sm.h_wout->n_resolved, sm.max_waiting);
+  const uint32_t n_res = std::min(sm.h_wout->n_resolved, sm.caps.max_waiting);
   const uint32_t n_wait = sm.h_wout->n_waiting;
-  if (n_wait > sm.max_waiting)
-    return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u > max_waiting %u", n_wait, sm.max_waiting);
+  if (n_wait > sm.caps.max_waiting)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u > max_waiting %u", n_wait, sm.caps.max_waiting);
   uint32_t expired = 0;  // (a resolved Timeout is an expired entry: a live one that timed out stays)
   for (uint32_t i = 0; i < n_res; ++i) expired += sm.h_res_idx[i] == YDC_IDX_TIMEOUT;
   if (n_res && wt->out_resolved_tags != sm.h_res_tag)
@@ -5465,7 +5469,7 @@ static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tas
   const uint32_t live = sm.n_waiting - std::min(sm.n_waiting, expired);
   c->stats.n_tasks = n_tasks + live;
   // (the new region's padding is taken off by the caller, as in a plain tick; W's here)
-  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_waiting - live);
+  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.caps.max_waiting - live);
   sm.n_waiting = n_wait;
   sm.last_now = wt->now;
   return YDC_OK;
@@ -5473,17 +5477,34 @@ static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tas
 
 // The lease outcome block is this tick's and |L| is in range.
 static bool stream_lease_outcome_ok(const ydc_context::Stream& sm) {
-  if (sm.max_book && (sm.h_bout->tick_no != sm.lease_tick || sm.h_bout->n_entries > sm.max_book)) return false;
-  return sm.h_lout->tick_no == sm.lease_tick && sm.h_lout->n_leases <= sm.max_leases;
+  if (sm.max_book && (sm.book.h_bout->tick_no != sm.lease_tick || sm.book.h_bout->n_entries > sm.max_book)) return false;
+  return sm.h_lout->tick_no == sm.lease_tick && sm.h_lout->n_leases <= sm.caps.max_leases;
 }
 
+// What the steps of a tick hand on to the steps behind them (stream_tick). Leaving a tick while
+// the removal route's leases are parked, by whichever return, sweeps them.
+struct TickState {
+  ydc_context* c;
+  uint32_t rows_new = 0;    // check: the rows of an rpc tick's new requests
+  uint32_t n_ids = 0;       // check: the reported ids
+  bool structural = false;  // heartbeats: they took the eager path
+  uint32_t graph_upd = 0;   // heartbeats, expiry: the heartbeats that are left to the step
+  bool parked = false;      // expiry: the tick removes servants, and their leases are parked
+  LeaseTick lt_alive{};     // expiry: the lease arguments with the reports renumbered
+  BatchPlan eager;          // run: the plan of a batch the host placed itself
+  const BatchPlan* plan = nullptr;  // run: the plan the batch was placed with
+  uint32_t rounds = 0;              // run: ... and the passes it took
+  ~TickState() {
+    if (parked) alive_orphans_after_error(c);
+  }
+};
+
 // The lease part of a tick's ending, once the outcome is known to be good: renewal and report
-// answers to the caller, the host's mirror of |L| and the statistics.
-static void stream_lease_apply(ydc_context* c, const LeaseTick* lt) {
+// answers to the caller, the host's mirror of |L| and the statistics. n_ids: the reported ids.
+static void stream_lease_apply(ydc_context* c, const LeaseTick* lt, uint32_t n_ids) {
   auto& sm = c->stream_mode;
   const LeaseOutcome& o = *sm.h_lout;
   if (lt->n_renew) std::memcpy(lt->out_renewed, sm.h_renewed, lt->n_renew);
-  const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
   if (n_ids) std::memcpy(lt->out_unknown, sm.h_unknown, n_ids);
   *lt->out_n_leases = o.n_leases;
   c->stats.leases_expired = o.expired;
@@ -5491,39 +5512,41 @@ static void stream_lease_apply(ydc_context* c, const LeaseTick* lt) {
   c->stats.leases_freed = o.freed;
   c->stats.renewals_refused = o.renew_refused;
   sm.n_leases = o.n_leases;
-  if (sm.max_book) sm.n_book = sm.h_bout->n_entries;
+  if (sm.max_book) sm.book.n = sm.book.h_bout->n_entries;
   sm.last_now = lt->now;
 }
 
 // Leased mode, after the step: the ids and the lease part.
-static int stream_lease_finish(ydc_context* c, const LeaseTick* lt, uint32_t n_tasks) {
+static int stream_lease_finish(ydc_context* c, const LeaseTick* lt, uint32_t n_tasks, uint32_t n_ids) {
   auto& sm = c->stream_mode;
   if (!stream_lease_outcome_ok(sm))
     return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: outcome of tick %u (expected %u), %u leases of %u",
-                sm.h_lout->tick_no, sm.lease_tick, sm.h_lout->n_leases, sm.max_leases);
-  stream_lease_apply(c, lt);
+                sm.h_lout->tick_no, sm.lease_tick, sm.h_lout->n_leases, sm.caps.max_leases);
+  stream_lease_apply(c, lt, n_ids);
   if (n_tasks) std::memcpy(lt->out_task_id, sm.h_task_id, (size_t)n_tasks * 8);
   return YDC_OK;
 }
 
 // RPC mode, after the step: every list to the caller, the host's mirrors of |W|, rows(W) and |L|,
 // and the statistics (n_tasks counts the batch's rows; padding counts nowhere).
-static int stream_rpc_finish(ydc_context* c, const WaitTick* wt, const LeaseTick* lt, const RpcTick* rt,
-                             uint32_t n_req, uint32_t* out_servant_idx) {
+static int stream_rpc_finish(ydc_context* c, const StreamCall& t, const TickState& ts) {
   auto& sm = c->stream_mode;
+  const WaitTick* wt = t.wt;
+  const LeaseTick* lt = t.lt;
+  const RpcTick* rt = t.rt;
   const LeaseOutcome& lo = *sm.h_lout;
   const RpcOutcome& o = *sm.rh.outcome;
-  if (!stream_lease_outcome_ok(sm) || o.n_waiting > sm.max_waiting || o.n_resolved > sm.max_waiting ||
-      o.n_rows > sm.max_rows || o.n_res_grants > sm.max_rows)
+  if (!stream_lease_outcome_ok(sm) || o.n_waiting > sm.caps.max_waiting || o.n_resolved > sm.caps.max_waiting ||
+      o.n_rows > sm.caps.max_rows || o.n_res_grants > sm.caps.max_rows)
     return fail(c, YDC_ERR_NOT_CONVERGED, "rpc stream: outcome of tick %u (expected %u), %u leases, %u waiting, %u rows",
                 lo.tick_no, sm.lease_tick, lo.n_leases, o.n_waiting, o.n_rows);
-  if (sm.rows_new) {
-    std::memcpy(out_servant_idx, sm.rh.new_srv, (size_t)sm.rows_new * 4);
-    std::memcpy(lt->out_task_id, sm.rh.new_id, (size_t)sm.rows_new * 8);
+  if (ts.rows_new) {
+    std::memcpy(t.out_servant_idx, sm.rh.new_srv, (size_t)ts.rows_new * 4);
+    std::memcpy(lt->out_task_id, sm.rh.new_id, (size_t)ts.rows_new * 8);
   }
-  if (n_req) {
-    std::memcpy(rt->out_status, sm.rh.status, (size_t)n_req * 4);
-    std::memcpy(rt->out_n_granted, sm.rh.n_granted, (size_t)n_req * 4);
+  if (t.n_tasks) {
+    std::memcpy(rt->out_status, sm.rh.status, (size_t)t.n_tasks * 4);
+    std::memcpy(rt->out_n_granted, sm.rh.n_granted, (size_t)t.n_tasks * 4);
   }
   if (o.n_resolved) {
     std::memcpy(wt->out_resolved_tags, sm.rh.res_tag, (size_t)o.n_resolved * 8);
@@ -5535,12 +5558,12 @@ static int stream_rpc_finish(ydc_context* c, const WaitTick* wt, const LeaseTick
     std::memcpy(rt->out_resolved_servant_idx, sm.rh.res_srv, (size_t)o.n_res_grants * 4);
     std::memcpy(wt->out_resolved_task_id, sm.rh.res_id, (size_t)o.n_res_grants * 8);
   }
-  stream_lease_apply(c, lt);
+  stream_lease_apply(c, lt, ts.n_ids);
   *wt->out_n_resolved = o.n_resolved;
   *wt->out_n_waiting = o.n_waiting;
   *rt->out_n_waiting_rows = o.n_waiting_rows;
   c->stats.n_tasks = o.n_rows;
-  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_rows - o.n_rows);  // padding
+  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.caps.max_rows - o.n_rows);  // padding
   sm.n_waiting = o.n_waiting;
   sm.n_wait_rows = o.n_waiting_rows;
   return YDC_OK;
@@ -5554,97 +5577,81 @@ static int stream_rpc_finish(ydc_context* c, const WaitTick* wt, const LeaseTick
 // tick's clock.
 static int stream_answer_eager(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
-  if (sm.max_waiting || sm.max_leases) {  // (ungated; in leased mode with the ids and the leases)
+  if (sm.waiting() || sm.leased()) {  // (ungated; in leased mode with the ids and the leases)
     enqueue_stream_answer(c, a, nullptr, kNone);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
   } else {
-    HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.max_tasks * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(sm.h_out, c->d_out_idx.p, (size_t)sm.caps.max_tasks * 4, hipMemcpyDeviceToHost));
   }
   return YDC_OK;
 }
 
-// The end of every tick: the statistics of the placement (p, rounds) without the padding, waiting
-// mode's resolved list, the answers to the caller.
-static int stream_tick_finish(ydc_context* c, const BatchPlan& p, uint32_t rounds, uint32_t n_tasks,
-                              uint32_t* out_servant_idx, const WaitTick* wt, const LeaseTick* lt,
-                              const RpcTick* rt) {
-  auto& sm = c->stream_mode;
-  fill_stats(c, p, rounds);
-  if (rt) return stream_rpc_finish(c, wt, lt, rt, n_tasks, out_servant_idx);
-  c->stats.n_tasks = n_tasks;
-  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.max_tasks - n_tasks);  // padding
-  if (wt)
-    if (int rc = stream_wait_finish(c, wt, n_tasks)) return rc;
-  if (lt)
-    if (int rc = stream_lease_finish(c, lt, n_tasks)) return rc;
-  if (n_tasks && out_servant_idx != sm.h_out) std::memcpy(out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
-  return YDC_OK;
-}
+// ---- a tick, step by step: check, heartbeats, servants' expiry, stage, run, finish ----
 
-static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
-                       const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
-                       const uint32_t* release_servant_idx, uint32_t n_rel, const ydc_task_soa* tasks,
-                       uint32_t n_tasks, uint32_t* out_servant_idx, const WaitTick* wt,
-                       const LeaseTick* lt = nullptr, const RpcTick* rt = nullptr) {
-  if (!c || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
+// Step 1: everything a tick can be refused for, in a fixed order, before anything of the stream
+// or the registry is written — except the stamps of the two OnceMarks, which a refused tick may
+// leave advanced. Hands on: the rows of an rpc tick's new requests and the reported ids.
+static int stream_tick_check(ydc_context* c, const StreamCall& t, TickState* ts) {
   auto& sm = c->stream_mode;
-  if (sm.max_rows && !rt)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_rpc takes ydc_stream_tick_rpc");
-  if (rt && !sm.max_rows)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_rpc on a context begun without ydc_stream_begin_rpc");
-  if (sm.max_leases && sm.max_waiting && !(wt && lt))
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_waiting_leased takes "
-                "ydc_stream_tick_waiting_leased");
-  if (wt && lt && !(sm.max_leases && sm.max_waiting))
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_waiting_leased on a context begun without a waiting "
-                "queue and a lease table");
-  if (lt && !sm.max_leases)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_leased on a context begun without a lease table");
-  if (!lt && sm.max_leases)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_leased takes "
-                "ydc_stream_tick_leased");
-  if (wt && !sm.max_waiting)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_tick_waiting on a context begun without a waiting queue");
-  if (!wt && sm.max_waiting)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with ydc_stream_begin_waiting takes "
-                "ydc_stream_tick_waiting");
-  if (n_upd > sm.max_upd || n_rel > sm.max_rel || n_tasks > sm.max_tasks)
+  const WaitTick* wt = t.wt;
+  const LeaseTick* lt = t.lt;
+  const RpcTick* rt = t.rt;
+  const uint32_t n_upd = t.n_upd, n_tasks = t.n_tasks;
+  // A stream takes the ticks of its mode. Of the stream's mode and the call's, the one that has
+  // more parts names the mismatch.
+  static const struct {
+    const char *begin, *tick, *part;
+  } kModes[] = {{"ydc_stream_begin", "ydc_stream_tick", ""},
+                {"ydc_stream_begin_waiting", "ydc_stream_tick_waiting", "a waiting queue"},
+                {"ydc_stream_begin_leased", "ydc_stream_tick_leased", "a lease table"},
+                {"ydc_stream_begin_waiting_leased", "ydc_stream_tick_waiting_leased", "a waiting queue and a lease table"},
+                {"ydc_stream_begin_rpc", "ydc_stream_tick_rpc", "ydc_stream_begin_rpc"}};
+  const int has = sm.rpc() ? 4 : sm.waiting() && sm.leased() ? 3 : sm.leased() ? 2 : sm.waiting() ? 1 : 0;
+  const int got = rt ? 4 : wt && lt ? 3 : lt ? 2 : wt ? 1 : 0;
+  if (has > got)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "a context begun with %s takes %s", kModes[has].begin, kModes[has].tick);
+  if (got > has)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s on a context begun without %s", kModes[got].tick, kModes[got].part);
+  if (n_upd > sm.caps.max_updates || t.n_rel > sm.caps.max_releases || n_tasks > sm.caps.max_tasks)
     return fail(c, YDC_ERR_CAPACITY, "tick (%u updates, %u releases, %u tasks) exceeds the capacity "
-                "given to ydc_stream_begin (%u, %u, %u)", n_upd, n_rel, n_tasks, sm.max_upd,
-                sm.max_rel, sm.max_tasks);
-  if ((n_upd && (!upd_idx || !upd_rows)) || (n_rel && !release_servant_idx) ||
-      (n_tasks && (!tasks || !out_servant_idx)))
+                "given to ydc_stream_begin (%u, %u, %u)", n_upd, t.n_rel, n_tasks, sm.caps.max_updates,
+                sm.caps.max_releases, sm.caps.max_tasks);
+  if ((n_upd && (!t.upd_idx || !t.upd_rows)) || (t.n_rel && !t.rel) || (n_tasks && (!t.tasks || !t.out_servant_idx)))
     return YDC_ERR_INVALID_ARGUMENT;
+  // (one clock per tick: a waiting tick meets this refusal in its own part, a leased one in its)
+  const int64_t now = wt ? wt->now : lt ? lt->now : 0;
+  auto clock_runs_back = [&] {
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "now %lld is before the previous tick's %lld", (long long)now,
+                (long long)sm.last_now);
+  };
   if (wt) {
     // (nothing is applied unless the whole tick is acceptable)
-    if ((uint64_t)sm.n_waiting + n_tasks > sm.max_waiting)
+    if ((uint64_t)sm.n_waiting + n_tasks > sm.caps.max_waiting)
       return fail(c, YDC_ERR_CAPACITY, "%u waiting + %u new requests > max_waiting %u", sm.n_waiting, n_tasks,
-                  sm.max_waiting);
-    if (wt->now < sm.last_now)
-      return fail(c, YDC_ERR_INVALID_ARGUMENT, "now %lld is before the previous tick's %lld", (long long)wt->now,
-                  (long long)sm.last_now);
+                  sm.caps.max_waiting);
+    if (now < sm.last_now) return clock_runs_back();
     if ((n_tasks && (!wt->deadlines || !wt->tags)) || !wt->out_n_resolved || !wt->out_n_waiting ||
         !wt->out_resolved_tags || !wt->out_resolved_idx || (lt && !wt->out_resolved_task_id))
       return YDC_ERR_INVALID_ARGUMENT;
   }
   if (lt) {
     // (nothing is applied unless the whole tick is acceptable)
-    if (lt->n_renew > sm.max_renew || lt->n_free > sm.max_free || lt->n_rep > sm.max_rep)
+    if (lt->n_renew > sm.caps.max_renewals || lt->n_free > sm.caps.max_frees || lt->n_rep > sm.caps.max_reports)
       return fail(c, YDC_ERR_CAPACITY, "tick (%u renewals, %u frees by id, %u reports) exceeds the capacity given "
-                  "to ydc_stream_begin_leased (%u, %u, %u)", lt->n_renew, lt->n_free, lt->n_rep, sm.max_renew,
-                  sm.max_free, sm.max_rep);
+                  "to ydc_stream_begin_leased (%u, %u, %u)", lt->n_renew, lt->n_free, lt->n_rep, sm.caps.max_renewals,
+                  sm.caps.max_frees, sm.caps.max_reports);
     if ((lt->n_renew && (!lt->renew_id || !lt->renew_exp || !lt->out_renewed)) || (lt->n_free && !lt->free_id) ||
         (lt->n_rep && (!lt->rep_srv || !lt->rep_off)) || (n_tasks && (!lt->lease_exp || !lt->out_task_id)) ||
         !lt->out_n_leases)
       return YDC_ERR_INVALID_ARGUMENT;
     // (with a waiting queue: every waiting entry may be granted in this tick)
-    if (!rt && wt && (uint64_t)sm.n_leases + sm.n_waiting + n_tasks > sm.max_leases)
+    if (!rt && wt && (uint64_t)sm.n_leases + sm.n_waiting + n_tasks > sm.caps.max_leases)
       return fail(c, YDC_ERR_CAPACITY, "%u leases + %u waiting + %u new requests > max_leases %u", sm.n_leases,
-                  sm.n_waiting, n_tasks, sm.max_leases);
-    if (!rt && (uint64_t)sm.n_leases + n_tasks > sm.max_leases)
+                  sm.n_waiting, n_tasks, sm.caps.max_leases);
+    if (!rt && (uint64_t)sm.n_leases + n_tasks > sm.caps.max_leases)
       return fail(c, YDC_ERR_CAPACITY, "%u leases + %u new requests > max_leases %u", sm.n_leases, n_tasks,
-                  sm.max_leases);
+                  sm.caps.max_leases);
     if (rt) {
       // (every row of W's entries and of the new requests may be granted in this tick)
       if ((n_tasks && (!rt->n_imm || !rt->n_pre || !rt->out_status || !rt->out_n_granted)) ||
@@ -5657,238 +5664,221 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
         if (!r) return fail(c, YDC_ERR_INVALID_ARGUMENT, "request %u asks for no grant (n_immediate + n_prefetch == 0)", i);
         rows += r;
       }
-      if (sm.n_wait_rows + rows > sm.max_rows)
+      if (sm.n_wait_rows + rows > sm.caps.max_rows)
         return fail(c, YDC_ERR_CAPACITY, "%u waiting rows + %llu new rows > max_rows %u", sm.n_wait_rows,
-                    (unsigned long long)rows, sm.max_rows);
-      if ((uint64_t)sm.n_leases + sm.n_wait_rows + rows > sm.max_leases)
+                    (unsigned long long)rows, sm.caps.max_rows);
+      if ((uint64_t)sm.n_leases + sm.n_wait_rows + rows > sm.caps.max_leases)
         return fail(c, YDC_ERR_CAPACITY, "%u leases + %u waiting rows + %llu new rows > max_leases %u", sm.n_leases,
-                    sm.n_wait_rows, (unsigned long long)rows, sm.max_leases);
-      sm.rows_new = (uint32_t)rows;
+                    sm.n_wait_rows, (unsigned long long)rows, sm.caps.max_leases);
+      ts->rows_new = (uint32_t)rows;
     }
-    if (lt->now < sm.last_now)
-      return fail(c, YDC_ERR_INVALID_ARGUMENT, "now %lld is before the previous tick's %lld", (long long)lt->now,
-                  (long long)sm.last_now);
+    if (!wt && now < sm.last_now) return clock_runs_back();
     if (lt->n_rep) {
       if (lt->rep_off[0] != 0) return fail(c, YDC_ERR_INVALID_ARGUMENT, "report_off[0] must be 0");
       for (uint32_t r = 0; r < lt->n_rep; ++r)
         if (lt->rep_off[r + 1] < lt->rep_off[r])
           return fail(c, YDC_ERR_INVALID_ARGUMENT, "report_off must not decrease (entry %u)", r + 1);
       const uint32_t n_ids = lt->rep_off[lt->n_rep];
-      if (n_ids > sm.max_rep_ids)
-        return fail(c, YDC_ERR_CAPACITY, "%u reported ids > max_report_ids %u", n_ids, sm.max_rep_ids);
+      if (n_ids > sm.caps.max_report_ids)
+        return fail(c, YDC_ERR_CAPACITY, "%u reported ids > max_report_ids %u", n_ids, sm.caps.max_report_ids);
       if (n_ids && (!lt->rep_id || !lt->out_unknown)) return YDC_ERR_INVALID_ARGUMENT;
+      ts->n_ids = n_ids;
       // A servant reports at most once per tick (a servant this tick's heartbeats add may report too).
       uint32_t S = c->n_servants;
-      for (uint32_t i = 0; i < n_upd; ++i) S = std::max(S, upd_idx[i] + 1);
-      if (sm.rep_seen.size() < S) sm.rep_seen.resize(S, 0);
-      if (++sm.rep_mark == 0) {  // (a mark per look at a report list, refused ticks included)
-        std::fill(sm.rep_seen.begin(), sm.rep_seen.end(), 0u);
-        sm.rep_mark = 1;
-      }
-      uint32_t bad = kNone;
-      for (uint32_t r = 0; r < lt->n_rep && bad == kNone; ++r) {
+      for (uint32_t i = 0; i < n_upd; ++i) S = std::max(S, t.upd_idx[i] + 1);
+      sm.rep_once.begin(S);
+      for (uint32_t r = 0; r < lt->n_rep; ++r) {
         const uint32_t s = lt->rep_srv[r];
-        if (s >= S || sm.rep_seen[s] == sm.rep_mark) bad = r;
-        else sm.rep_seen[s] = sm.rep_mark;
-      }
-      if (bad != kNone) {
-        return fail(c, YDC_ERR_INVALID_ARGUMENT, "report %u names servant %u, which is unknown or reports twice", bad,
-                    lt->rep_srv[bad]);
+        if (s >= S || !sm.rep_once.first(s))
+          return fail(c, YDC_ERR_INVALID_ARGUMENT, "report %u names servant %u, which is unknown or reports twice", r, s);
       }
     }
     if (sm.max_book) {
       // (conservative like the |L| bound: every reported id may be permitted, no entry dropped)
-      const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
-      if (sm.book_staged && sm.stage_stid.size() != n_ids)
+      if (sm.book.staged.on && sm.book.staged.stid.size() != ts->n_ids)
         return fail(c, YDC_ERR_INVALID_ARGUMENT, "%zu ids staged with ydc_stream_book_stage, %u reported",
-                    sm.stage_stid.size(), n_ids);
-      if ((uint64_t)sm.n_book + n_ids > sm.max_book)
-        return fail(c, YDC_ERR_CAPACITY, "%u book entries + %u reported ids > max_book %u", sm.n_book, n_ids,
+                    sm.book.staged.stid.size(), ts->n_ids);
+      if ((uint64_t)sm.book.n + ts->n_ids > sm.max_book)
+        return fail(c, YDC_ERR_CAPACITY, "%u book entries + %u reported ids > max_book %u", sm.book.n, ts->n_ids,
                     sm.max_book);
     }
   }
-  if (sm.alive) {
+  if (sm.alive.on) {
     // Every heartbeat brings its expiry, and a servant at most one (k_apply_tick leaves the winner of
     // two rows for one servant undefined; an expiry cannot be).
-    if (sm.alive_staged ? sm.alive_stage.size() != n_upd : n_upd != 0)
+    if (sm.alive.staged ? sm.alive.stage.size() != n_upd : n_upd != 0)
       return fail(c, YDC_ERR_INVALID_ARGUMENT, "%u heartbeats, %zu expiries staged with ydc_stream_alive_stage", n_upd,
-                  sm.alive_staged ? sm.alive_stage.size() : (size_t)0);
+                  sm.alive.staged ? sm.alive.stage.size() : (size_t)0);
     const uint64_t S = (uint64_t)c->n_servants + n_upd;  // (the tick's heartbeats may add that many rows)
-    if (sm.alive_seen.size() < S) sm.alive_seen.resize(S, 0);
-    if (++sm.alive_mark == 0) {
-      std::fill(sm.alive_seen.begin(), sm.alive_seen.end(), 0u);
-      sm.alive_mark = 1;
-    }
+    sm.alive.once.begin(S);
     for (uint32_t i = 0; i < n_upd; ++i) {
-      const uint32_t s = upd_idx[i];
+      const uint32_t s = t.upd_idx[i];
       if (s >= S) return fail(c, YDC_ERR_INVALID_ARGUMENT, "servant index %u out of order", s);
-      if (sm.alive_seen[s] == sm.alive_mark)
+      if (!sm.alive.once.first(s))
         return fail(c, YDC_ERR_INVALID_ARGUMENT, "heartbeat %u names servant %u a second time", i, s);
-      sm.alive_seen[s] = sm.alive_mark;
     }
   }
-  if (upd_env_masks && (env_words == 0 || env_words > YDC_MAX_ENV_WORDS))
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "env_words %u out of range", env_words);
-  HIP_TRY(c, hipSetDevice(c->device));
-  // Heartbeats: structural ones (and new servants) take the eager path. With masks (the wide
-  // form) a changed environment set is structural like any other change; without them, rows of
-  // a table with several mask words cannot say what the servant advertises — it keeps its
-  // environments, and a NEW servant (which would silently have none) is refused.
-  const uint32_t EW = c->env_words;
-  bool structural = false;
-  if (!upd_env_masks && EW > 1)  // (every entry is looked at: the scan below stops at the first structural one)
+  if (t.upd_env_masks && (t.env_words == 0 || t.env_words > YDC_MAX_ENV_WORDS))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "env_words %u out of range", t.env_words);
+  // Without masks (the plain form), rows of a table with several mask words cannot say what the
+  // servant advertises: a known servant keeps its environments, and a NEW one (which would
+  // silently have none) is refused.
+  if (!t.upd_env_masks && c->env_words > 1)
     for (uint32_t i = 0; i < n_upd; ++i)
-      if (upd_idx[i] >= c->n_servants)
+      if (t.upd_idx[i] >= c->n_servants)
         return fail(c, YDC_ERR_INVALID_ARGUMENT, "a tick that adds a servant to a table with %u mask "
-                    "words needs its environments: use ydc_stream_tick_wide", EW);
-  for (uint32_t i = 0; i < n_upd && !structural; ++i)
-    structural = row_is_structural(c, upd_idx[i], upd_rows[i], upd_env_masks, env_words, i);
-  uint32_t graph_upd = n_upd;
-  auto apply_eager = [&]() -> int {
-    if (upd_env_masks) return ydc_update_servants_wide(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd);
-    if (EW == 1) return ydc_update_servants(c, upd_idx, upd_rows, n_upd);
-    // Rows without masks on a wide table: the (known) servants keep their environments.
-    std::vector<uint64_t> env((size_t)n_upd * EW, 0);
-    for (uint32_t i = 0; i < n_upd; ++i)
-      if (upd_idx[i] < c->n_servants)  // (new servants were refused above)
-        std::copy_n(&c->h_env[(size_t)upd_idx[i] * EW], EW, &env[(size_t)i * EW]);
-    return ydc_update_servants_wide(c, upd_idx, upd_rows, env.data(), EW, n_upd);
-  };
-  if (structural) {
-    if (int rc = apply_eager()) return rc;
-    graph_upd = 0;
+                    "words needs its environments: use ydc_stream_tick_wide", c->env_words);
+  return YDC_OK;
+}
+
+// All of a tick's heartbeats applied to the registry now, the way a structural one has to go.
+static int stream_heartbeats_eager(ydc_context* c, const StreamCall& t) {
+  const uint32_t EW = c->env_words, n_upd = t.n_upd;
+  if (t.upd_env_masks) return ydc_update_servants_wide(c, t.upd_idx, t.upd_rows, t.upd_env_masks, t.env_words, n_upd);
+  if (EW == 1) return ydc_update_servants(c, t.upd_idx, t.upd_rows, n_upd);
+  // Rows without masks on a wide table: the (known) servants keep their environments.
+  std::vector<uint64_t> env((size_t)n_upd * EW, 0);
+  for (uint32_t i = 0; i < n_upd; ++i)
+    if (t.upd_idx[i] < c->n_servants)  // (new servants were refused by the check)
+      std::copy_n(&c->h_env[(size_t)t.upd_idx[i] * EW], EW, &env[(size_t)i * EW]);
+  return ydc_update_servants_wide(c, t.upd_idx, t.upd_rows, env.data(), EW, n_upd);
+}
+
+// Step 2, the heartbeats: structural ones (and new servants) take the eager path — with masks (the
+// wide form) a changed environment set is structural like any other change — and leave nothing
+// to the step; the others are mirrored on the host and left to k_apply_tick.
+static int stream_tick_heartbeats(ydc_context* c, const StreamCall& t, TickState* ts) {
+  auto& sm = c->stream_mode;
+  for (uint32_t i = 0; i < t.n_upd && !ts->structural; ++i)
+    ts->structural = row_is_structural(c, t.upd_idx[i], t.upd_rows[i], t.upd_env_masks, t.env_words, i);
+  ts->graph_upd = t.n_upd;
+  if (ts->structural) {
+    if (int rc = stream_heartbeats_eager(c, t)) return rc;
+    ts->graph_upd = 0;
   } else {
-    mirror_rows(c, upd_idx, upd_rows, n_upd);
+    mirror_rows(c, t.upd_idx, t.upd_rows, t.n_upd);
   }
   // Inspection (stream_inspect.h): a servant this tick's heartbeats appended was discovered now.
-  if (sm.inspect)
-    if (int rc = inspect_fit(c, lt->now)) return rc;
-  // Aliveness (servant_alive.h): step 5 is the whole of OnExpirationTimer. No servant can be due while
-  // the host's bound of min(E) is not below the clock; when it is, k_alive_due says who is, and a tick
-  // in which somebody is takes the removal route here, in front of the step.
-  bool removal = false;
-  struct ParkedGuard {  // (every return between the parking and the tick's ending sweeps the parked leases)
-    ydc_context* c;
-    bool armed = false;
-    ~ParkedGuard() {
-      if (armed) alive_orphans_after_error(c);
-    }
-  } parked{c};
-  LeaseTick lt_alive;
-  if (sm.alive) {
-    const int64_t now = lt->now;
-    if (int rc = alive_fit(c)) return rc;  // (rows the heartbeats added: "never" until filed below)
-    const int64_t* stage = sm.alive_stage.data();
-    bool filed = false;
-    if (structural) {  // (heartbeats that took the eager path: so do their expiries)
-      if (int rc = alive_file(c, upd_idx, stage, n_upd)) return rc;
-      filed = true;
-    }
-    for (uint32_t i = 0; i < n_upd; ++i) sm.alive_bound = std::min(sm.alive_bound, stage[i]);
-    sm.alive_removed.clear();
-    sm.alive_orphans = 0;
-    uint32_t n_due = 0;
-    if (sm.alive_bound < now) {
-      if (!filed)
-        if (int rc = alive_file(c, upd_idx, stage, n_upd)) return rc;  // (again inside the step: idempotent)
-      if (int rc = alive_due(c, now, &n_due)) return rc;
-    }
-    if (n_due) {
-      if (!structural) {  // (all of the tick's heartbeats eagerly, as the structural branch does)
-        if (int rc = apply_eager()) return rc;
-        graph_upd = 0;
-      }
-      sm.alive_removed.assign(sm.h_alive_list, sm.h_alive_list + n_due);
-      const uint32_t* gone = sm.alive_removed.data();
-      parked.armed = true;
-      if (int rc = remove_rows(c, gone, n_due, true)) return rc;
-      sm.alive_removals += n_due;
-      // The staged tick in the new numbering (the reports were validated on the caller's, above).
-      sm.alive_rel.assign(release_servant_idx, release_servant_idx + n_rel);
-      for (uint32_t& s : sm.alive_rel) s = alive_renumber(gone, n_due, s);
-      release_servant_idx = sm.alive_rel.data();
-      sm.alive_rep.assign(lt->rep_srv, lt->rep_srv + lt->n_rep);
-      for (uint32_t& s : sm.alive_rep) s = alive_renumber(gone, n_due, s);
-      lt_alive = *lt;
-      lt_alive.rep_srv = sm.alive_rep.data();
-      lt = &lt_alive;
-      removal = true;
-    }
+  if (sm.inspect.on)
+    if (int rc = inspect_fit(c, t.lt->now)) return rc;
+  return YDC_OK;
+}
+
+// Step 3, aliveness (servant_alive.h): the whole of OnExpirationTimer. No servant can be due while the
+// host's bound of min(E) is not below the clock; when it is, k_alive_due says who is, and a tick in
+// which somebody is takes the removal route here, in front of the step: the due rows leave the registry,
+// their leases are parked, and `t` gets the releases and reports rewritten in the new numbering.
+static int stream_tick_expiry(ydc_context* c, StreamCall& t, TickState* ts) {
+  auto& sm = c->stream_mode;
+  auto& al = sm.alive;
+  const int64_t now = t.lt->now;
+  const uint32_t n_upd = t.n_upd;
+  if (int rc = alive_fit(c)) return rc;  // (rows the heartbeats added: "never" until filed below)
+  const int64_t* stage = al.stage.data();
+  for (uint32_t i = 0; i < n_upd; ++i) al.bound = std::min(al.bound, stage[i]);
+  const bool alarm = al.bound < now;
+  // Heartbeats that took the eager path: so do their expiries. In front of an alarm the others' are
+  // filed as well (and again inside the step: idempotent).
+  if (ts->structural || alarm)
+    if (int rc = alive_file(c, t.upd_idx, stage, n_upd)) return rc;
+  al.removed.clear();
+  al.orphans = 0;
+  uint32_t n_due = 0;
+  if (alarm)
+    if (int rc = alive_due(c, now, &n_due)) return rc;
+  if (!n_due) return YDC_OK;
+  if (!ts->structural) {  // (all of the tick's heartbeats eagerly, as the structural branch does)
+    if (int rc = stream_heartbeats_eager(c, t)) return rc;
+    ts->graph_upd = 0;
   }
-  // The end of the tick; behind a removal the parked leases go first.
-  auto finish = [&](const BatchPlan& fp, uint32_t frounds) -> int {
-    if (removal) {
-      parked.armed = false;
-      if (int rc = alive_orphans(c)) return rc;
-    }
-    return stream_tick_finish(c, fp, frounds, n_tasks, out_servant_idx, wt, lt, rt);
-  };
-  if (sm.stale || c->tables_dirty)
-    if (int rc = stream_capture(c)) return rc;
-  // Stage the tick (padding = no-ops).
-  // (a caller that filled the arena itself — ydc_stream_buffers_get — has nothing to copy)
+  const uint32_t* due = (const uint32_t*)al.due.p;
+  al.removed.assign(due, due + n_due);
+  const uint32_t* gone = al.removed.data();
+  ts->parked = true;
+  if (int rc = remove_rows(c, gone, n_due, true)) return rc;
+  al.removals += n_due;
+  // The staged tick in the new numbering (the reports were validated on the caller's, by the check).
+  al.rel.assign(t.rel, t.rel + t.n_rel);
+  for (uint32_t& s : al.rel) s = alive_renumber(gone, n_due, s);
+  t.rel = al.rel.data();
+  al.rep.assign(t.lt->rep_srv, t.lt->rep_srv + t.lt->n_rep);
+  for (uint32_t& s : al.rep) s = alive_renumber(gone, n_due, s);
+  ts->lt_alive = *t.lt;
+  ts->lt_alive.rep_srv = al.rep.data();
+  t.lt = &ts->lt_alive;
+  return YDC_OK;
+}
+
+// Step 4: the tick into the arena (padding = no-ops), the staged columns consumed, the lease header
+// and the tick number written.
+static void stream_tick_stage(ydc_context* c, const StreamCall& t, const TickState& ts) {
+  auto& sm = c->stream_mode;
   const TickArena& h = sm.h;
-  if (graph_upd) {
-    if (upd_idx != h.upd_idx) std::memcpy(h.upd_idx, upd_idx, (size_t)graph_upd * 4);
-    if (upd_rows != h.upd_rows) std::memcpy(h.upd_rows, upd_rows, (size_t)graph_upd * sizeof(ydc_servant_row));
+  const LeaseTick* lt = t.lt;
+  const uint32_t graph_upd = ts.graph_upd, n_rel = t.n_rel, n_tasks = t.n_tasks, n_ids = ts.n_ids;
+  // (a caller that filled the arena itself — ydc_stream_buffers_get — has nothing to copy)
+  auto put = [](void* dst, const void* src, size_t n, size_t width) {
+    if (n && src != dst) std::memcpy(dst, src, n * width);
+  };
+  put(h.upd_idx, t.upd_idx, graph_upd, 4);
+  put(h.upd_rows, t.upd_rows, graph_upd, sizeof(ydc_servant_row));
+  for (uint32_t i = graph_upd; i < sm.caps.max_updates; ++i) h.upd_idx[i] = 0xFFFFFFFFu;
+  if (sm.alive.on) {  // (the staged expiries, consumed)
+    put(h.upd_exp, sm.alive.stage.data(), graph_upd, 8);
+    sm.alive.staged = false;
+    sm.alive.stage.clear();
   }
-  for (uint32_t i = graph_upd; i < sm.max_upd; ++i) h.upd_idx[i] = 0xFFFFFFFFu;
-  if (sm.alive) {  // (the staged expiries, consumed)
-    if (graph_upd) std::memcpy(h.upd_exp, sm.alive_stage.data(), (size_t)graph_upd * 8);
-    sm.alive_staged = false;
-    sm.alive_stage.clear();
-  }
-  if (n_rel && release_servant_idx != h.rel) std::memcpy(h.rel, release_servant_idx, (size_t)n_rel * 4);
-  for (uint32_t i = n_rel; i < sm.max_rel; ++i) h.rel[i] = 0xFFFFFFFFu;
+  put(h.rel, t.rel, n_rel, 4);
+  for (uint32_t i = n_rel; i < sm.caps.max_releases; ++i) h.rel[i] = 0xFFFFFFFFu;
   if (n_tasks) {
-    if (tasks->env_id != h.env) std::memcpy(h.env, tasks->env_id, (size_t)n_tasks * 4);
-    if (tasks->min_version != h.minv) std::memcpy(h.minv, tasks->min_version, (size_t)n_tasks * 4);
-    if (tasks->requestor_ip != h.ip) std::memcpy(h.ip, tasks->requestor_ip, (size_t)n_tasks * 4);
+    put(h.env, t.tasks->env_id, n_tasks, 4);
+    put(h.minv, t.tasks->min_version, n_tasks, 4);
+    put(h.ip, t.tasks->requestor_ip, n_tasks, 4);
   }
-  for (uint32_t i = n_tasks; i < sm.max_tasks; ++i) {
+  for (uint32_t i = n_tasks; i < sm.caps.max_tasks; ++i) {
     h.env[i] = 0xFFFFFFFFu;  // a digest nobody has: EnvironmentNotFound, consumes nothing
     h.minv[i] = 0;
     h.ip[i] = 0;
   }
-  if (wt) {
-    if (n_tasks && wt->deadlines != h.dl) std::memcpy(h.dl, wt->deadlines, (size_t)n_tasks * 8);
-    if (n_tasks && wt->tags != h.tag) std::memcpy(h.tag, wt->tags, (size_t)n_tasks * 8);
-    *h.now = wt->now;
+  if (t.wt) {
+    put(h.dl, t.wt->deadlines, n_tasks, 8);
+    put(h.tag, t.wt->tags, n_tasks, 8);
+    *h.now = t.wt->now;
   }
   if (lt) {
-    if (n_tasks) std::memcpy(h.lexp, lt->lease_exp, (size_t)n_tasks * 8);
-    if (lt->n_renew) {
-      std::memcpy(h.ren_id, lt->renew_id, (size_t)lt->n_renew * 8);
-      std::memcpy(h.ren_exp, lt->renew_exp, (size_t)lt->n_renew * 8);
-    }
-    if (lt->n_free) std::memcpy(h.free_id, lt->free_id, (size_t)lt->n_free * 8);
-    const uint32_t n_ids = lt->n_rep ? lt->rep_off[lt->n_rep] : 0;
-    if (lt->n_rep) {
-      std::memcpy(h.rep_srv, lt->rep_srv, (size_t)lt->n_rep * 4);
-      std::memcpy(h.rep_off, lt->rep_off, ((size_t)lt->n_rep + 1) * 4);
-    }
-    if (n_ids) std::memcpy(h.rep_id, lt->rep_id, (size_t)n_ids * 8);
+    put(h.lexp, lt->lease_exp, n_tasks, 8);
+    put(h.ren_id, lt->renew_id, lt->n_renew, 8);
+    put(h.ren_exp, lt->renew_exp, lt->n_renew, 8);
+    put(h.free_id, lt->free_id, lt->n_free, 8);
+    put(h.rep_srv, lt->rep_srv, lt->n_rep, 4);
+    put(h.rep_off, lt->rep_off, lt->n_rep ? (size_t)lt->n_rep + 1 : 0, 4);
+    put(h.rep_id, lt->rep_id, n_ids, 8);
     if (sm.max_book) {  // (the staged payload columns, consumed; nothing staged: zeros)
-      if (n_ids && sm.book_staged) {
-        std::memcpy(h.bk_stid, sm.stage_stid.data(), (size_t)n_ids * 8);
-        std::memcpy(h.bk_dkey, sm.stage_dkey.data(), (size_t)n_ids * 8);
+      if (sm.book.staged.on) {
+        put(h.bk_stid, sm.book.staged.stid.data(), n_ids, 8);
+        put(h.bk_dkey, sm.book.staged.dkey.data(), n_ids, 8);
       } else if (n_ids) {
         std::memset(h.bk_stid, 0, (size_t)n_ids * 8);
         std::memset(h.bk_dkey, 0, (size_t)n_ids * 8);
       }
-      sm.book_staged = false;
+      sm.book.staged.on = false;
     }
     // (the counts make the unused capacity a no-op; a tick number's low 30 bits are never 0)
     if ((++sm.lease_tick & kLeaseStamp) == 0) ++sm.lease_tick;
     *h.lh = LeaseHdr{lt->now, lt->n_renew, lt->n_free, lt->n_rep, n_ids, sm.lease_tick, 0};
   }
-  if (rt) {
-    if (n_tasks) {
-      std::memcpy(h.nimm, rt->n_imm, (size_t)n_tasks * 4);
-      std::memcpy(h.npre, rt->n_pre, (size_t)n_tasks * 4);
-    }
-    for (uint32_t i = n_tasks; i < sm.max_tasks; ++i) h.nimm[i] = h.npre[i] = 0;  // (no rows: padding)
+  if (t.rt) {
+    put(h.nimm, t.rt->n_imm, n_tasks, 4);
+    put(h.npre, t.rt->n_pre, n_tasks, 4);
+    for (uint32_t i = n_tasks; i < sm.caps.max_tasks; ++i) h.nimm[i] = h.npre[i] = 0;  // (no rows: padding)
   }
+}
+
+// Step 5: the staged tick run — replayed from the captured step (stream_graph=0: enqueued), or
+// enqueued eagerly where the step cannot be captured or its capture did not do.
+static int stream_tick_run(ydc_context* c, const StreamCall& t, TickState* ts) {
+  auto& sm = c->stream_mode;
+  const bool wt = t.wt != nullptr, lt = t.lt != nullptr;
   // The ticks placed eagerly place this batch from the arena's device mirror. Waiting mode: the
   // batch is W's region + the new requests in HBM (k_wait_gather), its placement goes to wt_out
   // and k_wait_compact answers the caller.
@@ -5896,20 +5886,18 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
                                     : ydc_task_soa{sm.d.env, sm.d.minv, sm.d.ip};
   uint32_t* const batch_out = wt ? sm.wt_out : lt ? sm.lt_out : c->d_out_idx.p;
   const uint32_t NB = stream_batch_n(sm);
+  ts->plan = &ts->eager;
   if (sm.eager_only) {
     // The same step, enqueued instead of replayed: mirror the arena, apply, gather, place, answer.
     // (> kMaxWaveClasses classes: the bin sort, which needs at most that many, is never planned,
     // so place_batch never repeats the batch here)
-    HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in.p, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
     if (lt) enqueue_lease_pre(c, sm.d);
     enqueue_apply_tick(c, sm.d);
     if (wt) enqueue_stream_gather(c, sm.d);
-    BatchPlan pe;
-    uint32_t rounds_e = 0;
-    if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &pe, &rounds_e))
+    if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &ts->eager, &ts->rounds))
       return rc;
-    if (int rc = stream_answer_eager(c, sm.d)) return rc;
-    return finish(pe, rounds_e);
+    return stream_answer_eager(c, sm.d);
   }
   const bool second = sm.swaps && c->d_running.p == sm.run_b;
   if (sm.swaps && !second && c->d_running.p != sm.run_a)
@@ -5941,12 +5929,11 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
     note_bin_overflow(c);
     // (the captured step read the arena in place: the device copy is stale; in waiting mode the
     // gathered batch in HBM is what is placed again, and W is still as the gather read it)
-    HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
-    BatchPlan p2;
-    if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &p2, &rounds))
+    HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in.p, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
+    ts->rounds = rounds;
+    if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &ts->eager, &ts->rounds))
       return rc;
-    if (int rc = stream_answer_eager(c, sm.d)) return rc;
-    return finish(p2, rounds);
+    return stream_answer_eager(c, sm.d);
   }
   if (p.wave_path) {
     if (c->h_prm->n_changed[(sm.passes - 1) & 63] != 0) {
@@ -5975,23 +5962,63 @@ static int stream_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servan
       }
     }
   }
-  return finish(p, rounds);
+  ts->plan = &p;
+  ts->rounds = rounds;
+  return YDC_OK;
+}
+
+// Step 6, the end of every tick: the statistics of the placement without the padding,
+// waiting mode's resolved list, the answers to the caller.
+static int stream_tick_finish(ydc_context* c, const StreamCall& t, const TickState& ts) {
+  auto& sm = c->stream_mode;
+  const uint32_t n_tasks = t.n_tasks;
+  fill_stats(c, *ts.plan, ts.rounds);
+  if (t.rt) return stream_rpc_finish(c, t, ts);
+  c->stats.n_tasks = n_tasks;
+  c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.caps.max_tasks - n_tasks);  // padding
+  if (t.wt)
+    if (int rc = stream_wait_finish(c, t.wt, n_tasks)) return rc;
+  if (t.lt)
+    if (int rc = stream_lease_finish(c, t.lt, n_tasks, ts.n_ids)) return rc;
+  if (n_tasks && t.out_servant_idx != sm.h_out) std::memcpy(t.out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
+  return YDC_OK;
+}
+
+// (t by value: the removal route points it at the renumbered releases and reports)
+static int stream_tick(ydc_context* c, StreamCall t) {
+  if (!c || !c->stream_mode.active) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  TickState ts{c};
+  if (int rc = stream_tick_check(c, t, &ts)) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int rc = stream_tick_heartbeats(c, t, &ts)) return rc;
+  if (sm.alive.on)
+    if (int rc = stream_tick_expiry(c, t, &ts)) return rc;
+  if (sm.stale || c->tables_dirty)
+    if (int rc = stream_capture(c)) return rc;
+  stream_tick_stage(c, t, ts);
+  if (int rc = stream_tick_run(c, t, &ts)) return rc;
+  if (ts.parked) {  // (behind a removal the parked leases go first)
+    ts.parked = false;
+    if (int rc = alive_orphans(c)) return rc;
+  }
+  return stream_tick_finish(c, t, ts);
 }
 
 int ydc_stream_tick_wide(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
                          const uint64_t* upd_env_masks, uint32_t env_words, uint32_t n_upd,
                          const uint32_t* release_servant_idx, uint32_t n_rel, const ydc_task_soa* tasks,
                          uint32_t n_tasks, uint32_t* out_servant_idx) {
-  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
-                     n_tasks, out_servant_idx, nullptr);
+  return stream_tick(c, StreamCall{upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
+                                   n_tasks, out_servant_idx, nullptr, nullptr, nullptr});
 }
 
 int ydc_stream_begin_leased(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
                             uint32_t max_leases, uint32_t max_renewals, uint32_t max_frees, uint32_t max_reports,
                             uint32_t max_report_ids) {
   if (!c || !max_leases) return YDC_ERR_INVALID_ARGUMENT;
-  const LeaseCaps lc{max_leases, max_renewals, max_frees, max_reports, max_report_ids};
-  return stream_begin(c, max_updates, max_releases, max_tasks, 0, &lc);
+  return stream_begin(c, ydc_stream_caps{max_updates, max_releases, max_tasks, 0, 0, max_leases, max_renewals, max_frees,
+                                         max_reports, max_report_ids});
 }
 
 int ydc_stream_tick_leased(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
@@ -6006,16 +6033,16 @@ int ydc_stream_tick_leased(ydc_context* c, const uint32_t* upd_idx, const ydc_se
   const LeaseTick lt{renew_task_id, renew_expires_at, n_renew, free_task_id, n_free, report_servant_idx,
                      report_off, report_task_id, n_rep, lease_expires_at, now, out_task_id, out_renewed,
                      out_report_unknown, out_n_leases};
-  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
-                     n_tasks, out_servant_idx, nullptr, &lt);
+  return stream_tick(c, StreamCall{upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
+                                   n_tasks, out_servant_idx, nullptr, &lt, nullptr});
 }
 
 int ydc_stream_begin_waiting_leased(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_tasks,
                                     uint32_t max_waiting, uint32_t max_leases, uint32_t max_renewals,
                                     uint32_t max_frees, uint32_t max_reports, uint32_t max_report_ids) {
   if (!c || !max_waiting || !max_leases) return YDC_ERR_INVALID_ARGUMENT;
-  const LeaseCaps lc{max_leases, max_renewals, max_frees, max_reports, max_report_ids};
-  return stream_begin(c, max_updates, max_releases, max_tasks, max_waiting, &lc);
+  return stream_begin(c, ydc_stream_caps{max_updates, max_releases, max_tasks, 0, max_waiting, max_leases, max_renewals,
+                                         max_frees, max_reports, max_report_ids});
 }
 
 int ydc_stream_tick_waiting_leased(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
@@ -6037,16 +6064,16 @@ int ydc_stream_tick_waiting_leased(ydc_context* c, const uint32_t* upd_idx, cons
                      out_report_unknown, out_n_leases};
   const WaitTick wt{deadlines, tags, now, out_resolved_tags, out_resolved_idx, out_n_resolved, out_n_waiting,
                     out_resolved_task_id};
-  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
-                     n_tasks, out_servant_idx, &wt, &lt);
+  return stream_tick(c, StreamCall{upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
+                                   n_tasks, out_servant_idx, &wt, &lt, nullptr});
 }
 
 int ydc_stream_begin_rpc(ydc_context* c, uint32_t max_updates, uint32_t max_releases, uint32_t max_requests,
                          uint32_t max_rows, uint32_t max_waiting, uint32_t max_leases, uint32_t max_renewals,
                          uint32_t max_frees, uint32_t max_reports, uint32_t max_report_ids) {
   if (!c || !max_requests || !max_rows || !max_waiting || !max_leases) return YDC_ERR_INVALID_ARGUMENT;
-  const LeaseCaps lc{max_leases, max_renewals, max_frees, max_reports, max_report_ids};
-  return stream_begin(c, max_updates, max_releases, max_requests, max_waiting, &lc, max_rows);
+  return stream_begin(c, ydc_stream_caps{max_updates, max_releases, max_requests, max_rows, max_waiting, max_leases,
+                                         max_renewals, max_frees, max_reports, max_report_ids});
 }
 
 int ydc_stream_tick_rpc(ydc_context* c, const uint32_t* upd_idx, const ydc_servant_row* upd_rows,
@@ -6070,14 +6097,14 @@ int ydc_stream_tick_rpc(ydc_context* c, const uint32_t* upd_idx, const ydc_serva
                     out_resolved_task_id};
   const RpcTick rt{n_immediate, n_prefetch, out_status, out_n_granted, out_resolved_n_granted, out_resolved_first,
                    out_resolved_servant_idx, out_n_waiting_rows};
-  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, requests,
-                     n_req, out_servant_idx, &wt, &lt, &rt);
+  return stream_tick(c, StreamCall{upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel,
+                                   requests, n_req, out_servant_idx, &wt, &lt, &rt});
 }
 
 // The table as it is, in id order: one copy of the columns, the live slots picked and sorted here.
 int ydc_stream_leases_get(ydc_context* c, uint64_t* out_task_id, uint32_t* out_servant_idx,
                           int64_t* out_expires_at, uint8_t* out_zombie, uint32_t cap, uint32_t* out_n) {
-  if (!c || !out_n || !c->stream_mode.active || !c->stream_mode.max_leases) return YDC_ERR_INVALID_ARGUMENT;
+  if (!c || !out_n || !c->stream_mode.active || !c->stream_mode.leased()) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -6115,8 +6142,8 @@ int ydc_stream_tick_waiting(ydc_context* c, const uint32_t* upd_idx, const ydc_s
                             uint32_t* out_n_resolved, uint32_t* out_n_waiting) {
   const WaitTick wt{deadlines, tags, now, out_resolved_tags, out_resolved_idx, out_n_resolved, out_n_waiting,
                     nullptr};
-  return stream_tick(c, upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
-                     n_tasks, out_servant_idx, &wt);
+  return stream_tick(c, StreamCall{upd_idx, upd_rows, upd_env_masks, env_words, n_upd, release_servant_idx, n_rel, tasks,
+                                   n_tasks, out_servant_idx, &wt, nullptr, nullptr});
 }
 
 }  // extern "C"
@@ -6131,20 +6158,18 @@ void snap_describe(const ydc_context* c, snap::Header* h) {
   std::memset(h, 0, sizeof *h);
   h->magic = snap::kMagic;
   h->version = snap::kVersion;
-  h->mode = (sm.max_waiting ? snap::kModeWaiting : 0) | (sm.max_leases ? snap::kModeLeased : 0) |
-            (sm.max_rows ? snap::kModeRpc : 0) | (sm.max_book ? snap::kModeBook : 0) | (sm.alive ? snap::kModeAlive : 0);
+  h->mode = (sm.waiting() ? snap::kModeWaiting : 0) | (sm.leased() ? snap::kModeLeased : 0) |
+            (sm.rpc() ? snap::kModeRpc : 0) | (sm.max_book ? snap::kModeBook : 0) | (sm.alive.on ? snap::kModeAlive : 0);
   h->env_words = c->env_words;
   h->n_servants = c->n_servants;
   h->n_alias = (uint32_t)c->h_alias_ip.size();
-  const uint32_t caps[snap::kCaps] = {sm.max_upd,    sm.max_rel,   sm.max_tasks, sm.max_rows, sm.max_waiting,
-                                      sm.max_leases, sm.max_renew, sm.max_free,  sm.max_rep,  sm.max_rep_ids};
-  std::copy_n(caps, (size_t)snap::kCaps, h->caps);
+  for (int i = 0; i < snap::kCaps; ++i) h->caps[i] = sm.caps.*kCapFields[i];
   h->max_book = sm.max_book;
-  h->n_leases = sm.max_leases ? sm.n_leases : 0;
-  h->n_waiting = sm.max_waiting ? sm.n_waiting : 0;
-  h->n_wait_rows = sm.max_rows ? sm.n_wait_rows : 0;
-  h->n_book = sm.max_book ? sm.n_book : 0;
-  h->lease_tick = sm.max_leases ? sm.lease_tick : 0;
+  h->n_leases = sm.leased() ? sm.n_leases : 0;
+  h->n_waiting = sm.waiting() ? sm.n_waiting : 0;
+  h->n_wait_rows = sm.rpc() ? sm.n_wait_rows : 0;
+  h->n_book = sm.max_book ? sm.book.n : 0;
+  h->lease_tick = sm.leased() ? sm.lease_tick : 0;
   h->last_now = sm.last_now;
   h->alive_bound = INT64_MAX;
   snap::layout(h);
@@ -6194,50 +6219,37 @@ int stream_snapshot(ydc_context* c, uint8_t* out, const snap::Header& h0) {
     std::memcpy(at(v.alias_servant), c->h_alias_servant.data(), (size_t)h.n_alias * 4);
   }
   // W, B, E: compact between ticks, [0, n) of every column as it lies.
-  if (sm.max_waiting) {
+  if (sm.waiting()) {
     uint32_t cnt = 0;
     HIP_TRY(c, hipMemcpy(&cnt, &sm.ws->count, 4, hipMemcpyDeviceToHost));
     if (cnt != h.n_waiting)
       return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u on the device, %u on the host", cnt, h.n_waiting);
-    auto carry = [&](const uint8_t* dst, const void* src, size_t width) {
-      return cnt && src ? hipMemcpyAsync(at(dst), src, cnt * width, hipMemcpyDeviceToHost, st) : hipSuccess;
-    };
-    HIP_TRY(c, carry(v.w_deadline, sm.wq.deadline, 8));
-    HIP_TRY(c, carry(v.w_tag, sm.wq.tag, 8));
-    HIP_TRY(c, carry(v.w_for, sm.wl.w_for, 8));  // (with leases)
-    HIP_TRY(c, carry(v.w_env, sm.wq.env, 4));
-    HIP_TRY(c, carry(v.w_minv, sm.wq.minv, 4));
-    HIP_TRY(c, carry(v.w_ip, sm.wq.ip, 4));
-    HIP_TRY(c, carry(v.w_nimm, sm.rw.n_imm, 4));  // (rpc mode)
-    HIP_TRY(c, carry(v.w_npre, sm.rw.n_pre, 4));
+    const auto from = w_cols(sm);
+    const auto to = w_cols(v);
+    for (size_t k = 0; k < kWCols; ++k)
+      if (cnt && from[k].p)
+        HIP_TRY(c, hipMemcpyAsync(at(to[k]), from[k].p, cnt * from[k].width, hipMemcpyDeviceToHost, st));
   }
   if (h.n_book) {
-    const size_t nb = h.n_book;
-    HIP_TRY(c, hipMemcpyAsync(at(v.b_grant), sm.bk.grant, nb * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(at(v.b_stid), sm.bk.stid, nb * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(at(v.b_dkey), sm.bk.dkey, nb * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(at(v.b_srv), sm.bk.servant, nb * 4, hipMemcpyDeviceToHost, st));
+    const auto from = b_cols(sm);
+    const auto to = b_cols(v);
+    for (size_t k = 0; k < kBCols; ++k)
+      HIP_TRY(c, hipMemcpyAsync(at(to[k]), from[k].p, h.n_book * from[k].width, hipMemcpyDeviceToHost, st));
   }
-  if (sm.alive && n) HIP_TRY(c, hipMemcpyAsync(at(v.e_exp), sm.d_alive.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  if (sm.alive.on && n) HIP_TRY(c, hipMemcpyAsync(at(v.e_exp), sm.alive.col.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
   // L: packed on the device, brought over through one page-locked block (the four columns behind each
   // other), sorted by id here.
-  if (sm.max_leases) {
+  if (sm.leased()) {
     const uint32_t nl = h.n_leases;
     const size_t cap = std::max(nl, 1u);
     HIP_TRY(c, c->d_snap.reserve(cap * 24 + 16));
-    if (c->h_snap_cap < cap * 24) {
-      if (c->h_snap) (void)hipHostFree(c->h_snap);
-      c->h_snap = nullptr;
-      c->h_snap_cap = 0;
-      const size_t want = cap * 24 + cap * 6;  // (a quarter more: |L| moves from snapshot to snapshot)
-      HIP_TRY(c, hipHostMalloc((void**)&c->h_snap, want, hipHostMallocDefault));
-      c->h_snap_cap = want;
-    }
+    if (c->h_snap.cap < cap * 24)  // (a quarter more: |L| moves from snapshot to snapshot)
+      HIP_TRY(c, c->h_snap.reserve(cap * 24 + cap * 6, hipHostMallocDefault));
     uint8_t* d = c->d_snap.p;
     const LeasePacked pk{(unsigned long long*)d, (int64_t*)(d + cap * 8), (uint32_t*)(d + cap * 16),
                          (uint32_t*)(d + cap * 20), (uint32_t)cap};
     uint32_t* d_count = (uint32_t*)(d + cap * 24);
-    const uint8_t* stage = c->h_snap;
+    const uint8_t* stage = c->h_snap.p;
     HIP_TRY(c, hipMemsetAsync(d_count, 0, 4, st));
     YDC_LAUNCH(c, "k_lease_pack", k_lease_pack, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, st, sm.lt,
                pk, d_count);
@@ -6280,7 +6292,7 @@ int stream_snapshot(ydc_context* c, uint8_t* out, const snap::Header& h0) {
   }
   HIP_TRY(c, hipStreamSynchronize(st));
   // alive_bound: the column's minimum itself (the host's bound only errs low, by what it has seen).
-  for (uint32_t s = 0; sm.alive && s < n; ++s) h.alive_bound = std::min(h.alive_bound, snap::get<int64_t>(v.e_exp, s));
+  for (uint32_t s = 0; sm.alive.on && s < n; ++s) h.alive_bound = std::min(h.alive_bound, snap::get<int64_t>(v.e_exp, s));
   std::memcpy(out, &h, sizeof h);
   h.checksum = snap::checksum(out, h.total_bytes);
   std::memcpy(out, &h, sizeof h);
@@ -6295,18 +6307,18 @@ int ydc_stream_snapshot(ydc_context* c, void* out, size_t cap, size_t* out_bytes
   if (!c || !out_bytes) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
   if (!sm.active) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: no stream is open");
-  if (!sm.max_waiting && !sm.max_leases)
+  if (!sm.waiting() && !sm.leased())
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: a stream begun with ydc_stream_begin keeps no state "
                 "on the device");
   if (c->group.n_ranks) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: the context is in a group");
   if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: pipelined batches are outstanding");
-  if (sm.book_staged || sm.alive_staged)
+  if (sm.book.staged.on || sm.alive.staged)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: a staging for the next tick is pending (a snapshot "
                 "is taken between ticks)");
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (sm.alive)
+  if (sm.alive.on)
     if (int rc = alive_fit(c)) return rc;  // (rows the registry gained outside a tick: "never")
   snap::Header h;
   snap_describe(c, &h);
@@ -6327,27 +6339,18 @@ int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc
   const snap::Header& h = v.h;
   if (h.env_words > YDC_MAX_ENV_WORDS)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: env_words %u > %u", h.env_words, YDC_MAX_ENV_WORDS);
-  const ydc_stream_caps none{};
-  const ydc_stream_caps& w = want ? *want : none;
-  if (!(h.mode & snap::kModeWaiting) && w.max_waiting)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: max_waiting for a stream without a waiting queue");
-  if (!(h.mode & snap::kModeLeased) && (w.max_leases | w.max_renewals | w.max_frees | w.max_reports | w.max_report_ids))
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: lease capacities for a stream without a lease table");
-  if (!(h.mode & snap::kModeRpc) && w.max_rows)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: max_rows for a stream that is not an rpc stream");
-  const uint32_t max_upd = std::max(h.caps[snap::kUpdates], w.max_updates);
-  const uint32_t max_rel = std::max(h.caps[snap::kReleases], w.max_releases);
-  const uint32_t max_tasks = std::max(h.caps[snap::kTasks], w.max_tasks), max_rows = std::max(h.caps[snap::kRows], w.max_rows);
-  const uint32_t max_waiting = std::max(h.caps[snap::kWaiting], w.max_waiting);
-  const LeaseCaps lc{std::max(h.caps[snap::kLeases], w.max_leases), std::max(h.caps[snap::kRenewals], w.max_renewals),
-                     std::max(h.caps[snap::kFrees], w.max_frees), std::max(h.caps[snap::kReports], w.max_reports),
-                     std::max(h.caps[snap::kReportIds], w.max_report_ids)};
-  const LeaseCaps* lcp = (h.mode & snap::kModeLeased) ? &lc : nullptr;
-  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, max_tasks, max_waiting, lcp, max_rows, h.max_book)) return rc;
+  // (snap::validate has seen to it that the blob's bounds fit its mode bits: a part is there
+  // exactly if its bound is not 0)
+  ydc_stream_caps had{};
+  for (int i = 0; i < snap::kCaps; ++i) had.*kCapFields[i] = h.caps[i];
+  if (const char* why = want ? stream_caps_foreign(had, *want) : nullptr)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_restore: %s", why);
+  const ydc_stream_caps k = want ? stream_caps_grown(had, *want) : had;
+  if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, k, h.max_book)) return rc;
   if (c->max_servants && h.n_servants > c->max_servants)
     return fail(c, YDC_ERR_CAPACITY, "ydc_stream_restore: %u servants > max_servants %u", h.n_servants, c->max_servants);
-  if (c->max_tasks && max_tasks > c->max_tasks)
-    return fail(c, YDC_ERR_CAPACITY, "ydc_stream_restore: max_tasks %u > the context's %u", max_tasks, c->max_tasks);
+  if (c->max_tasks && k.max_tasks > c->max_tasks)
+    return fail(c, YDC_ERR_CAPACITY, "ydc_stream_restore: max_tasks %u > the context's %u", k.max_tasks, c->max_tasks);
   // The blob is good. From here on a failure is the device's (YDC_ERR_HIP, or a load that lost
   // records: YDC_ERR_NOT_CONVERGED) and leaves the blob's registry and no open stream.
   HIP_TRY(c, hipSetDevice(c->device));
@@ -6381,10 +6384,10 @@ int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc
   // A second stream, complete before it becomes the context's.
   ydc_context::Stream fresh;
   auto load = [&]() -> int {
-    if (int rc = stream_alloc(c, fresh, max_upd, max_rel, max_tasks, max_waiting, lcp, max_rows, h.max_book)) return rc;
+    if (int rc = stream_alloc(c, fresh, k, h.max_book)) return rc;
     if (int rc = stream_reset(c, fresh)) return rc;
     hipStream_t st = c->stream;
-    if (lcp) {
+    if (fresh.leased()) {
       const uint32_t nl = h.n_leases;
       PackedBufs pk;
       HIP_TRY(c, pk.reserve(std::max(nl, 1u)));
@@ -6409,35 +6412,26 @@ int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc
       if (n) HIP_TRY(c, hipMemcpy(fresh.d_rep_tick.p, col32(v.rep_tick, n).data(), (size_t)n * 4, hipMemcpyHostToDevice));
     }
     if (h.n_waiting) {
-      const size_t cnt = h.n_waiting;
-      auto carry = [&](void* dst, const uint8_t* src, size_t width) {
-        // (pageable and unaligned source: a synchronous copy)
-        return dst ? hipMemcpy(dst, src, cnt * width, hipMemcpyHostToDevice) : hipSuccess;
-      };
-      HIP_TRY(c, carry(fresh.wq.deadline, v.w_deadline, 8));
-      HIP_TRY(c, carry(fresh.wq.tag, v.w_tag, 8));
-      HIP_TRY(c, carry(fresh.wl.w_for, v.w_for, 8));  // (with leases)
-      HIP_TRY(c, carry(fresh.wq.env, v.w_env, 4));
-      HIP_TRY(c, carry(fresh.wq.minv, v.w_minv, 4));
-      HIP_TRY(c, carry(fresh.wq.ip, v.w_ip, 4));
-      HIP_TRY(c, carry(fresh.rw.n_imm, v.w_nimm, 4));  // (rpc mode)
-      HIP_TRY(c, carry(fresh.rw.n_pre, v.w_npre, 4));
+      // (pageable and unaligned sources: synchronous copies)
+      const auto from = w_cols(v);
+      const auto to = w_cols(fresh);
+      for (size_t k = 0; k < kWCols; ++k)
+        if (to[k].p) HIP_TRY(c, hipMemcpy(to[k].p, from[k], h.n_waiting * to[k].width, hipMemcpyHostToDevice));
       HIP_TRY(c, hipMemcpy(&fresh.ws->count, &h.n_waiting, 4, hipMemcpyHostToDevice));
     }
     if (h.n_book) {
-      const size_t nb = h.n_book;
-      HIP_TRY(c, hipMemcpy(fresh.bk.grant, v.b_grant, nb * 8, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(fresh.bk.stid, v.b_stid, nb * 8, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(fresh.bk.dkey, v.b_dkey, nb * 8, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(fresh.bk.servant, v.b_srv, nb * 4, hipMemcpyHostToDevice));
-      HIP_TRY(c, hipMemcpy(&fresh.bks->n_entries, &h.n_book, 4, hipMemcpyHostToDevice));
+      const auto from = b_cols(v);
+      const auto to = b_cols(fresh);
+      for (size_t k = 0; k < kBCols; ++k)
+        HIP_TRY(c, hipMemcpy(to[k].p, from[k], h.n_book * to[k].width, hipMemcpyHostToDevice));
+      HIP_TRY(c, hipMemcpy(&fresh.book.bks->n_entries, &h.n_book, 4, hipMemcpyHostToDevice));
     }
     if (h.mode & snap::kModeAlive) {  // (ydc_stream_alive_begin's allocation)
-      HIP_TRY(c, fresh.d_alive.reserve((size_t)n + n / 2 + 1024));
-      if (n) HIP_TRY(c, hipMemcpy(fresh.d_alive.p, v.e_exp, (size_t)n * 8, hipMemcpyHostToDevice));
-      fresh.alive = true;
-      fresh.alive_n = n;
-      fresh.alive_bound = h.alive_bound;
+      HIP_TRY(c, fresh.alive.col.reserve((size_t)n + n / 2 + 1024));
+      if (n) HIP_TRY(c, hipMemcpy(fresh.alive.col.p, v.e_exp, (size_t)n * 8, hipMemcpyHostToDevice));
+      fresh.alive.on = true;
+      fresh.alive.n = n;
+      fresh.alive.bound = h.alive_bound;
     }
     // The host's mirrors. What a stream learns (want_passes and its window) and the per-tick marks
     // (rep_seen / rep_mark, alive_seen / alive_mark) start fresh: none of them outlives a tick in
@@ -6445,7 +6439,7 @@ int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc
     fresh.n_waiting = h.n_waiting;
     fresh.n_wait_rows = h.n_wait_rows;
     fresh.n_leases = h.n_leases;
-    fresh.n_book = h.n_book;
+    fresh.book.n = h.n_book;
     fresh.last_now = h.last_now;
     fresh.lease_tick = h.lease_tick;
     return YDC_OK;
