@@ -24,6 +24,7 @@
 #include "../../include/yadcc_dispatch.h"
 #include "dispatch_core.h"
 #include "host_tables.h"
+#include "registry_mirror.h"
 #include "kernels.h"
 #include "wait_queue.h"
 #include "lease_table.h"
@@ -41,8 +42,7 @@ using namespace ydc;
 
 namespace {
 
-// Owns one device allocation (freed with the context: `delete c` releases whatever
-// ydc_destroy did not name).
+// Owns one device allocation (freed with whatever holds it: the context, a stream, the group).
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
@@ -118,6 +118,40 @@ struct PinnedBuf {
   }
 };
 
+// A PinnedBuf that holds objects of one type: the block at its host address, dev() at the device's.
+template <typename T>
+struct PinnedAs : PinnedBuf {
+  T* get() const { return (T*)p; }
+  T* dev() const { return (T*)z; }
+  operator T*() const { return get(); }
+  T* operator->() const { return get(); }
+};
+
+// Own one event / one stream in the same way; created at their first use.
+struct OwnedEvent {
+  hipEvent_t e = nullptr;
+  OwnedEvent() = default;
+  OwnedEvent(const OwnedEvent&) = delete;
+  OwnedEvent& operator=(const OwnedEvent&) = delete;
+  OwnedEvent(OwnedEvent&& o) noexcept : e(std::exchange(o.e, nullptr)) {}
+  ~OwnedEvent() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+  operator hipEvent_t() const { return e; }
+};
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() = default;
+  OwnedStream(const OwnedStream&) = delete;
+  OwnedStream& operator=(const OwnedStream&) = delete;
+  ~OwnedStream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  operator hipStream_t() const { return s; }
+};
+
 }  // namespace
 
 namespace {
@@ -178,25 +212,22 @@ struct TickArena {
 
 struct ydc_context {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  // The first member, so the last to go: everything below is released while it still exists.
+  OwnedStream own_stream;        // the context's stream where the caller brought none
+  hipStream_t stream = nullptr;  // the caller's, or own_stream
   uint32_t max_servants = 0, max_tasks = 0, max_slots = 0;
   std::string last_error;
 
-  // Host mirror of the registry columns the derived tables need.
-  uint32_t n_servants = 0;
-  std::vector<uint32_t> h_version, h_nproc, h_load, h_max_tasks, h_flags, h_ip;
-  std::vector<uint32_t> h_alias_ip, h_alias_servant;  // ydc_set_host_aliases: further ip table entries
-  std::vector<uint64_t> h_env;  // env_words words per servant
-  uint32_t env_words = 1;
+  // Host mirror of the registry columns the derived tables need, and the host aliases.
+  RegistryMirror reg;
   uint32_t n_parts = 1;         // independent parts of the registry (host_tables.h)
   HostTables tables;
   KeyFormat kf{};
   bool tables_dirty = true;
 
-  // Resident registry.
+  // Resident registry (its six per-servant columns: kRegCols, below).
   DevBuf<uint32_t> d_version, d_nproc, d_load, d_max_tasks, d_running, d_flags, d_class_of;
-  DevBuf<uint32_t> d_spare[6];  // ydc_remove_servants compacts into these, then swaps
+  DevBuf<uint32_t> d_spare[6];  // ydc_remove_servants compacts into these (kRegCols' order), then swaps
   DevBuf<uint32_t> d_ip_hash, d_ip_filter;
   DevBuf<uint32_t> d_bin_tile_start, d_bin_tile_base;  // slot tiles of the bin sort's front (host_tables.h)
   DevBuf<uint32_t> d_ip_sorted, d_ip_servant, d_cls_ver, d_ver_sorted, d_cls_comp, d_part_base;
@@ -231,12 +262,10 @@ struct ydc_context {
     uint32_t* out_idx = nullptr;
     double* out_util = nullptr;
     uint32_t* out_running = nullptr;
-    DeviceParams* h_outcome = nullptr;  // pinned
-    DeviceParams* d_h_outcome = nullptr;  // ... its device address
-    hipEvent_t ev = nullptr;
+    PinnedAs<DeviceParams> h_outcome;  // where k_finalize stores the batch's outcome
+    OwnedEvent ev;
   } pend[2];
   uint32_t pend_head = 0, pend_count = 0;
-  bool enqueue_pipelined = false;  // the finalise being enqueued belongs to a pipelined batch
   uint64_t pipeline_misses = 0;
 
   // Multi-GPU group (ydc_group_*): this context is one rank of a sharded dispatcher.
@@ -280,8 +309,7 @@ struct ydc_context {
     DevBuf<uint32_t> d_pad, d_gather, d_all[3], d_all_idx;  // replicated fallback (whole batch)
     DevBuf<double> d_all_util;
     DevBuf<ClassState> d_send, d_bounds;
-    ClassState* h_bounds = nullptr;  // pinned
-    size_t h_bounds_cap = 0;
+    PinnedAs<ClassState> h_bounds;   // page-locked (debug_sim's look at the ranks' records)
     uint32_t passes = 0;             // of the last sharded batch
     uint32_t pass_hint = 3;          // passes to pre-launch before looking at the outcome
   } group;
@@ -461,11 +489,7 @@ struct ydc_context {
   DevBuf<uint8_t> d_dirty;
   bool debug_sim = false;
   DevBuf<DeviceParams> d_prm;
-  DeviceParams* h_prm = nullptr;  // pinned
-  DeviceParams* d_h_prm = nullptr;  // ... its device address
-  // Where the finalise being enqueued hands the batch's outcome to the host itself (NULL: the
-  // caller reads d_prm back with a copy) — kernels.h: RunningArgs::host_outcome.
-  DeviceParams* finalize_outcome = nullptr;
+  PinnedAs<DeviceParams> h_prm;   // the outcome block: stored by k_finalize itself, or d_prm copied back
   bool opt_outcome_store = true;  // (outcome_store=0: always the copy)
   bool opt_release_counted = true;  // long release lists counted in LDS first (release_counted=0: an atomic per slot)
 
@@ -473,38 +497,23 @@ struct ydc_context {
   // one pinned arena and its device mirror (one H2D copy), the results (indexes |
   // running_tasks | utilisation) in another pair (one D2H copy, enqueued right behind the
   // finalise kernels so that the batch needs a single wait).
-  uint8_t *h_in = nullptr, *h_res = nullptr;
-  uint32_t* h_rel = nullptr;  // pinned staging of ydc_release_slots
-  size_t h_rel_cap = 0;
-  hipEvent_t h_rel_ev = nullptr;
-  size_t h_in_cap = 0, h_res_cap = 0;
+  // The request columns are only needed by the classification, so the slot generation and the
+  // sort are enqueued first and run while the host stages the columns and the H2D copy travels on
+  // a stream of its own (BatchCall::host_in, stage_host_requests).
+  PinnedBuf h_in, h_res;  // (not mapped: they only feed and receive copies)
+  PinnedAs<uint32_t> h_rel;  // staging of ydc_release_slots (not mapped either)
+  OwnedEvent h_rel_ev;
   DevBuf<uint8_t> d_in, d_res;
-  struct {
-    void* dst = nullptr;
-    const void* src = nullptr;
-    size_t bytes = 0;
-  } post_copy;  // D2H copy to enqueue after every finalise of the current batch (bytes == 0: none)
-  // ydc_dispatch: the request columns are only needed by the classification, so the slot
-  // generation and the sort are enqueued first and run while the host stages the columns and
-  // the H2D copy travels on a stream of its own (stage_host_requests).
-  struct {
-    bool active = false;
-    const ydc_task_soa* tk = nullptr;
-    uint32_t n = 0;
-    size_t col = 0, bytes = 0;
-  } host_in;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t copy_ev = nullptr;
+  OwnedStream copy_stream;
+  OwnedEvent copy_ev;
   DevBuf<uint32_t> d_out_idx, d_upd_idx;
   DevBuf<ydc_servant_row> d_upd_rows;
 
   // Small-batch path (tick_kernel.h): one launch per call, requests / deltas / results as kernel
   // arguments and plain stores to page-locked memory.
   DevBuf<uint32_t> d_ip;            // resident copy of the ip_id column (rebuild_tables)
-  TickDone* h_tick_done = nullptr;  // page-locked, coherent: the kernel's stamp + counters
-  TickDone* d_tick_done = nullptr;  // ... its device address
-  uint8_t *h_tick_io = nullptr, *d_tick_io = nullptr;  // page-locked arena: columns / deltas in, results out
-  size_t tick_io_cap = 0;
+  PinnedAs<TickDone> h_tick_done;  // page-locked, coherent: the kernel's stamp + counters
+  PinnedBuf h_tick_io;             // page-locked arena: columns / deltas in, results out
   uint32_t tick_seq = 0;
   // Batches up to this many requests take it (small_batch=0: none does). kSmallBatchAuto: by
   // registry size — a pick costs ~1 us at 2k servants and ~4 us at 16k, the batch pipeline
@@ -515,7 +524,7 @@ struct ydc_context {
   // one merge (tick_merges): ~0.5 us per request at 2k servants, ~1 us at 16k.
   uint32_t small_batch(bool same = false) const {
     if (opt_small_batch != kSmallBatchAuto) return opt_small_batch;
-    return n_servants <= 4096 || same ? 64u : n_servants <= 8192 ? 48u : 32u;
+    return reg.n <= 4096 || same ? 64u : reg.n <= 8192 ? 48u : 32u;
   }
   uint64_t tick_batches = 0;
   // The resident form: the kernel of a COMMITting tick stays on its CU, the registry in its
@@ -524,9 +533,9 @@ struct ydc_context {
   bool opt_resident = true;        // (resident=0: every tick is a launch)
   bool opt_tick_packed = true;     // (packed_tick=0: the two-word candidate everywhere)
   uint32_t opt_resident_idle_ms = 50;  // the kernel leaves by itself when nobody has asked for this long
-  TickBox *h_box = nullptr, *d_box = nullptr;
-  hipStream_t res_stream = nullptr;
-  hipEvent_t res_ev = nullptr;
+  PinnedAs<TickBox> h_box;  // (the resident kernel reads it: resident_stop comes before its release)
+  OwnedStream res_stream;
+  OwnedEvent res_ev;
   bool res_live = false;  // a resident kernel was launched and has not been seen to leave
   bool res_util = false;  // ... and it stores utilisations (fixed at its launch: TickArgs::out_util)
   uint64_t tick_resident = 0, tick_launches = 0, pipeline_batches = 0;
@@ -589,21 +598,18 @@ struct ydc_context {
   // from their own hosts: 554 passes, 1.2 s; healthy batches need 2 - 4) — `walk_after` passes, then
   // a scout and the walk.
   // COMMIT by exchanging the resident running_tasks column with k_finalize's output instead of
-  // copying it back (set around enqueue_finalize by callers that do the exchange; never while a
-  // captured streaming step holds the two addresses).
-  bool commit_by_swap = false;
+  // copying it back (BatchCall::by_swap).
   bool opt_commit_swap = true;  // (commit_swap=0: always the copy)
   uint32_t opt_walk_after = 12;
-  uint32_t walk_flag = 0;
   uint32_t walked_at = 0;  // passes launched before the last batch's walk (0: it was not walked)
   bool profiling = false;
-  hipEvent_t ev[YDC_STAGE_COUNT + 1] = {};
+  OwnedEvent ev[YDC_STAGE_COUNT + 1];
   ydc_stats stats{};
 
   // Per-kernel timing (profiling only): one event pair per launch.
   struct KernelSample {
     const char* name;
-    hipEvent_t a, b;
+    OwnedEvent a, b;
   };
   std::vector<KernelSample> ksamples;
   size_t ksamples_used = 0;
@@ -611,6 +617,67 @@ struct ydc_context {
 };
 
 namespace {
+
+// The six per-servant columns of the resident registry, listed once: the device column, where an
+// upload (ydc_servant_soa), the host mirror and a snapshot hold it. d_spare[k] is the spare of
+// kRegCols[k]. running_tasks has no host copy: it lives on the device alone.
+struct RegCol {
+  DevBuf<uint32_t> ydc_context::*dev;
+  const uint32_t* ydc_servant_soa::*up;
+  std::vector<uint32_t> RegistryMirror::*host;
+  const uint8_t* snap::View::*snap;
+};
+constexpr RegCol kRegCols[6] = {
+    {&ydc_context::d_version, &ydc_servant_soa::version, &RegistryMirror::version, &snap::View::version},
+    {&ydc_context::d_nproc, &ydc_servant_soa::num_processors, &RegistryMirror::nproc, &snap::View::nproc},
+    {&ydc_context::d_load, &ydc_servant_soa::current_load, &RegistryMirror::load, &snap::View::load},
+    {&ydc_context::d_max_tasks, &ydc_servant_soa::max_tasks, &RegistryMirror::max_tasks, &snap::View::max_tasks},
+    {&ydc_context::d_running, &ydc_servant_soa::running_tasks, nullptr, &snap::View::running},
+    {&ydc_context::d_flags, &ydc_servant_soa::flags, &RegistryMirror::flags, &snap::View::flags}};
+
+// What one batch is asked to do, handed down from the entry point to the launches: nothing of it
+// is kept in the context.
+struct BatchCall {
+  uint32_t flags = 0;
+  uint32_t* out_idx = nullptr;  // device addresses (NULL: not asked for)
+  double* out_util = nullptr;
+  uint32_t* out_running = nullptr;
+  // ydc_dispatch from pageable memory: the request columns are staged and copied inside the batch,
+  // behind the launches that do not read them (tk == NULL: they are on the device already).
+  struct {
+    const ydc_task_soa* tk = nullptr;
+    uint32_t n = 0;
+    size_t col = 0, bytes = 0;
+  } host_in;
+  // D2H copy to enqueue behind every finalise of the batch (bytes == 0: none).
+  struct {
+    void* dst = nullptr;
+    const void* src = nullptr;
+    size_t bytes = 0;
+  } post_copy;
+  // The finalise: of a pipelined batch; where k_finalize hands the outcome to the host itself
+  // (a device address; NULL: d_prm is read back with a copy — kernels.h: RunningArgs::host_outcome);
+  // COMMIT by exchanging the running_tasks column with k_finalize's output afterwards, not by copy.
+  bool pipelined = false;
+  DeviceParams* outcome = nullptr;
+  bool by_swap = false;
+  bool staged() const { return host_in.tk || post_copy.bytes; }
+};
+
+// A batch outside a captured streaming step (which decides the last two for itself: the two
+// addresses are baked into it). outcome: the page-locked block's device address.
+BatchCall batch_call(const ydc_context* c, uint32_t flags, uint32_t* out_idx, double* out_util, uint32_t* out_running,
+                     DeviceParams* outcome) {
+  BatchCall b;
+  b.flags = flags;
+  b.out_idx = out_idx;
+  b.out_util = out_util;
+  b.out_running = out_running;
+  // (k_finalize stores the outcome itself where it has servant workgroups)
+  b.outcome = c->opt_outcome_store && c->reg.n ? outcome : nullptr;
+  b.by_swap = c->opt_commit_swap && !c->stream_mode.active && (flags & YDC_DISPATCH_COMMIT) && c->reg.n;
+  return b;
+}
 
 void stream_release(ydc_context* c);  // streaming mode, defined further down
 int alive_fit(ydc_context* c);         // ... its servants' expiry column, defined further down
@@ -718,10 +785,10 @@ inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 int rebuild_tables(ydc_context* c) {
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
-  const uint32_t n = c->n_servants;
-  c->tables.build(n, c->h_env.data(), c->h_version.data(), c->h_max_tasks.data(),
-                  c->h_nproc.data(), c->h_ip.data(), c->env_words, (uint32_t)c->h_alias_ip.size(),
-                  c->h_alias_ip.data(), c->h_alias_servant.data());
+  const RegistryMirror& reg = c->reg;
+  const uint32_t n = reg.n;
+  c->tables.build(n, reg.env.data(), reg.version.data(), reg.max_tasks.data(), reg.nproc.data(), reg.ip.data(),
+                  reg.env_words, (uint32_t)reg.alias_ip.size(), reg.alias_ip.data(), reg.alias_servant.data());
   const uint32_t n_ip = (uint32_t)c->tables.ip_sorted.size();
   c->n_parts = c->tables.n_comp;
   const uint32_t C = c->tables.n_classes();
@@ -748,7 +815,7 @@ int rebuild_tables(ydc_context* c) {
   HIP_TRY(c, c->d_ip_filter.reserve(c->tables.ip_filter.size()));
   HIP_TRY(c, hipMemcpyAsync(c->d_ip_filter.p, c->tables.ip_filter.data(), c->tables.ip_filter.size() * 4,
                             hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, c->d_cls_env.reserve((size_t)C * c->env_words));
+  HIP_TRY(c, c->d_cls_env.reserve((size_t)C * c->reg.env_words));
   HIP_TRY(c, c->d_cls_ver.reserve(C));
   HIP_TRY(c, c->d_cls_begin.reserve(C + 1));
   HIP_TRY(c, c->d_part_base.reserve(kMaxComponents + 1));
@@ -764,14 +831,14 @@ int rebuild_tables(ydc_context* c) {
   if (n) {
     HIP_TRY(c, hipMemcpyAsync(c->d_class_of.p, c->tables.class_of.data(), n * 4,
                               hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_ip.p, c->h_ip.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_ip.p, c->reg.ip.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_ip_sorted.p, c->tables.ip_sorted.data(), (size_t)n_ip * 4,
                               hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_ip_servant.p, c->tables.ip_servant.data(), (size_t)n_ip * 4,
                               hipMemcpyHostToDevice, c->stream));
   }
   if (C) {
-    HIP_TRY(c, hipMemcpyAsync(c->d_cls_env.p, c->tables.cls_env.data(), (size_t)C * c->env_words * 8,
+    HIP_TRY(c, hipMemcpyAsync(c->d_cls_env.p, c->tables.cls_env.data(), (size_t)C * c->reg.env_words * 8,
                               hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_cls_ver.p, c->tables.cls_ver.data(), C * 4,
                               hipMemcpyHostToDevice, c->stream));
@@ -803,12 +870,7 @@ int rebuild_tables(ydc_context* c) {
 }
 
 int reserve_registry(ydc_context* c, uint32_t n) {
-  HIP_TRY(c, c->d_version.reserve(n));
-  HIP_TRY(c, c->d_nproc.reserve(n));
-  HIP_TRY(c, c->d_load.reserve(n));
-  HIP_TRY(c, c->d_max_tasks.reserve(n));
-  HIP_TRY(c, c->d_running.reserve(n));
-  HIP_TRY(c, c->d_flags.reserve(n));
+  for (auto& col : kRegCols) HIP_TRY(c, (c->*col.dev).reserve(n));
   HIP_TRY(c, c->d_running_out.reserve(n));
   HIP_TRY(c, c->d_slot_base.reserve((size_t)n + 1));
   HIP_TRY(c, c->d_pos_last.reserve(n));
@@ -826,9 +888,9 @@ struct KernelTimer {
   KernelTimer(ydc_context* ctx, const char* name) : c(ctx) {
     if (!c->profiling) return;
     if (c->ksamples_used == c->ksamples.size()) {
-      ydc_context::KernelSample n{name, nullptr, nullptr};
-      if (hipEventCreate(&n.a) != hipSuccess || hipEventCreate(&n.b) != hipSuccess) return;
-      c->ksamples.push_back(n);
+      ydc_context::KernelSample n{name, {}, {}};
+      if (n.a.create() != hipSuccess || n.b.create() != hipSuccess) return;
+      c->ksamples.push_back(std::move(n));
     }
     s = &c->ksamples[c->ksamples_used++];
     s->name = name;
@@ -951,22 +1013,20 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
   if (stream) {
     c->stream = (hipStream_t)stream;
   } else {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (c->own_stream.create() != hipSuccess) {
       delete c;
       return YDC_ERR_HIP;
     }
-    c->own_stream = true;
+    c->stream = c->own_stream;
   }
-  if (c->d_prm.reserve(1) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_prm, sizeof(DeviceParams), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&c->d_h_prm, c->h_prm, 0) != hipSuccess ||
+  if (c->d_prm.reserve(1) != hipSuccess || c->h_prm.reserve(sizeof(DeviceParams)) != hipSuccess ||
       c->d_row_total.reserve(1u << kMaxRadixBits) != hipSuccess) {
     ydc_destroy(c);
     return YDC_ERR_HIP;
   }
   (void)hipMemset(c->d_prm.p, 0, sizeof(DeviceParams));  // batch_seq starts at 0
   for (auto& e : c->ev) {
-    if (hipEventCreate(&e) != hipSuccess) {
+    if (e.create() != hipSuccess) {
       ydc_destroy(c);
       return YDC_ERR_HIP;
     }
@@ -1024,56 +1084,8 @@ int ydc_destroy(ydc_context* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   stream_release(c);
   group_release(c);
-  for (auto* b : {&c->d_version, &c->d_nproc, &c->d_load, &c->d_max_tasks, &c->d_running,
-                  &c->d_flags, &c->d_class_of, &c->d_ip_hash, &c->d_ip_filter, &c->d_bin_tile_start, &c->d_bin_tile_base, &c->d_ip_sorted, &c->d_ip_servant, &c->d_cls_ver,
-                  &c->d_cls_comp, &c->d_part_base,
-                  &c->d_slot_base, &c->d_cls_begin, &c->d_vals[0], &c->d_vals[1], &c->d_hist, &c->d_tile_first,
-                  &c->d_row_total, &c->d_self_lo, &c->d_self_hi, &c->d_chunk_consuming,
-                  &c->d_before, &c->d_slot_of, &c->d_pos_last, &c->d_running_out, &c->d_out_idx,
-                  &c->d_upd_idx})
-    b->release();
-  for (auto* b : {&c->d_cls_env, &c->d_env_ver_mask, &c->d_keys[0], &c->d_keys[1], &c->d_mask}) b->release();
-  c->d_ver_sorted.release();
-  c->d_cls_single.release();
-  for (auto& b : c->d_spare) b.release();
-  c->d_cls_by_g.release();
-  c->d_owner.release();
-  c->d_rank_to_g.release();
-  c->d_zone_box.release();
-  c->d_guess[0].release();
-  c->d_endst.release();
-  c->d_checkpoint.release();
-  c->d_early.release();
-  c->d_claim.release();
-  c->d_runs.release();
-  c->d_dirty.release();
-  c->d_prm.release();
-  if (c->h_prm) (void)hipHostFree(c->h_prm);
-  for (auto& pd : c->pend) {
-    if (pd.h_outcome) (void)hipHostFree(pd.h_outcome);
-    if (pd.ev) (void)hipEventDestroy(pd.ev);
-  }
-  if (c->h_in) (void)hipHostFree(c->h_in);
-  if (c->h_rel) (void)hipHostFree(c->h_rel);
-  if (c->h_rel_ev) (void)hipEventDestroy(c->h_rel_ev);
-  if (c->copy_ev) (void)hipEventDestroy(c->copy_ev);
-  if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-  if (c->h_res) (void)hipHostFree(c->h_res);
-  if (c->h_box) (void)hipHostFree(c->h_box);
-  if (c->res_ev) (void)hipEventDestroy(c->res_ev);
-  if (c->res_stream) (void)hipStreamDestroy(c->res_stream);
-  if (c->h_tick_done) (void)hipHostFree(c->h_tick_done);
-  if (c->h_tick_io) (void)hipHostFree(c->h_tick_io);
-  c->d_ip.release();
-  c->d_in.release();
-  c->d_res.release();
-  for (auto& e : c->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& k : c->ksamples) {
-    if (k.a) (void)hipEventDestroy(k.a);
-    if (k.b) (void)hipEventDestroy(k.b);
-  }
-  if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
+  // Everything else the context took goes with its members, in reverse order of declaration (the
+  // device is current; the resident kernel, which reads h_box, has left).
   delete c;
   return YDC_OK;
 }
@@ -1088,43 +1100,13 @@ int ydc_upload_servants(ydc_context* c, const ydc_servant_soa* sv, uint32_t n) {
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (released slots may still be on their way)
   if (int rc = reserve_registry(c, n)) return rc;
-  c->n_servants = n;
-  c->h_alias_ip.clear();  // (they name rows of the table that is being replaced)
-  c->h_alias_servant.clear();
-  c->h_version.assign(sv ? sv->version : nullptr, sv ? sv->version + n : nullptr);
-  c->h_nproc.assign(sv ? sv->num_processors : nullptr, sv ? sv->num_processors + n : nullptr);
-  c->h_load.assign(sv ? sv->current_load : nullptr, sv ? sv->current_load + n : nullptr);
-  c->h_max_tasks.assign(sv ? sv->max_tasks : nullptr, sv ? sv->max_tasks + n : nullptr);
-  c->h_flags.assign(sv ? sv->flags : nullptr, sv ? sv->flags + n : nullptr);
-  c->h_ip.assign(sv ? sv->ip_id : nullptr, sv ? sv->ip_id + n : nullptr);
-  c->env_words = sv && sv->env_words ? sv->env_words : 1;
-  c->h_env.assign(sv ? sv->env_mask : nullptr, sv ? sv->env_mask + (size_t)n * c->env_words : nullptr);
-  if (n) {
-    HIP_TRY(c, hipMemcpyAsync(c->d_version.p, sv->version, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_nproc.p, sv->num_processors, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_load.p, sv->current_load, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_max_tasks.p, sv->max_tasks, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_running.p, sv->running_tasks, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_flags.p, sv->flags, n * 4, hipMemcpyHostToDevice, c->stream));
-  }
+  c->reg.assign(sv, n);  // (the aliases go too: they name rows of the table that is being replaced)
+  if (n)
+    for (auto& col : kRegCols)
+      HIP_TRY(c, hipMemcpyAsync((c->*col.dev).p, sv->*col.up, n * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return rebuild_tables(c);
 }
-
-namespace {
-// Re-lays the host copy of the environment masks out for `words` words per servant (the
-// device only holds per-class masks, which rebuild_tables derives from this copy).
-void widen_env(ydc_context* c, uint32_t words) {
-  if (words <= c->env_words) return;
-  std::vector<uint64_t> wide((size_t)c->n_servants * words, 0);
-  for (uint32_t s = 0; s < c->n_servants; ++s)
-    for (uint32_t w = 0; w < c->env_words; ++w)
-      wide[(size_t)s * words + w] = c->h_env[(size_t)s * c->env_words + w];
-  c->h_env.swap(wide);
-  c->env_words = words;
-  c->tables_dirty = true;
-}
-}  // namespace
 
 int ydc_update_servants_wide(ydc_context* c, const uint32_t* idx, const ydc_servant_row* rows,
                              const uint64_t* env_masks, uint32_t env_words, uint32_t n) {
@@ -1133,72 +1115,42 @@ int ydc_update_servants_wide(ydc_context* c, const uint32_t* idx, const ydc_serv
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "env_words %u out of range", env_words);
   // A row carries one mask word: on a wider table it would silently clear the servant's other
   // environments (KeepServantAlive replaces the whole set, task_dispatcher.cc:195-201).
-  if (!env_masks && n && c->env_words > 1)
+  if (!env_masks && n && c->reg.env_words > 1)
     return fail(c, YDC_ERR_INVALID_ARGUMENT,
-                "the table holds %u mask words per servant: use ydc_update_servants_wide", c->env_words);
+                "the table holds %u mask words per servant: use ydc_update_servants_wide", c->reg.env_words);
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   // Appends first (they may need bigger buffers).
-  uint32_t new_n = c->n_servants;
+  uint32_t new_n = c->reg.n;
   for (uint32_t i = 0; i < n; ++i) {
     if (idx[i] > new_n) return fail(c, YDC_ERR_INVALID_ARGUMENT, "servant index %u out of order", idx[i]);
     if (idx[i] == new_n) ++new_n;
   }
   if (c->max_servants && new_n > c->max_servants)
     return fail(c, YDC_ERR_CAPACITY, "%u servants > max_servants %u", new_n, c->max_servants);
-  if (env_masks) widen_env(c, env_words);
-  const uint32_t EW = c->env_words;
-  auto resize_host = [&](uint32_t m) {
-    c->h_version.resize(m);
-    c->h_nproc.resize(m);
-    c->h_load.resize(m);
-    c->h_max_tasks.resize(m);
-    c->h_flags.resize(m);
-    c->h_ip.resize(m);
-    c->h_env.resize((size_t)m * EW);
-  };
+  if (env_masks && c->reg.widen_env(env_words)) c->tables_dirty = true;
+  const uint32_t old_n = c->reg.n;
   if (new_n > c->d_version.cap) {
     // Grow: read the running column back, reallocate, re-upload everything. Released slots
     // (ydc_release_slots only enqueues) must have reached the column first.
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::vector<uint32_t> run(c->n_servants);
-    if (c->n_servants)
-      HIP_TRY(c, hipMemcpy(run.data(), c->d_running.p, c->n_servants * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> run(old_n);
+    if (old_n) HIP_TRY(c, hipMemcpy(run.data(), c->d_running.p, old_n * 4, hipMemcpyDeviceToHost));
     run.resize(new_n, 0);
     if (int rc = reserve_registry(c, std::max<uint32_t>(new_n, new_n + new_n / 2))) return rc;
-    resize_host(new_n);
+    c->reg.resize(new_n);
     HIP_TRY(c, hipMemcpy(c->d_running.p, run.data(), new_n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_version.p, c->h_version.data(), new_n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_nproc.p, c->h_nproc.data(), new_n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_load.p, c->h_load.data(), new_n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_max_tasks.p, c->h_max_tasks.data(), new_n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_flags.p, c->h_flags.data(), new_n * 4, hipMemcpyHostToDevice));
-  } else if (new_n > c->n_servants) {
-    resize_host(new_n);
-    HIP_TRY(c, hipMemsetAsync(c->d_running.p + c->n_servants, 0, (new_n - c->n_servants) * 4, c->stream));
+    for (auto& col : kRegCols)
+      if (col.host)
+        HIP_TRY(c, hipMemcpy((c->*col.dev).p, (c->reg.*col.host).data(), new_n * 4, hipMemcpyHostToDevice));
+  } else if (new_n > old_n) {
+    c->reg.resize(new_n);
+    HIP_TRY(c, hipMemsetAsync(c->d_running.p + old_n, 0, (new_n - old_n) * 4, c->stream));
   }
-  bool structural = new_n != c->n_servants;
-  c->n_servants = new_n;
+  bool structural = new_n != old_n;  // (the appended rows are there already, zeroed)
   for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t s = idx[i];
-    const ydc_servant_row& r = rows[i];
-    uint64_t* env = &c->h_env[(size_t)s * EW];
-    bool env_changed = false;
-    for (uint32_t w = 0; w < EW; ++w) {
-      const uint64_t m = env_masks ? (w < env_words ? env_masks[(size_t)i * env_words + w] : 0)
-                                   : (w == 0 ? r.env_mask : 0);
-      env_changed |= env[w] != m;
-      env[w] = m;
-    }
-    structural |= env_changed || c->h_version[s] != r.version ||
-                  c->h_ip[s] != r.ip_id || (c->h_max_tasks[s] == 0) != (r.max_tasks == 0) ||
-                  std::min(c->h_max_tasks[s], c->h_nproc[s]) != std::min(r.max_tasks, r.num_processors);
-    c->h_version[s] = r.version;
-    c->h_nproc[s] = r.num_processors;
-    c->h_load[s] = r.current_load;
-    c->h_max_tasks[s] = r.max_tasks;
-    c->h_flags[s] = r.flags;
-    c->h_ip[s] = r.ip_id;
+    structural |= c->reg.structural(idx[i], rows[i], env_masks, env_words, i);
+    c->reg.store_row(idx[i], rows[i], env_masks, env_words, i);
   }
   if (n) {
     // One staged copy of the update list + one scatter kernel (rows are SoA on the device).
@@ -1209,7 +1161,7 @@ int ydc_update_servants_wide(ydc_context* c, const uint32_t* idx, const ydc_serv
     HIP_TRY(c, hipMemcpyAsync(c->d_upd_rows.p, rows, (size_t)n * sizeof(ydc_servant_row),
                               hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_apply_rows, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, c->d_upd_idx.p,
-                       (const ServantRowDev*)c->d_upd_rows.p, n, c->n_servants, c->d_version.p,
+                       (const ServantRowDev*)c->d_upd_rows.p, n, c->reg.n, c->d_version.p,
                        c->d_nproc.p, c->d_load.p, c->d_max_tasks.p, c->d_flags.p);
     HIP_TRY(c, hipGetLastError());
   }
@@ -1226,13 +1178,13 @@ int ydc_update_servants(ydc_context* c, const uint32_t* idx, const ydc_servant_r
 int ydc_set_host_aliases(ydc_context* c, const uint32_t* ip_id, const uint32_t* servant_idx, uint32_t n) {
   if (!c || (n && (!ip_id || !servant_idx))) return YDC_ERR_INVALID_ARGUMENT;
   for (uint32_t i = 0; i < n; ++i)
-    if (servant_idx[i] >= c->n_servants)
-      return fail(c, YDC_ERR_INVALID_ARGUMENT, "alias %u names servant %u of %u", i, servant_idx[i], c->n_servants);
+    if (servant_idx[i] >= c->reg.n)
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "alias %u names servant %u of %u", i, servant_idx[i], c->reg.n);
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->h_alias_ip.assign(ip_id, ip_id + n);
-  c->h_alias_servant.assign(servant_idx, servant_idx + n);
+  c->reg.alias_ip.assign(ip_id, ip_id + n);  // (n == 0: none)
+  c->reg.alias_servant.assign(servant_idx, servant_idx + n);
   return rebuild_tables(c);
 }
 
@@ -1243,7 +1195,7 @@ int ydc_set_host_aliases(ydc_context* c, const uint32_t* ip_id, const uint32_t* 
 static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_tick) {
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
-  const uint32_t S = c->n_servants, kept = S - n, EW = c->env_words;
+  const uint32_t S = c->reg.n, kept = S - n;
   auto& sm = c->stream_mode;
   const bool leased = sm.active && sm.leased();
   const bool alive = leased && sm.alive.on;
@@ -1265,9 +1217,8 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
   // Device: order-preserving compaction of the six resident columns into spare buffers,
   // which then take their place (running_tasks of the survivors never leaves the device).
   HIP_TRY(c, hipMemcpyAsync(c->d_upd_idx.p, idx, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  CompactCols in{{c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p, c->d_running.p, c->d_flags.p}};
-  CompactCols out{{c->d_spare[0].p, c->d_spare[1].p, c->d_spare[2].p, c->d_spare[3].p, c->d_spare[4].p,
-                   c->d_spare[5].p}};
+  CompactCols in{}, out{};
+  for (int k = 0; k < 6; ++k) in.col[k] = (c->*kRegCols[k].dev).p, out.col[k] = c->d_spare[k].p;
   hipLaunchKernelGGL(k_compact_rows, dim3(ceil_div(S, 256)), dim3(256), 0, c->stream, in, out,
                      c->d_upd_idx.p, n, S);
   // A leased stream: the leases of the removed rows vanish (UnsafeSweepOrphans), the others follow
@@ -1298,9 +1249,7 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (idx is pageable; the swap below retires the old columns)
   if (leased) HIP_TRY(c, hipMemcpy(&sm.n_leases, &sm.ls->n_leases, 4, hipMemcpyDeviceToHost));
   if (booked) HIP_TRY(c, hipMemcpy(&sm.book.n, &sm.book.bks->n_entries, 4, hipMemcpyDeviceToHost));
-  DevBuf<uint32_t>* cols[6] = {&c->d_version, &c->d_nproc, &c->d_load, &c->d_max_tasks, &c->d_running,
-                               &c->d_flags};
-  for (int k = 0; k < 6; ++k) std::swap(*cols[k], c->d_spare[k]);
+  for (int k = 0; k < 6; ++k) std::swap(c->*kRegCols[k].dev, c->d_spare[k]);
   if (alive) {
     std::swap(sm.alive.col, sm.alive.spare);
     sm.alive.n = kept;
@@ -1311,47 +1260,11 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
     sm.inspect.n = kept;
     sm.stale = true;  // (a captured step holds the count column's address)
   }
-  // Host mirror.
-  uint32_t w = 0, next = 0;
-  for (uint32_t s = 0; s < S; ++s) {
-    if (next < n && idx[next] == s) {
-      ++next;
-      continue;
-    }
-    if (w != s) {
-      c->h_version[w] = c->h_version[s];
-      c->h_nproc[w] = c->h_nproc[s];
-      c->h_load[w] = c->h_load[s];
-      c->h_max_tasks[w] = c->h_max_tasks[s];
-      c->h_flags[w] = c->h_flags[s];
-      c->h_ip[w] = c->h_ip[s];
-      for (uint32_t e = 0; e < EW; ++e) c->h_env[(size_t)w * EW + e] = c->h_env[(size_t)s * EW + e];
-    }
-    ++w;
-  }
-  c->n_servants = kept;
-  if (in_tick) {  // (the survivors' entries, in the new numbering)
-    size_t wa = 0;
-    for (size_t a = 0; a < c->h_alias_servant.size(); ++a) {
-      const uint32_t s = c->h_alias_servant[a];
-      const uint32_t before = (uint32_t)(std::lower_bound(idx, idx + n, s) - idx);
-      if (before < n && idx[before] == s) continue;
-      c->h_alias_ip[wa] = c->h_alias_ip[a];
-      c->h_alias_servant[wa++] = s - before;
-    }
-    c->h_alias_ip.resize(wa);
-    c->h_alias_servant.resize(wa);
-  } else {
-    c->h_alias_ip.clear();  // (row numbers moved)
-    c->h_alias_servant.clear();
-  }
-  c->h_version.resize(kept);
-  c->h_nproc.resize(kept);
-  c->h_load.resize(kept);
-  c->h_max_tasks.resize(kept);
-  c->h_flags.resize(kept);
-  c->h_ip.resize(kept);
-  c->h_env.resize((size_t)kept * EW);
+  // Host mirror; in a tick the survivors' aliases stay, in the new numbering (elsewhere the caller
+  // sets them again: row numbers moved).
+  c->reg.compact(idx, n);
+  if (in_tick) c->reg.renumber_aliases(idx, n);
+  else c->reg.clear_aliases();
   return rebuild_tables(c);  // classes, the ip table and the slot bound follow the registry
 }
 
@@ -1359,22 +1272,22 @@ int ydc_remove_servants(ydc_context* c, const uint32_t* idx, uint32_t n) {
   if (!c || (n && !idx)) return YDC_ERR_INVALID_ARGUMENT;
   if (!n) return YDC_OK;
   for (uint32_t i = 0; i < n; ++i)
-    if (idx[i] >= c->n_servants || (i && idx[i] <= idx[i - 1]))
-      return fail(c, YDC_ERR_INVALID_ARGUMENT, "removed rows must be ascending and < %u", c->n_servants);
+    if (idx[i] >= c->reg.n || (i && idx[i] <= idx[i - 1]))
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "removed rows must be ascending and < %u", c->reg.n);
   return remove_rows(c, idx, n, false);
 }
 
 // FreeTask's --running_tasks for a list of grants (servant indexes on the device).
 static void launch_release(ydc_context* c, const uint32_t* d_idx, uint32_t n) {
-  if (n >= 4096 && c->n_servants <= 16384 && c->opt_release_counted) {
-    if ((size_t)c->n_servants * 4 > 48 * 1024)  // (above 48 KB of dynamic LDS the runtime wants to be told)
+  if (n >= 4096 && c->reg.n <= 16384 && c->opt_release_counted) {
+    if ((size_t)c->reg.n * 4 > 48 * 1024)  // (above 48 KB of dynamic LDS the runtime wants to be told)
       (void)hipFuncSetAttribute((const void*)k_release_slots_counted, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((size_t)c->n_servants * 4));
+                                (int)((size_t)c->reg.n * 4));
     hipLaunchKernelGGL(k_release_slots_counted, dim3(ceil_div(n, kReleaseTile)), dim3(1024),
-                       (size_t)c->n_servants * 4, c->stream, d_idx, n, c->n_servants, c->d_running.p);
+                       (size_t)c->reg.n * 4, c->stream, d_idx, n, c->reg.n, c->d_running.p);
   } else {
     hipLaunchKernelGGL(k_release_slots, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, d_idx, n,
-                       c->n_servants, c->d_running.p);
+                       c->reg.n, c->d_running.p);
   }
 }
 
@@ -1387,15 +1300,9 @@ int ydc_release_slots(ydc_context* c, const uint32_t* servant_idx, uint32_t n) {
   // Through a pinned staging buffer, stream-ordered: no wait here (the next batch follows on
   // the same stream). The buffer is reused only after its previous copy has run.
   if (c->h_rel_ev) HIP_TRY(c, hipEventSynchronize(c->h_rel_ev));
-  if ((size_t)n * 4 > c->h_rel_cap) {
-    if (c->h_rel) (void)hipHostFree(c->h_rel);
-    c->h_rel = nullptr;
-    c->h_rel_cap = 0;
-    const size_t want = std::max<size_t>((size_t)n * 6, 4096);
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_rel, want));
-    c->h_rel_cap = want;
-  }
-  if (!c->h_rel_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->h_rel_ev, hipEventDisableTiming));
+  if ((size_t)n * 4 > c->h_rel.cap)
+    HIP_TRY(c, c->h_rel.reserve(std::max<size_t>((size_t)n * 6, 4096), hipHostMallocDefault));
+  HIP_TRY(c, c->h_rel_ev.create(hipEventDisableTiming));
   std::memcpy(c->h_rel, servant_idx, (size_t)n * 4);
   HIP_TRY(c, hipMemcpyAsync(c->d_upd_idx.p, c->h_rel, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipEventRecord(c->h_rel_ev, c->stream));
@@ -1415,7 +1322,7 @@ int ydc_release_slots_device(ydc_context* c, const uint32_t* d_servant_idx, uint
 }
 
 int ydc_set_running(ydc_context* c, const uint32_t* running, uint32_t n) {
-  if (!c || n != c->n_servants || (n && !running)) return YDC_ERR_INVALID_ARGUMENT;
+  if (!c || n != c->reg.n || (n && !running)) return YDC_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (released slots may still be on their way)
@@ -1424,7 +1331,7 @@ int ydc_set_running(ydc_context* c, const uint32_t* running, uint32_t n) {
 }
 
 int ydc_get_running(ydc_context* c, uint32_t* out, uint32_t n) {
-  if (!c || n != c->n_servants || (n && !out)) return YDC_ERR_INVALID_ARGUMENT;
+  if (!c || n != c->reg.n || (n && !out)) return YDC_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (released slots may still be on their way)
@@ -1453,7 +1360,7 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
   if (c->tables_dirty)
     if (int rc = rebuild_tables(c)) return rc;
   p.N = N;
-  p.S = c->n_servants;
+  p.S = c->reg.n;
   p.C = c->tables.n_classes();
   p.W = std::max<uint32_t>(1, ceil_div(p.C, 64));
   const uint64_t slot_bound64 = c->tables.max_slots;
@@ -1751,7 +1658,7 @@ void enqueue_gen(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk, boo
   ClassifyArgs ca{};
   if (N && classify) {
     ca = ClassifyArgs{TaskColumns{tk->env_id, tk->min_version, tk->requestor_ip}, N,
-                      c->d_cls_env.p, c->d_cls_ver.p, C, W, c->env_words,
+                      c->d_cls_env.p, c->d_cls_ver.p, C, W, c->reg.env_words,
                       c->tables.env_ver_mask.empty() ? nullptr : c->d_ver_sorted.p,
                       c->tables.env_ver_mask.empty() ? nullptr : c->d_env_ver_mask.p,
                       (uint32_t)c->tables.ver_sorted.size(), c->d_ip_sorted.p, c->d_ip_servant.p, S,
@@ -1922,24 +1829,24 @@ int enqueue_front_b(ydc_context* c, const BatchPlan& p, const uint32_t* d_base) 
 
 // Host columns -> pinned arena -> device mirror, on the copy stream; the dispatch stream waits
 // for the copy (only the kernels behind this point read the columns).
-int stage_host_requests(ydc_context* c) {
-  auto& h = c->host_in;
-  std::memcpy(c->h_in, h.tk->env_id, (size_t)h.n * 4);
-  std::memcpy(c->h_in + h.col, h.tk->min_version, (size_t)h.n * 4);
-  std::memcpy(c->h_in + 2 * h.col, h.tk->requestor_ip, (size_t)h.n * 4);
-  HIP_TRY(c, hipMemcpyAsync(c->d_in.p, c->h_in, h.bytes, hipMemcpyHostToDevice, c->copy_stream));
+int stage_host_requests(ydc_context* c, const BatchCall& call) {
+  auto& h = call.host_in;
+  std::memcpy(c->h_in.p, h.tk->env_id, (size_t)h.n * 4);
+  std::memcpy(c->h_in.p + h.col, h.tk->min_version, (size_t)h.n * 4);
+  std::memcpy(c->h_in.p + 2 * h.col, h.tk->requestor_ip, (size_t)h.n * 4);
+  HIP_TRY(c, hipMemcpyAsync(c->d_in.p, c->h_in.p, h.bytes, hipMemcpyHostToDevice, c->copy_stream));
   HIP_TRY(c, hipEventRecord(c->copy_ev, c->copy_stream));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, c->copy_ev, 0));
   return YDC_OK;
 }
 
-int enqueue_front(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk) {
-  if (c->host_in.active && p.N) {
+int enqueue_front(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk, const BatchCall& call) {
+  if (call.host_in.tk && p.N) {
     // Host-buffer entry point: everything that does not read the requests first.
     enqueue_scan(c, p, c->d_cls_begin.p);
     enqueue_gen(c, p, tk, true, false);
     if (int rc = enqueue_sort(c, p, false)) return rc;
-    if (int rc = stage_host_requests(c)) return rc;
+    if (int rc = stage_host_requests(c, call)) return rc;
     enqueue_gen(c, p, tk, false, true);
     const PrefixArgs pa = prefix_args(c, p);
     YDC_LAUNCH(c, "k_chunk_prefix", k_chunk_prefix, dim3(1), dim3(1024), 0, c->stream, pa, c->d_prm.p);
@@ -1950,13 +1857,14 @@ int enqueue_front(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk) {
 }
 
 // One matching pass (match_kernel.h). device_check: return at once when the previous pass
-// found every chunk consistent.
-void enqueue_pass(ydc_context* c, const BatchPlan& p, uint32_t pass, uint32_t device_check) {
+// found every chunk consistent. walk: 8 for the walk's scout, 16 for the walk itself, 0 for an
+// ordinary pass (match_kernel.h).
+void enqueue_pass(ydc_context* c, const BatchPlan& p, uint32_t pass, uint32_t device_check, uint32_t walk = 0) {
   if (p.fuse01 && pass == 1) return;  // (the launch of pass 0 did it)
   const size_t lds = (size_t)p.ring_total * 8;
   device_check |= c->debug_sim ? 2u : 0u;
   device_check |= c->opt_pair ? 4u : 0u;
-  device_check |= c->walk_flag;  // (8: the walk's scout, 16: the walk itself — match_kernel.h)
+  device_check |= walk;
   device_check |= p.ring_total << 8;
   DeviceParams* prm = c->d_prm.p;
   // (rings of 32 entries are watched by the fast loop itself: match_kernel.h, CHECKED)
@@ -1984,8 +1892,7 @@ void enqueue_pass(ydc_context* c, const BatchPlan& p, uint32_t pass, uint32_t de
 // slot -> servant index, utilisation, running_tasks (one launch). check_slot != kNone: only
 // takes effect when the pass with that counter slot found every chunk consistent. start_state
 // (multi-GPU): class states before this rank's first request; d_taken: its slot deltas.
-int enqueue_finalize(ydc_context* c, const BatchPlan& p, uint32_t flags, uint32_t* d_out_idx,
-                     double* d_out_util, uint32_t* d_out_running, uint32_t check_slot,
+int enqueue_finalize(ydc_context* c, const BatchPlan& p, const BatchCall& call, uint32_t check_slot,
                      uint32_t* d_taken = nullptr, const ClassState* start_state = nullptr) {
   const uint32_t S = p.S, N = p.N;
   const uint32_t req_blocks = ceil_div(N, 256), srv_blocks = ceil_div(S, 256);
@@ -2002,24 +1909,24 @@ int enqueue_finalize(ydc_context* c, const BatchPlan& p, uint32_t flags, uint32_
   ra.cap_bits = c->kf.cap_bits;
   ra.n_servants = S;
   ra.running_out = c->d_running_out.p;
-  ra.out_a = d_out_running;
+  ra.out_a = call.out_running;
   // The resident column is NOT written by this launch: its servant threads read the running
   // value of other servants (the head of their class list), so COMMIT is a copy behind it.
   ra.out_b = nullptr;
   ra.taken_out = d_taken;
-  ra.pipelined = c->enqueue_pipelined ? 1u : 0u;
-  ra.host_outcome = srv_blocks && c->opt_outcome_store ? c->finalize_outcome : nullptr;
+  ra.pipelined = call.pipelined ? 1u : 0u;
+  ra.host_outcome = srv_blocks && c->opt_outcome_store ? call.outcome : nullptr;
   ra.srv_blocks = srv_blocks;
   YDC_LAUNCH(c, "k_finalize", k_finalize, dim3(req_blocks + srv_blocks), dim3(256), 0, c->stream, p.sv,
              c->d_slot_base.p, c->d_owner.p, p.rank_to_g, c->d_slot_of.p, N, p.wave_path ? 1u : 0u,
-             d_out_idx, d_out_util, check_slot, c->d_prm.p, p.gbits ? (1u << p.gbits) - 1 : 0xFFFFFFFFu,
+             call.out_idx, call.out_util, check_slot, c->d_prm.p, p.gbits ? (1u << p.gbits) - 1 : 0xFFFFFFFFu,
              req_blocks, ra, p.rank_stride);
   // COMMIT (`++pick->running_tasks`, task_dispatcher.cc:123): running_out -> the resident column.
   // When the passes have not converged yet running_out == running and the step is repeated.
   // Round 5: no copy where the caller can simply make running_out THE column afterwards
-  // (commit_by_swap; a 4 us blit kernel per committed batch otherwise — kept where pointers are
+  // (BatchCall::by_swap; a 4 us blit kernel per committed batch otherwise — kept where pointers are
   // baked into a captured step).
-  if ((flags & YDC_DISPATCH_COMMIT) && S && !c->commit_by_swap)
+  if ((call.flags & YDC_DISPATCH_COMMIT) && S && !call.by_swap)
     HIP_TRY(c, hipMemcpyAsync(c->d_running.p, c->d_running_out.p, (size_t)S * 4, hipMemcpyDeviceToDevice,
                               c->stream));
   return YDC_OK;
@@ -2164,8 +2071,7 @@ uint32_t first_group(const ydc_context* c, const BatchPlan& p) {
 
 // Passes [launched, ...) in groups until one finds every chunk consistent, each group
 // followed by the (gated) finalise and one look at the counters.
-int run_passes_until_consistent(ydc_context* c, const BatchPlan& p, uint32_t launched, uint32_t flags,
-                                uint32_t* d_out_idx, double* d_out_util, uint32_t* d_out_running,
+int run_passes_until_consistent(ydc_context* c, const BatchPlan& p, uint32_t launched, const BatchCall& call,
                                 uint32_t* rounds) {
   bool walked = false;
   for (;;) {
@@ -2179,41 +2085,30 @@ int run_passes_until_consistent(ydc_context* c, const BatchPlan& p, uint32_t lau
       }
     }
     const uint32_t first = launched;
-    // (k_finalize stores the outcome to the page-locked block itself where it has servant workgroups)
-    const bool outcome_stored = c->opt_outcome_store && p.S != 0;
-    c->finalize_outcome = outcome_stored ? c->d_h_prm : nullptr;
     if (launched >= c->opt_walk_after && !walked && group >= 4) {
       // Parallel repair is not getting anywhere (one chunk per pass): scout + walk, then two
       // ordinary passes that find everything consistent (match_kernel.h: walk_scout / walk_run).
       walked = true;
       c->walked_at = launched;
       HIP_TRY(c, hipMemsetAsync(&c->d_prm.p->reserved0, 0xFF, 4, c->stream));
-      c->walk_flag = 8u;
-      enqueue_pass(c, p, launched, 1u);
-      c->walk_flag = 16u;
-      enqueue_pass(c, p, launched + 1, 1u);
-      c->walk_flag = 0;
+      enqueue_pass(c, p, launched, 1u, 8u);
+      enqueue_pass(c, p, launched + 1, 1u, 16u);
       for (uint32_t r = launched + 2; r < launched + group; ++r) enqueue_pass(c, p, r, 1u);
     } else {
       for (uint32_t r = launched; r < launched + group; ++r) enqueue_pass(c, p, r, 1u);
     }
     launched += group;
-    const bool by_swap = c->opt_commit_swap && !c->stream_mode.active && (flags & YDC_DISPATCH_COMMIT) && p.S;
-    c->commit_by_swap = by_swap;
-    const int frc = enqueue_finalize(c, p, flags, d_out_idx, d_out_util, d_out_running, (launched - 1) & 63);
-    c->commit_by_swap = false;
-    c->finalize_outcome = nullptr;
-    if (frc) return frc;
+    if (int frc = enqueue_finalize(c, p, call, (launched - 1) & 63)) return frc;
     mark(c, 7);
-    if (c->post_copy.bytes)  // a finalise that was gated out is repeated, and so is the copy
-      HIP_TRY(c, hipMemcpyAsync(c->post_copy.dst, c->post_copy.src, c->post_copy.bytes,
+    if (call.post_copy.bytes)  // a finalise that was gated out is repeated, and so is the copy
+      HIP_TRY(c, hipMemcpyAsync(call.post_copy.dst, call.post_copy.src, call.post_copy.bytes,
                                 hipMemcpyDeviceToHost, c->stream));
-    int done = read_outcome(c, p, first, launched, rounds, outcome_stored);
+    int done = read_outcome(c, p, first, launched, rounds, call.outcome != nullptr);
     if (done < 0) return done;
     if (done == 2) return kRetryRadix;
     if (done) {
       // (the finalise just waited for was the final one: its output IS the column now)
-      if (by_swap) std::swap(c->d_running, c->d_running_out);
+      if (call.by_swap) std::swap(c->d_running, c->d_running_out);
       if (c->debug_sim) {
         fprintf(stderr, "[ydc match] K=%u cs=%u R=%u fill=%u rounds=%u sims=%u pass changed ends:", p.K,
                 p.cs, 1u << p.rshift, p.init_fill, *rounds, c->h_prm->chunk_sims);
@@ -2287,11 +2182,10 @@ int verify_binsort(ydc_context* c, const BatchPlan& p) {
 
 // Front, matching passes and finalise of a planned batch; returns when the results are there.
 // kRetryRadix: the plan used the bin sort and a bin overflowed — nothing was committed.
-int run_planned_batch(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk, uint32_t flags,
-                      uint32_t* d_out_idx, double* d_out_util, uint32_t* d_out_running,
+int run_planned_batch(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk, const BatchCall& call,
                       uint32_t* rounds_out) {
   const uint32_t N = p.N;
-  if (int rc = enqueue_front(c, p, tk)) return rc;
+  if (int rc = enqueue_front(c, p, tk, call)) return rc;
   if (p.binsort && c->debug_verify_binsort)
     if (int rc = verify_binsort(c, p)) return rc;
   hipStream_t st = c->stream;
@@ -2300,9 +2194,7 @@ int run_planned_batch(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk
   mark(c, 6);
   if (p.wave_path) {
     c->walked_at = 0;
-    if (int rc = run_passes_until_consistent(c, p, 0, flags, d_out_idx, d_out_util, d_out_running,
-                                             &rounds))
-      return rc;
+    if (int rc = run_passes_until_consistent(c, p, 0, call, &rounds)) return rc;
     // (a batch that had to be walked says nothing about how many passes the next one wants —
     // but if it is another of its kind, it should get to the walk as early)
     c->round_hint = c->walked_at ? std::min(c->walked_at, 3u) : rounds;
@@ -2390,14 +2282,12 @@ int run_planned_batch(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk
           return fail(c, YDC_ERR_NOT_CONVERGED, "no fixpoint after %u rounds", rounds);
       }
     }
-    const bool by_swap = c->opt_commit_swap && !c->stream_mode.active && (flags & YDC_DISPATCH_COMMIT) && p.S;
-    c->commit_by_swap = by_swap;
-    const int frc = enqueue_finalize(c, p, flags, d_out_idx, d_out_util, d_out_running, kNone);
-    c->commit_by_swap = false;
-    if (frc) return frc;
+    BatchCall fin = call;
+    fin.outcome = nullptr;  // (the host has checked the rounds itself: d_prm is read back below)
+    if (int frc = enqueue_finalize(c, p, fin, kNone)) return frc;
     mark(c, 7);
-    if (c->post_copy.bytes)
-      HIP_TRY(c, hipMemcpyAsync(c->post_copy.dst, c->post_copy.src, c->post_copy.bytes,
+    if (call.post_copy.bytes)
+      HIP_TRY(c, hipMemcpyAsync(call.post_copy.dst, call.post_copy.src, call.post_copy.bytes,
                                 hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(c->h_prm, prm, sizeof(DeviceParams), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
@@ -2405,7 +2295,7 @@ int run_planned_batch(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk
     if (c->h_prm->overflow)
       return fail(c, YDC_ERR_CAPACITY, "slot workspace overflow (bound %u)", p.slot_bound);
     if (p.binsort && c->h_prm->window_miss) return kRetryRadix;
-    if (by_swap) std::swap(c->d_running, c->d_running_out);  // (an ungated finalise: always final here)
+    if (call.by_swap) std::swap(c->d_running, c->d_running_out);  // (an ungated finalise: always final here)
   }
   *rounds_out = rounds;
   return YDC_OK;
@@ -2421,14 +2311,14 @@ void note_bin_overflow(ydc_context* c) {
 
 // Plans a batch and places it, host-checked (*p: the plan it was placed with); a bin overflow
 // places it once more with the radix sort.
-int place_batch(ydc_context* c, uint32_t N, const ydc_task_soa* tk, uint32_t flags, uint32_t* d_out_idx,
-                double* d_out_util, uint32_t* d_out_running, BatchPlan* p, uint32_t* rounds_out) {
+int place_batch(ydc_context* c, uint32_t N, const ydc_task_soa* tk, const BatchCall& call, BatchPlan* p,
+                uint32_t* rounds_out) {
   if (int rc = plan_batch(c, N, p)) return rc;
-  int rc = run_planned_batch(c, *p, tk, flags, d_out_idx, d_out_util, d_out_running, rounds_out);
+  int rc = run_planned_batch(c, *p, tk, call, rounds_out);
   if (rc == kRetryRadix) {
     note_bin_overflow(c);
     if (int rc2 = plan_batch(c, N, p)) return rc2;
-    rc = run_planned_batch(c, *p, tk, flags, d_out_idx, d_out_util, d_out_running, rounds_out);
+    rc = run_planned_batch(c, *p, tk, call, rounds_out);
   }
   return rc;
 }
@@ -2448,7 +2338,7 @@ namespace {
 // the key otherwise (packed_tick=0: always).
 bool tick_packed(const ydc_context* c, uint32_t* idx_bits_out = nullptr) {
   uint32_t idx_bits = 1;
-  while ((1u << idx_bits) < std::max(c->n_servants, 2u)) ++idx_bits;
+  while ((1u << idx_bits) < std::max(c->reg.n, 2u)) ++idx_bits;
   if (idx_bits_out) *idx_bits_out = idx_bits;
   return c->opt_tick_packed && c->tables.cap_bits <= 10 && 2 * c->tables.cap_bits + 1 + idx_bits <= 32;
 }
@@ -2465,44 +2355,9 @@ bool tick_same_requests(const ydc_task_soa* tk, uint32_t n) {
 
 bool tick_takes(const ydc_context* c, uint32_t n_tasks, bool same = false) {
   same = same && tick_packed(c);  // (the wide builds of the kernel merge with one-word candidates only)
-  return n_tasks <= c->small_batch(same) && c->small_batch() && c->n_servants <= kTickMaxServants &&
-         c->tables.n_classes() <= kTickMaxClasses && c->h_alias_ip.empty() && c->group.n_ranks == 0 &&
+  return n_tasks <= c->small_batch(same) && c->small_batch() && c->reg.n <= kTickMaxServants &&
+         c->tables.n_classes() <= kTickMaxClasses && c->reg.alias_ip.empty() && c->group.n_ranks == 0 &&
          !c->stream_mode.active && c->pend_count == 0 && !c->debug_sim && !c->debug_verify_binsort;
-}
-
-// A heartbeat row that changes what the derived tables are built from (classes, the ip table,
-// the slot bound): a new servant, another version / host / capacity bound, or (row i of
-// env_masks, env_words words each) another environment set, the shorter of the two masks
-// extended with zero words. A row without masks on a table of several mask words cannot say what
-// the servant advertises: it keeps its environments.
-bool row_is_structural(const ydc_context* c, uint32_t s, const ydc_servant_row& r, const uint64_t* env_masks,
-                       uint32_t env_words, uint32_t i) {
-  if (s >= c->n_servants) return true;
-  const uint32_t EW = c->env_words;
-  bool env_changed = false;
-  if (env_masks) {
-    for (uint32_t w = 0; w < std::max(EW, env_words); ++w) {
-      const uint64_t have = w < EW ? c->h_env[(size_t)s * EW + w] : 0;
-      const uint64_t want = w < env_words ? env_masks[(size_t)i * env_words + w] : 0;
-      env_changed |= have != want;
-    }
-  } else if (EW == 1) {
-    env_changed = c->h_env[s] != r.env_mask;
-  }
-  return env_changed || c->h_version[s] != r.version || c->h_ip[s] != r.ip_id ||
-         (c->h_max_tasks[s] == 0) != (r.max_tasks == 0) ||
-         std::min(c->h_max_tasks[s], c->h_nproc[s]) != std::min(r.max_tasks, r.num_processors);
-}
-
-// The host mirror of the columns that heartbeat rows which change no structure replace.
-void mirror_rows(ydc_context* c, const uint32_t* idx, const ydc_servant_row* rows, uint32_t n) {
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t s = idx[i];
-    c->h_nproc[s] = rows[i].num_processors;
-    c->h_load[s] = rows[i].current_load;
-    c->h_max_tasks[s] = rows[i].max_tasks;
-    c->h_flags[s] = rows[i].flags;
-  }
 }
 
 // ---- the resident kernel (tick_kernel.h: TickBox) ----
@@ -2586,12 +2441,11 @@ void resident_atexit() {
 
 int resident_prepare(ydc_context* c) {
   if (!c->h_box) {
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_box, sizeof(TickBox), hipHostMallocCoherent | hipHostMallocMapped));
+    HIP_TRY(c, c->h_box.reserve(sizeof(TickBox)));
     std::memset(c->h_box, 0, sizeof(TickBox));
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&c->d_box, c->h_box, 0));
   }
-  if (!c->res_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->res_stream, hipStreamNonBlocking));
-  if (!c->res_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->res_ev, hipEventDisableTiming));
+  HIP_TRY(c, c->res_stream.create());
+  HIP_TRY(c, c->res_ev.create(hipEventDisableTiming));
   return YDC_OK;
 }
 
@@ -2618,7 +2472,7 @@ void tick_stats(ydc_context* c, uint32_t N, uint32_t granted, uint32_t timeouts,
   ydc_stats& st = c->stats;
   std::memset(&st, 0, sizeof(st));
   st.n_tasks = N;
-  st.n_servants = c->n_servants;
+  st.n_servants = c->reg.n;
   st.n_classes = c->tables.n_classes();
   st.key_bits = c->kf.key_bits;
   st.n_chunks = 1;
@@ -2651,7 +2505,7 @@ bool resident_receive(ydc_context* c, const TickCall& io, uint32_t seq) {
 }
 
 int tick_run(ydc_context* c, const TickCall& io) {
-  const uint32_t S = c->n_servants, C = c->tables.n_classes(), N = io.n_tasks;
+  const uint32_t S = c->reg.n, C = c->tables.n_classes(), N = io.n_tasks;
   const uint32_t W = std::max<uint32_t>(1, ceil_div(C, 64));
   const bool commit0 = (io.flags & YDC_DISPATCH_COMMIT) != 0;
   // The resident form takes what a scheduler's turn looks like: COMMIT, host buffers, everything
@@ -2714,9 +2568,8 @@ int tick_run(ydc_context* c, const TickCall& io) {
   if (resident)
     if (int rc = resident_prepare(c)) return rc;
   if (!c->h_tick_done) {
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_tick_done, sizeof(TickDone), hipHostMallocCoherent | hipHostMallocMapped));
+    HIP_TRY(c, c->h_tick_done.reserve(sizeof(TickDone)));
     std::memset(c->h_tick_done, 0, sizeof(TickDone));
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&c->d_tick_done, c->h_tick_done, 0));
   }
   auto pad = [](size_t b) { return (b + 63) & ~(size_t)63; };
   // Arena: [request columns] [heartbeat indexes | rows] [released] | [idx] [utilisation]
@@ -2728,15 +2581,7 @@ int tick_run(ydc_context* c, const TickCall& io) {
   const size_t o_idx = o_rel + (rel_ptr ? pad((size_t)io.n_rel * 4) : 0);
   const size_t o_util = o_idx + (io.out_on_device ? 0 : pad((size_t)N * 4));
   const size_t need = o_util + (!io.out_on_device && io.out_util ? pad((size_t)N * 8) : 0);
-  if (need > c->tick_io_cap) {
-    if (c->h_tick_io) (void)hipHostFree(c->h_tick_io);
-    c->h_tick_io = c->d_tick_io = nullptr;
-    c->tick_io_cap = 0;
-    const size_t want = std::max<size_t>(need + need / 2, 8192);
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_tick_io, want, hipHostMallocCoherent | hipHostMallocMapped));
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&c->d_tick_io, c->h_tick_io, 0));
-    c->tick_io_cap = want;
-  }
+  if (need > c->h_tick_io.cap) HIP_TRY(c, c->h_tick_io.reserve(std::max<size_t>(need + need / 2, 8192)));
   const bool commit = (io.flags & YDC_DISPATCH_COMMIT) != 0;
   TickArgs a;
   a.nproc = c->d_nproc.p;
@@ -2750,7 +2595,7 @@ int tick_run(ydc_context* c, const TickCall& io) {
   a.cls_ver = c->d_cls_ver.p;
   a.S = S;
   a.C = C;
-  a.EW = c->env_words;
+  a.EW = c->reg.env_words;
   a.W = W;
   // running_tasks: the picks work on the resident column (COMMIT) or on a copy of it.
   uint32_t* dev_run_out = io.out_running ? (io.out_on_device ? io.out_running : c->d_running_out.p) : nullptr;
@@ -2764,12 +2609,12 @@ int tick_run(ydc_context* c, const TickCall& io) {
     a.t_rip = io.tasks->requestor_ip;
   } else if (tasks_ptr) {
     const size_t col = pad((size_t)N * 4);
-    std::memcpy(c->h_tick_io + o_env, io.tasks->env_id, (size_t)N * 4);
-    std::memcpy(c->h_tick_io + o_env + col, io.tasks->min_version, (size_t)N * 4);
-    std::memcpy(c->h_tick_io + o_env + 2 * col, io.tasks->requestor_ip, (size_t)N * 4);
-    a.t_env = (const uint32_t*)(c->d_tick_io + o_env);
-    a.t_minv = (const uint32_t*)(c->d_tick_io + o_env + col);
-    a.t_rip = (const uint32_t*)(c->d_tick_io + o_env + 2 * col);
+    std::memcpy(c->h_tick_io.p + o_env, io.tasks->env_id, (size_t)N * 4);
+    std::memcpy(c->h_tick_io.p + o_env + col, io.tasks->min_version, (size_t)N * 4);
+    std::memcpy(c->h_tick_io.p + o_env + 2 * col, io.tasks->requestor_ip, (size_t)N * 4);
+    a.t_env = (const uint32_t*)(c->h_tick_io.z + o_env);
+    a.t_minv = (const uint32_t*)(c->h_tick_io.z + o_env + col);
+    a.t_rip = (const uint32_t*)(c->h_tick_io.z + o_env + 2 * col);
   } else {
     for (uint32_t i = 0; i < N; ++i) {
       a.in_env[i] = io.tasks->env_id[i];
@@ -2781,29 +2626,29 @@ int tick_run(ydc_context* c, const TickCall& io) {
   a.upd_idx = nullptr;
   a.upd_rows = nullptr;
   {
-    uint32_t* idx = upd_ptr ? (uint32_t*)(c->h_tick_io + o_upd) : a.in_upd_idx;
-    TickRow* rows = upd_ptr ? (TickRow*)(c->h_tick_io + o_rows) : a.in_upd;
+    uint32_t* idx = upd_ptr ? (uint32_t*)(c->h_tick_io.p + o_upd) : a.in_upd_idx;
+    TickRow* rows = upd_ptr ? (TickRow*)(c->h_tick_io.p + o_rows) : a.in_upd;
     for (uint32_t i = 0; i < io.n_upd; ++i) {
       idx[i] = io.upd_idx[i];
       rows[i] = TickRow{io.upd_rows[i].num_processors, io.upd_rows[i].current_load, io.upd_rows[i].max_tasks,
                         io.upd_rows[i].flags};
     }
     if (upd_ptr) {
-      a.upd_idx = (const uint32_t*)(c->d_tick_io + o_upd);
-      a.upd_rows = (const TickRow*)(c->d_tick_io + o_rows);
+      a.upd_idx = (const uint32_t*)(c->h_tick_io.z + o_upd);
+      a.upd_rows = (const TickRow*)(c->h_tick_io.z + o_rows);
     }
   }
   a.n_rel = io.n_rel;
   a.rel = nullptr;
   if (rel_ptr) {
-    std::memcpy(c->h_tick_io + o_rel, io.rel, (size_t)io.n_rel * 4);
-    a.rel = (const uint32_t*)(c->d_tick_io + o_rel);
+    std::memcpy(c->h_tick_io.p + o_rel, io.rel, (size_t)io.n_rel * 4);
+    a.rel = (const uint32_t*)(c->h_tick_io.z + o_rel);
   } else if (io.n_rel) {
     std::memcpy(a.in_rel, io.rel, (size_t)io.n_rel * 4);
   }
-  a.out_idx = io.out_on_device ? io.out_idx : (uint32_t*)(c->d_tick_io + o_idx);
-  a.out_util = io.out_util ? (io.out_on_device ? io.out_util : (double*)(c->d_tick_io + o_util)) : nullptr;
-  a.done = c->d_tick_done;
+  a.out_idx = io.out_on_device ? io.out_idx : (uint32_t*)(c->h_tick_io.z + o_idx);
+  a.out_util = io.out_util ? (io.out_on_device ? io.out_util : (double*)(c->h_tick_io.z + o_util)) : nullptr;
+  a.done = c->h_tick_done.dev();
   a.box = nullptr;
   a.idle_ticks = 0;
   if (++c->tick_seq == 0) c->tick_seq = 1;
@@ -2812,10 +2657,10 @@ int tick_run(ydc_context* c, const TickCall& io) {
   if (resident) {
     // This launch stays: it answers through the mailbox like every later command, on a stream of
     // its own, behind whatever the context's stream still has in flight.
-    a.box = c->d_box;
+    a.box = c->h_box.dev();
     a.idle_ticks = (unsigned long long)c->opt_resident_idle_ms * 100000ull;
-    a.out_idx = c->d_box->out_idx;
-    a.out_util = io.out_util ? c->d_box->out_util : nullptr;
+    a.out_idx = c->h_box.dev()->out_idx;
+    a.out_util = io.out_util ? c->h_box.dev()->out_util : nullptr;
     __atomic_store_n(&c->h_box->alive, 1u, __ATOMIC_RELEASE);
     HIP_TRY(c, hipEventRecord(c->res_ev, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(c->res_stream, c->res_ev, 0));
@@ -2899,8 +2744,8 @@ int tick_run(ydc_context* c, const TickCall& io) {
   if (io.out_on_device || (io.out_running && !io.out_on_device) || c->profiling)
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // (device outputs: complete when the call returns)
   if (!io.out_on_device) {
-    if (N) std::memcpy(io.out_idx, c->h_tick_io + o_idx, (size_t)N * 4);
-    if (N && io.out_util) std::memcpy(io.out_util, c->h_tick_io + o_util, (size_t)N * 8);
+    if (N) std::memcpy(io.out_idx, c->h_tick_io.p + o_idx, (size_t)N * 4);
+    if (N && io.out_util) std::memcpy(io.out_util, c->h_tick_io.p + o_util, (size_t)N * 8);
     if (io.out_running && S)
       HIP_TRY(c, hipMemcpy(io.out_running, dev_run_out, (size_t)S * 4, hipMemcpyDeviceToHost));
   }
@@ -2914,19 +2759,15 @@ int tick_run(ydc_context* c, const TickCall& io) {
   return YDC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ydc_dispatch_device(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t flags,
-                        uint32_t* d_out_idx, double* d_out_util, uint32_t* d_out_running) {
-  if (!c || (N && !tk)) return YDC_ERR_INVALID_ARGUMENT;
+// One batch whose request columns (tk) and outputs are device addresses, placed when this returns:
+// the body of ydc_dispatch_device, and what ydc_dispatch hands its staged call to.
+int dispatch_batch(ydc_context* c, const ydc_task_soa* tk, uint32_t N, const BatchCall& call) {
   if (c->max_tasks && N > c->max_tasks)
     return fail(c, YDC_ERR_CAPACITY, "%u tasks > max_tasks %u", N, c->max_tasks);
   if (c->pend_count && !c->pend[c->pend_head].rerun && c->pend[c->pend_head].active)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "pipelined batches outstanding: ydc_dispatch_wait first");
   HIP_TRY(c, hipSetDevice(c->device));
-  if (N && N <= c->small_batch() && d_out_idx && !c->host_in.active && !c->post_copy.bytes) {
+  if (N && N <= c->small_batch() && call.out_idx && !call.staged()) {
     // A handful of requests: one launch of the one-workgroup kernel (tick_kernel.h).
     if (c->tables_dirty)
       if (int rc = rebuild_tables(c)) return rc;
@@ -2935,10 +2776,10 @@ int ydc_dispatch_device(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint
       io.tasks = tk;
       io.tasks_on_device = true;
       io.n_tasks = N;
-      io.flags = flags;
-      io.out_idx = d_out_idx;
-      io.out_util = d_out_util;
-      io.out_running = d_out_running;
+      io.flags = call.flags;
+      io.out_idx = call.out_idx;
+      io.out_util = call.out_util;
+      io.out_running = call.out_running;
       io.out_on_device = true;
       return tick_run(c, io);
     }
@@ -2946,7 +2787,7 @@ int ydc_dispatch_device(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   BatchPlan p;
   uint32_t rounds = 0;
-  if (int rc = place_batch(c, N, tk, flags, d_out_idx, d_out_util, d_out_running, &p, &rounds)) return rc;
+  if (int rc = place_batch(c, N, tk, call, &p, &rounds)) return rc;
   fill_stats(c, p, rounds);
   ydc_stats& s = c->stats;
   if (c->profiling) {
@@ -2955,6 +2796,16 @@ int ydc_dispatch_device(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint
     collect_kernel_profile(c);
   }
   return YDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ydc_dispatch_device(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t flags,
+                        uint32_t* d_out_idx, double* d_out_util, uint32_t* d_out_running) {
+  if (!c || (N && !tk)) return YDC_ERR_INVALID_ARGUMENT;
+  return dispatch_batch(c, tk, N, batch_call(c, flags, d_out_idx, d_out_util, d_out_running, c->h_prm.dev()));
 }
 
 // Pipelined form of ydc_dispatch_device: enqueues the whole batch (front, the matching passes the
@@ -2973,11 +2824,8 @@ int ydc_dispatch_device_async(ydc_context* c, const ydc_task_soa* tk, uint32_t N
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   auto& pd = c->pend[(c->pend_head + c->pend_count) & 1];
-  if (!pd.h_outcome) {
-    HIP_TRY(c, hipHostMalloc((void**)&pd.h_outcome, sizeof(DeviceParams), hipHostMallocCoherent | hipHostMallocMapped));
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&pd.d_h_outcome, pd.h_outcome, 0));
-  }
-  if (!pd.ev) HIP_TRY(c, hipEventCreateWithFlags(&pd.ev, hipEventDisableTiming));
+  HIP_TRY(c, pd.h_outcome.reserve(sizeof(DeviceParams)));
+  HIP_TRY(c, pd.ev.create(hipEventDisableTiming));
   pd.active = true;
   pd.rerun = false;
   pd.tk = tk ? *tk : ydc_task_soa{};
@@ -3000,25 +2848,19 @@ int ydc_dispatch_device_async(ydc_context* c, const ydc_task_soa* tk, uint32_t N
     // (registries without the wave path have host-checked rounds: placed when waited for)
     pd.rerun = true;
   } else {
-    if (int rc = enqueue_front(c, pd.plan, &pd.tk)) return give_up(rc);
+    // (the outcome block: stored by k_finalize's last servant workgroup; a registry without
+    // servants has none, then it is read back with a copy)
+    BatchCall call = batch_call(c, flags, d_out_idx, d_out_util, d_out_running, pd.h_outcome.dev());
+    call.pipelined = true;
+    const bool outcome_stored = call.outcome != nullptr;
+    if (int rc = enqueue_front(c, pd.plan, &pd.tk, call)) return give_up(rc);
     const uint32_t group = first_group(c, pd.plan);
     for (uint32_t r = 0; r < group; ++r) enqueue_pass(c, pd.plan, r, 1u);
     pd.launched = group;
-    c->enqueue_pipelined = true;
-    // (the outcome block: stored by k_finalize's last servant workgroup; a registry without
-    // servants has none, then it is read back with a copy)
-    const bool outcome_stored = c->opt_outcome_store && pd.plan.S != 0;
-    c->finalize_outcome = outcome_stored ? pd.d_h_outcome : nullptr;
-    const bool by_swap = c->opt_commit_swap && !c->stream_mode.active && (flags & YDC_DISPATCH_COMMIT) && pd.plan.S;
-    c->commit_by_swap = by_swap;
-    int rc = enqueue_finalize(c, pd.plan, flags, d_out_idx, d_out_util, d_out_running, (group - 1) & 63);
-    c->commit_by_swap = false;
-    c->finalize_outcome = nullptr;
-    c->enqueue_pipelined = false;
-    if (rc) return give_up(rc);
+    if (int rc = enqueue_finalize(c, pd.plan, call, (group - 1) & 63)) return give_up(rc);
     // (a batch that turns out not to be final wrote the column's own values: the exchange is
     // harmless then, and the replay plans with the pointers as they are)
-    if (by_swap) std::swap(c->d_running, c->d_running_out);
+    if (call.by_swap) std::swap(c->d_running, c->d_running_out);
     // (from here on the batch may take effect: a failing copy / event leaves it to be waited for
     // the slow way — a stream synchronise instead of the event)
     if ((!outcome_stored &&
@@ -3047,7 +2889,7 @@ int ydc_dispatch_wait(ydc_context* c) {
   uint32_t rounds = 0;
   if (!miss) {
     HIP_TRY(c, hipEventSynchronize(pd.ev));
-    const DeviceParams& o = *pd.h_outcome;
+    const DeviceParams& o = *pd.h_outcome.get();
     if (o.overflow) {
       // Took no effect and latched the pipeline (k_finalize's gate includes overflow for
       // pipelined batches), so the batch behind it has not taken any either: drain, clear the
@@ -3115,7 +2957,7 @@ int ydc_dispatch(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t fl
       return tick_run(c, io);
     }
   }
-  const uint32_t S = c->n_servants;
+  const uint32_t S = c->reg.n;
   auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // Page-locked caller buffers (ydc_host_register / ydc_host_alloc) are used as they are: the
   // classification reads the request columns and k_finalize writes the results through their
@@ -3135,60 +2977,46 @@ int ydc_dispatch(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t fl
   const size_t col = pad((size_t)N * 4), in_bytes = 3 * col;
   const size_t o_run = pad((size_t)N * 4), o_util = o_run + pad((size_t)(out_running ? S : 0) * 4);
   const size_t res_bytes = o_util + (out_util ? (size_t)N * 8 : 0);
-  auto pinned = [&](uint8_t** q, size_t* cap, size_t want) -> hipError_t {
-    if (want <= *cap) return hipSuccess;
-    if (*q) (void)hipHostFree(*q);
-    *q = nullptr;
-    *cap = 0;
-    want = std::max<size_t>(want + want / 2, 4096);
-    hipError_t e = hipHostMalloc((void**)q, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
+  // (the staging arenas grow by half as much again as is asked for)
+  auto arena = [](PinnedBuf& b, size_t want) {
+    return want <= b.cap ? hipSuccess : b.reserve(std::max<size_t>(want + want / 2, 4096), hipHostMallocDefault);
   };
   // Request columns: read in place (in_pinned), or staged through the context's own pinned arena
   // (pageable caller memory).
   ydc_task_soa d{};
-  c->host_in.active = false;
+  BatchCall call = batch_call(c, flags, m_idx, out_util ? m_util : nullptr, out_running && S ? m_run : nullptr,
+                              c->h_prm.dev());
   if (in_pinned) {
     d = ydc_task_soa{m_in[0], m_in[1], m_in[2]};
   } else if (N) {
-    HIP_TRY(c, pinned(&c->h_in, &c->h_in_cap, in_bytes));
+    HIP_TRY(c, arena(c->h_in, in_bytes));
     HIP_TRY(c, c->d_in.reserve(std::max<size_t>(in_bytes, 256)));
-    if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    if (!c->copy_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->copy_ev, hipEventDisableTiming));
+    HIP_TRY(c, c->copy_stream.create());
+    HIP_TRY(c, c->copy_ev.create(hipEventDisableTiming));
     // The columns are staged and copied inside the batch, behind the launches that do not need
     // them (enqueue_front / stage_host_requests).
-    c->host_in.active = true;
-    c->host_in.tk = tk;
-    c->host_in.n = N;
-    c->host_in.col = col;
-    c->host_in.bytes = in_bytes;
+    call.host_in.tk = tk;
+    call.host_in.n = N;
+    call.host_in.col = col;
+    call.host_in.bytes = in_bytes;
     d = ydc_task_soa{(const uint32_t*)c->d_in.p, (const uint32_t*)(c->d_in.p + col),
                      (const uint32_t*)(c->d_in.p + 2 * col)};
   }
-  int rc;
-  if (out_pinned) {
-    c->post_copy.bytes = 0;
-    rc = ydc_dispatch_device(c, &d, N, flags, m_idx, out_util ? m_util : nullptr,
-                             out_running && S ? m_run : nullptr);
-    c->host_in.active = false;
-    return rc;  // ydc_dispatch_device has waited for the stream: the results are in the caller's buffers
-  }
-  HIP_TRY(c, pinned(&c->h_res, &c->h_res_cap, res_bytes));
+  // (dispatch_batch waits for the stream: the results are in the caller's buffers)
+  if (out_pinned) return dispatch_batch(c, &d, N, call);
+  HIP_TRY(c, arena(c->h_res, res_bytes));
   HIP_TRY(c, c->d_res.reserve(std::max<size_t>(res_bytes, 256)));
-  c->post_copy.dst = c->h_res;
-  c->post_copy.src = c->d_res.p;
-  c->post_copy.bytes = res_bytes;
-  rc = ydc_dispatch_device(c, &d, N, flags, (uint32_t*)c->d_res.p,
-                           out_util ? (double*)(c->d_res.p + o_util) : nullptr,
-                           out_running && S ? (uint32_t*)(c->d_res.p + o_run) : nullptr);
-  c->post_copy.bytes = 0;
-  c->host_in.active = false;
-  if (rc) return rc;
-  // ydc_dispatch_device has waited for the stream: the results are in the pinned arena.
-  if (N) std::memcpy(out_idx, c->h_res, (size_t)N * 4);
-  if (out_running && S) std::memcpy(out_running, c->h_res + o_run, (size_t)S * 4);
-  if (out_util && N) std::memcpy(out_util, c->h_res + o_util, (size_t)N * 8);
+  call.out_idx = (uint32_t*)c->d_res.p;
+  call.out_util = out_util ? (double*)(c->d_res.p + o_util) : nullptr;
+  call.out_running = out_running && S ? (uint32_t*)(c->d_res.p + o_run) : nullptr;
+  call.post_copy.dst = c->h_res.p;
+  call.post_copy.src = c->d_res.p;
+  call.post_copy.bytes = res_bytes;
+  if (int rc = dispatch_batch(c, &d, N, call)) return rc;
+  // ... or in the pinned arena.
+  if (N) std::memcpy(out_idx, c->h_res.p, (size_t)N * 4);
+  if (out_running && S) std::memcpy(out_running, c->h_res.p + o_run, (size_t)S * 4);
+  if (out_util && N) std::memcpy(out_util, c->h_res.p + o_util, (size_t)N * 8);
   return YDC_OK;
 }
 
@@ -3208,10 +3036,10 @@ int ydc_dispatch_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant
   // does not take (a large batch, a registry beyond its limits). So do mask words beyond the
   // table's width and rows without masks on a table of several words (ydc_update_servants_wide
   // refuses those: let it say so).
-  const bool wider = upd_env_masks ? env_words > c->env_words : c->env_words > 1;
+  const bool wider = upd_env_masks ? env_words > c->reg.env_words : c->reg.env_words > 1;
   bool structural = false;
   for (uint32_t i = 0; i < n_upd && !structural; ++i)
-    structural = wider || row_is_structural(c, upd_idx[i], upd_rows[i], upd_env_masks, env_words, i);
+    structural = wider || c->reg.structural(upd_idx[i], upd_rows[i], upd_env_masks, env_words, i);
   if (!structural && c->tables_dirty)
     if (int rc = rebuild_tables(c)) return rc;
   // (registry deltas ride in the launch only with COMMIT: running_tasks goes back once, into the
@@ -3232,7 +3060,8 @@ int ydc_dispatch_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant
       return ydc_dispatch(c, tasks, n_tasks, flags, out_servant_idx, out_utilization, nullptr);
     }
   }
-  mirror_rows(c, upd_idx, upd_rows, n_upd);
+  // (the host mirror of the columns such rows replace)
+  for (uint32_t i = 0; i < n_upd; ++i) c->reg.store_light(upd_idx[i], upd_rows[i]);
   TickCall io;
   io.tasks = tasks;
   io.n_tasks = n_tasks;
@@ -3476,10 +3305,7 @@ void group_release(ydc_context* c) {
   g.d_all_util.release();
   g.d_send.release();
   g.d_bounds.release();
-  if (g.h_bounds) (void)hipHostFree(g.h_bounds);
-  g.h_bounds = nullptr;
-  g.h_bounds_cap = 0;
-  g.n_ranks = 0;
+  g.n_ranks = 0;  // (h_bounds stays for the next group, or goes with the context)
 }
 
 // librccl must sit on the SAME HIP runtime as this library: a process may hold two
@@ -3858,12 +3684,7 @@ int ydc_dispatch_sharded(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uin
   HIP_TRY(c, g.d_bounds.reserve(rec * G));
   HIP_TRY(c, g.d_delta.reserve(S));
   HIP_TRY(c, g.d_deltas.reserve((size_t)S * G));
-  if (g.h_bounds_cap < rec * G) {
-    if (g.h_bounds) (void)hipHostFree(g.h_bounds);
-    g.h_bounds = nullptr;
-    HIP_TRY(c, hipHostMalloc((void**)&g.h_bounds, rec * G * sizeof(ClassState)));
-    g.h_bounds_cap = rec * G;
-  }
+  HIP_TRY(c, g.h_bounds.reserve(rec * G * sizeof(ClassState), hipHostMallocDefault));
   hipStream_t st = c->stream;
   DeviceParams* prm = c->d_prm.p;
 
@@ -3994,9 +3815,11 @@ int ydc_dispatch_sharded(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uin
       // on every rank): placement of this rank's slice, then the global running_tasks from
       // everybody's slot deltas. Not converged yet (or a window missed): the deltas are zero
       // and nothing changes.
-      if (int rc = enqueue_finalize(c, p, 0u, d_out_idx, d_out_util, nullptr, (launched - 1) & 63,
-                                    g.d_delta.p, p.mb.boundary_in))
-        return rc;
+      // (no COMMIT and no running_tasks from the finalise: k_sum_deltas does both, below)
+      BatchCall slice;
+      slice.out_idx = d_out_idx;
+      slice.out_util = d_out_util;
+      if (int rc = enqueue_finalize(c, p, slice, (launched - 1) & 63, g.d_delta.p, p.mb.boundary_in)) return rc;
       if (S) {
         if (int rc = group_all_gather(c, g.d_delta.p, g.d_deltas.p, (size_t)S * 4)) return rc;
         hipLaunchKernelGGL(k_sum_deltas, dim3(ceil_div(S, 256)), dim3(256), 0, st, c->d_running.p,
@@ -4123,7 +3946,7 @@ void enqueue_apply_tick(ydc_context* c, const TickArena& a) {
   const uint32_t upd_blocks = ceil_div(sm.caps.max_updates, 256);
   hipLaunchKernelGGL(k_apply_tick, dim3(upd_blocks + ceil_div(sm.caps.max_releases, 256)), dim3(256), 0, c->stream,
                      a.upd_idx, (ServantRowDev*)a.upd_rows, sm.caps.max_updates, upd_blocks, a.rel, sm.caps.max_releases,
-                     c->n_servants, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p, c->d_flags.p,
+                     c->reg.n, c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p, c->d_flags.p,
                      c->d_running.p);
 }
 
@@ -4175,7 +3998,7 @@ void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
   const ydc_stream_caps& k = sm.caps;
   const LeaseIn in = lease_in(a);
-  const uint32_t S = c->n_servants;
+  const uint32_t S = c->reg.n;
   const uint32_t ren_blocks = ceil_div(k.max_renewals, 256), rep_blocks = ceil_div(k.max_reports, 256);
   // With aliveness: the heartbeats' expiries into E (servant_alive.h). Here for the reason the book's
   // pass is here: once per tick on every path.
@@ -4206,7 +4029,7 @@ void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
 // placed batch's columns as the pass indexes them.
 InspectIn inspect_in(ydc_context* c, const uint32_t* env, const uint32_t* ip) {
   auto& sm = c->stream_mode;
-  return InspectIn{sm.d_insp_rec.p, sm.d_insp_pre.p, sm.inspect.ever.p, std::min(sm.inspect.n, c->n_servants),
+  return InspectIn{sm.d_insp_rec.p, sm.d_insp_pre.p, sm.inspect.ever.p, std::min(sm.inspect.n, c->reg.n),
                    env,             ip,              sm.rp.n_imm,      sm.rpc() ? sm.caps.max_waiting + sm.caps.max_tasks : 0};
 }
 
@@ -4291,19 +4114,18 @@ int stream_enqueue_step(ydc_context* c, const BatchPlan& plan, bool by_swap) {
   if (waiting) enqueue_stream_gather(c, sm.z);
   ydc_task_soa d{sm.z.env, sm.z.minv, sm.z.ip};
   if (waiting) d = ydc_task_soa{sm.wt.env, sm.wt.minv, sm.wt.ip};
-  if (rc == YDC_OK) rc = enqueue_front(c, plan, &d);
+  // (the captured step decides the finalise for itself: by_swap is the capture's, the outcome block the context's)
+  const bool outcome_stored = c->opt_outcome_store && plan.S != 0;
+  BatchCall call;
+  call.flags = YDC_DISPATCH_COMMIT;
+  call.out_idx = waiting ? sm.wt_out : leased ? sm.lt_out : sm.z_out;
+  call.outcome = outcome_stored ? c->h_prm.dev() : nullptr;
+  call.by_swap = by_swap;
+  if (rc == YDC_OK) rc = enqueue_front(c, plan, &d, call);
   if (rc == YDC_OK && plan.wave_path)
     for (uint32_t r = 0; r < sm.passes; ++r) enqueue_pass(c, plan, r, 1u);
-  const bool outcome_stored = c->opt_outcome_store && plan.S != 0;
   const uint32_t check_slot = plan.wave_path ? (sm.passes - 1) & 63 : kNone;
-  if (rc == YDC_OK) {
-    c->finalize_outcome = outcome_stored ? c->d_h_prm : nullptr;
-    c->commit_by_swap = by_swap;
-    rc = enqueue_finalize(c, plan, YDC_DISPATCH_COMMIT, waiting ? sm.wt_out : leased ? sm.lt_out : sm.z_out,
-                          nullptr, nullptr, check_slot);
-    c->commit_by_swap = false;
-    c->finalize_outcome = nullptr;
-  }
+  if (rc == YDC_OK) rc = enqueue_finalize(c, plan, call, check_slot);
   if (rc == YDC_OK) enqueue_stream_answer(c, sm.z, c->d_prm.p, check_slot);
   if (!outcome_stored) cap(hipMemcpyAsync(c->h_prm, c->d_prm.p, sizeof(DeviceParams), hipMemcpyDeviceToHost, st));
   return rc;
@@ -4333,10 +4155,10 @@ int stream_capture(ydc_context* c) {
   const bool was_profiling = c->profiling;
   c->profiling = false;  // no event pairs inside a capture
   // Sizes and workspace first (allocations and table uploads cannot be captured).
-  if (sm.leased() && sm.d_rep_tick.cap < c->n_servants) {
+  if (sm.leased() && sm.d_rep_tick.cap < c->reg.n) {
     // (a tick number is never 0, and a servant's stamp matters within its tick only)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, sm.d_rep_tick.reserve((size_t)c->n_servants + 1024));
+    HIP_TRY(c, sm.d_rep_tick.reserve((size_t)c->reg.n + 1024));
     HIP_TRY(c, hipMemset(sm.d_rep_tick.p, 0, sm.d_rep_tick.cap * 4));
   }
   if (int rc = plan_batch(c, stream_batch_n(sm), &sm.plan)) return rc;
@@ -4886,7 +4708,7 @@ int fit_rows(ydc_context* c, DevBuf<T>& col, uint32_t have, uint32_t want, T fil
 int inspect_fit(ydc_context* c, int64_t when) {
   auto& sm = c->stream_mode;
   auto& in = sm.inspect;
-  const uint32_t S = c->n_servants;
+  const uint32_t S = c->reg.n;
   if (S < in.n) in.n = S;
   if (S == in.n) return YDC_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -4901,7 +4723,7 @@ int inspect_fit(ydc_context* c, int64_t when) {
 int alive_fit(ydc_context* c) {
   auto& sm = c->stream_mode;
   auto& al = sm.alive;
-  const uint32_t S = c->n_servants;
+  const uint32_t S = c->reg.n;
   if (S < al.n) al.n = S;
   if (S == al.n) return YDC_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -5045,8 +4867,8 @@ int ydc_stream_alive_begin(ydc_context* c, const int64_t* expires_at, uint32_t n
   auto& sm = c->stream_mode;
   if (!sm.active || !sm.leased())
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_begin: no leased, waiting-and-leased or rpc stream is open");
-  if (n != c->n_servants)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_begin: %u expiries for %u servants", n, c->n_servants);
+  if (n != c->reg.n)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_alive_begin: %u expiries for %u servants", n, c->reg.n);
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -5123,8 +4945,8 @@ int ydc_stream_inspect_begin(ydc_context* c, const int64_t* discovered_at, const
   auto& sm = c->stream_mode;
   if (!sm.active || !sm.leased())
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_begin: no leased, waiting-and-leased or rpc stream is open");
-  if (n != c->n_servants)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_begin: %u rows for %u servants", n, c->n_servants);
+  if (n != c->reg.n)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_begin: %u rows for %u servants", n, c->reg.n);
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -5326,7 +5148,7 @@ int ydc_stream_outlook_get(ydc_context* c, const uint32_t* env_id, const uint32_
   auto& sm = c->stream_mode;
   if (c->tables_dirty)
     if (int rc = rebuild_tables(c)) return rc;  // (what the next tick would do first)
-  const uint32_t S = c->n_servants, C = c->tables.n_classes(), EW = c->env_words, bins = 64 * EW + 1;
+  const uint32_t S = c->reg.n, C = c->tables.n_classes(), EW = c->reg.env_words, bins = 64 * EW + 1;
   const bool with_w = sm.waiting(), with_l = sm.leased() && sm.inspect.on;
   const size_t n_agg = (size_t)std::max(C, 1u) * kOutlookCols, n_res = (size_t)n * kOutlookCols;
   HIP_TRY(c, sm.outlook.agg.reserve(n_agg));
@@ -5684,7 +5506,7 @@ static int stream_tick_check(ydc_context* c, const StreamCall& t, TickState* ts)
       if (n_ids && (!lt->rep_id || !lt->out_unknown)) return YDC_ERR_INVALID_ARGUMENT;
       ts->n_ids = n_ids;
       // A servant reports at most once per tick (a servant this tick's heartbeats add may report too).
-      uint32_t S = c->n_servants;
+      uint32_t S = c->reg.n;
       for (uint32_t i = 0; i < n_upd; ++i) S = std::max(S, t.upd_idx[i] + 1);
       sm.rep_once.begin(S);
       for (uint32_t r = 0; r < lt->n_rep; ++r) {
@@ -5709,7 +5531,7 @@ static int stream_tick_check(ydc_context* c, const StreamCall& t, TickState* ts)
     if (sm.alive.staged ? sm.alive.stage.size() != n_upd : n_upd != 0)
       return fail(c, YDC_ERR_INVALID_ARGUMENT, "%u heartbeats, %zu expiries staged with ydc_stream_alive_stage", n_upd,
                   sm.alive.staged ? sm.alive.stage.size() : (size_t)0);
-    const uint64_t S = (uint64_t)c->n_servants + n_upd;  // (the tick's heartbeats may add that many rows)
+    const uint64_t S = (uint64_t)c->reg.n + n_upd;  // (the tick's heartbeats may add that many rows)
     sm.alive.once.begin(S);
     for (uint32_t i = 0; i < n_upd; ++i) {
       const uint32_t s = t.upd_idx[i];
@@ -5723,24 +5545,24 @@ static int stream_tick_check(ydc_context* c, const StreamCall& t, TickState* ts)
   // Without masks (the plain form), rows of a table with several mask words cannot say what the
   // servant advertises: a known servant keeps its environments, and a NEW one (which would
   // silently have none) is refused.
-  if (!t.upd_env_masks && c->env_words > 1)
+  if (!t.upd_env_masks && c->reg.env_words > 1)
     for (uint32_t i = 0; i < n_upd; ++i)
-      if (t.upd_idx[i] >= c->n_servants)
+      if (t.upd_idx[i] >= c->reg.n)
         return fail(c, YDC_ERR_INVALID_ARGUMENT, "a tick that adds a servant to a table with %u mask "
-                    "words needs its environments: use ydc_stream_tick_wide", c->env_words);
+                    "words needs its environments: use ydc_stream_tick_wide", c->reg.env_words);
   return YDC_OK;
 }
 
 // All of a tick's heartbeats applied to the registry now, the way a structural one has to go.
 static int stream_heartbeats_eager(ydc_context* c, const StreamCall& t) {
-  const uint32_t EW = c->env_words, n_upd = t.n_upd;
+  const uint32_t EW = c->reg.env_words, n_upd = t.n_upd;
   if (t.upd_env_masks) return ydc_update_servants_wide(c, t.upd_idx, t.upd_rows, t.upd_env_masks, t.env_words, n_upd);
   if (EW == 1) return ydc_update_servants(c, t.upd_idx, t.upd_rows, n_upd);
   // Rows without masks on a wide table: the (known) servants keep their environments.
   std::vector<uint64_t> env((size_t)n_upd * EW, 0);
   for (uint32_t i = 0; i < n_upd; ++i)
-    if (t.upd_idx[i] < c->n_servants)  // (new servants were refused by the check)
-      std::copy_n(&c->h_env[(size_t)t.upd_idx[i] * EW], EW, &env[(size_t)i * EW]);
+    if (t.upd_idx[i] < c->reg.n)  // (new servants were refused by the check)
+      std::copy_n(&c->reg.env[(size_t)t.upd_idx[i] * EW], EW, &env[(size_t)i * EW]);
   return ydc_update_servants_wide(c, t.upd_idx, t.upd_rows, env.data(), EW, n_upd);
 }
 
@@ -5750,13 +5572,13 @@ static int stream_heartbeats_eager(ydc_context* c, const StreamCall& t) {
 static int stream_tick_heartbeats(ydc_context* c, const StreamCall& t, TickState* ts) {
   auto& sm = c->stream_mode;
   for (uint32_t i = 0; i < t.n_upd && !ts->structural; ++i)
-    ts->structural = row_is_structural(c, t.upd_idx[i], t.upd_rows[i], t.upd_env_masks, t.env_words, i);
+    ts->structural = c->reg.structural(t.upd_idx[i], t.upd_rows[i], t.upd_env_masks, t.env_words, i);
   ts->graph_upd = t.n_upd;
   if (ts->structural) {
     if (int rc = stream_heartbeats_eager(c, t)) return rc;
     ts->graph_upd = 0;
   } else {
-    mirror_rows(c, t.upd_idx, t.upd_rows, t.n_upd);
+    for (uint32_t i = 0; i < t.n_upd; ++i) c->reg.store_light(t.upd_idx[i], t.upd_rows[i]);
   }
   // Inspection (stream_inspect.h): a servant this tick's heartbeats appended was discovered now.
   if (sm.inspect.on)
@@ -5886,6 +5708,8 @@ static int stream_tick_run(ydc_context* c, const StreamCall& t, TickState* ts) {
                                     : ydc_task_soa{sm.d.env, sm.d.minv, sm.d.ip};
   uint32_t* const batch_out = wt ? sm.wt_out : lt ? sm.lt_out : c->d_out_idx.p;
   const uint32_t NB = stream_batch_n(sm);
+  // (whatever of the tick is placed eagerly: COMMIT by copy, the stream being open)
+  const BatchCall eager = batch_call(c, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, c->h_prm.dev());
   ts->plan = &ts->eager;
   if (sm.eager_only) {
     // The same step, enqueued instead of replayed: mirror the arena, apply, gather, place, answer.
@@ -5895,7 +5719,7 @@ static int stream_tick_run(ydc_context* c, const StreamCall& t, TickState* ts) {
     if (lt) enqueue_lease_pre(c, sm.d);
     enqueue_apply_tick(c, sm.d);
     if (wt) enqueue_stream_gather(c, sm.d);
-    if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &ts->eager, &ts->rounds))
+    if (int rc = place_batch(c, NB, &batch_dev, eager, &ts->eager, &ts->rounds))
       return rc;
     return stream_answer_eager(c, sm.d);
   }
@@ -5931,7 +5755,7 @@ static int stream_tick_run(ydc_context* c, const StreamCall& t, TickState* ts) {
     // gathered batch in HBM is what is placed again, and W is still as the gather read it)
     HIP_TRY(c, hipMemcpyAsync(sm.d_in.p, sm.h_in.p, sm.in_bytes, hipMemcpyHostToDevice, c->stream));
     ts->rounds = rounds;
-    if (int rc = place_batch(c, NB, &batch_dev, YDC_DISPATCH_COMMIT, batch_out, nullptr, nullptr, &ts->eager, &ts->rounds))
+    if (int rc = place_batch(c, NB, &batch_dev, eager, &ts->eager, &ts->rounds))
       return rc;
     return stream_answer_eager(c, sm.d);
   }
@@ -5939,9 +5763,7 @@ static int stream_tick_run(ydc_context* c, const StreamCall& t, TickState* ts) {
     if (c->h_prm->n_changed[(sm.passes - 1) & 63] != 0) {
       // The captured passes were not enough (rare): finish eagerly and capture a longer
       // step next time.
-      if (int rc = run_passes_until_consistent(c, p, sm.passes, YDC_DISPATCH_COMMIT, batch_out,
-                                               nullptr, nullptr, &rounds))
-        return rc;
+      if (int rc = run_passes_until_consistent(c, p, sm.passes, eager, &rounds)) return rc;
       if (int rc = stream_answer_eager(c, sm.z)) return rc;
       c->round_hint = rounds;
       sm.want_passes = std::min(rounds + 1, 12u);
@@ -6160,9 +5982,9 @@ void snap_describe(const ydc_context* c, snap::Header* h) {
   h->version = snap::kVersion;
   h->mode = (sm.waiting() ? snap::kModeWaiting : 0) | (sm.leased() ? snap::kModeLeased : 0) |
             (sm.rpc() ? snap::kModeRpc : 0) | (sm.max_book ? snap::kModeBook : 0) | (sm.alive.on ? snap::kModeAlive : 0);
-  h->env_words = c->env_words;
-  h->n_servants = c->n_servants;
-  h->n_alias = (uint32_t)c->h_alias_ip.size();
+  h->env_words = c->reg.env_words;
+  h->n_servants = c->reg.n;
+  h->n_alias = (uint32_t)c->reg.alias_ip.size();
   for (int i = 0; i < snap::kCaps; ++i) h->caps[i] = sm.caps.*kCapFields[i];
   h->max_book = sm.max_book;
   h->n_leases = sm.leased() ? sm.n_leases : 0;
@@ -6204,19 +6026,17 @@ int stream_snapshot(ydc_context* c, uint8_t* out, const snap::Header& h0) {
   // last) and for running_tasks. ip_id and the environment masks change on the structural path only,
   // which writes the host's copy first; per servant, the device holds neither.
   if (n) {
-    std::memcpy(at(v.env_mask), c->h_env.data(), (size_t)n * h.env_words * 8);
-    std::memcpy(at(v.ip), c->h_ip.data(), (size_t)n * 4);
-    const std::pair<const uint8_t*, const uint32_t*> cols[] = {
-        {v.version, c->d_version.p}, {v.nproc, c->d_nproc.p}, {v.load, c->d_load.p},
-        {v.max_tasks, c->d_max_tasks.p}, {v.flags, c->d_flags.p}, {v.running, c->d_running.p}};
-    for (auto& col : cols) HIP_TRY(c, hipMemcpyAsync(at(col.first), col.second, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    std::memcpy(at(v.env_mask), c->reg.env.data(), (size_t)n * h.env_words * 8);
+    std::memcpy(at(v.ip), c->reg.ip.data(), (size_t)n * 4);
+    for (auto& col : kRegCols)
+      HIP_TRY(c, hipMemcpyAsync(at(v.*col.snap), (c->*col.dev).p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     // (rows behind the column's end have not reported yet: 0, which no tick number is)
     const uint32_t have = (uint32_t)std::min<size_t>(n, sm.d_rep_tick.cap);
     if (have) HIP_TRY(c, hipMemcpyAsync(at(v.rep_tick), sm.d_rep_tick.p, (size_t)have * 4, hipMemcpyDeviceToHost, st));
   }
   if (h.n_alias) {
-    std::memcpy(at(v.alias_ip), c->h_alias_ip.data(), (size_t)h.n_alias * 4);
-    std::memcpy(at(v.alias_servant), c->h_alias_servant.data(), (size_t)h.n_alias * 4);
+    std::memcpy(at(v.alias_ip), c->reg.alias_ip.data(), (size_t)h.n_alias * 4);
+    std::memcpy(at(v.alias_servant), c->reg.alias_servant.data(), (size_t)h.n_alias * 4);
   }
   // W, B, E: compact between ticks, [0, n) of every column as it lies.
   if (sm.waiting()) {
