@@ -158,8 +158,11 @@ def test_ticks_with_heartbeats_and_releases(n_servants, n_envs, big, resident, p
     then another version or environment set, which changes structure and takes the general path),
     released grants, a handful of requests — COMMITted; the oracle replays every turn on its own
     snapshot. Delta lists beyond what travels as kernel arguments (16 rows, 64 releases) included.
-    resident = 1: the kernel of a turn stays on its CU and takes the following turns from its
-    mailbox (until a turn it does not take — a structural heartbeat, a long list — ends it);
+    resident = 1: the kernel of a turn stays on its CU, but the get_running() that closes every
+    turn here ends it (ydc_get_running stops the resident kernel first), so every turn is a launch
+    whose command arrives as kernel arguments — what this adds over resident = 0 is the stop and
+    the relaunch on columns the kernel before wrote back. Turns that do come from the mailbox, with
+    deltas: tests/test_tick_merge_gpu.py.
     resident = 0: every turn is a launch."""
     monkeypatch.setenv("YDC_RESIDENT", resident)
     monkeypatch.setenv("YDC_PACKED_TICK", packed)

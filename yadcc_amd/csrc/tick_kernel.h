@@ -55,7 +55,7 @@ constexpr uint32_t kTickMaxServants = 16384;  // 512 threads x 32 servants in re
 constexpr uint32_t kTickMaxClasses = 4096;    // eligible-class mask of a request: 64 words of LDS
 constexpr uint64_t kTickNoKey = ~0ull;
 // Which builds of k_tick carry the merge of identical requests (its lists: 32 bytes of LDS per
-// thread, a dozen registers): the 256-thread ones and, with one-word candidates, 512 x 16.
+// thread, a dozen registers): the 256-thread ones and 512 threads with one-word candidates.
 __host__ __device__ constexpr bool tick_merges(int threads, int k, bool packed) {
   return threads <= 256 || (threads == 512 && packed);
 }

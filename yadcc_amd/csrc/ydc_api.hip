@@ -2671,13 +2671,11 @@ int tick_run(ydc_context* c, const TickCall& io) {
     c->ksamples_used = 0;
     for (int s = 0; s <= 6; ++s) mark(c, s);
   }
-  // As few waves as hold the registry in registers, at most 16 servants per thread
-  // (tick_kernel.h): 256 threads up to 4096 servants, 512 beyond (32 per thread above 8192).
+  // As few waves as hold the registry in registers (tick_kernel.h): 256 threads with up to 16
+  // servants each up to 4096 servants, 512 threads above 4096 (32 per thread above 8192).
   const uint32_t per_thread = std::max(1u, ceil_div(S, 256u));
-  // As few waves as hold the registry in registers, at most 16 servants per thread
-  // (tick_kernel.h): 256 threads up to 4096 servants, 512 beyond (32 per thread above 8192).
-  // LDS: the eligible-class mask, the candidate lists of the merge (256-thread kernels, 32 B per
-  // thread), the servants' hosts and classes (6 B per servant slot).
+  // LDS: the eligible-class mask, the candidate lists of the merge (the builds tick_merges names,
+  // 32 B per thread), the servants' hosts and classes (6 B per servant slot).
   auto launch = [&](auto kernel, uint32_t threads, uint32_t k, bool pk) -> int {
     const size_t lds = (size_t)W * 8 + (tick_merges((int)threads, (int)k, pk) ? (size_t)32 * threads : 0) +
                        (size_t)6 * threads * k;
