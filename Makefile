@@ -26,7 +26,7 @@ oracle:
 model:
 	$(MAKE) -s -C tests/model
 # Native (C++) drive of the dispatcher through the scheduler harness; plain g++, links libydc.so.
-native: tests/native/harness_test tests/native/td_linearize_gpu tools/td_native_bench tools/hbm_calib tests/tools/launch_probe tests/tools/overlap_probe tests/tools/atomic_probe
+native: tests/native/harness_test tests/native/td_linearize_gpu tools/td_native_bench tools/hbm_calib tests/tools/launch_probe tests/tools/overlap_probe tests/tools/atomic_probe tests/native/key_forms_gpu
 	$(MAKE) -s -C tests/native all
 # Counter calibration microbenchmark (tools/calibrate.sh runs it under rocprofv3 on the GPU box).
 tools/hbm_calib: tools/hbm_calib.hip
@@ -38,6 +38,9 @@ tests/tools/overlap_probe: tests/tools/overlap_probe.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -o $@ tests/tools/overlap_probe.hip
 tests/tools/atomic_probe: tests/tools/atomic_probe.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -o $@ tests/tools/atomic_probe.hip
+# The closed forms of dispatch_core.h, one thread per case (tests/test_key_forms_gpu.py).
+tests/native/key_forms_gpu: tests/native/key_forms_gpu.hip tests/native/key_forms.h $(CSRC)/dispatch_core.h
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Wall -o $@ tests/native/key_forms_gpu.hip
 tools/td_native_bench: tools/td_native_bench.cc tools/parked_workload.h yadcc_amd/libydc.so $(HDRS)
 	g++ -O2 -std=c++17 -Wall -I$(CSRC) -Iinclude -Itools -o $@ tools/td_native_bench.cc \
 	    -Lyadcc_amd -lydc -Wl,-rpath,'$$ORIGIN/../yadcc_amd' -lpthread

@@ -621,3 +621,75 @@ extern "C" uint32_t model_check_first_slot(uint32_t seed, uint32_t iterations) {
   }
   return bad;
 }
+
+// The second closed-form check: cases made for the key (tests/key_edge_cases.py: servants of the
+// edge families, K = the key of an actual slot of the servant or of a partner, and that key +- 1).
+// Evaluates every case through tests/native/key_forms.h — what the device program runs — into
+// `out`, and checks first_slot_not_below, _direct, _direct32 (where it applies) and
+// servant_slots_before (exact and fp64 keys) against a walk over the servant's slots; servants
+// with more than 64 slots (constant capacity: strictly ascending keys) by bisection over the
+// same per-slot keys. Returns the mismatches; *n_direct32 = cases the 32-bit form was run on.
+#include "../native/key_forms.h"
+
+extern "C" uint32_t model_check_key_forms(const KeyFormCase* tab, uint32_t n, KeyFormOut* out,
+                                          uint32_t* n_direct32) {
+  uint32_t bad = 0, n32 = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const KeyFormCase& c = tab[i];
+    KeyFormOut& o = out[i];
+    key_forms_eval(c, o);
+    const uint32_t cnt = servant_slot_count(c.nproc, c.load, c.max_tasks, c.running, c.flags);
+    const uint32_t top = c.running + cnt;
+    auto key_at = [&](uint32_t r, bool exact) {
+      return slot_sort_key(c.nproc, c.load, c.max_tasks, c.flags, r, exact ? c.part_key : 0ull, exact, c.cap_bits);
+    };
+    uint32_t want[2];  // first r with key >= K: fp64 keys, exact keys
+    for (int exact = 0; exact < 2; ++exact) {
+      uint32_t r = c.running;
+      if (cnt <= 64) {
+        while (r < top && key_at(r, exact) < c.K) ++r;
+      } else {
+        uint32_t hi = top;
+        while (r < hi) {
+          const uint32_t mid = r + (hi - r) / 2;
+          if (key_at(mid, exact) < c.K) r = mid + 1; else hi = mid;
+        }
+      }
+      want[exact] = r;
+    }
+    bad += o.first != want[1];
+    bad += o.first_direct != want[1];
+    if (key_form_direct32_applies(c)) {
+      ++n32;
+      bad += o.first_direct32 != want[1];
+    }
+    for (int exact = 0; exact < 2; ++exact) {
+      const uint32_t r = want[exact];
+      const uint32_t before = r - c.running + (r < top && c.s < c.head_servant && key_at(r, exact) == c.K ? 1u : 0u);
+      bad += (exact ? o.before_exact : o.before_fp64) != before;
+    }
+  }
+  if (n_direct32) *n_direct32 = n32;
+  return bad;
+}
+
+// What the planner derives from a registry's key width, for tests that assert the device's stats
+// against it: out[0] = key_bits, out[1] = radix passes (choose_key_format with the kernels' digit
+// width, kernels.h: kMaxRadixBits == 11), out[2] = 1 when a record of the bin sort fits its LDS
+// word — key bits below the bin | slot | class — with at most 2048 bins (bin_sort.h: kMaxBins;
+// the loop of plan_batch in ydc_api.hip that halves the bins' width until the word fits).
+extern "C" void model_plan_formats(uint32_t cap_bits, uint32_t n_comp, uint64_t slot_bound, uint32_t n_classes,
+                                   uint32_t* out) {
+  const KeyFormat kf = choose_key_format(cap_bits, 11, &n_comp);
+  out[0] = kf.key_bits;
+  out[1] = kf.passes;
+  BinFormat bf = choose_bins(kf.key_bits, slot_bound, 2048);
+  uint32_t slot_bits = 1, cls_bits = 0;
+  while (slot_bits < 32 && (slot_bound >> slot_bits)) ++slot_bits;
+  while ((1u << cls_bits) < n_classes) ++cls_bits;
+  while (bf.shift + slot_bits + cls_bits > 32 && bf.n_bins < 2048 && bf.shift) {
+    bf.n_bins <<= 1;
+    --bf.shift;
+  }
+  out[2] = bf.shift + slot_bits + cls_bits <= 32 ? 1u : 0u;
+}
