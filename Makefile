@@ -57,11 +57,12 @@ tests/native/harness_test: tests/native/harness_test.cc tests/native/scheduler_h
 tests/native/td_linearize_gpu: tests/native/td_linearize.cc yadcc_amd/libydc.so include/yadcc_dispatch.h
 	g++ -O2 -std=c++17 -Wall -Iinclude -o $@ tests/native/td_linearize.cc \
 	    -Lyadcc_amd -lydc -Wl,-rpath,'$$ORIGIN/../../yadcc_amd' -lpthread
-# Sanitizer builds of the host class against the CPU stand-in of the device API (no GPU).
-tsan asan:
+# Sanitizer builds of the host class against the CPU stand-in of the device API, and of the
+# headers that are free of HIP (no GPU).
+tsan asan flatmap shardplan:
 	$(MAKE) -s -C tests/native $@
 clean:
 	rm -f yadcc_amd/libydc.so tests/model/libmodel.so
 	$(MAKE) -C tests/native clean
 	$(MAKE) -C oracle clean
-.PHONY: all lib probe oracle model native tsan asan clean
+.PHONY: all lib probe oracle model native tsan asan flatmap shardplan clean

@@ -7,8 +7,9 @@ segment when a rank cannot open a peer's IPC handle (every rank then switches al
 
 usage: python -m tests.mp_rank_worker <dir> <rank> <n_ranks> <spec.json>
 spec: {"case": {random_case kwargs} | "config": name, "cuts": [...], "batches": k, "commit": bool,
-       "transport": "ipc" | "ipc-host", "device": 0}
-Writes <dir>/result_<rank>.npz (idx, util, running of every batch, stats, transport)."""
+       "transport": "ipc" | "ipc-host", "device": 0, "regroup": bool}
+regroup: between batch 0 and batch 1 the rank leaves the group, exports again and joins anew.
+Writes <dir>/result_<rank>.npz (idx, util, running of every batch, stats, transport, transport_2)."""
 import json
 import os
 import sys
@@ -51,32 +52,50 @@ def main():
     ctx.upload_servants(pack.to_abi_columns(sv))
     want = {"ipc": binding.TRANSPORT_IPC_DEVICE, "ipc-host": binding.TRANSPORT_IPC_HOST}[
         spec.get("transport", "ipc")]
-    publish(os.path.join(d, "handle_%d" % rank), ctx.group_ipc_export(rank, G))
-    hpaths = [os.path.join(d, "handle_%d" % r) for r in range(G)]
-    wait_for(hpaths, 120, "handles")
-    handles = [open(p, "rb").read() for p in hpaths]
-    # Agree on the flavour: everybody tries the wanted one and says how it went; one failure
-    # anywhere sends everybody to the host segment.
-    note = ""
-    try:
-        ctx.group_init_ipc(handles, rank, G, want)
-        ok = True
-    except binding.YdcError as e:
-        ok, note = False, str(e)
-    publish(os.path.join(d, "try_%d" % rank), b"1" if ok else b"0")
-    tpaths = [os.path.join(d, "try_%d" % r) for r in range(G)]
-    wait_for(tpaths, 120, "first-attempt verdicts")
-    if not all(open(p, "rb").read() == b"1" for p in tpaths):
-        if want == binding.TRANSPORT_IPC_HOST:
-            raise RuntimeError("host mailbox transport failed: %s" % note)
-        ctx.group_init_ipc(handles, rank, G, binding.TRANSPORT_IPC_HOST)
-    transport = ctx.group_transport()
+    notes = []
+
+    def join(tag, flavour, fallback):
+        """Export, exchange the handles (files handle<tag>_<rank>), and agree on the flavour:
+        everybody tries the wanted one and says how it went; one failure anywhere sends everybody
+        to the fallback. Returns the group's transport."""
+        publish(os.path.join(d, "handle%s_%d" % (tag, rank)), ctx.group_ipc_export(rank, G))
+        hpaths = [os.path.join(d, "handle%s_%d" % (tag, r)) for r in range(G)]
+        wait_for(hpaths, 120, "handles")
+        handles = [open(p, "rb").read() for p in hpaths]
+        try:
+            ctx.group_init_ipc(handles, rank, G, flavour)
+            ok = True
+        except binding.YdcError as e:
+            ok = False
+            notes.append(str(e))
+        publish(os.path.join(d, "try%s_%d" % (tag, rank)), b"1" if ok else b"0")
+        tpaths = [os.path.join(d, "try%s_%d" % (tag, r)) for r in range(G)]
+        wait_for(tpaths, 120, "first-attempt verdicts")
+        if not all(open(p, "rb").read() == b"1" for p in tpaths):
+            if flavour == fallback:
+                raise RuntimeError("%s mailbox transport failed: %s" % (
+                    binding.TRANSPORT_NAMES[flavour], "; ".join(notes)))
+            ctx.group_init_ipc(handles, rank, G, fallback)
+        return ctx.group_transport()
+
+    transport = join("", want, binding.TRANSPORT_IPC_HOST)
+    transport_2 = binding.TRANSPORT_NONE
     cuts = spec["cuts"]
     nb = int(spec.get("batches", 1))
     n = len(tk["env_id"])
     per = n // nb
     out = {}
     for b in range(nb):
+        if b == 1 and spec.get("regroup"):
+            # Leave the group and make it again on the committed state: exported a second time, in
+            # the other flavour where every rank exported both, in the same one otherwise. (Nobody
+            # tears its mailbox down while a peer's batch 0 may still be reading it.)
+            publish(os.path.join(d, "batch0_%d" % rank), b"1")
+            wait_for([os.path.join(d, "batch0_%d" % r) for r in range(G)], 120, "batch 0 of the other ranks")
+            ctx.group_destroy()
+            other = (binding.TRANSPORT_IPC_HOST if transport == binding.TRANSPORT_IPC_DEVICE
+                     else binding.TRANSPORT_IPC_DEVICE)
+            transport_2 = join("b", other, transport)
         b0, b1 = b * per, (n if b == nb - 1 else (b + 1) * per)
         c = cuts[b] if isinstance(cuts[0], list) else cuts
         lo, hi = b0 + c[rank], b0 + c[rank + 1]
@@ -96,7 +115,8 @@ def main():
         out["stats_%d" % b] = np.array(json.dumps({k: v for k, v in st.items() if k != "stage_ms"}))
     out["resident_running"] = ctx.get_running()
     out["transport"] = np.int32(transport)
-    out["note"] = np.array(note)
+    out["transport_2"] = np.int32(transport_2)
+    out["note"] = np.array("; ".join(notes))
     tmp = os.path.join(d, "result_%d.tmp.npz" % rank)
     np.savez(tmp, **out)
     os.replace(tmp, os.path.join(d, "result_%d.npz" % rank))

@@ -106,6 +106,27 @@ def test_processes_empty_slice_commit_two_batches_late_rank():
         assert np.array_equal(r["run_1"], wrun) and np.array_equal(r["resident_running"], wrun)
 
 
+def test_processes_mailbox_exported_twice():
+    """2 processes, COMMIT: after batch 0 both leave the group, export their mailboxes a second
+    time and join again — in the other flavour where every rank exported both, in the first one
+    otherwise — and place batch 1 on the committed state. Both batches are the oracle's sequential
+    placement and every rank ends with the oracle's running_tasks."""
+    kw = dict(seed=83, n_tasks=6000, n_servants=200, n_envs=3, self_frac=0.1)
+    sv, tk = cases.random_case(**kw)
+    res = run_ranks(2, dict(case=kw, batches=2, commit=True, regroup=True,
+                            cuts=[[0, 1_000, 3_000], [0, 2_200, 3_000]]))
+    want, wutil, wrun = O.dispatch(sv, tk, "sorted")
+    got = np.concatenate([r["idx_0"] for r in res] + [r["idx_1"] for r in res])
+    assert np.array_equal(got, want)
+    mailbox = (binding.TRANSPORT_IPC_DEVICE, binding.TRANSPORT_IPC_HOST)
+    for r in res:
+        assert np.array_equal(r["run_1"], wrun) and np.array_equal(r["resident_running"], wrun)
+        assert int(r["transport"]) in mailbox and int(r["transport_2"]) in mailbox
+    assert len({(int(r["transport"]), int(r["transport_2"])) for r in res}) == 1  # the ranks agreed, twice
+    print("transports:", [binding.TRANSPORT_NAMES[int(res[0][k])] for k in ("transport", "transport_2")],
+          "notes:", [str(r["note"]) for r in res])
+
+
 def test_processes_shared_hosts_host_segment():
     """Hosts that run several servants (`self` resolved at replay time; full sort on every rank),
     over the shared-host-segment flavour of the transport."""

@@ -12,6 +12,7 @@
 #include <array>
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <cstdarg>
 #include <cstdio>
@@ -25,6 +26,7 @@
 #include "dispatch_core.h"
 #include "host_tables.h"
 #include "registry_mirror.h"
+#include "shard_plan.h"
 #include "kernels.h"
 #include "wait_queue.h"
 #include "lease_table.h"
@@ -269,49 +271,46 @@ struct ydc_context {
   uint64_t pipeline_misses = 0;
 
   // Multi-GPU group (ydc_group_*): this context is one rank of a sharded dispatcher.
-  struct LocalHub;  // single-process transport: several contexts on one device
+  // One way of exchanging between the ranks (an all-gather a handful of times per matching pass,
+  // a few hundred bytes to S*4 bytes per rank). Chosen once, when the group is made; whoever
+  // exchanges asks the record, nobody looks at what it is made of. Its destructor gives back
+  // everything the transport took. The implementations are with the ydc_group_* entry points.
+  struct Transport {
+    virtual ~Transport() = default;
+    virtual int kind() const = 0;  // YDC_TRANSPORT_*
+    // recv[r * bytes ..) = rank r's send[0, bytes), ordered behind c->stream.
+    virtual int gather(ydc_context* c, const void* send, void* recv, size_t bytes) = 0;
+    // Waits for the stream; an error where an exchange so far did not deliver every peer's data.
+    // Whoever turns gathered words into sizes or inputs on the host asks here first.
+    virtual int settled(ydc_context* c);
+    // The transport's own count of the ranks, where it keeps one (ydc_group_size).
+    virtual int count(ydc_context*, int*) { return YDC_OK; }
+  };
   struct Group {
     int rank = 0, n_ranks = 0;  // n_ranks == 0: not in a group
-    void* rccl = nullptr;       // dlopen handle
-    ncclComm_t comm = nullptr;
-    decltype(&ncclAllGather) all_gather_fn = nullptr;
-    decltype(&ncclCommDestroy) comm_destroy_fn = nullptr;
-    decltype(&ncclCommCount) comm_count_fn = nullptr;
-    decltype(&ncclGetErrorString) error_string_fn = nullptr;
-    LocalHub* hub = nullptr;
-    // Inter-process mailbox transport (ydc_group_ipc_export / ydc_group_init_ipc): this rank's
-    // mailbox in both flavours — device memory behind a HIP IPC handle, a shared host segment —
-    // and the peers' as mapped into this process (kernels.h: k_mailbox_all_gather).
-    struct Mailbox {
-      int kind = 0;  // 0: not in use; YDC_TRANSPORT_IPC_DEVICE / YDC_TRANSPORT_IPC_HOST once initialised
-      int exported_ranks = 0, exported_rank = -1;
-      void* own_dev = nullptr;        // device flavour
-      bool own_dev_fine = false;
-      bool have_handle = false;
-      hipIpcMemHandle_t handle{};
-      void* own_host = nullptr;       // host flavour (mmap of the shm segment, registered)
-      char shm_name[64] = {};
-      size_t bytes = 0;
-      uint32_t slot_words = 0;
-      MailboxPeers peers{};
-      void* opened_dev[kMailboxMaxRanks] = {};   // hipIpcOpenMemHandle results to close
-      void* opened_host[kMailboxMaxRanks] = {};  // peers' segments mapped here
-      uint32_t seq = 0;                           // exchanges so far (the stamp; never 0)
-      unsigned long long timeout_ticks = 30ull * 100000000ull;
-    } box;
-    DevBuf<uint32_t> d_totals, d_meta, d_base, d_delta, d_deltas;
-    // Sharded sort (k_window): key-count table, per-servant windows, local prefix, class lists
-    // of the whole registry, local -> registry-wide list position shifts, the ranks' windows.
-    DevBuf<uint32_t> d_cum, d_r_first, d_lbase, d_cls_begin_glob, d_shift, d_winrec, d_winall;
-    DevBuf<ClassState> d_bound_local;
-    uint32_t margin_scale = 1;  // doubled after a batch whose window missed
-    uint64_t windowed_batches = 0, window_misses = 0;
-    DevBuf<uint32_t> d_pad, d_gather, d_all[3], d_all_idx;  // replicated fallback (whole batch)
-    DevBuf<double> d_all_util;
-    DevBuf<ClassState> d_send, d_bounds;
+    // (between ydc_group_ipc_export and ydc_group_init_ipc: the mailbox with this rank's own
+    // blocks, and n_ranks == 0)
+    std::unique_ptr<Transport> via;
+    // Device buffers of the sharded batches. They live as long as the group: group_release
+    // replaces the record with a fresh one, so a buffer added here is given back with the rest.
+    struct Workspace {
+      DevBuf<uint32_t> d_totals, d_meta, d_base, d_delta, d_deltas;
+      DevBuf<ClassState> d_bound_local, d_send, d_bounds;
+      // Sharded sort (k_window): key-count table, per-servant windows, local prefix, class lists
+      // of the whole registry, local -> registry-wide list position shifts, the ranks' windows.
+      DevBuf<uint32_t> d_cum, d_r_first, d_lbase, d_cls_begin_glob, d_shift, d_winrec, d_winall;
+      DevBuf<uint32_t> d_pad, d_gather, d_all[3], d_all_idx;  // replicated fallback (whole batch)
+      DevBuf<double> d_all_util;
+    } ws;
+    // What follows outlives a group: it stays for the next one, or goes with the context.
     PinnedAs<ClassState> h_bounds;   // page-locked (debug_sim's look at the ranks' records)
+    uint32_t margin_scale = 1;       // doubled after a batch whose window missed
+    uint64_t windowed_batches = 0, window_misses = 0;  // ydc_get_stats: shard_sort_batches / _misses
     uint32_t passes = 0;             // of the last sharded batch
     uint32_t pass_hint = 3;          // passes to pre-launch before looking at the outcome
+    // Mailbox time-out (YDC_TUNE ipc_timeout_ms, read at every export; the slot size is read there
+    // too and is kept by the mailbox alone).
+    unsigned long long mailbox_timeout_ticks = 30ull * 100000000ull;
   } group;
 
   // Streaming mode (ydc_stream_*): one tick = row updates + slot releases + one
@@ -1688,8 +1687,8 @@ void enqueue_gen(ydc_context* c, const BatchPlan& p, const ydc_task_soa* tk, boo
   if (gen_blocks + cls_blocks == 0) return;
   const size_t lds0 = ((size_t)4 << bits0);
   // Key window (sharded sort): local prefix, first local slot and registry-wide names.
-  const uint32_t* base = p.win ? c->group.d_lbase.p : c->d_slot_base.p;
-  const uint32_t* r_first = p.win ? c->group.d_r_first.p : nullptr;
+  const uint32_t* base = p.win ? c->group.ws.d_lbase.p : c->d_slot_base.p;
+  const uint32_t* r_first = p.win ? c->group.ws.d_r_first.p : nullptr;
   const uint32_t* gbase = p.win ? c->d_slot_base.p : nullptr;
   uint16_t* cls_by_g = C > 1 && !p.gbits ? c->d_cls_by_g.p : nullptr;
   if (p.binsort && gen) {
@@ -3154,156 +3153,33 @@ int ydc_host_free(void* p) {
 // the per-servant slot deltas. Transport: RCCL (librccl.so.1, resolved with dlopen so
 // that a single-GPU scheduler has no RCCL dependency), or — for several contexts of one
 // process on one device, which is how the protocol is tested on a single-GPU box — a
-// barrier + device copies.
+// barrier + device copies; or, between processes, mailboxes in HIP IPC device memory or a
+// shared host segment.
+// On the host a group holds one Transport, chosen by the ydc_group_init* call that made it, and
+// one Workspace; ydc_dispatch_sharded carries a ShardCall through named stages — front, pass
+// group, tail, outcome — under a short loop that holds the retry policy; what the ranks have to
+// compute alike is in shard_plan.h. Every rank must take the same branches and issue the same
+// exchanges in the same order: a rank that did not would leave its peers waiting in-stream.
 // ---------------------------------------------------------------------------
-struct ydc_context::LocalHub {
-  int n = 0;
-  std::mutex mu;
-  std::condition_variable cv;
-  int arrived = 0;
-  uint64_t generation = 0;
-  std::vector<const void*> send;
-  int refs = 0;
-  void barrier() {
-    std::unique_lock<std::mutex> lk(mu);
-    const uint64_t gen = generation;
-    if (++arrived == n) {
-      arrived = 0;
-      ++generation;
-      cv.notify_all();
-    } else {
-      cv.wait(lk, [&] { return generation != gen; });
-    }
-  }
-};
-
-namespace {
-
-int group_all_gather(ydc_context* c, const void* send, void* recv, size_t bytes) {
-  auto& g = c->group;
-  if (g.n_ranks == 1 && !g.hub) {
-    // A group of one: the gather is a copy (the communicator / mailbox exists, nothing to wait for).
-    if (bytes) HIP_TRY(c, hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, c->stream));
-    return YDC_OK;
-  }
-  if (g.box.kind) {
-    if (bytes % 4) return fail(c, YDC_ERR_INVALID_ARGUMENT, "mailbox exchange of %zu bytes", bytes);
-    const uint32_t words = (uint32_t)(bytes / 4), G = (uint32_t)g.n_ranks;
-    for (uint32_t off = 0; off < words; off += g.box.slot_words) {
-      const uint32_t n = std::min(g.box.slot_words, words - off);
-      if (++g.box.seq == 0) ++g.box.seq;
-      const uint32_t bpp = std::min(16u, std::max(1u, ceil_div(n, 1024)));
-      YDC_LAUNCH(c, "k_mailbox_all_gather", k_mailbox_all_gather, dim3(G * bpp), dim3(256), 0, c->stream,
-                 g.box.peers, (uint32_t)g.rank, G, (const uint32_t*)send + off, (uint32_t*)recv + off, n,
-                 words, g.box.slot_words, g.box.seq & 1u, g.box.seq, bpp, g.box.timeout_ticks, c->d_prm.p);
-    }
-    return YDC_OK;
-  }
-  if (g.comm) {
-    ncclResult_t r = g.all_gather_fn(send, recv, bytes, ncclUint8, g.comm, c->stream);
-    if (r != ncclSuccess)
-      return fail(c, YDC_ERR_HIP, "ncclAllGather: %s", g.error_string_fn ? g.error_string_fn(r) : "?");
-    return YDC_OK;
-  }
-  if (g.hub) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the send buffer is complete
-    g.hub->send[g.rank] = send;
-    g.hub->barrier();
-    for (int r = 0; r < g.n_ranks; ++r)
-      HIP_TRY(c, hipMemcpyAsync((char*)recv + (size_t)r * bytes, g.hub->send[r], bytes,
-                                hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    g.hub->barrier();  // nobody rewrites its send buffer before everybody has read it
-    return YDC_OK;
-  }
-  return fail(c, YDC_ERR_INVALID_ARGUMENT, "context is not part of a group");
-}
-
-// The mailbox transport reports a late peer only through DeviceParams::exchange_timeout (the
-// words it waited for read as 0): whoever turns gathered words into sizes or inputs on the host
-// asks here first. Waits for the stream.
-int group_exchange_check(ydc_context* c) {
-  auto& g = c->group;
-  if (!g.box.kind) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return YDC_OK;
-  }
-  uint32_t late = 0;
-  HIP_TRY(c, hipMemcpyAsync(&late, &c->d_prm.p->exchange_timeout, 4, hipMemcpyDeviceToHost, c->stream));
+int ydc_context::Transport::settled(ydc_context* c) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (late)
-    return fail(c, YDC_ERR_HIP, "a peer's data did not arrive within the mailbox time-out (rank %d of %d)",
-                g.rank, g.n_ranks);
   return YDC_OK;
 }
 
-// What a rank hands its peers (ydc_group_ipc_export; YDC_IPC_HANDLE_BYTES).
-struct MailboxBlob {
-  uint32_t magic, abi;
-  int32_t rank, n_ranks;
-  uint32_t slot_words, have_device, have_host, device_fine;
-  int32_t device, pid;
-  uint64_t bytes, raw_dev, raw_host;  // raw_*: the owner's own pointers (peers inside the owner's process)
-  hipIpcMemHandle_t handle;
-  char shm_name[64];
-};
-static_assert(sizeof(MailboxBlob) <= YDC_IPC_HANDLE_BYTES, "blob must fit the published size");
-constexpr uint32_t kMailboxMagic = 0x79646362u;  // "ydcb"
+namespace {
 
-void mailbox_release(ydc_context* c) {
-  auto& b = c->group.box;
-  for (uint32_t q = 0; q < kMailboxMaxRanks; ++q) {
-    if (b.opened_dev[q]) (void)hipIpcCloseMemHandle(b.opened_dev[q]);
-    b.opened_dev[q] = nullptr;
-    if (b.opened_host[q]) {
-      (void)hipHostUnregister(b.opened_host[q]);
-      (void)munmap(b.opened_host[q], b.bytes);
-    }
-    b.opened_host[q] = nullptr;
-    b.peers.box[q] = nullptr;
-  }
-  if (b.own_dev) (void)hipFree(b.own_dev);
-  b.own_dev = nullptr;
-  b.have_handle = false;
-  if (b.own_host) {
-    (void)hipHostUnregister(b.own_host);
-    (void)munmap(b.own_host, b.bytes);
-    (void)shm_unlink(b.shm_name);
-  }
-  b.own_host = nullptr;
-  b.shm_name[0] = 0;
-  b.kind = 0;
-  b.exported_ranks = 0;
-  b.exported_rank = -1;
-  b.bytes = 0;
-  b.seq = 0;
+// A group of one exchanges with nobody: the gather is a copy (the communicator / mailbox exists,
+// is reported and is released like any other; there is nothing to wait for).
+int solo_gather(ydc_context* c, const void* send, void* recv, size_t bytes) {
+  if (bytes) HIP_TRY(c, hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, c->stream));
+  return YDC_OK;
 }
 
-void group_release(ydc_context* c) {
-  auto& g = c->group;
-  mailbox_release(c);
-  if (g.comm && g.comm_destroy_fn) (void)g.comm_destroy_fn(g.comm);
-  g.comm = nullptr;
-  if (g.rccl) (void)dlclose(g.rccl);
-  g.rccl = nullptr;
-  if (g.hub) {
-    bool last;
-    {
-      std::lock_guard<std::mutex> lk(g.hub->mu);
-      last = --g.hub->refs == 0;
-    }
-    if (last) delete g.hub;
-    g.hub = nullptr;
-  }
-  for (auto* b : {&g.d_totals, &g.d_meta, &g.d_base, &g.d_delta, &g.d_deltas, &g.d_pad, &g.d_gather,
-                  &g.d_all[0], &g.d_all[1], &g.d_all[2], &g.d_all_idx, &g.d_cum, &g.d_r_first,
-                  &g.d_lbase, &g.d_cls_begin_glob, &g.d_shift, &g.d_winrec, &g.d_winall})
-    b->release();
-  g.d_bound_local.release();
-  g.d_all_util.release();
-  g.d_send.release();
-  g.d_bounds.release();
-  g.n_ranks = 0;  // (h_bounds stays for the next group, or goes with the context)
+// The mailbox reports a late peer only through DeviceParams::exchange_timeout (the words it
+// waited for read as 0).
+int late_peer(ydc_context* c) {
+  return fail(c, YDC_ERR_HIP, "a peer's data did not arrive within the mailbox time-out (rank %d of %d)",
+              c->group.rank, c->group.n_ranks);
 }
 
 // librccl must sit on the SAME HIP runtime as this library: a process may hold two
@@ -3333,6 +3209,318 @@ void* open_rccl(std::string* err) {
   return nullptr;
 }
 
+// librccl as this library uses it: the handle and the entry points, resolved here and nowhere
+// else. An entry point the library lacks is NULL; who needs it says so.
+struct RcclApi {
+  void* lib = nullptr;
+  decltype(&ncclGetUniqueId) get_unique_id = nullptr;
+  decltype(&ncclCommInitRank) comm_init_rank = nullptr;
+  decltype(&ncclAllGather) all_gather = nullptr;
+  decltype(&ncclCommDestroy) comm_destroy = nullptr;
+  decltype(&ncclCommCount) comm_count = nullptr;
+  decltype(&ncclGetErrorString) error_string = nullptr;
+  bool open(std::string* err) {
+    lib = open_rccl(err);
+    if (!lib) return false;
+    get_unique_id = (decltype(get_unique_id))dlsym(lib, "ncclGetUniqueId");
+    comm_init_rank = (decltype(comm_init_rank))dlsym(lib, "ncclCommInitRank");
+    all_gather = (decltype(all_gather))dlsym(lib, "ncclAllGather");
+    comm_destroy = (decltype(comm_destroy))dlsym(lib, "ncclCommDestroy");
+    comm_count = (decltype(comm_count))dlsym(lib, "ncclCommCount");
+    error_string = (decltype(error_string))dlsym(lib, "ncclGetErrorString");
+    return true;
+  }
+  const char* text(ncclResult_t r) const { return error_string ? error_string(r) : "?"; }
+};
+
+// RCCL: owns the dlopen handle and the communicator.
+struct RcclTransport final : ydc_context::Transport {
+  RcclApi api;
+  ncclComm_t comm = nullptr;
+  bool solo = false;  // a communicator of one rank
+  ~RcclTransport() override {
+    if (comm) (void)api.comm_destroy(comm);
+    if (api.lib) (void)dlclose(api.lib);
+  }
+  int kind() const override { return YDC_TRANSPORT_RCCL; }
+  int gather(ydc_context* c, const void* send, void* recv, size_t bytes) override {
+    if (solo) return solo_gather(c, send, recv, bytes);
+    ncclResult_t r = api.all_gather(send, recv, bytes, ncclUint8, comm, c->stream);
+    if (r != ncclSuccess) return fail(c, YDC_ERR_HIP, "ncclAllGather: %s", api.text(r));
+    return YDC_OK;
+  }
+  // Ask the communicator itself (ncclCommCount), not our own bookkeeping.
+  int count(ydc_context* c, int* out) override {
+    if (!api.comm_count) return YDC_OK;
+    int n = 0;
+    if (api.comm_count(comm, &n) != ncclSuccess) return fail(c, YDC_ERR_HIP, "ncclCommCount failed");
+    *out = n;
+    return YDC_OK;
+  }
+};
+
+// Several contexts of one process on one device — how the protocol is tested on a single-GPU
+// box: a barrier + device copies. Every rank holds a reference on the hub; the last one out
+// deletes it.
+struct LocalHub {
+  int n = 0;
+  std::mutex mu;
+  std::condition_variable cv;
+  int arrived = 0;
+  uint64_t generation = 0;
+  std::vector<const void*> send;
+  void barrier() {
+    std::unique_lock<std::mutex> lk(mu);
+    const uint64_t gen = generation;
+    if (++arrived == n) {
+      arrived = 0;
+      ++generation;
+      cv.notify_all();
+    } else {
+      cv.wait(lk, [&] { return generation != gen; });
+    }
+  }
+};
+struct LocalHubTransport final : ydc_context::Transport {
+  std::shared_ptr<LocalHub> hub;
+  int rank = 0;
+  int kind() const override { return YDC_TRANSPORT_LOCAL; }
+  int gather(ydc_context* c, const void* send, void* recv, size_t bytes) override {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the send buffer is complete
+    hub->send[rank] = send;
+    hub->barrier();
+    for (int r = 0; r < hub->n; ++r)
+      HIP_TRY(c, hipMemcpyAsync((char*)recv + (size_t)r * bytes, hub->send[r], bytes, hipMemcpyDeviceToDevice,
+                                c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    hub->barrier();  // nobody rewrites its send buffer before everybody has read it
+    return YDC_OK;
+  }
+};
+
+// What a rank hands its peers (ydc_group_ipc_export; YDC_IPC_HANDLE_BYTES).
+struct MailboxBlob {
+  uint32_t magic, abi;
+  int32_t rank, n_ranks;
+  uint32_t slot_words, have_device, have_host, device_fine;
+  int32_t device, pid;
+  uint64_t bytes, raw_dev, raw_host;  // raw_*: the owner's own pointers (peers inside the owner's process)
+  hipIpcMemHandle_t handle;
+  char shm_name[64];
+};
+static_assert(sizeof(MailboxBlob) <= YDC_IPC_HANDLE_BYTES, "blob must fit the published size");
+constexpr uint32_t kMailboxMagic = 0x79646362u;  // "ydcb"
+
+// Own the pieces of a mailbox the way DevBuf owns an allocation. This rank's device block:
+// fine-grained device memory where the runtime exports it (peer writes have to be visible to a
+// kernel that is running — across devices that takes fine-grained memory), plain device memory
+// otherwise (enough between processes that share one device). Zeroed. Without a handle the block
+// serves peers inside this process only.
+struct MailboxDevBlock {
+  void* p = nullptr;
+  bool fine = false, have_handle = false;
+  hipIpcMemHandle_t handle{};
+  MailboxDevBlock() = default;
+  MailboxDevBlock(const MailboxDevBlock&) = delete;
+  MailboxDevBlock& operator=(const MailboxDevBlock&) = delete;
+  ~MailboxDevBlock() {
+    if (p) (void)hipFree(p);
+  }
+  // p stays NULL where the device gives neither kind; an error only from zeroing what it gave.
+  hipError_t create(size_t bytes, bool coarse_only) {
+    if (!coarse_only) {
+      if (hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained) == hipSuccess) {
+        if (hipIpcGetMemHandle(&handle, p) == hipSuccess) {
+          have_handle = fine = true;
+        } else {
+          (void)hipFree(p);
+          p = nullptr;
+        }
+      }
+      (void)hipGetLastError();
+    }
+    if (!p) {
+      if (hipMalloc(&p, bytes) == hipSuccess) have_handle = hipIpcGetMemHandle(&handle, p) == hipSuccess;
+      else p = nullptr;
+      (void)hipGetLastError();
+    }
+    return p ? hipMemset(p, 0, bytes) : hipSuccess;
+  }
+};
+// This rank's host segment: a POSIX shared-memory segment, page-locked and mapped into the
+// device's address space by every process that opens it. Zeroed; unlinked with its owner.
+struct MailboxHostSegment {
+  void* p = nullptr;
+  size_t bytes = 0;
+  char name[64] = {};
+  MailboxHostSegment() = default;
+  MailboxHostSegment(const MailboxHostSegment&) = delete;
+  MailboxHostSegment& operator=(const MailboxHostSegment&) = delete;
+  ~MailboxHostSegment() {
+    if (!p) return;
+    (void)hipHostUnregister(p);
+    (void)munmap(p, bytes);
+    (void)shm_unlink(name);
+  }
+  // Named after the process and the context. p stays NULL where the segment cannot be had.
+  void create(const void* owner, size_t n) {
+    snprintf(name, sizeof(name), "/ydc_box_%d_%llx", (int)getpid(), (unsigned long long)(uintptr_t)owner & 0xFFFFFFFFFFull);
+    (void)shm_unlink(name);
+    int fd = shm_open(name, O_CREAT | O_EXCL | O_RDWR, 0600);
+    if (fd < 0) return;
+    void* m = MAP_FAILED;
+    if (ftruncate(fd, (off_t)n) == 0) m = mmap(nullptr, n, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+    (void)close(fd);
+    if (m != MAP_FAILED) {
+      std::memset(m, 0, n);
+      if (hipHostRegister(m, n, hipHostRegisterMapped | hipHostRegisterPortable) == hipSuccess) {
+        p = m;
+        bytes = n;
+      } else {
+        (void)hipGetLastError();
+        (void)munmap(m, n);
+      }
+    }
+    if (!p) (void)shm_unlink(name);
+  }
+};
+// A peer's mailbox as opened in this process: its device block through the HIP IPC handle, or its
+// host segment mapped and page-locked here. (Neither for this rank itself and for a peer inside
+// this process, which are reached through their owner's pointers.)
+struct MailboxPeerMap {
+  void* dev = nullptr;
+  void* host = nullptr;
+  size_t bytes = 0;
+  MailboxPeerMap() = default;
+  MailboxPeerMap(const MailboxPeerMap&) = delete;
+  MailboxPeerMap& operator=(const MailboxPeerMap&) = delete;
+  ~MailboxPeerMap() { close(); }
+  void close() {
+    if (dev) (void)hipIpcCloseMemHandle(dev);
+    dev = nullptr;
+    if (host) {
+      (void)hipHostUnregister(host);
+      (void)munmap(host, bytes);
+    }
+    host = nullptr;
+  }
+};
+
+// Inter-process mailbox (kernels.h: k_mailbox_all_gather): this rank's mailbox in both flavours
+// and the peers' as mapped into this process. Two phases: ydc_group_ipc_export makes it with the
+// rank's own blocks (flavour 0, the context is not in a group yet); ydc_group_init_ipc maps the
+// peers' in one flavour — and once more in the other where a rank could not open a peer's handle.
+struct MailboxTransport final : ydc_context::Transport {
+  int flavour = 0;  // 0: exported only; YDC_TRANSPORT_IPC_DEVICE / YDC_TRANSPORT_IPC_HOST once initialised
+  int rank = -1, n_ranks = 0;  // as exported
+  size_t bytes = 0;            // two sets of n_ranks slots of 8-byte granules
+  uint32_t slot_words = 0;     // payload words of a slot (YDC_TUNE ipc_slot_words, read at every export)
+  uint32_t seq = 0;            // exchanges so far (the stamp; never 0)
+  MailboxHostSegment own_host;
+  MailboxDevBlock own_dev;
+  MailboxPeers peers{};
+  MailboxPeerMap opened[kMailboxMaxRanks];
+  ~MailboxTransport() override { close_peers(); }  // (then the own blocks, device first)
+
+  void close_peers() {
+    for (uint32_t q = 0; q < kMailboxMaxRanks; ++q) {
+      opened[q].close();
+      peers.box[q] = nullptr;
+    }
+    flavour = 0;
+    seq = 0;
+  }
+  // Rank q's mailbox of the given flavour, from the blob it exported, into peers.box[q].
+  int open_peer(ydc_context* c, const MailboxBlob& pb, int q, bool host) {
+    const bool same_process = pb.pid == (int32_t)getpid();
+    void* dev_ptr = nullptr;
+    if (!host) {
+      if (!pb.have_device) return fail(c, YDC_ERR_HIP, "rank %d exported no device mailbox", q);
+      if (q == rank) {
+        dev_ptr = own_dev.p;
+      } else if (same_process) {
+        dev_ptr = (void*)(uintptr_t)pb.raw_dev;  // a peer inside this process: its own pointer
+      } else {
+        hipError_t e = hipIpcOpenMemHandle(&dev_ptr, pb.handle, hipIpcMemLazyEnablePeerAccess);
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          return fail(c, YDC_ERR_HIP, "hipIpcOpenMemHandle(rank %d): %s", q, hipGetErrorString(e));
+        }
+        opened[q].dev = dev_ptr;
+      }
+    } else {
+      if (!pb.have_host) return fail(c, YDC_ERR_HIP, "rank %d exported no host mailbox", q);
+      void* m = nullptr;
+      if (q == rank) {
+        m = own_host.p;
+      } else if (same_process) {
+        m = (void*)(uintptr_t)pb.raw_host;
+      } else {
+        int fd = shm_open(pb.shm_name, O_RDWR, 0600);
+        if (fd < 0) return fail(c, YDC_ERR_HIP, "shm_open(%s) of rank %d failed", pb.shm_name, q);
+        m = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+        (void)close(fd);
+        if (m == MAP_FAILED) return fail(c, YDC_ERR_HIP, "mmap of rank %d's mailbox failed", q);
+        hipError_t e = hipHostRegister(m, bytes, hipHostRegisterMapped | hipHostRegisterPortable);
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          (void)munmap(m, bytes);
+          return fail(c, YDC_ERR_HIP, "hipHostRegister of rank %d's mailbox: %s", q, hipGetErrorString(e));
+        }
+        opened[q].host = m;
+        opened[q].bytes = bytes;
+      }
+      HIP_TRY(c, hipHostGetDevicePointer(&dev_ptr, m, 0));
+    }
+    peers.box[q] = (unsigned long long*)dev_ptr;
+    return YDC_OK;
+  }
+
+  int kind() const override { return flavour; }
+  int gather(ydc_context* c, const void* send, void* recv, size_t nbytes) override {
+    if (n_ranks == 1) return solo_gather(c, send, recv, nbytes);
+    if (nbytes % 4) return fail(c, YDC_ERR_INVALID_ARGUMENT, "mailbox exchange of %zu bytes", nbytes);
+    const uint32_t words = (uint32_t)(nbytes / 4), G = (uint32_t)n_ranks;
+    for (uint32_t off = 0; off < words; off += slot_words) {
+      const uint32_t n = std::min(slot_words, words - off);
+      if (++seq == 0) ++seq;
+      const uint32_t bpp = std::min(16u, std::max(1u, ceil_div(n, 1024)));
+      YDC_LAUNCH(c, "k_mailbox_all_gather", k_mailbox_all_gather, dim3(G * bpp), dim3(256), 0, c->stream, peers,
+                 (uint32_t)rank, G, (const uint32_t*)send + off, (uint32_t*)recv + off, n, words, slot_words,
+                 seq & 1u, seq, bpp, c->group.mailbox_timeout_ticks, c->d_prm.p);
+    }
+    return YDC_OK;
+  }
+  int settled(ydc_context* c) override {
+    uint32_t late = 0;
+    HIP_TRY(c, hipMemcpyAsync(&late, &c->d_prm.p->exchange_timeout, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return late ? late_peer(c) : YDC_OK;
+  }
+};
+
+// Leaves the group: the transport gives back what it took, the workspace goes as a whole.
+void group_release(ydc_context* c) {
+  auto& g = c->group;
+  g.via.reset();
+  g.ws = ydc_context::Group::Workspace{};
+  g.n_ranks = 0;
+}
+
+// What every entry point of the group does first: the context's device, the resident kernel out
+// of the way (the registry leaves its registers), and — except for a batch, whose stream is in
+// order already — the stream drained and the present group left. ydc_group_init_ipc alone keeps
+// what is there: it completes the mailbox ydc_group_ipc_export made.
+enum class GroupKeep { kNothing, kExport, kGroup };
+int group_enter(ydc_context* c, GroupKeep keep) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);
+  if (keep == GroupKeep::kGroup) return YDC_OK;
+  if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (keep == GroupKeep::kNothing) group_release(c);
+  return YDC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3340,65 +3528,60 @@ extern "C" {
 int ydc_group_unique_id(void* out_id128) {
   if (!out_id128) return YDC_ERR_INVALID_ARGUMENT;
   static_assert(sizeof(ncclUniqueId) == 128, "ydc_group_unique_id hands out 128 bytes");
+  RcclApi api;  // the handle stays open: ydc_group_init reuses the loaded library
   std::string rccl_err;
-  void* h = open_rccl(&rccl_err);
-  if (!h) set_create_error(rccl_err);
-  if (!h) return YDC_ERR_HIP;
-  auto fn = (decltype(&ncclGetUniqueId))dlsym(h, "ncclGetUniqueId");
-  if (!fn) {
+  if (!api.open(&rccl_err)) {
+    set_create_error(rccl_err);
+    return YDC_ERR_HIP;
+  }
+  if (!api.get_unique_id) {
     set_create_error("librccl has no ncclGetUniqueId");
     return YDC_ERR_HIP;
   }
   ncclUniqueId id;
-  ncclResult_t r = fn(&id);
-  if (r != ncclSuccess) {
+  if (api.get_unique_id(&id) != ncclSuccess) {
     set_create_error("ncclGetUniqueId failed");
     return YDC_ERR_HIP;
   }
   std::memcpy(out_id128, &id, sizeof(id));
-  return YDC_OK;  // the handle stays open: ydc_group_init reuses the loaded library
+  return YDC_OK;
 }
 
 int ydc_group_init(ydc_context* c, const void* id128, int rank, int n_ranks) {
   if (!c || !id128 || n_ranks < 1 || rank < 0 || rank >= n_ranks) return YDC_ERR_INVALID_ARGUMENT;
-  HIP_TRY(c, hipSetDevice(c->device));
-  resident_stop(c);  // (the registry leaves the resident kernel's registers)
-  group_release(c);
-  auto& g = c->group;
+  if (int rc = group_enter(c, GroupKeep::kNothing)) return rc;
+  auto t = std::make_unique<RcclTransport>();
   std::string err;
-  g.rccl = open_rccl(&err);
-  if (!g.rccl) return fail(c, YDC_ERR_HIP, "%s", err.c_str());
-  auto init_fn = (decltype(&ncclCommInitRank))dlsym(g.rccl, "ncclCommInitRank");
-  g.all_gather_fn = (decltype(&ncclAllGather))dlsym(g.rccl, "ncclAllGather");
-  g.comm_destroy_fn = (decltype(&ncclCommDestroy))dlsym(g.rccl, "ncclCommDestroy");
-  g.error_string_fn = (decltype(&ncclGetErrorString))dlsym(g.rccl, "ncclGetErrorString");
-  g.comm_count_fn = (decltype(&ncclCommCount))dlsym(g.rccl, "ncclCommCount");
-  if (!init_fn || !g.all_gather_fn || !g.comm_destroy_fn)
+  if (!t->api.open(&err)) return fail(c, YDC_ERR_HIP, "%s", err.c_str());
+  if (!t->api.comm_init_rank || !t->api.all_gather || !t->api.comm_destroy)
     return fail(c, YDC_ERR_HIP, "librccl lacks ncclCommInitRank / ncclAllGather / ncclCommDestroy");
   ncclUniqueId id;
   std::memcpy(&id, id128, sizeof(id));
-  ncclResult_t r = init_fn(&g.comm, n_ranks, id, rank);
+  ncclResult_t r = t->api.comm_init_rank(&t->comm, n_ranks, id, rank);
   if (r != ncclSuccess) {
-    g.comm = nullptr;
-    return fail(c, YDC_ERR_HIP, "ncclCommInitRank(rank %d of %d): %s", rank, n_ranks,
-                g.error_string_fn ? g.error_string_fn(r) : "?");
+    t->comm = nullptr;
+    return fail(c, YDC_ERR_HIP, "ncclCommInitRank(rank %d of %d): %s", rank, n_ranks, t->api.text(r));
   }
-  g.rank = rank;
-  g.n_ranks = n_ranks;
+  t->solo = n_ranks == 1;
+  c->group.via = std::move(t);
+  c->group.rank = rank;
+  c->group.n_ranks = n_ranks;
   return YDC_OK;
 }
 
 int ydc_group_init_local(ydc_context** ctxs, int n) {
   if (!ctxs || n < 1) return YDC_ERR_INVALID_ARGUMENT;
-  auto* hub = new ydc_context::LocalHub();
+  for (int r = 0; r < n; ++r)
+    if (!ctxs[r]) return YDC_ERR_INVALID_ARGUMENT;
+  auto hub = std::make_shared<LocalHub>();
   hub->n = n;
   hub->send.assign(n, nullptr);
-  hub->refs = n;
   for (int r = 0; r < n; ++r) {
-    if (!ctxs[r]) return YDC_ERR_INVALID_ARGUMENT;
-    resident_stop(ctxs[r]);
-    group_release(ctxs[r]);
-    ctxs[r]->group.hub = hub;
+    if (int rc = group_enter(ctxs[r], GroupKeep::kNothing)) return rc;
+    auto t = std::make_unique<LocalHubTransport>();
+    t->hub = hub;
+    t->rank = r;
+    ctxs[r]->group.via = std::move(t);
     ctxs[r]->group.rank = r;
     ctxs[r]->group.n_ranks = n;
   }
@@ -3408,88 +3591,39 @@ int ydc_group_init_local(ydc_context** ctxs, int n) {
 int ydc_group_ipc_export(ydc_context* c, int rank, int n_ranks, void* out_handle) {
   if (!c || !out_handle || n_ranks < 1 || n_ranks > (int)kMailboxMaxRanks || rank < 0 || rank >= n_ranks)
     return YDC_ERR_INVALID_ARGUMENT;
-  HIP_TRY(c, hipSetDevice(c->device));
-  resident_stop(c);  // (the registry leaves the resident kernel's registers)
-  if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
-  group_release(c);
-  auto& b = c->group.box;
+  if (int rc = group_enter(c, GroupKeep::kNothing)) return rc;
+  auto box = std::make_unique<MailboxTransport>();
   // Slots of 64 KB of payload (a configs[3] registry's slot deltas: 16k servants x 4 B) unless
   // tuned; two sets of n_ranks slots of 8-byte granules.
-  uint32_t slot_words = 16384;
-  if (const char* e = tune_value("ipc_slot_words")) slot_words = (uint32_t)std::max(64, atoi(e));
+  box->slot_words = 16384;
+  if (const char* e = tune_value("ipc_slot_words")) box->slot_words = (uint32_t)std::max(64, atoi(e));
   if (const char* e = tune_value("ipc_timeout_ms"))
-    b.timeout_ticks = (unsigned long long)std::max(1, atoi(e)) * 100000ull;  // 100 MHz wall clock
-  b.slot_words = slot_words;
-  b.bytes = (size_t)2 * n_ranks * slot_words * 8;
+    c->group.mailbox_timeout_ticks = (unsigned long long)std::max(1, atoi(e)) * 100000ull;  // 100 MHz wall clock
+  box->bytes = (size_t)2 * n_ranks * box->slot_words * 8;
+  box->rank = rank;
+  box->n_ranks = n_ranks;
+  const char* coarse = tune_value("ipc_coarse");
+  HIP_TRY(c, box->own_dev.create(box->bytes, coarse && atoi(coarse)));
+  box->own_host.create(c, box->bytes);
   MailboxBlob blob{};
   blob.magic = kMailboxMagic;
   blob.abi = ydc_abi_version();
   blob.rank = rank;
   blob.n_ranks = n_ranks;
-  blob.slot_words = slot_words;
+  blob.slot_words = box->slot_words;
   blob.device = c->device;
   blob.pid = (int32_t)getpid();
-  blob.bytes = b.bytes;
-  // Device flavour: fine-grained device memory where the runtime exports it (peer writes have to
-  // be visible to a kernel that is running — across devices that takes fine-grained memory), plain
-  // device memory otherwise (enough between processes that share one device).
-  const char* coarse = tune_value("ipc_coarse");
-  if (!(coarse && atoi(coarse))) {
-    if (hipExtMallocWithFlags(&b.own_dev, b.bytes, hipDeviceMallocFinegrained) == hipSuccess) {
-      if (hipIpcGetMemHandle(&b.handle, b.own_dev) == hipSuccess) {
-        b.have_handle = true;
-        b.own_dev_fine = true;
-      } else {
-        (void)hipFree(b.own_dev);
-        b.own_dev = nullptr;
-      }
-    }
-    (void)hipGetLastError();
-  }
-  if (!b.own_dev) {
-    if (hipMalloc(&b.own_dev, b.bytes) == hipSuccess) {
-      b.have_handle = hipIpcGetMemHandle(&b.handle, b.own_dev) == hipSuccess;
-      b.own_dev_fine = false;
-    } else {
-      b.own_dev = nullptr;
-    }
-    (void)hipGetLastError();
-  }
-  if (b.own_dev) HIP_TRY(c, hipMemset(b.own_dev, 0, b.bytes));
-  blob.have_device = b.own_dev != nullptr;  // (without a handle: peers inside this process only)
-  blob.device_fine = b.own_dev_fine;
-  blob.raw_dev = (uint64_t)(uintptr_t)b.own_dev;
-  if (b.have_handle) blob.handle = b.handle;
-  // Host flavour: a POSIX shared-memory segment, page-locked and mapped into the device's
-  // address space by every process that opens it.
-  snprintf(b.shm_name, sizeof(b.shm_name), "/ydc_box_%d_%llx", (int)getpid(),
-           (unsigned long long)(uintptr_t)c & 0xFFFFFFFFFFull);
-  (void)shm_unlink(b.shm_name);
-  int fd = shm_open(b.shm_name, O_CREAT | O_EXCL | O_RDWR, 0600);
-  if (fd >= 0) {
-    void* m = MAP_FAILED;
-    if (ftruncate(fd, (off_t)b.bytes) == 0) m = mmap(nullptr, b.bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    (void)close(fd);
-    if (m != MAP_FAILED) {
-      std::memset(m, 0, b.bytes);
-      if (hipHostRegister(m, b.bytes, hipHostRegisterMapped | hipHostRegisterPortable) == hipSuccess) {
-        b.own_host = m;
-      } else {
-        (void)hipGetLastError();
-        (void)munmap(m, b.bytes);
-      }
-    }
-    if (!b.own_host) (void)shm_unlink(b.shm_name);
-  }
-  blob.have_host = b.own_host != nullptr;
-  blob.raw_host = (uint64_t)(uintptr_t)b.own_host;
-  std::memcpy(blob.shm_name, b.shm_name, sizeof(blob.shm_name));
-  if (!blob.have_device && !blob.have_host) {
-    mailbox_release(c);
+  blob.bytes = box->bytes;
+  blob.have_device = box->own_dev.p != nullptr;
+  blob.device_fine = box->own_dev.fine;
+  blob.raw_dev = (uint64_t)(uintptr_t)box->own_dev.p;
+  if (box->own_dev.have_handle) blob.handle = box->own_dev.handle;
+  blob.have_host = box->own_host.p != nullptr;
+  blob.raw_host = (uint64_t)(uintptr_t)box->own_host.p;
+  std::memcpy(blob.shm_name, box->own_host.name, sizeof(blob.shm_name));
+  if (!blob.have_device && !blob.have_host)
     return fail(c, YDC_ERR_HIP, "neither a device nor a host mailbox could be set up");
-  }
-  b.exported_ranks = n_ranks;
-  b.exported_rank = rank;
+  c->group.via = std::move(box);  // (n_ranks stays 0: not in a group before ydc_group_init_ipc)
   std::memset(out_handle, 0, YDC_IPC_HANDLE_BYTES);
   std::memcpy(out_handle, &blob, sizeof(blob));
   return YDC_OK;
@@ -3501,73 +3635,24 @@ int ydc_group_init_ipc(ydc_context* c, const void* handles, int rank, int n_rank
   if (transport != YDC_TRANSPORT_IPC_DEVICE && transport != YDC_TRANSPORT_IPC_HOST)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "transport %d is not a mailbox transport", transport);
   auto& g = c->group;
-  auto& b = g.box;
-  if (b.exported_ranks != n_ranks || b.exported_rank != rank)
+  auto* box = dynamic_cast<MailboxTransport*>(g.via.get());
+  if (!box || box->n_ranks != n_ranks || box->rank != rank)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_group_ipc_export(rank %d of %d) first", rank, n_ranks);
-  HIP_TRY(c, hipSetDevice(c->device));
-  resident_stop(c);  // (the registry leaves the resident kernel's registers)
-  const bool host = transport == YDC_TRANSPORT_IPC_HOST;
-  // (a second attempt with the other flavour: drop what the first one mapped)
-  for (uint32_t q = 0; q < kMailboxMaxRanks; ++q) {
-    if (b.opened_dev[q]) (void)hipIpcCloseMemHandle(b.opened_dev[q]);
-    b.opened_dev[q] = nullptr;
-    if (b.opened_host[q]) {
-      (void)hipHostUnregister(b.opened_host[q]);
-      (void)munmap(b.opened_host[q], b.bytes);
-    }
-    b.opened_host[q] = nullptr;
-    b.peers.box[q] = nullptr;
-  }
-  b.kind = 0;
+  if (int rc = group_enter(c, GroupKeep::kExport)) return rc;
+  // (a second attempt with the other flavour: drop what the first one mapped; not in a group
+  // until every peer is)
+  g.n_ranks = 0;
+  box->close_peers();
   for (int q = 0; q < n_ranks; ++q) {
     MailboxBlob pb;
     std::memcpy(&pb, (const char*)handles + (size_t)q * YDC_IPC_HANDLE_BYTES, sizeof(pb));
-    if (pb.magic != kMailboxMagic || pb.rank != q || pb.n_ranks != n_ranks || pb.slot_words != b.slot_words ||
-        pb.bytes != b.bytes)
-      return fail(c, YDC_ERR_INVALID_ARGUMENT, "handle %d does not describe rank %d of %d with %u-word slots",
-                  q, q, n_ranks, b.slot_words);
-    void* dev_ptr = nullptr;
-    if (!host) {
-      if (!pb.have_device) return fail(c, YDC_ERR_HIP, "rank %d exported no device mailbox", q);
-      if (q == rank) {
-        dev_ptr = b.own_dev;
-      } else if (pb.pid == (int32_t)getpid()) {
-        dev_ptr = (void*)(uintptr_t)pb.raw_dev;  // a peer inside this process: its own pointer
-      } else {
-        hipError_t e = hipIpcOpenMemHandle(&dev_ptr, pb.handle, hipIpcMemLazyEnablePeerAccess);
-        if (e != hipSuccess) {
-          (void)hipGetLastError();
-          return fail(c, YDC_ERR_HIP, "hipIpcOpenMemHandle(rank %d): %s", q, hipGetErrorString(e));
-        }
-        b.opened_dev[q] = dev_ptr;
-      }
-    } else {
-      if (!pb.have_host) return fail(c, YDC_ERR_HIP, "rank %d exported no host mailbox", q);
-      void* m = nullptr;
-      if (q == rank) {
-        m = b.own_host;
-      } else if (pb.pid == (int32_t)getpid()) {
-        m = (void*)(uintptr_t)pb.raw_host;
-      } else {
-        int fd = shm_open(pb.shm_name, O_RDWR, 0600);
-        if (fd < 0) return fail(c, YDC_ERR_HIP, "shm_open(%s) of rank %d failed", pb.shm_name, q);
-        m = mmap(nullptr, b.bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-        (void)close(fd);
-        if (m == MAP_FAILED) return fail(c, YDC_ERR_HIP, "mmap of rank %d's mailbox failed", q);
-        hipError_t e = hipHostRegister(m, b.bytes, hipHostRegisterMapped | hipHostRegisterPortable);
-        if (e != hipSuccess) {
-          (void)hipGetLastError();
-          (void)munmap(m, b.bytes);
-          return fail(c, YDC_ERR_HIP, "hipHostRegister of rank %d's mailbox: %s", q, hipGetErrorString(e));
-        }
-        b.opened_host[q] = m;
-      }
-      HIP_TRY(c, hipHostGetDevicePointer(&dev_ptr, m, 0));
-    }
-    b.peers.box[q] = (unsigned long long*)dev_ptr;
+    if (pb.magic != kMailboxMagic || pb.rank != q || pb.n_ranks != n_ranks || pb.slot_words != box->slot_words ||
+        pb.bytes != box->bytes)
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "handle %d does not describe rank %d of %d with %u-word slots", q,
+                  q, n_ranks, box->slot_words);
+    if (int rc = box->open_peer(c, pb, q, transport == YDC_TRANSPORT_IPC_HOST)) return rc;
   }
-  b.kind = transport;
-  b.seq = 0;
+  box->flavour = transport;
   g.rank = rank;
   g.n_ranks = n_ranks;
   return YDC_OK;
@@ -3575,117 +3660,343 @@ int ydc_group_init_ipc(ydc_context* c, const void* handles, int rank, int n_rank
 
 int ydc_group_transport(ydc_context* c) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
-  auto& g = c->group;
-  if (g.n_ranks < 1) return YDC_TRANSPORT_NONE;
-  if (g.comm) return YDC_TRANSPORT_RCCL;
-  if (g.hub) return YDC_TRANSPORT_LOCAL;
-  return g.box.kind ? g.box.kind : YDC_TRANSPORT_NONE;
+  return c->group.n_ranks < 1 ? YDC_TRANSPORT_NONE : c->group.via->kind();
 }
 
 int ydc_group_size(ydc_context* c, int* out_ranks, int* out_is_rccl) {
   if (!c || !out_ranks) return YDC_ERR_INVALID_ARGUMENT;
   auto& g = c->group;
   *out_ranks = g.n_ranks;
-  if (out_is_rccl) *out_is_rccl = g.comm ? 1 : 0;
-  if (g.comm && g.comm_count_fn) {
-    // Ask the communicator itself (ncclCommCount), not our own bookkeeping.
-    int n = 0;
-    ncclResult_t r = g.comm_count_fn(g.comm, &n);
-    if (r != ncclSuccess) return fail(c, YDC_ERR_HIP, "ncclCommCount failed");
-    *out_ranks = n;
-  }
-  return YDC_OK;
+  if (out_is_rccl) *out_is_rccl = g.n_ranks >= 1 && g.via->kind() == YDC_TRANSPORT_RCCL;
+  return g.n_ranks >= 1 ? g.via->count(c, out_ranks) : YDC_OK;
 }
 
 int ydc_group_destroy(ydc_context* c) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  group_release(c);
+  if (group_enter(c, GroupKeep::kNothing)) group_release(c);  // (whatever the device says, the group goes)
   return YDC_OK;
 }
+
+}  // extern "C"
+
+namespace {
+
+// One ydc_dispatch_sharded call: this rank's slice and where its results go (device addresses).
+struct ShardCall {
+  const ydc_task_soa* tk = nullptr;
+  uint32_t N = 0, flags = 0;
+  uint32_t* out_idx = nullptr;
+  double* out_util = nullptr;
+  uint32_t* out_running = nullptr;
+};
+
+// One attempt at the batch: the plan it runs with and how far it has got. The sizes are those
+// of the registry and the group, the same on every rank.
+struct ShardAttempt {
+  uint32_t G = 0, C = 0, S = 0, K = 0;
+  uint32_t P = 0;   // counts are exchanged per independent part of the registry
+  uint32_t MS = 0;  // words of a rank's k_rank_meta record
+  size_t rec = 0;   // ClassStates a rank publishes per pass
+  BatchPlan p;
+  bool windowed = false;
+  uint32_t launched = 0;  // matching passes enqueued so far
+};
+
+// What the host finds behind a group of passes and its tail.
+struct ShardOutcome {
+  enum What { kSettled, kGoOn, kMissed, kFailed } what = kFailed;
+  uint32_t rounds = 0;  // kSettled: passes up to the first in which no rank changed anything
+  int rc = YDC_OK;      // kFailed
+};
+
+// Registries the sharded matching does not take (> 256 classes: thread-per-chunk path): every
+// rank gathers the whole batch, places it redundantly with the single-GPU pipeline — identical
+// on all ranks — and keeps its own slice of the placement.
+int sharded_replicated(ydc_context* c, const ShardCall& call) {
+  auto& g = c->group;
+  auto& w = g.ws;
+  const uint32_t G = (uint32_t)g.n_ranks, N = call.N;
+  HIP_TRY(c, w.d_totals.reserve(G + 1));
+  HIP_TRY(c, hipMemcpyAsync(w.d_totals.p + G, &N, 4, hipMemcpyHostToDevice, c->stream));
+  if (int rc = g.via->gather(c, w.d_totals.p + G, w.d_totals.p, 4)) return rc;
+  std::vector<uint32_t> sizes(G);
+  HIP_TRY(c, hipMemcpyAsync(sizes.data(), w.d_totals.p, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
+  if (int rc = g.via->settled(c)) return rc;  // (a late peer's size would read as 0)
+  const ShardSlices sl = shard_slices(sizes.data(), G, (uint32_t)g.rank);
+  HIP_TRY(c, w.d_pad.reserve(sl.max_n));
+  HIP_TRY(c, w.d_gather.reserve((size_t)sl.max_n * G));
+  for (auto& col : w.d_all) HIP_TRY(c, col.reserve(sl.total));
+  HIP_TRY(c, w.d_all_idx.reserve(sl.total));
+  if (call.out_util) HIP_TRY(c, w.d_all_util.reserve(sl.total));
+  const uint32_t* cols[3] = {N ? call.tk->env_id : nullptr, N ? call.tk->min_version : nullptr,
+                             N ? call.tk->requestor_ip : nullptr};
+  for (int k = 0; k < 3; ++k) {
+    if (N) HIP_TRY(c, hipMemcpyAsync(w.d_pad.p, cols[k], (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (int rc = g.via->gather(c, w.d_pad.p, w.d_gather.p, (size_t)sl.max_n * 4)) return rc;
+    uint32_t off = 0;
+    for (uint32_t r = 0; r < G; ++r) {
+      if (sizes[r])
+        HIP_TRY(c, hipMemcpyAsync(w.d_all[k].p + off, w.d_gather.p + (size_t)r * sl.max_n, (size_t)sizes[r] * 4,
+                                  hipMemcpyDeviceToDevice, c->stream));
+      off += sizes[r];
+    }
+  }
+  // (... and a late peer's columns as zeros: nothing is placed, let alone committed, on them)
+  if (int rc = g.via->settled(c)) return rc;
+  ydc_task_soa all{w.d_all[0].p, w.d_all[1].p, w.d_all[2].p};
+  if (int rc = ydc_dispatch_device(c, &all, sl.total, call.flags, w.d_all_idx.p,
+                                   call.out_util ? w.d_all_util.p : nullptr, call.out_running))
+    return rc;
+  if (N && call.out_idx)
+    HIP_TRY(c, hipMemcpyAsync(call.out_idx, w.d_all_idx.p + sl.my_off, (size_t)N * 4, hipMemcpyDeviceToDevice,
+                              c->stream));
+  if (N && call.out_util)
+    HIP_TRY(c, hipMemcpyAsync(call.out_util, w.d_all_util.p + sl.my_off, (size_t)N * 8, hipMemcpyDeviceToDevice,
+                              c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // Stats describe the whole batch in this mode; report this rank's share of the grants.
+  c->stats.n_tasks = N;
+  g.passes = c->stats.rounds;
+  return YDC_OK;
+}
+
+// The sizes of the batch and the workspace every attempt uses.
+int shard_prepare(ydc_context* c, const BatchPlan& full_plan, ShardAttempt* a) {
+  auto& g = c->group;
+  auto& w = g.ws;
+  a->G = (uint32_t)g.n_ranks, a->C = full_plan.C, a->S = full_plan.S, a->K = full_plan.K;
+  a->rec = (size_t)a->C + 1;
+  a->P = c->n_parts;
+  a->MS = a->P + 1;
+  HIP_TRY(c, w.d_totals.reserve((size_t)a->G * a->MS));
+  HIP_TRY(c, w.d_meta.reserve(a->MS));
+  HIP_TRY(c, w.d_bound_local.reserve(a->C ? a->C : 1));
+  HIP_TRY(c, w.d_base.reserve(a->P));
+  HIP_TRY(c, w.d_send.reserve(a->rec));
+  HIP_TRY(c, w.d_bounds.reserve(a->rec * a->G));
+  HIP_TRY(c, w.d_delta.reserve(a->S));
+  HIP_TRY(c, w.d_deltas.reserve((size_t)a->S * a->G));
+  HIP_TRY(c, g.h_bounds.reserve(a->rec * a->G * sizeof(ClassState), hipHostMallocDefault));
+  return YDC_OK;
+}
+
+// The plan of one attempt, from the full or the window plan: this rank's place in the group
+// and, for a window, its size (shard_plan.h) and its buffers.
+int shard_plan_attempt(ydc_context* c, const ShardCall& call, const BatchPlan& plan, ShardAttempt* a) {
+  auto& g = c->group;
+  auto& w = g.ws;
+  BatchPlan& p = a->p;
+  p = plan;
+  a->launched = 0;
+  p.mb.has_successor = g.rank + 1 < g.n_ranks ? 1u : 0u;
+  p.zone = false;  // (the walk of the tier's end is a single-context thing: zone_guess.h)
+  p.mb.zone_box = nullptr;
+  if (a->windowed) {
+    const ShardWindow win = shard_window(call.N, g.margin_scale, c->opt_shard_margin, plan.slot_bound, kSortThreads);
+    p.win = true;
+    p.win_margin = win.win_margin;
+    p.slot_bound = win.slot_bound;
+    p.sort_items = win.sort_items;
+    p.n_tiles = win.n_tiles;
+    if (p.mb.tile_tab) {  // (the window's own tiles: ranks are registry-wide, rank_offset apart)
+      p.mb.tile_tab_tiles = p.n_tiles;
+      p.mb.tile_tab_elems = kSortThreads * p.sort_items;
+    }
+    HIP_TRY(c, w.d_cum.reserve(kWindowThresholds + 1));
+    HIP_TRY(c, w.d_r_first.reserve(a->S));
+    HIP_TRY(c, w.d_lbase.reserve((size_t)a->S + 1));
+    HIP_TRY(c, w.d_cls_begin_glob.reserve((size_t)a->C + 1));
+    HIP_TRY(c, w.d_shift.reserve(a->C));
+    HIP_TRY(c, w.d_winrec.reserve((size_t)2 * a->C));
+    HIP_TRY(c, w.d_winall.reserve((size_t)2 * a->C * a->G));
+    ++g.windowed_batches;
+  }
+  // The chunks of this rank continue those of the nearest rank below that has requests
+  // (k_global_flag / k_boundary_in copy its end state — sharded sort: translated into this
+  // rank's local list positions — into d_bound_local after every exchange).
+  p.mb.boundary_in = g.rank == 0 ? nullptr : w.d_bound_local.p;
+  return YDC_OK;
+}
+
+// Front: the slot order (full: scan, generation and sort of the whole registry; windowed:
+// classification, the counts' exchange, key counts, this rank's window, the windows' exchange,
+// generation and sort of the window) and the chunks' level guesses from the gathered counts.
+int shard_front(ydc_context* c, const ShardCall& call, ShardAttempt* a) {
+  auto& g = c->group;
+  auto& w = g.ws;
+  BatchPlan& p = a->p;
+  const uint32_t N = call.N, G = a->G, C = a->C, K = a->K, P = a->P, MS = a->MS;
+  hipStream_t st = c->stream;
+  DeviceParams* prm = c->d_prm.p;
+  if (!a->windowed) {
+    if (int rc = enqueue_front_a(c, p, call.tk)) return rc;
+  } else {
+    enqueue_scan(c, p, w.d_cls_begin_glob.p);
+    enqueue_gen(c, p, call.tk, false, true);  // classification only
+    if (N) {
+      PrefixArgs pa{c->d_chunk_consuming.p, K, c->d_before.p, P, 0u, 0u};
+      YDC_LAUNCH(c, "k_chunk_prefix", k_chunk_prefix, dim3(1), dim3(1024), 0, st, pa, prm);
+    }
+  }
+  if (!N) HIP_TRY(c, hipMemsetAsync(c->d_before.p, 0, (size_t)4 * P, st));  // totals row of K == 0
+  // Level guesses count the consuming requests of the ranks before this one; a rank without
+  // requests is skipped by its successor (k_rank_meta: counts per part + number of requests).
+  hipLaunchKernelGGL(k_rank_meta, dim3(1), dim3(64), 0, st, c->d_before.p + (size_t)K * P, P, N, w.d_meta.p);
+  if (int rc = g.via->gather(c, w.d_meta.p, w.d_totals.p, (size_t)4 * MS)) return rc;
+  if (a->windowed) {
+    const uint32_t log_t = 7;  // kWindowThresholds == 128
+    static_assert(kWindowThresholds == 128, "threshold shift");
+    const uint32_t shift = c->kf.key_bits > log_t ? c->kf.key_bits - log_t : 0;
+    YDC_LAUNCH(c, "k_key_count", k_key_count, dim3(kWindowThresholds - 1), dim3(256), 0, st, p.sv, c->kf.cap_bits,
+               shift, w.d_cum.p);
+    WindowArgs wa{w.d_cum.p, c->kf.cap_bits, shift, w.d_totals.p, MS, (uint32_t)g.rank, G, p.win_margin,
+                  p.slot_bound, c->d_slot_base.p, w.d_cls_begin_glob.p, C, w.d_r_first.p,
+                  w.d_lbase.p, c->d_cls_begin.p, w.d_shift.p, w.d_winrec.p};
+    YDC_LAUNCH(c, "k_window", k_window, dim3(1), dim3(1024), (size_t)2 * C * 4, st, p.sv, wa, prm);
+    if (int rc = g.via->gather(c, w.d_winrec.p, w.d_winall.p, (size_t)2 * C * 4)) return rc;
+    enqueue_gen(c, p, call.tk, true, false);  // the window's slots
+    if (int rc = enqueue_sort(c, p, false)) return rc;
+  }
+  if (p.wave_path && p.W == 1 && c->opt_own_guess) {
+    // Pass 0 works the guesses out itself, from the gathered counts.
+    p.mb.before = c->d_before.p;
+    p.mb.base_totals = w.d_totals.p;
+    p.mb.base_rank = (uint32_t)g.rank;
+    p.mb.base_stride = MS;
+    if (int rc = enqueue_front_b(c, p, nullptr)) return rc;
+  } else {
+    hipLaunchKernelGGL(k_rank_base, dim3(1), dim3(64), 0, st, w.d_totals.p, (uint32_t)g.rank, P, MS, w.d_base.p);
+    if (int rc = enqueue_front_b(c, p, w.d_base.p)) return rc;
+  }
+  mark(c, 6);
+  return YDC_OK;
+}
+
+// Matching passes [first, first + count), pre-launched like on one GPU: after every pass the
+// ranks all-gather (end state of the last chunk, "changed an end state" flag); k_global_flag /
+// k_boundary_in turn the flags into one global flag per pass, which gates the following passes
+// on every rank alike.
+int shard_passes(ydc_context* c, ShardAttempt* a, uint32_t first, uint32_t count) {
+  auto& g = c->group;
+  auto& w = g.ws;
+  const BatchPlan& p = a->p;
+  const uint32_t G = a->G, C = a->C, MS = a->MS, rec = (uint32_t)a->rec;
+  hipStream_t st = c->stream;
+  DeviceParams* prm = c->d_prm.p;
+  for (uint32_t r = first; r < first + count; ++r) {
+    if (first) {  // (the first group's counter slots were cleared with the batch)
+      HIP_TRY(c, hipMemsetAsync(&prm->n_changed[r & 63], 0, 4, st));
+      HIP_TRY(c, hipMemsetAsync(&prm->n_sampled[r & 63], 0, 4, st));
+    }
+    if (p.wave_path) enqueue_pass(c, p, r, 1u);
+    hipLaunchKernelGGL(k_pack_boundary, dim3(ceil_div(rec, 256)), dim3(256), 0, st, p.L, c->d_endst.p,
+                       p.wave_path ? a->K : 0u, p.mb.boundary_in, prm, r, w.d_send.p,
+                       a->windowed ? w.d_shift.p : nullptr);
+    if (int rc = g.via->gather(c, w.d_send.p, w.d_bounds.p, a->rec * sizeof(ClassState))) return rc;
+    if (a->windowed) {
+      hipLaunchKernelGGL(k_boundary_in, dim3(ceil_div(C, 256)), dim3(256), 0, st, w.d_bounds.p, rec, C, G,
+                         (uint32_t)g.rank, r, w.d_winall.p, w.d_cls_begin_glob.p, w.d_totals.p, MS, w.d_shift.p,
+                         w.d_bound_local.p, prm);
+    } else {
+      hipLaunchKernelGGL(k_global_flag, dim3(std::max(1u, ceil_div(C, 256))), dim3(256), 0, st, w.d_bounds.p, rec,
+                         C, G, (uint32_t)g.rank, r, w.d_totals.p, MS, c->d_cls_begin.p, w.d_bound_local.p, prm);
+    }
+  }
+  a->launched = first + count;
+  return YDC_OK;
+}
+
+// The tail behind a group of passes, gated on the device by the last pass's global flag (the
+// same on every rank): placement of this rank's slice, then the global running_tasks from
+// everybody's slot deltas. Not converged yet (or a window missed): the deltas are zero and
+// nothing changes.
+int shard_tail(ydc_context* c, const ShardCall& call, const ShardAttempt& a) {
+  auto& g = c->group;
+  auto& w = g.ws;
+  // (no COMMIT and no running_tasks from the finalise: k_sum_deltas does both, below)
+  BatchCall slice;
+  slice.out_idx = call.out_idx;
+  slice.out_util = call.out_util;
+  if (int rc = enqueue_finalize(c, a.p, slice, (a.launched - 1) & 63, w.d_delta.p, a.p.mb.boundary_in)) return rc;
+  if (a.S) {
+    if (int rc = g.via->gather(c, w.d_delta.p, w.d_deltas.p, (size_t)a.S * 4)) return rc;
+    hipLaunchKernelGGL(k_sum_deltas, dim3(ceil_div(a.S, 256)), dim3(256), 0, c->stream, c->d_running.p,
+                       w.d_deltas.p, a.S, a.G, c->d_running_out.p, call.out_running,
+                       (call.flags & YDC_DISPATCH_COMMIT) ? c->d_running.p : nullptr, c->d_prm.p);
+  }
+  mark(c, 7);
+  return YDC_OK;
+}
+
+// debug_sim: what the passes [first, launched) left, and on rank 0 every rank's record of the
+// last pass (registry-wide positions).
+void shard_debug_dump(ydc_context* c, const ShardAttempt& a, uint32_t first) {
+  auto& g = c->group;
+  const uint32_t G = a.G, C = a.C;
+  const size_t rec = a.rec;
+  fprintf(stderr, "[ydc sharded] rank %d/%u windowed %d launched %u n_slots %u rank_offset %u miss %u changed:",
+          g.rank, G, (int)a.windowed, a.launched, c->h_prm->n_slots, c->h_prm->rank_offset, c->h_prm->window_miss);
+  for (uint32_t r = first; r < a.launched; ++r) fprintf(stderr, " %u", c->h_prm->n_changed[r & 63]);
+  fprintf(stderr, "\n");
+  if (g.rank != 0 || a.launched > 30) return;
+  (void)hipMemcpy(g.h_bounds, g.ws.d_bounds.p, rec * G * sizeof(ClassState), hipMemcpyDeviceToHost);
+  for (uint32_t q = 0; q < G; ++q) {
+    fprintf(stderr, "   rank %u flag %u:", q, g.h_bounds[q * rec + C].cursor);
+    for (uint32_t k = 0; k < std::min(C, 8u); ++k)
+      fprintf(stderr, " (%u,%u,%x)", g.h_bounds[q * rec + k].cursor, g.h_bounds[q * rec + k].lo,
+              g.h_bounds[q * rec + k].hown_lo);
+    fprintf(stderr, "\n");
+  }
+}
+
+// Reads DeviceParams back behind the tail of the passes [first, launched) and says what they
+// came to — the same verdict on every rank, from flags every rank sees alike.
+ShardOutcome shard_outcome(ydc_context* c, const ShardAttempt& a, uint32_t first) {
+  ShardOutcome o;
+  auto failed = [&](int rc) {
+    o.what = ShardOutcome::kFailed;
+    o.rc = rc;
+    return o;
+  };
+  auto readback = [&]() -> int {
+    HIP_TRY(c, hipMemcpyAsync(c->h_prm, c->d_prm.p, sizeof(DeviceParams), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return YDC_OK;
+  };
+  if (int rc = readback()) return failed(rc);
+  if (c->debug_sim) shard_debug_dump(c, a, first);
+  if (c->h_prm->overflow) return failed(fail(c, YDC_ERR_CAPACITY, "slot workspace overflow on some rank"));
+  if (c->h_prm->exchange_timeout) return failed(late_peer(c));
+  // (Belt and braces: a sharded sort that has not settled after 256 passes — the same count
+  // on every rank — is treated like a missed window.)
+  if (c->h_prm->window_miss || (a.windowed && a.launched >= 256)) {
+    o.what = ShardOutcome::kMissed;
+  } else if (c->h_prm->n_changed[(a.launched - 1) & 63] == 0) {
+    o.what = ShardOutcome::kSettled;
+    o.rounds = shard_rounds(c->h_prm->n_changed, first, a.launched - first);
+  } else {
+    o.what = ShardOutcome::kGoOn;
+  }
+  return o;
+}
+
+}  // namespace
+
+extern "C" {
 
 int ydc_dispatch_sharded(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t flags,
                          uint32_t* d_out_idx, double* d_out_util, uint32_t* d_out_running) {
   if (!c || (N && !tk)) return YDC_ERR_INVALID_ARGUMENT;
   auto& g = c->group;
   if (g.n_ranks < 1) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_group_init first");
-  HIP_TRY(c, hipSetDevice(c->device));
-  resident_stop(c);  // (the registry leaves the resident kernel's registers)
-  BatchPlan full_plan;
+  if (int rc = group_enter(c, GroupKeep::kGroup)) return rc;
+  const ShardCall call{tk, N, flags, d_out_idx, d_out_util, d_out_running};
+  BatchPlan full_plan, win_plan;
   if (int rc = plan_batch(c, N, &full_plan)) return rc;
-  BatchPlan p = full_plan;
-  if (p.use_generic) {
-    // Registries the sharded matching does not take (> 256 classes: thread-per-chunk path):
-    // every rank gathers the whole batch, places it redundantly with the single-GPU pipeline
-    // — identical on all ranks — and keeps its own slice of the placement.
-    const uint32_t G = (uint32_t)g.n_ranks;
-    HIP_TRY(c, g.d_totals.reserve(G + 1));
-    HIP_TRY(c, hipMemcpyAsync(g.d_totals.p + G, &N, 4, hipMemcpyHostToDevice, c->stream));
-    if (int rc = group_all_gather(c, g.d_totals.p + G, g.d_totals.p, 4)) return rc;
-    std::vector<uint32_t> sizes(G);
-    HIP_TRY(c, hipMemcpyAsync(sizes.data(), g.d_totals.p, (size_t)G * 4, hipMemcpyDeviceToHost, c->stream));
-    if (int rc = group_exchange_check(c)) return rc;  // (a late peer's size would read as 0)
-    uint32_t max_n = 1, total = 0, my_off = 0;
-    for (uint32_t r = 0; r < G; ++r) {
-      max_n = std::max(max_n, sizes[r]);
-      if (r < (uint32_t)g.rank) my_off += sizes[r];
-      total += sizes[r];
-    }
-    HIP_TRY(c, g.d_pad.reserve(max_n));
-    HIP_TRY(c, g.d_gather.reserve((size_t)max_n * G));
-    HIP_TRY(c, g.d_all[0].reserve(total));
-    HIP_TRY(c, g.d_all[1].reserve(total));
-    HIP_TRY(c, g.d_all[2].reserve(total));
-    HIP_TRY(c, g.d_all_idx.reserve(total));
-    if (d_out_util) HIP_TRY(c, g.d_all_util.reserve(total));
-    const uint32_t* cols[3] = {N ? tk->env_id : nullptr, N ? tk->min_version : nullptr,
-                               N ? tk->requestor_ip : nullptr};
-    for (int k = 0; k < 3; ++k) {
-      if (N) HIP_TRY(c, hipMemcpyAsync(g.d_pad.p, cols[k], (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
-      if (int rc = group_all_gather(c, g.d_pad.p, g.d_gather.p, (size_t)max_n * 4)) return rc;
-      uint32_t off = 0;
-      for (uint32_t r = 0; r < G; ++r) {
-        if (sizes[r])
-          HIP_TRY(c, hipMemcpyAsync(g.d_all[k].p + off, g.d_gather.p + (size_t)r * max_n,
-                                    (size_t)sizes[r] * 4, hipMemcpyDeviceToDevice, c->stream));
-        off += sizes[r];
-      }
-    }
-    // (... and a late peer's columns as zeros: nothing is placed, let alone committed, on them)
-    if (int rc = group_exchange_check(c)) return rc;
-    ydc_task_soa all{g.d_all[0].p, g.d_all[1].p, g.d_all[2].p};
-    if (int rc = ydc_dispatch_device(c, &all, total, flags, g.d_all_idx.p,
-                                     d_out_util ? g.d_all_util.p : nullptr, d_out_running))
-      return rc;
-    if (N && d_out_idx)
-      HIP_TRY(c, hipMemcpyAsync(d_out_idx, g.d_all_idx.p + my_off, (size_t)N * 4,
-                                hipMemcpyDeviceToDevice, c->stream));
-    if (N && d_out_util)
-      HIP_TRY(c, hipMemcpyAsync(d_out_util, g.d_all_util.p + my_off, (size_t)N * 8,
-                                hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    // Stats describe the whole batch in this mode; report this rank's share of the grants.
-    c->stats.n_tasks = N;
-    g.passes = c->stats.rounds;
-    return YDC_OK;
-  }
-  const uint32_t G = (uint32_t)g.n_ranks, C = p.C, S = p.S, K = p.K;
-  const size_t rec = (size_t)C + 1;  // ClassStates a rank publishes per pass
-  const uint32_t P = c->n_parts;  // counts are exchanged per independent part of the registry
-  const uint32_t MS = P + 1;  // words of a rank's k_rank_meta record
-  HIP_TRY(c, g.d_totals.reserve((size_t)G * MS));
-  HIP_TRY(c, g.d_meta.reserve(MS));
-  HIP_TRY(c, g.d_bound_local.reserve(C ? C : 1));
-  HIP_TRY(c, g.d_base.reserve(P));
-  HIP_TRY(c, g.d_send.reserve(rec));
-  HIP_TRY(c, g.d_bounds.reserve(rec * G));
-  HIP_TRY(c, g.d_delta.reserve(S));
-  HIP_TRY(c, g.d_deltas.reserve((size_t)S * G));
-  HIP_TRY(c, g.h_bounds.reserve(rec * G * sizeof(ClassState), hipHostMallocDefault));
-  hipStream_t st = c->stream;
-  DeviceParams* prm = c->d_prm.p;
-
+  if (full_plan.use_generic) return sharded_replicated(c, call);
+  ShardAttempt a;
+  if (int rc = shard_prepare(c, full_plan, &a)) return rc;
   // Sharded sort (kernels.h: k_key_count / k_window): this rank generates and
   // sorts only the key window its rank range can reach. Taken for integer keys, one part, a
   // servant per host, 2 .. 256 classes; anything else — and any batch whose window turns out
@@ -3695,197 +4006,49 @@ int ydc_dispatch_sharded(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uin
   // A registry small enough for the bin sort is ordered whole on every rank (two launches, no
   // exchange) — cheaper than the key-count / window / radix sequence until the slot count is in
   // the millions; the windows are for the registries the bin sort does not take.
-  bool windowed = G > 1 && c->opt_shard_sort && c->kf.exact && P == 1 && !p.use_generic && C >= 2 &&
-                  !p.any_shared && !(full_plan.binsort && c->opt_group_binsort);
-  BatchPlan win_plan;
-  if (windowed)
+  WindowedInputs wi;
+  wi.n_ranks = a.G, wi.n_parts = a.P, wi.n_classes = a.C;
+  wi.shard_sort = c->opt_shard_sort, wi.exact_keys = c->kf.exact;
+  wi.use_generic = full_plan.use_generic, wi.any_shared = full_plan.any_shared;
+  wi.binsort = full_plan.binsort, wi.group_binsort = c->opt_group_binsort;
+  a.windowed = shard_windowed(wi);
+  if (a.windowed)
     if (int rc = plan_batch(c, N, &win_plan, true)) return rc;
-  uint32_t rounds = 0;
+  // An attempt is a front and groups of passes, each with its tail, until one settles. The host
+  // looks at the outcome once per group.
+  ShardOutcome o;
   for (;;) {
-    p = windowed ? win_plan : full_plan;
-    p.mb.has_successor = g.rank + 1 < g.n_ranks ? 1u : 0u;
-    p.zone = false;  // (the walk of the tier's end is a single-context thing: zone_guess.h)
-    p.mb.zone_box = nullptr;
-    if (windowed) {
-      // Slots of the window: this rank's requests + a margin on both sides (classes run ahead
-      // of or behind the global level) + the granularity of the thresholds.
-      const uint64_t margin = c->opt_shard_margin >= 0
-                                  ? (uint64_t)c->opt_shard_margin
-                                  : (uint64_t)g.margin_scale * std::max<uint64_t>(N / 8, 8192);
-      const uint64_t bound = std::min<uint64_t>(
-          win_plan.slot_bound, (uint64_t)N + 2 * margin + win_plan.slot_bound / 8 + 65536);
-      p.win = true;
-      p.win_margin = (uint32_t)std::min<uint64_t>(margin, 0x7FFFFFFFu);
-      p.slot_bound = (uint32_t)bound;
-      p.sort_items = p.slot_bound <= 300000 ? 2 : (p.slot_bound <= 700000 ? 4 : 8);
-      p.n_tiles = std::max<uint32_t>(1, ceil_div(p.slot_bound, kSortThreads * p.sort_items));
-      if (p.mb.tile_tab) {  // (the window's own tiles: ranks are registry-wide, rank_offset apart)
-        p.mb.tile_tab_tiles = p.n_tiles;
-        p.mb.tile_tab_elems = kSortThreads * p.sort_items;
-      }
-      HIP_TRY(c, g.d_cum.reserve(kWindowThresholds + 1));
-      HIP_TRY(c, g.d_r_first.reserve(S));
-      HIP_TRY(c, g.d_lbase.reserve((size_t)S + 1));
-      HIP_TRY(c, g.d_cls_begin_glob.reserve((size_t)C + 1));
-      HIP_TRY(c, g.d_shift.reserve(C));
-      HIP_TRY(c, g.d_winrec.reserve((size_t)2 * C));
-      HIP_TRY(c, g.d_winall.reserve((size_t)2 * C * G));
-      ++g.windowed_batches;
-    }
-    // The chunks of this rank continue those of the nearest rank below that has requests
-    // (k_global_flag / k_boundary_in copy its end state — sharded sort: translated into this
-    // rank's local list positions — into d_bound_local after every exchange).
-    p.mb.boundary_in = g.rank == 0 ? nullptr : g.d_bound_local.p;
-
-    if (!windowed) {
-      if (int rc = enqueue_front_a(c, p, tk)) return rc;
-    } else {
-      enqueue_scan(c, p, g.d_cls_begin_glob.p);
-      enqueue_gen(c, p, tk, false, true);  // classification only
-      if (N) {
-        PrefixArgs pa{c->d_chunk_consuming.p, K, c->d_before.p, P, 0u, 0u};
-        YDC_LAUNCH(c, "k_chunk_prefix", k_chunk_prefix, dim3(1), dim3(1024), 0, st, pa, prm);
-      }
-    }
-    if (!N) HIP_TRY(c, hipMemsetAsync(c->d_before.p, 0, (size_t)4 * P, st));  // totals row of K == 0
-    // Level guesses count the consuming requests of the ranks before this one; a rank without
-    // requests is skipped by its successor (k_rank_meta: counts per part + number of requests).
-    hipLaunchKernelGGL(k_rank_meta, dim3(1), dim3(64), 0, st, c->d_before.p + (size_t)K * P, P, N, g.d_meta.p);
-    if (int rc = group_all_gather(c, g.d_meta.p, g.d_totals.p, (size_t)4 * MS)) return rc;
-    if (windowed) {
-      const uint32_t log_t = 7;  // kWindowThresholds == 128
-      static_assert(kWindowThresholds == 128, "threshold shift");
-      const uint32_t shift = c->kf.key_bits > log_t ? c->kf.key_bits - log_t : 0;
-      YDC_LAUNCH(c, "k_key_count", k_key_count, dim3(kWindowThresholds - 1), dim3(256), 0, st, p.sv,
-                 c->kf.cap_bits, shift, g.d_cum.p);
-      WindowArgs wa{g.d_cum.p, c->kf.cap_bits, shift, g.d_totals.p, MS, (uint32_t)g.rank, G, p.win_margin,
-                    p.slot_bound, c->d_slot_base.p, g.d_cls_begin_glob.p, C, g.d_r_first.p,
-                    g.d_lbase.p, c->d_cls_begin.p, g.d_shift.p, g.d_winrec.p};
-      YDC_LAUNCH(c, "k_window", k_window, dim3(1), dim3(1024), (size_t)2 * C * 4, st, p.sv, wa, prm);
-      if (int rc = group_all_gather(c, g.d_winrec.p, g.d_winall.p, (size_t)2 * C * 4)) return rc;
-      enqueue_gen(c, p, tk, true, false);  // the window's slots
-      if (int rc = enqueue_sort(c, p, false)) return rc;
-    }
-    if (p.wave_path && p.W == 1 && c->opt_own_guess) {
-      // Pass 0 works the guesses out itself, from the gathered counts.
-      p.mb.before = c->d_before.p;
-      p.mb.base_totals = g.d_totals.p;
-      p.mb.base_rank = (uint32_t)g.rank;
-      p.mb.base_stride = MS;
-      if (int rc = enqueue_front_b(c, p, nullptr)) return rc;
-    } else {
-      hipLaunchKernelGGL(k_rank_base, dim3(1), dim3(64), 0, st, g.d_totals.p, (uint32_t)g.rank, P, MS, g.d_base.p);
-      if (int rc = enqueue_front_b(c, p, g.d_base.p)) return rc;
-    }
-    mark(c, 6);
-
-    // Matching passes, pre-launched in groups like on one GPU: after every pass the ranks
-    // all-gather (end state of the last chunk, "changed an end state" flag); k_global_flag /
-    // k_boundary_in turn the flags into one global flag per pass, which gates the following
-    // passes on every rank alike. The host looks at the outcome once per group.
-    uint32_t launched = 0;
-    bool miss = false;
-    for (;;) {
-      const uint32_t group = launched == 0 ? std::max(2u, std::min(g.pass_hint, 12u)) : 3u;
-      for (uint32_t r = launched; r < launched + group; ++r) {
-        if (launched) {
-          HIP_TRY(c, hipMemsetAsync(&prm->n_changed[r & 63], 0, 4, st));
-          HIP_TRY(c, hipMemsetAsync(&prm->n_sampled[r & 63], 0, 4, st));
-        }
-        if (p.wave_path) enqueue_pass(c, p, r, 1u);
-        hipLaunchKernelGGL(k_pack_boundary, dim3(ceil_div((uint32_t)rec, 256)), dim3(256), 0, st, p.L,
-                           c->d_endst.p, p.wave_path ? K : 0u, p.mb.boundary_in, prm, r, g.d_send.p,
-                           windowed ? g.d_shift.p : nullptr);
-        if (int rc = group_all_gather(c, g.d_send.p, g.d_bounds.p, rec * sizeof(ClassState))) return rc;
-        if (windowed) {
-          hipLaunchKernelGGL(k_boundary_in, dim3(ceil_div(C, 256)), dim3(256), 0, st, g.d_bounds.p,
-                             (uint32_t)rec, C, G, (uint32_t)g.rank, r, g.d_winall.p,
-                             g.d_cls_begin_glob.p, g.d_totals.p, MS, g.d_shift.p, g.d_bound_local.p, prm);
-        } else {
-          hipLaunchKernelGGL(k_global_flag, dim3(std::max(1u, ceil_div(C, 256))), dim3(256), 0, st,
-                             g.d_bounds.p, (uint32_t)rec, C, G, (uint32_t)g.rank, r, g.d_totals.p, MS,
-                             c->d_cls_begin.p, g.d_bound_local.p, prm);
-        }
-      }
-      const uint32_t first = launched;
-      launched += group;
-      // The tail behind the group, gated on the device by the last pass's global flag (the same
-      // on every rank): placement of this rank's slice, then the global running_tasks from
-      // everybody's slot deltas. Not converged yet (or a window missed): the deltas are zero
-      // and nothing changes.
-      // (no COMMIT and no running_tasks from the finalise: k_sum_deltas does both, below)
-      BatchCall slice;
-      slice.out_idx = d_out_idx;
-      slice.out_util = d_out_util;
-      if (int rc = enqueue_finalize(c, p, slice, (launched - 1) & 63, g.d_delta.p, p.mb.boundary_in)) return rc;
-      if (S) {
-        if (int rc = group_all_gather(c, g.d_delta.p, g.d_deltas.p, (size_t)S * 4)) return rc;
-        hipLaunchKernelGGL(k_sum_deltas, dim3(ceil_div(S, 256)), dim3(256), 0, st, c->d_running.p,
-                           g.d_deltas.p, S, G, c->d_running_out.p, d_out_running,
-                           (flags & YDC_DISPATCH_COMMIT) ? c->d_running.p : nullptr, prm);
-      }
-      mark(c, 7);
-      HIP_TRY(c, hipMemcpyAsync(c->h_prm, prm, sizeof(DeviceParams), hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      HIP_TRY(c, hipGetLastError());
-      if (c->debug_sim) {
-        fprintf(stderr, "[ydc sharded] rank %d/%u windowed %d launched %u n_slots %u rank_offset %u miss %u changed:",
-                g.rank, G, (int)windowed, launched, c->h_prm->n_slots, c->h_prm->rank_offset,
-                c->h_prm->window_miss);
-        for (uint32_t r = first; r < launched; ++r) fprintf(stderr, " %u", c->h_prm->n_changed[r & 63]);
-        fprintf(stderr, "\n");
-        if (g.rank == 0 && launched <= 30) {  // every rank's record of the last pass (registry-wide positions)
-          (void)hipMemcpy(g.h_bounds, g.d_bounds.p, rec * G * sizeof(ClassState), hipMemcpyDeviceToHost);
-          for (uint32_t q = 0; q < G; ++q) {
-            fprintf(stderr, "   rank %u flag %u:", q, g.h_bounds[q * rec + C].cursor);
-            for (uint32_t k = 0; k < std::min(C, 8u); ++k)
-              fprintf(stderr, " (%u,%u,%x)", g.h_bounds[q * rec + k].cursor, g.h_bounds[q * rec + k].lo,
-                      g.h_bounds[q * rec + k].hown_lo);
-            fprintf(stderr, "\n");
-          }
-        }
-      }
-      if (c->h_prm->overflow) return fail(c, YDC_ERR_CAPACITY, "slot workspace overflow on some rank");
-      if (c->h_prm->exchange_timeout)
-        return fail(c, YDC_ERR_HIP, "a peer's data did not arrive within the mailbox time-out (rank %d of %u)",
-                    g.rank, G);
-      // (Belt and braces: a sharded sort that has not settled after 256 passes — the same count
-      // on every rank — is treated like a missed window.)
-      if (c->h_prm->window_miss || (windowed && launched >= 256)) {
-        miss = true;
-        break;
-      }
-      if (c->h_prm->n_changed[(launched - 1) & 63] == 0) {
-        rounds = launched;
-        for (uint32_t r = first; r < launched; ++r)
-          if (c->h_prm->n_changed[r & 63] == 0) {
-            rounds = r + 1;  // first pass in which no rank changed anything
-            break;
-          }
-        g.pass_hint = rounds;
-        break;
-      }
-      // Worst case one chunk per pass becomes final; K differs per rank, so bound it loosely.
-      if (launched > 200000u) return fail(c, YDC_ERR_NOT_CONVERGED, "no fixpoint");
-    }
-    if (!miss) break;
-    if (!windowed && p.binsort) {
+    if (int rc = shard_plan_attempt(c, call, a.windowed ? win_plan : full_plan, &a)) return rc;
+    if (int rc = shard_front(c, call, &a)) return rc;
+    do {
+      const uint32_t first = a.launched;
+      if (int rc = shard_passes(c, &a, first, shard_pass_group(first, g.pass_hint))) return rc;
+      if (int rc = shard_tail(c, call, a)) return rc;
+      o = shard_outcome(c, a, first);
+      // More than 200000 passes: given up. (Worst case one chunk per pass becomes final; K
+      // differs per rank, so bound it loosely.)
+      if (o.what == ShardOutcome::kGoOn && a.launched > 200000u) return fail(c, YDC_ERR_NOT_CONVERGED, "no fixpoint");
+    } while (o.what == ShardOutcome::kGoOn);
+    if (o.what == ShardOutcome::kFailed) return o.rc;
+    if (o.what == ShardOutcome::kSettled) break;
+    if (!a.windowed && a.p.binsort) {
       // A bin of the bin sort overflowed (bin_sort.h; the registry decides, so every rank met
       // the same): once more with the radix pipeline, which then stays.
       note_bin_overflow(c);
       if (int rc = plan_batch(c, N, &full_plan)) return rc;
       continue;
     }
-    if (!windowed) return fail(c, YDC_ERR_NOT_CONVERGED, "window miss flagged without a window");
-    // Some rank's window did not cover what its requests reached (every rank saw the same
-    // flag): once more with the full sort everywhere, and wider margins from now on.
+    if (!a.windowed) return fail(c, YDC_ERR_NOT_CONVERGED, "window miss flagged without a window");
+    // Some rank's window did not cover what its requests reached, or 256 windowed passes did
+    // not settle (every rank saw the same): once more with the full sort everywhere, and wider
+    // margins from now on.
     ++g.window_misses;
-    g.margin_scale = std::min(g.margin_scale * 2, 64u);
-    windowed = false;
+    g.margin_scale = shard_margin_after_miss(g.margin_scale);
+    a.windowed = false;
   }
-  g.passes = rounds;
+  g.pass_hint = g.passes = o.rounds;
 
-  fill_stats(c, p, rounds);
+  fill_stats(c, a.p, o.rounds);
   if (c->profiling) collect_kernel_profile(c);
   return YDC_OK;
 }
