@@ -998,7 +998,8 @@ __global__ __launch_bounds__(64) void k_walk_groups(ClassLists L, TaskTable T, u
 #ifdef YDC_PHASE_PROBE
   if (lane == 0) {
     const unsigned long long v[16] = {gp_block, gp_scan, gp_gen, gp_claim, gp_taint, gp_commit, wall_clock64() - gp_total0,
-                                      gp_iters, gp_gens, gp_rounds, gp_commits, gp_losers, gp_blocked, gp_pending, 0, 0};
+                                      gp_iters, gp_gens, gp_rounds, gp_commits, gp_losers, gp_blocked, gp_pending,
+                                      PACKED ? 2u : 1u, 0};  // (word 30: which form of the walk ran)
     for (int i = 0; i < 16; ++i) ydc_phase_probe[16 + i] = v[i];
   }
 #endif
