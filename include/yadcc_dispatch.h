@@ -569,6 +569,54 @@ int ydc_stream_book_stage(ydc_context* ctx, const uint64_t* servant_task_id, con
 int ydc_stream_book_get(ydc_context* ctx, uint32_t* out_servant_idx, uint64_t* out_task_grant_id,
                         uint64_t* out_servant_task_id, uint64_t* out_digest_key, uint32_t cap, uint32_t* out_n);
 
+/* ---- the book by digest: what a daemon's RunningTaskKeeper asks of GetRunningTasks -------------
+ * The reference's one consumer of the list folds it into a map from task_digest to (servant,
+ * servant_task_id) in which the LAST entry of the list wins (running_task_keeper.cc:55-60) and asks
+ * that map once per compile task, before it asks for a grant (TryFindTask, :67-75). With B on, the
+ * two calls below answer from a digest index over B on the device, so nobody has to copy B out and
+ * hash it again. The index is derived state: built by the first call that needs it, kept while B
+ * cannot have changed, built again on demand. Both calls only read the stream; a stream that never
+ * calls them launches what it launched before.
+ *   Keys: all 2^64 values of digest_key are ordinary keys, 0 (what entries carry when nothing was
+ *     staged) and 0xFFFFFFFFFFFFFFFF included. Queries may repeat.
+ *   ydc_stream_book_find: out[i] describes the last entry of B, in B's order, whose digest_key equals
+ *     digest_key[i] — the answer of a RunningTaskKeeper after a Refresh from this list —: pos is its
+ *     position in B as ydc_stream_book_get orders it, servant_idx / task_grant_id / servant_task_id
+ *     are its columns, count is how many entries of B share the key. No such entry: pos =
+ *     YDC_BOOK_NOT_FOUND and every other field 0. n == 0 returns YDC_OK (NULL columns allowed);
+ *     n > 2^24: YDC_ERR_INVALID_ARGUMENT, the caller splits.
+ *   ydc_stream_book_distinct: B folded to what that map would hold, one row per key that occurs in
+ *     B — the winning (last) entry's four columns and the key's count —, ordered by the winning
+ *     entries' positions, ascending. *out_n: the number of distinct keys; more than cap of them:
+ *     YDC_ERR_CAPACITY with *out_n set and nothing written. Any output column may be NULL.
+ *   Both run between ticks and synchronise. Like ydc_stream_outlook_get they end the resident tick
+ *     kernel and refuse, with YDC_ERR_INVALID_ARGUMENT, while pipelined batches are outstanding; the
+ *     same code for no open stream, a stream without a book, and n > 0 with a NULL digest_key or out.
+ *     A staging that no tick has consumed yet does not matter. An allocation that fails is
+ *     YDC_ERR_HIP, and the stream stays usable.
+ *   Nothing of theirs is carried by ydc_stream_reserve, ydc_stream_book_begin, ydc_stream_snapshot or
+ *     ydc_stream_restore: a snapshot taken after any number of calls is byte-identical to one taken
+ *     without, and the next tick answers as on a context that never called them.
+ *   *out_rebuilt (nullable): 1 if and only if this call built the index. 0 on a call that follows
+ *     another one with nothing in between, and after accepted ticks that carried no report
+ *     (n_rep == 0) and erased no servant; 1 on the first call after a tick that carried a report
+ *     (an empty one included), after a tick in which aliveness erased a servant (even if the tick
+ *     failed afterwards: last paragraph of the aliveness section), after ydc_remove_servants and after
+ *     ydc_stream_restore; after a ydc_stream_book_begin or ydc_stream_reserve that took effect, either. */
+#define YDC_BOOK_NOT_FOUND 0xFFFFFFFFu
+typedef struct ydc_book_hit {   /* 32 bytes */
+  uint32_t pos;          /* position in B of the LAST entry with this digest_key; YDC_BOOK_NOT_FOUND */
+  uint32_t count;        /* entries of B with this digest_key (0 on a miss) */
+  uint32_t servant_idx;  /* that entry's columns; 0 on a miss */
+  uint32_t reserved;     /* 0 */
+  uint64_t task_grant_id, servant_task_id;
+} ydc_book_hit;
+int ydc_stream_book_find(ydc_context* ctx, const uint64_t* digest_key, uint32_t n, ydc_book_hit* out,
+                         uint32_t* out_rebuilt /* nullable */);
+int ydc_stream_book_distinct(ydc_context* ctx, uint32_t* out_servant_idx, uint64_t* out_task_grant_id,
+                             uint64_t* out_servant_task_id, uint64_t* out_digest_key, uint32_t* out_count,
+                             uint32_t cap, uint32_t* out_n, uint32_t* out_rebuilt /* nullable */);
+
 /* ---- the servants' expiry on the device: KeepServantAlive's expires_in and the servant half of
  * OnExpirationTimer (task_dispatcher.cc:190-220, :498-520) inside the tick -------------------------
  * With aliveness on, every servant has an expires_at (int64, on the clock the ticks carry as `now`)

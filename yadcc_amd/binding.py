@@ -23,6 +23,7 @@ IDX_WAITING = 0xFFFFFFFD  # streaming waiting mode: queued on the device, answer
 INSPECT_NO_ID = 0xFFFFFFFF  # env_id / requestor_ip of a lease granted while inspection was off
 INSPECT_NO_TIME = -(1 << 63)  # ... its started_at
 OUTLOOK_UNKNOWN = 0xFFFFFFFF  # leases / zombies of an outlook row while inspection is off
+BOOK_NOT_FOUND = 0xFFFFFFFF  # pos of a ydc_book_hit whose digest_key is not in the book
 DISPATCH_COMMIT = 1
 STAGES = ("servant_scan", "slot_gen", "sort", "class_lists", "task_classify", "match", "finalize",
           "total")
@@ -43,6 +44,7 @@ ABI_SYMBOLS = (
     "ydc_stream_begin_waiting_leased", "ydc_stream_tick_waiting_leased",
     "ydc_stream_begin_rpc", "ydc_stream_tick_rpc", "ydc_stream_caps_get", "ydc_stream_reserve",
     "ydc_stream_book_begin", "ydc_stream_book_stage", "ydc_stream_book_get",
+    "ydc_stream_book_find", "ydc_stream_book_distinct",
     "ydc_stream_alive_begin", "ydc_stream_alive_stage", "ydc_stream_alive_removed", "ydc_stream_alive_get",
     "ydc_stream_inspect_begin", "ydc_stream_inspect_load", "ydc_stream_inspect_servants", "ydc_stream_inspect_tasks",
     "ydc_stream_outlook_get", "ydc_stream_inspect_waiting",
@@ -84,6 +86,11 @@ class StreamOutlook(C.Structure):
 OUTLOOK_DTYPE = np.dtype([("eligible", "<u4"), ("free_servants", "<u4"), ("grants_available", "<u8"),
                           ("running_tasks", "<u8"), ("max_tasks", "<u8"), ("capacity_available", "<u8"),
                           ("waiting", "<u4"), ("waiting_rows", "<u4"), ("leases", "<u4"), ("zombies", "<u4")])
+
+
+# numpy view of ydc_book_hit (32 bytes)
+HIT_DTYPE = np.dtype([("pos", "<u4"), ("count", "<u4"), ("servant_idx", "<u4"), ("reserved", "<u4"),
+                      ("task_grant_id", "<u8"), ("servant_task_id", "<u8")])
 
 
 # numpy view of ydc_servant_row (32 bytes)
@@ -234,6 +241,9 @@ def lib():
         L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_uint32, C.POINTER(C.c_uint32)]
+        L.ydc_stream_book_find.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.ydc_stream_book_distinct.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_uint32, C.POINTER(C.c_uint32),
+                                                                                  C.POINTER(C.c_uint32)]
         L.ydc_group_unique_id.argtypes = [C.c_void_p]
         L.ydc_group_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ydc_group_init_local.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -980,6 +990,39 @@ class Context:
         self._check(lib().ydc_stream_book_get(self._h, srv.ctypes.data, gid.ctypes.data, stid.ctypes.data,
                                               dkey.ctypes.data, cap, C.byref(n)), "ydc_stream_book_get")
         return srv, gid, stid, dkey
+
+    def stream_book_find(self, keys):
+        """Who already compiles each digest (ydc_stream_book_find): (structured array of HIT_DTYPE, one
+        row per key — the LAST entry of the book with that digest_key, pos == BOOK_NOT_FOUND where
+        there is none —, rebuilt: whether this call built the digest index)."""
+        q = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros(len(q), HIT_DTYPE)
+        rebuilt = C.c_uint32(0)
+        for at in range(0, max(len(q), 1), 1 << 24):  # (the call takes 2^24 queries)
+            part, res, once = q[at:at + (1 << 24)], out[at:at + (1 << 24)], C.c_uint32(0)
+            self._check(lib().ydc_stream_book_find(self._h, _ptr(part), len(part), _ptr(res), C.byref(once)),
+                        "ydc_stream_book_find")
+            rebuilt.value |= once.value
+        return out, bool(rebuilt.value)
+
+    def stream_book_distinct(self):
+        """The book folded to one row per digest_key, the last entry winning, in the order of the
+        winners' positions (ydc_stream_book_distinct): ((servant_idx uint32, task_grant_id,
+        servant_task_id, digest_key uint64, count uint32), rebuilt)."""
+        n, rebuilt = C.c_uint32(0), C.c_uint32(0)
+        rc = lib().ydc_stream_book_distinct(self._h, None, None, None, None, None, 0, C.byref(n), C.byref(rebuilt))
+        cap = int(n.value)
+        if rc != 0 and cap == 0:
+            self._check(rc, "ydc_stream_book_distinct")
+        srv, cnt = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+        gid, stid, dkey = np.empty(cap, np.uint64), np.empty(cap, np.uint64), np.empty(cap, np.uint64)
+        if cap:
+            again = C.c_uint32(0)
+            self._check(lib().ydc_stream_book_distinct(self._h, srv.ctypes.data, gid.ctypes.data, stid.ctypes.data,
+                                                       dkey.ctypes.data, cnt.ctypes.data, cap, C.byref(n),
+                                                       C.byref(again)), "ydc_stream_book_distinct")
+            rebuilt.value |= again.value
+        return (srv, gid, stid, dkey, cnt), bool(rebuilt.value)
 
     def stream_alive_begin(self, expires_at=None, n=None):
         """Switches the servants' expiry column of the open leased, waiting-and-leased or rpc stream

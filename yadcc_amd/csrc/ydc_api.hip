@@ -33,6 +33,7 @@
 #include "rpc_stream.h"
 #include "wait_lease.h"
 #include "running_book.h"
+#include "book_index.h"
 #include "servant_alive.h"
 #include "stream_inspect.h"
 #include "stream_outlook.h"
@@ -437,6 +438,21 @@ struct ydc_context {
         bool on = false;
         std::vector<uint64_t> stid, dkey;
       } staged;
+      // The digest index over B (book_index.h; ydc_stream_book_find / ydc_stream_book_distinct):
+      // derived state, built on demand and sized by |B| then. `valid`: it describes B as B is now.
+      // The rule errs on the stale side: a Book starts without an index (so every stream_alloc —
+      // begin, end, ydc_stream_reserve, ydc_stream_book_begin, restore — drops it), and the two places
+      // that launch a pass over B with something to drop clear the mark before the launch: a tick
+      // that carries a report (stream_tick_stage) and remove_rows (ydc_remove_servants and the
+      // removal route of a tick with aliveness). Everything else here is the read calls' scratch.
+      struct Index {
+        bool valid = false;
+        DevBuf<uint8_t> d;  // key | last1 | cnt | side
+        BookIndex ix{};
+        DevBuf<unsigned long long> q;  // find: the queries ...
+        DevBuf<BookHit> res;           // ... and their results
+        DevBuf<uint8_t> rows;          // distinct: its state and look-back words | the five output columns
+      } index;
     } book;
     // The servants' expiry column E of a leased stream (ydc_stream_alive_begin; servant_alive.h): sized
     // by the registry like d_rep_tick, with a spare the removal route compacts into. !alive.on: no
@@ -1239,6 +1255,7 @@ static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_
   // ... and with a running-task book the entries of the removed rows (DropServant).
   const bool booked = leased && sm.max_book;
   if (booked) {
+    sm.book.index.valid = false;  // (positions and servant numbers move)
     const uint32_t tiles = ceil_div(sm.max_book, kBookTile);
     HIP_TRY(c, hipMemsetAsync(sm.book.lb, 0, (size_t)tiles * 8, c->stream));
     hipLaunchKernelGGL(k_book_remap, dim3(tiles), dim3(256), 0, c->stream, sm.book.bk, sm.book.bks, sm.max_book,
@@ -5023,6 +5040,110 @@ int ydc_stream_book_get(ydc_context* c, uint32_t* out_servant_idx, uint64_t* out
   return YDC_OK;
 }
 
+static int outlook_enter(ydc_context* c, const char* who);  // (further down, with the outlook)
+
+// What both read calls of the digest index do first: the outlook's refusals and its draining of the
+// stream, then the index over B as B is now — built here when the one at hand is stale or there is
+// none (book_index.h). *rebuilt: this call built it. A failed build leaves no index and the stream
+// as it was.
+static int book_index_enter(ydc_context* c, const char* who, uint32_t* rebuilt) {
+  *rebuilt = 0;
+  if (int rc = outlook_enter(c, who)) return rc;
+  auto& sm = c->stream_mode;
+  if (!sm.max_book) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the stream has no running-task book", who);
+  auto& ix = sm.book.index;
+  if (ix.valid) return YDC_OK;
+  const uint32_t n = sm.book.n, slots = book_index_slots(n);
+  const size_t o_last = (size_t)slots * 8, o_cnt = o_last + (size_t)slots * 4, o_side = o_cnt + (size_t)slots * 4;
+  HIP_TRY(c, ix.d.reserve(o_side + 8));
+  uint8_t* const b = ix.d.p;
+  ix.ix = BookIndex{(unsigned long long*)b, (uint32_t*)(b + o_last), (uint32_t*)(b + o_cnt), (uint32_t*)(b + o_side),
+                    slots - 1};
+  HIP_TRY(c, hipMemsetAsync(b, 0xFF, o_last, c->stream));               // every slot free
+  HIP_TRY(c, hipMemsetAsync(b + o_last, 0, o_side + 8 - o_last, c->stream));  // last1 | cnt | side
+  if (n)
+    YDC_LAUNCH(c, "k_book_index_build", k_book_index_build, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream,
+               sm.book.bk.dkey, n, ix.ix);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ix.valid = true;
+  *rebuilt = 1;
+  return YDC_OK;
+}
+
+int ydc_stream_book_find(ydc_context* c, const uint64_t* digest_key, uint32_t n, ydc_book_hit* out,
+                         uint32_t* out_rebuilt) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (out_rebuilt) *out_rebuilt = 0;
+  if (n > (1u << 24))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_find: %u queries > 2^24 in one call", n);
+  if (n && (!digest_key || !out))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_find: %u queries without their columns", n);
+  uint32_t rebuilt = 0;
+  const int rc = book_index_enter(c, "ydc_stream_book_find", &rebuilt);
+  if (out_rebuilt) *out_rebuilt = rebuilt;
+  if (rc || !n) return rc;
+  auto& sm = c->stream_mode;
+  auto& ix = sm.book.index;
+  static_assert(sizeof(ydc_book_hit) == sizeof(BookHit), "ydc_book_hit");
+  HIP_TRY(c, ix.q.reserve(n));
+  HIP_TRY(c, ix.res.reserve(n));
+  HIP_TRY(c, hipMemcpy(ix.q.p, digest_key, (size_t)n * 8, hipMemcpyHostToDevice));
+  YDC_LAUNCH(c, "k_book_index_find", k_book_index_find, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, ix.q.p, n, ix.ix,
+             sm.book.bk, sm.book.n, ix.res.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(out, ix.res.p, (size_t)n * sizeof(BookHit), hipMemcpyDeviceToHost));
+  return YDC_OK;
+}
+
+int ydc_stream_book_distinct(ydc_context* c, uint32_t* out_servant_idx, uint64_t* out_task_grant_id,
+                             uint64_t* out_servant_task_id, uint64_t* out_digest_key, uint32_t* out_count,
+                             uint32_t cap, uint32_t* out_n, uint32_t* out_rebuilt) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  if (out_rebuilt) *out_rebuilt = 0;
+  uint32_t rebuilt = 0;
+  const int rc = book_index_enter(c, "ydc_stream_book_distinct", &rebuilt);
+  if (out_rebuilt) *out_rebuilt = rebuilt;
+  if (rc) return rc;
+  auto& sm = c->stream_mode;
+  auto& ix = sm.book.index;
+  const uint32_t n = sm.book.n;
+  *out_n = 0;
+  if (!n) return YDC_OK;
+  // The pass's own ticket, count and look-back words | the five output columns, |B| rows each.
+  const uint32_t tiles = ceil_div(n, kBookTile);
+  size_t off = 0;
+  const size_t o_state = section(&off, sizeof(BookDistinctState)), o_lb = section(&off, (size_t)tiles * 8);
+  const size_t clear = off;
+  const size_t o_gr = section(&off, (size_t)n * 8), o_st = section(&off, (size_t)n * 8), o_dk = section(&off, (size_t)n * 8);
+  const size_t o_srv = section(&off, (size_t)n * 4), o_cnt = section(&off, (size_t)n * 4);
+  HIP_TRY(c, ix.rows.reserve(off));
+  uint8_t* const b = ix.rows.p;
+  BookDistinctState* const ds = (BookDistinctState*)(b + o_state);
+  const BookDistinctOut rows{(uint32_t*)(b + o_srv), (unsigned long long*)(b + o_gr), (unsigned long long*)(b + o_st),
+                             (unsigned long long*)(b + o_dk), (uint32_t*)(b + o_cnt)};
+  HIP_TRY(c, hipMemsetAsync(b, 0, clear, c->stream));
+  YDC_LAUNCH(c, "k_book_distinct", k_book_distinct, dim3(tiles), dim3(256), 0, c->stream, sm.book.bk, n, ix.ix, ds,
+             (unsigned long long*)(b + o_lb), rows);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint32_t m = 0;
+  HIP_TRY(c, hipMemcpy(&m, &ds->n_rows, 4, hipMemcpyDeviceToHost));
+  if (m > n) return fail(c, YDC_ERR_NOT_CONVERGED, "%u distinct keys among %u book entries", m, n);
+  *out_n = m;
+  if (m > cap) return fail(c, YDC_ERR_CAPACITY, "%u distinct keys > cap %u", m, cap);
+  const struct {
+    void* to;
+    const void* from;
+    size_t width;
+  } cols[] = {{out_servant_idx, rows.servant, 4}, {out_task_grant_id, rows.grant, 8}, {out_servant_task_id, rows.stid, 8},
+              {out_digest_key, rows.dkey, 8}, {out_count, rows.count, 4}};
+  for (const auto& k : cols)
+    if (k.to) HIP_TRY(c, hipMemcpy(k.to, k.from, m * k.width, hipMemcpyDeviceToHost));
+  return YDC_OK;
+}
+
 int ydc_stream_alive_begin(ydc_context* c, const int64_t* expires_at, uint32_t n) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
@@ -5845,6 +5966,8 @@ static void stream_tick_stage(ydc_context* c, const StreamCall& t, const TickSta
         std::memset(h.bk_dkey, 0, (size_t)n_ids * 8);
       }
       sm.book.staged.on = false;
+      // (a report replaces its servant's entries, an empty one included: the digest index is stale)
+      if (lt->n_rep) sm.book.index.valid = false;
     }
     // (the counts make the unused capacity a no-op; a tick number's low 30 bits are never 0)
     if ((++sm.lease_tick & kLeaseStamp) == 0) ++sm.lease_tick;

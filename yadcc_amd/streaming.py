@@ -180,3 +180,14 @@ def outlook_table(outlook, digest_names, env_id=None, min_version=None):
     width = [max(len(r[c]) for r in rows) for c in range(len(rows[0]))]
     return "\n".join("  ".join(cell.ljust(width[c]) if c == 0 else cell.rjust(width[c])
                                for c, cell in enumerate(r)).rstrip() for r in rows)
+
+
+def find_running(ctx, row_to_location, keys):
+    """The daemon's TryFindTask (running_task_keeper.cc:67-75) for a batch of digests, asked of an
+    open stream's book (binding.Context.stream_book_find) instead of a copy of the whole list: per
+    key (location, servant_task_id) of the servant that already compiles it — the last entry of the
+    book with that digest_key, as after a Refresh —, or None. row_to_location: per servant row its
+    location, as the scheduler keeps it. No compute: every number is the call's."""
+    hits, _ = ctx.stream_book_find(keys)
+    return [None if int(h["pos"]) == binding.BOOK_NOT_FOUND
+            else (row_to_location[int(h["servant_idx"])], int(h["servant_task_id"])) for h in hits]
