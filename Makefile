@@ -61,8 +61,14 @@ tests/native/td_linearize_gpu: tests/native/td_linearize.cc yadcc_amd/libydc.so 
 # headers that are free of HIP (no GPU).
 tsan asan flatmap shardplan:
 	$(MAKE) -s -C tests/native $@
+# The lane-choice rule of the pipelined batches (lane_rule.h) row by row, ASan + UBSan, no GPU
+# (tests/test_lane_rule.py builds and runs the same program).
+tests/native/lane_rule_test: tests/native/lane_rule_test.cc $(CSRC)/lane_rule.h
+	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tests/native/lane_rule_test.cc
+lanerule: tests/native/lane_rule_test
+	tests/native/lane_rule_test
 clean:
-	rm -f yadcc_amd/libydc.so tests/model/libmodel.so
+	rm -f yadcc_amd/libydc.so tests/model/libmodel.so tests/native/lane_rule_test
 	$(MAKE) -C tests/native clean
 	$(MAKE) -C oracle clean
-.PHONY: all lib probe oracle model native tsan asan flatmap shardplan clean
+.PHONY: all lib probe oracle model native tsan asan flatmap shardplan lanerule clean

@@ -231,6 +231,7 @@ def lib():
         L.ydc_stream_alive_removed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.ydc_stream_alive_get.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.ydc_debug_alive.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ydc_debug_pipeline.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ydc_stream_inspect_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_inspect_load.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_uint32]
         L.ydc_stream_inspect_servants.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_void_p]
@@ -289,7 +290,7 @@ def _ptr(a):
 _TUNE_KEYS = ("DEBUG_SIM", "CHUNK_SIZE", "TARGET_CHUNKS", "FUSED_CLASS", "OWN_GUESS", "PAIR", "RING_TOTAL",
               "GROUP_WALK", "WALK_PACKED", "ZONE_GUESS", "ZONE_LEAD", "ZONE_TRAIL", "ZONE_MAX_CHUNKS",
               "PACKED_CLASS", "SHARD_SORT", "BINSORT", "FUSE_PASSES", "WARM_UP",
-              "HAND_TRIES", "CP_EVERY", "WALK_PARK", "WIDE", "WIDE_LISTS", "GROUP_BINSORT",
+              "HAND_TRIES", "LANES", "CP_EVERY", "WALK_PARK", "WIDE", "WIDE_LISTS", "GROUP_BINSORT",
               "BINSORT_VERIFY", "BINSORT_MAX_SLOTS", "SHARD_MARGIN",
               "ROUNDS_PER_CHECK", "WALK_AFTER", "OUTCOME_STORE", "STREAM_GRAPH", "COMMIT_SWAP", "RELEASE_COUNTED", "SMALL_BATCH", "RESIDENT", "RESIDENT_IDLE_MS", "PACKED_TICK", "IPC_SLOT_WORDS", "IPC_TIMEOUT_MS", "IPC_COARSE")
 _tune_injected = ""
@@ -590,6 +591,13 @@ class Context:
 
     def synchronize(self):
         self._check(lib().ydc_synchronize(self._h), "ydc_synchronize")
+
+    def debug_pipeline(self):
+        """Tests and tools: (batches placed so far, pipelined batches that were enqueued on the second
+        device lane, batches dispatch_wait had to place again)."""
+        b, s, m = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(lib().ydc_debug_pipeline(self._h, C.byref(b), C.byref(s), C.byref(m)), "ydc_debug_pipeline")
+        return int(b.value), int(s.value), int(m.value)
 
     # -- multi-GPU group ---------------------------------------------------------------
     def group_init(self, unique_id, rank, n_ranks):

@@ -25,6 +25,7 @@
 #include "../../include/yadcc_dispatch.h"
 #include "dispatch_core.h"
 #include "host_tables.h"
+#include "lane_rule.h"
 #include "registry_mirror.h"
 #include "shard_plan.h"
 #include "kernels.h"
@@ -267,9 +268,46 @@ struct ydc_context {
     uint32_t* out_running = nullptr;
     PinnedAs<DeviceParams> h_outcome;  // where k_finalize stores the batch's outcome
     OwnedEvent ev;
+    LaneBatch lb;  // what the lane rule knows of it (lb.lane: the lane its launches are on)
+    uint64_t lb_epoch = 0;  // lane0_epoch when it was enqueued
   } pend[2];
   uint32_t pend_head = 0, pend_count = 0;
   uint64_t pipeline_misses = 0;
+
+  // Lane 1 (lane_rule.h): a second stream and a second instance of everything a batch writes on the
+  // device, so that a pipelined batch which does not depend on the outstanding one runs beside it
+  // instead of behind it. Made at the first batch sent there. While such a batch is enqueued
+  // (LaneScope) its members stand in the context's own — every launch site reads c->stream, c->d_prm
+  // and the workspace as ever — and the context's wait here; at any other time this is lane 1's.
+  struct Lane {
+    OwnedStream own;
+    hipStream_t stream = nullptr;
+    DevBuf<DeviceParams> d_prm;  // its own counters, latch and batch number (its granules' stamps)
+    DevBuf<uint32_t> d_slot_base, d_cls_begin, d_vals[2], d_hist, d_row_total, d_tile_first;
+    DevBuf<uint64_t> d_keys[2];
+    DevBuf<uint16_t> d_cls_by_g;
+    DevBuf<uint32_t> d_owner, d_rank_to_g;
+    DevBuf<unsigned long long> d_zone_box;
+    DevBuf<uint32_t> d_binbase, d_binruns, d_level_tab, d_row_of;
+    DevBuf<uint32_t> d_bin_tile_base, d_part_base;  // (sized with the derived tables, written by every batch)
+    DevBuf<uint64_t> d_mask;
+    DevBuf<uint32_t> d_self_lo, d_self_hi, d_chunk_consuming, d_before, d_slot_of, d_pos_last, d_chunk_tail;
+    DevBuf<uint32_t> d_running_out;
+    DevBuf<ClassState> d_guess[1], d_endst, d_checkpoint, d_early;
+    DevBuf<unsigned long long> d_claim, d_hand;
+    DevBuf<ClassRun> d_runs;
+    DevBuf<uint8_t> d_dirty;
+  };
+  std::unique_ptr<Lane> lane1;
+  bool opt_lanes = true;       // (lanes=0: every batch on lane 0)
+  // The host has seen a lane-0 batch complete since anything but a pipelined batch last used the
+  // context's stream (a registry upload or update, a release, rebuild_tables, ...): what lane 1
+  // reads of the registry and its tables is in place, with no event between the lanes.
+  // As two counts: such uses so far, and how many of them the last lane-0 batch seen complete was
+  // enqueued behind (Pending::lb_epoch). Settled when they are equal.
+  uint64_t lane0_epoch = 1, lane0_seen = 0;
+  bool lane0_settled() const { return lane0_seen == lane0_epoch; }
+  uint64_t lane1_batches = 0;  // ydc_debug_pipeline
 
   // Multi-GPU group (ydc_group_*): this context is one rank of a sharded dispatcher.
   // One way of exchanging between the ranks (an all-gather a handful of times per matching pass,
@@ -676,6 +714,9 @@ struct BatchCall {
   bool pipelined = false;
   DeviceParams* outcome = nullptr;
   bool by_swap = false;
+  // ydc_dispatch_wait placing a batch again after it has drained both lanes: a batch that is still
+  // to be collected from the other lane is complete and not in the way.
+  bool replay = false;
   bool staged() const { return host_in.tk || post_copy.bytes; }
 };
 
@@ -896,6 +937,87 @@ void mark(ydc_context* c, int stage) {
   if (c->profiling) (void)hipEventRecord(c->ev[stage], c->stream);
 }
 
+// ---- lanes (lane_rule.h; ydc_context::Lane) ----
+
+// The one list of what belongs to a lane: f(the context's member, lane 1's).
+template <typename F>
+void lane_pairs(ydc_context* c, ydc_context::Lane& l, F f) {
+  f(c->d_prm, l.d_prm);
+  f(c->d_slot_base, l.d_slot_base), f(c->d_cls_begin, l.d_cls_begin), f(c->d_vals[0], l.d_vals[0]);
+  f(c->d_vals[1], l.d_vals[1]), f(c->d_hist, l.d_hist), f(c->d_row_total, l.d_row_total);
+  f(c->d_tile_first, l.d_tile_first), f(c->d_keys[0], l.d_keys[0]), f(c->d_keys[1], l.d_keys[1]);
+  f(c->d_cls_by_g, l.d_cls_by_g), f(c->d_owner, l.d_owner), f(c->d_rank_to_g, l.d_rank_to_g);
+  f(c->d_zone_box, l.d_zone_box), f(c->d_binbase, l.d_binbase), f(c->d_binruns, l.d_binruns);
+  f(c->d_level_tab, l.d_level_tab), f(c->d_row_of, l.d_row_of), f(c->d_bin_tile_base, l.d_bin_tile_base);
+  f(c->d_part_base, l.d_part_base), f(c->d_mask, l.d_mask), f(c->d_self_lo, l.d_self_lo);
+  f(c->d_self_hi, l.d_self_hi), f(c->d_chunk_consuming, l.d_chunk_consuming), f(c->d_before, l.d_before);
+  f(c->d_slot_of, l.d_slot_of), f(c->d_pos_last, l.d_pos_last), f(c->d_chunk_tail, l.d_chunk_tail);
+  f(c->d_running_out, l.d_running_out), f(c->d_guess[0], l.d_guess[0]), f(c->d_endst, l.d_endst);
+  f(c->d_checkpoint, l.d_checkpoint), f(c->d_early, l.d_early), f(c->d_claim, l.d_claim);
+  f(c->d_hand, l.d_hand), f(c->d_runs, l.d_runs), f(c->d_dirty, l.d_dirty);
+}
+
+// Lane 1, made at its first batch, with what the context sizes outside plan_batch (by the registry
+// and its tables: reserve_registry, rebuild_tables, ydc_create) as large as lane 0's. Everything
+// else plan_batch reserves under the LaneScope, the zeroed stamp arrays included.
+int lane1_prepare(ydc_context* c) {
+  if (!c->lane1) {
+    auto l = std::make_unique<ydc_context::Lane>();
+    HIP_TRY(c, l->own.create());
+    l->stream = l->own;
+    HIP_TRY(c, l->d_prm.reserve(1));
+    HIP_TRY(c, hipMemsetAsync(l->d_prm.p, 0, sizeof(DeviceParams), l->stream));  // batch_seq starts at 0
+    c->lane1 = std::move(l);
+  }
+  ydc_context::Lane& l = *c->lane1;
+  HIP_TRY(c, l.d_slot_base.reserve(c->d_slot_base.cap));
+  HIP_TRY(c, l.d_pos_last.reserve(c->d_pos_last.cap));
+  HIP_TRY(c, l.d_running_out.reserve(c->d_running_out.cap));
+  HIP_TRY(c, l.d_cls_begin.reserve(c->d_cls_begin.cap));
+  HIP_TRY(c, l.d_bin_tile_base.reserve(c->d_bin_tile_base.cap));
+  HIP_TRY(c, l.d_part_base.reserve(c->d_part_base.cap));
+  HIP_TRY(c, l.d_row_total.reserve(c->d_row_total.cap));
+  return YDC_OK;
+}
+
+// For the length of one enqueue, lane `lane`'s stream, workspace and params are the context's
+// current ones (lane 0: nothing to do, and nothing done).
+struct LaneScope {
+  ydc_context* c;
+  bool on;
+  static void exchange(ydc_context* c) {
+    ydc_context::Lane& l = *c->lane1;
+    std::swap(c->stream, l.stream);
+    lane_pairs(c, l, [](auto& mine, auto& theirs) { std::swap(mine, theirs); });
+  }
+  LaneScope(ydc_context* ctx, uint32_t lane) : c(ctx), on(lane == 1) {
+    if (on) exchange(c);
+  }
+  ~LaneScope() {
+    if (on) exchange(c);
+  }
+  LaneScope(const LaneScope&) = delete;
+  LaneScope& operator=(const LaneScope&) = delete;
+};
+
+bool lane1_busy(const ydc_context* c) {
+  for (const auto& pd : c->pend)
+    if (pd.active && !pd.rerun && pd.lb.lane == 1) return true;
+  return false;
+}
+
+// First in every entry point that takes the context's stream to order it behind the outstanding
+// batches (all but ydc_dispatch_device_async, ydc_dispatch_wait, ydc_get_stats, ydc_last_error):
+// waits for lane 1 where it has a batch in flight. What follows may write what lane 1 reads, on the
+// context's stream: the next batches stay on lane 0 until one of them has been seen complete.
+void join_lanes(ydc_context* c) {
+  ++c->lane0_epoch;
+  if (c->lane1 && lane1_busy(c)) {
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->lane1->stream);
+  }
+}
+
 // Brackets one kernel launch with events when profiling is on.
 struct KernelTimer {
   ydc_context* c;
@@ -1067,6 +1189,7 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
   if (const char* s = tune_value("fuse_passes")) c->opt_fuse_passes = atoi(s) != 0;
   if (const char* s = tune_value("warm_up")) c->opt_warm_up = (uint32_t)std::min(64, std::max(1, atoi(s)));
   if (const char* s = tune_value("hand_tries")) c->opt_hand_tries = (uint32_t)std::max(0, atoi(s));
+  if (const char* s = tune_value("lanes")) c->opt_lanes = atoi(s) != 0;
   if (const char* s = tune_value("cp_every")) {
     uint32_t v = (uint32_t)std::max(1, atoi(s)), p2 = 1;
     while (p2 * 2 <= v && p2 < 1024) p2 *= 2;
@@ -1095,6 +1218,7 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
 int ydc_destroy(ydc_context* c) {
   if (!c) return YDC_OK;
   (void)hipSetDevice(c->device);
+  join_lanes(c);
   resident_stop(c);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   stream_release(c);
@@ -1112,6 +1236,7 @@ int ydc_upload_servants(ydc_context* c, const ydc_servant_soa* sv, uint32_t n) {
   if (c->max_servants && n > c->max_servants)
     return fail(c, YDC_ERR_CAPACITY, "%u servants > max_servants %u", n, c->max_servants);
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (released slots may still be on their way)
   if (int rc = reserve_registry(c, n)) return rc;
@@ -1134,6 +1259,7 @@ int ydc_update_servants_wide(ydc_context* c, const uint32_t* idx, const ydc_serv
     return fail(c, YDC_ERR_INVALID_ARGUMENT,
                 "the table holds %u mask words per servant: use ydc_update_servants_wide", c->reg.env_words);
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   // Appends first (they may need bigger buffers).
   uint32_t new_n = c->reg.n;
@@ -1196,6 +1322,7 @@ int ydc_set_host_aliases(ydc_context* c, const uint32_t* ip_id, const uint32_t* 
     if (servant_idx[i] >= c->reg.n)
       return fail(c, YDC_ERR_INVALID_ARGUMENT, "alias %u names servant %u of %u", i, servant_idx[i], c->reg.n);
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->reg.alias_ip.assign(ip_id, ip_id + n);  // (n == 0: none)
@@ -1209,6 +1336,7 @@ int ydc_set_host_aliases(ydc_context* c, const uint32_t* ip_id, const uint32_t* 
 // cannot set them again in the middle of a tick).
 static int remove_rows(ydc_context* c, const uint32_t* idx, uint32_t n, bool in_tick) {
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   const uint32_t S = c->reg.n, kept = S - n;
   auto& sm = c->stream_mode;
@@ -1311,6 +1439,7 @@ int ydc_release_slots(ydc_context* c, const uint32_t* servant_idx, uint32_t n) {
   if (!c || (n && !servant_idx)) return YDC_ERR_INVALID_ARGUMENT;
   if (!n) return YDC_OK;
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, c->d_upd_idx.reserve(n));
   // Through a pinned staging buffer, stream-ordered: no wait here (the next batch follows on
@@ -1331,6 +1460,7 @@ int ydc_release_slots_device(ydc_context* c, const uint32_t* d_servant_idx, uint
   if (!c || (n && !d_servant_idx)) return YDC_ERR_INVALID_ARGUMENT;
   if (!n) return YDC_OK;
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   launch_release(c, d_servant_idx, n);
   HIP_TRY(c, hipGetLastError());
@@ -1340,6 +1470,7 @@ int ydc_release_slots_device(ydc_context* c, const uint32_t* d_servant_idx, uint
 int ydc_set_running(ydc_context* c, const uint32_t* running, uint32_t n) {
   if (!c || n != c->reg.n || (n && !running)) return YDC_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (released slots may still be on their way)
   if (n) HIP_TRY(c, hipMemcpy(c->d_running.p, running, n * 4, hipMemcpyHostToDevice));
@@ -1349,6 +1480,7 @@ int ydc_set_running(ydc_context* c, const uint32_t* running, uint32_t n) {
 int ydc_get_running(ydc_context* c, uint32_t* out, uint32_t n) {
   if (!c || n != c->reg.n || (n && !out)) return YDC_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   HIP_TRY(c, hipStreamSynchronize(c->stream));  // (released slots may still be on their way)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2778,7 +2910,7 @@ int tick_run(ydc_context* c, const TickCall& io) {
 int dispatch_batch(ydc_context* c, const ydc_task_soa* tk, uint32_t N, const BatchCall& call) {
   if (c->max_tasks && N > c->max_tasks)
     return fail(c, YDC_ERR_CAPACITY, "%u tasks > max_tasks %u", N, c->max_tasks);
-  if (c->pend_count && !c->pend[c->pend_head].rerun && c->pend[c->pend_head].active)
+  if (c->pend_count && !c->pend[c->pend_head].rerun && c->pend[c->pend_head].active && !call.replay)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "pipelined batches outstanding: ydc_dispatch_wait first");
   HIP_TRY(c, hipSetDevice(c->device));
   if (N && N <= c->small_batch() && call.out_idx && !call.staged()) {
@@ -2819,8 +2951,19 @@ extern "C" {
 int ydc_dispatch_device(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t flags,
                         uint32_t* d_out_idx, double* d_out_util, uint32_t* d_out_running) {
   if (!c || (N && !tk)) return YDC_ERR_INVALID_ARGUMENT;
+  join_lanes(c);
   return dispatch_batch(c, tk, N, batch_call(c, flags, d_out_idx, d_out_util, d_out_running, c->h_prm.dev()));
 }
+
+namespace {
+// A pipelined batch whose event has completed: it took no effect (not final within its launches,
+// a bin sort's window missed, the latch of its lane was set, or its slots overflowed).
+bool outcome_missed(const ydc_context::Pending& pd) {
+  const DeviceParams& o = *pd.h_outcome.get();
+  return o.overflow || o.pipeline_broken || (pd.plan.binsort && o.window_miss) ||
+         o.n_changed[(pd.launched - 1) & 63] != 0;
+}
+}  // namespace
 
 // Pipelined form of ydc_dispatch_device: enqueues the whole batch (front, the matching passes the
 // last batches needed, the gated finalise, the outcome read-back) and returns; the host looks at
@@ -2828,7 +2971,8 @@ int ydc_dispatch_device(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint
 // the device does not idle while the host turns around. Exact whatever happens: a batch that is
 // not final within its pre-launched passes (or whose bins overflowed) takes no effect, latches
 // DeviceParams::pipeline_broken so that the batch behind it takes none either, and both are
-// replayed in order by ydc_dispatch_wait.
+// replayed in order by ydc_dispatch_wait. A batch that does not depend on the outstanding one is
+// enqueued on the other lane and runs beside it (lane_rule.h).
 int ydc_dispatch_device_async(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t flags,
                               uint32_t* d_out_idx, double* d_out_util, uint32_t* d_out_running) {
   if (!c || (N && !tk)) return YDC_ERR_INVALID_ARGUMENT;
@@ -2849,8 +2993,44 @@ int ydc_dispatch_device_async(ydc_context* c, const ydc_task_soa* tk, uint32_t N
   pd.out_util = d_out_util;
   pd.out_running = d_out_running;
   pd.launched = 0;
+  // Which lane (lane_rule.h). Whether the plan will take the enqueued path below is known from
+  // the tables: plan_batch must already run under the lane's scope, its views are the lane's.
+  ydc_context::Pending* const ahead = c->pend_count == 1 ? &c->pend[c->pend_head] : nullptr;
+  const uint32_t n_cls = c->tables_dirty ? 0u : c->tables.n_classes();
+  pd.lb = LaneBatch{};
+  pd.lb_epoch = c->lane0_epoch;
+  pd.lb.commit = (flags & YDC_DISPATCH_COMMIT) != 0;
+  pd.lb.enqueued = !(ahead && ahead->rerun) && N && n_cls && n_cls <= kMaxWaveClasses && !c->profiling &&
+                   !c->debug_verify_binsort;
+  pd.lb.out[0] = LaneOutput{d_out_idx, (size_t)N * 4};
+  pd.lb.out[1] = LaneOutput{d_out_util, (size_t)N * 8};
+  pd.lb.out[2] = LaneOutput{d_out_running, (size_t)c->reg.n * 4};
+  LaneChoice lane;
+  if (ahead) {
+    ahead->lb.enqueued = !ahead->rerun;
+    const LaneContext lc{c->opt_lanes, c->own_stream.s != nullptr, c->group.n_ranks != 0 || c->group.via != nullptr,
+                         c->stream_mode.active, c->lane0_settled()};
+    lane = lane_for(lc, &ahead->lb, pd.lb);
+  }
+  if (lane.wait_first) {
+    // Behind a batch on lane 1 without an event between the lanes: the host waits for it. If it
+    // took no effect, neither may this one (on lane 0 it does not see lane 1's latch): both are
+    // replayed in order by ydc_dispatch_wait.
+    if (hipEventSynchronize(ahead->ev) != hipSuccess) {
+      pd.active = false;
+      return fail(c, YDC_ERR_HIP, "could not wait for the batch on the second lane");
+    }
+    if (outcome_missed(*ahead)) ahead->rerun = true;
+  }
+  if (lane.lane == 1)
+    if (int rc = lane1_prepare(c)) {
+      pd.active = false;
+      return rc;
+    }
+  pd.lb.lane = lane.lane;
+  const LaneScope scope(c, lane.lane);
   // A batch behind one that already has to be replayed is not worth enqueueing.
-  const bool behind_rerun = c->pend_count == 1 && c->pend[c->pend_head].rerun;
+  const bool behind_rerun = ahead && ahead->rerun;
   // A batch that cannot be enqueued completely is not outstanding: nothing of it can take effect
   // without its finalise, which is enqueued last; the slot is free again.
   auto give_up = [&](int rc) {
@@ -2861,6 +3041,7 @@ int ydc_dispatch_device_async(ydc_context* c, const ydc_task_soa* tk, uint32_t N
   if (behind_rerun || !pd.plan.wave_path || c->profiling || c->debug_verify_binsort) {
     // (registries without the wave path have host-checked rounds: placed when waited for)
     pd.rerun = true;
+    pd.lb.lane = 0;
   } else {
     // (the outcome block: stored by k_finalize's last servant workgroup; a registry without
     // servants has none, then it is read back with a copy)
@@ -2883,6 +3064,7 @@ int ydc_dispatch_device_async(ydc_context* c, const ydc_task_soa* tk, uint32_t N
       (void)hipStreamSynchronize(c->stream);
       return give_up(fail(c, YDC_ERR_HIP, "could not enqueue the outcome read-back of a pipelined batch"));
     }
+    if (lane.lane == 1) ++c->lane1_batches;
   }
   ++c->pend_count;
   return YDC_OK;
@@ -2899,6 +3081,19 @@ int ydc_dispatch_wait(ydc_context* c) {
     c->pend_head ^= 1;
     --c->pend_count;
   };
+  // Both lanes idle and the latch of this batch's lane cleared; the batch behind it on the same
+  // lane took no effect either and is replayed when it is waited for. One on the other lane was
+  // enqueued as independent of this one: it has taken effect validly and stays as it is.
+  auto drain = [&]() -> int {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->lane1) HIP_TRY(c, hipStreamSynchronize(c->lane1->stream));
+    const bool second = pd.lb.lane == 1 && c->lane1;
+    HIP_TRY(c, hipMemsetAsync(&(second ? c->lane1->d_prm : c->d_prm).p->pipeline_broken, 0, 4,
+                              second ? c->lane1->stream : c->stream));
+    auto& behind = c->pend[c->pend_head ^ 1];
+    if (c->pend_count == 2 && behind.lb.lane == pd.lb.lane) behind.rerun = true;
+    return YDC_OK;
+  };
   bool miss = pd.rerun;
   uint32_t rounds = 0;
   if (!miss) {
@@ -2909,9 +3104,7 @@ int ydc_dispatch_wait(ydc_context* c) {
       // pipelined batches), so the batch behind it has not taken any either: drain, clear the
       // latch, leave that batch to be replayed when it is waited for, report this one.
       const uint32_t bound = pd.plan.slot_bound;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      HIP_TRY(c, hipMemsetAsync(&c->d_prm.p->pipeline_broken, 0, 4, c->stream));
-      if (c->pend_count == 2) c->pend[c->pend_head ^ 1].rerun = true;
+      if (int rc = drain()) return rc;
       pop();
       return fail(c, YDC_ERR_CAPACITY, "slot workspace overflow (bound %u)", bound);
     }
@@ -2927,30 +3120,34 @@ int ydc_dispatch_wait(ydc_context* c) {
       c->round_hint = rounds;
       zone_feedback(c, pd.plan, o, rounds);
       fill_stats(c, pd.plan, rounds);
+      if (pd.lb.lane == 0) c->lane0_seen = pd.lb_epoch;
       pop();
       return YDC_OK;
     }
   }
   // Not final in the pipeline (or never enqueued): nothing of this batch — nor of the one behind
-  // it — has taken effect. Drain, clear the latch, place it the synchronous way; the batch
-  // behind it is replayed when it is waited for.
+  // it on its lane — has taken effect. Drain, clear the latch, place it the synchronous way; the
+  // batch behind it is replayed when it is waited for.
   ++c->pipeline_misses;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemsetAsync(&c->d_prm.p->pipeline_broken, 0, 4, c->stream));
-  if (c->pend_count == 2) c->pend[c->pend_head ^ 1].rerun = true;
+  if (int rc = drain()) return rc;
   const ydc_task_soa tk = pd.tk;
   const uint32_t n = pd.n, flags = pd.flags;
   uint32_t* oi = pd.out_idx;
   double* ou = pd.out_util;
   uint32_t* orun = pd.out_running;
   pop();
-  return ydc_dispatch_device(c, &tk, n, flags, oi, ou, orun);
+  BatchCall call = batch_call(c, flags, oi, ou, orun, c->h_prm.dev());
+  call.replay = true;
+  const int rc = dispatch_batch(c, &tk, n, call);
+  if (rc == YDC_OK) c->lane0_seen = c->lane0_epoch;  // (placed and complete, on lane 0)
+  return rc;
 }
 
 int ydc_dispatch(ydc_context* c, const ydc_task_soa* tk, uint32_t N, uint32_t flags,
                  uint32_t* out_idx, double* out_util, uint32_t* out_running) {
   if (!c || (N && (!tk || !out_idx))) return YDC_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   const bool same = N <= kTickBlock && tick_same_requests(tk, N);
   if (N && N <= c->small_batch(same)) {
     // A handful of requests: one launch of the one-workgroup kernel, the requests as kernel
@@ -3041,6 +3238,7 @@ int ydc_dispatch_tick(ydc_context* c, const uint32_t* upd_idx, const ydc_servant
   if (!c || (n_upd && (!upd_idx || !upd_rows)) || (n_rel && !release_servant_idx) ||
       (n_tasks && (!tasks || !out_servant_idx)))
     return YDC_ERR_INVALID_ARGUMENT;
+  join_lanes(c);
   if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "pipelined batches outstanding: ydc_dispatch_wait first");
   if (c->max_tasks && n_tasks > c->max_tasks)
     return fail(c, YDC_ERR_CAPACITY, "%u tasks > max_tasks %u", n_tasks, c->max_tasks);
@@ -3531,6 +3729,7 @@ void group_release(ydc_context* c) {
 enum class GroupKeep { kNothing, kExport, kGroup };
 int group_enter(ydc_context* c, GroupKeep keep) {
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);
   if (keep == GroupKeep::kGroup) return YDC_OK;
   if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -4792,6 +4991,7 @@ int stream_begin(ydc_context* c, const ydc_stream_caps& k) {
   if (!c || !k.max_tasks) return YDC_ERR_INVALID_ARGUMENT;
   if (int rc = stream_caps_check(c, YDC_ERR_CAPACITY, k, 0)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   stream_release(c);
   if (int rc = stream_alloc(c, c->stream_mode, k, 0)) return rc;
@@ -5541,6 +5741,7 @@ int ydc_stream_buffers_get(ydc_context* c, ydc_stream_buffers* out) {
 int ydc_stream_end(ydc_context* c) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipSetDevice(c->device));
+  join_lanes(c);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   stream_release(c);
   return YDC_OK;
@@ -6562,12 +6763,24 @@ extern "C" {
 
 int ydc_synchronize(ydc_context* c) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  join_lanes(c);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return YDC_OK;
+}
+
+// For the tests (not declared in the header): batches placed so far, how many of the pipelined
+// ones were enqueued on the second lane, and how many ydc_dispatch_wait had to place again.
+int ydc_debug_pipeline(ydc_context* c, uint64_t* out_batches, uint64_t* out_on_second_lane, uint64_t* out_misses) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (out_batches) *out_batches = c->pipeline_batches;
+  if (out_on_second_lane) *out_on_second_lane = c->lane1_batches;
+  if (out_misses) *out_misses = c->pipeline_misses;
   return YDC_OK;
 }
 
 int ydc_set_profiling(ydc_context* c, int on) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  join_lanes(c);
   c->profiling = on != 0;
   return YDC_OK;
 }
