@@ -1523,7 +1523,11 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
   p.any_shared = c->tables.any_shared_ip;
   p.use_generic = p.C > kMaxWaveClasses;
   p.wave_path = N && p.C && !p.use_generic;
-  p.cs = c->opt_chunk_size;
+  // A tuned size in whole blocks of 64 requests, like every automatic one: checkpoints are kept
+  // per block ((kc * cs) >> 6 names a chunk's first), the chunks' tails are counted by the block
+  // that ends them, and the walk of the tier's end steps through blocks and records its rows at
+  // t_start + j * cs (zone_guess.h) — with 96 it would publish row j at another chunk's request.
+  p.cs = (c->opt_chunk_size + 63u) & ~63u;
   if (p.cs == 0) {
     uint32_t want = ceil_div(std::max<uint32_t>(N, 1), std::max<uint32_t>(1, c->opt_target_chunks));
     p.cs = 64;

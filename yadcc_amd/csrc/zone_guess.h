@@ -18,8 +18,9 @@
 // its own servant at a head picks differently once in thousands of picks; the guesses need to be
 // close, not exact — every start state is verified by the passes as before). Started a couple of
 // chunks before the tier's end from the level guess of that point, it is on the true track within
-// a chunk (numpy restatement on cfg3: no deviation at any chunk boundary of the stretch, where
-// the level guesses are off by up to 149 positions) and publishes the class cursors at the points
+// a chunk (tests/guess_edge_cases.py restates this walk in Python, zone_restate; the tests beside it
+// hold its rows and this kernel's to the cursors the oracle's placement implies, on pools whose
+// level guesses are off by up to 82 positions) and publishes the class cursors at the points
 // where the stretch's chunks start their replays, as 8-byte granules {cursor, batch number}: a
 // chunk of the stretch (the header granules say which chunks those are) waits for its row
 // instead of starting from its level guess — the sequential part of the batch runs while the
@@ -45,8 +46,19 @@ __device__ __forceinline__ void zone_walk(const ClassLists& L, const uint64_t* m
                                           DeviceParams* prm, uint32_t* zwin, uint32_t ring_total) {
 #ifdef YDC_PHASE_PROBE
 #define YDC_ZSTAMP(i) do { if (threadIdx.x == 0) ydc_phase_probe[59990 + (i)] = wall_clock64(); } while (0)
+// (words 60000 .. 60003: T0, z_lo, z_hi, t_start — at every way out, so that "no zone" is visible too)
+#define YDC_ZHEAD(t0, zl, zh, ts)                                                     \
+  do {                                                                                \
+    if (threadIdx.x == 0) {                                                           \
+      ydc_phase_probe[60000] = (t0);                                                  \
+      ydc_phase_probe[60001] = (zl);                                                  \
+      ydc_phase_probe[60002] = (zh);                                                  \
+      ydc_phase_probe[60003] = (ts);                                                  \
+    }                                                                                 \
+  } while (0)
 #else
 #define YDC_ZSTAMP(i) do { } while (0)
+#define YDC_ZHEAD(t0, zl, zh, ts) do { } while (0)
 #endif
   YDC_ZSTAMP(0);
   __builtin_amdgcn_s_setprio(3);  // (the batch waits for this wave: first on its SIMD)
@@ -57,6 +69,7 @@ __device__ __forceinline__ void zone_walk(const ClassLists& L, const uint64_t* m
     if (lane < 2) zone_put(box + lane, 0u, seq);
   };
   const uint32_t M = prm->n_slots;
+  YDC_ZHEAD(0xFFFFFFFFu, 0u, 0u, 0u);  // (T0 not looked for yet)
   if (M == 0 || K < 2 || L.list_p == nullptr || B.before == nullptr || C == 0) return no_zone();
   // ---- T0: the first slot of tier 1 in the global order (64 probes per round)
   uint32_t lo = 0, hi = M;  // T0 in [lo, hi]; hi == M or the slot at hi is tier 1
@@ -78,6 +91,7 @@ __device__ __forceinline__ void zone_walk(const ClassLists& L, const uint64_t* m
   }
   const uint32_t T0 = lo;
   YDC_ZSTAMP(1);
+  YDC_ZHEAD(T0, 0u, 0u, 0u);
   if (T0 == 0 || T0 >= M) return no_zone();  // one tier only
   // ---- the zone's first chunk: the first whose level is within `lead` of T0
   const uint32_t from = T0 > B.zone_lead ? T0 - B.zone_lead : 0u;
@@ -116,6 +130,7 @@ __device__ __forceinline__ void zone_walk(const ClassLists& L, const uint64_t* m
     prm->zone_rows = z_hi - z_lo;  // (the host: did the chunks that were served come out consistent?)
   }
   YDC_ZSTAMP(2);
+  YDC_ZHEAD(T0, z_lo, z_hi, z_lo * cs - warm);
   if (z_hi - z_lo < 2) return;  // (row 0 is the chunk's own level guess: nobody waits for anything)
   // ---- start: the level guess of the point where chunk z_lo's replay starts
   const uint32_t t_start = z_lo * cs - warm;
@@ -240,14 +255,6 @@ __device__ __forceinline__ void zone_walk(const ClassLists& L, const uint64_t* m
     x += ((an - an0) & ((ring << 2) - 1)) >> 2;  // this class's wins in the block
   }
   YDC_ZSTAMP(5);
-#ifdef YDC_PHASE_PROBE
-  if (lane == 0) {
-    ydc_phase_probe[60000] = T0;
-    ydc_phase_probe[60001] = z_lo;
-    ydc_phase_probe[60002] = z_hi;
-    ydc_phase_probe[60003] = t_start;
-  }
-#endif
 }
 
 }  // namespace ydc
