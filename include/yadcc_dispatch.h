@@ -31,6 +31,10 @@ extern "C" {
  * in the context's queue and is answered in a later tick's resolved list. No registry index
  * ever has this value. */
 #define YDC_IDX_WAITING 0xFFFFFFFDu
+/* Streams with withdrawal only (ydc_stream_withdraw_begin): the waiting request was taken out of the
+ * queue by its tag. Only ever in a resolved list / an rpc resolved status. No registry index ever
+ * has this value: ydc_create refuses a max_servants above it. */
+#define YDC_IDX_WITHDRAWN 0xFFFFFFFCu
 
 /* ---- error codes ---------------------------------------------------------- */
 #define YDC_OK 0
@@ -769,6 +773,54 @@ int ydc_stream_inspect_waiting(ydc_context* ctx, uint64_t* out_tag, uint32_t* ou
                                int64_t* out_lease_for, uint32_t* out_n_immediate, uint32_t* out_n_prefetch,
                                uint32_t cap, uint32_t* out_n);
 
+/* ---- withdrawal: waiting requests taken out of W by tag, inside the tick ------------------------
+ * A blocked WaitForStartingTask call whose client went away (connection dropped, daemon restarted,
+ * build interrupted) would otherwise stay in W until its deadline, be retried every tick and, if
+ * granted, hold a slot, a task id and a lease nobody renews. The host keeps no list of waiters and
+ * cannot know between ticks whether the next one grants the entry, so the tick itself takes it out,
+ * before W is retried. Opt-in, like the book and aliveness; the write-side counterpart of
+ * ydc_stream_inspect_waiting. The reference has no such call: its waiter sleeps until max_wait. In
+ * its terms a withdrawn call is a call whose max_wait ended in this tick.
+ *   ydc_stream_withdraw_begin: switches the capability on, for the open waiting, waiting-and-leased
+ *     or rpc stream, with room for max_withdraw tags per tick; a later call with a larger
+ *     max_withdraw grows it; a smaller or equal one returns YDC_OK and does nothing (the captured
+ *     step stays). An effective call allocates a second set of the stream's buffers, copies, then
+ *     swaps, all or nothing as ydc_stream_book_begin does (pointers of ydc_stream_buffers_get change),
+ *     and the step is captured again at the next tick. No such stream open, a plain or leased-only
+ *     stream, max_withdraw == 0 or max_withdraw > 2^30: YDC_ERR_INVALID_ARGUMENT. ydc_stream_end
+ *     and the next begin call switch it off; ydc_stream_reserve and ydc_stream_book_begin carry it
+ *     over, max_withdraw unchanged; ydc_stream_restore leaves it off, like inspection (the blob says
+ *     nothing about it).
+ *   ydc_stream_withdraw_stage: the tags for the NEXT accepted tick, unsorted, repeats allowed.
+ *     Staging again replaces the previous staging; n == 0 clears it. n > max_withdraw:
+ *     YDC_ERR_CAPACITY; the capability off: YDC_ERR_INVALID_ARGUMENT. A refused tick leaves the
+ *     staging in place, an accepted tick consumes it. ydc_stream_snapshot is refused while one is
+ *     pending. ydc_stream_waiting_take leaves a pending staging alone (it then finds nothing in W).
+ *   In the tick, before the queue's expiry step (step 2 of a waiting tick, step 7 of a
+ *     waiting-and-leased or rpc tick): every entry of W as the tick found it whose tag is staged
+ *     leaves W, untried, whether or not its deadline has passed (withdrawal wins over expiry). It
+ *     consumes nothing: no slot, no task id, no lease, no inspection record, no ever_assigned count.
+ *     It appears in the resolved list at its queue position among the other resolved entries:
+ *     (tag, YDC_IDX_WITHDRAWN) with the task id undefined; in rpc mode status YDC_IDX_WITHDRAWN,
+ *     n_granted 0 and `first` as for any entry without grants. *out_n_waiting and
+ *     *out_n_waiting_rows reflect the removal. A NEW request of the same tick that carries a staged
+ *     tag is not withdrawn: it may queue, and can be withdrawn from the next tick on. Tags need not
+ *     be unique: every entry with a staged tag goes.
+ *     Apart from the label YDC_IDX_WITHDRAWN, the tick and all later ticks are exactly those of a
+ *     stream in which the withdrawn entries' deadlines had been <= now in this tick.
+ *   ydc_stream_withdraw_result: about the most recent accepted tick. *out_n: the tags staged for it
+ *     (0: none); out_count[i]: the entries removed for the caller's i-th staged tag, in the caller's
+ *     order (a tag staged twice reports the same count twice); *out_n_withdrawn (nullable): the
+ *     entries removed, each counted once. cap < *out_n: YDC_ERR_CAPACITY with *out_n set and nothing
+ *     written. A count of 0: the call was answered already or was never queued; its answer (a grant
+ *     with its task id included, to be freed by id as usual) is in that or an earlier tick's results.
+ *   No tick signature changes; a stream that never calls ydc_stream_withdraw_begin launches what
+ *     it launched before. ydc_get_stats keeps its layout. */
+int ydc_stream_withdraw_begin(ydc_context* ctx, uint32_t max_withdraw);
+int ydc_stream_withdraw_stage(ydc_context* ctx, const uint64_t* tags, uint32_t n);
+int ydc_stream_withdraw_result(ydc_context* ctx, uint32_t* out_count, uint32_t cap, uint32_t* out_n,
+                               uint32_t* out_n_withdrawn);
+
 /* ---- snapshot and restore of an open stream --------------------------------------------
  * Everything an open waiting, leased, waiting-and-leased or rpc stream keeps on the device (L with
  * next_id and the report stamps, W, B, E, running_tasks, the registry's columns, the clock and the
@@ -781,8 +833,8 @@ int ydc_stream_inspect_waiting(ydc_context* ctx, uint64_t* out_tag, uint32_t* ou
  *   - ydc_stream_snapshot: between ticks. cap too small: YDC_ERR_CAPACITY, *out_bytes the size
  *     needed, nothing written (out may be NULL then). Refused with YDC_ERR_INVALID_ARGUMENT: no
  *     stream open, a plain ydc_stream_begin stream (it keeps no state on the device), a context in
- *     a group, pipelined batches outstanding, a ydc_stream_book_stage or ydc_stream_alive_stage
- *     that no tick has consumed yet. The stream is not changed.
+ *     a group, pipelined batches outstanding, a ydc_stream_book_stage, ydc_stream_alive_stage or
+ *     ydc_stream_withdraw_stage that no tick has consumed yet. The stream is not changed.
  *   - ydc_stream_restore: ctx becomes what the snapshotted context was: registry (as by
  *     ydc_upload_servants), running_tasks, host aliases and the open stream. Its bounds are
  *     max(blob's, *want) field by field (want may be NULL); a want that names a part the blob's
@@ -856,7 +908,9 @@ int ydc_set_profiling(ydc_context* ctx, int on);
 int ydc_get_stats(const ydc_context* ctx, ydc_stats* out);
 /* Profiling on: per-kernel totals of the most recent dispatch, measured with HIP
  * events on the context stream, as JSON {"kernel": [launches, total_ms], ...}.
- * The string lives until the next dispatch. */
+ * The string lives until the next dispatch. A streaming tick that is enqueued eagerly (a
+ * registry above 256 classes) reports its launches too, from the batch's front on; a replayed
+ * step leaves the string as it was. */
 const char* ydc_kernel_profile(const ydc_context* ctx);
 
 

@@ -20,6 +20,7 @@ TRANSPORT_NAMES = ("none", "rccl", "local", "ipc", "ipc-host")
 IDX_TIMEOUT = 0xFFFFFFFF
 IDX_ENV_NOT_FOUND = 0xFFFFFFFE
 IDX_WAITING = 0xFFFFFFFD  # streaming waiting mode: queued on the device, answered in a later tick
+IDX_WITHDRAWN = 0xFFFFFFFC  # resolved lists only: the waiting request was withdrawn by its tag
 INSPECT_NO_ID = 0xFFFFFFFF  # env_id / requestor_ip of a lease granted while inspection was off
 INSPECT_NO_TIME = -(1 << 63)  # ... its started_at
 OUTLOOK_UNKNOWN = 0xFFFFFFFF  # leases / zombies of an outlook row while inspection is off
@@ -48,6 +49,7 @@ ABI_SYMBOLS = (
     "ydc_stream_alive_begin", "ydc_stream_alive_stage", "ydc_stream_alive_removed", "ydc_stream_alive_get",
     "ydc_stream_inspect_begin", "ydc_stream_inspect_load", "ydc_stream_inspect_servants", "ydc_stream_inspect_tasks",
     "ydc_stream_outlook_get", "ydc_stream_inspect_waiting",
+    "ydc_stream_withdraw_begin", "ydc_stream_withdraw_stage", "ydc_stream_withdraw_result",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
@@ -238,6 +240,9 @@ def lib():
         L.ydc_stream_inspect_tasks.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
         L.ydc_stream_outlook_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.ydc_stream_inspect_waiting.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
+        L.ydc_stream_withdraw_begin.argtypes = [C.c_void_p, C.c_uint32]
+        L.ydc_stream_withdraw_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ydc_stream_withdraw_result.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.ydc_stream_book_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1172,6 +1177,31 @@ class Context:
         self._check(lib().ydc_stream_inspect_waiting(self._h, *[_ptr(a) for a in cols.values()], cap, C.byref(n)),
                     "ydc_stream_inspect_waiting")
         return {k: a[:n.value].copy() for k, a in cols.items()}
+
+    def stream_withdraw_begin(self, max_withdraw):
+        """Switches withdrawal by tag on for the open waiting, waiting-and-leased or rpc stream, or
+        grows it (ydc_stream_withdraw_begin): room for max_withdraw tags per tick."""
+        self._check(lib().ydc_stream_withdraw_begin(self._h, int(max_withdraw)), "ydc_stream_withdraw_begin")
+
+    def stream_withdraw_stage(self, tags):
+        """The tags whose waiting requests the next accepted tick takes out of the queue, answered as
+        IDX_WITHDRAWN in its resolved list (ydc_stream_withdraw_stage); an empty list clears."""
+        t = np.ascontiguousarray(tags, dtype=np.uint64)
+        self._check(lib().ydc_stream_withdraw_stage(self._h, _ptr(t) if len(t) else None, len(t)),
+                    "ydc_stream_withdraw_stage")
+
+    def stream_withdraw_result(self):
+        """(entries removed per tag staged for the most recent accepted tick, in the staged order;
+        entries removed in all) (ydc_stream_withdraw_result)."""
+        n, total = C.c_uint32(0), C.c_uint32(0)
+        rc = lib().ydc_stream_withdraw_result(self._h, None, 0, C.byref(n), C.byref(total))
+        if n.value == 0:
+            self._check(rc, "ydc_stream_withdraw_result")
+            return np.empty(0, np.uint32), int(total.value)
+        counts = np.empty(n.value, np.uint32)
+        self._check(lib().ydc_stream_withdraw_result(self._h, counts.ctypes.data, len(counts), C.byref(n),
+                                                     C.byref(total)), "ydc_stream_withdraw_result")
+        return counts, int(total.value)
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

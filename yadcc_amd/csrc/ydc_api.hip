@@ -14,6 +14,7 @@
 #include <condition_variable>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +41,7 @@
 #include "stream_outlook.h"
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
+#include "stream_withdraw.h"
 #include "tick_kernel.h"
 
 using namespace ydc;
@@ -211,6 +213,8 @@ struct TickArena {
   uint32_t *nimm, *npre;  // rpc mode: grants asked for per request (NULL in any other context)
   unsigned long long *bk_stid, *bk_dkey;  // with a running-task book: the reports' payload columns, beside rep_id
   int64_t* upd_exp;  // leased modes: the heartbeats' expiries, beside upd_idx (read only with aliveness on)
+  uint64_t* wd_tag;  // with withdrawal: the tick's staged tags (sorted, unique) and their number
+  uint32_t* wd_n;
 };
 }  // namespace
 
@@ -360,6 +364,7 @@ struct ydc_context {
     // well (rpc mode: max_tasks is max_requests). max_book: the running-task book's (0: none).
     ydc_stream_caps caps{};
     uint32_t max_book = 0;
+    uint32_t max_withdraw = 0;  // tags one tick can withdraw (ydc_stream_withdraw_begin; 0: the capability is off)
     bool waiting() const { return caps.max_waiting != 0; }
     bool leased() const { return caps.max_leases != 0; }
     bool rpc() const { return caps.max_rows != 0; }
@@ -526,6 +531,25 @@ struct ydc_context {
       DevBuf<InspectSums> sums;
       DevBuf<uint8_t> pack;     // k_inspect_pack's columns and their count
     } inspect;
+    // Withdrawal by tag (ydc_stream_withdraw_begin; stream_withdraw.h): the tick's list and counts in HBM
+    // and the page-locked result block, sized by max_withdraw. max_withdraw == 0: none of this exists,
+    // and the step launches what it launches without it. `host` moves to a grown stream as it is.
+    struct Withdraw {
+      DevBuf<uint8_t> d;  // tag | count | n
+      WithdrawList list{};
+      PinnedBuf h_res;  // page-locked: counts | WithdrawDone
+      uint32_t *h_count = nullptr, *z_count = nullptr;
+      WithdrawDone *h_done = nullptr, *z_done = nullptr;
+      struct Host {
+        // ydc_stream_withdraw_stage: the tags of the next accepted tick, as the caller gave them.
+        bool staged = false;
+        std::vector<uint64_t> tags;
+        // The most recent accepted tick (ydc_stream_withdraw_result): per staged tag its place in the
+        // tick's sorted list, the list's length, and the counts read back per place.
+        std::vector<uint32_t> place, counts;
+        uint32_t n_unique = 0;
+      } host;
+    } withdraw;
     // ydc_stream_outlook_get (stream_outlook.h): scratch only, reserved at the first call and
     // released with the stream; nothing of it is state, so reserve / restore carry nothing over.
     struct Outlook {
@@ -1134,6 +1158,12 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
                void* stream, ydc_context** out) {
   if (!out) return YDC_ERR_INVALID_ARGUMENT;
   *out = nullptr;
+  // (a servant index is below the number of servants: with this bound none is ever a sentinel, of which
+  // YDC_IDX_WITHDRAWN is the lowest; max_servants == 0 is bounded the same way where the registry grows)
+  if (max_servants > YDC_IDX_WITHDRAWN) {
+    set_create_error("max_servants " + std::to_string(max_servants) + " > " + std::to_string(YDC_IDX_WITHDRAWN));
+    return YDC_ERR_INVALID_ARGUMENT;
+  }
   int n_dev = 0;
   hipError_t de = hipGetDeviceCount(&n_dev);
   if (de != hipSuccess || n_dev <= 0 || device < 0 || device >= n_dev) {
@@ -1233,7 +1263,7 @@ int ydc_upload_servants(ydc_context* c, const ydc_servant_soa* sv, uint32_t n) {
   if (!c || (n && !sv)) return YDC_ERR_INVALID_ARGUMENT;
   if (sv && sv->env_words > YDC_MAX_ENV_WORDS)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "env_words %u > %u", sv->env_words, YDC_MAX_ENV_WORDS);
-  if (c->max_servants && n > c->max_servants)
+  if (n > (c->max_servants ? c->max_servants : YDC_IDX_WITHDRAWN))
     return fail(c, YDC_ERR_CAPACITY, "%u servants > max_servants %u", n, c->max_servants);
   HIP_TRY(c, hipSetDevice(c->device));
   join_lanes(c);
@@ -1267,7 +1297,7 @@ int ydc_update_servants_wide(ydc_context* c, const uint32_t* idx, const ydc_serv
     if (idx[i] > new_n) return fail(c, YDC_ERR_INVALID_ARGUMENT, "servant index %u out of order", idx[i]);
     if (idx[i] == new_n) ++new_n;
   }
-  if (c->max_servants && new_n > c->max_servants)
+  if (new_n > (c->max_servants ? c->max_servants : YDC_IDX_WITHDRAWN))
     return fail(c, YDC_ERR_CAPACITY, "%u servants > max_servants %u", new_n, c->max_servants);
   if (env_masks && c->reg.widen_env(env_words)) c->tables_dirty = true;
   const uint32_t old_n = c->reg.n;
@@ -4355,7 +4385,17 @@ void enqueue_rpc_expand(ydc_context* c, const TickArena& a) {
 
 // The tick's batch columns in HBM, in the context's mode.
 void enqueue_stream_gather(ydc_context* c, const TickArena& a) {
-  if (c->stream_mode.rpc()) enqueue_rpc_expand(c, a);
+  auto& sm = c->stream_mode;
+  // With withdrawal: the staged tags' entries of W expire here, in front of the gather that reads W
+  // (stream_withdraw.h). In this helper, so once per tick on every route.
+  if (sm.max_withdraw) {
+    const uint32_t MX = sm.max_withdraw;
+    YDC_LAUNCH(c, "k_withdraw_load", k_withdraw_load, dim3(ceil_div(MX, 256)), dim3(256), 0, c->stream, a.wd_tag,
+               a.wd_n, MX, sm.withdraw.list);
+    YDC_LAUNCH(c, "k_withdraw_mark", k_withdraw_mark, dim3(ceil_div(sm.caps.max_waiting, 256)), dim3(256), 0, c->stream,
+               sm.withdraw.list, MX, sm.wq.tag, sm.wq.deadline, sm.ws, sm.caps.max_waiting);
+  }
+  if (sm.rpc()) enqueue_rpc_expand(c, a);
   else enqueue_wait_gather(c, a);
 }
 
@@ -4469,6 +4509,15 @@ void enqueue_stream_answer(ydc_context* c, const TickArena& a, const DeviceParam
   else if (sm.waiting() && sm.leased()) enqueue_wait_lease_commit(c, a, prm, check_slot);
   else if (sm.waiting()) enqueue_wait_compact(c, a.now, prm, check_slot);
   else if (sm.leased()) enqueue_lease_grant(c, a, prm, check_slot);
+  // With withdrawal: the withdrawn entries' label in the resolved list the pass above wrote, and the
+  // counts (stream_withdraw.h), under the same gate.
+  if (sm.max_withdraw) {
+    const bool rpc = sm.rpc();
+    YDC_LAUNCH(c, "k_withdraw_label", k_withdraw_label, dim3(ceil_div(std::max(sm.caps.max_waiting, sm.max_withdraw), 256)),
+               dim3(256), 0, c->stream, sm.withdraw.list, sm.max_withdraw, rpc ? sm.rz.res_tag : sm.z_res_tag,
+               rpc ? sm.rz.res_status : sm.z_res_idx, rpc ? &sm.rz.outcome->n_resolved : &sm.z_wout->n_resolved,
+               sm.caps.max_waiting, sm.withdraw.z_count, sm.withdraw.z_done, prm, check_slot);
+  }
 }
 
 // The step itself, enqueued on the context's stream (inside a capture, or — stream_graph=0 — as it is).
@@ -4669,9 +4718,11 @@ const char* stream_caps_foreign(const ydc_stream_caps& have, const ydc_stream_ca
 
 // Layout and allocation of everything a stream of these bounds has, into `sm` (released, or
 // fresh). Its contents are not defined before stream_reset; after a failure the caller releases it.
-int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps& k, uint32_t max_book) {
+int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps& k, uint32_t max_book,
+                 uint32_t max_withdraw) {
   sm.caps = k;
   sm.max_book = max_book;
+  sm.max_withdraw = max_withdraw;
   const uint32_t max_updates = k.max_updates, max_releases = k.max_releases, max_tasks = k.max_tasks;
   const uint32_t max_waiting = k.max_waiting, max_rows = k.max_rows;
   const bool leased = sm.leased();
@@ -4703,6 +4754,9 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
   const size_t o_bdkey = max_book ? section(&off, (size_t)k.max_report_ids * 8) : 0;
   // ... and, last (no other section moves), the heartbeats' expiries of a leased stream.
   const size_t o_uexp = leased ? section(&off, (size_t)max_updates * 8) : 0;
+  // ... and behind it, with withdrawal, the staged tags and their number.
+  const size_t o_wdt = max_withdraw ? section(&off, (size_t)max_withdraw * 8) : 0;
+  const size_t o_wdn = max_withdraw ? section(&off, 4) : 0;
   auto arena_at = [&](uint8_t* b) {
     TickArena a{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
                 (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
@@ -4726,6 +4780,10 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
     if (max_book) {
       a.bk_stid = (unsigned long long*)(b + o_bstid);
       a.bk_dkey = (unsigned long long*)(b + o_bdkey);
+    }
+    if (max_withdraw) {
+      a.wd_tag = (uint64_t*)(b + o_wdt);
+      a.wd_n = (uint32_t*)(b + o_wdn);
     }
     return a;
   };
@@ -4877,6 +4935,21 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
     sm.book.h_bout = (BookOutcome*)sm.book.h_res.p;
     sm.book.z_bout = (BookOutcome*)sm.book.h_res.z;
   }
+  if (max_withdraw) {
+    // HBM: the tick's list, its counts and its length. Page-locked: the counts and the done block.
+    size_t d_off = 0, r_off = 0;
+    const size_t o_tag = section(&d_off, (size_t)max_withdraw * 8), o_cnt = section(&d_off, (size_t)max_withdraw * 4);
+    const size_t o_n = section(&d_off, 4);
+    HIP_TRY(c, sm.withdraw.d.reserve(d_off));
+    uint8_t* b = sm.withdraw.d.p;
+    sm.withdraw.list = WithdrawList{(unsigned long long*)(b + o_tag), (uint32_t*)(b + o_cnt), (uint32_t*)(b + o_n)};
+    const size_t r_cnt = section(&r_off, (size_t)max_withdraw * 4), r_done = section(&r_off, sizeof(WithdrawDone));
+    HIP_TRY(c, sm.withdraw.h_res.reserve(r_off));
+    sm.withdraw.h_count = (uint32_t*)(sm.withdraw.h_res.p + r_cnt);
+    sm.withdraw.z_count = (uint32_t*)(sm.withdraw.h_res.z + r_cnt);
+    sm.withdraw.h_done = (WithdrawDone*)(sm.withdraw.h_res.p + r_done);
+    sm.withdraw.z_done = (WithdrawDone*)(sm.withdraw.h_res.z + r_done);
+  }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
   sm.stale = true;
   return YDC_OK;
@@ -4903,6 +4976,10 @@ int stream_reset(ydc_context* c, ydc_context::Stream& sm) {
     HIP_TRY(c, hipMemsetAsync(sm.book.bks, 0, sizeof(BookState), c->stream));
     std::memset(sm.book.h_bout, 0, sizeof(BookOutcome));
     sm.book.n = 0;
+  }
+  if (sm.max_withdraw) {  // (an empty list)
+    HIP_TRY(c, hipMemsetAsync(sm.withdraw.list.n, 0, 4, c->stream));
+    std::memset(sm.withdraw.h_done, 0, sizeof(WithdrawDone));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   sm.active = true;
@@ -4998,12 +5075,13 @@ int stream_begin(ydc_context* c, const ydc_stream_caps& k) {
   join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   stream_release(c);
-  if (int rc = stream_alloc(c, c->stream_mode, k, 0)) return rc;
+  if (int rc = stream_alloc(c, c->stream_mode, k, 0, 0)) return rc;
   return stream_reset(c, c->stream_mode);
 }
 
-// The open stream in a second, larger set of buffers (ydc_stream_reserve, ydc_stream_book_begin).
-int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book) {
+// The open stream in a second, larger set of buffers (ydc_stream_reserve, ydc_stream_book_begin,
+// ydc_stream_withdraw_begin).
+int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, uint32_t max_withdraw) {
   auto& sm = c->stream_mode;
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
@@ -5011,7 +5089,7 @@ int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book) {
   // A second set of buffers, filled from the first, which is released only once that has worked:
   // after any failure the stream is as it was.
   ydc_context::Stream grown;
-  int rc = stream_alloc(c, grown, k, max_book);
+  int rc = stream_alloc(c, grown, k, max_book, max_withdraw);
   if (rc == YDC_OK) rc = stream_reset(c, grown);
   if (rc == YDC_OK) rc = stream_migrate(c, sm, grown);
   if (rc != YDC_OK) {
@@ -5023,6 +5101,7 @@ int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book) {
   grown.alive = std::move(sm.alive);      // (a pending staging goes along)
   grown.inspect = std::move(sm.inspect);  // (the detail records have moved already: stream_migrate)
   grown.book.staged = std::move(sm.book.staged);
+  grown.withdraw.host = std::move(sm.withdraw.host);  // (a pending staging and the last result go along)
   std::swap(sm, grown);
   stream_release(grown);  // (the old buffers and the old captures; sm.stale: the step is captured again)
   return YDC_OK;
@@ -5061,7 +5140,7 @@ int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
   const ydc_stream_caps k = stream_caps_grown(sm.caps, *want);  // (growth only)
   if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, k, sm.max_book)) return rc;
   if (!std::memcmp(&k, &sm.caps, sizeof k)) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, k, sm.max_book);
+  return stream_regrow(c, k, sm.max_book, sm.max_withdraw);
 }
 
 }  // extern "C"
@@ -5206,7 +5285,7 @@ int ydc_stream_book_begin(ydc_context* c, uint32_t max_book) {
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_begin: no leased, waiting-and-leased or rpc stream is open");
   if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, sm.caps, max_book)) return rc;
   if (max_book <= sm.max_book) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, ydc_stream_caps(sm.caps), max_book);  // (a copy: regrow replaces the stream)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), max_book, sm.max_withdraw);  // (a copy: regrow replaces the stream)
 }
 
 int ydc_stream_book_stage(ydc_context* c, const uint64_t* servant_task_id, const uint64_t* digest_key,
@@ -5222,6 +5301,47 @@ int ydc_stream_book_stage(ydc_context* c, const uint64_t* servant_task_id, const
   if (servant_task_id) std::copy_n(servant_task_id, n_ids, sm.book.staged.stid.begin());
   if (digest_key) std::copy_n(digest_key, n_ids, sm.book.staged.dkey.begin());
   sm.book.staged.on = true;
+  return YDC_OK;
+}
+
+int ydc_stream_withdraw_begin(ydc_context* c, uint32_t max_withdraw) {
+  if (!c || !max_withdraw) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.waiting())
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_withdraw_begin: no waiting, waiting-and-leased or rpc stream is open");
+  if (max_withdraw > (1u << 30))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "max_withdraw %u out of range (1 .. 2^30)", max_withdraw);
+  if (max_withdraw <= sm.max_withdraw) return YDC_OK;  // (nothing to do: the captured step stays)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, max_withdraw);  // (a copy: regrow replaces the stream)
+}
+
+int ydc_stream_withdraw_stage(ydc_context* c, const uint64_t* tags, uint32_t n) {
+  if (!c || (n && !tags)) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_withdraw)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_withdraw_stage: the stream withdraws nothing "
+                "(ydc_stream_withdraw_begin)");
+  if (n > sm.max_withdraw) return fail(c, YDC_ERR_CAPACITY, "%u staged tags > max_withdraw %u", n, sm.max_withdraw);
+  auto& w = sm.withdraw.host;
+  w.tags.assign(tags, tags + n);
+  w.staged = n != 0;
+  return YDC_OK;
+}
+
+int ydc_stream_withdraw_result(ydc_context* c, uint32_t* out_count, uint32_t cap, uint32_t* out_n,
+                               uint32_t* out_n_withdrawn) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_withdraw)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_withdraw_result: the stream withdraws nothing "
+                "(ydc_stream_withdraw_begin)");
+  const auto& w = sm.withdraw.host;
+  const uint32_t n = (uint32_t)w.place.size();
+  *out_n = n;
+  if (cap < n) return fail(c, YDC_ERR_CAPACITY, "%u staged tags > cap %u", n, cap);
+  if (n && !out_count) return YDC_ERR_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < n; ++i) out_count[i] = w.counts[w.place[i]];
+  if (out_n_withdrawn) *out_n_withdrawn = std::accumulate(w.counts.begin(), w.counts.end(), 0u);
   return YDC_OK;
 }
 
@@ -5767,7 +5887,8 @@ static int stream_wait_finish(ydc_context* c, const WaitTick* wt, uint32_t n_tas
   if (n_wait > sm.caps.max_waiting)
     return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u > max_waiting %u", n_wait, sm.caps.max_waiting);
   uint32_t expired = 0;  // (a resolved Timeout is an expired entry: a live one that timed out stays)
-  for (uint32_t i = 0; i < n_res; ++i) expired += sm.h_res_idx[i] == YDC_IDX_TIMEOUT;
+  for (uint32_t i = 0; i < n_res; ++i)  // (a withdrawn entry was placed as an expired one)
+    expired += sm.h_res_idx[i] == YDC_IDX_TIMEOUT || sm.h_res_idx[i] == YDC_IDX_WITHDRAWN;
   if (n_res && wt->out_resolved_tags != sm.h_res_tag)
     std::memcpy(wt->out_resolved_tags, sm.h_res_tag, (size_t)n_res * 8);
   if (n_res && wt->out_resolved_idx != sm.h_res_idx)
@@ -6118,6 +6239,24 @@ static int stream_tick_expiry(ydc_context* c, StreamCall& t, TickState* ts) {
   return YDC_OK;
 }
 
+// With withdrawal: the staged tags into the arena, sorted and without duplicates (the kernels search the
+// list), each staged tag's place in that list kept for ydc_stream_withdraw_result; the staging consumed.
+static void stream_withdraw_stage_tick(ydc_context::Stream& sm) {
+  auto& w = sm.withdraw.host;
+  std::vector<uint64_t> sorted(w.staged ? w.tags : std::vector<uint64_t>{});
+  std::sort(sorted.begin(), sorted.end());
+  sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+  w.place.resize(w.staged ? w.tags.size() : 0);
+  for (size_t i = 0; i < w.place.size(); ++i)
+    w.place[i] = (uint32_t)(std::lower_bound(sorted.begin(), sorted.end(), w.tags[i]) - sorted.begin());
+  w.n_unique = (uint32_t)sorted.size();
+  w.counts.assign(w.n_unique, 0);
+  if (w.n_unique) std::memcpy(sm.h.wd_tag, sorted.data(), (size_t)w.n_unique * 8);
+  *sm.h.wd_n = w.n_unique;
+  w.staged = false;
+  w.tags.clear();
+}
+
 // Step 4: the tick into the arena (padding = no-ops), the staged columns consumed, the lease header
 // and the tick number written.
 static void stream_tick_stage(ydc_context* c, const StreamCall& t, const TickState& ts) {
@@ -6178,6 +6317,7 @@ static void stream_tick_stage(ydc_context* c, const StreamCall& t, const TickSta
     if ((++sm.lease_tick & kLeaseStamp) == 0) ++sm.lease_tick;
     *h.lh = LeaseHdr{lt->now, lt->n_renew, lt->n_free, lt->n_rep, n_ids, sm.lease_tick, 0};
   }
+  if (sm.max_withdraw) stream_withdraw_stage_tick(sm);
   if (t.rt) {
     put(h.nimm, t.rt->n_imm, n_tasks, 4);
     put(h.npre, t.rt->n_pre, n_tasks, 4);
@@ -6210,7 +6350,10 @@ static int stream_tick_run(ydc_context* c, const StreamCall& t, TickState* ts) {
     if (wt) enqueue_stream_gather(c, sm.d);
     if (int rc = place_batch(c, NB, &batch_dev, eager, &ts->eager, &ts->rounds))
       return rc;
-    return stream_answer_eager(c, sm.d);
+    if (int rc = stream_answer_eager(c, sm.d)) return rc;
+    // (profiling: the enqueued step names its launches, from the batch's front on — ydc_kernel_profile)
+    if (c->profiling) collect_kernel_profile(c);
+    return YDC_OK;
   }
   const bool second = sm.swaps && c->d_running.p == sm.run_b;
   if (sm.swaps && !second && c->d_running.p != sm.run_a)
@@ -6284,6 +6427,12 @@ static int stream_tick_finish(ydc_context* c, const StreamCall& t, const TickSta
   auto& sm = c->stream_mode;
   const uint32_t n_tasks = t.n_tasks;
   fill_stats(c, *ts.plan, ts.rounds);
+  if (sm.max_withdraw) {  // (the label pass has stored the counts of the list it saw)
+    auto& w = sm.withdraw.host;
+    if (sm.withdraw.h_done->n != w.n_unique)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "withdrawal: counts of %u tags, %u staged", sm.withdraw.h_done->n, w.n_unique);
+    std::copy_n(sm.withdraw.h_count, w.n_unique, w.counts.begin());
+  }
   if (t.rt) return stream_rpc_finish(c, t, ts);
   c->stats.n_tasks = n_tasks;
   c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.caps.max_tasks - n_tasks);  // padding
@@ -6621,7 +6770,7 @@ int ydc_stream_snapshot(ydc_context* c, void* out, size_t cap, size_t* out_bytes
                 "on the device");
   if (c->group.n_ranks) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: the context is in a group");
   if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: pipelined batches are outstanding");
-  if (sm.book.staged.on || sm.alive.staged)
+  if (sm.book.staged.on || sm.alive.staged || sm.withdraw.host.staged)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: a staging for the next tick is pending (a snapshot "
                 "is taken between ticks)");
   HIP_TRY(c, hipSetDevice(c->device));
@@ -6693,7 +6842,7 @@ int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc
   // A second stream, complete before it becomes the context's.
   ydc_context::Stream fresh;
   auto load = [&]() -> int {
-    if (int rc = stream_alloc(c, fresh, k, h.max_book)) return rc;
+    if (int rc = stream_alloc(c, fresh, k, h.max_book, 0)) return rc;  // (withdrawal stays off, like inspection)
     if (int rc = stream_reset(c, fresh)) return rc;
     hipStream_t st = c->stream;
     if (fresh.leased()) {
