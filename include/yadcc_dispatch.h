@@ -773,6 +773,64 @@ int ydc_stream_inspect_waiting(ydc_context* ctx, uint64_t* out_tag, uint32_t* ou
                                int64_t* out_lease_for, uint32_t* out_n_immediate, uint32_t* out_n_prefetch,
                                uint32_t cap, uint32_t* out_n);
 
+/* ---- the load per requestor, and the admission arithmetic that goes with it ---------------------
+ * Who holds the cluster: per requestor_ip the leases it owns (with inspection on every lease keeps
+ * its requestor beside it) and the entries of W it is blocked on, summed on the device, so nobody has
+ * to copy L and W out and fold them on the host every tick. The reference answers a failed grant
+ * STATUS_NO_QUOTA_AVAILABLE (scheduler_service_impl.cc:266-269) but keeps no quota; a scheduler that
+ * knows each requestor's outstanding grants when it assembles a tick can enforce one at the door.
+ *   Keys: all 2^32 values of requestor_ip are ordinary keys, 0 and 0xFFFFFFFF included. A lease that
+ *     was granted while inspection was off (its record says YDC_INSPECT_NO_TIME) belongs to nobody:
+ *     it is counted in *out_unattributed and under no key, 0xFFFFFFFF neither.
+ *   Columns: leases counts the requestor's live leases, zombies included; zombies uses the zombie bit
+ *     as ydc_stream_inspect_tasks reports it; prefetch_leases counts the leases whose prefetch flag is
+ *     set. waiting counts its entries of W, an entry whose deadline has passed but which is still
+ *     queued included (ydc_stream_inspect_waiting lists it too); waiting_rows sums n_immediate +
+ *     n_prefetch over them in rpc mode and equals waiting otherwise.
+ *   Modes: a waiting stream (no L) answers the lease columns YDC_REQUESTOR_UNKNOWN and real demand
+ *     columns; a leased stream (no W) answers demand columns 0; a stream with L whose inspection is
+ *     off answers the lease columns YDC_REQUESTOR_UNKNOWN and *out_unattributed =
+ *     YDC_REQUESTOR_UNKNOWN. Without L *out_unattributed is YDC_REQUESTOR_UNKNOWN as well.
+ *   ydc_stream_requestor_find: out[i] for requestor_ip[i], n of them; queries may repeat;
+ *     out[i].requestor_ip echoes the query; a requestor that holds nothing is a row of zeros. n == 0
+ *     returns YDC_OK (NULL columns allowed); n > 2^24: YDC_ERR_INVALID_ARGUMENT, the caller splits.
+ *   ydc_stream_requestor_get: one row per requestor that has at least one lease or one entry of W.
+ *     THE ORDER OF THE ROWS IS UNSPECIFIED. *out_n: the number of rows; more than cap of them:
+ *     YDC_ERR_CAPACITY with *out_n set and nothing written.
+ *   Both run between ticks and synchronise. Like ydc_stream_outlook_get they end the resident tick
+ *     kernel and refuse, with YDC_ERR_INVALID_ARGUMENT, while pipelined batches are outstanding; the
+ *     same code for no open stream, a plain ydc_stream_begin stream, and n > 0 with a NULL
+ *     requestor_ip or out. An allocation that fails is YDC_ERR_HIP, and the stream stays usable.
+ *   They change nothing: the sums are built by each call from L and W as they stand, the next tick's
+ *     results are those of a twin context that never called them, no tick launches anything else
+ *     because of them, and nothing of theirs is carried by ydc_stream_reserve, ydc_stream_snapshot or
+ *     ydc_stream_restore: a snapshot taken after any number of calls is byte-identical to one taken
+ *     without.
+ *   ydc_admit_clip: no context, no device. Rows are a tick's requests in arrival order, load[i] is
+ *     the row of ydc_stream_requestor_find for requestor_ip[i], cap the grants one requestor may have
+ *     outstanding. room = cap - min(cap, leases + waiting_rows) (zombies are inside leases: they still
+ *     hold slots). With pre_i the sum of n_immediate + n_prefetch over the earlier rows of the same
+ *     requestor, row i is admitted a_i = min(pre_i + want_i, room) - min(pre_i, room) grants:
+ *     out_immediate[i] = min(n_immediate[i], a_i), out_prefetch[i] = a_i - out_immediate[i], so
+ *     prefetch is clipped first. Sums are 64-bit. n_prefetch == NULL means zeros and out_prefetch may
+ *     be NULL then (the modes without RPC rows). Rows of different requestors never interact: a
+ *     scheduler with per-host caps calls it once per cap class. A load whose leases is
+ *     YDC_REQUESTOR_UNKNOWN, or n > 0 with a NULL requestor_ip, n_immediate, load or out_immediate
+ *     (or out_prefetch with n_prefetch given): YDC_ERR_INVALID_ARGUMENT, nothing written. */
+#define YDC_REQUESTOR_UNKNOWN 0xFFFFFFFFu
+typedef struct ydc_requestor_load {     /* 24 bytes */
+  uint32_t requestor_ip;
+  uint32_t leases, zombies, prefetch_leases;  /* YDC_REQUESTOR_UNKNOWN with inspection off or no L */
+  uint32_t waiting, waiting_rows;             /* 0 without W (a leased stream) */
+} ydc_requestor_load;
+int ydc_stream_requestor_find(ydc_context* ctx, const uint32_t* requestor_ip, uint32_t n,
+                              ydc_requestor_load* out, uint32_t* out_unattributed /* nullable */);
+int ydc_stream_requestor_get(ydc_context* ctx, ydc_requestor_load* out, uint32_t cap, uint32_t* out_n,
+                             uint32_t* out_unattributed /* nullable */);
+int ydc_admit_clip(const uint32_t* requestor_ip, const uint32_t* n_immediate, const uint32_t* n_prefetch,
+                   uint32_t n, const ydc_requestor_load* load /* [n], load[i] for requestor_ip[i] */,
+                   uint32_t cap, uint32_t* out_immediate, uint32_t* out_prefetch);
+
 /* ---- withdrawal: waiting requests taken out of W by tag, inside the tick ------------------------
  * A blocked WaitForStartingTask call whose client went away (connection dropped, daemon restarted,
  * build interrupted) would otherwise stay in W until its deadline, be retried every tick and, if

@@ -25,6 +25,7 @@ INSPECT_NO_ID = 0xFFFFFFFF  # env_id / requestor_ip of a lease granted while ins
 INSPECT_NO_TIME = -(1 << 63)  # ... its started_at
 OUTLOOK_UNKNOWN = 0xFFFFFFFF  # leases / zombies of an outlook row while inspection is off
 BOOK_NOT_FOUND = 0xFFFFFFFF  # pos of a ydc_book_hit whose digest_key is not in the book
+REQUESTOR_UNKNOWN = 0xFFFFFFFF  # lease columns of a ydc_requestor_load while inspection is off or without leases
 DISPATCH_COMMIT = 1
 STAGES = ("servant_scan", "slot_gen", "sort", "class_lists", "task_classify", "match", "finalize",
           "total")
@@ -49,6 +50,7 @@ ABI_SYMBOLS = (
     "ydc_stream_alive_begin", "ydc_stream_alive_stage", "ydc_stream_alive_removed", "ydc_stream_alive_get",
     "ydc_stream_inspect_begin", "ydc_stream_inspect_load", "ydc_stream_inspect_servants", "ydc_stream_inspect_tasks",
     "ydc_stream_outlook_get", "ydc_stream_inspect_waiting",
+    "ydc_stream_requestor_find", "ydc_stream_requestor_get", "ydc_admit_clip",
     "ydc_stream_withdraw_begin", "ydc_stream_withdraw_stage", "ydc_stream_withdraw_result",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
@@ -93,6 +95,11 @@ OUTLOOK_DTYPE = np.dtype([("eligible", "<u4"), ("free_servants", "<u4"), ("grant
 # numpy view of ydc_book_hit (32 bytes)
 HIT_DTYPE = np.dtype([("pos", "<u4"), ("count", "<u4"), ("servant_idx", "<u4"), ("reserved", "<u4"),
                       ("task_grant_id", "<u8"), ("servant_task_id", "<u8")])
+
+
+# numpy view of ydc_requestor_load (24 bytes)
+REQUESTOR_DTYPE = np.dtype([("requestor_ip", "<u4"), ("leases", "<u4"), ("zombies", "<u4"), ("prefetch_leases", "<u4"),
+                            ("waiting", "<u4"), ("waiting_rows", "<u4")])
 
 
 # numpy view of ydc_servant_row (32 bytes)
@@ -240,6 +247,11 @@ def lib():
         L.ydc_stream_inspect_tasks.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
         L.ydc_stream_outlook_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.ydc_stream_inspect_waiting.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
+        L.ydc_stream_requestor_find.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.ydc_stream_requestor_get.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint32)]
+        L.ydc_admit_clip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                     C.c_void_p, C.c_void_p]
         L.ydc_stream_withdraw_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_withdraw_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_withdraw_result.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -297,7 +309,8 @@ _TUNE_KEYS = ("DEBUG_SIM", "CHUNK_SIZE", "TARGET_CHUNKS", "FUSED_CLASS", "OWN_GU
               "PACKED_CLASS", "SHARD_SORT", "BINSORT", "FUSE_PASSES", "WARM_UP",
               "HAND_TRIES", "LANES", "CP_EVERY", "WALK_PARK", "WIDE", "WIDE_LISTS", "GROUP_BINSORT",
               "BINSORT_VERIFY", "BINSORT_MAX_SLOTS", "SHARD_MARGIN",
-              "ROUNDS_PER_CHECK", "WALK_AFTER", "OUTCOME_STORE", "STREAM_GRAPH", "COMMIT_SWAP", "RELEASE_COUNTED", "SMALL_BATCH", "RESIDENT", "RESIDENT_IDLE_MS", "PACKED_TICK", "IPC_SLOT_WORDS", "IPC_TIMEOUT_MS", "IPC_COARSE")
+              "ROUNDS_PER_CHECK", "WALK_AFTER", "OUTCOME_STORE", "STREAM_GRAPH", "COMMIT_SWAP", "RELEASE_COUNTED", "SMALL_BATCH", "RESIDENT", "RESIDENT_IDLE_MS", "PACKED_TICK", "IPC_SLOT_WORDS", "IPC_TIMEOUT_MS", "IPC_COARSE",
+              "REQUESTOR_COMBINE")
 _tune_injected = ""
 
 
@@ -316,6 +329,22 @@ def compose_tune():
         os.environ["YDC_TUNE"] = both
     else:
         os.environ.pop("YDC_TUNE", None)
+
+
+def admit_clip(requestor_ip, n_immediate, n_prefetch, load, cap):
+    """The admission arithmetic (ydc_admit_clip; no context, no device): the tick's rows in arrival
+    order, load a REQUESTOR_DTYPE array with load[i] for requestor_ip[i], cap the grants a requestor
+    may have outstanding. n_prefetch: None means zeros. -> (out_immediate, out_prefetch), uint32."""
+    ips = np.ascontiguousarray(requestor_ip, dtype=np.uint32)
+    imm = np.ascontiguousarray(n_immediate, dtype=np.uint32)
+    pre = None if n_prefetch is None else np.ascontiguousarray(n_prefetch, dtype=np.uint32)
+    ld = np.ascontiguousarray(load, dtype=REQUESTOR_DTYPE)
+    assert ips.ndim == 1 and imm.shape == ips.shape and ld.shape == ips.shape and (pre is None or pre.shape == ips.shape)
+    out_imm, out_pre = np.zeros(len(ips), np.uint32), np.zeros(len(ips), np.uint32)
+    rc = lib().ydc_admit_clip(_ptr(ips), _ptr(imm), _ptr(pre), len(ips), _ptr(ld), int(cap), _ptr(out_imm), _ptr(out_pre))
+    if rc:
+        raise YdcError("ydc_admit_clip: %s (a load with unknown lease columns?)" % lib().ydc_strerror(rc).decode())
+    return out_imm, out_pre
 
 
 def device_count():
@@ -1177,6 +1206,34 @@ class Context:
         self._check(lib().ydc_stream_inspect_waiting(self._h, *[_ptr(a) for a in cols.values()], cap, C.byref(n)),
                     "ydc_stream_inspect_waiting")
         return {k: a[:n.value].copy() for k, a in cols.items()}
+
+    def stream_requestor_find(self, ips):
+        """What each requestor holds (ydc_stream_requestor_find): (structured array of REQUESTOR_DTYPE,
+        one row per queried requestor_ip — zeros where it holds nothing, the lease columns
+        REQUESTOR_UNKNOWN while inspection is off or without leases —, unattributed: the leases
+        granted while inspection was off, or REQUESTOR_UNKNOWN)."""
+        q = np.ascontiguousarray(ips, dtype=np.uint32)
+        out = np.zeros(len(q), REQUESTOR_DTYPE)
+        un = C.c_uint32(0)
+        for at in range(0, max(len(q), 1), 1 << 24):  # (the call takes 2^24 queries)
+            part, res = q[at:at + (1 << 24)], out[at:at + (1 << 24)]
+            self._check(lib().ydc_stream_requestor_find(self._h, _ptr(part) if len(part) else None, len(part),
+                                                        _ptr(res) if len(part) else None, C.byref(un)),
+                        "ydc_stream_requestor_find")
+        return out, int(un.value)
+
+    def stream_requestors(self):
+        """Every requestor that holds a lease or waits (ydc_stream_requestor_get): (structured array
+        of REQUESTOR_DTYPE sorted by requestor_ip, unattributed)."""
+        n, un = C.c_uint32(0), C.c_uint32(0)
+        rc = lib().ydc_stream_requestor_get(self._h, None, 0, C.byref(n), C.byref(un))
+        if rc != -4:  # (YDC_ERR_CAPACITY with the count is the expected answer; nobody: 0)
+            self._check(rc, "ydc_stream_requestor_get")
+        out = np.zeros(int(n.value), REQUESTOR_DTYPE)
+        if len(out):
+            self._check(lib().ydc_stream_requestor_get(self._h, _ptr(out), len(out), C.byref(n), C.byref(un)),
+                        "ydc_stream_requestor_get")
+        return out[np.argsort(out["requestor_ip"], kind="stable")], int(un.value)
 
     def stream_withdraw_begin(self, max_withdraw):
         """Switches withdrawal by tag on for the open waiting, waiting-and-leased or rpc stream, or

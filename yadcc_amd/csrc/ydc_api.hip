@@ -39,6 +39,8 @@
 #include "servant_alive.h"
 #include "stream_inspect.h"
 #include "stream_outlook.h"
+#include "requestor_index.h"
+#include "admit_clip.h"
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
 #include "stream_withdraw.h"
@@ -556,6 +558,14 @@ struct ydc_context {
       DevBuf<unsigned long long> agg, res;  // per class; per query (kOutlookCols each)
       DevBuf<uint32_t> q, hist;             // queries (env | minv); W's and L's histograms
     } outlook;
+    // ydc_stream_requestor_find / _get (requestor_index.h): scratch only, like the outlook's. The index
+    // is built by each call, so there is no mark to keep and nothing for reserve / restore to carry.
+    struct Requestor {
+      DevBuf<uint8_t> d;          // word | the five sums | unattributed
+      DevBuf<uint32_t> q;         // find: the queries ...
+      DevBuf<RequestorLoad> res;  // ... and their rows
+      DevBuf<uint8_t> rows;       // get: the fold's state and look-back words | its rows
+    } requestor;
   } stream_mode;
   // ydc_stream_snapshot: the packed columns of L with their count on the device, and the page-locked
   // block they cross the bus into. Kept for the next snapshot (a standby is fed periodically, and
@@ -568,6 +578,7 @@ struct ydc_context {
   DevBuf<DeviceParams> d_prm;
   PinnedAs<DeviceParams> h_prm;   // the outcome block: stored by k_finalize itself, or d_prm copied back
   bool opt_outcome_store = true;  // (outcome_store=0: always the copy)
+  bool opt_requestor_combine = true;  // equal requestors combined inside the wave first (requestor_combine=0: an atomic per entry)
   bool opt_release_counted = true;  // long release lists counted in LDS first (release_counted=0: an atomic per slot)
 
   // Staging for the host-pointer entry point (ydc_dispatch): the three request columns in
@@ -1238,6 +1249,7 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
   if (const char* s = tune_value("commit_swap")) c->opt_commit_swap = atoi(s) != 0;
   if (const char* s = tune_value("outcome_store")) c->opt_outcome_store = atoi(s) != 0;
   if (const char* s = tune_value("release_counted")) c->opt_release_counted = atoi(s) != 0;
+  if (const char* s = tune_value("requestor_combine")) c->opt_requestor_combine = atoi(s) != 0;
   if (const char* s = tune_value("walk_after")) c->opt_walk_after = (uint32_t)std::max(2, atoi(s));
   if (const char* s = tune_value("rounds_per_check"))
     c->opt_rounds_per_check = std::max(1, atoi(s));
@@ -5830,6 +5842,125 @@ int ydc_stream_inspect_waiting(ydc_context* c, uint64_t* out_tag, uint32_t* out_
   }
   if (!sm.rpc() && out_n_immediate) std::fill(out_n_immediate, out_n_immediate + n, 1u);
   return YDC_OK;
+}
+
+// ---- the load per requestor (requestor_index.h) ----
+
+// |L| + |W| as the index counts them in: L only where its records say whose a lease is.
+static uint64_t requestor_entries(const ydc_context::Stream& sm) {
+  return (uint64_t)(sm.leased() && sm.inspect.on ? sm.n_leases : 0u) + (uint64_t)(sm.waiting() ? sm.n_waiting : 0u);
+}
+
+// What both read calls of the requestor index do behind outlook_enter: the index over L and W as
+// they are now, enqueued on the stream (the caller's kernel follows it there). *with_l: the lease
+// columns are known.
+static int requestor_index_build(ydc_context* c, RequestorIndex* out_ix, bool* with_l) {
+  auto& sm = c->stream_mode;
+  const bool with_w = sm.waiting();
+  *with_l = sm.leased() && sm.inspect.on;
+  const uint32_t slots = requestor_index_slots(requestor_entries(sm));
+  const size_t o_sum = (size_t)slots * 8, o_un = o_sum + (size_t)slots * 4 * kRequestorCols;
+  HIP_TRY(c, sm.requestor.d.reserve(o_un + 16));
+  uint8_t* const b = sm.requestor.d.p;
+  const RequestorIndex ix{(unsigned long long*)b, (uint32_t*)(b + o_sum), (uint32_t*)(b + o_un), slots - 1};
+  *out_ix = ix;
+  HIP_TRY(c, hipMemsetAsync(b, 0, o_un + 16, c->stream));  // every slot free, every sum 0
+  const uint32_t combine = c->opt_requestor_combine ? 1u : 0u;
+  if (*with_l && sm.n_leases)
+    YDC_LAUNCH(c, "k_requestor_leases", k_requestor_leases, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0,
+               c->stream, sm.lt, sm.d_insp_rec.p, sm.d_insp_pre.p, ix, combine);
+  if (with_w && sm.n_waiting)
+    YDC_LAUNCH(c, "k_requestor_waiting", k_requestor_waiting, dim3(ceil_div(sm.n_waiting, 256)), dim3(256), 0, c->stream,
+               sm.wq.ip, sm.rw.n_imm, sm.rw.n_pre, sm.ws, sm.caps.max_waiting, ix, combine);
+  HIP_TRY(c, hipGetLastError());
+  return YDC_OK;
+}
+
+int ydc_stream_requestor_find(ydc_context* c, const uint32_t* requestor_ip, uint32_t n, ydc_requestor_load* out,
+                              uint32_t* out_unattributed) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (n > (1u << 24))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_requestor_find: %u queries > 2^24 in one call", n);
+  if (n && (!requestor_ip || !out))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_requestor_find: %u queries without their columns", n);
+  static_assert(sizeof(ydc_requestor_load) == sizeof(RequestorLoad), "ydc_requestor_load");
+  if (int rc = outlook_enter(c, "ydc_stream_requestor_find")) return rc;
+  if (!n && !out_unattributed) return YDC_OK;
+  auto& sm = c->stream_mode;
+  RequestorIndex ix{};
+  bool with_l = false;
+  if (n) {  // (before the build is enqueued: a failed allocation leaves nothing in flight)
+    HIP_TRY(c, sm.requestor.q.reserve(n));
+    HIP_TRY(c, sm.requestor.res.reserve(n));
+  }
+  if (int rc = requestor_index_build(c, &ix, &with_l)) return rc;
+  if (n) {
+    HIP_TRY(c, hipMemcpyAsync(sm.requestor.q.p, requestor_ip, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    YDC_LAUNCH(c, "k_requestor_find", k_requestor_find, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, sm.requestor.q.p,
+               n, ix, with_l ? 1u : 0u, sm.requestor.res.p);
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n) HIP_TRY(c, hipMemcpy(out, sm.requestor.res.p, (size_t)n * sizeof(RequestorLoad), hipMemcpyDeviceToHost));
+  if (out_unattributed) {
+    *out_unattributed = YDC_REQUESTOR_UNKNOWN;
+    if (with_l) HIP_TRY(c, hipMemcpy(out_unattributed, ix.unattributed, 4, hipMemcpyDeviceToHost));
+  }
+  return YDC_OK;
+}
+
+int ydc_stream_requestor_get(ydc_context* c, ydc_requestor_load* out, uint32_t cap, uint32_t* out_n,
+                             uint32_t* out_unattributed) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  *out_n = 0;
+  if (int rc = outlook_enter(c, "ydc_stream_requestor_get")) return rc;
+  auto& sm = c->stream_mode;
+  RequestorIndex ix{};
+  bool with_l = false;
+  // The fold's ticket, count and look-back words | its rows: a requestor has at least one entry.
+  const uint64_t most = requestor_entries(sm);
+  const uint32_t slots = requestor_index_slots(most), tiles = ceil_div(slots, kRequestorTile);
+  const uint32_t room = (uint32_t)std::min<uint64_t>(most, slots);
+  size_t off = 0;
+  const size_t o_state = section(&off, sizeof(RequestorFoldState)), o_lb = section(&off, (size_t)tiles * 8);
+  const size_t clear = off;
+  const size_t o_rows = section(&off, (size_t)room * sizeof(RequestorLoad));
+  HIP_TRY(c, sm.requestor.rows.reserve(off));
+  if (int rc = requestor_index_build(c, &ix, &with_l)) return rc;
+  uint8_t* const b = sm.requestor.rows.p;
+  RequestorFoldState* const fs = (RequestorFoldState*)(b + o_state);
+  RequestorLoad* const rows = (RequestorLoad*)(b + o_rows);
+  uint32_t m = 0;
+  if (most) {
+    HIP_TRY(c, hipMemsetAsync(b, 0, clear, c->stream));
+    YDC_LAUNCH(c, "k_requestor_fold", k_requestor_fold, dim3(tiles), dim3(256), 0, c->stream, ix, with_l ? 1u : 0u, fs,
+               (unsigned long long*)(b + o_lb), rows, room);
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (most) HIP_TRY(c, hipMemcpy(&m, &fs->n_rows, 4, hipMemcpyDeviceToHost));
+  if (m > room) return fail(c, YDC_ERR_NOT_CONVERGED, "%u requestors among %u entries", m, room);
+  *out_n = m;
+  if (m > cap) return fail(c, YDC_ERR_CAPACITY, "%u requestors > cap %u", m, cap);
+  if (m && !out) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_requestor_get: %u rows without their column", m);
+  if (m) HIP_TRY(c, hipMemcpy(out, rows, (size_t)m * sizeof(RequestorLoad), hipMemcpyDeviceToHost));
+  if (out_unattributed) {
+    *out_unattributed = YDC_REQUESTOR_UNKNOWN;
+    if (with_l) HIP_TRY(c, hipMemcpy(out_unattributed, ix.unattributed, 4, hipMemcpyDeviceToHost));
+  }
+  return YDC_OK;
+}
+
+int ydc_admit_clip(const uint32_t* requestor_ip, const uint32_t* n_immediate, const uint32_t* n_prefetch, uint32_t n,
+                   const ydc_requestor_load* load, uint32_t cap, uint32_t* out_immediate, uint32_t* out_prefetch) {
+  static_assert(sizeof(ydc_requestor_load) == sizeof(AdmitLoad), "ydc_requestor_load");
+  if (!n) return YDC_OK;
+  if (!requestor_ip || !n_immediate || !load || !out_immediate || (n_prefetch && !out_prefetch))
+    return YDC_ERR_INVALID_ARGUMENT;
+  return admit_clip(requestor_ip, n_immediate, n_prefetch, n, reinterpret_cast<const AdmitLoad*>(load), cap,
+                    out_immediate, out_prefetch)
+             ? YDC_OK
+             : YDC_ERR_INVALID_ARGUMENT;
 }
 
 int ydc_stream_waiting_take(ydc_context* c, uint64_t* out_tags, uint32_t cap, uint32_t* out_n) {

@@ -191,3 +191,41 @@ def find_running(ctx, row_to_location, keys):
     hits, _ = ctx.stream_book_find(keys)
     return [None if int(h["pos"]) == binding.BOOK_NOT_FOUND
             else (row_to_location[int(h["servant_idx"])], int(h["servant_task_id"])) for h in hits]
+
+
+REQUESTOR_COLUMNS = ("leases", "zombies", "prefetch_leases", "waiting", "waiting_rows")
+
+
+def requestor_table(load, host_names):
+    """The per-requestor table of /inspect, next to outlook_table: one line per row of a
+    binding.Context.stream_requestors / stream_requestor_find result, named by the requestor's
+    address. No compute: every number is the call's. host_names: requestor_ip id -> address (a dict
+    or a list); an id without a name prints as "#id"; a column that is REQUESTOR_UNKNOWN (the lease
+    columns while inspection is off or on a stream without leases) prints as "-"."""
+    def name(ip):
+        got = host_names.get(ip) if isinstance(host_names, dict) else (host_names[ip] if ip < len(host_names) else None)
+        return got if got is not None else "#%d" % ip
+    rows = [("requestor",) + REQUESTOR_COLUMNS]
+    for r in load:
+        cells = []
+        for k in REQUESTOR_COLUMNS:
+            v = int(r[k])
+            cells.append("-" if k in REQUESTOR_COLUMNS[:3] and v == binding.REQUESTOR_UNKNOWN else str(v))
+        rows.append((name(int(r["requestor_ip"])),) + tuple(cells))
+    width = [max(len(r[c]) for r in rows) for c in range(len(rows[0]))]
+    return "\n".join("  ".join(cell.ljust(width[c]) if c == 0 else cell.rjust(width[c])
+                               for c, cell in enumerate(r)).rstrip() for r in rows)
+
+
+def admit(ctx, requests, n_immediate, n_prefetch, cap):
+    """A fair share at the door: the tick's requests (dict with a requestor_ip column, arrival order)
+    clipped so that no requestor has more than `cap` grants outstanding — leases, zombies included,
+    plus the rows it waits for — once they are all admitted. One ctx.stream_requestor_find for the
+    requestors of the tick, then binding.admit_clip. n_prefetch: None outside rpc mode.
+    -> (n_immediate, n_prefetch, keep): the two clipped columns (prefetch is clipped first) and the
+    mask of the rows that are admitted any grant; a scheduler answers the others
+    STATUS_NO_QUOTA_AVAILABLE and sends the kept rows with their clipped counts."""
+    ips = np.ascontiguousarray(requests["requestor_ip"], dtype=np.uint32)
+    load, _ = ctx.stream_requestor_find(ips)
+    imm, pre = binding.admit_clip(ips, n_immediate, n_prefetch, load, cap)
+    return imm, pre, (imm.astype(np.uint64) + pre) > 0
