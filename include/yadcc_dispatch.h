@@ -35,6 +35,13 @@ extern "C" {
  * queue by its tag. Only ever in a resolved list / an rpc resolved status. No registry index ever
  * has this value: ydc_create refuses a max_servants above it. */
 #define YDC_IDX_WITHDRAWN 0xFFFFFFFCu
+/* Streams with a quota only (ydc_stream_quota_begin): the new request was admitted nothing, its
+ * requestor being at its cap. Only ever a new request's answer / an rpc new request's status. No
+ * registry index has this value in such a stream: ydc_stream_quota_begin refuses a context whose
+ * bound of servants lies above it. */
+#define YDC_IDX_OVER_QUOTA 0xFFFFFFFBu
+/* ydc_stream_quota_set: no cap. */
+#define YDC_QUOTA_UNLIMITED 0xFFFFFFFFu
 
 /* ---- error codes ---------------------------------------------------------- */
 #define YDC_OK 0
@@ -878,6 +885,65 @@ int ydc_stream_withdraw_begin(ydc_context* ctx, uint32_t max_withdraw);
 int ydc_stream_withdraw_stage(ydc_context* ctx, const uint64_t* tags, uint32_t n);
 int ydc_stream_withdraw_result(ydc_context* ctx, uint32_t* out_count, uint32_t cap, uint32_t* out_n,
                                uint32_t* out_n_withdrawn);
+
+/* ---- quota: a cap of outstanding grants per requestor, enforced inside the tick -------------------
+ * ydc_stream_requestor_find + ydc_admit_clip is a fair share at the door: one synchronising call in
+ * front of every tick, with loads from before the tick, so a requestor at its cap that frees ten
+ * tasks and asks for ten more in one tick is refused all ten. Here the tick itself clips its new
+ * requests, by ydc_admit_clip's rule, with the loads of L and W at the moment its batch is built.
+ * Opt-in, for an open waiting-and-leased or rpc stream with inspection on. The reference has no
+ * quota: it answers NO_QUOTA_AVAILABLE only when the pool is empty (scheduler_service_impl.cc:266-269).
+ *   ydc_stream_quota_begin: switches the capability on, with room for max_overrides per-requestor
+ *     caps; a later call with a larger max_overrides grows it; a smaller or equal one returns YDC_OK
+ *     and does nothing (the captured step stays). An effective call allocates a second set of the
+ *     stream's buffers, copies, then swaps, all or nothing as ydc_stream_withdraw_begin does (pointers
+ *     of ydc_stream_buffers_get change), and the step is captured again at the next tick. Refused with
+ *     YDC_ERR_INVALID_ARGUMENT: no such stream open, a plain, waiting-only or leased-only stream,
+ *     inspection off, max_overrides > 2^24, a context whose bound of servants (ydc_create's
+ *     max_servants; 0: unbounded) could produce the index YDC_IDX_OVER_QUOTA. ydc_stream_end and the
+ *     next begin call switch it off; ydc_stream_reserve, ydc_stream_book_begin and
+ *     ydc_stream_withdraw_begin carry it over with its settings; ydc_stream_restore leaves it off (the
+ *     blob says nothing about it). After the first begin every cap is YDC_QUOTA_UNLIMITED: begin alone
+ *     changes no answer.
+ *   ydc_stream_quota_set: default_cap for every requestor, and n overrides (requestor_ip[i], cap[i]) in
+ *     any order. Holds from the next accepted tick until the next set, which replaces all of it. A
+ *     cap of 0 refuses everything of that requestor. A requestor named twice:
+ *     YDC_ERR_INVALID_ARGUMENT; n > max_overrides: YDC_ERR_CAPACITY; the capability off:
+ *     YDC_ERR_INVALID_ARGUMENT. A refused call or a refused tick leaves the settings as they were. They
+ *     are no per-tick staging: ydc_stream_snapshot is not refused because of them, and carries none.
+ *   In the tick, inside step 8 — after steps 1-6, the servants' expiry and the withdrawal's mark,
+ *     before W and the new requests are gathered: per requestor r
+ *       held(r) = its live leases by the inspection records, zombies included (a lease whose record
+ *                 says YDC_INSPECT_NO_TIME belongs to nobody), plus the rows of its entries of W with
+ *                 deadline > now (an entry that expires or is withdrawn in this tick no longer counts)
+ *       room(r) = cap(r) - min(cap(r), held(r))
+ *     and with pre_i the sum of n_immediate + n_prefetch (1 outside rpc mode) over the tick's EARLIER
+ *     new requests of the same requestor, request i is admitted
+ *       a_i = min(pre_i + want_i, room) - min(pre_i, room)
+ *     grants: adm_immediate = min(n_immediate, a_i), adm_prefetch = a_i - adm_immediate (prefetch is
+ *     clipped first). A request for an unknown digest takes room like any other.
+ *     Apart from the label, the tick and all later ticks are exactly those of a stream that was given
+ *     the clipped requests: counts adm_immediate / adm_prefetch, and requests with a_i == 0 left out.
+ *     So W stores the admitted counts, inspection's prefetch flag follows the admitted n_immediate,
+ *     and in rpc mode the expanded outputs are laid out BY ADMITTED ROWS: request i's rows begin at the
+ *     sum of adm_immediate + adm_prefetch over the requests in front of it, and a request with a_i == 0
+ *     takes none. Such a request consumes nothing — no slot, no id, no lease, no record, no
+ *     ever_assigned — never enters W, and is answered YDC_IDX_OVER_QUOTA (rpc: status
+ *     YDC_IDX_OVER_QUOTA, n_granted 0). W's own entries are never clipped again. The tick's refusals
+ *     (YDC_ERR_CAPACITY and the like) are computed from the SUBMITTED counts.
+ *     After every tick, for every requestor: leases + waiting_rows <= max(cap, its value before).
+ *   ydc_stream_quota_result: about the most recent accepted tick. *out_n: its new requests;
+ *     out_immediate[i] / out_prefetch[i]: what request i was admitted, in the caller's order (outside
+ *     rpc mode out_immediate is 0 / 1 and out_prefetch, which may be NULL, zeros); *out_rows_clipped
+ *     (nullable): submitted minus admitted grants in total; *out_n_refused (nullable): requests with
+ *     a_i == 0. cap < *out_n: YDC_ERR_CAPACITY with *out_n set and nothing written.
+ *   No tick signature changes; a stream that never calls ydc_stream_quota_begin launches what it
+ *     launched before. ydc_get_stats keeps its layout (a refused request counts nowhere). */
+int ydc_stream_quota_begin(ydc_context* ctx, uint32_t max_overrides);
+int ydc_stream_quota_set(ydc_context* ctx, uint32_t default_cap, const uint32_t* requestor_ip, const uint32_t* cap,
+                         uint32_t n);
+int ydc_stream_quota_result(ydc_context* ctx, uint32_t* out_immediate, uint32_t* out_prefetch, uint32_t cap,
+                            uint32_t* out_n, uint32_t* out_rows_clipped, uint32_t* out_n_refused);
 
 /* ---- snapshot and restore of an open stream --------------------------------------------
  * Everything an open waiting, leased, waiting-and-leased or rpc stream keeps on the device (L with

@@ -21,6 +21,8 @@ IDX_TIMEOUT = 0xFFFFFFFF
 IDX_ENV_NOT_FOUND = 0xFFFFFFFE
 IDX_WAITING = 0xFFFFFFFD  # streaming waiting mode: queued on the device, answered in a later tick
 IDX_WITHDRAWN = 0xFFFFFFFC  # resolved lists only: the waiting request was withdrawn by its tag
+IDX_OVER_QUOTA = 0xFFFFFFFB  # streams with a quota only: the new request was admitted nothing (its requestor is at its cap)
+QUOTA_UNLIMITED = 0xFFFFFFFF  # stream_quota_set: no cap
 INSPECT_NO_ID = 0xFFFFFFFF  # env_id / requestor_ip of a lease granted while inspection was off
 INSPECT_NO_TIME = -(1 << 63)  # ... its started_at
 OUTLOOK_UNKNOWN = 0xFFFFFFFF  # leases / zombies of an outlook row while inspection is off
@@ -52,6 +54,7 @@ ABI_SYMBOLS = (
     "ydc_stream_outlook_get", "ydc_stream_inspect_waiting",
     "ydc_stream_requestor_find", "ydc_stream_requestor_get", "ydc_admit_clip",
     "ydc_stream_withdraw_begin", "ydc_stream_withdraw_stage", "ydc_stream_withdraw_result",
+    "ydc_stream_quota_begin", "ydc_stream_quota_set", "ydc_stream_quota_result",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
@@ -255,6 +258,10 @@ def lib():
         L.ydc_stream_withdraw_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_withdraw_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_withdraw_result.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.ydc_stream_quota_begin.argtypes = [C.c_void_p, C.c_uint32]
+        L.ydc_stream_quota_set.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ydc_stream_quota_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
         L.ydc_stream_book_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1259,6 +1266,36 @@ class Context:
         self._check(lib().ydc_stream_withdraw_result(self._h, counts.ctypes.data, len(counts), C.byref(n),
                                                      C.byref(total)), "ydc_stream_withdraw_result")
         return counts, int(total.value)
+
+    def stream_quota_begin(self, max_overrides=0):
+        """Switches the cap per requestor on for the open waiting-and-leased or rpc stream with
+        inspection on, or grows it (ydc_stream_quota_begin): room for max_overrides per-requestor caps.
+        Every cap is QUOTA_UNLIMITED until stream_quota_set."""
+        self._check(lib().ydc_stream_quota_begin(self._h, int(max_overrides)), "ydc_stream_quota_begin")
+
+    def stream_quota_set(self, default_cap, overrides=None):
+        """The caps from the next accepted tick on (ydc_stream_quota_set): default_cap for everybody,
+        overrides a dict (or pairs) requestor_ip -> cap. A request whose requestor has no room is
+        answered IDX_OVER_QUOTA."""
+        pairs = list(overrides.items()) if isinstance(overrides, dict) else list(overrides or ())
+        ips = np.ascontiguousarray([p[0] for p in pairs], dtype=np.uint32)
+        caps = np.ascontiguousarray([p[1] for p in pairs], dtype=np.uint32)
+        self._check(lib().ydc_stream_quota_set(self._h, int(default_cap), _ptr(ips) if len(ips) else None,
+                                               _ptr(caps) if len(caps) else None, len(ips)), "ydc_stream_quota_set")
+
+    def stream_quota_result(self):
+        """(admitted n_immediate, admitted n_prefetch, rows clipped, requests refused) of the most recent
+        accepted tick, per new request in the caller's order (ydc_stream_quota_result); outside rpc mode
+        the first is 0 / 1 and the second zeros."""
+        n, clipped, refused = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        rc = lib().ydc_stream_quota_result(self._h, None, None, 0, C.byref(n), C.byref(clipped), C.byref(refused))
+        if n.value == 0:
+            self._check(rc, "ydc_stream_quota_result")
+        imm, pre = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+        if n.value:
+            self._check(lib().ydc_stream_quota_result(self._h, imm.ctypes.data, pre.ctypes.data, len(imm), C.byref(n),
+                                                      C.byref(clipped), C.byref(refused)), "ydc_stream_quota_result")
+        return imm, pre, int(clipped.value), int(refused.value)
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

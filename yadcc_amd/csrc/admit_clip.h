@@ -14,12 +14,41 @@
 //
 // Sums are 64-bit. pre_i only ever enters as min(pre_i, room) with room < 2^32, so it is carried
 // saturated at 2^62 (a row adds less than 2^33): no input makes an intermediate wrap.
+//
+// The rule itself — admit_room_of, admit_rows, admit_split — is written once, for the host loop below
+// and for the tick's own clip on the device (stream_quota.h), which instantiates it
+// with 32-bit sums: there pre + want < 2^31 (an accepted tick's rows) and held < 2^31.
 #pragma once
 #include <stdint.h>
 
 #include <unordered_map>
 
+#if defined(__HIPCC__)
+#define YDC_ADMIT_HD __host__ __device__
+#else
+#define YDC_ADMIT_HD
+#endif
+
 namespace ydc {
+
+// room = cap - min(cap, held).
+template <class T>
+YDC_ADMIT_HD inline T admit_room_of(T cap, T held) {
+  return cap - (held < cap ? held : cap);
+}
+
+// a = min(pre + want, room) - min(pre, room). The caller sees to it that pre + want does not wrap.
+template <class T>
+YDC_ADMIT_HD inline T admit_rows(T pre, T want, T room) {
+  const T before = pre < room ? pre : room;
+  const T after = pre + want < room ? pre + want : room;
+  return after - before;
+}
+
+// Prefetch is clipped first: of `a` admitted grants the immediate ones come first.
+YDC_ADMIT_HD inline uint32_t admit_split(uint32_t n_immediate, uint64_t a) {
+  return n_immediate < a ? n_immediate : (uint32_t)a;
+}
 
 // ydc_requestor_load.
 struct AdmitLoad {
@@ -33,8 +62,7 @@ constexpr uint32_t kAdmitUnknown = 0xFFFFFFFFu;  // YDC_REQUESTOR_UNKNOWN
 constexpr uint64_t kAdmitSaturated = 1ull << 62;
 
 inline uint64_t admit_room(const AdmitLoad& l, uint32_t cap) {
-  const uint64_t held = (uint64_t)l.leases + (uint64_t)l.waiting_rows;
-  return (uint64_t)cap - (held < cap ? held : (uint64_t)cap);
+  return admit_room_of<uint64_t>(cap, (uint64_t)l.leases + (uint64_t)l.waiting_rows);
 }
 
 // false: a load with unknown lease columns (nothing is written then). n_prefetch == NULL: zeros.
@@ -47,11 +75,9 @@ inline bool admit_clip(const uint32_t* requestor_ip, const uint32_t* n_immediate
     const uint64_t room = admit_room(load[i], cap);
     const uint64_t want = (uint64_t)n_immediate[i] + (n_prefetch ? (uint64_t)n_prefetch[i] : 0u);
     uint64_t& pre = asked[requestor_ip[i]];
-    const uint64_t before = pre < room ? pre : room;
-    const uint64_t after = pre + want < room ? pre + want : room;
-    const uint64_t a = after - before;
+    const uint64_t a = admit_rows<uint64_t>(pre, want, room);
     pre = pre + want < kAdmitSaturated ? pre + want : kAdmitSaturated;
-    const uint32_t imm = n_immediate[i] < a ? n_immediate[i] : (uint32_t)a;
+    const uint32_t imm = admit_split(n_immediate[i], a);
     out_immediate[i] = imm;
     if (out_prefetch) out_prefetch[i] = (uint32_t)(a - imm);
   }

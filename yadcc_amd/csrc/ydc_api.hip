@@ -43,6 +43,7 @@
 #include "admit_clip.h"
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
+#include "stream_quota.h"
 #include "stream_withdraw.h"
 #include "tick_kernel.h"
 
@@ -217,6 +218,7 @@ struct TickArena {
   int64_t* upd_exp;  // leased modes: the heartbeats' expiries, beside upd_idx (read only with aliveness on)
   uint64_t* wd_tag;  // with withdrawal: the tick's staged tags (sorted, unique) and their number
   uint32_t* wd_n;
+  uint32_t* q_n;  // with a quota: the tick's number of new requests (the columns behind it are padding)
 };
 }  // namespace
 
@@ -552,6 +554,35 @@ struct ydc_context {
         uint32_t n_unique = 0;
       } host;
     } withdraw;
+    // The cap per requestor inside the tick (ydc_stream_quota_begin; stream_quota.h): the table keyed by
+    // the tick's new requestors, the settings' device copy, the admitted counts per new request in HBM
+    // and the page-locked results. !on: none of this exists, and the step launches what it launches
+    // without it. `host` moves to a grown stream as it is.
+    struct Quota {
+      bool on = false;
+      uint32_t max_overrides = 0;
+      DevBuf<uint8_t> d;
+      QuotaTable tb{};
+      QuotaCaps caps{};
+      QuotaTick tk{};
+      uint32_t tiles = 0;
+      PinnedBuf h_res;  // page-locked: admitted immediate | admitted prefetch | QuotaDone
+      uint32_t *h_imm = nullptr, *z_imm = nullptr, *h_pre = nullptr, *z_pre = nullptr;
+      QuotaDone *h_done = nullptr, *z_done = nullptr;
+      struct Host {
+        // ydc_stream_quota_set: the default and the overrides (sorted by requestor), and whether the
+        // device copy still has to follow them (a set, a grown stream).
+        uint32_t default_cap = YDC_QUOTA_UNLIMITED;
+        std::vector<uint32_t> ip, cap;
+        bool dirty = true;
+        bool table_dirty = false;  // a tick ended in an error behind its clip: the table is cleared before the next
+        // The most recent accepted tick (ydc_stream_quota_result).
+        std::vector<uint32_t> imm, pre;
+        uint32_t rows_clipped = 0, n_refused = 0;
+      } host;
+      // 0: off; otherwise max_overrides + 1 (what stream_alloc and stream_regrow are told).
+      uint32_t code() const { return on ? max_overrides + 1 : 0; }
+    } quota;
     // ydc_stream_outlook_get (stream_outlook.h): scratch only, reserved at the first call and
     // released with the stream; nothing of it is state, so reserve / restore carry nothing over.
     struct Outlook {
@@ -4379,7 +4410,9 @@ void enqueue_wait_gather(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
   const uint32_t N = stream_batch_n(sm);
   YDC_LAUNCH(c, "k_wait_gather", k_wait_gather, dim3(ceil_div(std::max(N, sm.lookback_n), 256)), dim3(256), 0,
-             c->stream, sm.wq, sm.wt, WaitNew{a.env, a.minv, a.ip, a.dl, a.tag, a.now}, sm.caps.max_waiting, N, sm.ws,
+             c->stream, sm.wq, sm.wt,
+             // (with a quota: the env column in which a refused request is padding — stream_quota.h)
+             WaitNew{sm.quota.on ? sm.quota.tk.env : a.env, a.minv, a.ip, a.dl, a.tag, a.now}, sm.caps.max_waiting, N, sm.ws,
              sm.lookback, sm.leased() ? 0u : sm.lookback_n,  // (with leases: k_lease_renew has cleared the words)
              WaitExtra{sm.wl.w_for, sm.wl.t_for, sm.wl.t_for ? a.lexp : nullptr});
 }
@@ -4388,8 +4421,11 @@ void enqueue_wait_gather(ydc_context* c, const TickArena& a) {
 void enqueue_rpc_expand(ydc_context* c, const TickArena& a) {
   auto& sm = c->stream_mode;
   const uint32_t P = sm.caps.max_waiting + sm.caps.max_tasks, NR = sm.caps.max_rows;
+  // (with a quota: the new requests' counts are the admitted ones, in HBM — stream_quota.h)
+  const uint32_t* const nimm = sm.quota.on ? sm.quota.tk.adm_imm : a.nimm;
+  const uint32_t* const npre = sm.quota.on ? sm.quota.tk.adm_pre : a.npre;
   YDC_LAUNCH(c, "k_rpc_scan", k_rpc_scan, dim3(ceil_div(P, kRpcTile)), dim3(256), 0, c->stream, sm.rw,
-             RpcNew{a.env, a.minv, a.ip, a.dl, a.tag, a.lexp, a.nimm, a.npre}, sm.rp, a.lh, sm.caps.max_waiting, P, sm.ws,
+             RpcNew{a.env, a.minv, a.ip, a.dl, a.tag, a.lexp, nimm, npre}, sm.rp, a.lh, sm.caps.max_waiting, P, sm.ws,
              sm.rs, sm.lb_scan, sm.rb.row_start);
   YDC_LAUNCH(c, "k_rpc_expand", k_rpc_expand, dim3(ceil_div(NR, 256)), dim3(256), 0, c->stream, sm.rp, P, NR, sm.rb,
              sm.rs);
@@ -4406,6 +4442,22 @@ void enqueue_stream_gather(ydc_context* c, const TickArena& a) {
                a.wd_n, MX, sm.withdraw.list);
     YDC_LAUNCH(c, "k_withdraw_mark", k_withdraw_mark, dim3(ceil_div(sm.caps.max_waiting, 256)), dim3(256), 0, c->stream,
                sm.withdraw.list, MX, sm.wq.tag, sm.wq.deadline, sm.ws, sm.caps.max_waiting);
+  }
+  // With a quota: the new requests clipped to their requestors' room, by the loads of L and W as they
+  // are here — behind the tick's frees, expiry and the withdrawal's mark (stream_quota.h). In this
+  // helper, so once per tick on every route.
+  if (sm.quota.on) {
+    const auto& q = sm.quota;
+    const bool rpc = sm.rpc();
+    const uint32_t MT = sm.caps.max_tasks, MW = sm.caps.max_waiting;
+    const uint32_t l_blocks = ceil_div(sm.lt.mask + 1, kLeaseTile);
+    YDC_LAUNCH(c, "k_quota_claim", k_quota_claim, dim3(ceil_div(std::max(MT, q.tiles), 256)), dim3(256), 0, c->stream,
+               a.ip, a.q_n, MT, q.tiles, q.tb, q.tk);
+    YDC_LAUNCH(c, "k_quota_loads", k_quota_loads, dim3(l_blocks + ceil_div(MW, 256)), dim3(256), 0, c->stream, sm.lt,
+               sm.d_insp_rec.p, l_blocks, rpc ? sm.rw.ip : sm.wq.ip, rpc ? sm.rw.deadline : sm.wq.deadline,
+               rpc ? sm.rw.n_imm : nullptr, rpc ? sm.rw.n_pre : nullptr, sm.ws, MW, a.lh, q.tb);
+    YDC_LAUNCH(c, "k_quota_clip", k_quota_clip, dim3(q.tiles), dim3(256), 0, c->stream, a.ip, a.env,
+               rpc ? a.nimm : nullptr, rpc ? a.npre : nullptr, a.q_n, MT, q.tb, q.caps, q.tk);
   }
   if (sm.rpc()) enqueue_rpc_expand(c, a);
   else enqueue_wait_gather(c, a);
@@ -4529,6 +4581,15 @@ void enqueue_stream_answer(ydc_context* c, const TickArena& a, const DeviceParam
                dim3(256), 0, c->stream, sm.withdraw.list, sm.max_withdraw, rpc ? sm.rz.res_tag : sm.z_res_tag,
                rpc ? sm.rz.res_status : sm.z_res_idx, rpc ? &sm.rz.outcome->n_resolved : &sm.z_wout->n_resolved,
                sm.caps.max_waiting, sm.withdraw.z_count, sm.withdraw.z_done, prm, check_slot);
+  }
+  // With a quota: the table cleared for the next tick, and under the commit pass's gate the label of the
+  // requests that were admitted nothing, the admitted counts and the result block (stream_quota.h).
+  if (sm.quota.on) {
+    const auto& q = sm.quota;
+    const bool rpc = sm.rpc();
+    YDC_LAUNCH(c, "k_quota_label", k_quota_label, dim3(ceil_div(std::max(sm.caps.max_tasks, q.tb.mask + 1), 256)),
+               dim3(256), 0, c->stream, q.tb, q.tk, a.q_n, sm.caps.max_tasks, a.lh, rpc ? sm.rz.status : sm.z_out, q.z_imm,
+               rpc ? q.z_pre : nullptr, q.z_done, prm, check_slot);
   }
 }
 
@@ -4731,10 +4792,12 @@ const char* stream_caps_foreign(const ydc_stream_caps& have, const ydc_stream_ca
 // Layout and allocation of everything a stream of these bounds has, into `sm` (released, or
 // fresh). Its contents are not defined before stream_reset; after a failure the caller releases it.
 int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps& k, uint32_t max_book,
-                 uint32_t max_withdraw) {
+                 uint32_t max_withdraw, uint32_t quota) {
   sm.caps = k;
   sm.max_book = max_book;
   sm.max_withdraw = max_withdraw;
+  sm.quota.on = quota != 0;  // (Stream::Quota::code)
+  sm.quota.max_overrides = quota ? quota - 1 : 0;
   const uint32_t max_updates = k.max_updates, max_releases = k.max_releases, max_tasks = k.max_tasks;
   const uint32_t max_waiting = k.max_waiting, max_rows = k.max_rows;
   const bool leased = sm.leased();
@@ -4769,6 +4832,8 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
   // ... and behind it, with withdrawal, the staged tags and their number.
   const size_t o_wdt = max_withdraw ? section(&off, (size_t)max_withdraw * 8) : 0;
   const size_t o_wdn = max_withdraw ? section(&off, 4) : 0;
+  // ... and behind that, with a quota, the number of the tick's new requests.
+  const size_t o_qn = quota ? section(&off, 4) : 0;
   auto arena_at = [&](uint8_t* b) {
     TickArena a{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
                 (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
@@ -4797,6 +4862,7 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
       a.wd_tag = (uint64_t*)(b + o_wdt);
       a.wd_n = (uint32_t*)(b + o_wdn);
     }
+    if (quota) a.q_n = (uint32_t*)(b + o_qn);
     return a;
   };
   sm.in_bytes = off;
@@ -4962,6 +5028,35 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
     sm.withdraw.h_done = (WithdrawDone*)(sm.withdraw.h_res.p + r_done);
     sm.withdraw.z_done = (WithdrawDone*)(sm.withdraw.h_res.z + r_done);
   }
+  if (quota) {
+    // HBM: the table (word | held | asked), the settings, the per-request arrays, the counters and the
+    // chain words. Page-locked: the admitted counts and the done block.
+    auto& q = sm.quota;
+    const uint32_t slots = quota_slots(max_tasks), MO = q.max_overrides;
+    q.tiles = ceil_div(max_tasks, kQuotaTile);
+    size_t d_off = 0, r_off = 0;
+    auto qsec = [&](size_t bytes) { return section(&d_off, bytes); };
+    const size_t o_word = qsec((size_t)slots * 8), o_held = qsec((size_t)slots * 4), o_asked = qsec((size_t)slots * 4);
+    const size_t o_oip = qsec((size_t)MO * 4), o_ocap = qsec((size_t)MO * 4), o_hdr = qsec(8);
+    const size_t o_slot = qsec((size_t)max_tasks * 4), o_imm = qsec((size_t)max_tasks * 4);
+    const size_t o_pre = qsec((size_t)max_tasks * 4), o_env = qsec((size_t)max_tasks * 4);
+    const size_t o_cnt = qsec(16), o_chain = qsec((size_t)q.tiles * 4);
+    HIP_TRY(c, q.d.reserve(d_off));
+    uint8_t* b = q.d.p;
+    q.tb = QuotaTable{(unsigned long long*)(b + o_word), (uint32_t*)(b + o_held), (uint32_t*)(b + o_asked), slots - 1};
+    q.caps = QuotaCaps{(uint32_t*)(b + o_oip), (uint32_t*)(b + o_ocap), (uint32_t*)(b + o_hdr), MO};
+    q.tk = QuotaTick{(uint32_t*)(b + o_slot), (uint32_t*)(b + o_imm), (uint32_t*)(b + o_pre), (uint32_t*)(b + o_env),
+                     (uint32_t*)(b + o_cnt), (uint32_t*)(b + o_chain)};
+    const size_t r_imm = section(&r_off, (size_t)max_tasks * 4), r_pre = section(&r_off, (size_t)max_tasks * 4);
+    const size_t r_done = section(&r_off, sizeof(QuotaDone));
+    HIP_TRY(c, q.h_res.reserve(r_off));
+    q.h_imm = (uint32_t*)(q.h_res.p + r_imm);
+    q.z_imm = (uint32_t*)(q.h_res.z + r_imm);
+    q.h_pre = (uint32_t*)(q.h_res.p + r_pre);
+    q.z_pre = (uint32_t*)(q.h_res.z + r_pre);
+    q.h_done = (QuotaDone*)(q.h_res.p + r_done);
+    q.z_done = (QuotaDone*)(q.h_res.z + r_done);
+  }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
   sm.stale = true;
   return YDC_OK;
@@ -4992,6 +5087,11 @@ int stream_reset(ydc_context* c, ydc_context::Stream& sm) {
   if (sm.max_withdraw) {  // (an empty list)
     HIP_TRY(c, hipMemsetAsync(sm.withdraw.list.n, 0, 4, c->stream));
     std::memset(sm.withdraw.h_done, 0, sizeof(WithdrawDone));
+  }
+  if (sm.quota.on) {  // (every slot of the table free; the settings follow at the next tick)
+    HIP_TRY(c, hipMemsetAsync(sm.quota.d.p, 0, sm.quota.d.cap, c->stream));
+    std::memset(sm.quota.h_done, 0, sizeof(QuotaDone));
+    sm.quota.host.dirty = true;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   sm.active = true;
@@ -5087,13 +5187,13 @@ int stream_begin(ydc_context* c, const ydc_stream_caps& k) {
   join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   stream_release(c);
-  if (int rc = stream_alloc(c, c->stream_mode, k, 0, 0)) return rc;
+  if (int rc = stream_alloc(c, c->stream_mode, k, 0, 0, 0)) return rc;
   return stream_reset(c, c->stream_mode);
 }
 
 // The open stream in a second, larger set of buffers (ydc_stream_reserve, ydc_stream_book_begin,
-// ydc_stream_withdraw_begin).
-int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, uint32_t max_withdraw) {
+// ydc_stream_withdraw_begin, ydc_stream_quota_begin). quota: Stream::Quota::code.
+int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, uint32_t max_withdraw, uint32_t quota) {
   auto& sm = c->stream_mode;
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
@@ -5101,7 +5201,7 @@ int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, u
   // A second set of buffers, filled from the first, which is released only once that has worked:
   // after any failure the stream is as it was.
   ydc_context::Stream grown;
-  int rc = stream_alloc(c, grown, k, max_book, max_withdraw);
+  int rc = stream_alloc(c, grown, k, max_book, max_withdraw, quota);
   if (rc == YDC_OK) rc = stream_reset(c, grown);
   if (rc == YDC_OK) rc = stream_migrate(c, sm, grown);
   if (rc != YDC_OK) {
@@ -5114,6 +5214,9 @@ int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, u
   grown.inspect = std::move(sm.inspect);  // (the detail records have moved already: stream_migrate)
   grown.book.staged = std::move(sm.book.staged);
   grown.withdraw.host = std::move(sm.withdraw.host);  // (a pending staging and the last result go along)
+  grown.quota.host = std::move(sm.quota.host);        // (the settings and the last result go along)
+  grown.quota.host.dirty = true;                      // (... and the new device copy has to follow them)
+  grown.quota.host.table_dirty = false;
   std::swap(sm, grown);
   stream_release(grown);  // (the old buffers and the old captures; sm.stale: the step is captured again)
   return YDC_OK;
@@ -5152,7 +5255,7 @@ int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
   const ydc_stream_caps k = stream_caps_grown(sm.caps, *want);  // (growth only)
   if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, k, sm.max_book)) return rc;
   if (!std::memcmp(&k, &sm.caps, sizeof k)) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, k, sm.max_book, sm.max_withdraw);
+  return stream_regrow(c, k, sm.max_book, sm.max_withdraw, sm.quota.code());
 }
 
 }  // extern "C"
@@ -5297,7 +5400,7 @@ int ydc_stream_book_begin(ydc_context* c, uint32_t max_book) {
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_begin: no leased, waiting-and-leased or rpc stream is open");
   if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, sm.caps, max_book)) return rc;
   if (max_book <= sm.max_book) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, ydc_stream_caps(sm.caps), max_book, sm.max_withdraw);  // (a copy: regrow replaces the stream)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), max_book, sm.max_withdraw, sm.quota.code());  // (a copy: regrow replaces the stream)
 }
 
 int ydc_stream_book_stage(ydc_context* c, const uint64_t* servant_task_id, const uint64_t* digest_key,
@@ -5324,7 +5427,7 @@ int ydc_stream_withdraw_begin(ydc_context* c, uint32_t max_withdraw) {
   if (max_withdraw > (1u << 30))
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "max_withdraw %u out of range (1 .. 2^30)", max_withdraw);
   if (max_withdraw <= sm.max_withdraw) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, max_withdraw);  // (a copy: regrow replaces the stream)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, max_withdraw, sm.quota.code());  // (a copy: regrow replaces the stream)
 }
 
 int ydc_stream_withdraw_stage(ydc_context* c, const uint64_t* tags, uint32_t n) {
@@ -5354,6 +5457,73 @@ int ydc_stream_withdraw_result(ydc_context* c, uint32_t* out_count, uint32_t cap
   if (n && !out_count) return YDC_ERR_INVALID_ARGUMENT;
   for (uint32_t i = 0; i < n; ++i) out_count[i] = w.counts[w.place[i]];
   if (out_n_withdrawn) *out_n_withdrawn = std::accumulate(w.counts.begin(), w.counts.end(), 0u);
+  return YDC_OK;
+}
+
+int ydc_stream_quota_begin(ydc_context* c, uint32_t max_overrides) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.waiting() || !sm.leased())
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_begin: no waiting-and-leased or rpc stream is open");
+  if (!sm.inspect.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_begin: inspection is off, so no lease says whose it is "
+                "(ydc_stream_inspect_begin)");
+  if (max_overrides > (1u << 24))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "max_overrides %u out of range (0 .. 2^24)", max_overrides);
+  // (a servant index is below the context's bound of servants: none may be YDC_IDX_OVER_QUOTA)
+  const uint32_t bound = c->max_servants ? c->max_servants : YDC_IDX_WITHDRAWN;
+  if (bound > YDC_IDX_OVER_QUOTA)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_begin: a context of up to %u servants could answer index "
+                "%u, which is YDC_IDX_OVER_QUOTA (give ydc_create a max_servants)", bound, YDC_IDX_OVER_QUOTA);
+  if (sm.quota.on && max_overrides <= sm.quota.max_overrides) return YDC_OK;  // (nothing to do: the captured step stays)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, sm.max_withdraw, max_overrides + 1);  // (a copy: regrow replaces the stream)
+}
+
+int ydc_stream_quota_set(ydc_context* c, uint32_t default_cap, const uint32_t* requestor_ip, const uint32_t* cap,
+                         uint32_t n) {
+  if (!c || (n && (!requestor_ip || !cap))) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.quota.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_set: the stream has no quota (ydc_stream_quota_begin)");
+  if (n > sm.quota.max_overrides)
+    return fail(c, YDC_ERR_CAPACITY, "%u overrides > max_overrides %u", n, sm.quota.max_overrides);
+  // Sorted by requestor (the kernels search the list); a requestor named twice is refused.
+  std::vector<uint32_t> order(n);
+  std::iota(order.begin(), order.end(), 0u);
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return requestor_ip[a] < requestor_ip[b]; });
+  for (uint32_t i = 1; i < n; ++i)
+    if (requestor_ip[order[i]] == requestor_ip[order[i - 1]])
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_set: requestor %u has two overrides", requestor_ip[order[i]]);
+  auto& h = sm.quota.host;
+  h.default_cap = default_cap;
+  h.ip.resize(n);
+  h.cap.resize(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    h.ip[i] = requestor_ip[order[i]];
+    h.cap[i] = cap[order[i]];
+  }
+  h.dirty = true;  // (the device copy follows in front of the next accepted tick)
+  return YDC_OK;
+}
+
+int ydc_stream_quota_result(ydc_context* c, uint32_t* out_immediate, uint32_t* out_prefetch, uint32_t cap,
+                            uint32_t* out_n, uint32_t* out_rows_clipped, uint32_t* out_n_refused) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.quota.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_result: the stream has no quota (ydc_stream_quota_begin)");
+  const auto& h = sm.quota.host;
+  const uint32_t n = (uint32_t)h.imm.size();
+  *out_n = n;
+  if (cap < n) return fail(c, YDC_ERR_CAPACITY, "%u new requests > cap %u", n, cap);
+  if (n && (!out_immediate || (sm.rpc() && !out_prefetch))) return YDC_ERR_INVALID_ARGUMENT;
+  if (n) std::memcpy(out_immediate, h.imm.data(), (size_t)n * 4);
+  if (n && out_prefetch) {
+    if (sm.rpc()) std::memcpy(out_prefetch, h.pre.data(), (size_t)n * 4);
+    else std::memset(out_prefetch, 0, (size_t)n * 4);
+  }
+  if (out_rows_clipped) *out_rows_clipped = h.rows_clipped;
+  if (out_n_refused) *out_n_refused = h.n_refused;
   return YDC_OK;
 }
 
@@ -6388,6 +6558,28 @@ static void stream_withdraw_stage_tick(ydc_context::Stream& sm) {
   w.tags.clear();
 }
 
+// With a quota, in front of an accepted tick: the settings' device copy follows the host's (after a set,
+// in a grown stream), and a table that a failed tick left behind is cleared. The stream is idle.
+static int stream_quota_sync(ydc_context* c) {
+  auto& q = c->stream_mode.quota;
+  auto& h = q.host;
+  if (h.table_dirty) {
+    HIP_TRY(c, hipMemset(q.tb.word, 0, ((size_t)q.tb.mask + 1) * 8));
+    h.table_dirty = false;
+  }
+  if (!h.dirty) return YDC_OK;
+  const uint32_t n = (uint32_t)h.ip.size();
+  if (n > q.max_overrides) return fail(c, YDC_ERR_NOT_CONVERGED, "%u overrides > max_overrides %u", n, q.max_overrides);
+  if (n) {
+    HIP_TRY(c, hipMemcpy(const_cast<uint32_t*>(q.caps.ip), h.ip.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(const_cast<uint32_t*>(q.caps.cap), h.cap.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  }
+  const uint32_t hdr[2] = {h.default_cap, n};
+  HIP_TRY(c, hipMemcpy(const_cast<uint32_t*>(q.caps.hdr), hdr, sizeof hdr, hipMemcpyHostToDevice));
+  h.dirty = false;
+  return YDC_OK;
+}
+
 // Step 4: the tick into the arena (padding = no-ops), the staged columns consumed, the lease header
 // and the tick number written.
 static void stream_tick_stage(ydc_context* c, const StreamCall& t, const TickState& ts) {
@@ -6449,6 +6641,7 @@ static void stream_tick_stage(ydc_context* c, const StreamCall& t, const TickSta
     *h.lh = LeaseHdr{lt->now, lt->n_renew, lt->n_free, lt->n_rep, n_ids, sm.lease_tick, 0};
   }
   if (sm.max_withdraw) stream_withdraw_stage_tick(sm);
+  if (sm.quota.on) *h.q_n = n_tasks;
   if (t.rt) {
     put(h.nimm, t.rt->n_imm, n_tasks, 4);
     put(h.npre, t.rt->n_pre, n_tasks, 4);
@@ -6564,6 +6757,18 @@ static int stream_tick_finish(ydc_context* c, const StreamCall& t, const TickSta
       return fail(c, YDC_ERR_NOT_CONVERGED, "withdrawal: counts of %u tags, %u staged", sm.withdraw.h_done->n, w.n_unique);
     std::copy_n(sm.withdraw.h_count, w.n_unique, w.counts.begin());
   }
+  uint32_t n_refused = 0;
+  if (sm.quota.on) {  // (the label pass has stored what the clip admitted)
+    auto& q = sm.quota;
+    const QuotaDone& d = *q.h_done;
+    if (d.tick_no != sm.lease_tick || d.n != n_tasks)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "quota: result of tick %u with %u requests (expected %u, %u)", d.tick_no, d.n,
+                  sm.lease_tick, n_tasks);
+    q.host.imm.assign(q.h_imm, q.h_imm + n_tasks);
+    if (t.rt) q.host.pre.assign(q.h_pre, q.h_pre + n_tasks);
+    q.host.rows_clipped = d.rows_clipped;
+    q.host.n_refused = n_refused = d.n_refused;
+  }
   if (t.rt) return stream_rpc_finish(c, t, ts);
   c->stats.n_tasks = n_tasks;
   c->stats.env_not_found -= std::min(c->stats.env_not_found, sm.caps.max_tasks - n_tasks);  // padding
@@ -6571,6 +6776,10 @@ static int stream_tick_finish(ydc_context* c, const StreamCall& t, const TickSta
     if (int rc = stream_wait_finish(c, t.wt, n_tasks)) return rc;
   if (t.lt)
     if (int rc = stream_lease_finish(c, t.lt, n_tasks, ts.n_ids)) return rc;
+  if (n_refused) {  // (a refused request was placed as padding: the statistics are those of a tick without it)
+    c->stats.n_tasks -= std::min(c->stats.n_tasks, n_refused);
+    c->stats.env_not_found -= std::min(c->stats.env_not_found, n_refused);
+  }
   if (n_tasks && t.out_servant_idx != sm.h_out) std::memcpy(t.out_servant_idx, sm.h_out, (size_t)n_tasks * 4);
   return YDC_OK;
 }
@@ -6587,8 +6796,13 @@ static int stream_tick(ydc_context* c, StreamCall t) {
     if (int rc = stream_tick_expiry(c, t, &ts)) return rc;
   if (sm.stale || c->tables_dirty)
     if (int rc = stream_capture(c)) return rc;
+  if (sm.quota.on)
+    if (int rc = stream_quota_sync(c)) return rc;
   stream_tick_stage(c, t, ts);
-  if (int rc = stream_tick_run(c, t, &ts)) return rc;
+  if (int rc = stream_tick_run(c, t, &ts)) {
+    sm.quota.host.table_dirty = sm.quota.on;  // (its label pass may not have run)
+    return rc;
+  }
   if (ts.parked) {  // (behind a removal the parked leases go first)
     ts.parked = false;
     if (int rc = alive_orphans(c)) return rc;
@@ -6973,7 +7187,7 @@ int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc
   // A second stream, complete before it becomes the context's.
   ydc_context::Stream fresh;
   auto load = [&]() -> int {
-    if (int rc = stream_alloc(c, fresh, k, h.max_book, 0)) return rc;  // (withdrawal stays off, like inspection)
+    if (int rc = stream_alloc(c, fresh, k, h.max_book, 0, 0)) return rc;  // (withdrawal and the quota stay off, like inspection)
     if (int rc = stream_reset(c, fresh)) return rc;
     hipStream_t st = c->stream;
     if (fresh.leased()) {

@@ -56,7 +56,8 @@ class EventStream:
 
     def commit(self, servant_idx):
         """Feeds the placement of the tick's requests back (grants become live)."""
-        granted = servant_idx[servant_idx < binding.IDX_ENV_NOT_FOUND]
+        # (below every sentinel: IDX_OVER_QUOTA, the lowest, is never a servant)
+        granted = servant_idx[servant_idx < binding.IDX_OVER_QUOTA]
         np.add.at(self.running, granted, 1)
         self.live = np.concatenate([self.live, granted.astype(np.uint32)])
 
@@ -73,6 +74,22 @@ def rpc_grants(result, i):
     a = int(result["row_off"][i])
     b = a + int(result["n_granted"][i])
     return result["servants"][a:b], result["task_ids"][a:b]
+
+
+def rpc_admitted(result, adm_immediate, adm_prefetch):
+    """A stream_tick_rpc result of a stream with a quota (binding.Context.stream_quota_begin), unpacked
+    by ADMITTED rows: the tick laid its expanded outputs out as if every request had asked for what
+    it was admitted (binding.Context.stream_quota_result), so request i's rows begin at the sum of
+    adm_immediate + adm_prefetch over the requests in front of it and a request answered
+    IDX_OVER_QUOTA has none. -> the result with row_off, servants and task_ids by that layout;
+    rpc_grants then reads it as usual."""
+    rows = np.asarray(adm_immediate, np.int64) + np.asarray(adm_prefetch, np.int64)
+    row_off = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    out = dict(result)
+    out["row_off"] = row_off
+    out["servants"] = result["servants"][:int(row_off[-1])]
+    out["task_ids"] = result["task_ids"][:int(row_off[-1])]
+    return out
 
 
 def rpc_resolved_grants(result, j):
