@@ -67,6 +67,12 @@ tests/native/lane_rule_test: tests/native/lane_rule_test.cc $(CSRC)/lane_rule.h
 	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tests/native/lane_rule_test.cc
 lanerule: tests/native/lane_rule_test
 	tests/native/lane_rule_test
+# The occupancy rule of a batch (occupancy_plan.h: the bin sort's width) against a written table,
+# ASan + UBSan, no GPU (tests/test_occupancy_plan.py builds and runs the same program).
+tests/native/occupancy_plan_test: tests/native/occupancy_plan_test.cc $(CSRC)/occupancy_plan.h
+	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tests/native/occupancy_plan_test.cc
+occupancyplan: tests/native/occupancy_plan_test
+	tests/native/occupancy_plan_test
 # The admission arithmetic (admit_clip.h) against its written rule with 128-bit sums, ASan + UBSan, no GPU
 # (tests/test_stream_requestor_model.py builds and runs the same program).
 tests/native/admit_clip_test: tests/native/admit_clip_test.cc $(CSRC)/admit_clip.h
@@ -74,7 +80,7 @@ tests/native/admit_clip_test: tests/native/admit_clip_test.cc $(CSRC)/admit_clip
 admitclip: tests/native/admit_clip_test
 	tests/native/admit_clip_test
 clean:
-	rm -f yadcc_amd/libydc.so tests/model/libmodel.so tests/native/lane_rule_test tests/native/admit_clip_test
+	rm -f yadcc_amd/libydc.so tests/model/libmodel.so tests/native/lane_rule_test tests/native/admit_clip_test tests/native/occupancy_plan_test
 	$(MAKE) -C tests/native clean
 	$(MAKE) -C oracle clean
-.PHONY: all lib probe oracle model native tsan asan flatmap shardplan admitclip lanerule clean
+.PHONY: all lib probe oracle model native tsan asan flatmap shardplan admitclip lanerule occupancyplan clean

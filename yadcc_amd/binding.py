@@ -315,7 +315,7 @@ _TUNE_KEYS = ("DEBUG_SIM", "CHUNK_SIZE", "TARGET_CHUNKS", "FUSED_CLASS", "OWN_GU
               "GROUP_WALK", "WALK_PACKED", "ZONE_GUESS", "ZONE_LEAD", "ZONE_TRAIL", "ZONE_MAX_CHUNKS",
               "PACKED_CLASS", "SHARD_SORT", "BINSORT", "FUSE_PASSES", "WARM_UP",
               "HAND_TRIES", "LANES", "CP_EVERY", "WALK_PARK", "WIDE", "WIDE_LISTS", "GROUP_BINSORT",
-              "BINSORT_VERIFY", "BINSORT_MAX_SLOTS", "SHARD_MARGIN",
+              "BINSORT_VERIFY", "BINSORT_MAX_SLOTS", "BIN_THREADS", "SHARD_MARGIN",
               "ROUNDS_PER_CHECK", "WALK_AFTER", "OUTCOME_STORE", "STREAM_GRAPH", "COMMIT_SWAP", "RELEASE_COUNTED", "SMALL_BATCH", "RESIDENT", "RESIDENT_IDLE_MS", "PACKED_TICK", "IPC_SLOT_WORDS", "IPC_TIMEOUT_MS", "IPC_COARSE",
               "REQUESTOR_COMBINE")
 _tune_injected = ""

@@ -366,13 +366,20 @@ __global__ __launch_bounds__(256) void k_front_bins(ServantTable sv, uint32_t n_
 // order — the global order inside the bin. (3) A stable partition by class gives the places in
 // the class lists. A record lives in LDS as one word: key bits below the bin | slot | class.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kBinThreads = 1024;
-constexpr uint32_t kBinWaves = kBinThreads / 64;
-constexpr uint32_t kBinRounds = kBinCap / kBinThreads;  // records per thread
-// LDS words: two record buffers, the counter table ([waves][256]; the tile tables before that),
-// digit totals / starts, class-list cursors.
-constexpr uint32_t kBinLdsWords = 2 * kBinCap + kBinWaves * 256 + 256 + 256;
-static_assert(2 * kBinMaxTiles + 1 <= kBinWaves * 256 + 256, "tile tables alias the counter table");
+// The kernel is built for two workgroup widths (occupancy_plan.h picks one per plan): a bin holds
+// at most kBinCap records either way, a narrower workgroup walks them in more rounds per thread.
+template <uint32_t THREADS>
+struct BinShape {
+  static_assert(THREADS >= 256 && THREADS <= 1024 && kBinCap % THREADS == 0 && kBinMaxTiles % THREADS == 0,
+                "a digit per thread in the counting passes; whole rounds");
+  static constexpr uint32_t kWaves = THREADS / 64;
+  static constexpr uint32_t kRounds = kBinCap / THREADS;        // records per thread
+  static constexpr uint32_t kTilesPer = kBinMaxTiles / THREADS;  // run-table entries per thread
+  // LDS words: two record buffers (the tile tables of step 1 live in the second), the counter
+  // table ([waves][256]), digit totals / starts, class-list cursors.
+  static constexpr uint32_t kLdsWords = 2 * kBinCap + kWaves * 256 + 256 + 256;
+};
+static_assert(2 * kBinMaxTiles <= kBinCap, "tile tables alias the second record buffer (+ one word of the counter table)");
 
 struct BinSortArgs {
   const uint2* stage;
@@ -390,7 +397,11 @@ struct BinSortArgs {
   uint32_t* level_tab;
 };
 
-__global__ __launch_bounds__(kBinThreads, 8) void k_bin_sort(BinSortArgs a, DeviceParams* prm, PrefixArgs pa) {
+template <uint32_t THREADS>
+__global__ __launch_bounds__(THREADS, 8) void k_bin_sort(BinSortArgs a, DeviceParams* prm, PrefixArgs pa) {
+  using Shape = BinShape<THREADS>;
+  constexpr uint32_t kBinThreads = THREADS, kBinWaves = Shape::kWaves, kBinRounds = Shape::kRounds,
+                     kTilesPer = Shape::kTilesPer;
   extern __shared__ __attribute__((aligned(16))) uint32_t bsm[];
   __shared__ uint32_t lds[17];
 #ifdef YDC_PHASE_PROBE
@@ -412,21 +423,21 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_sort(BinSortArgs a, Devi
   uint32_t* tab = bsm + 2 * kBinCap;           // [kBinWaves][256]
   uint32_t* dtot = tab + kBinWaves * 256;      // [256]
   uint32_t* cbase = dtot + 256;                // [256] next free position of every class list
-  uint32_t* rsrc = tab;                        // [n_tiles] (step 1 only) where the tile's run sits in the staging array
-  uint32_t* rstart = tab + kBinMaxTiles;       // [n_tiles + 1] first record of the tile's run (runs into dtot)
+  uint32_t* rsrc = buf1;                       // [n_tiles] (step 1 only) where the tile's run sits in the staging array
+  uint32_t* rstart = buf1 + kBinMaxTiles;      // [n_tiles + 1] first record of the tile's run (runs into tab)
   const uint32_t C = a.n_classes, row = C + 1, j = blockIdx.x, T = a.bt.n_tiles;
   const uint32_t lo = a.bt.base[(size_t)j * row + C], hi = a.bt.base[(size_t)(j + 1) * row + C];
   const uint32_t n = hi - lo;
-  // The bin's runs: tiles 2 * threadIdx.x and 2 * threadIdx.x + 1 (T <= 2 * kBinThreads).
-  uint32_t r0 = 0, r1 = 0, b0 = 0, b1 = 0;
-  const uint32_t t0 = 2 * threadIdx.x;
-  if (t0 < T) {
-    r0 = a.bt.runs[(size_t)t0 * a.bt.n_bins + j];
-    b0 = a.bt.tile_base[t0];
-  }
-  if (t0 + 1 < T) {
-    r1 = a.bt.runs[(size_t)(t0 + 1) * a.bt.n_bins + j];
-    b1 = a.bt.tile_base[t0 + 1];
+  // The bin's runs: tiles kTilesPer * threadIdx.x + u (T <= kBinMaxTiles == kTilesPer * kBinThreads).
+  uint32_t rn[kTilesPer], rb[kTilesPer];
+  const uint32_t t0 = kTilesPer * threadIdx.x;
+#pragma unroll
+  for (uint32_t u = 0; u < kTilesPer; ++u) {
+    rn[u] = rb[u] = 0;
+    if (t0 + u < T) {
+      rn[u] = a.bt.runs[(size_t)(t0 + u) * a.bt.n_bins + j];
+      rb[u] = a.bt.tile_base[t0 + u];
+    }
   }
   if (n == 0 || prm->n_slots == 0) return;
   if (n > kBinCap) {
@@ -442,14 +453,17 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_sort(BinSortArgs a, Devi
   // ---- (1) the runs, tile by tile
   {
     uint32_t total;
-    const uint32_t ex = block_exclusive_scan((r0 & 0xFFFFu) + (r1 & 0xFFFFu), lds, &total);
-    if (t0 < T) {
-      rstart[t0] = ex;
-      rsrc[t0] = b0 + (r0 >> 16);
-    }
-    if (t0 + 1 < T) {
-      rstart[t0 + 1] = ex + (r0 & 0xFFFFu);
-      rsrc[t0 + 1] = b1 + (r1 >> 16);
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < kTilesPer; ++u) mine += rn[u] & 0xFFFFu;
+    uint32_t ex = block_exclusive_scan(mine, lds, &total);
+#pragma unroll
+    for (uint32_t u = 0; u < kTilesPer; ++u) {
+      if (t0 + u < T) {
+        rstart[t0 + u] = ex;
+        rsrc[t0 + u] = rb[u] + (rn[u] >> 16);
+      }
+      ex += rn[u] & 0xFFFFu;
     }
     if (threadIdx.x == 0) rstart[T] = total;
     __syncthreads();
@@ -484,19 +498,17 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_sort(BinSortArgs a, Devi
     for (uint32_t t = threadIdx.x; t < kBinWaves * 256; t += blockDim.x) tab[t] = 0;
     __syncthreads();
     uint32_t* wtab = tab + wave * 256;
-    uint32_t e[kBinRounds], dig[kBinRounds], rk[kBinRounds];
+    // Only the ranks stay in registers across the barriers (a narrow workgroup has eight rounds
+    // per thread): the scatter reads the record again and takes its digit again.
+    uint32_t rk[kBinRounds];
 #pragma unroll
     for (int r = 0; r < (int)kBinRounds; ++r) {
-      e[r] = dig[r] = rk[r] = 0;
+      rk[r] = 0;
       if ((uint32_t)r < R) {  // (uniform)
         const uint32_t idx = (wave * R + r) * 64 + lane;
         const bool valid = idx < n;
         uint32_t d = 0;
-        if (valid) {
-          e[r] = src[idx];
-          d = (e[r] >> (sbits + sh)) & ((1u << dbits) - 1);
-        }
-        dig[r] = d;
+        if (valid) d = (src[idx] >> (sbits + sh)) & ((1u << dbits) - 1);
         uint64_t peers = __ballot(valid);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -531,7 +543,10 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_sort(BinSortArgs a, Devi
     for (int r = 0; r < (int)kBinRounds; ++r) {
       if ((uint32_t)r < R) {
         const uint32_t idx = (wave * R + r) * 64 + lane;
-        if (idx < n) dst[dtot[dig[r]] + wtab[dig[r]] + rk[r]] = e[r];
+        if (idx < n) {
+          const uint32_t e = src[idx], d = (e >> (sbits + sh)) & ((1u << dbits) - 1);
+          dst[dtot[d] + wtab[d] + rk[r]] = e;
+        }
       }
     }
     __syncthreads();
@@ -540,7 +555,7 @@ __global__ __launch_bounds__(kBinThreads, 8) void k_bin_sort(BinSortArgs a, Devi
     dst = t;
   }
   YDC_BPROBE(3);  // counting passes done
-  // ---- (3) places. Positions are walked 1024 at a time; within a round (wave, lane) order ==
+  // ---- (3) places. Positions are walked a workgroup's width at a time; within a round (wave, lane) order ==
   // position order, so "earlier slots of the same class" = earlier rounds (cbase) + earlier
   // waves of this round (tab) + lower lanes of this wave (ballot match on the class bits).
   for (uint32_t t = threadIdx.x; t < kBinWaves * 256; t += blockDim.x) tab[t] = 0;

@@ -27,6 +27,7 @@
 #include "dispatch_core.h"
 #include "host_tables.h"
 #include "lane_rule.h"
+#include "occupancy_plan.h"
 #include "registry_mirror.h"
 #include "shard_plan.h"
 #include "kernels.h"
@@ -184,6 +185,7 @@ struct BatchPlan {
   bool zone_eligible = false;   // ... or would, if zone_decide had found it worth its while
   uint32_t n_bins = 0, bin_shift = 0, bin_slot_bits = 0, bin_cls_bits = 0;
   uint32_t bin_group = 0, bin_tiles = 0;  // servants per slot tile, slot tiles (k_front_bins)
+  uint32_t bin_threads = kBinThreadsWide;  // width of a k_bin_sort workgroup (occupancy_plan.h)
   ServantTable sv{};
   ClassLists L{};
   TaskTable T{};
@@ -662,8 +664,10 @@ struct ydc_context {
   uint32_t opt_chunk_size = 0;     // 0: automatic
   uint32_t opt_target_chunks = 2048;
   // 16 KB of LDS per matching wave = 10 waves per CU. Smaller rings (more waves per CU, shorter
-  // chunks) were measured and bring nothing: the waves saturate VALU issue at ~2 per SIMD.
+  // chunks) were measured and bring nothing: the waves saturate VALU issue at ~2 per SIMD. Nor do
+  // rings sized to the class count help the batch on the other lane (NOTES_rejected.md 7.1).
   uint32_t opt_ring_total = 0;  // entries of a matching wave's rings; 0: chosen per batch (YDC_RING_TOTAL)
+  uint32_t opt_bin_threads = 0;  // width of a k_bin_sort workgroup, 512 or 1024; 0: occupancy_plan.h's rule
   bool opt_group_walk = true;  // sparse eligibility: the walk in groups of 64 requests (YDC_GROUP_WALK=0: one at a time)
   uint32_t opt_zone_guess = 1;  // start guesses around the dedicated tier's end from a walk of that stretch: 1 where it pays, 2 always, 0 never
   // lead: where the walk starts, in levels before the tier's end (the first chunk boundary inside
@@ -1256,6 +1260,7 @@ int ydc_create(int device, uint32_t max_servants, uint32_t max_tasks, uint32_t m
   if (const char* s = tune_value("packed_class")) c->opt_packed_class = atoi(s) != 0;
   if (const char* s = tune_value("shard_sort")) c->opt_shard_sort = atoi(s) != 0;
   if (const char* s = tune_value("binsort")) c->opt_binsort = atoi(s) != 0;
+  if (const char* s = tune_value("bin_threads")) c->opt_bin_threads = (uint32_t)std::max(0, atoi(s));
   if (const char* s = tune_value("stream_graph")) c->opt_stream_graph = atoi(s) != 0;
   if (const char* s = tune_value("walk_park")) c->opt_walk_park = atoi(s) != 0;
   if (const char* s = tune_value("fuse_passes")) c->opt_fuse_passes = atoi(s) != 0;
@@ -1572,10 +1577,11 @@ int ydc_get_running(ydc_context* c, uint32_t* out, uint32_t n) {
 namespace {
 
 // for_window: the plan of a multi-GPU batch whose slot sort is sharded (k_window generates only a
-// key window of the slots: radix pipeline).
+// key window of the slots: radix pipeline). beside: the batch may run next to one on the other
+// lane (occupancy_plan.h).
 bool zone_decide(ydc_context* c, uint32_t N, uint32_t K, uint32_t C);
 
-int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = false) {
+int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = false, bool beside = false) {
   BatchPlan& p = *out;
   p = BatchPlan{};
   if (c->tables_dirty)
@@ -1680,6 +1686,7 @@ int plan_batch(ydc_context* c, uint32_t N, BatchPlan* out, bool for_window = fal
     // (host_tables.h: bin_tile_start; at most kBinMaxGroup servants and 2048 slots each).
     p.bin_group = kBinMaxGroup;
     p.bin_tiles = (uint32_t)c->tables.bin_tile_start.size() - 1;
+    p.bin_threads = bin_sort_threads(c->opt_bin_threads, beside);
     if (p.bin_shift + p.bin_slot_bits + p.bin_cls_bits > 32 || p.bin_tiles > kBinMaxTiles) p.binsort = false;
   }
   if (p.binsort) {
@@ -1969,8 +1976,17 @@ int enqueue_sort(ydc_context* c, const BatchPlan& p, bool prefix_pending) {
                    p.C, p.gbits, p.bin_slot_bits, p.bin_cls_bits, c->d_slot_base.p, c->d_cls_begin.p,
                    (uint2*)c->d_keys[1].p, c->d_rank_to_g.p,
                    c->n_parts <= 1 ? c->d_level_tab.p : nullptr};
-    YDC_LAUNCH(c, "k_bin_sort", k_bin_sort, dim3(p.n_bins + (pending_prefix ? 1 : 0)), dim3(kBinThreads),
-               (size_t)kBinLdsWords * 4, c->stream, ba, c->d_prm.p, pending_prefix ? pa : PrefixArgs{});
+    // (the workgroup's width: occupancy_plan.h)
+    const dim3 grid(p.n_bins + (pending_prefix ? 1 : 0));
+    if (p.bin_threads == kBinThreadsNarrow) {
+      YDC_LAUNCH(c, "k_bin_sort", k_bin_sort<kBinThreadsNarrow>, grid, dim3(kBinThreadsNarrow),
+                 (size_t)BinShape<kBinThreadsNarrow>::kLdsWords * 4, c->stream, ba, c->d_prm.p,
+                 pending_prefix ? pa : PrefixArgs{});
+    } else {
+      YDC_LAUNCH(c, "k_bin_sort", k_bin_sort<kBinThreadsWide>, grid, dim3(kBinThreadsWide),
+                 (size_t)BinShape<kBinThreadsWide>::kLdsWords * 4, c->stream, ba, c->d_prm.p,
+                 pending_prefix ? pa : PrefixArgs{});
+    }
     mark(c, 3);
     mark(c, 4);
     return YDC_OK;
@@ -3114,7 +3130,10 @@ int ydc_dispatch_device_async(ydc_context* c, const ydc_task_soa* tk, uint32_t N
     pd.active = false;
     return rc;
   };
-  if (int rc = plan_batch(c, N, &pd.plan)) return give_up(rc);
+  // (beside: a context that may use the second lane at all — this batch or the next one behind it)
+  const bool beside = c->opt_lanes && c->own_stream.s != nullptr && c->group.n_ranks == 0 && c->group.via == nullptr &&
+                      !c->stream_mode.active;
+  if (int rc = plan_batch(c, N, &pd.plan, false, beside)) return give_up(rc);
   if (behind_rerun || !pd.plan.wave_path || c->profiling || c->debug_verify_binsort) {
     // (registries without the wave path have host-checked rounds: placed when waited for)
     pd.rerun = true;
