@@ -945,6 +945,67 @@ int ydc_stream_quota_set(ydc_context* ctx, uint32_t default_cap, const uint32_t*
 int ydc_stream_quota_result(ydc_context* ctx, uint32_t* out_immediate, uint32_t* out_prefetch, uint32_t cap,
                             uint32_t* out_n, uint32_t* out_rows_clipped, uint32_t* out_n_refused);
 
+/* ---- departure: a requestor's leases and waiting calls leave inside the tick -----------------------
+ * A requestor goes away: a restarted daemon, an interrupted build, a host that dropped off the network.
+ * Its blocked calls could be withdrawn by tag only if the host kept every tag per requestor; its leases
+ * stay until they expire and then as zombies until the servant's next report, holding slots W is waiting
+ * for and counting against the requestor's own quota when it comes back. Freeing them by hand means
+ * ydc_stream_inspect_tasks (all of L copied out), a filter on the host and a free_task_id list one tick
+ * later. The device has what is needed: every lease keeps its requestor in its inspection record, every
+ * entry of W in its requestor_ip column. Opt-in; completes ydc_stream_requestor_find (who holds what),
+ * ydc_stream_withdraw_* (by tag) and ydc_stream_quota_* (cap per requestor). The reference has no such
+ * call: in its terms the daemon sent one FreeTask per task it held and its waiters' max_wait ended.
+ *   ydc_stream_depart_begin: switches the capability on, for the open leased, waiting-and-leased or rpc
+ *     stream with inspection on, with room for max_depart requestors per tick; a later call with a
+ *     larger max_depart grows it; a smaller or equal one returns YDC_OK and does nothing (the captured
+ *     step stays). An effective call allocates a second set of the stream's buffers, copies, then
+ *     swaps, all or nothing as ydc_stream_withdraw_begin does (pointers of ydc_stream_buffers_get
+ *     change), and the step is captured again at the next tick. No such stream open, a plain or
+ *     waiting-only stream, inspection off, max_depart == 0 or max_depart > 2^24:
+ *     YDC_ERR_INVALID_ARGUMENT. ydc_stream_end and the next begin call switch it off;
+ *     ydc_stream_reserve, ydc_stream_book_begin, ydc_stream_withdraw_begin and ydc_stream_quota_begin
+ *     carry it over, max_depart unchanged; ydc_stream_restore leaves it off, like inspection.
+ *   ydc_stream_depart_stage: the requestors for the NEXT accepted tick, unsorted, repeats allowed. All
+ *     2^32 values are ordinary keys, 0 and 0xFFFFFFFF included. Staging again replaces the previous
+ *     staging; n == 0 clears it. n > max_depart: YDC_ERR_CAPACITY; the capability off:
+ *     YDC_ERR_INVALID_ARGUMENT. A refused tick leaves the staging in place, an accepted tick consumes
+ *     it. ydc_stream_snapshot is refused while one is pending.
+ *   In the tick, with the set R staged: the tick and all later ticks are exactly those of a stream
+ *     without the capability that was given
+ *       - in step 3, behind the caller's own free_task_id: one FreeTask for every lease L still holds
+ *         at that point whose inspection record names a requestor in R. Zombie or not, it is freed
+ *         (running_tasks - 1, lease erased). A lease granted while inspection was off (started_at ==
+ *         YDC_INSPECT_NO_TIME) belongs to nobody and stays, even when 0xFFFFFFFF is staged. A lease
+ *         the caller's own list freed is the caller's and is not counted here. A renewal of such a
+ *         lease in step 2 of the same tick still answers out_renewed = 1; a report that lists it in
+ *         step 6 finds it unknown. running_tasks, *out_n_leases, ydc_get_stats().leases_freed and the
+ *         quota's held(r) follow.
+ *       - where W is aged: a deadline <= now for every entry of W, as the tick found it, whose
+ *         requestor_ip is in R — behind withdrawal's mark where both capabilities are on. The entry
+ *         resolves at its queue position as YDC_IDX_TIMEOUT, untried, with 0 grants, and consumes
+ *         nothing. There is no label of its own: nobody is left to answer. An entry that withdrawal
+ *         took in the same tick is withdrawal's: counted and labelled there, not here.
+ *     NEW requests of a staged requestor in the same tick are not touched (a restarted daemon asks again
+ *     at once): what they are granted stays, what queues can be dismissed from the next tick on.
+ *   ydc_stream_depart_result: about the most recent accepted tick. *out_n: the requestors staged for
+ *     it (0: none); out[i]: the caller's i-th staged requestor, in the caller's order (a requestor
+ *     staged twice reports the same row twice): the leases of it the tick erased, how many of those
+ *     were zombies when the tick found them, the entries of W it took out and their rows (= entries
+ *     outside rpc mode). *out_leases_freed and *out_n_withdrawn (both nullable): the totals, each lease
+ *     and entry counted once. cap < *out_n: YDC_ERR_CAPACITY with *out_n set and nothing written.
+ *   No tick signature changes; a stream that never calls ydc_stream_depart_begin launches what it
+ *     launched before. With the capability on and nothing staged a tick costs the launches, no pass
+ *     over L. ydc_get_stats keeps its layout. */
+typedef struct ydc_depart_count { /* 20 bytes */
+  uint32_t requestor_ip;          /* echoes the staged value */
+  uint32_t leases, zombies;       /* leases of it this tick erased; how many of those were zombies */
+  uint32_t waiting, waiting_rows; /* entries of W it took out, and their rows (= waiting outside rpc mode) */
+} ydc_depart_count;
+int ydc_stream_depart_begin(ydc_context* ctx, uint32_t max_depart);
+int ydc_stream_depart_stage(ydc_context* ctx, const uint32_t* requestor_ip, uint32_t n);
+int ydc_stream_depart_result(ydc_context* ctx, ydc_depart_count* out, uint32_t cap, uint32_t* out_n,
+                             uint32_t* out_leases_freed /* nullable */, uint32_t* out_n_withdrawn /* nullable */);
+
 /* ---- snapshot and restore of an open stream --------------------------------------------
  * Everything an open waiting, leased, waiting-and-leased or rpc stream keeps on the device (L with
  * next_id and the report stamps, W, B, E, running_tasks, the registry's columns, the clock and the
@@ -957,8 +1018,9 @@ int ydc_stream_quota_result(ydc_context* ctx, uint32_t* out_immediate, uint32_t*
  *   - ydc_stream_snapshot: between ticks. cap too small: YDC_ERR_CAPACITY, *out_bytes the size
  *     needed, nothing written (out may be NULL then). Refused with YDC_ERR_INVALID_ARGUMENT: no
  *     stream open, a plain ydc_stream_begin stream (it keeps no state on the device), a context in
- *     a group, pipelined batches outstanding, a ydc_stream_book_stage, ydc_stream_alive_stage or
- *     ydc_stream_withdraw_stage that no tick has consumed yet. The stream is not changed.
+ *     a group, pipelined batches outstanding, a ydc_stream_book_stage, ydc_stream_alive_stage,
+ *     ydc_stream_withdraw_stage or ydc_stream_depart_stage that no tick has consumed yet. The stream
+ *     is not changed.
  *   - ydc_stream_restore: ctx becomes what the snapshotted context was: registry (as by
  *     ydc_upload_servants), running_tasks, host aliases and the open stream. Its bounds are
  *     max(blob's, *want) field by field (want may be NULL); a want that names a part the blob's

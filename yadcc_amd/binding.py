@@ -55,6 +55,7 @@ ABI_SYMBOLS = (
     "ydc_stream_requestor_find", "ydc_stream_requestor_get", "ydc_admit_clip",
     "ydc_stream_withdraw_begin", "ydc_stream_withdraw_stage", "ydc_stream_withdraw_result",
     "ydc_stream_quota_begin", "ydc_stream_quota_set", "ydc_stream_quota_result",
+    "ydc_stream_depart_begin", "ydc_stream_depart_stage", "ydc_stream_depart_result",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
@@ -103,6 +104,15 @@ HIT_DTYPE = np.dtype([("pos", "<u4"), ("count", "<u4"), ("servant_idx", "<u4"), 
 # numpy view of ydc_requestor_load (24 bytes)
 REQUESTOR_DTYPE = np.dtype([("requestor_ip", "<u4"), ("leases", "<u4"), ("zombies", "<u4"), ("prefetch_leases", "<u4"),
                             ("waiting", "<u4"), ("waiting_rows", "<u4")])
+
+
+class DepartCount(C.Structure):
+    """ydc_depart_count (20 bytes)."""
+    _fields_ = [(k, C.c_uint32) for k in ("requestor_ip", "leases", "zombies", "waiting", "waiting_rows")]
+
+
+# numpy view of ydc_depart_count
+DEPART_DTYPE = np.dtype([(k, "<u4") for k, _ in DepartCount._fields_])
 
 
 # numpy view of ydc_servant_row (32 bytes)
@@ -262,6 +272,10 @@ def lib():
         L.ydc_stream_quota_set.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_quota_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
+        L.ydc_stream_depart_begin.argtypes = [C.c_void_p, C.c_uint32]
+        L.ydc_stream_depart_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ydc_stream_depart_result.argtypes = [C.c_void_p, C.POINTER(DepartCount), C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
         L.ydc_stream_book_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -452,6 +466,30 @@ class DeviceArray:
             self.free()
         except Exception:
             pass
+
+
+def _depart_count(v, name):
+    """A capacity of the departure calls: a whole number that fits uint32 (no silent wrap)."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError("%s must be an integer, not %s" % (name, type(v).__name__))
+    if not 0 <= int(v) < 1 << 32:
+        raise ValueError("%s %d does not fit uint32" % (name, int(v)))
+    return int(v)
+
+
+def _depart_keys(requestors):
+    """The staged requestors as a contiguous uint32 column; anything that is not a flat sequence of whole
+    numbers in [0, 2^32) is refused here (numpy would wrap or truncate it)."""
+    a = np.asarray(requestors)
+    if a.ndim != 1:
+        raise TypeError("requestors must be a flat sequence of requestor_ip ids")
+    if a.size == 0:
+        return np.empty(0, np.uint32)
+    if a.dtype.kind not in "iu":
+        raise TypeError("requestors must be whole numbers (requestor_ip ids), not %s" % a.dtype)
+    if int(a.min()) < 0 or int(a.max()) >= 1 << 32:
+        raise ValueError("a requestor_ip id does not fit uint32")
+    return np.ascontiguousarray(a, dtype=np.uint32)
 
 
 class Context:
@@ -1296,6 +1334,35 @@ class Context:
             self._check(lib().ydc_stream_quota_result(self._h, imm.ctypes.data, pre.ctypes.data, len(imm), C.byref(n),
                                                       C.byref(clipped), C.byref(refused)), "ydc_stream_quota_result")
         return imm, pre, int(clipped.value), int(refused.value)
+
+    def stream_depart_begin(self, max_depart):
+        """Switches the departure of requestors on for the open leased, waiting-and-leased or rpc stream
+        with inspection on, or grows it (ydc_stream_depart_begin): room for max_depart requestors per
+        tick."""
+        n = _depart_count(max_depart, "max_depart")
+        self._check(lib().ydc_stream_depart_begin(self._h, n), "ydc_stream_depart_begin")
+
+    def stream_depart_stage(self, requestors):
+        """The requestors whose leases the next accepted tick frees and whose waiting requests it lets
+        run out (ydc_stream_depart_stage); an empty list clears. Ids as the requestor_ip column carries
+        them: whole numbers in [0, 2^32)."""
+        r = _depart_keys(requestors)
+        self._check(lib().ydc_stream_depart_stage(self._h, _ptr(r) if len(r) else None, len(r)),
+                    "ydc_stream_depart_stage")
+
+    def stream_depart_result(self):
+        """(rows of DEPART_DTYPE, one per requestor staged for the most recent accepted tick in the staged
+        order; leases freed in all; entries of W taken out in all) (ydc_stream_depart_result)."""
+        n, leases, waiting = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        rc = lib().ydc_stream_depart_result(self._h, None, 0, C.byref(n), C.byref(leases), C.byref(waiting))
+        if n.value == 0:
+            self._check(rc, "ydc_stream_depart_result")
+            return np.zeros(0, DEPART_DTYPE), int(leases.value), int(waiting.value)
+        out = np.zeros(n.value, DEPART_DTYPE)
+        self._check(lib().ydc_stream_depart_result(self._h, out.ctypes.data_as(C.POINTER(DepartCount)), len(out),
+                                                   C.byref(n), C.byref(leases), C.byref(waiting)),
+                    "ydc_stream_depart_result")
+        return out, int(leases.value), int(waiting.value)
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

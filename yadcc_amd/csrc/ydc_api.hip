@@ -44,6 +44,7 @@
 #include "admit_clip.h"
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
+#include "stream_depart.h"
 #include "stream_quota.h"
 #include "stream_withdraw.h"
 #include "tick_kernel.h"
@@ -221,6 +222,8 @@ struct TickArena {
   uint64_t* wd_tag;  // with withdrawal: the tick's staged tags (sorted, unique) and their number
   uint32_t* wd_n;
   uint32_t* q_n;  // with a quota: the tick's number of new requests (the columns behind it are padding)
+  uint32_t* dp_ip;  // with departure: the tick's staged requestors (sorted, unique) and their number
+  uint32_t* dp_n;
 };
 }  // namespace
 
@@ -371,6 +374,7 @@ struct ydc_context {
     ydc_stream_caps caps{};
     uint32_t max_book = 0;
     uint32_t max_withdraw = 0;  // tags one tick can withdraw (ydc_stream_withdraw_begin; 0: the capability is off)
+    uint32_t max_depart = 0;  // requestors one tick can dismiss (ydc_stream_depart_begin; 0: the capability is off)
     bool waiting() const { return caps.max_waiting != 0; }
     bool leased() const { return caps.max_leases != 0; }
     bool rpc() const { return caps.max_rows != 0; }
@@ -556,6 +560,26 @@ struct ydc_context {
         uint32_t n_unique = 0;
       } host;
     } withdraw;
+    // Departure of requestors (ydc_stream_depart_begin; stream_depart.h): the tick's list and counts in HBM
+    // and the page-locked result block, sized by max_depart. max_depart == 0: none of this exists, and
+    // the step launches what it launches without it. `host` moves to a grown stream as it is.
+    struct Depart {
+      DevBuf<uint8_t> d;  // ip | count | n
+      DepartList list{};
+      PinnedBuf h_res;  // page-locked: counts | DepartDone
+      uint4 *h_count = nullptr, *z_count = nullptr;
+      DepartDone *h_done = nullptr, *z_done = nullptr;
+      struct Host {
+        // ydc_stream_depart_stage: the requestors of the next accepted tick, as the caller gave them.
+        bool staged = false;
+        std::vector<uint32_t> ips;
+        // The most recent accepted tick (ydc_stream_depart_result): the staged requestors, per staged
+        // requestor its place in the tick's sorted list, and the counts read back per place.
+        std::vector<uint32_t> asked, place;
+        std::vector<uint4> counts;
+        uint32_t n_unique = 0;
+      } host;
+    } depart;
     // The cap per requestor inside the tick (ydc_stream_quota_begin; stream_quota.h): the table keyed by
     // the tick's new requestors, the settings' device copy, the admitted counts per new request in HBM
     // and the page-locked results. !on: none of this exists, and the step launches what it launches
@@ -4462,6 +4486,14 @@ void enqueue_stream_gather(ydc_context* c, const TickArena& a) {
     YDC_LAUNCH(c, "k_withdraw_mark", k_withdraw_mark, dim3(ceil_div(sm.caps.max_waiting, 256)), dim3(256), 0, c->stream,
                sm.withdraw.list, MX, sm.wq.tag, sm.wq.deadline, sm.ws, sm.caps.max_waiting);
   }
+  // With departure: the staged requestors' entries of W expire here as well, behind withdrawal's mark
+  // (an entry both name is withdrawal's) and in front of the quota's loads (stream_depart.h).
+  if (sm.max_depart) {
+    const bool rpc = sm.rpc();
+    YDC_LAUNCH(c, "k_depart_mark", k_depart_mark, dim3(ceil_div(sm.caps.max_waiting, 256)), dim3(256), 0, c->stream,
+               sm.depart.list, sm.max_depart, rpc ? sm.rw.ip : sm.wq.ip, rpc ? sm.rw.deadline : sm.wq.deadline,
+               rpc ? sm.rw.n_imm : nullptr, rpc ? sm.rw.n_pre : nullptr, sm.ws, sm.caps.max_waiting);
+  }
   // With a quota: the new requests clipped to their requestors' room, by the loads of L and W as they
   // are here — behind the tick's frees, expiry and the withdrawal's mark (stream_quota.h). In this
   // helper, so once per tick on every route.
@@ -4515,6 +4547,16 @@ void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
   if (k.max_renewals + k.max_frees)
     YDC_LAUNCH(c, "k_lease_free", k_lease_free, dim3(ren_blocks + ceil_div(k.max_frees, 256)), dim3(256), 0, c->stream,
                sm.lt, sm.ls, in, k.max_renewals, ren_blocks, sm.ren_slot, k.max_frees, S, c->d_running.p);
+  // With departure: the staged requestors' leases freed, behind the caller's own frees and in front of
+  // the reports and the sweep (stream_depart.h). Here for the reason the book's pass is here: once per
+  // tick on every path.
+  if (sm.max_depart) {
+    const uint32_t MX = sm.max_depart;
+    YDC_LAUNCH(c, "k_depart_load", k_depart_load, dim3(ceil_div(MX, 256)), dim3(256), 0, c->stream, a.dp_ip, a.dp_n, MX,
+               sm.depart.list);
+    YDC_LAUNCH(c, "k_depart_leases", k_depart_leases, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
+               sm.lt, sm.ls, sm.d_insp_rec.p, sm.depart.list, MX, S, c->d_running.p);
+  }
   if (k.max_reports)
     YDC_LAUNCH(c, "k_lease_report", k_lease_report, dim3(rep_blocks + ceil_div(k.max_report_ids, 256)), dim3(256), 0,
                c->stream, sm.lt, sm.ls, in, k.max_reports, rep_blocks, k.max_report_ids, S, sm.d_rep_tick.p, sm.z_unknown);
@@ -4601,6 +4643,10 @@ void enqueue_stream_answer(ydc_context* c, const TickArena& a, const DeviceParam
                rpc ? sm.rz.res_status : sm.z_res_idx, rpc ? &sm.rz.outcome->n_resolved : &sm.z_wout->n_resolved,
                sm.caps.max_waiting, sm.withdraw.z_count, sm.withdraw.z_done, prm, check_slot);
   }
+  // With departure: the counts to the page-locked result block, under the same gate (stream_depart.h).
+  if (sm.max_depart)
+    YDC_LAUNCH(c, "k_depart_done", k_depart_done, dim3(ceil_div(sm.max_depart, 256)), dim3(256), 0, c->stream,
+               sm.depart.list, sm.max_depart, a.lh, sm.depart.z_count, sm.depart.z_done, prm, check_slot);
   // With a quota: the table cleared for the next tick, and under the commit pass's gate the label of the
   // requests that were admitted nothing, the admitted counts and the result block (stream_quota.h).
   if (sm.quota.on) {
@@ -4811,10 +4857,11 @@ const char* stream_caps_foreign(const ydc_stream_caps& have, const ydc_stream_ca
 // Layout and allocation of everything a stream of these bounds has, into `sm` (released, or
 // fresh). Its contents are not defined before stream_reset; after a failure the caller releases it.
 int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps& k, uint32_t max_book,
-                 uint32_t max_withdraw, uint32_t quota) {
+                 uint32_t max_withdraw, uint32_t quota, uint32_t max_depart) {
   sm.caps = k;
   sm.max_book = max_book;
   sm.max_withdraw = max_withdraw;
+  sm.max_depart = max_depart;
   sm.quota.on = quota != 0;  // (Stream::Quota::code)
   sm.quota.max_overrides = quota ? quota - 1 : 0;
   const uint32_t max_updates = k.max_updates, max_releases = k.max_releases, max_tasks = k.max_tasks;
@@ -4853,6 +4900,9 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
   const size_t o_wdn = max_withdraw ? section(&off, 4) : 0;
   // ... and behind that, with a quota, the number of the tick's new requests.
   const size_t o_qn = quota ? section(&off, 4) : 0;
+  // ... and last, with departure, the staged requestors and their number.
+  const size_t o_dpi = max_depart ? section(&off, (size_t)max_depart * 4) : 0;
+  const size_t o_dpn = max_depart ? section(&off, 4) : 0;
   auto arena_at = [&](uint8_t* b) {
     TickArena a{(uint32_t*)(b + o_idx), (ydc_servant_row*)(b + o_rows), (uint32_t*)(b + o_rel),
                 (uint32_t*)(b + o_env), (uint32_t*)(b + o_minv), (uint32_t*)(b + o_ip),
@@ -4882,6 +4932,10 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
       a.wd_n = (uint32_t*)(b + o_wdn);
     }
     if (quota) a.q_n = (uint32_t*)(b + o_qn);
+    if (max_depart) {
+      a.dp_ip = (uint32_t*)(b + o_dpi);
+      a.dp_n = (uint32_t*)(b + o_dpn);
+    }
     return a;
   };
   sm.in_bytes = off;
@@ -5047,6 +5101,22 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
     sm.withdraw.h_done = (WithdrawDone*)(sm.withdraw.h_res.p + r_done);
     sm.withdraw.z_done = (WithdrawDone*)(sm.withdraw.h_res.z + r_done);
   }
+  if (max_depart) {
+    // HBM: the tick's list, its counts and its length. Page-locked: the counts and the done block.
+    auto& dp = sm.depart;
+    size_t d_off = 0, r_off = 0;
+    const size_t o_ip = section(&d_off, (size_t)max_depart * 4), o_cnt = section(&d_off, (size_t)max_depart * 16);
+    const size_t o_n = section(&d_off, 4);
+    HIP_TRY(c, dp.d.reserve(d_off));
+    uint8_t* b = dp.d.p;
+    dp.list = DepartList{(uint32_t*)(b + o_ip), (uint4*)(b + o_cnt), (uint32_t*)(b + o_n)};
+    const size_t r_cnt = section(&r_off, (size_t)max_depart * 16), r_done = section(&r_off, sizeof(DepartDone));
+    HIP_TRY(c, dp.h_res.reserve(r_off));
+    dp.h_count = (uint4*)(dp.h_res.p + r_cnt);
+    dp.z_count = (uint4*)(dp.h_res.z + r_cnt);
+    dp.h_done = (DepartDone*)(dp.h_res.p + r_done);
+    dp.z_done = (DepartDone*)(dp.h_res.z + r_done);
+  }
   if (quota) {
     // HBM: the table (word | held | asked), the settings, the per-request arrays, the counters and the
     // chain words. Page-locked: the admitted counts and the done block.
@@ -5106,6 +5176,10 @@ int stream_reset(ydc_context* c, ydc_context::Stream& sm) {
   if (sm.max_withdraw) {  // (an empty list)
     HIP_TRY(c, hipMemsetAsync(sm.withdraw.list.n, 0, 4, c->stream));
     std::memset(sm.withdraw.h_done, 0, sizeof(WithdrawDone));
+  }
+  if (sm.max_depart) {  // (an empty list)
+    HIP_TRY(c, hipMemsetAsync(sm.depart.list.n, 0, 4, c->stream));
+    std::memset(sm.depart.h_done, 0, sizeof(DepartDone));
   }
   if (sm.quota.on) {  // (every slot of the table free; the settings follow at the next tick)
     HIP_TRY(c, hipMemsetAsync(sm.quota.d.p, 0, sm.quota.d.cap, c->stream));
@@ -5206,13 +5280,14 @@ int stream_begin(ydc_context* c, const ydc_stream_caps& k) {
   join_lanes(c);
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
   stream_release(c);
-  if (int rc = stream_alloc(c, c->stream_mode, k, 0, 0, 0)) return rc;
+  if (int rc = stream_alloc(c, c->stream_mode, k, 0, 0, 0, 0)) return rc;
   return stream_reset(c, c->stream_mode);
 }
 
 // The open stream in a second, larger set of buffers (ydc_stream_reserve, ydc_stream_book_begin,
-// ydc_stream_withdraw_begin, ydc_stream_quota_begin). quota: Stream::Quota::code.
-int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, uint32_t max_withdraw, uint32_t quota) {
+// ydc_stream_withdraw_begin, ydc_stream_quota_begin, ydc_stream_depart_begin). quota: Stream::Quota::code.
+int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, uint32_t max_withdraw, uint32_t quota,
+                  uint32_t max_depart) {
   auto& sm = c->stream_mode;
   HIP_TRY(c, hipSetDevice(c->device));
   resident_stop(c);  // (the registry leaves the resident kernel's registers)
@@ -5220,7 +5295,7 @@ int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, u
   // A second set of buffers, filled from the first, which is released only once that has worked:
   // after any failure the stream is as it was.
   ydc_context::Stream grown;
-  int rc = stream_alloc(c, grown, k, max_book, max_withdraw, quota);
+  int rc = stream_alloc(c, grown, k, max_book, max_withdraw, quota, max_depart);
   if (rc == YDC_OK) rc = stream_reset(c, grown);
   if (rc == YDC_OK) rc = stream_migrate(c, sm, grown);
   if (rc != YDC_OK) {
@@ -5233,6 +5308,7 @@ int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, u
   grown.inspect = std::move(sm.inspect);  // (the detail records have moved already: stream_migrate)
   grown.book.staged = std::move(sm.book.staged);
   grown.withdraw.host = std::move(sm.withdraw.host);  // (a pending staging and the last result go along)
+  grown.depart.host = std::move(sm.depart.host);      // (likewise)
   grown.quota.host = std::move(sm.quota.host);        // (the settings and the last result go along)
   grown.quota.host.dirty = true;                      // (... and the new device copy has to follow them)
   grown.quota.host.table_dirty = false;
@@ -5274,7 +5350,7 @@ int ydc_stream_reserve(ydc_context* c, const ydc_stream_caps* want) {
   const ydc_stream_caps k = stream_caps_grown(sm.caps, *want);  // (growth only)
   if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, k, sm.max_book)) return rc;
   if (!std::memcmp(&k, &sm.caps, sizeof k)) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, k, sm.max_book, sm.max_withdraw, sm.quota.code());
+  return stream_regrow(c, k, sm.max_book, sm.max_withdraw, sm.quota.code(), sm.max_depart);
 }
 
 }  // extern "C"
@@ -5419,7 +5495,7 @@ int ydc_stream_book_begin(ydc_context* c, uint32_t max_book) {
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_book_begin: no leased, waiting-and-leased or rpc stream is open");
   if (int rc = stream_caps_check(c, YDC_ERR_INVALID_ARGUMENT, sm.caps, max_book)) return rc;
   if (max_book <= sm.max_book) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, ydc_stream_caps(sm.caps), max_book, sm.max_withdraw, sm.quota.code());  // (a copy: regrow replaces the stream)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), max_book, sm.max_withdraw, sm.quota.code(), sm.max_depart);  // (a copy: regrow replaces the stream)
 }
 
 int ydc_stream_book_stage(ydc_context* c, const uint64_t* servant_task_id, const uint64_t* digest_key,
@@ -5446,7 +5522,7 @@ int ydc_stream_withdraw_begin(ydc_context* c, uint32_t max_withdraw) {
   if (max_withdraw > (1u << 30))
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "max_withdraw %u out of range (1 .. 2^30)", max_withdraw);
   if (max_withdraw <= sm.max_withdraw) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, max_withdraw, sm.quota.code());  // (a copy: regrow replaces the stream)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, max_withdraw, sm.quota.code(), sm.max_depart);  // (a copy: regrow replaces the stream)
 }
 
 int ydc_stream_withdraw_stage(ydc_context* c, const uint64_t* tags, uint32_t n) {
@@ -5479,6 +5555,59 @@ int ydc_stream_withdraw_result(ydc_context* c, uint32_t* out_count, uint32_t cap
   return YDC_OK;
 }
 
+int ydc_stream_depart_begin(ydc_context* c, uint32_t max_depart) {
+  if (!c || !max_depart) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.leased())
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_depart_begin: no leased, waiting-and-leased or rpc stream is open");
+  if (!sm.inspect.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_depart_begin: inspection is off, so no lease says whose it is "
+                "(ydc_stream_inspect_begin)");
+  if (max_depart > (1u << 24))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "max_depart %u out of range (1 .. 2^24)", max_depart);
+  if (max_depart <= sm.max_depart) return YDC_OK;  // (nothing to do: the captured step stays)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, sm.max_withdraw, sm.quota.code(), max_depart);  // (a copy: regrow replaces the stream)
+}
+
+int ydc_stream_depart_stage(ydc_context* c, const uint32_t* requestor_ip, uint32_t n) {
+  if (!c || (n && !requestor_ip)) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_depart)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_depart_stage: the stream dismisses nobody "
+                "(ydc_stream_depart_begin)");
+  if (n > sm.max_depart) return fail(c, YDC_ERR_CAPACITY, "%u staged requestors > max_depart %u", n, sm.max_depart);
+  auto& d = sm.depart.host;
+  d.ips.assign(requestor_ip, requestor_ip + n);
+  d.staged = n != 0;
+  return YDC_OK;
+}
+
+int ydc_stream_depart_result(ydc_context* c, ydc_depart_count* out, uint32_t cap, uint32_t* out_n,
+                             uint32_t* out_leases_freed, uint32_t* out_n_withdrawn) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.max_depart)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_depart_result: the stream dismisses nobody "
+                "(ydc_stream_depart_begin)");
+  const auto& d = sm.depart.host;
+  const uint32_t n = (uint32_t)d.place.size();
+  *out_n = n;
+  if (cap < n) return fail(c, YDC_ERR_CAPACITY, "%u staged requestors > cap %u", n, cap);
+  if (n && !out) return YDC_ERR_INVALID_ARGUMENT;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint4& k = d.counts[d.place[i]];
+    out[i] = ydc_depart_count{d.asked[i], k.x, k.y, k.z, k.w};
+  }
+  uint32_t leases = 0, waiting = 0;  // (each lease and entry once: over the list, not over the staging)
+  for (const uint4& k : d.counts) {
+    leases += k.x;
+    waiting += k.z;
+  }
+  if (out_leases_freed) *out_leases_freed = leases;
+  if (out_n_withdrawn) *out_n_withdrawn = waiting;
+  return YDC_OK;
+}
+
 int ydc_stream_quota_begin(ydc_context* c, uint32_t max_overrides) {
   if (!c) return YDC_ERR_INVALID_ARGUMENT;
   auto& sm = c->stream_mode;
@@ -5495,7 +5624,7 @@ int ydc_stream_quota_begin(ydc_context* c, uint32_t max_overrides) {
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_begin: a context of up to %u servants could answer index "
                 "%u, which is YDC_IDX_OVER_QUOTA (give ydc_create a max_servants)", bound, YDC_IDX_OVER_QUOTA);
   if (sm.quota.on && max_overrides <= sm.quota.max_overrides) return YDC_OK;  // (nothing to do: the captured step stays)
-  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, sm.max_withdraw, max_overrides + 1);  // (a copy: regrow replaces the stream)
+  return stream_regrow(c, ydc_stream_caps(sm.caps), sm.max_book, sm.max_withdraw, max_overrides + 1, sm.max_depart);  // (a copy: regrow replaces the stream)
 }
 
 int ydc_stream_quota_set(ydc_context* c, uint32_t default_cap, const uint32_t* requestor_ip, const uint32_t* cap,
@@ -6577,6 +6706,27 @@ static void stream_withdraw_stage_tick(ydc_context::Stream& sm) {
   w.tags.clear();
 }
 
+// With departure: the staged requestors into the arena, sorted and without duplicates (the kernels search
+// the list), each staged requestor's place in that list kept for ydc_stream_depart_result; the staging
+// consumed.
+static void stream_depart_stage_tick(ydc_context::Stream& sm) {
+  auto& d = sm.depart.host;
+  if (!d.staged) d.ips.clear();
+  std::vector<uint32_t> sorted(d.ips);
+  std::sort(sorted.begin(), sorted.end());
+  sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+  d.place.resize(d.ips.size());
+  for (size_t i = 0; i < d.place.size(); ++i)
+    d.place[i] = (uint32_t)(std::lower_bound(sorted.begin(), sorted.end(), d.ips[i]) - sorted.begin());
+  d.n_unique = (uint32_t)sorted.size();
+  d.counts.assign(d.n_unique, make_uint4(0, 0, 0, 0));
+  if (d.n_unique) std::memcpy(sm.h.dp_ip, sorted.data(), (size_t)d.n_unique * 4);
+  *sm.h.dp_n = d.n_unique;
+  d.asked = std::move(d.ips);
+  d.ips.clear();
+  d.staged = false;
+}
+
 // With a quota, in front of an accepted tick: the settings' device copy follows the host's (after a set,
 // in a grown stream), and a table that a failed tick left behind is cleared. The stream is idle.
 static int stream_quota_sync(ydc_context* c) {
@@ -6660,6 +6810,7 @@ static void stream_tick_stage(ydc_context* c, const StreamCall& t, const TickSta
     *h.lh = LeaseHdr{lt->now, lt->n_renew, lt->n_free, lt->n_rep, n_ids, sm.lease_tick, 0};
   }
   if (sm.max_withdraw) stream_withdraw_stage_tick(sm);
+  if (sm.max_depart) stream_depart_stage_tick(sm);
   if (sm.quota.on) *h.q_n = n_tasks;
   if (t.rt) {
     put(h.nimm, t.rt->n_imm, n_tasks, 4);
@@ -6775,6 +6926,14 @@ static int stream_tick_finish(ydc_context* c, const StreamCall& t, const TickSta
     if (sm.withdraw.h_done->n != w.n_unique)
       return fail(c, YDC_ERR_NOT_CONVERGED, "withdrawal: counts of %u tags, %u staged", sm.withdraw.h_done->n, w.n_unique);
     std::copy_n(sm.withdraw.h_count, w.n_unique, w.counts.begin());
+  }
+  if (sm.max_depart) {  // (k_depart_done has stored the counts of the list it saw)
+    auto& d = sm.depart.host;
+    const DepartDone& dd = *sm.depart.h_done;
+    if (dd.n != d.n_unique || dd.tick_no != sm.lease_tick)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "departure: counts of %u requestors of tick %u (expected %u, %u)", dd.n,
+                  dd.tick_no, d.n_unique, sm.lease_tick);
+    std::copy_n(sm.depart.h_count, d.n_unique, d.counts.begin());
   }
   uint32_t n_refused = 0;
   if (sm.quota.on) {  // (the label pass has stored what the clip admitted)
@@ -7134,7 +7293,7 @@ int ydc_stream_snapshot(ydc_context* c, void* out, size_t cap, size_t* out_bytes
                 "on the device");
   if (c->group.n_ranks) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: the context is in a group");
   if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: pipelined batches are outstanding");
-  if (sm.book.staged.on || sm.alive.staged || sm.withdraw.host.staged)
+  if (sm.book.staged.on || sm.alive.staged || sm.withdraw.host.staged || sm.depart.host.staged)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_snapshot: a staging for the next tick is pending (a snapshot "
                 "is taken between ticks)");
   HIP_TRY(c, hipSetDevice(c->device));
@@ -7206,7 +7365,7 @@ int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc
   // A second stream, complete before it becomes the context's.
   ydc_context::Stream fresh;
   auto load = [&]() -> int {
-    if (int rc = stream_alloc(c, fresh, k, h.max_book, 0, 0)) return rc;  // (withdrawal and the quota stay off, like inspection)
+    if (int rc = stream_alloc(c, fresh, k, h.max_book, 0, 0, 0)) return rc;  // (withdrawal, the quota and departure stay off, like inspection)
     if (int rc = stream_reset(c, fresh)) return rc;
     hipStream_t st = c->stream;
     if (fresh.leased()) {

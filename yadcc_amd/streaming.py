@@ -246,3 +246,23 @@ def admit(ctx, requests, n_immediate, n_prefetch, cap):
     load, _ = ctx.stream_requestor_find(ips)
     imm, pre = binding.admit_clip(ips, n_immediate, n_prefetch, load, cap)
     return imm, pre, (imm.astype(np.uint64) + pre) > 0
+
+
+DEPART_COLUMNS = ("requestor_ip", "leases", "zombies", "waiting", "waiting_rows")
+
+
+def dismiss(ctx, requestors):
+    """A departed requestor (connection closed, daemon restarted, host gone): its leases and waiting
+    calls leave inside the NEXT accepted tick (binding.Context.stream_depart_stage), with no list of
+    its grants or tags kept on the host. Stages `requestors` (requestor_ip ids, any order, repeats
+    allowed) and returns the function to call after that tick: -> a dict of columns, one row per staged
+    requestor in the staged order (DEPART_COLUMNS), plus "leases_freed" and "n_withdrawn", the totals
+    with every lease and entry counted once. No compute: every number is the call's."""
+    ctx.stream_depart_stage(requestors)
+
+    def result():
+        rows, leases, waiting = ctx.stream_depart_result()
+        out = {k: rows[k].copy() for k in DEPART_COLUMNS}
+        out["leases_freed"], out["n_withdrawn"] = leases, waiting
+        return out
+    return result
