@@ -79,8 +79,15 @@ tests/native/admit_clip_test: tests/native/admit_clip_test.cc $(CSRC)/admit_clip
 	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tests/native/admit_clip_test.cc
 admitclip: tests/native/admit_clip_test
 	tests/native/admit_clip_test
+# The predicate of the lease select (lease_filter.h) against a second restatement, all 2^9 combinations of
+# its predicates on edge values, ASan + UBSan, no GPU (tests/test_stream_select_binding.py builds and runs
+# the same program).
+tests/native/lease_filter_test: tests/native/lease_filter_test.cc $(CSRC)/lease_filter.h
+	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tests/native/lease_filter_test.cc
+leasefilter: tests/native/lease_filter_test
+	tests/native/lease_filter_test
 clean:
-	rm -f yadcc_amd/libydc.so tests/model/libmodel.so tests/native/lane_rule_test tests/native/admit_clip_test tests/native/occupancy_plan_test
+	rm -f yadcc_amd/libydc.so tests/model/libmodel.so tests/native/lane_rule_test tests/native/admit_clip_test tests/native/occupancy_plan_test tests/native/lease_filter_test
 	$(MAKE) -C tests/native clean
 	$(MAKE) -C oracle clean
-.PHONY: all lib probe oracle model native tsan asan flatmap shardplan admitclip lanerule occupancyplan clean
+.PHONY: all lib probe oracle model native tsan asan flatmap shardplan admitclip lanerule occupancyplan leasefilter clean

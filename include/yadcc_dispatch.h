@@ -780,6 +780,57 @@ int ydc_stream_inspect_waiting(ydc_context* ctx, uint64_t* out_tag, uint32_t* ou
                                int64_t* out_lease_for, uint32_t* out_n_immediate, uint32_t* out_n_prefetch,
                                uint32_t cap, uint32_t* out_n);
 
+/* ---- which leases, not just how many: the lease table filtered and paged on the device ----------
+ * ydc_stream_inspect_tasks and ydc_stream_leases_get copy all of L out. These two calls filter L on
+ * the device by a conjunction of the columns inspection exposes, so that only the rows asked for cross
+ * the bus. Read-only, between ticks, on an open leased, waiting-and-leased or rpc stream; they
+ * synchronise.
+ *   Let T be the rows ydc_stream_inspect_tasks would return at the same moment (with inspection off:
+ *     the rows of ydc_stream_leases_get with details YDC_INSPECT_NO_TIME, YDC_INSPECT_NO_ID,
+ *     YDC_INSPECT_NO_ID, 0).
+ *   ydc_stream_inspect_select: *out_matches = the rows of T that satisfy every predicate selected in
+ *     f->fields; *out_n = min(*out_matches, cap); the output columns hold the first *out_n matching
+ *     rows of T, in T's ascending id order. Never YDC_ERR_CAPACITY; cap == 0 is a pure count; any
+ *     output column may be NULL. To page, repeat the call with YDC_SEL_AFTER_ID and after_id = the
+ *     last id received: the pages, concatenated, are the filtered T.
+ *   ydc_stream_inspect_count: out_matches[i] for each of n filters, from one pass over L for all of
+ *     them. n == 0 is YDC_OK; n > YDC_SELECT_MAX_FILTERS is YDC_ERR_INVALID_ARGUMENT.
+ *   The record predicates (ENV, REQUESTOR, PREFETCH, STARTED_BEFORE, UNATTRIBUTED): a lease granted
+ *     while inspection was off (started_at == YDC_INSPECT_NO_TIME: attribution is decided by started_at,
+ *     never by the ids, whose 2^32 values are all ordinary keys) satisfies none of the first four.
+ *     UNATTRIBUTED selects exactly those leases; together with any of the first four it matches
+ *     nothing, which is no error. With inspection off a record predicate is YDC_ERR_INVALID_ARGUMENT;
+ *     the four table predicates work. A servant_idx the registry does not have matches nothing.
+ *   YDC_ERR_INVALID_ARGUMENT with nothing written: no stream open, a plain or waiting-only stream,
+ *     pipelined batches outstanding, an unknown bit in fields, zombie or prefetch > 1 where selected,
+ *     a NULL f, out_n or out_matches.
+ *   They change nothing: the next tick's results, ydc_stream_snapshot's bytes and ydc_get_stats are
+ *     those of a twin context that never called them; nothing of theirs is carried by
+ *     ydc_stream_reserve, ydc_stream_snapshot or ydc_stream_restore; a stream that never calls them
+ *     launches what it launched before. */
+#define YDC_SEL_SERVANT         0x001u  /* L.servant == servant_idx */
+#define YDC_SEL_ZOMBIE          0x002u  /* zombie bit == zombie (0 / 1) */
+#define YDC_SEL_EXPIRES_BEFORE  0x004u  /* expires_at <  expires_before */
+#define YDC_SEL_AFTER_ID        0x008u  /* id > after_id: the cursor */
+#define YDC_SEL_ENV             0x010u  /* record's env_id == env_id            (inspection) */
+#define YDC_SEL_REQUESTOR       0x020u  /* record's requestor_ip == requestor_ip (inspection) */
+#define YDC_SEL_PREFETCH        0x040u  /* record's prefetch == prefetch (0 / 1) (inspection) */
+#define YDC_SEL_STARTED_BEFORE  0x080u  /* started_at < started_before           (inspection) */
+#define YDC_SEL_UNATTRIBUTED    0x100u  /* started_at == YDC_INSPECT_NO_TIME     (inspection) */
+#define YDC_SELECT_MAX_FILTERS  64u
+typedef struct ydc_lease_filter {
+  uint32_t fields;               /* which of the members below take part; 0 matches every lease */
+  uint32_t servant_idx, env_id, requestor_ip;
+  uint8_t  zombie, prefetch, pad[2];
+  int64_t  expires_before, started_before;
+  uint64_t after_id;
+} ydc_lease_filter;              /* 48 bytes */
+int ydc_stream_inspect_select(ydc_context* ctx, const ydc_lease_filter* f, uint64_t* out_task_id,
+                              uint32_t* out_servant_idx, int64_t* out_expires_at, uint8_t* out_zombie,
+                              int64_t* out_started_at, uint32_t* out_env_id, uint32_t* out_requestor_ip,
+                              uint8_t* out_prefetch, uint32_t cap, uint32_t* out_n, uint32_t* out_matches);
+int ydc_stream_inspect_count(ydc_context* ctx, const ydc_lease_filter* f, uint32_t n, uint32_t* out_matches);
+
 /* ---- the load per requestor, and the admission arithmetic that goes with it ---------------------
  * Who holds the cluster: per requestor_ip the leases it owns (with inspection on every lease keeps
  * its requestor beside it) and the entries of W it is blocked on, summed on the device, so nobody has

@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "ydc_stream_alive_begin", "ydc_stream_alive_stage", "ydc_stream_alive_removed", "ydc_stream_alive_get",
     "ydc_stream_inspect_begin", "ydc_stream_inspect_load", "ydc_stream_inspect_servants", "ydc_stream_inspect_tasks",
     "ydc_stream_outlook_get", "ydc_stream_inspect_waiting",
+    "ydc_stream_inspect_select", "ydc_stream_inspect_count",
     "ydc_stream_requestor_find", "ydc_stream_requestor_get", "ydc_admit_clip",
     "ydc_stream_withdraw_begin", "ydc_stream_withdraw_stage", "ydc_stream_withdraw_result",
     "ydc_stream_quota_begin", "ydc_stream_quota_set", "ydc_stream_quota_result",
@@ -80,6 +81,42 @@ class StreamTotals(C.Structure):
     """ydc_stream_totals."""
     _fields_ = [(k, C.c_uint64) for k in ("servants_up", "running_tasks", "capacity", "capacity_available",
                                           "capacity_unavailable")]
+
+
+# ydc_lease_filter's `fields` bits (YDC_SEL_*), by the keyword Context.stream_inspect_select takes.
+SEL_SERVANT, SEL_ZOMBIE, SEL_EXPIRES_BEFORE, SEL_AFTER_ID = 0x001, 0x002, 0x004, 0x008
+SEL_ENV, SEL_REQUESTOR, SEL_PREFETCH, SEL_STARTED_BEFORE, SEL_UNATTRIBUTED = 0x010, 0x020, 0x040, 0x080, 0x100
+SELECT_MAX_FILTERS = 64
+
+
+class LeaseFilter(C.Structure):
+    """ydc_lease_filter."""
+    _fields_ = [("fields", C.c_uint32), ("servant_idx", C.c_uint32), ("env_id", C.c_uint32),
+                ("requestor_ip", C.c_uint32), ("zombie", C.c_uint8), ("prefetch", C.c_uint8), ("pad", C.c_uint8 * 2),
+                ("expires_before", C.c_int64), ("started_before", C.c_int64), ("after_id", C.c_uint64)]
+
+
+def lease_filter(servant=None, zombie=None, expires_before=None, after_id=None, env_id=None, requestor_ip=None,
+                 prefetch=None, started_before=None, unattributed=False):
+    """A LeaseFilter from keywords: a predicate takes part when its keyword is not None (unattributed:
+    when true). Values are checked by the library, not here, except that they must fit their member."""
+    f = LeaseFilter()
+    for bit, name, v in ((SEL_SERVANT, "servant_idx", servant), (SEL_ZOMBIE, "zombie", zombie),
+                         (SEL_EXPIRES_BEFORE, "expires_before", expires_before), (SEL_AFTER_ID, "after_id", after_id),
+                         (SEL_ENV, "env_id", env_id), (SEL_REQUESTOR, "requestor_ip", requestor_ip),
+                         (SEL_PREFETCH, "prefetch", prefetch), (SEL_STARTED_BEFORE, "started_before", started_before)):
+        if v is None:
+            continue
+        v = int(v)
+        lo, hi = {"zombie": (0, 255), "prefetch": (0, 255), "expires_before": (-2**63, 2**63 - 1),
+                  "started_before": (-2**63, 2**63 - 1), "after_id": (0, 2**64 - 1)}.get(name, (0, 2**32 - 1))
+        if not lo <= v <= hi:
+            raise ValueError("lease filter: %s = %d does not fit" % (name, v))
+        f.fields |= bit
+        setattr(f, name, v)
+    if unattributed:
+        f.fields |= SEL_UNATTRIBUTED
+    return f
 
 
 class StreamOutlook(C.Structure):
@@ -260,6 +297,9 @@ def lib():
         L.ydc_stream_inspect_tasks.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
         L.ydc_stream_outlook_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.ydc_stream_inspect_waiting.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint32, C.c_void_p]
+        L.ydc_stream_inspect_select.argtypes = [C.c_void_p, C.POINTER(LeaseFilter)] + [C.c_void_p] * 8 + [
+            C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.ydc_stream_inspect_count.argtypes = [C.c_void_p, C.POINTER(LeaseFilter), C.c_uint32, C.c_void_p]
         L.ydc_stream_requestor_find.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
         L.ydc_stream_requestor_get.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint32)]
@@ -1251,6 +1291,46 @@ class Context:
         self._check(lib().ydc_stream_inspect_waiting(self._h, *[_ptr(a) for a in cols.values()], cap, C.byref(n)),
                     "ydc_stream_inspect_waiting")
         return {k: a[:n.value].copy() for k, a in cols.items()}
+
+    def stream_inspect_select(self, cap, servant=None, zombie=None, expires_before=None, after_id=None, env_id=None,
+                              requestor_ip=None, prefetch=None, started_before=None, unattributed=False):
+        """The `cap` smallest ids among the leases that satisfy every given predicate, filtered on the
+        device (ydc_stream_inspect_select): (dict of the columns stream_inspect_tasks returns, in
+        ascending id order; matches: how many leases satisfy the filter). To page, pass the last id
+        received as after_id. A predicate left None does not take part."""
+        cap = int(cap)
+        if not 0 <= cap < 2**32:
+            raise ValueError("stream_inspect_select: cap %d" % cap)
+        f = lease_filter(servant, zombie, expires_before, after_id, env_id, requestor_ip, prefetch, started_before,
+                         unattributed)
+        room = min(cap, self.stream_select_room())
+        cols = {"task_id": np.empty(room, np.uint64), "servant_idx": np.empty(room, np.uint32),
+                "expires_at": np.empty(room, np.int64), "zombie": np.empty(room, np.uint8),
+                "started_at": np.empty(room, np.int64), "env_id": np.empty(room, np.uint32),
+                "requestor_ip": np.empty(room, np.uint32), "prefetch": np.empty(room, np.uint8)}
+        n, m = C.c_uint32(0), C.c_uint32(0)
+        self._check(lib().ydc_stream_inspect_select(self._h, C.byref(f), *[_ptr(a) for a in cols.values()], room,
+                                                    C.byref(n), C.byref(m)), "ydc_stream_inspect_select")
+        return {k: a[:n.value].copy() for k, a in cols.items()}, int(m.value)
+
+    def stream_select_room(self):
+        """The rows a select can return at most, whatever cap says: the open stream's max_leases >= |L|
+        (0: no stream; the library then refuses the call)."""
+        caps = StreamCaps()
+        if lib().ydc_stream_caps_get(self._h, C.byref(caps)) != 0:
+            return 0
+        return int(caps.max_leases)
+
+    def stream_inspect_count(self, filters):
+        """How many leases satisfy each of up to SELECT_MAX_FILTERS filters, from one pass over the lease
+        table (ydc_stream_inspect_count). filters: LeaseFilter objects or dicts of lease_filter's
+        keywords. Returns a uint32 array."""
+        fs = [f if isinstance(f, LeaseFilter) else lease_filter(**f) for f in filters]
+        arr = (LeaseFilter * max(len(fs), 1))(*fs)
+        out = np.zeros(len(fs), np.uint32)
+        self._check(lib().ydc_stream_inspect_count(self._h, arr if fs else None, len(fs), _ptr(out) if fs else None),
+                    "ydc_stream_inspect_count")
+        return out
 
     def stream_requestor_find(self, ips):
         """What each requestor holds (ydc_stream_requestor_find): (structured array of REQUESTOR_DTYPE,

@@ -39,6 +39,7 @@
 #include "book_index.h"
 #include "servant_alive.h"
 #include "stream_inspect.h"
+#include "stream_select.h"
 #include "stream_outlook.h"
 #include "requestor_index.h"
 #include "admit_clip.h"
@@ -541,6 +542,12 @@ struct ydc_context {
       DevBuf<InspectSums> sums;
       DevBuf<uint8_t> pack;     // k_inspect_pack's columns and their count
     } inspect;
+    // ydc_stream_inspect_select / ydc_stream_inspect_count (stream_select.h): the calls' scratch, grown
+    // on demand: SelectState | the filters | k_select_pack's columns. Nothing a tick reads; a grown
+    // stream starts without it. The filters go through a page-locked block of the stream's own, so
+    // that their copy is an asynchronous one on the stream and not a blocking one out of the caller's memory.
+    DevBuf<uint8_t> select;
+    PinnedBuf select_h;
     // Withdrawal by tag (ydc_stream_withdraw_begin; stream_withdraw.h): the tick's list and counts in HBM
     // and the page-locked result block, sized by max_withdraw. max_withdraw == 0: none of this exists,
     // and the step launches what it launches without it. `host` moves to a grown stream as it is.
@@ -6159,6 +6166,164 @@ int ydc_stream_inspect_waiting(ydc_context* c, uint64_t* out_tag, uint32_t* out_
     else std::memset(to[k], 0, n * from[k].width);
   }
   if (!sm.rpc() && out_n_immediate) std::fill(out_n_immediate, out_n_immediate + n, 1u);
+  return YDC_OK;
+}
+
+// ---- select and count over L (stream_select.h, lease_filter.h) ----
+
+static_assert(sizeof(ydc_lease_filter) == sizeof(LeaseFilter), "ydc_lease_filter");
+constexpr size_t kSelectFiltersAt = sizeof(SelectState), kSelectPackAt = kSelectFiltersAt + kSelectMaxFilters * sizeof(LeaseFilter);
+static_assert(kSelectFiltersAt % 16 == 0 && kSelectPackAt % 16 == 0, "the scratch's sections hold 16-byte vectors");
+
+// What both calls do first: the filters checked, the outlook's refusals and its draining of the
+// stream, the refusals of their own; then the scratch with room for `pack_bytes` of packed rows,
+// the filters in it and its state cleared (enqueued).
+static int select_enter(ydc_context* c, const char* who, const ydc_lease_filter* f, uint32_t n, size_t pack_bytes) {
+  for (uint32_t i = 0; i < n; ++i) {
+    LeaseFilter lf;
+    std::memcpy(&lf, &f[i], sizeof lf);
+    if (!lease_filter_valid(lf))
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: filter %u selects 0x%x with zombie %u, prefetch %u", who, i, lf.fields,
+                  lf.zombie, lf.prefetch);
+  }
+  if (int rc = outlook_enter(c, who)) return rc;
+  auto& sm = c->stream_mode;
+  if (!sm.leased()) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: a waiting stream keeps no leases", who);
+  for (uint32_t i = 0; i < n; ++i)
+    if ((f[i].fields & kSelRecord) && !sm.inspect.on)
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: filter %u selects by a lease's record, and inspection is off "
+                  "(ydc_stream_inspect_begin)", who, i);
+  if (!n) return YDC_OK;
+  HIP_TRY(c, sm.select.reserve(kSelectPackAt + pack_bytes));
+  uint8_t* const d = sm.select.p;
+  SelectState* const st = (SelectState*)d;
+  HIP_TRY(c, sm.select_h.reserve(kSelectMaxFilters * sizeof(LeaseFilter)));
+  std::memcpy(sm.select_h.p, f, (size_t)n * sizeof(LeaseFilter));  // (n <= kSelectMaxFilters: both callers)
+  HIP_TRY(c, hipMemcpyAsync(d + kSelectFiltersAt, sm.select_h.p, (size_t)n * sizeof(LeaseFilter), hipMemcpyHostToDevice,
+                            c->stream));
+  HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(SelectState), c->stream));
+  HIP_TRY(c, hipMemsetAsync(&st->min_id, 0xFF, sizeof st->min_id, c->stream));
+  return YDC_OK;
+}
+
+int ydc_stream_inspect_select(ydc_context* c, const ydc_lease_filter* f, uint64_t* out_task_id, uint32_t* out_servant_idx,
+                              int64_t* out_expires_at, uint8_t* out_zombie, int64_t* out_started_at, uint32_t* out_env_id,
+                              uint32_t* out_requestor_ip, uint8_t* out_prefetch, uint32_t cap, uint32_t* out_n,
+                              uint32_t* out_matches) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (!f || !out_n || !out_matches)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_select: no filter, or nowhere to put the counts");
+  auto& sm = c->stream_mode;
+  // A call returns min(matches, cap) <= |L| rows, so that is the room the pack gets.
+  const uint32_t room = sm.active && sm.leased() ? std::min(cap, sm.n_leases) : 0u;
+  if (int rc = select_enter(c, "ydc_stream_inspect_select", f, 1, (size_t)std::max(room, 1u) * 41 + 3)) return rc;
+  uint8_t* const d = sm.select.p;
+  SelectState* const st = (SelectState*)d;
+  const LeaseFilter* const df = (const LeaseFilter*)(d + kSelectFiltersAt);
+  const uint4* const rec = sm.inspect.on ? sm.d_insp_rec.p : nullptr;
+  const uint8_t* const pre = sm.inspect.on ? sm.d_insp_pre.p : nullptr;
+  const dim3 grid(ceil_div(sm.lt.mask + 1, kLeaseTile)), block(256);
+  // Pass 1: the matches, the smallest and the largest matching id.
+  YDC_LAUNCH(c, "k_select_count", k_select_count<true>, grid, block, 0, c->stream, sm.lt, rec, pre, df, 1u, st);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  struct {
+    uint32_t matches[kSelectMaxFilters];
+    unsigned long long min_id, max_id;
+  } head;
+  static_assert(offsetof(SelectState, max_id) + 8 == sizeof head, "SelectState's head");
+  HIP_TRY(c, hipMemcpy(&head, st, sizeof head, hipMemcpyDeviceToHost));
+  const uint32_t matches = head.matches[0], n_out = std::min(matches, cap);
+  if (matches > sm.n_leases || (matches && head.min_id > head.max_id))
+    return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: %u matches, |L| %u on the host", matches, sm.n_leases);
+  if (!n_out) {
+    *out_n = 0;
+    *out_matches = matches;
+    return YDC_OK;
+  }
+  // More matches than room: the cap-th smallest matching id by a radix select over the bytes the
+  // matches do not share, eight launches of which those above `top` return at once. Otherwise
+  // every match is packed.
+  struct {
+    unsigned long long prefix;
+    uint32_t rank, n_packed;
+  } sel{~0ull, 0u, 0u};
+  static_assert(offsetof(SelectState, n_packed) - offsetof(SelectState, prefix) == 12, "SelectState's select part");
+  const bool cut = matches > cap;
+  uint32_t top = 0;
+  if (cut) {
+    top = (63u - (uint32_t)__builtin_clzll(head.min_id ^ head.max_id)) / 8u;  // (two matches: min != max)
+    sel.prefix = top >= 7 ? 0ull : head.min_id & ~((1ull << (8 * (top + 1))) - 1ull);
+    sel.rank = cap;
+  }
+  HIP_TRY(c, hipMemcpy(&st->prefix, &sel, sizeof sel, hipMemcpyHostToDevice));
+  if (cut)
+    for (uint32_t b = kSelectRounds; b-- > 0;) {
+      YDC_LAUNCH(c, "k_select_hist", k_select_hist, grid, block, 0, c->stream, sm.lt, rec, pre, df, b, top, st);
+      YDC_LAUNCH(c, "k_select_digit", k_select_digit, dim3(1), block, 0, c->stream, b, top, st);
+    }
+  // The pack: n_out rows in the layout of ydc_stream_inspect_tasks' pack, sized by n_out.
+  const size_t pc = n_out;
+  uint8_t* const pd = d + kSelectPackAt;
+  const InspectPacked pk{(unsigned long long*)(pd + pc * 16), (int64_t*)(pd + pc * 24), (uint4*)pd,
+                         (uint32_t*)(pd + pc * 32),            (uint32_t*)(pd + pc * 36), pd + pc * 40, n_out};
+  YDC_LAUNCH(c, "k_select_pack", k_select_pack, grid, block, 0, c->stream, sm.lt, rec, pre, df, pk, st);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(&sel, &st->prefix, sizeof sel, hipMemcpyDeviceToHost));
+  if (sel.n_packed != n_out)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "lease select: %u rows at or below the threshold, %u expected", sel.n_packed, n_out);
+  std::vector<uint8_t> h(pc * 41);
+  HIP_TRY(c, hipMemcpy(h.data(), pd, h.size(), hipMemcpyDeviceToHost));
+  // Sorted by id here, as ydc_stream_inspect_tasks sorts: n_out rows.
+  auto at = [&](size_t off, size_t width, uint32_t i, void* out) { std::memcpy(out, h.data() + off + (size_t)i * width, width); };
+  std::vector<std::pair<unsigned long long, uint32_t>> order(n_out);  // (id, packed position)
+  for (uint32_t i = 0; i < n_out; ++i) {
+    at(pc * 16, 8, i, &order[i].first);
+    order[i].second = i;
+  }
+  std::sort(order.begin(), order.end());
+  for (uint32_t k = 0; k < n_out; ++k) {
+    const uint32_t i = order[k].second;
+    uint32_t r[4], state = 0;
+    at(0, 16, i, r);
+    at(pc * 36, 4, i, &state);
+    if (out_task_id) out_task_id[k] = order[k].first;
+    if (out_servant_idx) at(pc * 32, 4, i, &out_servant_idx[k]);
+    if (out_expires_at) at(pc * 24, 8, i, &out_expires_at[k]);
+    if (out_zombie) out_zombie[k] = (state & kLeaseZombie) ? 1 : 0;
+    if (out_started_at) out_started_at[k] = (int64_t)((uint64_t)r[0] | ((uint64_t)r[1] << 32));
+    if (out_env_id) out_env_id[k] = r[2];
+    if (out_requestor_ip) out_requestor_ip[k] = r[3];
+    if (out_prefetch) out_prefetch[k] = h[pc * 40 + i];
+  }
+  *out_n = n_out;
+  *out_matches = matches;
+  return YDC_OK;
+}
+
+int ydc_stream_inspect_count(ydc_context* c, const ydc_lease_filter* f, uint32_t n, uint32_t* out_matches) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (n > kSelectMaxFilters)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_count: %u filters > %u in one call", n, kSelectMaxFilters);
+  if (n && (!f || !out_matches))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_inspect_count: %u filters without their columns", n);
+  if (int rc = select_enter(c, "ydc_stream_inspect_count", f, n, 0)) return rc;
+  if (!n) return YDC_OK;
+  auto& sm = c->stream_mode;
+  uint8_t* const d = sm.select.p;
+  SelectState* const st = (SelectState*)d;
+  YDC_LAUNCH(c, "k_select_count", k_select_count<false>, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, c->stream,
+             sm.lt, sm.inspect.on ? sm.d_insp_rec.p : nullptr, sm.inspect.on ? sm.d_insp_pre.p : nullptr,
+             (const LeaseFilter*)(d + kSelectFiltersAt), n, st);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  uint32_t got[kSelectMaxFilters];
+  HIP_TRY(c, hipMemcpy(got, st->matches, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n; ++i)
+    if (got[i] > sm.n_leases)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: %u matches, |L| %u on the host", got[i], sm.n_leases);
+  std::memcpy(out_matches, got, (size_t)n * 4);
   return YDC_OK;
 }
 

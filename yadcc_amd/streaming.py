@@ -210,6 +210,26 @@ def find_running(ctx, row_to_location, keys):
             else (row_to_location[int(h["servant_idx"])], int(h["servant_task_id"])) for h in hits]
 
 
+def iter_tasks(ctx, page, **filter):
+    """The leases that satisfy a filter, a page at a time (binding.Context.stream_inspect_select with the
+    cursor): yields dicts of the columns stream_inspect_tasks returns, at most `page` rows each, in
+    ascending id order; the pages, concatenated, are the filtered lease table. filter: the keywords of
+    stream_inspect_select; an after_id given is where the first page starts. Between two pages the
+    stream may tick: a page shows the table as it is when it is asked for. No compute: every number is
+    the call's."""
+    page = int(page)
+    if page < 1:
+        raise ValueError("iter_tasks: a page of %d rows" % page)
+    while True:
+        cols, matches = ctx.stream_inspect_select(page, **filter)
+        n = len(cols["task_id"])
+        if n:
+            yield cols
+        if matches <= n:
+            return
+        filter["after_id"] = int(cols["task_id"][-1])
+
+
 REQUESTOR_COLUMNS = ("leases", "zombies", "prefetch_leases", "waiting", "waiting_rows")
 
 
