@@ -86,8 +86,14 @@ tests/native/lease_filter_test: tests/native/lease_filter_test.cc $(CSRC)/lease_
 	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tests/native/lease_filter_test.cc
 leasefilter: tests/native/lease_filter_test
 	tests/native/lease_filter_test
+# The fair-share arithmetic (fair_level.h) against the literal progressive fill with 128-bit sums, ASan + UBSan,
+# no GPU (tests/test_stream_fair_binding.py builds and runs the same program).
+tests/native/fair_level_test: tests/native/fair_level_test.cc $(CSRC)/fair_level.h
+	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tests/native/fair_level_test.cc
+fairlevel: tests/native/fair_level_test
+	tests/native/fair_level_test
 clean:
-	rm -f yadcc_amd/libydc.so tests/model/libmodel.so tests/native/lane_rule_test tests/native/admit_clip_test tests/native/occupancy_plan_test tests/native/lease_filter_test
+	rm -f yadcc_amd/libydc.so tests/model/libmodel.so tests/native/lane_rule_test tests/native/admit_clip_test tests/native/occupancy_plan_test tests/native/lease_filter_test tests/native/fair_level_test
 	$(MAKE) -C tests/native clean
 	$(MAKE) -C oracle clean
-.PHONY: all lib probe oracle model native tsan asan flatmap shardplan admitclip lanerule occupancyplan leasefilter clean
+.PHONY: all lib probe oracle model native tsan asan flatmap shardplan admitclip lanerule occupancyplan leasefilter fairlevel clean

@@ -996,6 +996,103 @@ int ydc_stream_quota_set(ydc_context* ctx, uint32_t default_cap, const uint32_t*
 int ydc_stream_quota_result(ydc_context* ctx, uint32_t* out_immediate, uint32_t* out_prefetch, uint32_t cap,
                             uint32_t* out_n, uint32_t* out_rows_clipped, uint32_t* out_n_refused);
 
+/* ---- quota: a fair-share level per tick, computed on the device from demand ------------------------
+ * A static default_cap is a number somebody has to guess: set low, one build alone on an idle farm is
+ * clipped while servants stand free; set high, the first large build fills L and W of a saturated farm.
+ * The right cap depends on how much the cluster can run and on who is asking at this moment, and at the
+ * clip point of the tick the device has both. So the tick computes a max-min fair level: "everybody may
+ * hold up to the level; what fits below it is untouched". The static settings become an upper bound
+ * (default_cap) and a list of exceptions (the overrides). The reference has no such thing
+ * (scheduler_service_impl.cc:266-269). Opt-in: no answer changes until it is switched on.
+ *
+ * This is a setting of an open stream that has the quota on (ydc_stream_quota_begin). So it applies to
+ * a waiting-and-leased or rpc stream with inspection on.
+ *
+ * The tick evaluates everything at the quota's clip point. That point lies:
+ *   - behind steps 1 - 6,
+ *   - behind the servants' expiry,
+ *   - behind the tick's heartbeats (they are in the registry's columns),
+ *   - behind withdrawal's and departure's marks,
+ *   - behind the quota's loads (held(r), above),
+ *   - in front of the quota's clip.
+ *
+ * The pool P has two modes.
+ *   - Registry mode (YDC_FAIR_REGISTRY).
+ *       cap_now = sum over s of top(s) over the registry's rows.
+ *       top(s) = 0 if the low-memory flag is set, max_tasks == 0 or load >= nproc.
+ *       Otherwise top(s) = min(max_tasks, nproc).
+ *       This is the servant's slot count at running == 0, so it does not depend on running_tasks.
+ *       P = cap_now * percent / 100, with 64-bit arithmetic, floored and saturated at 2^32 - 2.
+ *   - Fixed mode (YDC_FAIR_FIXED). P is the caller's number (saturated likewise).
+ *
+ * Consumption and demand.
+ *   - T = live leases that are not parked (their servant did not expire in this tick), attributed or
+ *     not, zombies included, plus the rows of W's entries with deadline > now.
+ *   - Askers are the distinct requestor_ips of the tick's new requests.
+ *   - For an asker r: h_r = the quota's held(r), unchanged. a_r = the sum of its new requests' wants
+ *     (n_immediate + n_prefetch, or 1 outside rpc mode).
+ *   - O = T - sum over the askers of h_r. This is everything held by requestors that ask nothing in this
+ *     tick, or by nobody.
+ *   - It is taken as given. The tick revokes nothing.
+ *   - A requestor with an override is outside the fair share. It contributes the fixed term
+ *     max(h_r, min(h_r + a_r, cap_r)) and keeps its override as its cap.
+ *
+ * The level.
+ *   - f(level) = O + sum over the fair askers of max(h_r, min(h_r + a_r, level)) + sum over the
+ *     overrides of fixed_r. It is non-decreasing in the level.
+ *   - D = max over the fair askers of (h_r + a_r).
+ *   - If there is no fair asker, or f(D) <= P: level = YDC_QUOTA_UNLIMITED. All demand fits.
+ *   - Else if f(0) > P: level = 0.
+ *   - Else the level is the largest integer in [0, D) with f(level) <= P.
+ *   - Sums are 64 bit.
+ *   - The remainder P - f(level), less than one row per asker above the level, stays free in that tick.
+ *
+ * The cap.
+ *   - For a requestor without an override: min(default_cap, max(level, floor_cap)).
+ *   - For a requestor with an override: its override.
+ *   - The clip is then exactly the existing rule (ydc_admit_clip's), unchanged.
+ *
+ * Defining property. The tick and all later ticks, the labels and ydc_stream_quota_result included, are
+ * exactly those of a stream with the static quota whose default_cap was set to that value for this tick.
+ *
+ * Invariant. With floor_cap == 0, after the clip: O + sum over the askers of (h_r + admitted_r) <=
+ * max(P, T).
+ * (Where askers have overrides, what those are admitted stands on top of T: they are outside the fair
+ * share and keep their own caps, so the bound is max(P, T + sum over the overrides of admitted_r).)
+ *
+ *   ydc_stream_quota_fair: a setting like ydc_stream_quota_set, no per-tick staging: it holds from the
+ *     next accepted tick until it is changed; ydc_stream_snapshot is not refused because of it and
+ *     carries none of it. pool: the percent (>= 1) in registry mode, rows in fixed mode, ignored with
+ *     YDC_FAIR_OFF. Carried by ydc_stream_reserve, ydc_stream_book_begin, ydc_stream_withdraw_begin,
+ *     ydc_stream_depart_begin and ydc_stream_quota_begin; off after ydc_stream_end, a new begin and
+ *     ydc_stream_restore. Refused with YDC_ERR_INVALID_ARGUMENT when the quota is off, when the mode is
+ *     unknown, or when the percent is 0 in registry mode. A change between off and on has the step
+ *     captured again at the next tick; a change of numbers alone has not. With the mode off, or before
+ *     the first call, the stream launches exactly what a stream with the quota launches without it.
+ *   ydc_stream_quota_fair_result: about the most recent accepted tick: level (YDC_QUOTA_UNLIMITED: all
+ *     demand fitted), cap_default_effective (the cap of a requestor without an override), the askers and
+ *     those of them with an override, pool = P, held_total = T, held_others = O, asked_rows = the sum of
+ *     a_r, capacity_now = cap_now (both modes), the tick's number as the stream counts its leased ticks,
+ *     and the mode. A tick that ran with the mode off leaves mode == YDC_FAIR_OFF and zeros.
+ *   ydc_fair_level: the same arithmetic on the host; no context, no device. Requestor i holds held[i] and
+ *     asks asked[i]; fixed_cap (nullable: everybody is fair) names its override, YDC_QUOTA_UNLIMITED: it
+ *     is fair (an override of YDC_QUOTA_UNLIMITED itself is min(h + a, cap) = h + a: add it to others).
+ *     others = O, pool = P (saturated at 2^32 - 2). */
+#define YDC_FAIR_OFF 0u
+#define YDC_FAIR_REGISTRY 1u /* pool: percent of the registry's capacity, >= 1 */
+#define YDC_FAIR_FIXED 2u    /* pool: rows */
+int ydc_stream_quota_fair(ydc_context* ctx, uint32_t mode, uint32_t pool, uint32_t floor_cap);
+
+typedef struct {
+  uint32_t level, cap_default_effective, n_askers, n_override_askers;
+  uint64_t pool, held_total, held_others, asked_rows, capacity_now;
+  uint32_t tick_no, mode;
+} ydc_fair_result;
+int ydc_stream_quota_fair_result(ydc_context* ctx, ydc_fair_result* out); /* most recent accepted tick */
+
+int ydc_fair_level(const uint32_t* held, const uint32_t* asked, const uint32_t* fixed_cap /* YDC_QUOTA_UNLIMITED: fair */,
+                   uint32_t n, uint64_t others, uint64_t pool, uint32_t* out_level); /* host arithmetic, no device */
+
 /* ---- departure: a requestor's leases and waiting calls leave inside the tick -----------------------
  * A requestor goes away: a restarted daemon, an interrupted build, a host that dropped off the network.
  * Its blocked calls could be withdrawn by tag only if the host kept every tag per requestor; its leases

@@ -23,6 +23,7 @@ IDX_WAITING = 0xFFFFFFFD  # streaming waiting mode: queued on the device, answer
 IDX_WITHDRAWN = 0xFFFFFFFC  # resolved lists only: the waiting request was withdrawn by its tag
 IDX_OVER_QUOTA = 0xFFFFFFFB  # streams with a quota only: the new request was admitted nothing (its requestor is at its cap)
 QUOTA_UNLIMITED = 0xFFFFFFFF  # stream_quota_set: no cap
+FAIR_OFF, FAIR_REGISTRY, FAIR_FIXED = 0, 1, 2  # stream_quota_fair: the pool's mode (percent of the registry / rows)
 INSPECT_NO_ID = 0xFFFFFFFF  # env_id / requestor_ip of a lease granted while inspection was off
 INSPECT_NO_TIME = -(1 << 63)  # ... its started_at
 OUTLOOK_UNKNOWN = 0xFFFFFFFF  # leases / zombies of an outlook row while inspection is off
@@ -56,6 +57,7 @@ ABI_SYMBOLS = (
     "ydc_stream_requestor_find", "ydc_stream_requestor_get", "ydc_admit_clip",
     "ydc_stream_withdraw_begin", "ydc_stream_withdraw_stage", "ydc_stream_withdraw_result",
     "ydc_stream_quota_begin", "ydc_stream_quota_set", "ydc_stream_quota_result",
+    "ydc_stream_quota_fair", "ydc_stream_quota_fair_result", "ydc_fair_level",
     "ydc_stream_depart_begin", "ydc_stream_depart_stage", "ydc_stream_depart_result",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
@@ -141,6 +143,13 @@ HIT_DTYPE = np.dtype([("pos", "<u4"), ("count", "<u4"), ("servant_idx", "<u4"), 
 # numpy view of ydc_requestor_load (24 bytes)
 REQUESTOR_DTYPE = np.dtype([("requestor_ip", "<u4"), ("leases", "<u4"), ("zombies", "<u4"), ("prefetch_leases", "<u4"),
                             ("waiting", "<u4"), ("waiting_rows", "<u4")])
+
+
+class FairResult(C.Structure):
+    """ydc_fair_result (64 bytes)."""
+    _fields_ = ([(k, C.c_uint32) for k in ("level", "cap_default_effective", "n_askers", "n_override_askers")] +
+                [(k, C.c_uint64) for k in ("pool", "held_total", "held_others", "asked_rows", "capacity_now")] +
+                [(k, C.c_uint32) for k in ("tick_no", "mode")])
 
 
 class DepartCount(C.Structure):
@@ -312,6 +321,10 @@ def lib():
         L.ydc_stream_quota_set.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_quota_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
+        L.ydc_stream_quota_fair.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.ydc_stream_quota_fair_result.argtypes = [C.c_void_p, C.POINTER(FairResult)]
+        L.ydc_fair_level.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64,
+                                     C.POINTER(C.c_uint32)]
         L.ydc_stream_depart_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_depart_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_depart_result.argtypes = [C.c_void_p, C.POINTER(DepartCount), C.c_uint32, C.c_void_p, C.c_void_p,
@@ -406,6 +419,22 @@ def admit_clip(requestor_ip, n_immediate, n_prefetch, load, cap):
     if rc:
         raise YdcError("ydc_admit_clip: %s (a load with unknown lease columns?)" % lib().ydc_strerror(rc).decode())
     return out_imm, out_pre
+
+
+def fair_level(held, asked, fixed_cap=None, others=0, pool=0):
+    """The fair-share level (ydc_fair_level; no context, no device): requestor i holds held[i] and asks
+    asked[i]; fixed_cap[i] its override, QUOTA_UNLIMITED (or fixed_cap None) for a requestor inside the
+    fair share; others: what everybody else holds; pool: what may be held in all. -> the level,
+    QUOTA_UNLIMITED when all demand fits."""
+    h = np.ascontiguousarray(held, dtype=np.uint32)
+    a = np.ascontiguousarray(asked, dtype=np.uint32)
+    f = None if fixed_cap is None else np.ascontiguousarray(fixed_cap, dtype=np.uint32)
+    assert h.ndim == 1 and a.shape == h.shape and (f is None or f.shape == h.shape)
+    out = C.c_uint32(0)
+    rc = lib().ydc_fair_level(_ptr(h), _ptr(a), _ptr(f), len(h), int(others), int(pool), C.byref(out))
+    if rc:
+        raise YdcError("ydc_fair_level: %s" % lib().ydc_strerror(rc).decode())
+    return int(out.value)
 
 
 def device_count():
@@ -1414,6 +1443,20 @@ class Context:
             self._check(lib().ydc_stream_quota_result(self._h, imm.ctypes.data, pre.ctypes.data, len(imm), C.byref(n),
                                                       C.byref(clipped), C.byref(refused)), "ydc_stream_quota_result")
         return imm, pre, int(clipped.value), int(refused.value)
+
+    def stream_quota_fair(self, mode, pool=0, floor_cap=0):
+        """The fair-share level of the open stream's quota from the next accepted tick on
+        (ydc_stream_quota_fair): mode FAIR_REGISTRY with pool percent of the registry's capacity,
+        FAIR_FIXED with pool rows, or FAIR_OFF. A requestor without an override is capped at
+        min(default_cap, max(level, floor_cap)), the level found by the tick itself."""
+        self._check(lib().ydc_stream_quota_fair(self._h, int(mode), int(pool), int(floor_cap)), "ydc_stream_quota_fair")
+
+    def stream_quota_fair_result(self):
+        """The level of the most recent accepted tick and what it was found from
+        (ydc_stream_quota_fair_result): a dict of ydc_fair_result's fields."""
+        r = FairResult()
+        self._check(lib().ydc_stream_quota_fair_result(self._h, C.byref(r)), "ydc_stream_quota_fair_result")
+        return {k: int(getattr(r, k)) for k, _ in FairResult._fields_}
 
     def stream_depart_begin(self, max_depart):
         """Switches the departure of requestors on for the open leased, waiting-and-leased or rpc stream

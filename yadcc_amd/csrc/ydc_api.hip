@@ -46,6 +46,7 @@
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
 #include "stream_depart.h"
+#include "stream_fair.h"
 #include "stream_quota.h"
 #include "stream_withdraw.h"
 #include "tick_kernel.h"
@@ -602,6 +603,13 @@ struct ydc_context {
       PinnedBuf h_res;  // page-locked: admitted immediate | admitted prefetch | QuotaDone
       uint32_t *h_imm = nullptr, *z_imm = nullptr, *h_pre = nullptr, *z_pre = nullptr;
       QuotaDone *h_done = nullptr, *z_done = nullptr;
+      // The fair-share level (ydc_stream_quota_fair; stream_fair.h): ask[] beside the table, the pairs of
+      // fair askers, the sums, the tick's header and result and the settings' copy in HBM;
+      // the page-locked result. They exist with the quota; a stream whose mode is off launches nothing on them.
+      DevBuf<uint8_t> fd;
+      FairTick fair{};
+      PinnedBuf h_fair;
+      FairResult *h_fres = nullptr, *z_fres = nullptr;
       struct Host {
         // ydc_stream_quota_set: the default and the overrides (sorted by requestor), and whether the
         // device copy still has to follow them (a set, a grown stream).
@@ -612,7 +620,12 @@ struct ydc_context {
         // The most recent accepted tick (ydc_stream_quota_result).
         std::vector<uint32_t> imm, pre;
         uint32_t rows_clipped = 0, n_refused = 0;
+        // ydc_stream_quota_fair: the mode and its two numbers (`dirty` covers them), and the most recent
+        // accepted tick's result (ydc_stream_quota_fair_result).
+        uint32_t fair_mode = kFairOff, fair_pool = 0, fair_floor = 0;
+        FairResult fair_res{};
       } host;
+      bool fair_on() const { return on && host.fair_mode != kFairOff; }
       // 0: off; otherwise max_overrides + 1 (what stream_alloc and stream_regrow are told).
       uint32_t code() const { return on ? max_overrides + 1 : 0; }
     } quota;
@@ -4514,8 +4527,22 @@ void enqueue_stream_gather(ydc_context* c, const TickArena& a) {
     YDC_LAUNCH(c, "k_quota_loads", k_quota_loads, dim3(l_blocks + ceil_div(MW, 256)), dim3(256), 0, c->stream, sm.lt,
                sm.d_insp_rec.p, l_blocks, rpc ? sm.rw.ip : sm.wq.ip, rpc ? sm.rw.deadline : sm.wq.deadline,
                rpc ? sm.rw.n_imm : nullptr, rpc ? sm.rw.n_pre : nullptr, sm.ws, MW, a.lh, q.tb);
+    // With the fair-share level: the pool, what is held and what is asked summed up, the level found and
+    // the clip's header of this tick written (stream_fair.h). The clip then reads that header; the
+    // override arrays are the settings' own.
+    QuotaCaps caps = q.caps;
+    if (q.fair_on()) {
+      const uint32_t r_blocks = ceil_div(c->reg.n, 256), w_blocks = ceil_div(MW, 256);
+      YDC_LAUNCH(c, "k_fair_sums", k_fair_sums, dim3(r_blocks + l_blocks + w_blocks + ceil_div(MT, 256)), dim3(256), 0,
+                 c->stream, FairRegistry{c->d_nproc.p, c->d_load.p, c->d_max_tasks.p, c->d_flags.p, c->reg.n}, r_blocks,
+                 sm.lt, l_blocks, rpc ? sm.rw.deadline : sm.wq.deadline, rpc ? sm.rw.n_imm : nullptr,
+                 rpc ? sm.rw.n_pre : nullptr, sm.ws, MW, w_blocks, a.lh, rpc ? a.nimm : nullptr, rpc ? a.npre : nullptr,
+                 a.q_n, MT, q.tk, q.tb, q.fair);
+      YDC_LAUNCH(c, "k_fair_level", k_fair_level, dim3(1), dim3(kFairThreads), 0, c->stream, q.tb, q.caps, q.fair, a.lh);
+      caps.hdr = q.fair.hdr;
+    }
     YDC_LAUNCH(c, "k_quota_clip", k_quota_clip, dim3(q.tiles), dim3(256), 0, c->stream, a.ip, a.env,
-               rpc ? a.nimm : nullptr, rpc ? a.npre : nullptr, a.q_n, MT, q.tb, q.caps, q.tk);
+               rpc ? a.nimm : nullptr, rpc ? a.npre : nullptr, a.q_n, MT, q.tb, caps, q.tk);
   }
   if (sm.rpc()) enqueue_rpc_expand(c, a);
   else enqueue_wait_gather(c, a);
@@ -4662,6 +4689,9 @@ void enqueue_stream_answer(ydc_context* c, const TickArena& a, const DeviceParam
     YDC_LAUNCH(c, "k_quota_label", k_quota_label, dim3(ceil_div(std::max(sm.caps.max_tasks, q.tb.mask + 1), 256)),
                dim3(256), 0, c->stream, q.tb, q.tk, a.q_n, sm.caps.max_tasks, a.lh, rpc ? sm.rz.status : sm.z_out, q.z_imm,
                rpc ? q.z_pre : nullptr, q.z_done, prm, check_slot);
+    // With the fair-share level: its result block, under the same gate (stream_fair.h).
+    if (q.fair_on())
+      YDC_LAUNCH(c, "k_fair_done", k_fair_done, dim3(1), dim3(64), 0, c->stream, q.fair.res, q.z_fres, prm, check_slot);
   }
 }
 
@@ -5152,6 +5182,20 @@ int stream_alloc(ydc_context* c, ydc_context::Stream& sm, const ydc_stream_caps&
     q.z_pre = (uint32_t*)(q.h_res.z + r_pre);
     q.h_done = (QuotaDone*)(q.h_res.p + r_done);
     q.z_done = (QuotaDone*)(q.h_res.z + r_done);
+    // The fair-share level's columns (stream_fair.h): ask | the list of pairs | sums |
+    // the tick's header | the result | the settings.
+    size_t f_off = 0;
+    const size_t f_ask = section(&f_off, (size_t)slots * 4);
+    const size_t f_pair = section(&f_off, (size_t)slots * 8);
+    const size_t f_sums = section(&f_off, sizeof(FairSums)), f_hdr = section(&f_off, 8);
+    const size_t f_res = section(&f_off, sizeof(FairResult)), f_set = section(&f_off, sizeof(FairSet));
+    HIP_TRY(c, q.fd.reserve(f_off));
+    uint8_t* fb = q.fd.p;
+    q.fair = FairTick{(uint32_t*)(fb + f_ask), (uint2*)(fb + f_pair), (FairSums*)(fb + f_sums), (uint32_t*)(fb + f_hdr),
+                      (FairResult*)(fb + f_res), (const FairSet*)(fb + f_set)};
+    HIP_TRY(c, q.h_fair.reserve(sizeof(FairResult)));
+    q.h_fres = (FairResult*)q.h_fair.p;
+    q.z_fres = (FairResult*)q.h_fair.z;
   }
   sm.want_passes = sm.window_max = sm.window_ticks = 0;
   sm.stale = true;
@@ -5190,7 +5234,9 @@ int stream_reset(ydc_context* c, ydc_context::Stream& sm) {
   }
   if (sm.quota.on) {  // (every slot of the table free; the settings follow at the next tick)
     HIP_TRY(c, hipMemsetAsync(sm.quota.d.p, 0, sm.quota.d.cap, c->stream));
+    HIP_TRY(c, hipMemsetAsync(sm.quota.fd.p, 0, sm.quota.fd.cap, c->stream));  // (ask[] and the sums clear)
     std::memset(sm.quota.h_done, 0, sizeof(QuotaDone));
+    std::memset(sm.quota.h_fres, 0, sizeof(FairResult));
     sm.quota.host.dirty = true;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -5658,6 +5704,41 @@ int ydc_stream_quota_set(ydc_context* c, uint32_t default_cap, const uint32_t* r
     h.cap[i] = cap[order[i]];
   }
   h.dirty = true;  // (the device copy follows in front of the next accepted tick)
+  return YDC_OK;
+}
+
+int ydc_stream_quota_fair(ydc_context* c, uint32_t mode, uint32_t pool, uint32_t floor_cap) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.quota.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_fair: the stream has no quota (ydc_stream_quota_begin)");
+  if (mode > YDC_FAIR_FIXED) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_fair: mode %u is unknown", mode);
+  if (mode == YDC_FAIR_REGISTRY && pool == 0)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_fair: 0 percent of the registry's capacity");
+  auto& h = sm.quota.host;
+  // (between off and on the step launches other kernels: captured again at the next tick; numbers alone are read from HBM)
+  if ((h.fair_mode == kFairOff) != (mode == kFairOff)) sm.stale = true;
+  h.fair_mode = mode;
+  h.fair_pool = pool;
+  h.fair_floor = floor_cap;
+  h.dirty = true;  // (the device copy follows in front of the next accepted tick)
+  return YDC_OK;
+}
+
+int ydc_stream_quota_fair_result(ydc_context* c, ydc_fair_result* out) {
+  static_assert(sizeof(ydc_fair_result) == sizeof(FairResult), "ydc_fair_result");
+  if (!c || !out) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.quota.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_quota_fair_result: the stream has no quota (ydc_stream_quota_begin)");
+  std::memcpy(out, &sm.quota.host.fair_res, sizeof *out);
+  return YDC_OK;
+}
+
+int ydc_fair_level(const uint32_t* held, const uint32_t* asked, const uint32_t* fixed_cap, uint32_t n, uint64_t others,
+                   uint64_t pool, uint32_t* out_level) {
+  if (!out_level || (n && (!held || !asked))) return YDC_ERR_INVALID_ARGUMENT;
+  *out_level = fair_level(held, asked, fixed_cap, n, others, pool);
   return YDC_OK;
 }
 
@@ -6899,9 +6980,14 @@ static int stream_quota_sync(ydc_context* c) {
   auto& h = q.host;
   if (h.table_dirty) {
     HIP_TRY(c, hipMemset(q.tb.word, 0, ((size_t)q.tb.mask + 1) * 8));
+    // (... and so are ask[] and the sums of the fair-share level, which k_fair_level may not have cleared)
+    HIP_TRY(c, hipMemset(q.fair.ask, 0, ((size_t)q.tb.mask + 1) * 4));
+    HIP_TRY(c, hipMemset(q.fair.sums, 0, sizeof(FairSums)));
     h.table_dirty = false;
   }
   if (!h.dirty) return YDC_OK;
+  const FairSet set{h.fair_mode, h.fair_pool, h.fair_floor, 0};
+  HIP_TRY(c, hipMemcpy(const_cast<FairSet*>(q.fair.set), &set, sizeof set, hipMemcpyHostToDevice));
   const uint32_t n = (uint32_t)h.ip.size();
   if (n > q.max_overrides) return fail(c, YDC_ERR_NOT_CONVERGED, "%u overrides > max_overrides %u", n, q.max_overrides);
   if (n) {
@@ -7111,6 +7197,16 @@ static int stream_tick_finish(ydc_context* c, const StreamCall& t, const TickSta
     if (t.rt) q.host.pre.assign(q.h_pre, q.h_pre + n_tasks);
     q.host.rows_clipped = d.rows_clipped;
     q.host.n_refused = n_refused = d.n_refused;
+    if (q.fair_on()) {  // (k_fair_done has stored the level's result block)
+      const FairResult& f = *q.h_fres;
+      if (f.tick_no != sm.lease_tick || f.mode != q.host.fair_mode)
+        return fail(c, YDC_ERR_NOT_CONVERGED, "fair share: result of tick %u in mode %u (expected %u, %u)", f.tick_no, f.mode,
+                    sm.lease_tick, q.host.fair_mode);
+      q.host.fair_res = f;
+    } else {
+      q.host.fair_res = FairResult{};
+      q.host.fair_res.tick_no = sm.lease_tick;
+    }
   }
   if (t.rt) return stream_rpc_finish(c, t, ts);
   c->stats.n_tasks = n_tasks;

@@ -268,6 +268,16 @@ def admit(ctx, requests, n_immediate, n_prefetch, cap):
     return imm, pre, (imm.astype(np.uint64) + pre) > 0
 
 
+def fair_share(ctx, percent=100, floor=1):
+    """The common setting of the fair-share level (binding.Context.stream_quota_fair) for a stream with
+    the quota on: the pool is `percent` of what the registry can run, as every tick's heartbeats leave
+    it, and nobody without an override is capped below `floor`. The static default_cap stays an upper
+    bound, the overrides stay exceptions. -> the function to call after a tick for that tick's level
+    (binding.Context.stream_quota_fair_result). No compute: every number is the call's."""
+    ctx.stream_quota_fair(binding.FAIR_REGISTRY, percent, floor)
+    return ctx.stream_quota_fair_result
+
+
 DEPART_COLUMNS = ("requestor_ip", "leases", "zombies", "waiting", "waiting_rows")
 
 
