@@ -1376,6 +1376,12 @@ const char* ydc_td_dump_internals(ydc_td* td);
  * tests/td_scenarios.py:concurrent_callers_linearize checks. */
 int ydc_td_oplog_enable(ydc_td* td, int on);
 const char* ydc_td_oplog_take(ydc_td* td);
+/* Test counter (not part of ydc_td_stats): turns so far in which renumbering the parked requests
+ * created a requestor alias — a parked waiter's address had become a shorter prefix of a
+ * multi-colon servant location — while new requests were waiting to be served in the same turn.
+ * tests/native/td_linearize.cc reports it, so that a run can show that it met the situation.
+ * Negative: YDC_ERR_*. */
+int64_t ydc_td_alias_renumbered_turns(ydc_td* td);
 
 #ifdef __cplusplus
 }

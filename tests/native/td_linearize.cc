@@ -2,7 +2,17 @@
 // interpreter between the threads and the library), through the C-ABI alone: links the CPU
 // stand-in (libtd_stub.so; also built with -fsanitize=thread) or libydc.so on the GPU box.
 //
-//   td_linearize <out.json> [servants] [threads] [calls per thread] [max_tasks cap, 0 = none] [seed]
+//   td_linearize <out.json> [servants] [threads] [calls per thread] [max_tasks cap, 0 = none] [seed] [shape]
+//
+// shape "prefixes" (default "plain": 10.x.y.z:port): locations are bracketed and have several ':'
+// ("[f:1:2]:8335", three ports per host), so that each answers to several requestor addresses
+// (task_dispatcher.cc:66-69); the registry thread registers further such servants during the run
+// ("[f:40:1]:8335", ...; short leases, some renewed, some left to expire); a caller changes its
+// address every 25 calls — drawn from EVERY prefix of all those locations, matching or not, and
+// every other time from the shorter prefixes ("[f:40") of the locations that are about to be
+// registered: a waiter parked from such an address becomes an alias while it is parked, and the
+// turn that renumbers it has new requests to serve as well. How often that happened is written
+// out ("alias_renumbered_turns", ydc_td_alias_renumbered_turns).
 //
 // Caller threads mix single requests (some parked with a deadline), small batches, FreeTask
 // followed at once by the next request, lease renewals; a freer thread frees grants handed over to
@@ -19,7 +29,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <mutex>
+#include <set>
 #include <string>
 #include <thread>
 #include <vector>
@@ -89,7 +101,7 @@ void JsonStr(std::FILE* f, const std::string& s) {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: td_linearize out.json [servants threads calls cap seed]\n");
+    std::fprintf(stderr, "usage: td_linearize out.json [servants threads calls cap seed shape]\n");
     return 2;
   }
   const int n_servants = argc > 2 ? std::atoi(argv[2]) : 2000;
@@ -97,6 +109,13 @@ int main(int argc, char** argv) {
   const int calls = argc > 4 ? std::atoi(argv[4]) : 2000;
   const unsigned cap = argc > 5 ? (unsigned)std::atoi(argv[5]) : 0;
   const unsigned long long seed = argc > 6 ? std::strtoull(argv[6], nullptr, 10) : 1;
+  const std::string shape = argc > 7 ? argv[7] : "plain";
+  if (shape != "plain" && shape != "prefixes") {
+    std::fprintf(stderr, "unknown shape %s\n", shape.c_str());
+    return 2;
+  }
+  const bool prefixes = shape == "prefixes";
+  const int n_future = prefixes ? 512 : 0;  // servants the registry thread may add during the run
   for (int i = 0; i < 4; ++i) {
     char b[80];
     std::snprintf(b, sizeof b, "c0ffee%04d%054d", i, 0);
@@ -111,43 +130,91 @@ int main(int argc, char** argv) {
   ydc_td_set_clock_ns(td, 0);
   ydc_td_oplog_enable(td, 1);
   Pool pool;
-  pool.locations.resize(n_servants);
-  pool.envs.resize(n_servants);
-  pool.rows.resize(n_servants);
+  pool.locations.resize(n_servants + n_future);
+  pool.envs.resize(n_servants + n_future);
+  pool.rows.resize(n_servants + n_future);
   Rng r0{seed * 977 + 1};
-  std::vector<long long> lease_ms(n_servants);
-  for (int i = 0; i < n_servants; ++i) {
-    // (every fifth servant shares its host with the one before: the `self` rule, task_dispatcher.cc:372-396)
-    const int host = i % 5 == 4 ? i - 1 : i;
-    pool.locations[i] = "10." + std::to_string(2 + host / 60000) + "." + std::to_string((host / 250) % 240) + "." +
-                        std::to_string(host % 250) + ":" + std::to_string(8335 + (i - host));
+  std::vector<long long> lease_ms(n_servants + n_future);
+  auto hex = [](int v) {
+    char b[16];
+    std::snprintf(b, sizeof b, "%x", v);
+    return std::string(b);
+  };
+  for (int i = 0; i < n_servants + n_future; ++i) {
+    if (!prefixes) {
+      // (every fifth servant shares its host with the one before: the `self` rule, task_dispatcher.cc:372-396)
+      const int host = i % 5 == 4 ? i - 1 : i;
+      pool.locations[i] = "10." + std::to_string(2 + host / 60000) + "." + std::to_string((host / 250) % 240) + "." +
+                          std::to_string(host % 250) + ":" + std::to_string(8335 + (i - host));
+    } else if (i < n_servants) {
+      const int host = i / 3;  // three ports per host
+      pool.locations[i] = "[f:" + hex(host / 4) + ":" + hex(host % 4) + "]:" + std::to_string(8335 + i % 3);
+    } else {
+      const int j = i - n_servants;  // two ports per host, a second field no earlier servant has
+      pool.locations[i] = "[f:" + hex(0x40 + j / 2) + ":1]:" + std::to_string(8335 + j % 2);
+    }
     std::memset(&pool.rows[i], 0, sizeof pool.rows[i]);
     Personality(r0, i, cap, &pool);
-    lease_ms[i] = i % 7 == 0 ? 3000 + (long long)r0.below(6000) : 3600000;
-    if (ydc_td_keep_servant_alive(td, &pool.rows[i], lease_ms[i] * 1000000) != YDC_OK) return 3;
+    lease_ms[i] = i >= n_servants ? 40 + (long long)r0.below(200) : i % 7 == 0 ? 3000 + (long long)r0.below(6000) : 3600000;
+    if (i < n_servants && ydc_td_keep_servant_alive(td, &pool.rows[i], lease_ms[i] * 1000000) != YDC_OK) return 3;
   }
+  // prefixes: every prefix of every location, registered from the start or later, matching or not
+  // (the construction of tests/td_scenarios.py:address_prefix_forms).
+  std::vector<std::string> all_prefixes;
+  if (prefixes) {
+    std::set<std::string> seen;
+    for (const std::string& loc : pool.locations)
+      for (std::size_t n = 0; n <= loc.size(); ++n) seen.insert(loc.substr(0, n));
+    all_prefixes.assign(seen.begin(), seen.end());
+  }
+  std::atomic<int> next_future{0};  // pool.locations[n_servants + next_future] is registered next
   std::atomic<bool> stop{false};
   std::atomic<int> failed{0};
   std::mutex mu;  // handed_over, pool rows (registry thread only writes; callers never read rows)
   std::vector<unsigned long long> handed_over;
-  std::vector<std::vector<Op>> hist(n_threads + 1);
-  std::vector<std::string> ips(n_threads);
+  // A thread's calls in program order, per requestor address it used (one address unless `prefixes`;
+  // going back to an address appends to that address's list, which keeps the thread's order).
+  struct Calls {
+    std::string ip;
+    std::vector<Op> ops;
+  };
+  std::vector<std::deque<Calls>> hist(n_threads + 1);
+  hist[n_threads].emplace_back();  // the freer (no address)
 
   auto caller = [&](int k) {
     Rng r{seed * 1000 + (unsigned)k};
-    ips[k] = k % 3 ? "172.20." + std::to_string(k) + ".7"
-                   : pool.locations[(std::size_t)k * 37 % n_servants].substr(0, pool.locations[(std::size_t)k * 37 % n_servants].find(':'));
-    const std::string& ip = ips[k];
+    std::string ip = k % 3 ? "172.20." + std::to_string(k) + ".7"
+                           : pool.locations[(std::size_t)k * 37 % n_servants].substr(0, pool.locations[(std::size_t)k * 37 % n_servants].find(':'));
     std::vector<unsigned long long> mine;
-    std::vector<Op>& h = hist[k];
-    h.reserve(calls * 2);
+    std::vector<Op>* hp = nullptr;
+    auto use_address = [&] {
+      for (Calls& c : hist[k])
+        if (c.ip == ip) {
+          hp = &c.ops;
+          return;
+        }
+      hist[k].emplace_back();
+      hist[k].back().ip = ip;
+      hp = &hist[k].back().ops;
+    };
+    if (!prefixes) use_address();
     char loc[64];
     for (int c = 0; c < calls && !stop.load(std::memory_order_relaxed); ++c) {
+      if (prefixes && c % 25 == 0) {
+        if (r.below(2)) {
+          ip = all_prefixes[r.below((unsigned)all_prefixes.size())];
+        } else {
+          const std::string& soon = pool.locations[n_servants + (next_future.load() + (int)r.below(4)) % n_future];
+          ip = soon.substr(0, soon.find(':', 3));  // "[f:40": a shorter prefix of a location to come
+        }
+        use_address();
+      }
+      std::vector<Op>& h = *hp;
       const unsigned ev = r.below(100);
       if (ev < 55 || mine.empty()) {
         const std::string dg = r.below(50) == 0 ? std::string("unknown") : g_digests[r.below(4)];
         const long long leases[] = {40, 200, 60000};
-        const long long lease = leases[r.below(3)], timeout = r.below(4) == 0 ? 2 : 0;
+        const long long lease = leases[r.below(3)], timeout = r.below(prefixes ? 2 : 4) == 0 ? 2 : 0;
         std::uint64_t id = 0;
         Op op{0, 0, 0, "", NowNs(), 0};
         const int rc = ydc_td_wait_for_starting_new_task(td, ip.c_str(), r.below(2) ? 20 : 0, dg.c_str(), lease * 1000000,
@@ -214,7 +281,7 @@ int main(int argc, char** argv) {
     handed_over.insert(handed_over.end(), mine.begin(), mine.end());
   };
   auto freer = [&] {
-    std::vector<Op>& h = hist[n_threads];
+    std::vector<Op>& h = hist[n_threads][0].ops;
     for (;;) {
       unsigned long long id = ~0ull;
       {
@@ -239,7 +306,19 @@ int main(int argc, char** argv) {
     Rng r{seed * 31 + 7};
     std::uint64_t unknown[8];
     while (!stop.load()) {
-      const int i = (int)r.below((unsigned)n_servants);
+      int i = (int)r.below((unsigned)n_servants);
+      if (prefixes) {
+        // One call in eight registers the next new servant; the others renew what is registered,
+        // the new ones among them only now and then (odd ones never: they expire).
+        const int registered = next_future.load();
+        if (r.below(8) == 0 && registered < n_future) {
+          i = n_servants + registered;
+          next_future.store(registered + 1);
+        } else {
+          i = (int)r.below((unsigned)(n_servants + registered));
+          if (i >= n_servants && ((i & 1) || r.below(4))) i = (int)r.below((unsigned)n_servants);
+        }
+      }
       if (r.below(5)) {
         pool.rows[i].current_load = r.below((unsigned)(pool.rows[i].num_processors * 5 / 4));
       } else {
@@ -285,14 +364,17 @@ int main(int argc, char** argv) {
   ydc_td_host_stats(td, &hs);
   std::FILE* f = std::fopen(argv[1], "w");
   if (!f) return 4;
-  std::fprintf(f, "{\"requests_per_device_turn\": %.3f, \"dump\": %s,\n\"threads\": [", (double)hs.requests / (hs.batches ? hs.batches : 1),
-               dump.c_str());
-  for (int k = 0; k <= n_threads; ++k) {
+  std::fprintf(f, "{\"requests_per_device_turn\": %.3f, \"alias_renumbered_turns\": %lld, \"dump\": %s,\n\"threads\": [",
+               (double)hs.requests / (hs.batches ? hs.batches : 1), (long long)ydc_td_alias_renumbered_turns(td), dump.c_str());
+  std::vector<const Calls*> lists;  // one entry per (thread, address); the freer's comes last
+  for (const auto& of_thread : hist)
+    for (const Calls& c : of_thread) lists.push_back(&c);
+  for (std::size_t k = 0; k != lists.size(); ++k) {
     std::fprintf(f, "%s{\"ip\": ", k ? ",\n" : "");
-    if (k < n_threads) JsonStr(f, ips[k]); else std::fputs("null", f);
+    if (k + 1 != lists.size()) JsonStr(f, lists[k]->ip); else std::fputs("null", f);
     std::fputs(", \"ops\": [", f);
     bool first = true;
-    for (const Op& op : hist[k]) {
+    for (const Op& op : lists[k]->ops) {
       std::fputs(first ? "" : ", ", f);
       first = false;
       if (op.kind == 0) {

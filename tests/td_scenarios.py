@@ -627,11 +627,14 @@ def verify_linearizable(log, dump, threads, check_real_time=True):
     return n
 
 
-def native_linearize(binary, out_path, n_servants=2000, n_threads=12, calls=2000, cap=0, seed=1, env=None):
-    """Runs tests/native/td_linearize (threads in C++, through the C-ABI) and verifies what it wrote."""
+def native_linearize(binary, out_path, n_servants=2000, n_threads=12, calls=2000, cap=0, seed=1, env=None,
+                     shape="plain"):
+    """Runs tests/native/td_linearize (threads in C++, through the C-ABI) and verifies what it wrote.
+    shape "prefixes": bracketed multi-colon locations, requestor addresses from all their prefixes,
+    servants that register and expire during the run (td_linearize.cc)."""
     import json
     import subprocess
-    r = subprocess.run([binary, out_path, str(n_servants), str(n_threads), str(calls), str(cap), str(seed)],
+    r = subprocess.run([binary, out_path, str(n_servants), str(n_threads), str(calls), str(cap), str(seed), shape],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0 and "TD-LINEARIZE-WRITTEN" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     j = json.load(open(out_path))
@@ -643,6 +646,7 @@ def native_linearize(binary, out_path, n_servants=2000, n_threads=12, calls=2000
         k = e["op"] + (":%d" % e["st"] if e["op"] == "wait" else "")
         kinds[k] = kinds.get(k, 0) + 1
     return {"records": n, "kinds": kinds, "requests_per_device_turn": j["requests_per_device_turn"],
+            "alias_renumbered_turns": j["alias_renumbered_turns"],
             "retried_attempts": sum(1 for e in j["log"] if e["op"] == "wait" and e["try"] > 1)}
 
 

@@ -115,15 +115,29 @@ def test_concurrent_callers_linearize(shape):
 
 
 @needs_ref
-@pytest.mark.parametrize("shape", ["roomy", "saturated", "crowd"])
+@pytest.mark.parametrize("shape", ["roomy", "saturated", "crowd", "prefixes"])
 def test_native_callers_linearize(shape, tmp_path):
     """... with the threads in C++ (tests/native/td_linearize.cc linked against libydc.so): 16
     callers at full speed on 2000 servants (roomy: queued FreeTasks meet the same thread's next
-    request inside one device turn) and on a saturated pool (parked waiters retried at wake-ups)."""
+    request inside one device turn) and on a saturated pool (parked waiters retried at wake-ups).
+    prefixes: bracketed multi-colon locations on a saturated pool of 40, requestor addresses from
+    every prefix of them, servants registering and expiring during the run, so that parked waiters
+    turn into requestor aliases (host-table aliases on the device) while requests keep arriving.
+    Whether a turn renumbers parked waiters into aliases WITH arrivals in hand depends on the
+    threads' timing against the device's turns, so that count is reported, not asserted, here: the
+    deterministic proof of that turn is tests/native/td_alias_turn_test.cc on the stand-in
+    (tests/test_task_dispatcher_stub.py); this asserts that every answer equals the reference's."""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     subprocess.check_call(["make", "-s", "tests/native/td_linearize_gpu"], cwd=root)
+    if shape == "prefixes":
+        r = S.native_linearize(os.path.join(root, "tests", "native", "td_linearize_gpu"), str(tmp_path / "lin.json"),
+                               seed=3, n_servants=40, n_threads=16, calls=300, cap=1, shape="prefixes")
+        print("alias_renumbered_turns", r["alias_renumbered_turns"], "records", r["records"], "retried",
+              r["retried_attempts"])
+        assert r["records"] > 3000 and r["retried_attempts"] > 1000 and r["kinds"]["wait:0"] > 300
+        return
     args = {"roomy": dict(n_servants=2000, n_threads=16, calls=2500),
             "saturated": dict(n_servants=40, n_threads=16, calls=3000, cap=1),
             # more parked requests than a device turn takes: placed again in segments (gpu_task_dispatcher.cc:

@@ -112,6 +112,56 @@ def test_sanitizer_build(san):
                                                                      out.stderr[-4000:])
 
 
+ALIAS_TURN_CASES = "ABCD"
+
+
+def _alias_turn(target, out_dir):
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run(["make", "-s", "-C", NATIVE, target, "ALIASTURN_OUT=%s" % out_dir], capture_output=True,
+                         text=True, timeout=600, env=env)
+    assert out.returncode == 0 and "TD-ALIAS-TURN-OK" in out.stdout, (out.stdout[-2000:], out.stderr[-6000:])
+
+
+@pytest.fixture(scope="module")
+def alias_turn_logs(tmp_path_factory):
+    """What the ASan + UBSan build of tests/native/td_alias_turn_test.cc wrote for its cases."""
+    out_dir = tmp_path_factory.mktemp("alias_turn")
+    _alias_turn("aliasturn", out_dir)
+    return out_dir
+
+
+@pytest.mark.parametrize("san", ["asan", "tsan"])
+def test_alias_turn_sanitized(san, alias_turn_logs, tmp_path):
+    """One turn of UnsafeDrainQueue in which renumbering the parked waiters creates a requestor alias
+    (a waiter parked from "[fe80", then "[fe80:1]:8335" registers) while new requests arrive — held
+    together by a clock that blocks the registering thread under the dispatcher's lock
+    (tests/native/td_alias_turn_test.cc). A: 24 arrivals of 24 triples against one parked triple — a
+    turn that keeps the arrivals' numbers from before the renumbering reads sig_dead_ out of bounds
+    (AddressSanitizer: heap-buffer-overflow in UnsafeDrainQueue); B: the stale number collides with
+    the parked triple's and the arrival is answered Timeout unsent, where the reference grants it;
+    C: two aliases in one turn; D: the alias's servant expires again under a parked waiter."""
+    if san == "tsan":
+        _alias_turn("aliasturn_tsan", tmp_path)
+    for case in ALIAS_TURN_CASES:
+        assert (alias_turn_logs / ("alias_turn_%s.json" % case)).exists()
+
+
+@needs_ref
+@pytest.mark.parametrize("case", list(ALIAS_TURN_CASES))
+def test_alias_turn_matches_reference(case, alias_turn_logs):
+    """... and each case's logged order, replayed through the reference class, gives the same answers
+    and the same final DumpInternals; every thread finds its calls in program and real-time order."""
+    import json
+    j = json.load(open(alias_turn_logs / ("alias_turn_%s.json" % case)))
+    threads = [{"ip": t["ip"], "ops": [(o[0], tuple(o[1:4]), o[4], o[5]) if o[0] == "wait" else (o[0], o[1], o[2], o[3])
+                                       for o in t["ops"]]} for t in j["threads"]]
+    n = S.verify_linearizable(j["log"], j["dump"], threads)
+    waits = [e for e in j["log"] if e["op"] == "wait"]
+    assert n >= 20 and any(e["ip"] == "[fe80" for e in waits)
+    if case == "B":  # the request the unfixed turn declared a known Timeout
+        assert [(e["st"], e.get("loc")) for e in waits if e["ip"] == "7.7.7.7"] == [(D.GRANTED, "[fe80:1]:8335")]
+
+
 def test_flat_string_map_against_unordered_map():
     """The host class's string tables (yadcc_amd/csrc/flat_string_map.h: open addressing, backward
     shift on erase, miss filter) against std::unordered_map under random inserts / lookups /
@@ -133,14 +183,24 @@ def test_concurrent_callers_linearize(seed):
 
 
 @needs_ref
-@pytest.mark.parametrize("shape", ["roomy", "saturated", "crowd"])
+@pytest.mark.parametrize("shape", ["roomy", "saturated", "crowd", "prefixes"])
 def test_native_callers_linearize(shape, tmp_path):
     """The same proof with the threads in C++ (tests/native/td_linearize.cc, through the C-ABI): 12
     callers at full speed, so that FreeTask queued behind somebody's device turn and the same
     thread's next request do meet in one turn (a build that applies queued frees after placing
     fails here on program order). roomy: nobody parks, frees are queued; saturated: most requests
-    park and are retried at FreeTask's wake-ups."""
+    park and are retried at FreeTask's wake-ups. prefixes: bracketed multi-colon locations on a
+    saturated pool, requestor addresses from every prefix of them, servants registering and expiring
+    during the run — parked waiters turn into requestor aliases and are renumbered in turns that
+    have arrivals to serve (alias_renumbered_turns; seed 3 with 16 threads x 600 calls on 40 servants
+    gives 5 to 20 such turns on the stand-in, seeds 1-6 at half the calls 3 to 9)."""
     subprocess.check_call(["make", "-s", "-C", NATIVE, "linearize"])
+    if shape == "prefixes":
+        r = S.native_linearize(os.path.join(NATIVE, "td_linearize_stub"), str(tmp_path / "lin.json"), seed=3,
+                               n_servants=40, n_threads=16, calls=600, cap=1, shape="prefixes")
+        assert r["alias_renumbered_turns"] >= 1
+        assert r["records"] > 10000 and r["retried_attempts"] > 3000 and r["kinds"]["wait:0"] > 500
+        return
     args = {"roomy": dict(n_servants=300, calls=1500), "saturated": dict(n_servants=40, calls=3000, cap=1),
             # crowd: more parked requests than one device turn takes — placed again in segments, those
             # whose (digest, version, host) already came back Timeout in the turn not sent at all
@@ -159,6 +219,22 @@ def test_native_callers_linearize_tsan(tmp_path):
     r = S.native_linearize(os.path.join(NATIVE, "td_linearize_tsan"), str(tmp_path / "lin.json"), n_servants=60,
                            n_threads=8, calls=600, seed=4, env=env)
     assert r["records"] > 3000
+
+
+@needs_ref
+@pytest.mark.parametrize("san", ["tsan", "asan"])
+def test_native_callers_linearize_prefixes_sanitized(san, tmp_path):
+    """The prefixes shape under ThreadSanitizer and under ASan + UBSan: no report, the logged order
+    equals the reference's, and the run did renumber parked waiters into aliases with arrivals in the
+    turn (seed 4, 16 threads x 300 calls on 40 servants: 2 to 6 such turns in either build here). A
+    long-lived dispatcher's sig_dead_ keeps the capacity of earlier turns, so a stale index mostly
+    stays inside the allocation: the bounds proof is test_alias_turn_sanitized, this is the soak."""
+    subprocess.check_call(["make", "-s", "-C", NATIVE, "linearize"])
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1")
+    r = S.native_linearize(os.path.join(NATIVE, "td_linearize_" + san), str(tmp_path / "lin.json"), n_servants=40,
+                           n_threads=16, calls=300, cap=1, seed=4, env=env, shape="prefixes")
+    assert r["alias_renumbered_turns"] >= 1
+    assert r["records"] > 3000 and r["retried_attempts"] > 1000
 
 
 @needs_ref

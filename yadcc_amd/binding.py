@@ -70,6 +70,7 @@ ABI_SYMBOLS = (
     "ydc_td_free_tasks", "ydc_td_host_stats", "ydc_td_running_tasks_acquire", "ydc_td_running_tasks_release",
     "ydc_td_notify_servant_running_tasks", "ydc_td_get_running_tasks",
     "ydc_td_on_expiration_timer", "ydc_td_dump_internals", "ydc_td_oplog_enable", "ydc_td_oplog_take",
+    "ydc_td_alias_renumbered_turns",
 )
 
 

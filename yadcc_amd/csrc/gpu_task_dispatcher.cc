@@ -1220,6 +1220,13 @@ void GpuTaskDispatcher::UnsafePark(Pending* r) {
   ++parked_count_;
 }
 
+// r->sig names the list r was parked in: a parked request's sig is never recomputed in place.
+// UnsafeCacheColumns reaches a parked request from two places only. UnsafeReindexParked takes every
+// request off its list before it numbers them anew. UnsafeDispatch re-caches a segment that may hold
+// parked requests (a retry), but only after UnsafeDrainQueue has brought the parked requests and the
+// arrivals to one stable registry_epoch_, and nothing inside a turn moves the epoch (no registration,
+// no expiry, and every alias its requests can create exists by then): there the call returns at
+// its first line. The owner that gives up (WaitForStartingNewTask) unparks under the lock, between turns.
 void GpuTaskDispatcher::UnsafeUnpark(Pending* r) {
   if (!r->parked) return;
   ParkedList& l = parked_[r->sig];
@@ -1244,17 +1251,25 @@ void GpuTaskDispatcher::UnsafeReindexParked() {
   parked_.clear();
   parked_count_ = 0;
   std::sort(all.begin(), all.end(), [](const Pending* a, const Pending* b) { return a->arrival < b->arrival; });
-  for (Pending* r : all) UnsafeCacheColumns(r);
-  for (Pending* r : all) UnsafeCacheColumns(r);  // (an alias created on the way invalidated earlier ones)
+  UnsafeCacheColumnsOf(all);
   for (Pending* r : all) UnsafePark(r);
   parked_epoch_ = registry_epoch_;
+}
+
+// Looks the requests up until a whole pass has created no alias: one created on the way moves
+// registry_epoch_ and with it the numbering of those looked up before it. An address becomes an
+// alias once, so a second pass creates none: at most two passes look anything up.
+void GpuTaskDispatcher::UnsafeCacheColumnsOf(const std::vector<Pending*>& requests) {
+  for (std::uint64_t epoch = ~registry_epoch_; epoch != registry_epoch_;) {
+    epoch = registry_epoch_;
+    for (Pending* r : requests) UnsafeCacheColumns(r);
+  }
 }
 
 void GpuTaskDispatcher::UnsafeDispatch(const std::vector<Pending*>& batch) {
   if (batch.empty()) return;
   const std::uint64_t t0 = NowNs(), dev0 = host_stats_.device_ns;
-  for (Pending* r : batch) UnsafeCacheColumns(r);
-  for (Pending* r : batch) UnsafeCacheColumns(r);  // (an alias created on the way invalidated earlier ones)
+  UnsafeCacheColumnsOf(batch);  // (nothing to do for a segment of UnsafeDrainQueue: cached at a stable epoch there)
   RequestSpan span;
   span.pending = batch.data();
   span.n = batch.size();
@@ -1316,15 +1331,35 @@ void GpuTaskDispatcher::UnsafeDrainQueue() {
   // Arrival order: the parked requests (where the waiters were woken since they were last placed:
   // in the reference a waiter sleeps until notify_all or its deadline, and a heartbeat wakes
   // nobody, task_dispatcher.cc:116-118,187,190-220), then what has just come in.
-  for (Pending* r : arrivals) UnsafeCacheColumns(r);
-  for (Pending* r : arrivals) UnsafeCacheColumns(r);  // (an alias created on the way invalidated earlier ones)
-  if (parked_count_ != 0 && parked_epoch_ != registry_epoch_) UnsafeReindexParked();
+  // One numbering of the triples for the whole turn: the parked requests are renumbered FIRST (if the
+  // tables moved since they were), then the arrivals are looked up, and both again until nothing
+  // moves registry_epoch_ any more. Looking a request up can create a requestor alias (RequestorId),
+  // which clears sig_ids_: a sig handed out before that belongs to another numbering — it would
+  // index sig_dead_ past its end, or name a triple that is not the request's own.
+  bool alias_while_arrivals = false;
+  for (;;) {
+    const std::uint64_t epoch = registry_epoch_;
+    if (parked_count_ != 0 && parked_epoch_ != registry_epoch_) {
+      UnsafeReindexParked();
+      if (registry_epoch_ != epoch && !arrivals.empty()) alias_while_arrivals = true;
+    }
+    UnsafeCacheColumnsOf(arrivals);
+    if (registry_epoch_ == epoch) break;
+  }
+  if (alias_while_arrivals) ++host_stats_.alias_renumbered_turns;
   if (parked_count_ == 0) parked_epoch_ = registry_epoch_;
   for (Pending* r : arrivals) r->arrival = next_arrival_++;
   const bool retry = parked_count_ != 0 && retried_epoch_ != wake_epoch_;
   retried_epoch_ = wake_epoch_;
   if (!retry && arrivals.empty()) return;
+  // (sized only now, for the numbering that stands; and never indexed blindly — UnsafeDispatch
+  // looks requests up again and may hand out numbers this table has not seen)
   sig_dead_.assign(sig_ids_.size() + 1, 0);
+  auto is_dead = [&](const Pending* r) { return r->sig < sig_dead_.size() && sig_dead_[r->sig] != 0; };
+  auto mark_dead = [&](const Pending* r) {
+    if (r->sig >= sig_dead_.size()) sig_dead_.resize((std::size_t)r->sig + 1, 0);
+    sig_dead_[r->sig] = 1;
+  };
   std::vector<Pending*> served, seg;
   // Segments: a handful of requests first (one freed slot serves one waiter: 8 requests cost the
   // resident tick 13 us, 64 cost 40), four times as many while whole segments are granted.
@@ -1351,7 +1386,7 @@ void GpuTaskDispatcher::UnsafeDrainQueue() {
         UnsafeUnpark(r);
         served.push_back(r);
       } else {  // Timeout: so will every later request of its triple in this turn
-        sig_dead_[r->sig] = 1;
+        mark_dead(r);
         any_dead = true;
         if (!r->parked && !expire_now(r)) UnsafePark(r);
       }
@@ -1374,7 +1409,7 @@ void GpuTaskDispatcher::UnsafeDrainQueue() {
     while (!heads.empty()) {
       Pending* r = heads.top().second;
       heads.pop();
-      if (sig_dead_[r->sig]) {
+      if (is_dead(r)) {
         // (the rest of this triple's list stays where it is; walked only for the test log)
         if (oplog_on_)
           for (Pending* q = r; q; q = q->park_next) known_timeout(q);
@@ -1392,7 +1427,7 @@ void GpuTaskDispatcher::UnsafeDrainQueue() {
     // empty here, so nothing is pending behind it)
   }
   for (Pending* r : arrivals) {
-    if (sig_dead_[r->sig]) {
+    if (is_dead(r)) {
       known_timeout(r);
       if (!expire_now(r)) UnsafePark(r);
       continue;

@@ -248,6 +248,9 @@ class GpuTaskDispatcher {
     // how long it held the lock, and the longest any of them did.
     std::uint64_t timer_ticks = 0, timer_lease_entries_seen = 0, timer_last_ns = 0, timer_max_ns = 0;
     std::uint64_t lease_wheel_entries = 0;
+    // Turns of UnsafeDrainQueue in which renumbering the parked requests created a requestor alias
+    // while new requests were waiting to be served (tests: the situation was met).
+    std::uint64_t alias_renumbered_turns = 0;
   };
   HostStats host_stats() const;
 
@@ -574,6 +577,7 @@ class GpuTaskDispatcher {
   void UnsafeUnpark(Pending* r);
   void UnsafeReindexParked();
   void UnsafeCacheColumns(Pending* r);
+  void UnsafeCacheColumnsOf(const std::vector<Pending*>& requests);  // ... until no alias is created
   void UnsafeDrainQueue();
   void TimerLoop();
   std::string TaskRequestorIp(const Task& t) const;

@@ -295,4 +295,9 @@ const char* ydc_td_oplog_take(ydc_td* td) {
   return td->oplog.c_str();
 }
 
+int64_t ydc_td_alias_renumbered_turns(ydc_td* td) {
+  if (!td) return YDC_ERR_INVALID_ARGUMENT;
+  return (int64_t)td->impl->host_stats().alias_renumbered_turns;
+}
+
 }  // extern "C"

@@ -21,6 +21,7 @@ TD_SYMBOLS = (
     "ydc_td_free_tasks", "ydc_td_host_stats", "ydc_td_running_tasks_acquire", "ydc_td_running_tasks_release",
     "ydc_td_notify_servant_running_tasks", "ydc_td_get_running_tasks",
     "ydc_td_on_expiration_timer", "ydc_td_dump_internals", "ydc_td_oplog_enable", "ydc_td_oplog_take",
+    "ydc_td_alias_renumbered_turns",
 )
 
 
@@ -87,6 +88,8 @@ def type_td_functions(L):
         L.ydc_td_oplog_enable.argtypes = [C.c_void_p, C.c_int]
         L.ydc_td_oplog_take.argtypes = [C.c_void_p]
         L.ydc_td_oplog_take.restype = C.c_char_p
+        L.ydc_td_alias_renumbered_turns.argtypes = [C.c_void_p]
+        L.ydc_td_alias_renumbered_turns.restype = C.c_int64
         L._ydc_td_typed = True
     return L
 
