@@ -433,6 +433,23 @@ def test_remove_servants_by_the_caller_compacts_the_column():
     x.close()
 
 
+def alias_checked(es, batch, out, aliased):
+    """The placement `out` of `batch`, after asserting that it EQUALS the reference's on address
+    strings (tests/alias_reference.py) for the registry `es` holds at this moment. aliased: requestor
+    id -> the rows that answer to it through the alias list. A row's location is "<alias>:<ip>:<row>"
+    (it answers to "<alias>" and to nothing shorter than its whole host part), or "<ip>:<row>"."""
+    from tests import alias_reference as AR
+    sv = es.registry_snapshot()
+    alias_of = {s: ip for ip, rows in aliased.items() for s in rows}
+    locations = [("%d:" % alias_of[s] if s in alias_of else "") + "%d:%d" % (int(sv["ip"][s]), s)
+                 for s in range(len(sv["ip"]))]
+    assert not set(int(x) for x in sv["ip"]) & set(aliased), "an alias id that is also a primary id"
+    assert not {int(sv["ip"][s]) for s in alias_of} & {int(r) for r in batch["requestor_ip"]}  # (see the locations)
+    want = AR.dispatch(locations, sv, [str(int(r)) for r in batch["requestor_ip"]], batch)[0]
+    assert np.array_equal(np.asarray(out, np.uint32), want), (out, want, aliased)
+    return out
+
+
 def test_host_aliases_of_survivors_outlive_a_removal_tick():
     """Requests from an aliased host count as the aliased servant's own (they are not placed there).
     The alias still does after a row in front of that servant was erased inside a tick. Every tick
@@ -448,27 +465,32 @@ def test_host_aliases_of_survivors_outlive_a_removal_tick():
         ev = p.make_ev(p.ls, FAR, None, ask, dict(n=4, lease=[100] * 4, free=list(last)))
         ctx.stream_alive_stage(ev["upd_expires_at"])
         out, ids = lease.gpu_tick(ctx, p.ls, ev)[:2]
-        # (the model does not know the alias: it follows the device's placement)
+        # (the lease model does not know the alias; the placement it is handed is checked against
+        # the reference on address strings, on the registry as it is when the batch is placed)
         p.A.stage(ev["upd_expires_at"])
         held = set(p.ls.table.L)
-        r = p.ls.table.tick(p.ls.es.running, ev, lambda batch: out)
+        r = p.ls.table.tick(p.ls.es.running, ev, lambda batch: alias_checked(p.ls.es, batch, out, aliased))
         p.ls.commit(held, r["out"])
         assert np.array_equal(ids, r["task_id"]) and int((out < L.IDX_ENV_NOT_FOUND).sum()) == 4
         assert np.array_equal(ctx.get_running(), p.ls.es.running.astype(np.uint32))
         last[:] = ids.tolist()
         return out.tolist(), p.A.removed_last.tolist()
 
+    aliased = {}  # requestor id -> the rows that answer to it through the alias list
     out, _ = placed_on()
     target = max(out)  # where such requests go when nothing keeps them away
     assert target > 0, "the favourite is row 0: no row in front of it can be erased"
     ctx.set_host_aliases(np.array([alias_ip], np.uint32), np.array([target], np.uint32))
+    aliased[alias_ip] = {target}
     out, _ = placed_on()
     assert target not in out, "the alias does not keep its servant's own requests away"
     p.set_expiry(0, 0)
+    aliased[alias_ip] = {target - 1}  # (row 0 leaves inside the tick, before the batch is placed)
     out, removed = placed_on()
     assert removed == [0] and target - 1 not in out, "the alias did not follow its servant to row %d" % (target - 1)
     # (set again by the caller: without the entry the same requests do reach it)
     ctx.set_host_aliases(np.empty(0, np.uint32), np.empty(0, np.uint32))
+    aliased.clear()
     out, _ = placed_on()
     assert target - 1 in out
     p.x.close()

@@ -415,7 +415,9 @@ def test_host_aliases_and_wide_masks():
         got = [lease.gpu_tick(c, ls, ev) for c in run.ctxs]
         out, ids = got[0][:2]
         held = set(ls.table.L)
-        r = ls.table.tick(ls.es.running, ev, lambda batch: out)
+        # (the lease model does not know the alias; the placement it is handed must equal the
+        # reference's on address strings)
+        r = ls.table.tick(ls.es.running, ev, lambda batch: alive.alias_checked(ls.es, batch, out, aliased))
         ls.commit(held, r["out"])
         run.t += 1
         assert np.array_equal(ids, r["task_id"]) and int((out < L.IDX_ENV_NOT_FOUND).sum()) == 4
@@ -427,8 +429,10 @@ def test_host_aliases_and_wide_masks():
         last[:] = ids.tolist()
         return out.tolist()
 
+    aliased = {}
     target = max(placed_on())  # where such requests go when nothing keeps them away
     a.set_host_aliases(np.array([alias_ip], np.uint32), np.array([target], np.uint32))
+    aliased[alias_ip] = {target}
     run.aliases = ([alias_ip], [target])
     assert target not in placed_on(), "the alias does not keep its servant's own requests away"
     blob = run.fork()
