@@ -51,6 +51,7 @@ extern "C" {
 #define YDC_ERR_CAPACITY (-4)        /* more servants/tasks/slots than the context was created for */
 #define YDC_ERR_TOO_MANY_CLASSES (-5)/* more (env set, version) signatures than the entry point takes */
 #define YDC_ERR_NOT_CONVERGED (-6)   /* internal invariant broken (never expected) */
+#define YDC_ERR_NO_BASE (-7)         /* ydc_stream_delta: no base, or the chain of deltas has ended */
 
 /* Servant classes = distinct (env set, version) signatures among servants with max_tasks != 0.
  * Every entry point takes up to 65535. Up to 256 the lane-per-class kernel places the batch; above
@@ -1183,6 +1184,48 @@ int ydc_stream_depart_result(ydc_context* ctx, ydc_depart_count* out, uint32_t c
  *     (ydc_stream_alive_removed reports none), what the stream had learnt about its passes. */
 int ydc_stream_snapshot(ydc_context* ctx, void* out, size_t cap, size_t* out_bytes);
 int ydc_stream_restore(ydc_context* ctx, const void* blob, size_t bytes, const ydc_stream_caps* want);
+
+/* ---- delta snapshots: a standby that follows the primary tick by tick ---------------------
+ * For a leased, waiting-and-leased or rpc stream that is not in a group (a waiting-only stream has
+ * no lease table and a small full snapshot: YDC_ERR_INVALID_ARGUMENT, as for a plain stream, no
+ * stream, or a context in a group — from all four calls). The primary takes a base, then a delta
+ * every tick or every few ticks; the standby is restored from the base's bytes and applies every
+ * delta in order, without ticking. The format is DESIGN 3.3.18 (stream_delta_codec.h,
+ * yadcc_amd/snapshot.py): inserted, erased and updated leases as id-sorted lists, and whole the
+ * registry's light columns (version, num_processors, current_load, max_tasks, flags, running_tasks,
+ * the report ticks), W, E, and B when it changed. The device finds the lists itself.
+ *   - ydc_stream_delta_base: writes exactly the bytes ydc_stream_snapshot would write now (same
+ *     preconditions, same refusals, cap too small: YDC_ERR_CAPACITY with *out_bytes) and keeps, on
+ *     the device, the base image a later delta is taken against. Calling it again replaces the base.
+ *   - ydc_stream_delta: between ticks, preconditions as for a snapshot. Writes the delta from the
+ *     base state to the current one and makes the current state the new base. cap too small:
+ *     YDC_ERR_CAPACITY, *out_bytes the size needed, the base NOT advanced — the same call with a
+ *     larger buffer gives the bytes one call would have given. No base, or something a delta does
+ *     not carry has changed since the base: YDC_ERR_NO_BASE, nothing written, the base dropped; the
+ *     caller takes a new ydc_stream_delta_base (and restores the standby from it). That is the case
+ *     after any change of the registry's structure — n_servants, env_words, an environment mask, an
+ *     ip_id: so a structural heartbeat, a new servant, ydc_remove_servants, a tick in which a servant
+ *     expires —, of the host aliases, of a bound, max_book or the mode (an effective
+ *     ydc_stream_reserve, ydc_stream_book_begin, ydc_stream_alive_begin), and after the stream was
+ *     ended, restored or begun again. Detected when the call is made, from a stamp over the host's
+ *     copy of that structure; the paths themselves know nothing of a base.
+ *   - ydc_stream_delta_apply: ctx is a standby: restored from the base's bytes, every delta since
+ *     applied, never ticked. The whole blob is validated first (sizes, offsets, checksum, zero
+ *     padding, the id lists ascending, disjoint and in their ranges, live bits, servant indexes,
+ *     |L|, W's rows, E against alive_bound), then its base identity (lease_tick, next_id, |L|, |W|,
+ *     last_now, the structure stamp) is compared with ctx's, then a read-only pass over the table
+ *     checks that every erased and updated id is there and no inserted one is. Anything amiss:
+ *     YDC_ERR_INVALID_ARGUMENT, and ctx, its open stream included, is as it was. Afterwards ctx is
+ *     what the primary was when it took the delta: ydc_stream_snapshot gives the same bytes and
+ *     identical ticks give identical results. The table's buffers do not move: a step captured
+ *     before stays valid. Refused while inspection is on: like ydc_stream_restore, a delta carries
+ *     no inspection records, quota, withdrawal or departure settings; a standby that needs
+ *     inspection loads it at promotion with ydc_stream_inspect_load.
+ *   - ydc_stream_delta_stop: frees the base image (ydc_stream_end and ydc_destroy do so too). */
+int ydc_stream_delta_base(ydc_context* ctx, void* out, size_t cap, size_t* out_bytes);
+int ydc_stream_delta(ydc_context* ctx, void* out, size_t cap, size_t* out_bytes);
+int ydc_stream_delta_apply(ydc_context* ctx, const void* delta, size_t bytes);
+int ydc_stream_delta_stop(ydc_context* ctx);
 
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.

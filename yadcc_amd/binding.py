@@ -60,6 +60,7 @@ ABI_SYMBOLS = (
     "ydc_stream_quota_fair", "ydc_stream_quota_fair_result", "ydc_fair_level",
     "ydc_stream_depart_begin", "ydc_stream_depart_stage", "ydc_stream_depart_result",
     "ydc_stream_snapshot", "ydc_stream_restore",
+    "ydc_stream_delta_base", "ydc_stream_delta", "ydc_stream_delta_apply", "ydc_stream_delta_stop",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -295,6 +296,10 @@ def lib():
         L.ydc_stream_reserve.argtypes = [C.c_void_p, C.POINTER(StreamCaps)]
         L.ydc_stream_snapshot.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ydc_stream_restore.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(StreamCaps)]
+        L.ydc_stream_delta_base.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ydc_stream_delta.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ydc_stream_delta_apply.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        L.ydc_stream_delta_stop.argtypes = [C.c_void_p]
         L.ydc_stream_alive_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_alive_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_alive_removed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1092,6 +1097,37 @@ class Context:
         buf = C.create_string_buffer(need.value)
         self._check(lib().ydc_stream_snapshot(self._h, buf, C.c_size_t(need.value), C.byref(need)), "ydc_stream_snapshot")
         return buf.raw[:need.value]
+
+    def _sized_blob(self, fn, what):
+        """A call of ydc_stream_snapshot's shape: asked for the size, then for the bytes."""
+        need = C.c_size_t(0)
+        rc = fn(self._h, None, C.c_size_t(0), C.byref(need))
+        if rc != -4:  # (YDC_ERR_CAPACITY with the size needed is the expected answer)
+            self._check(rc or -1, what)
+        buf = C.create_string_buffer(need.value)
+        self._check(fn(self._h, buf, C.c_size_t(need.value), C.byref(need)), what)
+        return buf.raw[:need.value]
+
+    def stream_delta_base(self):
+        """ydc_stream_snapshot's bytes, and the base a later stream_delta is taken against is kept on the
+        device (ydc_stream_delta_base)."""
+        return self._sized_blob(lib().ydc_stream_delta_base, "ydc_stream_delta_base")
+
+    def stream_delta(self):
+        """The delta blob from the base state to the current one, which becomes the new base
+        (ydc_stream_delta; the format: yadcc_amd/snapshot.py parse_delta). YdcError "no delta base" when
+        there is no base or the chain has ended: take a new stream_delta_base."""
+        return self._sized_blob(lib().ydc_stream_delta, "ydc_stream_delta")
+
+    def stream_delta_apply(self, delta):
+        """Applies a delta to this standby: restored from the base's bytes, every delta since applied, never
+        ticked (ydc_stream_delta_apply). A refused delta leaves the context as it was."""
+        delta = bytes(delta)
+        self._check(lib().ydc_stream_delta_apply(self._h, delta, C.c_size_t(len(delta))), "ydc_stream_delta_apply")
+
+    def stream_delta_stop(self):
+        """Frees the base image (ydc_stream_delta_stop)."""
+        self._check(lib().ydc_stream_delta_stop(self._h), "ydc_stream_delta_stop")
 
     def stream_restore(self, blob, **want):
         """Makes this context what the snapshotted one was (ydc_stream_restore): registry, running_tasks,

@@ -43,6 +43,8 @@
 #include "stream_outlook.h"
 #include "requestor_index.h"
 #include "admit_clip.h"
+#include "stream_delta.h"
+#include "stream_delta_codec.h"
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
 #include "stream_depart.h"
@@ -643,6 +645,25 @@ struct ydc_context {
       DevBuf<RequestorLoad> res;  // ... and their rows
       DevBuf<uint8_t> rows;       // get: the fold's state and look-back words | its rows
     } requestor;
+    // ydc_stream_delta_base / ydc_stream_delta (stream_delta.h): the base a later delta is taken against.
+    // On the device the packed image of L (two buffers: a delta scans into the other one and they
+    // change roles when it succeeds), the lists' scratch and a copy of B's columns; on the host the
+    // base's identity and the structure stamp. !on: no base. It lives and dies with this record, so
+    // whatever replaces the stream (end, a begin call, restore, an effective ydc_stream_reserve or
+    // *_begin of a capability) ends the chain. `apply`: ydc_stream_delta_apply's lists on the device.
+    struct DeltaBase {
+      bool on = false;
+      DevBuf<uint8_t> img[2];  // id | expires_at | servant | state, `cap` records each
+      uint32_t cur = 0, cap = 0, n = 0;
+      DevBuf<uint8_t> lists;   // inserted (24 B) | erased (8 B) | updated (20 B), `cap` records each | DeltaCounts
+      DevBuf<uint8_t> book;    // grant | stid | dkey | servant, max_book entries each
+      uint32_t n_book = 0;
+      unsigned long long next_id = 0;
+      int64_t last_now = INT64_MIN;
+      uint32_t lease_tick = 0, n_waiting = 0;
+      uint64_t stamp = 0;
+      DevBuf<uint8_t> apply;
+    } delta;
   } stream_mode;
   // ydc_stream_snapshot: the packed columns of L with their count on the device, and the page-locked
   // block they cross the bus into. Kept for the next snapshot (a standby is fed periodically, and
@@ -1203,6 +1224,7 @@ const char* ydc_strerror(int code) {
     case YDC_ERR_CAPACITY: return "capacity of the context exceeded";
     case YDC_ERR_TOO_MANY_CLASSES: return "too many servant classes";
     case YDC_ERR_NOT_CONVERGED: return "chunk states did not converge";
+    case YDC_ERR_NO_BASE: return "no delta base (take a new ydc_stream_delta_base)";
     default: return "unknown error";
   }
 }
@@ -7691,6 +7713,423 @@ int ydc_stream_restore(ydc_context* c, const void* blob, size_t bytes, const ydc
     return rc;
   }
   std::swap(c->stream_mode, fresh);  // (stale: the next tick captures its step)
+  return YDC_OK;
+}
+
+}  // extern "C"
+
+// ---- delta snapshots (stream_delta.h, stream_delta_codec.h) ----
+namespace {
+
+// A packed image of `cap` records in one buffer, the four columns behind each other.
+LeasePacked packed_at(uint8_t* d, size_t cap) {
+  return LeasePacked{(unsigned long long*)d, (int64_t*)(d + cap * 8), (uint32_t*)(d + cap * 16), (uint32_t*)(d + cap * 20),
+                     (uint32_t)cap};
+}
+
+// The lists' scratch of the base: inserted | erased | updated | the counters.
+struct DeltaLists {
+  LeasePacked ins;
+  unsigned long long* era;
+  LeaseUpdates upd;
+  DeltaCounts* cnt;
+};
+DeltaLists delta_lists(uint8_t* d, size_t cap) {
+  uint8_t* u = d + cap * 32;
+  return DeltaLists{packed_at(d, cap), (unsigned long long*)(d + cap * 24),
+                    LeaseUpdates{(unsigned long long*)u, (int64_t*)(u + cap * 8), (uint32_t*)(u + cap * 16), (uint32_t)cap},
+                    (DeltaCounts*)(d + cap * 52)};
+}
+
+// B's columns in the base's copy (max_book entries each, b_cols' order).
+BookCols delta_book_at(uint8_t* d, size_t max_book) {
+  return BookCols{(uint32_t*)(d + max_book * 24), (unsigned long long*)d, (unsigned long long*)(d + max_book * 8),
+                  (unsigned long long*)(d + max_book * 16)};
+}
+
+// The structure stamp of the context as it is now (h: snap_describe's).
+uint64_t delta_stamp(const ydc_context* c, const snap::Header& h) {
+  return delta::stamp(h.mode, h.env_words, h.n_servants, h.n_alias, h.caps, h.max_book, c->reg.env.data(), c->reg.ip.data(),
+                      c->reg.alias_ip.data(), c->reg.alias_servant.data());
+}
+
+// What all four calls refuse.
+int delta_mode_check(ydc_context* c, const char* what) {
+  const auto& sm = c->stream_mode;
+  if (!sm.active) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: no stream is open", what);
+  if (!sm.leased()) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the stream keeps no lease table", what);
+  if (c->group.n_ranks) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the context is in a group", what);
+  return YDC_OK;
+}
+
+// ... and what a snapshot refuses besides; then the stream is brought to rest as a snapshot does.
+int delta_settle(ydc_context* c, const char* what) {
+  auto& sm = c->stream_mode;
+  if (c->pend_count) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: pipelined batches are outstanding", what);
+  if (sm.book.staged.on || sm.alive.staged || sm.withdraw.host.staged || sm.depart.host.staged)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: a staging for the next tick is pending", what);
+  HIP_TRY(c, hipSetDevice(c->device));
+  resident_stop(c);  // (the registry leaves the resident kernel's registers)
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (sm.alive.on)
+    if (int rc = alive_fit(c)) return rc;
+  return YDC_OK;
+}
+
+// B as it is now into the base's copy.
+int delta_keep_book(ydc_context* c) {
+  auto& sm = c->stream_mode;
+  auto& b = sm.delta;
+  b.n_book = sm.max_book ? sm.book.n : 0;
+  if (!b.n_book) return YDC_OK;
+  HIP_TRY(c, b.book.reserve((size_t)sm.max_book * 28));
+  const BookCols to = delta_book_at(b.book.p, sm.max_book);
+  const StateCol dst[kBCols] = {{to.grant, 8}, {to.stid, 8}, {to.dkey, 8}, {to.servant, 4}};
+  const auto from = b_cols(sm);
+  for (size_t k = 0; k < kBCols; ++k)
+    HIP_TRY(c, hipMemcpyAsync(dst[k].p, from[k].p, b.n_book * from[k].width, hipMemcpyDeviceToDevice, c->stream));
+  return YDC_OK;
+}
+
+// The base taken from the snapshot just written (h: its header): L's packed columns as k_lease_pack left
+// them in d_snap, device to device.
+int delta_take_base(ydc_context* c, const snap::Header& h) {
+  auto& sm = c->stream_mode;
+  auto& b = sm.delta;
+  b.on = false;
+  const size_t cap = sm.caps.max_leases;
+  for (auto& im : b.img) HIP_TRY(c, im.reserve(cap * 24));
+  HIP_TRY(c, b.lists.reserve(cap * 52 + sizeof(DeltaCounts)));
+  b.cap = (uint32_t)cap;
+  b.cur = 0;
+  const uint32_t nl = h.n_leases;
+  if (nl) {
+    const LeasePacked from = packed_at(c->d_snap.p, std::max(nl, 1u)), to = packed_at(b.img[0].p, cap);
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(to.id, from.id, (size_t)nl * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(to.expires, from.expires, (size_t)nl * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(to.servant, from.servant, (size_t)nl * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(to.state, from.state, (size_t)nl * 4, hipMemcpyDeviceToDevice, st));
+  }
+  if (int rc = delta_keep_book(c)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  b.n = nl;
+  b.next_id = h.next_id;
+  b.last_now = h.last_now;
+  b.lease_tick = h.lease_tick;
+  b.n_waiting = h.n_waiting;
+  b.stamp = delta_stamp(c, h);
+  b.on = true;
+  return YDC_OK;
+}
+
+// One column of a list: where it lies on the device, where it goes in the blob, its width.
+struct ListCol {
+  const void* dev;
+  uint8_t* to;
+  size_t width;
+};
+
+int stream_delta(ydc_context* c, void* out, size_t cap, size_t* out_bytes) {
+  auto& sm = c->stream_mode;
+  auto& b = sm.delta;
+  snap::Header sh;
+  snap_describe(c, &sh);
+  if (delta_stamp(c, sh) != b.stamp || sm.caps.max_leases != b.cap) {
+    b = ydc_context::Stream::DeltaBase{};
+    return fail(c, YDC_ERR_NO_BASE, "ydc_stream_delta: the registry's structure, the aliases, a bound or the mode changed "
+                "since the base");
+  }
+  hipStream_t st = c->stream;
+  const uint32_t n = sh.n_servants;
+  const LeasePacked old_img = packed_at(b.img[b.cur].p, b.cap), new_img = packed_at(b.img[b.cur ^ 1].p, b.cap);
+  const DeltaLists ls = delta_lists(b.lists.p, b.cap);
+  HIP_TRY(c, hipMemsetAsync(ls.cnt, 0, sizeof(DeltaCounts), st));
+  YDC_LAUNCH(c, "k_lease_delta_scan", k_lease_delta_scan, dim3(ceil_div(sm.lt.mask + 1, kLeaseTile)), dim3(256), 0, st,
+             sm.lt, new_img, ls.ins, b.next_id, ls.cnt);
+  HIP_TRY(c, hipGetLastError());
+  YDC_LAUNCH(c, "k_lease_delta_diff", k_lease_delta_diff, dim3(ceil_div(std::max(b.n, 1u), 256)), dim3(256), 0, st, sm.lt,
+             sm.ls, old_img, b.n, ls.era, b.cap, ls.upd, ls.cnt);
+  HIP_TRY(c, hipGetLastError());
+  const bool book_compared = sm.max_book && sm.book.n == b.n_book && b.n_book;
+  if (book_compared) {
+    YDC_LAUNCH(c, "k_book_delta_same", k_book_delta_same, dim3(ceil_div(b.n_book, 256)), dim3(256), 0, st, sm.book.bk,
+               delta_book_at(b.book.p, sm.max_book), b.n_book, ls.cnt);
+    HIP_TRY(c, hipGetLastError());
+  }
+  DeltaCounts cnt{};
+  LeaseState lst{};
+  uint32_t n_w = 0;
+  HIP_TRY(c, hipMemcpyAsync(&cnt, ls.cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&lst, sm.ls, sizeof lst, hipMemcpyDeviceToHost, st));
+  if (sm.waiting()) HIP_TRY(c, hipMemcpyAsync(&n_w, &sm.ws->count, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (cnt.n_img != sh.n_leases || lst.n_leases != sh.n_leases)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: %u live slots, |L| %u on the device, %u on the host", cnt.n_img,
+                lst.n_leases, sh.n_leases);
+  if (n_w != sh.n_waiting)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "waiting queue of %u on the device, %u on the host", n_w, sh.n_waiting);
+  if (cnt.servant_changed)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "ydc_stream_delta: %u leases changed their servant under an equal structure stamp",
+                cnt.servant_changed);
+  if (cnt.n_era > b.n || cnt.n_upd > b.n - cnt.n_era || cnt.n_ins > cnt.n_img ||
+      (uint64_t)b.n + cnt.n_ins - cnt.n_era != cnt.n_img || lst.next_id < b.next_id)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "ydc_stream_delta: %u inserted, %u erased, %u updated of %u do not make %u", cnt.n_ins,
+                cnt.n_era, cnt.n_upd, b.n, cnt.n_img);
+  // The header, and with it the size.
+  snap::Header base_h{};
+  base_h.next_id = b.next_id, base_h.last_now = b.last_now, base_h.lease_tick = b.lease_tick;
+  base_h.n_leases = b.n, base_h.n_waiting = b.n_waiting;
+  sh.next_id = lst.next_id;
+  delta::Header h = delta::describe(base_h, sh, b.stamp);
+  h.n_ins = cnt.n_ins, h.n_era = cnt.n_era, h.n_upd = cnt.n_upd;
+  h.book_present = sm.max_book && (!book_compared ? sm.book.n != b.n_book : cnt.book_differs != 0);
+  delta::layout(&h);
+  *out_bytes = (size_t)h.total_bytes;
+  if (cap < h.total_bytes)  // (the new image is simply not taken: the next call scans again)
+    return fail(c, YDC_ERR_CAPACITY, "a delta of %llu bytes > cap %zu", (unsigned long long)h.total_bytes, cap);
+  if (!out) return YDC_ERR_INVALID_ARGUMENT;
+  uint8_t* o = (uint8_t*)out;
+  std::memset(o, 0, (size_t)h.total_bytes);
+  delta::View v{};
+  v.h = h;
+  delta::place(&v, o);
+  auto at = [](const uint8_t* col) { return const_cast<uint8_t*>(col); };
+  // The three lists: brought over as they lie, sorted by id here (they are small).
+  auto sorted = [&](uint32_t k, const unsigned long long* d_id, std::initializer_list<ListCol> cols) -> int {
+    if (!k) return YDC_OK;
+    std::vector<unsigned long long> id(k);
+    HIP_TRY(c, hipMemcpy(id.data(), d_id, (size_t)k * 8, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> order(k);
+    for (uint32_t i = 0; i < k; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return id[x] < id[y]; });
+    std::vector<uint8_t> col;
+    for (const ListCol& lc : cols) {
+      col.resize((size_t)k * lc.width);
+      HIP_TRY(c, hipMemcpy(col.data(), lc.dev, col.size(), hipMemcpyDeviceToHost));
+      for (uint32_t i = 0; i < k; ++i) std::memcpy(lc.to + (size_t)i * lc.width, &col[(size_t)order[i] * lc.width], lc.width);
+    }
+    return YDC_OK;
+  };
+  if (int rc = sorted(h.n_ins, ls.ins.id, {{ls.ins.id, at(v.ins_id), 8}, {ls.ins.expires, at(v.ins_exp), 8},
+                                           {ls.ins.servant, at(v.ins_srv), 4}, {ls.ins.state, at(v.ins_state), 4}}))
+    return rc;
+  if (int rc = sorted(h.n_era, ls.era, {{ls.era, at(v.era_id), 8}})) return rc;
+  if (int rc = sorted(h.n_upd, ls.upd.id, {{ls.upd.id, at(v.upd_id), 8}, {ls.upd.expires, at(v.upd_exp), 8},
+                                           {ls.upd.state, at(v.upd_state), 4}}))
+    return rc;
+  for (uint32_t i = 0; i < h.n_ins; ++i)
+    if (snap::get<uint32_t>(v.ins_srv, i) >= n)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "an inserted lease names servant %u of %u", snap::get<uint32_t>(v.ins_srv, i), n);
+  // The registry's light columns (the device's are the truth: stream_snapshot), W, E and B, whole.
+  if (n) {
+    const uint32_t* reg[delta::kRegCols] = {c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p,
+                                           c->d_flags.p,   c->d_running.p, nullptr};
+    for (int k = 0; k + 1 < delta::kRegCols; ++k)
+      HIP_TRY(c, hipMemcpyAsync(at(v.reg[k]), reg[k], (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    const uint32_t have = (uint32_t)std::min<size_t>(n, sm.d_rep_tick.cap);
+    if (have) HIP_TRY(c, hipMemcpyAsync(at(v.reg[6]), sm.d_rep_tick.p, (size_t)have * 4, hipMemcpyDeviceToHost, st));
+  }
+  if (sm.waiting() && n_w) {
+    const auto from = w_cols(sm);
+    const uint8_t* to[kWCols] = {v.w_deadline, v.w_tag, v.w_for, v.w_env, v.w_minv, v.w_ip, v.w_nimm, v.w_npre};
+    for (size_t k = 0; k < kWCols; ++k)
+      if (from[k].p) HIP_TRY(c, hipMemcpyAsync(at(to[k]), from[k].p, n_w * from[k].width, hipMemcpyDeviceToHost, st));
+  }
+  if (sm.alive.on && n) HIP_TRY(c, hipMemcpyAsync(at(v.e_exp), sm.alive.col.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  if (h.book_present && h.n_book) {
+    const auto from = b_cols(sm);
+    const uint8_t* to[kBCols] = {v.b_grant, v.b_stid, v.b_dkey, v.b_srv};
+    for (size_t k = 0; k < kBCols; ++k)
+      HIP_TRY(c, hipMemcpyAsync(at(to[k]), from[k].p, h.n_book * from[k].width, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  for (uint32_t s = 0; sm.alive.on && s < n; ++s) h.alive_bound = std::min(h.alive_bound, snap::get<int64_t>(v.e_exp, s));
+  delta::seal(o, &h);
+  // The current state is the new base.
+  if (h.book_present)
+    if (int rc = delta_keep_book(c)) {
+      b = ydc_context::Stream::DeltaBase{};
+      return rc;
+    }
+  HIP_TRY(c, hipStreamSynchronize(st));
+  b.cur ^= 1;
+  b.n = cnt.n_img;
+  b.next_id = lst.next_id;
+  b.last_now = sh.last_now;
+  b.lease_tick = sh.lease_tick;
+  b.n_waiting = sh.n_waiting;
+  return YDC_OK;
+}
+
+int stream_delta_apply(ydc_context* c, const delta::View& v) {
+  auto& sm = c->stream_mode;
+  const delta::Header& h = v.h;
+  snap::Header sh;
+  snap_describe(c, &sh);
+  const uint32_t n = sh.n_servants;
+  // The delta's base is this context's state.
+  if (h.mode != sh.mode || h.env_words != sh.env_words || h.n_servants != n || h.max_leases != sm.caps.max_leases ||
+      h.max_waiting != sm.caps.max_waiting || h.max_rows != sm.caps.max_rows || h.max_book != sm.max_book ||
+      h.stamp != delta_stamp(c, sh))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: the delta's structure stamp is not this context's");
+  LeaseState lst{};
+  HIP_TRY(c, hipMemcpy(&lst, sm.ls, sizeof lst, hipMemcpyDeviceToHost));
+  if (h.base_lease_tick != sm.lease_tick || h.base_next_id != lst.next_id || h.base_n_leases != sm.n_leases ||
+      lst.n_leases != sm.n_leases || h.base_n_waiting != sh.n_waiting || h.base_last_now != sm.last_now)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: the delta's base (tick %u, next_id %llu, |L| %u, |W| %u) "
+                "is not this context's state (tick %u, next_id %llu, |L| %u, |W| %u)", h.base_lease_tick,
+                (unsigned long long)h.base_next_id, h.base_n_leases, h.base_n_waiting, sm.lease_tick, lst.next_id,
+                sm.n_leases, sh.n_waiting);
+  if (!h.book_present && sm.max_book && h.n_book != sm.book.n)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: |B| %u without B, %u here", h.n_book, sm.book.n);
+  hipStream_t st = c->stream;
+  // The lists on the device (aligned copies: the block's base may be any address), and the read-only
+  // pass: every erased and updated id is in the table, no inserted one is.
+  const size_t ni = h.n_ins, ne = h.n_era, nu = h.n_upd;
+  const size_t words = ni * 3 + ne + nu * 3 + 2;  // (8-byte units; the counters behind the lists)
+  std::vector<uint64_t> stage(words, 0);
+  uint8_t* s8 = (uint8_t*)stage.data();
+  const size_t o_ins = 0, o_era = ni * 24, o_upd = o_era + ne * 8, o_cnt = (o_upd + nu * 20 + 7) & ~(size_t)7;
+  std::memcpy(s8 + o_ins, v.ins_id, ni * 8);
+  std::memcpy(s8 + o_ins + ni * 8, v.ins_exp, ni * 8);
+  std::memcpy(s8 + o_ins + ni * 16, v.ins_srv, ni * 4);
+  std::memcpy(s8 + o_ins + ni * 20, v.ins_state, ni * 4);
+  std::memcpy(s8 + o_era, v.era_id, ne * 8);
+  std::memcpy(s8 + o_upd, v.upd_id, nu * 8);
+  std::memcpy(s8 + o_upd + nu * 8, v.upd_exp, nu * 8);
+  std::memcpy(s8 + o_upd + nu * 16, v.upd_state, nu * 4);
+  auto& buf = sm.delta.apply;
+  HIP_TRY(c, buf.reserve(o_cnt + sizeof(DeltaCounts)));
+  if (o_cnt) HIP_TRY(c, hipMemcpy(buf.p, s8, o_cnt, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemset(buf.p + o_cnt, 0, sizeof(DeltaCounts)));
+  const LeasePacked ins = packed_at(buf.p + o_ins, ni);
+  const unsigned long long* era = (const unsigned long long*)(buf.p + o_era);
+  uint8_t* u = buf.p + o_upd;
+  const LeaseUpdates upd{(unsigned long long*)u, (int64_t*)(u + nu * 8), (uint32_t*)(u + nu * 16), (uint32_t)nu};
+  DeltaCounts* d_cnt = (DeltaCounts*)(buf.p + o_cnt);
+  YDC_LAUNCH(c, "k_lease_delta_check", k_lease_delta_check, dim3(ceil_div((uint32_t)std::max<size_t>(ne + nu + ni, 1), 256)),
+             dim3(256), 0, st, sm.lt, sm.ls, era, (uint32_t)ne, upd.id, (uint32_t)nu, ins.id, (uint32_t)ni, d_cnt);
+  HIP_TRY(c, hipGetLastError());
+  DeltaCounts cnt{};
+  HIP_TRY(c, hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (cnt.found_old != ne + nu || cnt.found_new)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: %u of %zu erased and updated ids are leases here, and %u "
+                "of the inserted ones", cnt.found_old, ne + nu, cnt.found_new);
+  if (sm.d_rep_tick.cap < n) {  // (never after a restore, which sizes it by the registry; the step holds its address)
+    DevBuf<uint32_t> bigger;
+    HIP_TRY(c, bigger.reserve((size_t)n + 1024));
+    sm.d_rep_tick = std::move(bigger);
+    sm.stale = true;
+  }
+  // From here on the context is written. L first.
+  if (ne + nu) {
+    YDC_LAUNCH(c, "k_lease_delta_apply_old", k_lease_delta_apply_old, dim3(ceil_div((uint32_t)(ne + nu), 256)), dim3(256), 0,
+               st, sm.lt, sm.ls, era, (uint32_t)ne, upd, (uint32_t)nu);
+    HIP_TRY(c, hipGetLastError());
+  }
+  YDC_LAUNCH(c, "k_lease_delta_apply_new", k_lease_delta_apply_new, dim3(ceil_div((uint32_t)std::max<size_t>(ni, 1), 256)),
+             dim3(256), 0, st, sm.lt, sm.ls, ins, (uint32_t)ni, (unsigned long long)h.next_id, h.n_leases);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(st));
+  // The registry's light columns, on the device and in the host's mirror. Rows whose version or
+  // capacity bound moved (a structural turn the stamp does not cover) have the derived tables rebuilt.
+  bool structural = false;
+  if (n) {
+    uint32_t* dev[delta::kRegCols] = {c->d_version.p, c->d_nproc.p, c->d_load.p, c->d_max_tasks.p,
+                                     c->d_flags.p,   c->d_running.p, sm.d_rep_tick.p};
+    for (int k = 0; k < delta::kRegCols; ++k) HIP_TRY(c, hipMemcpy(dev[k], v.reg[k], (size_t)n * 4, hipMemcpyHostToDevice));
+    std::vector<uint32_t> version(n), nproc(n), maxt(n);
+    std::memcpy(version.data(), v.reg[0], (size_t)n * 4);
+    std::memcpy(nproc.data(), v.reg[1], (size_t)n * 4);
+    std::memcpy(maxt.data(), v.reg[3], (size_t)n * 4);
+    auto& r = c->reg;
+    for (uint32_t s = 0; s < n && !structural; ++s)
+      structural = version[s] != r.version[s] || (maxt[s] == 0) != (r.max_tasks[s] == 0) ||
+                   std::min(maxt[s], nproc[s]) != std::min(r.max_tasks[s], r.nproc[s]);
+    r.version = std::move(version), r.nproc = std::move(nproc), r.max_tasks = std::move(maxt);
+    std::memcpy(r.load.data(), v.reg[2], (size_t)n * 4);
+    std::memcpy(r.flags.data(), v.reg[4], (size_t)n * 4);
+  }
+  // W, E and B: plain copies (pageable and unaligned sources: synchronous ones).
+  if (sm.waiting()) {
+    const uint8_t* from[kWCols] = {v.w_deadline, v.w_tag, v.w_for, v.w_env, v.w_minv, v.w_ip, v.w_nimm, v.w_npre};
+    const auto to = w_cols(sm);
+    for (size_t k = 0; h.n_waiting && k < kWCols; ++k)
+      if (to[k].p) HIP_TRY(c, hipMemcpy(to[k].p, from[k], h.n_waiting * to[k].width, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(&sm.ws->count, &h.n_waiting, 4, hipMemcpyHostToDevice));
+    sm.n_waiting = h.n_waiting;
+    sm.n_wait_rows = h.n_wait_rows;
+  }
+  if (sm.alive.on) {
+    if (n) HIP_TRY(c, hipMemcpy(sm.alive.col.p, v.e_exp, (size_t)n * 8, hipMemcpyHostToDevice));
+    sm.alive.n = n;
+    sm.alive.bound = h.alive_bound;
+  }
+  if (h.book_present) {
+    const uint8_t* from[kBCols] = {v.b_grant, v.b_stid, v.b_dkey, v.b_srv};
+    const auto to = b_cols(sm);
+    for (size_t k = 0; h.n_book && k < kBCols; ++k)
+      HIP_TRY(c, hipMemcpy(to[k].p, from[k], h.n_book * to[k].width, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(&sm.book.bks->n_entries, &h.n_book, 4, hipMemcpyHostToDevice));
+    sm.book.n = h.n_book;
+    sm.book.index.valid = false;
+  }
+  sm.n_leases = h.n_leases;
+  sm.last_now = h.last_now;
+  sm.lease_tick = h.lease_tick;
+  if (structural) return rebuild_tables(c);
+  return YDC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ydc_stream_delta_base(ydc_context* c, void* out, size_t cap, size_t* out_bytes) {
+  if (!c || !out_bytes) return YDC_ERR_INVALID_ARGUMENT;
+  if (int rc = delta_mode_check(c, "ydc_stream_delta_base")) return rc;
+  if (int rc = ydc_stream_snapshot(c, out, cap, out_bytes)) return rc;  // (refused: the base, if any, stays)
+  snap::Header h;
+  std::memcpy(&h, out, sizeof h);
+  if (int rc = delta_take_base(c, h)) {
+    c->stream_mode.delta = ydc_context::Stream::DeltaBase{};
+    return rc;
+  }
+  return YDC_OK;
+}
+
+int ydc_stream_delta(ydc_context* c, void* out, size_t cap, size_t* out_bytes) {
+  if (!c || !out_bytes) return YDC_ERR_INVALID_ARGUMENT;
+  if (int rc = delta_mode_check(c, "ydc_stream_delta")) return rc;
+  if (!c->stream_mode.delta.on) return fail(c, YDC_ERR_NO_BASE, "ydc_stream_delta: the stream has no base");
+  if (int rc = delta_settle(c, "ydc_stream_delta")) return rc;
+  return stream_delta(c, out, cap, out_bytes);
+}
+
+int ydc_stream_delta_apply(ydc_context* c, const void* blob, size_t bytes) {
+  if (!c || !blob) return YDC_ERR_INVALID_ARGUMENT;
+  if (int rc = delta_mode_check(c, "ydc_stream_delta_apply")) return rc;
+  // Everything that can be wrong with the bytes, before anything of the context is looked at.
+  delta::View v{};
+  if (const char* why = delta::validate(blob, bytes, &v)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: %s", why);
+  if (c->stream_mode.inspect.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: inspection is on (a delta carries no inspection "
+                "records: load them at promotion)");
+  if (int rc = delta_settle(c, "ydc_stream_delta_apply")) return rc;
+  return stream_delta_apply(c, v);
+}
+
+int ydc_stream_delta_stop(ydc_context* c) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (int rc = delta_mode_check(c, "ydc_stream_delta_stop")) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  auto& b = c->stream_mode.delta;
+  DevBuf<uint8_t> keep = std::move(b.apply);  // (a standby's scratch is no base)
+  b = ydc_context::Stream::DeltaBase{};
+  b.apply = std::move(keep);
   return YDC_OK;
 }
 

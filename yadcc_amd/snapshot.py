@@ -184,3 +184,202 @@ def build(d):
     blob = bytes(blob)
     parse(blob)
     return blob
+
+
+# ---- delta blobs (ydc_stream_delta / ydc_stream_delta_apply) ----
+# The second, independent implementation of yadcc_amd/csrc/stream_delta_codec.h: a delta takes a leased,
+# waiting-and-leased or rpc stream from the state of one full snapshot to that of a later one.
+DELTA_MAGIC = 0x3141544C44434459  # "YDCDLTA1"
+DELTA_VERSION = 1
+DELTA_HEADER = struct.Struct("<QIIQQ4I4IQQq4IQqq8I14Q")
+DELTA_HEADER_BYTES = 272
+assert DELTA_HEADER.size == DELTA_HEADER_BYTES
+DELTA_SECTIONS = ("inserted", "erased", "updated", "registry", "W", "E", "B")
+# The registry's columns a heartbeat or a tick changes without a structural turn, in the blob's order.
+DELTA_REGISTRY = ("version", "num_processors", "current_load", "servant_max_tasks", "flags", "running_tasks", "rep_tick")
+_W_COLS = (("w_deadline", "<i8"), ("w_tag", "<u8"), ("w_lease_for", "<i8"), ("w_env_id", "<u4"), ("w_min_version", "<u4"),
+           ("w_requestor_ip", "<u4"), ("w_n_immediate", "<u4"), ("w_n_prefetch", "<u4"))
+_B_COLS = (("b_grant_id", "<u8"), ("b_servant_task_id", "<u8"), ("b_digest_key", "<u8"), ("b_servant", "<u4"))
+
+
+def structure_stamp(d):
+    """The stamp over what a delta does not carry, from a parsed full snapshot: mode bits, counts, the ten
+    bounds and max_book (ten words, the fourth 0), every environment mask, then ip_id, alias ip and alias
+    servant behind each other, zero-padded to a whole word; checksum() of that."""
+    n, n_alias = len(d["version"]), len(d["alias_ip"])
+    env = np.ascontiguousarray(d["env_mask"], "<u8").reshape(-1)
+    env_words = int(d["env_words"])
+    caps = [int(d[k]) for k in CAPS]
+    head = [DELTA_MAGIC, mode_of(d) | env_words << 32, n | n_alias << 32, 0] + [
+        caps[i] | caps[i + 1] << 32 for i in range(0, 10, 2)] + [int(d["max_book"])]
+    tail = b"".join(np.ascontiguousarray(d[k], "<u4").tobytes() for k in ("ip_id", "alias_ip", "alias_servant"))
+    tail += bytes(_pad8(len(tail)) - len(tail))
+    return checksum(np.array(head, "<u8").tobytes() + env.tobytes() + tail)
+
+
+def _delta_sections(mode, n, n_ins, n_era, n_upd, n_w, n_b, book_present):
+    """[(name, [(column, dtype, count)], bytes)] in the blob's order."""
+    rpc = mode & 4
+    w = [(c, dt, n_w) for c, dt in _W_COLS if rpc or c not in ("w_n_immediate", "w_n_prefetch")] if mode & 1 else []
+    secs = (("inserted", [("ins_id", "<u8", n_ins), ("ins_expires_at", "<i8", n_ins), ("ins_servant", "<u4", n_ins),
+                          ("ins_state", "<u4", n_ins)]),
+            ("erased", [("era_id", "<u8", n_era)]),
+            ("updated", [("upd_id", "<u8", n_upd), ("upd_expires_at", "<i8", n_upd), ("upd_state", "<u4", n_upd)]),
+            ("registry", [(k, "<u4", n) for k in DELTA_REGISTRY]),
+            ("W", w),
+            ("E", [("e_expires_at", "<i8", n)] if mode & 16 else []),
+            ("B", [(c, dt, n_b) for c, dt in _B_COLS] if book_present else []))
+    return [(name, cols, _pad8(sum(np.dtype(dt).itemsize * k for _, dt, k in cols))) for name, cols in secs]
+
+
+_DELTA_FIELDS = ("mode", "env_words", "n_servants", "book_present", "max_leases", "max_waiting", "max_rows", "max_book",
+                 "stamp", "base_next_id", "base_last_now", "base_lease_tick", "base_n_leases", "base_n_waiting", "reserved",
+                 "next_id", "last_now", "alive_bound", "lease_tick", "n_leases", "n_waiting", "n_wait_rows", "n_book",
+                 "n_ins", "n_era", "n_upd")
+
+
+def parse_delta(blob):
+    """The delta as a dict: the header's fields under _DELTA_FIELDS' names and every carried column. Raises
+    FormatError for anything ydc_stream_delta_apply would refuse for its bytes alone."""
+    blob = bytes(blob)
+    _check(len(blob) >= DELTA_HEADER_BYTES, "shorter than a header")
+    f = DELTA_HEADER.unpack_from(blob)
+    magic, version, hbytes, total, csum = f[:5]
+    d = dict(zip(_DELTA_FIELDS, f[5:31]))
+    directory = f[31:45]
+    _check(magic == DELTA_MAGIC, "not a stream delta (magic)")
+    _check(version == DELTA_VERSION, "unknown format version")
+    _check(hbytes == DELTA_HEADER_BYTES, "header size")
+    _check(total == len(blob) and total % 8 == 0, "total bytes differ from the block's size")
+    mode, n = d["mode"], d["n_servants"]
+    _check(mode & ~31 == 0 and mode & 2, "mode bits")
+    _check(not (mode & 4) or mode & 1, "rpc mode without W")
+    _check(1 <= d["env_words"] <= 64, "env_words out of range")
+    _check(d["book_present"] <= 1 and d["reserved"] == 0, "a reserved field is set")
+    _check(not d["book_present"] or mode & 8, "B without the book")
+    _check(d["max_leases"] > 0, "max_leases is 0")
+    for bit, cap in ((1, d["max_waiting"]), (4, d["max_rows"]), (8, d["max_book"])):
+        _check(bool(mode & bit) == bool(cap), "a bound does not fit the mode")
+    _check(max(d["n_leases"], d["base_n_leases"]) <= d["max_leases"] and max(d["n_waiting"], d["base_n_waiting"]) <=
+           d["max_waiting"] and d["n_book"] <= d["max_book"] and d["n_wait_rows"] <= d["max_rows"], "a count beyond its bound")
+    _check(d["n_era"] + d["n_upd"] <= d["base_n_leases"], "more erased and updated leases than the base holds")
+    _check(d["base_n_leases"] + d["n_ins"] - d["n_era"] == d["n_leases"], "|L| is not the base's + inserted - erased")
+    _check(d["base_next_id"] <= d["next_id"] and d["n_ins"] <= d["next_id"] - d["base_next_id"],
+           "more inserted leases than ids handed out")
+    _check(d["last_now"] >= d["base_last_now"], "the clock runs backwards")
+    for t in (d["lease_tick"], d["base_lease_tick"]):
+        _check(t == 0 or t & STAMP, "a tick number whose stamp is 0")
+    _check(mode & 16 or d["alive_bound"] == I64_MAX, "alive_bound without E")
+    off = DELTA_HEADER_BYTES
+    secs = _delta_sections(mode, n, d["n_ins"], d["n_era"], d["n_upd"], d["n_waiting"], d["n_book"], d["book_present"])
+    for k, (name, cols, size) in enumerate(secs):
+        _check(directory[2 * k] == off and directory[2 * k + 1] == size, "section %s is not where its counts put it" % name)
+        _check(off + size <= len(blob), "section %s reaches past the end" % name)
+        p = off
+        for col, dt, cnt in cols:
+            d[col] = np.frombuffer(blob, dt, cnt, p).copy()
+            p += np.dtype(dt).itemsize * cnt
+        _check(not any(blob[p:off + size]), "padding is not zero")
+        off += size
+    _check(off == len(blob), "bytes behind the last section")
+    _check(checksum(blob) == csum, "checksum")
+    for k in ("ins_id", "era_id", "upd_id"):
+        _check((d[k][1:] > d[k][:-1]).all(), "%s not ascending" % k)
+    _check(((d["ins_id"] >= d["base_next_id"]) & (d["ins_id"] < d["next_id"])).all(),
+           "an inserted id outside [base next_id, next_id)")
+    _check((d["era_id"] < d["base_next_id"]).all() and (d["upd_id"] < d["base_next_id"]).all(),
+           "an erased or updated id >= the base's next_id")
+    _check(not np.isin(d["era_id"], d["upd_id"]).any(), "a lease both erased and updated")
+    _check((d["ins_state"] & LIVE != 0).all() and (d["upd_state"] & LIVE != 0).all(), "a carried lease without the live bit")
+    _check((d["ins_servant"] < n).all(), "an inserted lease names no servant")
+    if mode & 4:
+        rows = d["w_n_immediate"].astype(np.uint64) + d["w_n_prefetch"]
+        _check((rows > 0).all() and int(rows.sum()) == d["n_wait_rows"], "rows(W) differs from the entries' sum")
+    else:
+        _check(d["n_wait_rows"] == 0, "rows(W) without rpc mode")
+    if d["book_present"]:
+        _check((d["b_servant"] < n).all(), "a book entry names no servant")
+    if mode & 16:
+        _check((d["e_expires_at"] >= d["alive_bound"]).all(), "alive_bound above an expiry")
+    return d
+
+
+def build_delta(before, after):
+    """The delta blob that takes the stream of the parsed full snapshot `before` to that of `after`: a
+    function of the two snapshots alone. FormatError where there is none: another structure stamp, a
+    stream without L, a lease on another servant."""
+    _check(before.get("leased") and after.get("leased"), "a snapshot without L")
+    st = structure_stamp(before)
+    _check(st == structure_stamp(after), "the structure differs")
+    mode, n = mode_of(after), len(after["version"])
+    a_id, b_id = np.asarray(before["l_id"], np.uint64), np.asarray(after["l_id"], np.uint64)
+    in_a, in_b = np.isin(b_id, a_id), np.isin(a_id, b_id)
+    _check((b_id[~in_a] >= np.uint64(before["next_id"])).all(), "a lease appeared below the base's next_id")
+    ka, kb = np.flatnonzero(in_b), np.flatnonzero(in_a)  # the leases in both, by position in each
+    _check(np.array_equal(before["l_servant"][ka], after["l_servant"][kb]), "a lease changed its servant")
+    ch = kb[(before["l_expires_at"][ka] != after["l_expires_at"][kb]) | (before["l_state"][ka] != after["l_state"][kb])]
+    cols = dict(ins_id=b_id[~in_a], ins_expires_at=after["l_expires_at"][~in_a], ins_servant=after["l_servant"][~in_a],
+                ins_state=after["l_state"][~in_a], era_id=a_id[~in_b], upd_id=b_id[ch],
+                upd_expires_at=after["l_expires_at"][ch], upd_state=after["l_state"][ch])
+    for k in DELTA_REGISTRY + tuple(c for c, _ in _W_COLS + _B_COLS) + ("e_expires_at",):
+        if k in after:
+            cols[k] = after[k]
+    n_b = len(after["b_grant_id"]) if mode & 8 else 0
+    book_present = int(bool(mode & 8) and (n_b != len(before["b_grant_id"]) or any(
+        not np.array_equal(before[c], after[c]) for c, _ in _B_COLS)))
+    n_w = len(after["w_tag"]) if mode & 1 else 0
+    secs = _delta_sections(mode, n, len(cols["ins_id"]), len(cols["era_id"]), len(cols["upd_id"]), n_w, n_b, book_present)
+    body, directory, off = [], [], DELTA_HEADER_BYTES
+    for name, sec, size in secs:
+        raw = b"".join(np.ascontiguousarray(cols[c], dt).tobytes() for c, dt, _ in sec)
+        body.append(raw + bytes(size - len(raw)))
+        directory += [off, size]
+        off += size
+    fields = [DELTA_MAGIC, DELTA_VERSION, DELTA_HEADER_BYTES, off, 0, mode, int(after["env_words"]), n, book_present,
+              int(after["max_leases"]), int(after["max_waiting"]), int(after["max_rows"]), int(after["max_book"]), st,
+              int(before["next_id"]), int(before["last_now"]), int(before["lease_tick"]), len(a_id),
+              len(before["w_tag"]) if mode & 1 else 0, 0, int(after["next_id"]), int(after["last_now"]),
+              int(after["alive_bound"]), int(after["lease_tick"]), len(b_id), n_w, int(after["n_wait_rows"]), n_b,
+              len(cols["ins_id"]), len(cols["era_id"]), len(cols["upd_id"])] + directory
+    blob = bytearray(DELTA_HEADER.pack(*fields) + b"".join(body))
+    struct.pack_into("<Q", blob, 8 * CHECKSUM_WORD, checksum(blob))
+    blob = bytes(blob)
+    parse_delta(blob)
+    return blob
+
+
+def apply_delta(before, delta):
+    """The parsed full snapshot that results when the delta (bytes or parse_delta's dict) is applied to the
+    parsed full snapshot `before`: what ydc_stream_delta_apply makes of a standby in that state. FormatError
+    where the delta's base is not `before`, an erased or updated id is missing, or an inserted one is there."""
+    d = delta if isinstance(delta, dict) else parse_delta(delta)
+    _check(before.get("leased") and d["mode"] == mode_of(before) and d["stamp"] == structure_stamp(before),
+           "the delta's structure stamp is not this state's")
+    ids = np.asarray(before["l_id"], np.uint64)
+    _check((d["base_lease_tick"], d["base_next_id"], d["base_n_leases"], d["base_last_now"]) ==
+           (before["lease_tick"], before["next_id"], len(ids), before["last_now"]) and
+           d["base_n_waiting"] == (len(before["w_tag"]) if before.get("waiting") else 0), "the delta's base is not this state")
+    _check(np.isin(d["era_id"], ids).all() and np.isin(d["upd_id"], ids).all(), "an erased or updated id is no lease")
+    _check(not np.isin(d["ins_id"], ids).any(), "an inserted id is a lease already")
+    out = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in before.items()}
+    exp, state = out["l_expires_at"], out["l_state"]
+    at = np.searchsorted(ids, d["upd_id"])
+    exp[at], state[at] = d["upd_expires_at"], d["upd_state"]
+    keep = ~np.isin(ids, d["era_id"])
+    l_id = np.concatenate([ids[keep], d["ins_id"]])
+    order = np.argsort(l_id, kind="stable")
+    out["l_id"] = l_id[order]
+    out["l_expires_at"] = np.concatenate([exp[keep], d["ins_expires_at"]])[order]
+    out["l_servant"] = np.concatenate([out["l_servant"][keep], d["ins_servant"]])[order]
+    out["l_state"] = np.concatenate([state[keep], d["ins_state"]])[order]
+    out["l_zombie"] = (out["l_state"] & ZOMBIE != 0).astype(np.uint8)
+    out["l_stamp"] = out["l_state"] & np.uint32(STAMP)
+    for k in DELTA_REGISTRY + ("e_expires_at",) + tuple(c for c, _ in _W_COLS) + (
+            tuple(c for c, _ in _B_COLS) if d["book_present"] else ()):
+        if k in d:
+            out[k] = d[k].copy()
+    if not d["book_present"] and before.get("book"):
+        _check(d["n_book"] == len(before["b_grant_id"]), "|B| differs without B")
+    for k in ("next_id", "last_now", "lease_tick", "alive_bound", "n_wait_rows"):
+        out[k] = d[k]
+    return out
