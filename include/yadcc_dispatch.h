@@ -1220,12 +1220,54 @@ int ydc_stream_restore(ydc_context* ctx, const void* blob, size_t bytes, const y
  *     identical ticks give identical results. The table's buffers do not move: a step captured
  *     before stays valid. Refused while inspection is on: like ydc_stream_restore, a delta carries
  *     no inspection records, quota, withdrawal or departure settings; a standby that needs
- *     inspection loads it at promotion with ydc_stream_inspect_load.
+ *     inspection applies every delta with its sidecar (ydc_stream_delta_apply_inspected, below).
  *   - ydc_stream_delta_stop: frees the base image (ydc_stream_end and ydc_destroy do so too). */
 int ydc_stream_delta_base(ydc_context* ctx, void* out, size_t cap, size_t* out_bytes);
 int ydc_stream_delta(ydc_context* ctx, void* out, size_t cap, size_t* out_bytes);
 int ydc_stream_delta_apply(ydc_context* ctx, const void* delta, size_t bytes);
 int ydc_stream_delta_stop(ydc_context* ctx);
+
+/* ---- inspection sidecars: a standby whose inspection records follow the deltas ------------
+ * A snapshot and a delta carry no inspection records. A sidecar carries them: beside a full snapshot
+ * (or ydc_stream_delta_base's bytes) the record of every lease, beside a delta the records of the
+ * delta's inserted leases — a record never changes after its grant and dies with its lease — and in
+ * both the two servant columns (discovered_at, ever_assigned) whole. The format is DESIGN 3.3.19
+ * (stream_inspect_delta_codec.h, yadcc_amd/snapshot.py): a header of 120 bytes that names the state
+ * the sidecar describes (lease_tick, next_id, |L|, last_now, the structure stamp) and the inspection
+ * epoch, then id, started_at, env_id, requestor_ip and prefetch as columns in ascending id order
+ * and the servant columns: 120 + 24n + pad8(n) + 16 * n_servants bytes. The epoch counts the calls
+ * that rewrite records of leases that exist already (ydc_stream_inspect_begin, ydc_stream_inspect_load):
+ * when it moves on the primary, its delta sidecars are refused and the standby takes a new base.
+ * Same modes as the delta calls; anything else is YDC_ERR_INVALID_ARGUMENT. The standby's recipe:
+ * ydc_stream_restore, ydc_stream_inspect_restore, then ydc_stream_delta_apply_inspected per delta.
+ *   - ydc_stream_delta_inspect: the primary, between ticks, inspection on; reads only, synchronises,
+ *     and touches nothing of the delta base. With `delta` (the blob ydc_stream_delta just returned,
+ *     validated here; its resulting lease_tick, next_id, |L|, last_now and stamp must be ctx's
+ *     current state, so the call comes before the next tick): the sidecar of that delta, its records
+ *     gathered on the device, one probe per inserted id. An inserted id that is no lease:
+ *     YDC_ERR_INVALID_ARGUMENT, nothing written. With delta == NULL (delta_bytes ignored): the full
+ *     sidecar, all of L as ydc_stream_inspect_tasks orders it. cap too small: YDC_ERR_CAPACITY,
+ *     *out_bytes the size needed, nothing written or changed; the call can be repeated.
+ *   - ydc_stream_inspect_restore: a full sidecar onto a context in the very state it describes (in
+ *     practice just restored from the matching snapshot). Switches inspection on with the sidecar's
+ *     servant columns, files every record and adopts the epoch. Checked before ctx is touched: the
+ *     bytes, the kind, the identity, n == |L| and every id a live lease. Anything amiss:
+ *     YDC_ERR_INVALID_ARGUMENT and ctx is as it was, with inspection off if it was off.
+ *   - ydc_stream_delta_apply_inspected: ydc_stream_delta_apply for a standby with inspection on.
+ *     Both blobs are validated; the sidecar must be a delta's, describe the state the delta results
+ *     in, carry exactly the delta's inserted ids, and have ctx's epoch; then all of
+ *     ydc_stream_delta_apply's checks, its read-only pass included. Every refusal comes before the
+ *     first write and is YDC_ERR_INVALID_ARGUMENT: ctx keeps its snapshot bytes and its inspection
+ *     columns. The thread that inserts a lease stores its record into the slot it took; the servant
+ *     columns are copied whole. Neither the table's nor the inspection columns' buffers move: a
+ *     step captured before stays valid. With inspection off on ctx: YDC_ERR_INVALID_ARGUMENT
+ *     (ydc_stream_delta_apply is the call). Quota, withdrawal and departure settings are not state
+ *     of the stream's: the host sets them again at promotion. */
+int ydc_stream_delta_inspect(ydc_context* ctx, const void* delta, size_t delta_bytes, void* out, size_t cap,
+                             size_t* out_bytes);
+int ydc_stream_inspect_restore(ydc_context* ctx, const void* side, size_t bytes);
+int ydc_stream_delta_apply_inspected(ydc_context* ctx, const void* delta, size_t delta_bytes, const void* side,
+                                     size_t side_bytes);
 
 /* ---- multi-GPU group: one batch sharded by rank range (BASELINE.json configs[3]) ------
  * One process per GPU; every rank creates its context and uploads the SAME servant table.

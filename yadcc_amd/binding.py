@@ -61,6 +61,7 @@ ABI_SYMBOLS = (
     "ydc_stream_depart_begin", "ydc_stream_depart_stage", "ydc_stream_depart_result",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_stream_delta_base", "ydc_stream_delta", "ydc_stream_delta_apply", "ydc_stream_delta_stop",
+    "ydc_stream_delta_inspect", "ydc_stream_inspect_restore", "ydc_stream_delta_apply_inspected",
     "ydc_group_unique_id", "ydc_group_init", "ydc_group_init_local", "ydc_group_destroy",
     "ydc_group_size", "ydc_group_ipc_export", "ydc_group_init_ipc", "ydc_group_transport",
     "ydc_dispatch_sharded",
@@ -300,6 +301,9 @@ def lib():
         L.ydc_stream_delta.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ydc_stream_delta_apply.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         L.ydc_stream_delta_stop.argtypes = [C.c_void_p]
+        L.ydc_stream_delta_inspect.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ydc_stream_inspect_restore.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        L.ydc_stream_delta_apply_inspected.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
         L.ydc_stream_alive_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_alive_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_alive_removed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1128,6 +1132,32 @@ class Context:
     def stream_delta_stop(self):
         """Frees the base image (ydc_stream_delta_stop)."""
         self._check(lib().ydc_stream_delta_stop(self._h), "ydc_stream_delta_stop")
+
+    def stream_delta_inspect(self, delta=None):
+        """The inspection sidecar of the delta just taken (its inserted leases' records), or with
+        delta=None the full one that goes beside stream_snapshot's or stream_delta_base's bytes; both with
+        the two servant columns whole (ydc_stream_delta_inspect; the format: yadcc_amd/snapshot.py
+        parse_inspect_delta). Called before the next tick."""
+        delta = None if delta is None else bytes(delta)
+        size = C.c_size_t(0 if delta is None else len(delta))
+
+        def fn(h, out, cap, need):
+            return lib().ydc_stream_delta_inspect(h, delta, size, out, cap, need)
+        return self._sized_blob(fn, "ydc_stream_delta_inspect")
+
+    def stream_inspect_restore(self, side):
+        """Switches inspection on with a full sidecar's servant columns, records and epoch, on a context in
+        the very state the sidecar describes: just restored from the matching snapshot
+        (ydc_stream_inspect_restore). A refused sidecar leaves the context as it was."""
+        side = bytes(side)
+        self._check(lib().ydc_stream_inspect_restore(self._h, side, C.c_size_t(len(side))), "ydc_stream_inspect_restore")
+
+    def stream_delta_apply_inspected(self, delta, side):
+        """stream_delta_apply on a standby with inspection on: the delta and its sidecar together
+        (ydc_stream_delta_apply_inspected). A refused pair leaves the context as it was."""
+        delta, side = bytes(delta), bytes(side)
+        self._check(lib().ydc_stream_delta_apply_inspected(self._h, delta, C.c_size_t(len(delta)), side, C.c_size_t(len(side))),
+                    "ydc_stream_delta_apply_inspected")
 
     def stream_restore(self, blob, **want):
         """Makes this context what the snapshotted one was (ydc_stream_restore): registry, running_tasks,

@@ -45,6 +45,8 @@
 #include "admit_clip.h"
 #include "stream_delta.h"
 #include "stream_delta_codec.h"
+#include "stream_inspect_delta.h"
+#include "stream_inspect_delta_codec.h"
 #include "stream_snapshot.h"
 #include "stream_snapshot_codec.h"
 #include "stream_depart.h"
@@ -539,6 +541,10 @@ struct ydc_context {
     struct Inspect {
       bool on = false;
       uint32_t n = 0;  // rows of the two servant columns that are filed
+      // The inspection epoch: counts the calls that rewrite records of leases that exist
+      // already (ydc_stream_inspect_begin, ydc_stream_inspect_load); ydc_stream_inspect_restore adopts a
+      // full sidecar's. A delta sidecar is applied only under the epoch it was taken in.
+      uint64_t epoch = 0;
       DevBuf<int64_t> disc, disc_spare;
       DevBuf<unsigned long long> ever, ever_spare;
       DevBuf<uint32_t> avail;   // k_inspect_servants' per-servant result
@@ -6019,6 +6025,7 @@ int ydc_stream_inspect_begin(ydc_context* c, const int64_t* discovered_at, const
   }
   sm.inspect.n = n;
   sm.inspect.on = true;
+  ++sm.inspect.epoch;
   sm.stale = true;  // (the step's granting pass changes, and it holds the columns' addresses: captured again)
   return YDC_OK;
 }
@@ -6075,6 +6082,7 @@ int ydc_stream_inspect_load(ydc_context* c, const uint64_t* task_id, const int64
   YDC_LAUNCH(c, "k_inspect_file", k_inspect_file, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, d_slot.p, n,
              sm.lt.mask + 1, d_at.p, d_env.p, d_ip.p, d_pre.p, sm.d_insp_rec.p, sm.d_insp_pre.p);
   HIP_TRY(c, hipGetLastError());
+  ++sm.inspect.epoch;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return YDC_OK;
 }
@@ -7962,7 +7970,9 @@ int stream_delta(ydc_context* c, void* out, size_t cap, size_t* out_bytes) {
   return YDC_OK;
 }
 
-int stream_delta_apply(ydc_context* c, const delta::View& v) {
+// The body of ydc_stream_delta_apply and ydc_stream_delta_apply_inspected. `side`: the delta's inspection
+// sidecar (validated, and checked against the delta by the caller), or nullptr on a stream without inspection.
+int stream_delta_apply(ydc_context* c, const char* what, const delta::View& v, const insd::View* side) {
   auto& sm = c->stream_mode;
   const delta::Header& h = v.h;
   snap::Header sh;
@@ -7972,25 +7982,28 @@ int stream_delta_apply(ydc_context* c, const delta::View& v) {
   if (h.mode != sh.mode || h.env_words != sh.env_words || h.n_servants != n || h.max_leases != sm.caps.max_leases ||
       h.max_waiting != sm.caps.max_waiting || h.max_rows != sm.caps.max_rows || h.max_book != sm.max_book ||
       h.stamp != delta_stamp(c, sh))
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: the delta's structure stamp is not this context's");
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the delta's structure stamp is not this context's", what);
   LeaseState lst{};
   HIP_TRY(c, hipMemcpy(&lst, sm.ls, sizeof lst, hipMemcpyDeviceToHost));
   if (h.base_lease_tick != sm.lease_tick || h.base_next_id != lst.next_id || h.base_n_leases != sm.n_leases ||
       lst.n_leases != sm.n_leases || h.base_n_waiting != sh.n_waiting || h.base_last_now != sm.last_now)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: the delta's base (tick %u, next_id %llu, |L| %u, |W| %u) "
-                "is not this context's state (tick %u, next_id %llu, |L| %u, |W| %u)", h.base_lease_tick,
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the delta's base (tick %u, next_id %llu, |L| %u, |W| %u) "
+                "is not this context's state (tick %u, next_id %llu, |L| %u, |W| %u)", what, h.base_lease_tick,
                 (unsigned long long)h.base_next_id, h.base_n_leases, h.base_n_waiting, sm.lease_tick, lst.next_id,
                 sm.n_leases, sh.n_waiting);
   if (!h.book_present && sm.max_book && h.n_book != sm.book.n)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: |B| %u without B, %u here", h.n_book, sm.book.n);
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: |B| %u without B, %u here", what, h.n_book, sm.book.n);
   hipStream_t st = c->stream;
   // The lists on the device (aligned copies: the block's base may be any address), and the read-only
   // pass: every erased and updated id is in the table, no inserted one is.
   const size_t ni = h.n_ins, ne = h.n_era, nu = h.n_upd;
-  const size_t words = ni * 3 + ne + nu * 3 + 2;  // (8-byte units; the counters behind the lists)
-  std::vector<uint64_t> stage(words, 0);
-  uint8_t* s8 = (uint8_t*)stage.data();
   const size_t o_ins = 0, o_era = ni * 24, o_upd = o_era + ne * 8, o_cnt = (o_upd + nu * 20 + 7) & ~(size_t)7;
+  // (with a sidecar, its records behind the counters: started_at | env_id | requestor_ip | prefetch)
+  const size_t o_rec = o_cnt + ((sizeof(DeltaCounts) + 7) & ~(size_t)7), rec_bytes = side ? ni * 17 : 0;
+  std::vector<uint64_t> stage((o_rec + rec_bytes + 7) / 8, 0);  // (8-byte units; the counters behind the lists)
+  uint8_t* s8 = (uint8_t*)stage.data();
+  if (side && (sm.inspect.n != n || sm.inspect.disc.cap < n || sm.inspect.ever.cap < n))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the inspection columns have %u rows for %u servants", what, sm.inspect.n, n);
   std::memcpy(s8 + o_ins, v.ins_id, ni * 8);
   std::memcpy(s8 + o_ins + ni * 8, v.ins_exp, ni * 8);
   std::memcpy(s8 + o_ins + ni * 16, v.ins_srv, ni * 4);
@@ -8000,9 +8013,16 @@ int stream_delta_apply(ydc_context* c, const delta::View& v) {
   std::memcpy(s8 + o_upd + nu * 8, v.upd_exp, nu * 8);
   std::memcpy(s8 + o_upd + nu * 16, v.upd_state, nu * 4);
   auto& buf = sm.delta.apply;
-  HIP_TRY(c, buf.reserve(o_cnt + sizeof(DeltaCounts)));
-  if (o_cnt) HIP_TRY(c, hipMemcpy(buf.p, s8, o_cnt, hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemset(buf.p + o_cnt, 0, sizeof(DeltaCounts)));
+  HIP_TRY(c, buf.reserve(o_rec + rec_bytes));
+  const InspectRecords recs{(int64_t*)(buf.p + o_rec), (uint32_t*)(buf.p + o_rec + ni * 8), (uint32_t*)(buf.p + o_rec + ni * 12),
+                            buf.p + o_rec + ni * 16};
+  if (side) {  // (lists, cleared counters and records in one copy)
+    if (ni) std::memcpy(s8 + o_rec, side->started_at, ni * 17);  // (the record section's four columns lie like this)
+    HIP_TRY(c, hipMemcpy(buf.p, s8, o_rec + rec_bytes, hipMemcpyHostToDevice));
+  } else {
+    if (o_cnt) HIP_TRY(c, hipMemcpy(buf.p, s8, o_cnt, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(buf.p + o_cnt, 0, sizeof(DeltaCounts)));
+  }
   const LeasePacked ins = packed_at(buf.p + o_ins, ni);
   const unsigned long long* era = (const unsigned long long*)(buf.p + o_era);
   uint8_t* u = buf.p + o_upd;
@@ -8015,8 +8035,8 @@ int stream_delta_apply(ydc_context* c, const delta::View& v) {
   HIP_TRY(c, hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   if (cnt.found_old != ne + nu || cnt.found_new)
-    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: %u of %zu erased and updated ids are leases here, and %u "
-                "of the inserted ones", cnt.found_old, ne + nu, cnt.found_new);
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: %u of %zu erased and updated ids are leases here, and %u "
+                "of the inserted ones", what, cnt.found_old, ne + nu, cnt.found_new);
   if (sm.d_rep_tick.cap < n) {  // (never after a restore, which sizes it by the registry; the step holds its address)
     DevBuf<uint32_t> bigger;
     HIP_TRY(c, bigger.reserve((size_t)n + 1024));
@@ -8029,10 +8049,20 @@ int stream_delta_apply(ydc_context* c, const delta::View& v) {
                st, sm.lt, sm.ls, era, (uint32_t)ne, upd, (uint32_t)nu);
     HIP_TRY(c, hipGetLastError());
   }
-  YDC_LAUNCH(c, "k_lease_delta_apply_new", k_lease_delta_apply_new, dim3(ceil_div((uint32_t)std::max<size_t>(ni, 1), 256)),
-             dim3(256), 0, st, sm.lt, sm.ls, ins, (uint32_t)ni, (unsigned long long)h.next_id, h.n_leases);
+  if (side) {
+    YDC_LAUNCH(c, "k_lease_delta_apply_inspect", k_lease_delta_apply_inspect,
+               dim3(ceil_div((uint32_t)std::max<size_t>(ni, 1), 256)), dim3(256), 0, st, sm.lt, sm.ls, ins, recs, (uint32_t)ni,
+               (unsigned long long)h.next_id, h.n_leases, sm.d_insp_rec.p, sm.d_insp_pre.p);
+  } else {
+    YDC_LAUNCH(c, "k_lease_delta_apply_new", k_lease_delta_apply_new, dim3(ceil_div((uint32_t)std::max<size_t>(ni, 1), 256)),
+               dim3(256), 0, st, sm.lt, sm.ls, ins, (uint32_t)ni, (unsigned long long)h.next_id, h.n_leases);
+  }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(st));
+  if (side && n) {  // (the two servant columns, whole, into buffers that stay where they are)
+    HIP_TRY(c, hipMemcpy(sm.inspect.disc.p, side->discovered_at, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(sm.inspect.ever.p, side->ever_assigned, (size_t)n * 8, hipMemcpyHostToDevice));
+  }
   // The registry's light columns, on the device and in the host's mirror. Rows whose version or
   // capacity bound moved (a structural turn the stamp does not cover) have the derived tables rebuilt.
   bool structural = false;
@@ -8116,9 +8146,9 @@ int ydc_stream_delta_apply(ydc_context* c, const void* blob, size_t bytes) {
   if (const char* why = delta::validate(blob, bytes, &v)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: %s", why);
   if (c->stream_mode.inspect.on)
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_delta_apply: inspection is on (a delta carries no inspection "
-                "records: load them at promotion)");
+                "records: ydc_stream_delta_apply_inspected takes it with its sidecar)");
   if (int rc = delta_settle(c, "ydc_stream_delta_apply")) return rc;
-  return stream_delta_apply(c, v);
+  return stream_delta_apply(c, "ydc_stream_delta_apply", v, nullptr);
 }
 
 int ydc_stream_delta_stop(ydc_context* c) {
@@ -8131,6 +8161,223 @@ int ydc_stream_delta_stop(ydc_context* c) {
   b = ydc_context::Stream::DeltaBase{};
   b.apply = std::move(keep);
   return YDC_OK;
+}
+
+// ---- inspection sidecars (stream_inspect_delta.h, stream_inspect_delta_codec.h) ----
+
+// The identity of the context's state as a sidecar names it (the stream at rest: delta_settle).
+static int inspect_identity(ydc_context* c, insd::Header* h) {
+  auto& sm = c->stream_mode;
+  snap::Header sh;
+  snap_describe(c, &sh);
+  LeaseState lst{};
+  HIP_TRY(c, hipMemcpy(&lst, sm.ls, sizeof lst, hipMemcpyDeviceToHost));
+  if (lst.n_leases != sh.n_leases)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "lease table: |L| %u on the device, %u on the host", lst.n_leases, sh.n_leases);
+  h->stamp = delta_stamp(c, sh);
+  h->next_id = lst.next_id;
+  h->last_now = sh.last_now;
+  h->lease_tick = sh.lease_tick;
+  h->n_leases = sh.n_leases;
+  h->n_servants = sh.n_servants;
+  return YDC_OK;
+}
+
+static bool inspect_same_state(const insd::Header& a, const insd::Header& b) {
+  return a.stamp == b.stamp && a.next_id == b.next_id && a.last_now == b.last_now && a.lease_tick == b.lease_tick &&
+         a.n_leases == b.n_leases && a.n_servants == b.n_servants;
+}
+
+// The state a delta results in, as a sidecar names it.
+static insd::Header inspect_result_of(const delta::Header& d) {
+  insd::Header h{};
+  h.stamp = d.stamp, h.next_id = d.next_id, h.last_now = d.last_now, h.lease_tick = d.lease_tick;
+  h.n_leases = d.n_leases, h.n_servants = d.n_servants;
+  return h;
+}
+
+int ydc_stream_delta_inspect(ydc_context* c, const void* delta_blob, size_t delta_bytes, void* out, size_t cap,
+                             size_t* out_bytes) {
+  if (!c || !out_bytes) return YDC_ERR_INVALID_ARGUMENT;
+  const char* const who = "ydc_stream_delta_inspect";
+  if (int rc = delta_mode_check(c, who)) return rc;
+  auto& sm = c->stream_mode;
+  if (!sm.inspect.on) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the stream has no inspection", who);
+  delta::View dv{};
+  if (delta_blob)
+    if (const char* why = delta::validate(delta_blob, delta_bytes, &dv)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: %s", who, why);
+  if (int rc = delta_settle(c, who)) return rc;
+  if (int rc = inspect_fit(c, sm.last_now == INT64_MIN ? 0 : sm.last_now)) return rc;
+  insd::Header now{};
+  if (int rc = inspect_identity(c, &now)) return rc;
+  if (delta_blob && !inspect_same_state(inspect_result_of(dv.h), now))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the delta's result (tick %u, next_id %llu, |L| %u) is not this context's state "
+                "(tick %u, next_id %llu, |L| %u): the sidecar is taken before the next tick", who, dv.h.lease_tick,
+                (unsigned long long)dv.h.next_id, dv.h.n_leases, now.lease_tick, (unsigned long long)now.next_id, now.n_leases);
+  const uint32_t S = now.n_servants, n = delta_blob ? dv.h.n_ins : now.n_leases;
+  insd::Header h = insd::describe(delta_blob ? insd::kDelta : insd::kFull, S, n);
+  h.stamp = now.stamp, h.next_id = now.next_id, h.last_now = now.last_now, h.lease_tick = now.lease_tick;
+  h.n_leases = now.n_leases, h.epoch = sm.inspect.epoch;
+  *out_bytes = (size_t)h.total_bytes;
+  if (cap < h.total_bytes) return fail(c, YDC_ERR_CAPACITY, "a sidecar of %llu bytes > cap %zu", (unsigned long long)h.total_bytes, cap);
+  if (!out) return YDC_ERR_INVALID_ARGUMENT;
+  // The records' columns on the host, in id order.
+  std::vector<uint64_t> id(n);
+  std::vector<int64_t> started(n);
+  std::vector<uint32_t> env(n), ip(n);
+  std::vector<uint8_t> pre(n);
+  if (delta_blob && n) {
+    // ids | started_at | env_id | requestor_ip | prefetch | the count of misses
+    std::memcpy(id.data(), dv.ins_id, (size_t)n * 8);
+    const size_t o_cnt = ((size_t)n * 25 + 3) & ~(size_t)3;
+    HIP_TRY(c, sm.inspect.pack.reserve(o_cnt + 4));
+    uint8_t* d = sm.inspect.pack.p;
+    const InspectRecords recs{(int64_t*)(d + (size_t)n * 8), (uint32_t*)(d + (size_t)n * 16), (uint32_t*)(d + (size_t)n * 20),
+                              d + (size_t)n * 24};
+    HIP_TRY(c, hipMemcpyAsync(d, id.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d + o_cnt, 0, 4, c->stream));
+    YDC_LAUNCH(c, "k_inspect_gather", k_inspect_gather, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, sm.lt, sm.ls,
+               sm.d_insp_rec.p, sm.d_insp_pre.p, (const unsigned long long*)d, n, recs, (uint32_t*)(d + o_cnt));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // The four columns and the count behind them, in one copy.
+    std::vector<uint8_t> back(o_cnt + 4 - (size_t)n * 8);
+    HIP_TRY(c, hipMemcpy(back.data(), d + (size_t)n * 8, back.size(), hipMemcpyDeviceToHost));
+    uint32_t missing = 0;
+    std::memcpy(&missing, back.data() + back.size() - 4, 4);
+    if (missing) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: %u of the delta's %u inserted ids are no lease", who, missing, n);
+    std::memcpy(started.data(), back.data(), (size_t)n * 8);
+    std::memcpy(env.data(), back.data() + (size_t)n * 8, (size_t)n * 4);
+    std::memcpy(ip.data(), back.data() + (size_t)n * 12, (size_t)n * 4);
+    std::memcpy(pre.data(), back.data() + (size_t)n * 16, n);
+  } else if (n) {
+    uint32_t got = 0;
+    if (int rc = ydc_stream_inspect_tasks(c, id.data(), nullptr, nullptr, nullptr, started.data(), env.data(), ip.data(),
+                                          pre.data(), n, &got))
+      return rc;
+    if (got != n) return fail(c, YDC_ERR_NOT_CONVERGED, "%s: %u records for |L| %u", who, got, n);
+  }
+  std::vector<int64_t> disc(S);
+  std::vector<uint64_t> ever(S);
+  if (S) {
+    HIP_TRY(c, hipMemcpy(disc.data(), sm.inspect.disc.p, (size_t)S * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(ever.data(), sm.inspect.ever.p, (size_t)S * 8, hipMemcpyDeviceToHost));
+  }
+  std::vector<uint8_t> blob;
+  insd::build(h, insd::Columns{id.data(), started.data(), env.data(), ip.data(), pre.data(), disc.data(), ever.data()}, &blob);
+  std::memcpy(out, blob.data(), blob.size());
+  return YDC_OK;
+}
+
+int ydc_stream_inspect_restore(ydc_context* c, const void* side, size_t bytes) {
+  if (!c || !side) return YDC_ERR_INVALID_ARGUMENT;
+  const char* const who = "ydc_stream_inspect_restore";
+  if (int rc = delta_mode_check(c, who)) return rc;
+  // Everything that can be wrong with the bytes, before anything of the context is looked at.
+  insd::View v{};
+  if (const char* why = insd::validate(side, bytes, &v)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: %s", who, why);
+  if (v.h.kind != insd::kFull) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: a delta's sidecar (ydc_stream_delta_apply_inspected takes it)", who);
+  if (int rc = delta_settle(c, who)) return rc;
+  auto& sm = c->stream_mode;
+  insd::Header now{};
+  if (int rc = inspect_identity(c, &now)) return rc;
+  if (!inspect_same_state(v.h, now))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the sidecar's state (tick %u, next_id %llu, |L| %u, %u servants) is not this "
+                "context's (tick %u, next_id %llu, |L| %u, %u servants)", who, v.h.lease_tick, (unsigned long long)v.h.next_id,
+                v.h.n_leases, v.h.n_servants, now.lease_tick, (unsigned long long)now.next_id, now.n_leases, now.n_servants);
+  const uint32_t n = v.h.n, S = v.h.n_servants;  // (n == |L|: validate)
+  // Every id is a live lease (read-only). The ids ascend, so n distinct leases of |L| == n are all of L.
+  DevBuf<unsigned long long> d_id;
+  DevBuf<int64_t> d_at;
+  DevBuf<uint32_t> d_slot, d_env, d_ip, d_miss;
+  DevBuf<uint8_t> d_pre;
+  const size_t nn = std::max(n, 1u);
+  HIP_TRY(c, d_id.reserve(nn));
+  HIP_TRY(c, d_slot.reserve(nn));
+  HIP_TRY(c, d_at.reserve(nn));
+  HIP_TRY(c, d_env.reserve(nn));
+  HIP_TRY(c, d_ip.reserve(nn));
+  HIP_TRY(c, d_pre.reserve(nn));
+  HIP_TRY(c, d_miss.reserve(1));
+  if (n) {
+    HIP_TRY(c, hipMemcpy(d_id.p, v.id, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_at.p, v.started_at, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_env.p, v.env_id, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_ip.p, v.requestor_ip, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_pre.p, v.prefetch, n, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemset(d_miss.p, 0, 4));
+    YDC_LAUNCH(c, "k_inspect_find", k_inspect_find, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, sm.lt, sm.ls, d_id.p, n,
+               d_slot.p, d_miss.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint32_t missing = 0;
+    HIP_TRY(c, hipMemcpy(&missing, d_miss.p, 4, hipMemcpyDeviceToHost));
+    if (missing) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: %u of %u ids are no lease", who, missing, n);
+  }
+  // Room for everything, still before the first write into the context's state.
+  const size_t slots = (size_t)sm.lt.mask + 1;
+  DevBuf<int64_t> disc;
+  DevBuf<unsigned long long> ever;
+  DevBuf<uint4> rec;
+  DevBuf<uint8_t> pre;
+  const bool fresh = !sm.inspect.on;
+  if (fresh) {
+    HIP_TRY(c, disc.reserve((size_t)S + S / 2 + 1024));
+    HIP_TRY(c, ever.reserve((size_t)S + S / 2 + 1024));
+    HIP_TRY(c, rec.reserve(slots));
+    HIP_TRY(c, pre.reserve(slots));
+  } else if (sm.inspect.disc.cap < S || sm.inspect.ever.cap < S) {
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the inspection columns hold %zu rows, %u servants", who, sm.inspect.disc.cap, S);
+  }
+  // From here on the context is written.
+  if (fresh) {
+    sm.inspect.disc = std::move(disc);
+    sm.inspect.ever = std::move(ever);
+    sm.d_insp_rec = std::move(rec);
+    sm.d_insp_pre = std::move(pre);
+    YDC_LAUNCH(c, "k_inspect_fill", k_inspect_fill, dim3(ceil_div((uint32_t)slots, 256)), dim3(256), 0, c->stream,
+               sm.d_insp_rec.p, sm.d_insp_pre.p, (uint32_t)slots);
+    HIP_TRY(c, hipGetLastError());
+  }
+  if (S) {
+    HIP_TRY(c, hipMemcpy(sm.inspect.disc.p, v.discovered_at, (size_t)S * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(sm.inspect.ever.p, v.ever_assigned, (size_t)S * 8, hipMemcpyHostToDevice));
+  }
+  if (n) {
+    YDC_LAUNCH(c, "k_inspect_file", k_inspect_file, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, d_slot.p, n,
+               (uint32_t)slots, d_at.p, d_env.p, d_ip.p, d_pre.p, sm.d_insp_rec.p, sm.d_insp_pre.p);
+    HIP_TRY(c, hipGetLastError());
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  sm.inspect.n = S;
+  sm.inspect.on = true;
+  sm.inspect.epoch = v.h.epoch;
+  sm.stale = true;  // (the step's granting pass changes, and it holds the columns' addresses: captured again)
+  return YDC_OK;
+}
+
+int ydc_stream_delta_apply_inspected(ydc_context* c, const void* blob, size_t bytes, const void* side, size_t side_bytes) {
+  if (!c || !blob || !side) return YDC_ERR_INVALID_ARGUMENT;
+  const char* const who = "ydc_stream_delta_apply_inspected";
+  if (int rc = delta_mode_check(c, who)) return rc;
+  // Everything that can be wrong with the bytes, and with the two blobs as a pair, before anything of the
+  // context is looked at.
+  delta::View v{};
+  insd::View sv{};
+  if (const char* why = delta::validate(blob, bytes, &v)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the delta: %s", who, why);
+  if (const char* why = insd::validate(side, side_bytes, &sv)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the sidecar: %s", who, why);
+  if (sv.h.kind != insd::kDelta) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: a full sidecar (ydc_stream_inspect_restore takes it)", who);
+  if (!inspect_same_state(sv.h, inspect_result_of(v.h)))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the sidecar describes another state than the delta results in", who);
+  if (sv.h.n != v.h.n_ins || (sv.h.n && std::memcmp(sv.id, v.ins_id, (size_t)sv.h.n * 8)))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the sidecar's ids are not the delta's inserted ones", who);
+  const auto& in = c->stream_mode.inspect;
+  if (!in.on) return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the stream has no inspection (ydc_stream_delta_apply is the call)", who);
+  if (sv.h.epoch != in.epoch)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the sidecar's inspection epoch %llu is not this context's %llu: records were "
+                "rewritten on the primary, take a new base", who, (unsigned long long)sv.h.epoch, (unsigned long long)in.epoch);
+  if (int rc = delta_settle(c, who)) return rc;
+  return stream_delta_apply(c, who, v, &sv);
 }
 
 }  // extern "C"

@@ -383,3 +383,141 @@ def apply_delta(before, delta):
     for k in ("next_id", "last_now", "lease_tick", "alive_bound", "n_wait_rows"):
         out[k] = d[k]
     return out
+
+
+# ---- inspection sidecars (ydc_stream_delta_inspect / ydc_stream_inspect_restore /
+# ydc_stream_delta_apply_inspected) ----
+# The second, independent implementation of yadcc_amd/csrc/stream_inspect_delta_codec.h: what a full
+# snapshot (kind 0) or a delta (kind 1) leaves out of a stream with inspection.
+INSPECT_DELTA_MAGIC = 0x3144534E49434459  # "YDCINSD1"
+INSPECT_DELTA_VERSION = 1
+INSPECT_DELTA_HEADER = struct.Struct("<QIIQQ4IQQqIIQ4Q")
+INSPECT_DELTA_HEADER_BYTES = 120
+assert INSPECT_DELTA_HEADER.size == INSPECT_DELTA_HEADER_BYTES
+INSPECT_FULL, INSPECT_DELTA = 0, 1
+INSPECT_NO_ID, INSPECT_NO_TIME = 0xFFFFFFFF, I64_MIN
+_INSPECT_FIELDS = ("kind", "n_servants", "n", "reserved", "stamp", "next_id", "last_now", "lease_tick", "n_leases", "epoch")
+_INSPECT_IDENTITY = ("stamp", "next_id", "last_now", "lease_tick", "n_leases")
+_INSPECT_RECORD = (("task_id", "<u8"), ("started_at", "<i8"), ("env_id", "<u4"), ("requestor_ip", "<u4"), ("prefetch", "u1"))
+_INSPECT_SERVANT = (("discovered_at", "<i8"), ("ever_assigned", "<u8"))
+
+
+def _inspect_sections(n, n_servants):
+    secs = (("records", [(c, dt, n) for c, dt in _INSPECT_RECORD]), ("servants", [(c, dt, n_servants) for c, dt in _INSPECT_SERVANT]))
+    return [(name, cols, _pad8(sum(np.dtype(dt).itemsize * k for _, dt, k in cols))) for name, cols in secs]
+
+
+def parse_inspect_delta(blob):
+    """The sidecar as a dict: the header's fields under _INSPECT_FIELDS' names, the records' columns under
+    ydc_stream_inspect_tasks' names and the two servant columns. Raises FormatError for anything the
+    three entry points would refuse for the bytes alone."""
+    blob = bytes(blob)
+    _check(len(blob) >= INSPECT_DELTA_HEADER_BYTES, "shorter than a header")
+    f = INSPECT_DELTA_HEADER.unpack_from(blob)
+    magic, version, hbytes, total, csum = f[:5]
+    d = dict(zip(_INSPECT_FIELDS, f[5:15]))
+    directory = f[15:19]
+    _check(magic == INSPECT_DELTA_MAGIC, "not an inspection sidecar (magic)")
+    _check(version == INSPECT_DELTA_VERSION, "unknown format version")
+    _check(hbytes == INSPECT_DELTA_HEADER_BYTES, "header size")
+    _check(total == len(blob) and total % 8 == 0, "total bytes differ from the block's size")
+    _check(d["kind"] in (INSPECT_FULL, INSPECT_DELTA), "unknown kind")
+    _check(d["reserved"] == 0, "a reserved field is set")
+    _check(d["lease_tick"] == 0 or d["lease_tick"] & STAMP, "a tick number whose stamp is 0")
+    _check(d["n"] <= d["n_leases"], "more records than leases")
+    _check(d["kind"] != INSPECT_FULL or d["n"] == d["n_leases"], "a full sidecar whose records are not |L|")
+    _check(d["n_leases"] <= d["next_id"], "more leases than ids handed out")
+    off = INSPECT_DELTA_HEADER_BYTES
+    for k, (name, cols, size) in enumerate(_inspect_sections(d["n"], d["n_servants"])):
+        _check(directory[2 * k] == off and directory[2 * k + 1] == size, "section %s is not where its counts put it" % name)
+        _check(off + size <= len(blob), "section %s reaches past the end" % name)
+        p = off
+        for col, dt, cnt in cols:
+            d[col] = np.frombuffer(blob, dt, cnt, p).copy()
+            p += np.dtype(dt).itemsize * cnt
+        _check(not any(blob[p:off + size]), "padding is not zero")
+        off += size
+    _check(off == len(blob), "bytes behind the last section")
+    _check(checksum(blob) == csum, "checksum")
+    ids = d["task_id"]
+    _check((ids[1:] > ids[:-1]).all(), "ids not ascending")
+    _check((ids < np.uint64(d["next_id"])).all(), "an id >= next_id")
+    _check((d["prefetch"] <= 1).all(), "a prefetch flag that is neither 0 nor 1")
+    return d
+
+
+def inspect_state(full, tasks, servants, epoch):
+    """What build_inspect_delta is given: the identity of the parsed full snapshot `full`, the records of
+    every lease (a dict shaped like binding.Context.stream_inspect_tasks' result), the two servant
+    columns (... stream_inspect_servants') and the inspection epoch."""
+    st = dict(stamp=structure_stamp(full), next_id=int(full["next_id"]), last_now=int(full["last_now"]),
+              lease_tick=int(full["lease_tick"]), n_leases=len(full["l_id"]), epoch=int(epoch))
+    for c, dt in _INSPECT_RECORD:
+        st[c] = np.ascontiguousarray(tasks[c], dt)
+    for c, dt in _INSPECT_SERVANT:
+        st[c] = np.ascontiguousarray(servants[c], dt)
+    _check(np.array_equal(st["task_id"], np.asarray(full["l_id"], np.uint64)), "the records are not L's")
+    return st
+
+
+def build_inspect_delta(state, ids, kind):
+    """The sidecar of `kind` for the stream in `state` (inspect_state()): the records of the leases `ids`
+    (ascending; ignored for INSPECT_FULL, which carries all of L) and the servant columns whole.
+    FormatError where an id is no lease."""
+    all_ids = state["task_id"]
+    ids = all_ids if kind == INSPECT_FULL else np.asarray(ids, np.uint64).reshape(-1)
+    at = np.searchsorted(all_ids, ids)
+    _check(len(ids) == 0 or (at < len(all_ids)).all() and (all_ids[np.minimum(at, len(all_ids) - 1)] == ids).all(),
+           "an id is no lease")
+    cols = {c: state[c][at] for c, _ in _INSPECT_RECORD}
+    cols.update({c: state[c] for c, _ in _INSPECT_SERVANT})
+    n, n_servants = len(ids), len(state["discovered_at"])
+    body, directory, off = [], [], INSPECT_DELTA_HEADER_BYTES
+    for name, sec, size in _inspect_sections(n, n_servants):
+        raw = b"".join(np.ascontiguousarray(cols[c], dt).tobytes() for c, dt, _ in sec)
+        body.append(raw + bytes(size - len(raw)))
+        directory += [off, size]
+        off += size
+    fields = [INSPECT_DELTA_MAGIC, INSPECT_DELTA_VERSION, INSPECT_DELTA_HEADER_BYTES, off, 0, int(kind), n_servants, n, 0,
+              state["stamp"], state["next_id"], state["last_now"], state["lease_tick"], state["n_leases"],
+              state["epoch"]] + directory
+    blob = bytearray(INSPECT_DELTA_HEADER.pack(*fields) + b"".join(body))
+    struct.pack_into("<Q", blob, 8 * CHECKSUM_WORD, checksum(blob))
+    blob = bytes(blob)
+    parse_inspect_delta(blob)
+    return blob
+
+
+def apply_inspect_delta(state, side, delta=None):
+    """The inspect_state() that results. A full sidecar (ydc_stream_inspect_restore) is the state itself;
+    `state` may be None. A delta sidecar (ydc_stream_delta_apply_inspected) needs its delta (bytes or
+    parse_delta's dict): FormatError where the sidecar's identity is not the delta's result, its ids are
+    not the delta's inserted ones, its epoch is not the state's, or the delta's base is not the state."""
+    s = side if isinstance(side, dict) else parse_inspect_delta(side)
+    out = {k: s[k] for k in _INSPECT_IDENTITY + ("epoch",)}
+    for c, _ in _INSPECT_SERVANT:
+        out[c] = s[c].copy()
+    if s["kind"] == INSPECT_FULL:
+        _check(delta is None, "a full sidecar beside a delta")
+        for c, _ in _INSPECT_RECORD:
+            out[c] = s[c].copy()
+        return out
+    _check(delta is not None, "a delta sidecar without its delta")
+    d = delta if isinstance(delta, dict) else parse_delta(delta)
+    _check(tuple(s[k] for k in _INSPECT_IDENTITY) == (d["stamp"], d["next_id"], d["last_now"], d["lease_tick"], d["n_leases"]),
+           "the sidecar's identity is not the delta's result")
+    _check(np.array_equal(s["task_id"], d["ins_id"]), "the sidecar's ids are not the delta's inserted ones")
+    _check(s["epoch"] == state["epoch"], "the inspection epoch differs")
+    _check((state["stamp"], state["next_id"], state["last_now"], state["lease_tick"], state["n_leases"]) ==
+           (d["stamp"], d["base_next_id"], d["base_last_now"], d["base_lease_tick"], d["base_n_leases"]),
+           "the delta's base is not this state")
+    ids = state["task_id"]
+    _check(np.isin(d["era_id"], ids).all() and not np.isin(d["ins_id"], ids).any(), "the delta's ids do not fit the state")
+    _check(len(s["discovered_at"]) == len(state["discovered_at"]), "another number of servants")
+    keep = ~np.isin(ids, d["era_id"])
+    l_id = np.concatenate([ids[keep], s["task_id"]])
+    order = np.argsort(l_id, kind="stable")
+    out["task_id"] = l_id[order]
+    for c, _ in _INSPECT_RECORD[1:]:
+        out[c] = np.concatenate([state[c][keep], s[c]])[order]
+    return out

@@ -296,3 +296,30 @@ def dismiss(ctx, requestors):
         out["leases_freed"], out["n_withdrawn"] = leases, waiting
         return out
     return result
+
+
+def standby_base(primary):
+    """What a standby of the stream on `primary` (inspection on) starts from: -> (base, sidecar), the bytes
+    of binding.Context.stream_delta_base and the full inspection sidecar beside them
+    (binding.Context.stream_delta_inspect). No compute: both are the calls'."""
+    return primary.stream_delta_base(), primary.stream_delta_inspect()
+
+
+def standby_restore(standby, base, sidecar):
+    """The standby's side of standby_base: ydc_stream_restore, then ydc_stream_inspect_restore. Afterwards
+    `standby` answers the snapshot and the inspection calls as the primary did when it took the base."""
+    caps = standby.stream_restore(base)
+    standby.stream_inspect_restore(sidecar)
+    return caps
+
+
+def standby_step(primary, standby=None):
+    """One step of the chain, between two ticks of the primary: -> (delta, sidecar), applied to `standby`
+    where one is given (binding.Context.stream_delta, stream_delta_inspect, stream_delta_apply_inspected).
+    At promotion the standby's host sets quota, withdrawal and departure settings again: they are not
+    state of the stream's."""
+    delta = primary.stream_delta()
+    sidecar = primary.stream_delta_inspect(delta)
+    if standby is not None:
+        standby.stream_delta_apply_inspected(delta, sidecar)
+    return delta, sidecar
