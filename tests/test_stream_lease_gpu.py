@@ -119,9 +119,12 @@ def quiet(ev, **over):
 
 def test_leased_long_lived_lease_is_found_past_its_home_slot():
     """max_leases 512: a table of 1024 slots, up to 40 % full. Leases 0 and 1024 live on while more
-    than 1024 younger ids come and go through the same slots, so ids are filed past their home slot
-    and found there again (every tick's frees look the previous tick's grants up); the two are then
-    renewed, reported, and freed by id."""
+    than 1024 younger ids come and go (every tick's frees look the previous tick's grants up); the
+    two are then renewed, reported, and freed by id. Written for the home slot id & (cap - 1), under
+    which 0 and 1024 collide; under the multiplicative home they do not, and a replay of the rule
+    (tests/lease_table_cases.py: replay_consecutive) files 1598 of these 1600 ids at their home slot
+    and 2 one slot behind it: this is a long-lived pair among short-lived neighbours, not a probe
+    past the home slot. Chains, holes inside them and the wrap: tests/test_lease_table_gpu.py."""
     sv = synth.make_servants(60, n_tasks_hint=2000, n_envs=2, seed=5)
     ls = M.LeaseStream(sv, 200, 0, 0, M.LeaseTable(512), n_envs=2)
     ctx = begin(ls, 512, 200)
