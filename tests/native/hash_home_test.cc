@@ -1,0 +1,31 @@
+// The arithmetic the digest index, the requestor index and the quota table share (index_home.h), printed
+// for tests/test_hash_index_model.py, which compares it with the restatement of tests/hash_index_cases.py.
+// Includes only index_home.h; built with ASan + UBSan and run as a program of its own.
+//
+// stdin, one request per line:  k <key, hex>  ->  <book_index_mix(key), hex>
+//                               s <n, decimal> ->  <book_index_slots(n)> <requestor_index_slots(n)> <quota_slots(n)>
+// "HASH-HOME-OK <lines answered>" ends the output; a line it cannot read ends the program with status 2.
+#include <cinttypes>
+#include <cstdio>
+
+#include "index_home.h"
+
+int main() {
+  char line[128];
+  unsigned long long answered = 0;
+  while (std::fgets(line, sizeof line, stdin)) {
+    uint64_t v = 0;
+    if (std::sscanf(line, "k %" SCNx64, &v) == 1) {
+      std::printf("%016" PRIx64 "\n", ydc::book_index_mix(v));
+    } else if (std::sscanf(line, "s %" SCNu64, &v) == 1 && v <= (1ull << 30)) {
+      std::printf("%u %u %u\n", (unsigned)ydc::book_index_slots((uint32_t)v), (unsigned)ydc::requestor_index_slots(v),
+                  (unsigned)ydc::quota_slots((uint32_t)v));
+    } else {
+      std::fprintf(stderr, "cannot read: %s", line);
+      return 2;
+    }
+    ++answered;
+  }
+  std::printf("HASH-HOME-OK %llu\n", answered);
+  return 0;
+}

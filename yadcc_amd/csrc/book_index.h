@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "index_home.h"
 #include "kernels.h"
 #include "running_book.h"
 #include "stream_tile.h"
@@ -41,7 +42,6 @@
 namespace ydc {
 
 constexpr unsigned long long kBookIndexEmpty = ~0ull;
-constexpr uint32_t kBookIndexMinSlots = 1024;
 constexpr uint32_t kBookNotFound = 0xFFFFFFFFu;  // YDC_BOOK_NOT_FOUND
 
 struct BookIndex {
@@ -59,22 +59,7 @@ struct BookHit {
 };
 static_assert(sizeof(BookHit) == 32, "ydc_book_hit is 32 bytes");
 
-// Slots for a book of n entries.
-inline uint32_t book_index_slots(uint32_t n) {
-  uint32_t s = kBookIndexMinSlots;
-  while (s < 2ull * n) s <<= 1;  // (n <= 2^30: at most 2^31)
-  return s;
-}
-
-// splitmix64's finaliser.
-__host__ __device__ __forceinline__ uint64_t book_index_mix(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
+// (book_index_slots and book_index_mix: index_home.h)
 
 // What the index knows of key k: last1 (0: the key is not in B) and the count.
 __device__ __forceinline__ uint2 book_index_lookup(const BookIndex& ix, unsigned long long k) {

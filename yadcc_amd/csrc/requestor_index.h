@@ -47,6 +47,7 @@
 #include <stdint.h>
 
 #include "book_index.h"
+#include "index_home.h"
 #include "kernels.h"
 #include "lease_table.h"
 #include "stream_inspect.h"
@@ -55,7 +56,6 @@
 
 namespace ydc {
 
-constexpr uint32_t kRequestorMinSlots = 1024;
 constexpr uint32_t kRequestorCols = 5;    // leases | zombies | prefetch_leases | waiting | waiting_rows
 constexpr uint32_t kRequestorRounds = 4;  // distinct keys a wave combines before its lanes go alone
 constexpr uint32_t kRequestorTile = 1024;  // slots per workgroup of the fold (256 x 4)
@@ -75,12 +75,7 @@ struct RequestorLoad {
 };
 static_assert(sizeof(RequestorLoad) == 24, "ydc_requestor_load is 24 bytes");
 
-// Slots for n entries of L and W together.
-inline uint32_t requestor_index_slots(uint64_t n) {
-  uint32_t s = kRequestorMinSlots;
-  while (s < 2 * n && s < (1u << 31)) s <<= 1;
-  return s;
-}
+// (requestor_index_slots: index_home.h)
 
 __device__ __forceinline__ uint32_t requestor_home(const RequestorIndex& ix, uint32_t ip) {
   return (uint32_t)book_index_mix(ip) & ix.mask;

@@ -51,6 +51,7 @@
 #include <stdint.h>
 
 #include "admit_clip.h"
+#include "index_home.h"
 #include "kernels.h"
 #include "lease_table.h"
 #include "requestor_index.h"
@@ -64,14 +65,8 @@ namespace ydc {
 constexpr uint32_t kIdxOverQuota = 0xFFFFFFFBu;   // YDC_IDX_OVER_QUOTA
 constexpr uint32_t kQuotaUnlimited = 0xFFFFFFFFu;  // YDC_QUOTA_UNLIMITED
 constexpr uint32_t kQuotaTile = 256;               // requests per workgroup of the clip pass
-constexpr uint32_t kQuotaMinSlots = 1024;
 
-// Slots of the table of a stream with max_tasks new requests per tick (load <= 1/2).
-inline uint32_t quota_slots(uint32_t max_tasks) {
-  uint32_t s = kQuotaMinSlots;
-  while (s < 2 * (uint64_t)max_tasks && s < (1u << 31)) s <<= 1;
-  return s;
-}
+// (quota_slots: index_home.h)
 
 // HBM: the table keyed by the tick's new requestors. word: requestor_index.h's.
 struct QuotaTable {
