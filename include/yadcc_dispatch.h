@@ -1155,6 +1155,70 @@ int ydc_stream_depart_stage(ydc_context* ctx, const uint32_t* requestor_ip, uint
 int ydc_stream_depart_result(ydc_context* ctx, ydc_depart_count* out, uint32_t cap, uint32_t* out_n,
                              uint32_t* out_leases_freed /* nullable */, uint32_t* out_n_withdrawn /* nullable */);
 
+/* ---- usage: slot-time and wait-time per requestor, kept across ticks --------------------------------
+ * ydc_stream_requestor_find says who holds the cluster now; the quota, the fair-share level and departure
+ * act on that inside the tick. None of them says who has USED the cluster over time: slot-seconds,
+ * zombie-seconds, prefetch-seconds and queueing time per requestor, the figures a shared build farm
+ * reports and charges by. The host could keep them only by keeping the leases and W again. Opt-in, on
+ * the open leased, waiting-and-leased or rpc stream with inspection on; no tick signature changes, a
+ * stream that never calls ydc_stream_usage_begin launches what it launched before, and no answer of a
+ * tick depends on it. The reference has no such call.
+ *   The interval. quantum > 0 is in the ticks' clock unit. For an accepted tick with clock `now`, `last`
+ *     is the clock of the previous accepted tick; if the capability was begun since that tick, the
+ *     clock at the begin call: the stream's last now or, before the stream's first tick, this tick's
+ *     own now. dq = floor(now / quantum) - floor(last / quantum), the division rounding toward minus
+ *     infinity (clocks may be negative), as a uint64 modulo 2^64 (ydc_usage_quanta). The sum of dq over
+ *     ticks telescopes, so nothing drifts. A refused tick accrues nothing; the next accepted one spans
+ *     the whole interval. A tick with dq == 0 changes nothing but `ticks`.
+ *   What is charged, at the head of the tick: L and W as the previous tick left them, before this
+ *     tick's renewals, frees, expiry, reports, withdrawals, departures and removals. Every lease adds dq
+ *     to slot_time of the requestor_ip of its inspection record; to zombie_time too if it is a zombie;
+ *     to prefetch_time too if its prefetch byte is set. A lease granted while inspection was off
+ *     (started_at == YDC_INSPECT_NO_TIME) adds dq to the one counter unattributed_time, never to key
+ *     0xFFFFFFFF. Every entry of W, expired or not, adds dq to wait_time of its requestor and rows x dq
+ *     to wait_row_time, rows = n_immediate + n_prefetch in rpc mode and 1 elsewhere. So a lease granted
+ *     in tick t and freed in tick u is charged exactly floor(now_u / q) - floor(now_t / q). All sums are
+ *     uint64 modulo 2^64. `quanta` is the sum of dq, `ticks` the accepted ticks with the capability on.
+ *   ydc_stream_usage_begin: switches the capability on with room for want_requestors distinct
+ *     requestors (the table has max(1024, the power of two >= 2 want_requestors) slots to begin with
+ *     and grows by itself between ticks, before it could pass half full: no addition is ever dropped;
+ *     a growth that cannot be allocated refuses the tick with YDC_ERR_HIP, nothing applied). Called
+ *     again while it is on: the same quantum only grows the table; another quantum is
+ *     YDC_ERR_INVALID_ARGUMENT. No such stream, inspection off, quantum <= 0: YDC_ERR_INVALID_ARGUMENT.
+ *     ydc_stream_end, a new begin of a stream, ydc_stream_restore and the delta-apply calls switch it
+ *     off; ydc_stream_reserve, the *_begin calls of the other capabilities and ydc_remove_servants keep
+ *     the table (it is keyed by requestor). The snapshot and delta formats do not carry it: a restarted
+ *     scheduler takes ydc_stream_usage_get on the old side and ydc_stream_usage_load on the new.
+ *   ydc_stream_usage_get: every requestor the table holds, IN NO SPECIFIED ORDER, and the totals
+ *     (nullable). *out_n: the rows; more than cap: YDC_ERR_CAPACITY with *out_n set, nothing written and
+ *     nothing reset. flags & YDC_USAGE_RESET: behind the copy the table and the totals are emptied, keys
+ *     included, so the next accrual claims today's holders again (how a long-running scheduler bounds
+ *     the table). totals->slots: the table's slots now.
+ *   ydc_stream_usage_find: out[i] for requestor_ip[i]; a requestor the table does not hold is a row of
+ *     zeros.
+ *   ydc_stream_usage_load: adds the given rows (duplicates add together; a row of zeros still files its
+ *     key) and, if `add` is given, its unattributed_time, quanta and ticks (n_keys and slots are ignored).
+ *   get, find and load change neither L nor W nor any answer of a tick; with the capability off they are
+ *     YDC_ERR_INVALID_ARGUMENT with their outputs untouched.
+ *   ydc_usage_quanta: the interval arithmetic on the host; no context, no device. quantum <= 0 or a NULL
+ *     out: YDC_ERR_INVALID_ARGUMENT. */
+typedef struct ydc_usage_row { /* 48 bytes */
+  uint32_t requestor_ip, pad;
+  uint64_t slot_time, zombie_time, prefetch_time, wait_time, wait_row_time;
+} ydc_usage_row;
+typedef struct ydc_usage_totals {
+  uint64_t unattributed_time, quanta, ticks;
+  uint32_t n_keys, slots;
+} ydc_usage_totals;
+#define YDC_USAGE_RESET 1u
+int ydc_stream_usage_begin(ydc_context* ctx, int64_t quantum, uint32_t want_requestors);
+int ydc_stream_usage_get(ydc_context* ctx, ydc_usage_row* rows, uint32_t cap, uint32_t* out_n,
+                         ydc_usage_totals* totals /* nullable */, uint32_t flags);
+int ydc_stream_usage_find(ydc_context* ctx, const uint32_t* requestor_ip, uint32_t n, ydc_usage_row* out);
+int ydc_stream_usage_load(ydc_context* ctx, const ydc_usage_row* rows, uint32_t n,
+                          const ydc_usage_totals* add /* nullable */);
+int ydc_usage_quanta(int64_t last, int64_t now, int64_t quantum, uint64_t* out);
+
 /* ---- snapshot and restore of an open stream --------------------------------------------
  * Everything an open waiting, leased, waiting-and-leased or rpc stream keeps on the device (L with
  * next_id and the report stamps, W, B, E, running_tasks, the registry's columns, the clock and the

@@ -59,6 +59,7 @@ ABI_SYMBOLS = (
     "ydc_stream_quota_begin", "ydc_stream_quota_set", "ydc_stream_quota_result",
     "ydc_stream_quota_fair", "ydc_stream_quota_fair_result", "ydc_fair_level",
     "ydc_stream_depart_begin", "ydc_stream_depart_stage", "ydc_stream_depart_result",
+    "ydc_stream_usage_begin", "ydc_stream_usage_get", "ydc_stream_usage_find", "ydc_stream_usage_load", "ydc_usage_quanta",
     "ydc_stream_snapshot", "ydc_stream_restore",
     "ydc_stream_delta_base", "ydc_stream_delta", "ydc_stream_delta_apply", "ydc_stream_delta_stop",
     "ydc_stream_delta_inspect", "ydc_stream_inspect_restore", "ydc_stream_delta_apply_inspected",
@@ -162,6 +163,24 @@ class DepartCount(C.Structure):
 
 # numpy view of ydc_depart_count
 DEPART_DTYPE = np.dtype([(k, "<u4") for k, _ in DepartCount._fields_])
+
+
+class UsageRow(C.Structure):
+    """ydc_usage_row (48 bytes)."""
+    _fields_ = ([("requestor_ip", C.c_uint32), ("pad", C.c_uint32)] +
+                [(k, C.c_uint64) for k in ("slot_time", "zombie_time", "prefetch_time", "wait_time", "wait_row_time")])
+
+
+class UsageTotals(C.Structure):
+    """ydc_usage_totals."""
+    _fields_ = ([(k, C.c_uint64) for k in ("unattributed_time", "quanta", "ticks")] +
+                [(k, C.c_uint32) for k in ("n_keys", "slots")])
+
+
+# numpy view of ydc_usage_row
+USAGE_DTYPE = np.dtype([(k, "<u4" if t is C.c_uint32 else "<u8") for k, t in UsageRow._fields_])
+USAGE_COLUMNS = ("slot_time", "zombie_time", "prefetch_time", "wait_time", "wait_row_time")
+USAGE_RESET = 1  # YDC_USAGE_RESET
 
 
 # numpy view of ydc_servant_row (32 bytes)
@@ -339,6 +358,11 @@ def lib():
         L.ydc_stream_depart_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_depart_result.argtypes = [C.c_void_p, C.POINTER(DepartCount), C.c_uint32, C.c_void_p, C.c_void_p,
                                                C.c_void_p]
+        L.ydc_stream_usage_begin.argtypes = [C.c_void_p, C.c_int64, C.c_uint32]
+        L.ydc_stream_usage_get.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ydc_stream_usage_find.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ydc_stream_usage_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ydc_usage_quanta.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64)]
         L.ydc_stream_book_begin.argtypes = [C.c_void_p, C.c_uint32]
         L.ydc_stream_book_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ydc_stream_book_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -444,6 +468,16 @@ def fair_level(held, asked, fixed_cap=None, others=0, pool=0):
     rc = lib().ydc_fair_level(_ptr(h), _ptr(a), _ptr(f), len(h), int(others), int(pool), C.byref(out))
     if rc:
         raise YdcError("ydc_fair_level: %s" % lib().ydc_strerror(rc).decode())
+    return int(out.value)
+
+
+def usage_quanta(last, now, quantum):
+    """The quanta a tick at `now` charges after one at `last` (ydc_usage_quanta; no context, no device):
+    floor(now / quantum) - floor(last / quantum) modulo 2^64."""
+    out = C.c_uint64(0)
+    rc = lib().ydc_usage_quanta(int(last), int(now), int(quantum), C.byref(out))
+    if rc:
+        raise YdcError("ydc_usage_quanta: %s" % lib().ydc_strerror(rc).decode())
     return int(out.value)
 
 
@@ -1553,6 +1587,51 @@ class Context:
                                                    C.byref(n), C.byref(leases), C.byref(waiting)),
                     "ydc_stream_depart_result")
         return out, int(leases.value), int(waiting.value)
+
+    def stream_usage_begin(self, quantum, want_requestors=0):
+        """Switches the usage accounting on for the open leased, waiting-and-leased or rpc stream with
+        inspection on (ydc_stream_usage_begin): every tick charges the leases and waiting requests it
+        finds for the quanta (of `quantum` clock units) since the previous tick. Called again with the
+        same quantum it only grows the table to want_requestors."""
+        q = int(quantum)
+        if not -(1 << 63) <= q < 1 << 63:
+            raise ValueError("quantum %d does not fit int64" % q)
+        self._check(lib().ydc_stream_usage_begin(self._h, q, _depart_count(want_requestors, "want_requestors")),
+                    "ydc_stream_usage_begin")
+
+    def stream_usage_get(self, reset=False):
+        """(rows of USAGE_DTYPE IN NO SPECIFIED ORDER, the totals as a dict) (ydc_stream_usage_get). reset:
+        the table and the totals are emptied behind the copy."""
+        n, tot = C.c_uint32(0), UsageTotals()
+        # (the row count first, without a reset: a table with rows answers YDC_ERR_CAPACITY and *out_n)
+        rc = lib().ydc_stream_usage_get(self._h, None, 0, C.byref(n), C.byref(tot), 0)
+        out = np.zeros(n.value, USAGE_DTYPE)
+        if n.value or (reset and not rc):
+            rc = lib().ydc_stream_usage_get(self._h, out.ctypes.data if n.value else None, len(out), C.byref(n),
+                                            C.byref(tot), USAGE_RESET if reset else 0)
+        self._check(rc, "ydc_stream_usage_get")
+        return out, {k: int(getattr(tot, k)) for k, _ in UsageTotals._fields_}
+
+    def stream_usage_find(self, requestors):
+        """Rows of USAGE_DTYPE, one per queried requestor in the queried order; a requestor the table does
+        not hold is a row of zeros (ydc_stream_usage_find)."""
+        r = _depart_keys(requestors)
+        out = np.zeros(len(r), USAGE_DTYPE)
+        self._check(lib().ydc_stream_usage_find(self._h, _ptr(r) if len(r) else None, len(r),
+                                                out.ctypes.data if len(r) else None), "ydc_stream_usage_find")
+        return out
+
+    def stream_usage_load(self, rows, totals=None):
+        """Adds rows of USAGE_DTYPE to the table, duplicates together, and what `totals` (a dict with
+        unattributed_time, quanta, ticks) names to the totals (ydc_stream_usage_load)."""
+        a = np.ascontiguousarray(rows, dtype=USAGE_DTYPE)
+        tot = None
+        if totals is not None:
+            tot = UsageTotals()
+            for k in ("unattributed_time", "quanta", "ticks"):
+                setattr(tot, k, int(totals.get(k, 0)) & ((1 << 64) - 1))
+        self._check(lib().ydc_stream_usage_load(self._h, a.ctypes.data if len(a) else None, len(a),
+                                                C.byref(tot) if tot is not None else None), "ydc_stream_usage_load")
 
     def stream_leases(self):
         """Snapshot of the lease table in id order (ydc_stream_leases_get): (task_ids uint64,

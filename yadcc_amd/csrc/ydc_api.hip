@@ -52,8 +52,10 @@
 #include "stream_depart.h"
 #include "stream_fair.h"
 #include "stream_quota.h"
+#include "stream_usage.h"
 #include "stream_withdraw.h"
 #include "tick_kernel.h"
+#include "usage_quanta.h"
 
 using namespace ydc;
 
@@ -637,6 +639,32 @@ struct ydc_context {
       // 0: off; otherwise max_overrides + 1 (what stream_alloc and stream_regrow are told).
       uint32_t code() const { return on ? max_overrides + 1 : 0; }
     } quota;
+    // Usage per requestor (ydc_stream_usage_begin; stream_usage.h): the persistent table and its totals in
+    // HBM, and a page-locked block of its own (the tick's dq | the result), so that no section of the
+    // arena moves. !on: none of this exists, and the step launches what it launches without it. Keyed by
+    // requestor and sized by its own keys, not by the stream's bounds: it moves to a grown stream as it is.
+    struct Usage {
+      bool on = false;
+      int64_t quantum = 0;
+      bool has_last = false;  // `last` is a clock (the begin call found a tick behind it, or a tick has run since)
+      int64_t last = 0;
+      DevBuf<uint8_t> d;  // word | the five sums
+      DevBuf<UsageState> st;
+      UsageTable tb{};
+      PinnedBuf h;  // page-locked: dq | UsageDone
+      unsigned long long *h_dq = nullptr, *z_dq = nullptr;
+      UsageDone *h_done = nullptr, *z_done = nullptr;
+      // The bound that errs high on the distinct keys the next accrual can meet: n_keys (exact: the
+      // device's after the last tick, load or reset) + fresh (the keys L and W can have gained since an
+      // accrual last claimed theirs: it adds up over ticks with dq == 0, which claim nothing; usage_bound).
+      uint32_t n_keys = 0;
+      uint64_t fresh = 0;
+      // The read calls' and load's scratch.
+      DevBuf<uint32_t> q;
+      DevBuf<UsageRow> rows;
+      DevBuf<uint8_t> fold;  // the fold's state and look-back words
+      uint32_t slots() const { return on ? tb.mask + 1 : 0; }
+    } usage;
     // ydc_stream_outlook_get (stream_outlook.h): scratch only, reserved at the first call and
     // released with the stream; nothing of it is state, so reserve / restore carry nothing over.
     struct Outlook {
@@ -4598,6 +4626,19 @@ void enqueue_lease_pre(ydc_context* c, const TickArena& a) {
   const LeaseIn in = lease_in(a);
   const uint32_t S = c->reg.n;
   const uint32_t ren_blocks = ceil_div(k.max_renewals, 256), rep_blocks = ceil_div(k.max_reports, 256);
+  // With usage: L and W as the previous tick left them charged for the quanta since then, before anything
+  // below changes them (stream_usage.h). Here for the reason the book's pass is here: once per tick on
+  // every path.
+  if (sm.usage.on) {
+    const auto& u = sm.usage;
+    const bool rpc = sm.rpc(), with_w = sm.waiting();
+    const uint32_t l_blocks = ceil_div(sm.lt.mask + 1, kLeaseTile);
+    const uint32_t w_blocks = with_w ? std::min(ceil_div(k.max_waiting, 256), kUsageWaitBlocks) : 0;
+    YDC_LAUNCH(c, "k_usage_accrue", k_usage_accrue, dim3(l_blocks + w_blocks), dim3(256), 0, c->stream, sm.lt,
+               sm.d_insp_rec.p, sm.d_insp_pre.p, l_blocks, with_w ? (rpc ? sm.rw.ip : sm.wq.ip) : nullptr,
+               rpc ? sm.rw.n_imm : nullptr, rpc ? sm.rw.n_pre : nullptr, sm.ws, k.max_waiting, u.tb, u.z_dq, a.lh, u.z_done,
+               c->opt_requestor_combine ? 1u : 0u);
+  }
   // With aliveness: the heartbeats' expiries into E (servant_alive.h). Here for the reason the book's
   // pass is here: once per tick on every path.
   if (sm.alive.on && k.max_updates)
@@ -5393,6 +5434,7 @@ int stream_regrow(ydc_context* c, const ydc_stream_caps& k, uint32_t max_book, u
   grown.quota.host = std::move(sm.quota.host);        // (the settings and the last result go along)
   grown.quota.host.dirty = true;                      // (... and the new device copy has to follow them)
   grown.quota.host.table_dirty = false;
+  grown.usage = std::move(sm.usage);  // (keyed by requestor: the table, its totals and its clock go along)
   std::swap(sm, grown);
   stream_release(grown);  // (the old buffers and the old captures; sm.stale: the step is captured again)
   return YDC_OK;
@@ -6083,6 +6125,7 @@ int ydc_stream_inspect_load(ydc_context* c, const uint64_t* task_id, const int64
              sm.lt.mask + 1, d_at.p, d_env.p, d_ip.p, d_pre.p, sm.d_insp_rec.p, sm.d_insp_pre.p);
   HIP_TRY(c, hipGetLastError());
   ++sm.inspect.epoch;
+  if (sm.usage.on) sm.usage.fresh += n;  // (the filed records may name requestors its table has not met)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return YDC_OK;
 }
@@ -6964,6 +7007,200 @@ static int stream_tick_expiry(ydc_context* c, StreamCall& t, TickState* ts) {
   return YDC_OK;
 }
 
+// ---- usage per requestor (stream_usage.h) ----
+
+static size_t usage_table_bytes(uint32_t slots) { return (size_t)slots * 8 * (1 + kUsageCols); }
+
+// The table over a buffer of `slots` slots: word | the five sums.
+static UsageTable usage_table_at(uint8_t* b, uint32_t slots, UsageState* st) {
+  return UsageTable{(unsigned long long*)b, (unsigned long long*)(b + (size_t)slots * 8), st, slots - 1};
+}
+
+// What the next accrual can meet in L and W that the table may not hold yet, when nothing narrower is known.
+static uint64_t usage_holders(const ydc_context::Stream& sm) {
+  return (uint64_t)sm.n_leases + (sm.waiting() ? sm.n_waiting : 0u);
+}
+
+// The bound that errs high on the distinct keys the table can hold after the next accrual: the keys it
+// has, plus those L and W can have gained since they were last claimed, which are no more than L and W hold.
+static uint64_t usage_bound(const ydc_context::Stream& sm) {
+  return (uint64_t)sm.usage.n_keys + std::min<uint64_t>(sm.usage.fresh, usage_holders(sm));
+}
+
+// Room for `keys` distinct requestors at a load of 1/2 at the most. A table that has to grow is filed
+// again into a larger one (k_usage_rehash), all or nothing, and the step is captured again: it holds
+// the table's addresses. The stream is brought to rest first.
+static int usage_fit(ydc_context* c, uint64_t keys) {
+  auto& sm = c->stream_mode;
+  auto& u = sm.usage;
+  const uint32_t want = usage_slots(keys);
+  if (want <= u.slots()) return YDC_OK;
+  if (2 * keys > want) return fail(c, YDC_ERR_CAPACITY, "usage: %llu requestors > 2^30", (unsigned long long)keys);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevBuf<uint8_t> bigger;
+  HIP_TRY(c, bigger.reserve(usage_table_bytes(want)));
+  HIP_TRY(c, hipMemsetAsync(bigger.p, 0, usage_table_bytes(want), c->stream));
+  HIP_TRY(c, hipMemsetAsync(&u.st.p->n_keys, 0, 4, c->stream));  // (the claims count the keys again)
+  const UsageTable grown = usage_table_at(bigger.p, want, u.st.p);
+  YDC_LAUNCH(c, "k_usage_rehash", k_usage_rehash, dim3(ceil_div(u.slots(), 256)), dim3(256), 0, c->stream, u.tb, grown);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  UsageState s{};
+  HIP_TRY(c, hipMemcpy(&s, u.st.p, sizeof s, hipMemcpyDeviceToHost));
+  if (s.n_keys != u.n_keys || s.dropped)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "usage: %u of %u requestors filed again (%u dropped)", s.n_keys, u.n_keys, s.dropped);
+  u.d = std::move(bigger);
+  u.tb = grown;
+  sm.stale = true;
+  return YDC_OK;
+}
+
+static int usage_enter(ydc_context* c, const char* who) {
+  const auto& sm = c->stream_mode;
+  if (!sm.active || !sm.usage.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the stream keeps no usage (ydc_stream_usage_begin)", who);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return YDC_OK;
+}
+
+int ydc_stream_usage_begin(ydc_context* c, int64_t quantum, uint32_t want_requestors) {
+  if (!c || quantum <= 0) return YDC_ERR_INVALID_ARGUMENT;
+  auto& sm = c->stream_mode;
+  if (!sm.active || !sm.leased())
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_begin: no leased, waiting-and-leased or rpc stream is open");
+  if (!sm.inspect.on)
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_begin: inspection is off, so no lease says whose it is "
+                "(ydc_stream_inspect_begin)");
+  if (want_requestors > (1u << 30))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "want_requestors %u out of range (0 .. 2^30)", want_requestors);
+  HIP_TRY(c, hipSetDevice(c->device));
+  auto& u = sm.usage;
+  if (u.on) {
+    if (quantum != u.quantum)
+      return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_begin: quantum %lld, the capability is on with %lld",
+                  (long long)quantum, (long long)u.quantum);
+    return usage_fit(c, want_requestors);
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  ydc_context::Stream::Usage n;
+  const uint32_t slots = usage_slots(want_requestors);
+  HIP_TRY(c, n.d.reserve(usage_table_bytes(slots)));
+  HIP_TRY(c, n.st.reserve(1));
+  HIP_TRY(c, n.h.reserve(64 + sizeof(UsageDone)));
+  HIP_TRY(c, hipMemset(n.d.p, 0, usage_table_bytes(slots)));
+  HIP_TRY(c, hipMemset(n.st.p, 0, sizeof(UsageState)));
+  std::memset(n.h.p, 0, 64 + sizeof(UsageDone));
+  n.tb = usage_table_at(n.d.p, slots, n.st.p);
+  n.h_dq = (unsigned long long*)n.h.p;
+  n.z_dq = (unsigned long long*)n.h.z;
+  n.h_done = (UsageDone*)(n.h.p + 64);
+  n.z_done = (UsageDone*)(n.h.z + 64);
+  n.quantum = quantum;
+  // The clock at this call: the stream's last now; before its first tick, that tick's own.
+  n.has_last = sm.last_now != INT64_MIN;
+  n.last = n.has_last ? sm.last_now : 0;
+  n.fresh = usage_holders(sm);
+  n.on = true;
+  u = std::move(n);
+  sm.stale = true;  // (the step gains a launch)
+  return YDC_OK;
+}
+
+int ydc_stream_usage_get(ydc_context* c, ydc_usage_row* rows, uint32_t cap, uint32_t* out_n, ydc_usage_totals* totals,
+                         uint32_t flags) {
+  if (!c || !out_n) return YDC_ERR_INVALID_ARGUMENT;
+  static_assert(sizeof(ydc_usage_row) == sizeof(UsageRow), "ydc_usage_row");
+  if (flags & ~YDC_USAGE_RESET) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_get: flags %#x", flags);
+  if (int rc = usage_enter(c, "ydc_stream_usage_get")) return rc;
+  auto& sm = c->stream_mode;
+  auto& u = sm.usage;
+  UsageState s{};
+  HIP_TRY(c, hipMemcpy(&s, u.st.p, sizeof s, hipMemcpyDeviceToHost));
+  const uint32_t m = s.n_keys;
+  if (m > u.slots()) return fail(c, YDC_ERR_NOT_CONVERGED, "usage: %u requestors in %u slots", m, u.slots());
+  if (m > cap) {
+    *out_n = m;
+    return fail(c, YDC_ERR_CAPACITY, "%u requestors > cap %u", m, cap);
+  }
+  if (m && !rows) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_get: %u rows without their column", m);
+  if (m) {
+    const uint32_t tiles = ceil_div(u.slots(), kUsageTile);
+    size_t off = 0;
+    const size_t o_state = section(&off, sizeof(UsageFoldState)), o_lb = section(&off, (size_t)tiles * 8);
+    HIP_TRY(c, u.fold.reserve(off));
+    HIP_TRY(c, u.rows.reserve(m));
+    uint8_t* const b = u.fold.p;
+    UsageFoldState* const fs = (UsageFoldState*)(b + o_state);
+    HIP_TRY(c, hipMemsetAsync(b, 0, off, c->stream));
+    YDC_LAUNCH(c, "k_usage_fold", k_usage_fold, dim3(tiles), dim3(256), 0, c->stream, u.tb, fs,
+               (unsigned long long*)(b + o_lb), u.rows.p, m);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint32_t got = 0;
+    HIP_TRY(c, hipMemcpy(&got, &fs->n_rows, 4, hipMemcpyDeviceToHost));
+    if (got != m) return fail(c, YDC_ERR_NOT_CONVERGED, "usage: %u rows folded, %u requestors", got, m);
+    HIP_TRY(c, hipMemcpy(rows, u.rows.p, (size_t)m * sizeof(UsageRow), hipMemcpyDeviceToHost));
+  }
+  *out_n = m;
+  if (totals) *totals = ydc_usage_totals{s.unattributed, s.quanta, s.ticks, m, u.slots()};
+  if (flags & YDC_USAGE_RESET) {  // (keys included: the next accrual claims today's holders again)
+    HIP_TRY(c, hipMemset(u.d.p, 0, usage_table_bytes(u.slots())));
+    HIP_TRY(c, hipMemset(u.st.p, 0, sizeof(UsageState)));
+    u.n_keys = 0;
+    u.fresh = usage_holders(sm);
+  }
+  return YDC_OK;
+}
+
+int ydc_stream_usage_find(ydc_context* c, const uint32_t* requestor_ip, uint32_t n, ydc_usage_row* out) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (n > (1u << 24)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_find: %u queries > 2^24 in one call", n);
+  if (n && (!requestor_ip || !out))
+    return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_find: %u queries without their columns", n);
+  if (int rc = usage_enter(c, "ydc_stream_usage_find")) return rc;
+  if (!n) return YDC_OK;
+  auto& u = c->stream_mode.usage;
+  HIP_TRY(c, u.q.reserve(n));
+  HIP_TRY(c, u.rows.reserve(n));
+  HIP_TRY(c, hipMemcpyAsync(u.q.p, requestor_ip, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  YDC_LAUNCH(c, "k_usage_find", k_usage_find, dim3(ceil_div(n, 256)), dim3(256), 0, c->stream, u.q.p, n, u.tb, u.rows.p);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(out, u.rows.p, (size_t)n * sizeof(UsageRow), hipMemcpyDeviceToHost));
+  return YDC_OK;
+}
+
+int ydc_stream_usage_load(ydc_context* c, const ydc_usage_row* rows, uint32_t n, const ydc_usage_totals* add) {
+  if (!c) return YDC_ERR_INVALID_ARGUMENT;
+  if (n > (1u << 24)) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_load: %u rows > 2^24 in one call", n);
+  if (n && !rows) return fail(c, YDC_ERR_INVALID_ARGUMENT, "ydc_stream_usage_load: %u rows without their column", n);
+  if (int rc = usage_enter(c, "ydc_stream_usage_load")) return rc;
+  if (!n && !add) return YDC_OK;
+  auto& u = c->stream_mode.usage;
+  // (every row may be a new key, and the next accrual's bound holds behind them)
+  if (int rc = usage_fit(c, usage_bound(c->stream_mode) + n)) return rc;
+  HIP_TRY(c, u.rows.reserve(std::max(n, 1u)));
+  if (n) HIP_TRY(c, hipMemcpyAsync(u.rows.p, rows, (size_t)n * sizeof(UsageRow), hipMemcpyHostToDevice, c->stream));
+  YDC_LAUNCH(c, "k_usage_load", k_usage_load, dim3(ceil_div(std::max(n, 1u), 256)), dim3(256), 0, c->stream, u.rows.p, n, u.tb,
+             (unsigned long long)(add ? add->unattributed_time : 0), (unsigned long long)(add ? add->quanta : 0),
+             (unsigned long long)(add ? add->ticks : 0));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  UsageState s{};
+  HIP_TRY(c, hipMemcpy(&s, u.st.p, sizeof s, hipMemcpyDeviceToHost));
+  if (s.dropped || s.n_keys > u.slots() / 2)
+    return fail(c, YDC_ERR_NOT_CONVERGED, "usage: %u requestors in %u slots, %u additions dropped", s.n_keys, u.slots(), s.dropped);
+  u.n_keys = s.n_keys;
+  return YDC_OK;
+}
+
+int ydc_usage_quanta(int64_t last, int64_t now, int64_t quantum, uint64_t* out) {
+  if (quantum <= 0 || !out) return YDC_ERR_INVALID_ARGUMENT;
+  *out = usage_quanta(last, now, quantum);
+  return YDC_OK;
+}
+
 // With withdrawal: the staged tags into the arena, sorted and without duplicates (the kernels search the
 // list), each staged tag's place in that list kept for ydc_stream_withdraw_result; the staging consumed.
 static void stream_withdraw_stage_tick(ydc_context::Stream& sm) {
@@ -7093,6 +7330,12 @@ static void stream_tick_stage(ydc_context* c, const StreamCall& t, const TickSta
   if (sm.max_withdraw) stream_withdraw_stage_tick(sm);
   if (sm.max_depart) stream_depart_stage_tick(sm);
   if (sm.quota.on) *h.q_n = n_tasks;
+  if (sm.usage.on && lt) {  // (the quanta since the previous accepted tick: the accrual's one word)
+    auto& u = sm.usage;
+    *u.h_dq = u.has_last ? usage_quanta(u.last, lt->now, u.quantum) : 0;
+    u.last = lt->now;
+    u.has_last = true;
+  }
   if (t.rt) {
     put(h.nimm, t.rt->n_imm, n_tasks, 4);
     put(h.npre, t.rt->n_pre, n_tasks, 4);
@@ -7216,6 +7459,18 @@ static int stream_tick_finish(ydc_context* c, const StreamCall& t, const TickSta
                   dd.tick_no, d.n_unique, sm.lease_tick);
     std::copy_n(sm.depart.h_count, d.n_unique, d.counts.begin());
   }
+  if (sm.usage.on) {  // (the accrual's last workgroup has stored the totals)
+    auto& u = sm.usage;
+    const UsageDone& d = *u.h_done;
+    if (d.tick_no != sm.lease_tick)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "usage: result of tick %u (expected %u)", d.tick_no, sm.lease_tick);
+    u.n_keys = d.n_keys;
+    // What L and W gained in this tick came with its new requests. A tick that claimed nothing (dq == 0)
+    // has left the keys of the ticks before it unclaimed: their allowance stays and this tick's joins it.
+    u.fresh = (*u.h_dq ? 0 : u.fresh) + n_tasks;
+    if (d.dropped || d.n_keys > u.slots() / 2)
+      return fail(c, YDC_ERR_NOT_CONVERGED, "usage: %u keys in %u slots, %u additions dropped", d.n_keys, u.slots(), d.dropped);
+  }
   uint32_t n_refused = 0;
   if (sm.quota.on) {  // (the label pass has stored what the clip admitted)
     auto& q = sm.quota;
@@ -7260,6 +7515,8 @@ static int stream_tick(ydc_context* c, StreamCall t) {
   TickState ts{c};
   if (int rc = stream_tick_check(c, t, &ts)) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
+  if (sm.usage.on)  // (in front of everything the tick applies: a table that cannot grow refuses it)
+    if (int rc = usage_fit(c, usage_bound(sm))) return rc;
   if (int rc = stream_tick_heartbeats(c, t, &ts)) return rc;
   if (sm.alive.on)
     if (int rc = stream_tick_expiry(c, t, &ts)) return rc;
@@ -8043,7 +8300,11 @@ int stream_delta_apply(ydc_context* c, const char* what, const delta::View& v, c
     sm.d_rep_tick = std::move(bigger);
     sm.stale = true;
   }
-  // From here on the context is written. L first.
+  // From here on the context is written. Usage goes off (a standby does not accrue: stream_usage.h); L first.
+  if (sm.usage.on) {
+    sm.usage = ydc_context::Stream::Usage{};
+    sm.stale = true;
+  }
   if (ne + nu) {
     YDC_LAUNCH(c, "k_lease_delta_apply_old", k_lease_delta_apply_old, dim3(ceil_div((uint32_t)(ne + nu), 256)), dim3(256), 0,
                st, sm.lt, sm.ls, era, (uint32_t)ne, upd, (uint32_t)nu);
@@ -8330,6 +8591,7 @@ int ydc_stream_inspect_restore(ydc_context* c, const void* side, size_t bytes) {
     return fail(c, YDC_ERR_INVALID_ARGUMENT, "%s: the inspection columns hold %zu rows, %u servants", who, sm.inspect.disc.cap, S);
   }
   // From here on the context is written.
+  if (sm.usage.on) sm.usage.fresh += n;  // (the records may name requestors its table has not met)
   if (fresh) {
     sm.inspect.disc = std::move(disc);
     sm.inspect.ever = std::move(ever);

@@ -298,6 +298,16 @@ def dismiss(ctx, requestors):
     return result
 
 
+def usage(ctx, reset=False):
+    """Who has used the cluster since the accounting began or was last reset
+    (binding.Context.stream_usage_get): -> (rows of binding.USAGE_DTYPE sorted by requestor_ip, the totals
+    as a dict: unattributed_time, quanta, ticks, n_keys, slots). Times are in quanta of the clock unit
+    given to stream_usage_begin. reset: the periodic export of a long-running scheduler, which empties
+    the table behind the copy. No compute beyond the sort: every number is the call's."""
+    rows, totals = ctx.stream_usage_get(reset=reset)
+    return rows[np.argsort(rows["requestor_ip"], kind="stable")], totals
+
+
 def standby_base(primary):
     """What a standby of the stream on `primary` (inspection on) starts from: -> (base, sidecar), the bytes
     of binding.Context.stream_delta_base and the full inspection sidecar beside them
