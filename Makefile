@@ -99,11 +99,12 @@ tests/native/usage_quanta_test: tests/native/usage_quanta_test.cc $(CSRC)/usage_
 usagequanta: tests/native/usage_quanta_test
 	tests/native/usage_quanta_test
 # The home slot and the slot counts of the three hashed tables (index_home.h), printed for the restatement of
-# tests/hash_index_cases.py, ASan + UBSan, no GPU (tests/test_hash_index_model.py builds and runs the same program).
+# tests/hash_index_cases.py, ASan + UBSan, no GPU (tests/test_hash_index_model.py and tests/test_usage_table_model.py
+# build and run the same program).
 tests/native/hash_home_test: tests/native/hash_home_test.cc $(CSRC)/index_home.h
 	g++ -O1 -g -std=c++17 -Wall -Werror -fsanitize=address,undefined -fno-sanitize-recover=undefined -I$(CSRC) -o $@ tests/native/hash_home_test.cc
 hashhome: tests/native/hash_home_test
-	printf 'k 0\nk 9e3779b97f4a7c15\ns 512\ns 513\n' | tests/native/hash_home_test
+	printf 'k 0\nk 9e3779b97f4a7c15\ns 512\ns 513\nu 512\nu 513\n' | tests/native/hash_home_test
 clean:
 	rm -f yadcc_amd/libydc.so tests/model/libmodel.so tests/native/lane_rule_test tests/native/admit_clip_test tests/native/occupancy_plan_test tests/native/lease_filter_test tests/native/fair_level_test tests/native/hash_home_test tests/native/usage_quanta_test
 	$(MAKE) -C tests/native clean

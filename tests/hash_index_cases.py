@@ -98,6 +98,11 @@ def slots_quota(max_tasks):
     return _slots(max_tasks, 1 << 31)
 
 
+def slots_usage(n):
+    """usage_slots: n distinct requestors of the usage table (stream_usage.h)."""
+    return _slots(n, 1 << 31)
+
+
 def bits_of(slots):
     assert slots >= FLOOR and slots & (slots - 1) == 0
     return slots.bit_length() - 1

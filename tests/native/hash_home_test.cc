@@ -1,9 +1,11 @@
-// The arithmetic the digest index, the requestor index and the quota table share (index_home.h), printed
-// for tests/test_hash_index_model.py, which compares it with the restatement of tests/hash_index_cases.py.
+// The arithmetic the digest index, the requestor index, the quota table and the usage table share
+// (index_home.h), printed for tests/test_hash_index_model.py and tests/test_usage_table_model.py, which
+// compare it with the restatement of tests/hash_index_cases.py.
 // Includes only index_home.h; built with ASan + UBSan and run as a program of its own.
 //
 // stdin, one request per line:  k <key, hex>  ->  <book_index_mix(key), hex>
 //                               s <n, decimal> ->  <book_index_slots(n)> <requestor_index_slots(n)> <quota_slots(n)>
+//                               u <n, decimal> ->  <usage_slots(n)>          (n up to 2^32)
 // "HASH-HOME-OK <lines answered>" ends the output; a line it cannot read ends the program with status 2.
 #include <cinttypes>
 #include <cstdio>
@@ -20,6 +22,8 @@ int main() {
     } else if (std::sscanf(line, "s %" SCNu64, &v) == 1 && v <= (1ull << 30)) {
       std::printf("%u %u %u\n", (unsigned)ydc::book_index_slots((uint32_t)v), (unsigned)ydc::requestor_index_slots(v),
                   (unsigned)ydc::quota_slots((uint32_t)v));
+    } else if (std::sscanf(line, "u %" SCNu64, &v) == 1 && v <= (1ull << 32)) {
+      std::printf("%u\n", (unsigned)ydc::usage_slots(v));
     } else {
       std::fprintf(stderr, "cannot read: %s", line);
       return 2;

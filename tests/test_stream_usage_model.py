@@ -161,6 +161,6 @@ def test_constants_and_layout_against_the_header():
     tot = re.search(r"typedef struct ydc_usage_totals \{[^}]*\} ydc_usage_totals;", text).group(0)
     assert re.findall(r"\b(unattributed_time|quanta|ticks|n_keys|slots)\b", tot) == ["unattributed_time", "quanta", "ticks",
                                                                                       "n_keys", "slots"]
-    src = open(os.path.join(ROOT, "yadcc_amd", "csrc", "stream_usage.h")).read()
+    src = open(os.path.join(ROOT, "yadcc_amd", "csrc", "index_home.h")).read()  # (the slot functions' common place)
     assert re.search(r"kUsageMinSlots = (\d+)", src).group(1) == str(U.MIN_SLOTS)
     assert [U.slots_for(n) for n in (0, 1, 512, 513, 1024, 1025, 3001)] == [1024, 1024, 1024, 2048, 2048, 4096, 8192]

@@ -58,16 +58,9 @@
 namespace ydc {
 
 constexpr uint32_t kUsageCols = 5;  // slot_time | zombie_time | prefetch_time | wait_time | wait_row_time
-constexpr uint32_t kUsageMinSlots = 1024;
 constexpr uint32_t kUsageTile = 1024;      // slots per workgroup of the fold (256 x 4)
 constexpr uint32_t kUsageWaitBlocks = 64;  // workgroups of the accrual's stride part at the most
-
-// Slots for n distinct requestors (load <= 1/2).
-inline uint32_t usage_slots(uint64_t n) {
-  uint32_t s = kUsageMinSlots;
-  while (s < 2 * n && s < (1u << 31)) s <<= 1;
-  return s;
-}
+// (kUsageMinSlots and usage_slots: index_home.h)
 
 struct UsageState {
   unsigned long long unattributed, quanta, ticks;
