@@ -12,7 +12,25 @@
 
 #include "index_home.h"
 
+// The four tables' slot counts are one function. The digest index once had a loop of its own, without the
+// 2^31 ceiling; over its documented range, n <= 2^30, that loop and the shared one agree.
+static bool book_slots_agree() {
+  for (uint32_t k = 0; k <= 30; ++k)
+    for (int64_t d = -2; d <= 2; ++d) {
+      const int64_t n = (int64_t(1) << k) + d;
+      if (n < 0 || n > (int64_t(1) << 30)) continue;
+      uint32_t s = 1024;
+      while (s < 2ull * (uint64_t)n) s <<= 1;
+      if (ydc::book_index_slots((uint32_t)n) != s || ydc::index_slots((uint64_t)n) != s) return false;
+    }
+  return ydc::kIndexMinSlots == 1024 && ydc::index_slots(0) == 1024 && ydc::index_slots(1ull << 32) == (1u << 31);
+}
+
 int main() {
+  if (!book_slots_agree()) {
+    std::fprintf(stderr, "book_index_slots differs from its former loop\n");
+    return 3;
+  }
   char line[128];
   unsigned long long answered = 0;
   while (std::fgets(line, sizeof line, stdin)) {

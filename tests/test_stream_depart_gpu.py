@@ -351,6 +351,28 @@ def test_waiting_queue_sizes(mode, sizes, device=True):
     rig.close()
 
 
+@pytest.mark.parametrize("d", [1, 4, 5, 64])
+@pytest.mark.parametrize("mode", ["wl", "rpc"])
+def test_one_wave_of_waiting_entries_of_d_requestors(mode, d, device=True):
+    """|W| == 64, one wave of the mark pass, its entries dealt round to d requestors that all depart: one
+    key, as many as a wave combines (4), one more (the lanes of the fifth add for themselves), and a key
+    for every lane. In rpc mode the entries have 1 ... 5 rows, so the two sums differ."""
+    rig = Rig(mode, tiny_pool(1, 1), 80, mw=80, max_leases=1 << 10, max_depart=64, device=device)
+    rig.tick(rig.event(one(B)))  # (the only slot is taken)
+    k = np.arange(64)
+    ips = (0x0C000000 + k % d).astype(np.uint32)
+    reqs = [(int(ips[i]), 1 + (i % 5) // 2, (i % 5) - (i % 5) // 2) if mode == "rpc" else (int(ips[i]), 1, 0) for i in range(64)]
+    rig.tick(rig.event(reqs), snapshot=False)
+    assert len(rig.ws.state.q) == 64
+    staged = np.unique(ips)[::-1].copy()
+    r = rig.tick(rig.event(), stage=staged)
+    rows, n_l, n_w = rows_of(rig)
+    per_row = 1 + k % 5 if mode == "rpc" else np.ones(64, np.int64)
+    assert rows == [(int(ip), 0, 0, int((ips == ip).sum()), int(per_row[ips == ip].sum())) for ip in staged]
+    assert (n_l, n_w) == (0, 64) and r["n_waiting"] == 0
+    rig.close()
+
+
 # ---- the staged list -------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("mode", ["wl", "leased"])

@@ -318,6 +318,20 @@ def test_one_asker_owns_every_request_of_a_tick():
     rig.close()
 
 
+@pytest.mark.parametrize("d,level", [(1, 40), (4, 10), (5, 8), (64, 0)])
+def test_one_wave_of_requests_of_d_askers(d, level):
+    """64 requests, one wave of the pass that sums the wants, dealt round to d askers that hold nothing: one
+    key, as many as a wave combines (4), one more (the lanes of the fifth add for themselves), and a key for
+    every lane. A pool of 40 rows: the level is where sum min(a_r, level) <= 40 last holds."""
+    rig = Rig("wl", TQ.tiny_pool(8, 1200), 128, 64, max_leases=1 << 14)
+    rig.fair(FIX, 40, 0)
+    r = rig.tick(rig.event([(0x0B000000 + i % d, 1, 0) for i in range(64)], wait=0), snapshot=False)
+    f = r["fair"]
+    assert (f["n_askers"], f["asked_rows"], f["held_total"], f["level"]) == (d, 64, 0, level), f
+    assert int((r["label"] == OQ).sum()) == 64 - sum(min(len(range(j, 64, d)), level) for j in range(d))
+    rig.close()
+
+
 # ---- the totals: L, W, the registry ---------------------------------------------------------------------
 
 def test_a_large_lease_table_with_a_hot_requestor_and_erased_leases():

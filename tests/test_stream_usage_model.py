@@ -162,5 +162,6 @@ def test_constants_and_layout_against_the_header():
     assert re.findall(r"\b(unattributed_time|quanta|ticks|n_keys|slots)\b", tot) == ["unattributed_time", "quanta", "ticks",
                                                                                       "n_keys", "slots"]
     src = open(os.path.join(ROOT, "yadcc_amd", "csrc", "index_home.h")).read()  # (the slot functions' common place)
-    assert re.search(r"kUsageMinSlots = (\d+)", src).group(1) == str(U.MIN_SLOTS)
+    assert re.search(r"kIndexMinSlots = (\d+)", src).group(1) == str(U.MIN_SLOTS)  # (one minimum for the four tables)
+    assert re.search(r"uint32_t usage_slots\(uint64_t n\) \{ return index_slots\(n\); \}", src)
     assert [U.slots_for(n) for n in (0, 1, 512, 513, 1024, 1025, 3001)] == [1024, 1024, 1024, 2048, 2048, 4096, 8192]

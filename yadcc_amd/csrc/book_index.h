@@ -20,16 +20,16 @@
 // incremental index would have to be rewritten as a whole anyway, and inside the tick.
 //
 //   k_book_index_build   thread per entry of B, the table cleared by the host in front of it. A slot
-//                        is claimed and its key published by ONE 64-bit compare-and-swap; whoever
-//                        finds the slot free or already holding its key adds itself with atomicMax /
-//                        atomicAdd. No thread ever waits for another's store (the lanes of a wave run
-//                        in lockstep: a claim-then-publish protocol with a spin hangs them).
+//                        is claimed and its key published by slot_claim (slot_probe.h: ONE 64-bit
+//                        compare-and-swap, no thread ever waits for another's store); whoever finds
+//                        the slot free or already holding its key adds itself with atomicMax /
+//                        atomicAdd.
 //   k_book_index_find    thread per query: probe to the key or a free slot, B's columns at last1 - 1.
 //   k_book_distinct      one ticket-ordered tile pass (stream_tile.h) over B's positions: position p
 //                        is kept iff its key's last1 == p + 1, and kept rows go at their rank to
 //                        output columns of the call's own. Its ticket and look-back words are the
 //                        call's own as well (the stream's belong to the tick); B is only read.
-// Every probe loop ends after `slots` steps at the latest.
+// Every probe ends after `slots` steps at the latest.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,6 +37,7 @@
 #include "index_home.h"
 #include "kernels.h"
 #include "running_book.h"
+#include "slot_probe.h"
 #include "stream_tile.h"
 
 namespace ydc {
@@ -64,14 +65,8 @@ static_assert(sizeof(BookHit) == 32, "ydc_book_hit is 32 bytes");
 // What the index knows of key k: last1 (0: the key is not in B) and the count.
 __device__ __forceinline__ uint2 book_index_lookup(const BookIndex& ix, unsigned long long k) {
   if (k == kBookIndexEmpty) return make_uint2(ix.side[0], ix.side[1]);
-  uint32_t h = (uint32_t)book_index_mix(k) & ix.mask;
-  for (uint32_t it = 0; it <= ix.mask; ++it) {
-    const unsigned long long at = ix.key[h];
-    if (at == k) return make_uint2(ix.last1[h], ix.cnt[h]);
-    if (at == kBookIndexEmpty) break;
-    h = (h + 1) & ix.mask;
-  }
-  return make_uint2(0u, 0u);
+  const uint32_t h = slot_lookup(ix.key, ix.mask, slot_home(k, ix.mask), kBookIndexEmpty, k);
+  return h == kNone ? make_uint2(0u, 0u) : make_uint2(ix.last1[h], ix.cnt[h]);
 }
 
 // ceil(n / 256) workgroups. n: |B| (the host's mirror, <= max_book).
@@ -84,20 +79,10 @@ __global__ __launch_bounds__(256) void k_book_index_build(const unsigned long lo
     atomicAdd(&ix.side[1], 1u);
     return;
   }
-  uint32_t h = (uint32_t)book_index_mix(k) & ix.mask;
-  for (uint32_t it = 0; it <= ix.mask; ++it) {
-    // (a published key never changes: a plain look first spares the slot's owner-to-be the CAS traffic
-    // of everybody who merely passes by or shares the key)
-    unsigned long long at = __hip_atomic_load(&ix.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (at == kBookIndexEmpty) at = atomicCAS(&ix.key[h], kBookIndexEmpty, k);
-    if (at == kBookIndexEmpty || at == k) {
-      atomicMax(&ix.last1[h], p + 1);
-      atomicAdd(&ix.cnt[h], 1u);
-      return;
-    }
-    h = (h + 1) & ix.mask;
-  }
-  // (not reached: the table has at least 2 n slots)
+  const uint32_t h = slot_claim(ix.key, ix.mask, slot_home(k, ix.mask), kBookIndexEmpty, k);
+  if (h == kNone) return;  // (never: the table has at least 2 n slots)
+  atomicMax(&ix.last1[h], p + 1);
+  atomicAdd(&ix.cnt[h], 1u);
 }
 
 // ceil(n / 256) workgroups; n_b: |B|. A last1 beyond |B| (there is none in a valid index) is a miss.

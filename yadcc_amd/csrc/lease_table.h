@@ -116,20 +116,31 @@ __device__ __forceinline__ uint32_t lease_find(const LeaseCols& L, const LeaseSt
   return kNone;
 }
 
-// A new lease in the first free slot from its home on. Always ends: the host checks before the tick
-// that |L| plus everything the tick can grant is <= max_leases <= cap / 2.
-__device__ __forceinline__ void lease_insert(const LeaseCols& L, LeaseState* st, unsigned long long id,
-                                             int64_t expires, uint32_t servant) {
+// THE insert: lease `id` filed in the first free slot from its home on, which one CAS on the key takes;
+// the winner then stores the columns and raises max_disp, in that order. A new grant's state word is
+// kLeaseLive; a rehash, a restore and a delta store the word they carry. Returns the slot (whoever keeps
+// columns beside the table stores them there afterwards). kNone never happens: the host checks before
+// the launch that |L| plus everything it can add is <= max_leases <= cap / 2.
+__device__ __forceinline__ uint32_t lease_file(const LeaseCols& L, LeaseState* st, unsigned long long id,
+                                               int64_t expires, uint32_t servant, uint32_t state) {
   const uint32_t h = lease_home(L, id);
   for (uint32_t d = 0; d <= L.mask; ++d) {
     const uint32_t slot = (h + d) & L.mask;
     if (L.key[slot] != kLeaseEmpty || atomicCAS(&L.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
     L.expires[slot] = expires;
     L.servant[slot] = servant;
-    L.state[slot] = kLeaseLive;
+    L.state[slot] = state;
     if (d) atomicMax(&st->max_disp, d);
-    return;
+    return slot;
   }
+  return kNone;
+}
+
+// The state words of slots i0 .. i0 + 3, one 16-byte load, for the passes in which thread i owns four
+// consecutive slots (i0 = 4 i; cap is a multiple of 4). Zeros, which no live slot has, beyond the table.
+__device__ __forceinline__ uint4 lease_states4(const LeaseCols& L, uint32_t i0) {
+  if (i0 > L.mask) return make_uint4(0, 0, 0, 0);
+  return *reinterpret_cast<const uint4*>(L.state + i0);
 }
 
 // The last workgroup of the last kernel of a leased tick: |L|, the outcome block, the tick's
@@ -244,37 +255,35 @@ __global__ __launch_bounds__(256) void k_lease_sweep(LeaseCols L, LeaseState* st
                                                      uint32_t* running) {
   const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
   uint32_t n_exp = 0, n_swept = 0;
-  if (i0 <= L.mask) {  // (cap is a multiple of 4)
-    uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-    if ((sv.x | sv.y | sv.z | sv.w) & kLeaseLive) {
-      const int64_t now = hdr->now;
-      const uint32_t tick = hdr->tick_no, stamp = tick & kLeaseStamp;
-      const uint4 srv = *reinterpret_cast<const uint4*>(L.servant + i0);
-      const longlong2 e01 = *reinterpret_cast<const longlong2*>(L.expires + i0);
-      const longlong2 e23 = *reinterpret_cast<const longlong2*>(L.expires + i0 + 2);
-      uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
-      const uint32_t s4[4] = {srv.x, srv.y, srv.z, srv.w};
-      const int64_t e4[4] = {e01.x, e01.y, e23.x, e23.y};
-      bool changed = false;
+  const uint4 sv = lease_states4(L, i0);
+  if ((sv.x | sv.y | sv.z | sv.w) & kLeaseLive) {
+    const int64_t now = hdr->now;
+    const uint32_t tick = hdr->tick_no, stamp = tick & kLeaseStamp;
+    const uint4 srv = *reinterpret_cast<const uint4*>(L.servant + i0);
+    const longlong2 e01 = *reinterpret_cast<const longlong2*>(L.expires + i0);
+    const longlong2 e23 = *reinterpret_cast<const longlong2*>(L.expires + i0 + 2);
+    uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
+    const uint32_t s4[4] = {srv.x, srv.y, srv.z, srv.w};
+    const int64_t e4[4] = {e01.x, e01.y, e23.x, e23.y};
+    bool changed = false;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        uint32_t v = st4[k];
-        if (!(v & kLeaseLive)) continue;
-        if (!(v & kLeaseZombie) && e4[k] < now) {
-          v |= kLeaseZombie;
-          ++n_exp;
-        }
-        if ((v & kLeaseZombie) && (v & kLeaseStamp) != stamp && s4[k] < n_servants && rep_tick[s4[k]] == tick) {
-          L.key[i0 + k] = kLeaseEmpty;
-          atomicSub(&running[s4[k]], 1u);
-          v = 0;
-          ++n_swept;
-        }
-        changed |= v != st4[k];
-        st4[k] = v;
+    for (int k = 0; k < 4; ++k) {
+      uint32_t v = st4[k];
+      if (!(v & kLeaseLive)) continue;
+      if (!(v & kLeaseZombie) && e4[k] < now) {
+        v |= kLeaseZombie;
+        ++n_exp;
       }
-      if (changed) *reinterpret_cast<uint4*>(L.state + i0) = make_uint4(st4[0], st4[1], st4[2], st4[3]);
+      if ((v & kLeaseZombie) && (v & kLeaseStamp) != stamp && s4[k] < n_servants && rep_tick[s4[k]] == tick) {
+        L.key[i0 + k] = kLeaseEmpty;
+        atomicSub(&running[s4[k]], 1u);
+        v = 0;
+        ++n_swept;
+      }
+      changed |= v != st4[k];
+      st4[k] = v;
     }
+    if (changed) *reinterpret_cast<uint4*>(L.state + i0) = make_uint4(st4[0], st4[1], st4[2], st4[3]);
   }
   // One atomic per workgroup and counter.
   __shared__ uint32_t s_cnt[2];
@@ -313,7 +322,7 @@ __global__ __launch_bounds__(256) void k_lease_remap(LeaseCols L, LeaseState* st
 }
 
 // ydc_stream_reserve: every lease of the table `o` filed into the larger, empty table `n` by
-// lease_insert's rule (multiplicative home, linear probing, one CAS on the key), its state word
+// lease_file (multiplicative home, linear probing, one CAS on the key), its state word
 // stored as it is: live, zombie and the report stamp. One pass shaped like k_lease_sweep:
 // ceil(old cap / kLeaseTile) workgroups, thread i owns four consecutive slots of `o`. n's
 // bookkeeping starts cleared: n_leases counts what was filed (the host compares it with |L|),
@@ -329,7 +338,7 @@ __global__ __launch_bounds__(256) void k_lease_rehash(LeaseCols o, const LeaseSt
     const ulonglong2 k23 = *reinterpret_cast<const ulonglong2*>(o.key + i0 + 2);
     const unsigned long long k4[4] = {k01.x, k01.y, k23.x, k23.y};
     if ((k4[0] & k4[1] & k4[2] & k4[3]) != kLeaseEmpty) {
-      const uint4 sv = *reinterpret_cast<const uint4*>(o.state + i0);
+      const uint4 sv = lease_states4(o, i0);
       const uint4 srv = *reinterpret_cast<const uint4*>(o.servant + i0);
       const longlong2 e01 = *reinterpret_cast<const longlong2*>(o.expires + i0);
       const longlong2 e23 = *reinterpret_cast<const longlong2*>(o.expires + i0 + 2);
@@ -337,21 +346,8 @@ __global__ __launch_bounds__(256) void k_lease_rehash(LeaseCols o, const LeaseSt
       const uint32_t s4[4] = {srv.x, srv.y, srv.z, srv.w};
       const int64_t e4[4] = {e01.x, e01.y, e23.x, e23.y};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const unsigned long long id = k4[k];
-        if (id == kLeaseEmpty) continue;
-        const uint32_t h = lease_home(n, id);
-        for (uint32_t d = 0; d <= n.mask; ++d) {
-          const uint32_t slot = (h + d) & n.mask;
-          if (n.key[slot] != kLeaseEmpty || atomicCAS(&n.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
-          n.expires[slot] = e4[k];
-          n.servant[slot] = s4[k];
-          n.state[slot] = st4[k];
-          if (d) atomicMax(&nst->max_disp, d);
-          ++moved;
-          break;
-        }
-      }
+      for (int k = 0; k < 4; ++k)
+        if (k4[k] != kLeaseEmpty && lease_file(n, nst, k4[k], e4[k], s4[k], st4[k]) != kNone) ++moved;
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) nst->next_id = ost->next_id;

@@ -32,24 +32,23 @@
 //                        go at their rank to the call's output rows. Its ticket and look-back words
 //                        are the call's own. Which slot a key landed in depends on who won a CAS, so
 //                        THE ORDER OF THE ROWS IS UNSPECIFIED (the Python wrapper sorts them).
-// A slot is claimed and its key published by ONE 64-bit compare-and-swap; nobody waits for another
-// thread's store (book_index.h says why). Every probe loop ends after `slots` steps at the latest. All
-// sums are integer atomics: the result does not depend on the order.
+// Claim, lookup and fold are slot_probe.h's: a slot is claimed and its key published by ONE 64-bit
+// compare-and-swap, nobody waits for another thread's store, every probe ends after `slots` steps at
+// the latest. All sums are integer atomics: the result does not depend on the order.
 //
 // Hot key: one requestor that owns most of L is the normal case (a farm's CI host), and a plain pass
 // would put |L| atomics on one address. The two counting kernels therefore combine equal keys inside
-// the wave first: a first-lane broadcast, a ballot of the lanes with that key, one lane adds the
-// wave's sums for it. After kRequestorRounds distinct keys the lanes that are left add for themselves
-// (a wave of 64 distinct keys would otherwise loop 64 times to save nothing). `combine` == false
-// (YDC_TUNE requestor_combine=0): every lane adds for itself.
+// the wave first (wave_combine of stream_tile.h: kRequestorRounds distinct keys, then the lanes that
+// are left add for themselves). `combine` == false (YDC_TUNE requestor_combine=0): every lane adds
+// for itself.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "book_index.h"
 #include "index_home.h"
 #include "kernels.h"
 #include "lease_table.h"
+#include "slot_probe.h"
 #include "stream_inspect.h"
 #include "stream_tile.h"
 #include "wait_queue.h"
@@ -57,8 +56,6 @@
 namespace ydc {
 
 constexpr uint32_t kRequestorCols = 5;    // leases | zombies | prefetch_leases | waiting | waiting_rows
-constexpr uint32_t kRequestorRounds = 4;  // distinct keys a wave combines before its lanes go alone
-constexpr uint32_t kRequestorTile = 1024;  // slots per workgroup of the fold (256 x 4)
 constexpr uint32_t kRequestorUnknown = 0xFFFFFFFFu;  // YDC_REQUESTOR_UNKNOWN
 constexpr unsigned long long kRequestorOccupied = 1ull << 32;
 
@@ -77,43 +74,25 @@ static_assert(sizeof(RequestorLoad) == 24, "ydc_requestor_load is 24 bytes");
 
 // (requestor_index_slots: index_home.h)
 
-__device__ __forceinline__ uint32_t requestor_home(const RequestorIndex& ix, uint32_t ip) {
-  return (uint32_t)book_index_mix(ip) & ix.mask;
-}
+// The three tables keyed by requestor (this one, stream_quota.h's and stream_usage.h's) share the slot
+// word, the home slot (slot_home of the id) and the probe (slot_probe.h).
 
 // The slot of `ip`, claimed if nobody had it. kNone: the table is full (never: it has at least twice
 // as many slots as there are entries).
-__device__ __forceinline__ uint32_t requestor_claim(const RequestorIndex& ix, uint32_t ip) {
-  const unsigned long long w = kRequestorOccupied | ip;
-  uint32_t h = requestor_home(ix, ip);
-  for (uint32_t it = 0; it <= ix.mask; ++it) {
-    // (a published word never changes: a plain look first spares the slot the CAS traffic of
-    // everybody who shares the key or merely passes by)
-    unsigned long long at = __hip_atomic_load(&ix.word[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (at == 0) at = atomicCAS(&ix.word[h], 0ull, w);
-    if (at == 0 || at == w) return h;
-    h = (h + 1) & ix.mask;
-  }
-  return kNone;
+__device__ __forceinline__ uint32_t requestor_claim(unsigned long long* word, uint32_t mask, uint32_t ip,
+                                                    bool* published = nullptr) {
+  return slot_claim(word, mask, slot_home(ip, mask), 0ull, kRequestorOccupied | ip, published);
 }
 
 // The slot of `ip`, or kNone.
-__device__ __forceinline__ uint32_t requestor_lookup(const RequestorIndex& ix, uint32_t ip) {
-  const unsigned long long w = kRequestorOccupied | ip;
-  uint32_t h = requestor_home(ix, ip);
-  for (uint32_t it = 0; it <= ix.mask; ++it) {
-    const unsigned long long at = ix.word[h];
-    if (at == w) return h;
-    if (at == 0) break;
-    h = (h + 1) & ix.mask;
-  }
-  return kNone;
+__device__ __forceinline__ uint32_t requestor_lookup(const unsigned long long* word, uint32_t mask, uint32_t ip) {
+  return slot_lookup(word, mask, slot_home(ip, mask), 0ull, kRequestorOccupied | ip);
 }
 
 // n entries of `ip` into columns col, col + 1, col + 2 of its slot: n | a | b.
 __device__ __forceinline__ void requestor_add_one(const RequestorIndex& ix, uint32_t ip, uint32_t col, uint32_t n,
                                                   uint32_t a, uint32_t b) {
-  const uint32_t h = requestor_claim(ix, ip);
+  const uint32_t h = requestor_claim(ix.word, ix.mask, ip);
   if (h == kNone) return;
   uint32_t* const dst = ix.sum + (size_t)col * ((size_t)ix.mask + 1) + h;
   atomicAdd(dst, n);
@@ -127,23 +106,14 @@ __device__ __forceinline__ uint32_t wave_sum_if_any(uint32_t v) {
 }
 
 // One entry per active lane: 1 | a | b for key `ip`. With `combine` every lane of the wave must get
-// here (wave-uniform control flow around the call).
+// here (wave_combine).
 __device__ __forceinline__ void requestor_add(const RequestorIndex& ix, bool combine, bool active, uint32_t ip,
                                               uint32_t col, uint32_t a, uint32_t b) {
-  if (combine) {
-    const uint32_t lane = lane_id();
-    unsigned long long todo = __ballot(active);
-    for (uint32_t round = 0; todo && round < kRequestorRounds; ++round) {  // (wave-uniform)
-      const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
-      const uint32_t ip0 = (uint32_t)__shfl((int)ip, (int)lead, 64);
-      const bool mine = active && ip == ip0;
-      const unsigned long long same = __ballot(mine);
+  if (combine)
+    active = wave_combine(active, ip, [&](uint32_t ip0, bool mine, unsigned long long same, bool leads, uint32_t) {
       const uint32_t sa = wave_sum_if_any(mine ? a : 0u), sb = wave_sum_if_any(mine ? b : 0u);
-      if (lane == lead) requestor_add_one(ix, ip0, col, (uint32_t)__popcll(same), sa, sb);
-      active = active && !mine;
-      todo &= ~same;
-    }
-  }
+      if (leads) requestor_add_one(ix, ip0, col, (uint32_t)__popcll(same), sa, sb);
+    });
   if (active) requestor_add_one(ix, ip, col, 1u, a, b);
 }
 
@@ -152,11 +122,8 @@ __device__ __forceinline__ void requestor_add(const RequestorIndex& ix, bool com
 __global__ __launch_bounds__(256) void k_requestor_leases(LeaseCols L, const uint4* rec, const uint8_t* pre,
                                                           RequestorIndex ix, uint32_t combine) {
   const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  uint32_t st4[4] = {0, 0, 0, 0};
-  if (i0 <= L.mask) {  // (the slot count is a multiple of 4)
-    const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-    st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
-  }
+  const uint4 sv = lease_states4(L, i0);
+  const uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const bool live = (st4[k] & kLeaseLive) != 0;
@@ -195,7 +162,7 @@ __global__ __launch_bounds__(256) void k_requestor_find(const uint32_t* q, uint3
                                                         uint32_t with_l, RequestorLoad* out) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t ip = q[i], h = requestor_lookup(ix, ip);
+  const uint32_t ip = q[i], h = requestor_lookup(ix.word, ix.mask, ip);
   const size_t slots = (size_t)ix.mask + 1;
   RequestorLoad r{ip, 0u, 0u, 0u, 0u, 0u};
   if (h != kNone) {
@@ -209,59 +176,21 @@ __global__ __launch_bounds__(256) void k_requestor_find(const uint32_t* q, uint3
   out[i] = r;
 }
 
-// The fold's own bookkeeping, cleared by the host in front of the launch; its look-back words
-// follow it.
-struct RequestorFoldState {
-  uint32_t ticket;
-  uint32_t n_rows;  // the result: occupied slots
-};
+// The fold's bookkeeping and tile: slot_probe.h's.
+using RequestorFoldState = SlotFoldState;
+constexpr uint32_t kRequestorTile = kSlotFoldTile;
 
-// ceil(slots / kRequestorTile) workgroups of 256 threads, thread i of a workgroup owning four
-// consecutive slots. out: out_cap rows of room (a rank beyond it is counted and not written).
+// slot_fold's grid: ceil(slots / kRequestorTile) workgroups of 256 threads. out: out_cap rows of room.
 __global__ __launch_bounds__(256) void k_requestor_fold(RequestorIndex ix, uint32_t with_l, RequestorFoldState* fs,
                                                         unsigned long long* lookback, RequestorLoad* out,
                                                         uint32_t out_cap) {
-  __shared__ uint32_t lds[17];
-  __shared__ uint32_t s_bid, s_pre;
-  if (threadIdx.x == 0) s_bid = atomicAdd(&fs->ticket, 1u);
-  __syncthreads();
-  const uint32_t bid = s_bid;
-  const uint32_t h0 = bid * kRequestorTile + threadIdx.x * 4;
-  unsigned long long w4[4] = {0, 0, 0, 0};
-  if (h0 <= ix.mask) {  // (the slot count is a multiple of 1024)
-    const ulonglong2 w01 = *reinterpret_cast<const ulonglong2*>(ix.word + h0);
-    const ulonglong2 w23 = *reinterpret_cast<const ulonglong2*>(ix.word + h0 + 2);
-    w4[0] = w01.x, w4[1] = w01.y, w4[2] = w23.x, w4[3] = w23.y;
-  }
-  uint32_t n_keep = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) n_keep += w4[i] ? 1u : 0u;
-  uint32_t tot = 0;
-  const uint32_t ex = block_exclusive_scan(n_keep, lds, &tot);
-  if (threadIdx.x < 64) {
-    LbWords<1> agg;
-    agg.w[0] = lb_pack(tot);
-    const LbWords<1> pre = tile_lookback<1>(lookback, bid, threadIdx.x, agg);
-    if (threadIdx.x == 0) {
-      s_pre = lb_lo(pre.w[0]);
-      if (bid == gridDim.x - 1) fs->n_rows = s_pre + tot;
-    }
-  }
-  __syncthreads();
-  uint32_t dst = s_pre + ex;
   const size_t slots = (size_t)ix.mask + 1;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (!w4[i]) continue;
-    const uint32_t h = h0 + i;
-    if (dst < out_cap) {
-      RequestorLoad r{(uint32_t)w4[i], ix.sum[h], ix.sum[slots + h], ix.sum[2 * slots + h], ix.sum[3 * slots + h],
-                      ix.sum[4 * slots + h]};
-      if (!with_l) r.leases = r.zombies = r.prefetch = kRequestorUnknown;
-      out[dst] = r;
-    }
-    ++dst;
-  }
+  slot_fold(ix.word, ix.mask, fs, lookback, out_cap, [&](uint32_t dst, unsigned long long w, uint32_t h) {
+    RequestorLoad r{(uint32_t)w, ix.sum[h], ix.sum[slots + h], ix.sum[2 * slots + h], ix.sum[3 * slots + h],
+                    ix.sum[4 * slots + h]};
+    if (!with_l) r.leases = r.zombies = r.prefetch = kRequestorUnknown;
+    out[dst] = r;
+  });
 }
 
 }  // namespace ydc

@@ -17,7 +17,7 @@
 //                  the tick's total up to max_rows are a digest nobody has.
 //   (front, passes, k_finalize place the max_rows rows as one batch)
 //   k_rpc_grant    thread per row, gated like k_finalize: stable scan of "granted", id = next_id +
-//                  rank, the lease (lease_insert of lease_table.h), the exclusive
+//                  rank, the lease (lease_file of lease_table.h), the exclusive
 //                  rank per row to HBM, servants and ids to page-locked memory: W's region packed by
 //                  rank (it leads the batch, so an entry's first grant is the rank of its first
 //                  row), the new requests' rows at row - rows(W).
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void k_rpc_grant(RpcBatch b, uint32_t NR, uint
     if (j < NR) b.rank[j] = rk;
     if (r[i] >= kIdxWaiting) continue;
     ids[i] = next + rk;
-    lease_insert(L, st, ids[i], now + b.lease_for[j], r[i]);  // the lease runs from the grant
+    lease_file(L, st, ids[i], now + b.lease_for[j], r[i], kLeaseLive);  // the lease runs from the grant
     if (j < w_rows) {  // a waiting RPC's grant: packed by rank (rk <= j < NR)
       o.res_srv[rk] = r[i];
       o.res_id[rk] = ids[i];

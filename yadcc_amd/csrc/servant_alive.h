@@ -133,24 +133,22 @@ __global__ __launch_bounds__(256) void k_alive_remap(LeaseCols L, const uint32_t
 __global__ __launch_bounds__(256) void k_alive_orphans(LeaseCols L, LeaseState* ls, AliveState* st) {
   const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
   uint32_t n_orph = 0, n_late = 0;
-  if (i0 <= L.mask) {  // (cap is a multiple of 4)
-    const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-    if ((sv.x | sv.y | sv.z | sv.w) & kLeaseLive) {
-      const uint4 srv = *reinterpret_cast<const uint4*>(L.servant + i0);
-      uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
-      const uint32_t s4[4] = {srv.x, srv.y, srv.z, srv.w};
-      bool changed = false;
+  const uint4 sv = lease_states4(L, i0);
+  if ((sv.x | sv.y | sv.z | sv.w) & kLeaseLive) {
+    const uint4 srv = *reinterpret_cast<const uint4*>(L.servant + i0);
+    uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
+    const uint32_t s4[4] = {srv.x, srv.y, srv.z, srv.w};
+    bool changed = false;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (!(st4[k] & kLeaseLive) || (s4[k] != kParkedLive && s4[k] != kParkedZombie)) continue;
-        n_late += (s4[k] == kParkedLive && (st4[k] & kLeaseZombie)) ? 1u : 0u;
-        ++n_orph;
-        L.key[i0 + k] = kLeaseEmpty;
-        st4[k] = 0;
-        changed = true;
-      }
-      if (changed) *reinterpret_cast<uint4*>(L.state + i0) = make_uint4(st4[0], st4[1], st4[2], st4[3]);
+    for (int k = 0; k < 4; ++k) {
+      if (!(st4[k] & kLeaseLive) || (s4[k] != kParkedLive && s4[k] != kParkedZombie)) continue;
+      n_late += (s4[k] == kParkedLive && (st4[k] & kLeaseZombie)) ? 1u : 0u;
+      ++n_orph;
+      L.key[i0 + k] = kLeaseEmpty;
+      st4[k] = 0;
+      changed = true;
     }
+    if (changed) *reinterpret_cast<uint4*>(L.state + i0) = make_uint4(st4[0], st4[1], st4[2], st4[3]);
   }
   // One atomic per workgroup and counter.
   __shared__ uint32_t s_cnt[2];

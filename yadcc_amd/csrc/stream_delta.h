@@ -18,8 +18,8 @@
 //                        inserted ones, the table holds. The host compares with the lists' lengths.
 //   k_lease_delta_apply_old   thread per erase (k_lease_free's CAS on the key, state 0; running_tasks is
 //                        carried as a column, not counted) and per update (expiry and state stored).
-//   k_lease_delta_apply_new   thread per insert, by lease_insert's rule with the state word stored as
-//                        given (k_lease_load's loop); thread 0 stores next_id and |L|.
+//   k_lease_delta_apply_new   thread per insert, by lease_file (lease_table.h) with the state word stored
+//                        as given (as k_lease_load); thread 0 stores next_id and |L|.
 // Appends are one ballot and one atomicAdd per wave and list (k_alive_due's pattern).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -66,19 +66,17 @@ __global__ __launch_bounds__(256) void k_lease_delta_scan(LeaseCols L, LeasePack
   uint32_t st4[4] = {0, 0, 0, 0}, s4[4] = {0, 0, 0, 0};
   unsigned long long k4[4] = {0, 0, 0, 0};
   int64_t e4[4] = {0, 0, 0, 0};
-  if (i0 <= L.mask) {  // (cap is a multiple of 4)
-    const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-    if ((sv.x | sv.y | sv.z | sv.w) & kLeaseLive) {
-      const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(L.key + i0);
-      const ulonglong2 k23 = *reinterpret_cast<const ulonglong2*>(L.key + i0 + 2);
-      const uint4 srv = *reinterpret_cast<const uint4*>(L.servant + i0);
-      const longlong2 e01 = *reinterpret_cast<const longlong2*>(L.expires + i0);
-      const longlong2 e23 = *reinterpret_cast<const longlong2*>(L.expires + i0 + 2);
-      st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
-      s4[0] = srv.x, s4[1] = srv.y, s4[2] = srv.z, s4[3] = srv.w;
-      k4[0] = k01.x, k4[1] = k01.y, k4[2] = k23.x, k4[3] = k23.y;
-      e4[0] = e01.x, e4[1] = e01.y, e4[2] = e23.x, e4[3] = e23.y;
-    }
+  const uint4 sv = lease_states4(L, i0);
+  if ((sv.x | sv.y | sv.z | sv.w) & kLeaseLive) {
+    const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(L.key + i0);
+    const ulonglong2 k23 = *reinterpret_cast<const ulonglong2*>(L.key + i0 + 2);
+    const uint4 srv = *reinterpret_cast<const uint4*>(L.servant + i0);
+    const longlong2 e01 = *reinterpret_cast<const longlong2*>(L.expires + i0);
+    const longlong2 e23 = *reinterpret_cast<const longlong2*>(L.expires + i0 + 2);
+    st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
+    s4[0] = srv.x, s4[1] = srv.y, s4[2] = srv.z, s4[3] = srv.w;
+    k4[0] = k01.x, k4[1] = k01.y, k4[2] = k23.x, k4[3] = k23.y;
+    e4[0] = e01.x, e4[1] = e01.y, e4[2] = e23.x, e4[3] = e23.y;
   }
   // One atomicAdd per wave and list: the wave's records in (k, lane) order behind the base it drew.
   unsigned long long m4[4], n4[4];
@@ -208,19 +206,7 @@ __global__ __launch_bounds__(256) void k_lease_delta_apply_new(LeaseCols L, Leas
                                                                uint32_t n_ins, unsigned long long next_id,
                                                                uint32_t n_leases) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_ins && i < ins.cap) {
-    const unsigned long long id = ins.id[i];
-    const uint32_t h = lease_home(L, id);
-    for (uint32_t d = 0; d <= L.mask; ++d) {
-      const uint32_t slot = (h + d) & L.mask;
-      if (L.key[slot] != kLeaseEmpty || atomicCAS(&L.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
-      L.expires[slot] = ins.expires[i];
-      L.servant[slot] = ins.servant[i];
-      L.state[slot] = ins.state[i];
-      if (d) atomicMax(&st->max_disp, d);
-      break;
-    }
-  }
+  if (i < n_ins && i < ins.cap) lease_file(L, st, ins.id[i], ins.expires[i], ins.servant[i], ins.state[i]);
   if (i == 0) {
     st->next_id = next_id;
     st->n_leases = n_leases;

@@ -28,7 +28,7 @@
 //                    workgroups per CU keep their room, and ten probes of a search stay on chip); a
 //                    longer list is searched in HBM / L2. One requestor that holds most of L is the usual
 //                    departure, so equal hits are combined before the global atomic: a thread's four
-//                    slots first, then inside the wave (requestor_index.h's rounds), then the four waves'
+//                    slots first, then inside the wave (wave_combine of stream_tile.h), then the four waves'
 //                    first rounds through LDS, so the hot requestor's count takes one atomic per
 //                    workgroup, as `freed` does. (Combined inside the wave only, the pass over 10^6
 //                    leases of one requestor took 755 us, all of it the 32 768 atomics on one address;
@@ -88,20 +88,14 @@ __device__ __forceinline__ uint32_t depart_find(P ip, uint32_t n, uint32_t key) 
 }
 
 // One entry per active lane for the list's place `at`: a | b into the pair of counts at `col`, equal
-// places combined inside the wave first (requestor_add's rounds). Every lane of the wave must get here.
+// places combined inside the wave first. Every lane of the wave must get here (wave_combine).
 // first != NULL: the first round's sums are left there (place | a | b) for the workgroup to combine,
 // instead of being added.
 __device__ __forceinline__ void depart_add(uint4* count, bool active, uint32_t at, uint32_t col, uint32_t a,
                                            uint32_t b, uint32_t* first = nullptr) {
-  const uint32_t lane = lane_id();
-  unsigned long long todo = __ballot(active);
-  for (uint32_t round = 0; todo && round < kRequestorRounds; ++round) {  // (wave-uniform)
-    const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
-    const uint32_t at0 = (uint32_t)__shfl((int)at, (int)lead, 64);
-    const bool mine = active && at == at0;
-    const unsigned long long same = __ballot(mine);
+  active = wave_combine(active, at, [&](uint32_t at0, bool mine, unsigned long long, bool leads, uint32_t round) {
     const uint32_t sa = wave_sum_if_any(mine ? a : 0u), sb = wave_sum_if_any(mine ? b : 0u);
-    if (lane == lead) {
+    if (leads) {
       if (first && round == 0) {
         first[0] = at0, first[1] = sa, first[2] = sb;
       } else {
@@ -110,9 +104,7 @@ __device__ __forceinline__ void depart_add(uint4* count, bool active, uint32_t a
         if (sb) atomicAdd(p + 1, sb);
       }
     }
-    active = active && !mine;
-    todo &= ~same;
-  }
+  });
   if (active) {
     uint32_t* const p = reinterpret_cast<uint32_t*>(count + at) + col;
     if (a) atomicAdd(p, a);
@@ -147,11 +139,8 @@ __global__ __launch_bounds__(256) void k_depart_leases(LeaseCols L, LeaseState* 
   if (threadIdx.x < 4) s_first[threadIdx.x][0] = kNone;
   __syncthreads();
   const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  uint32_t st4[4] = {0, 0, 0, 0};
-  if (i0 <= L.mask) {  // (cap is a multiple of 4)
-    const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-    st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
-  }
+  const uint4 sv = lease_states4(L, i0);
+  uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
   uint32_t n_freed = 0;
   if (__ballot(((st4[0] | st4[1] | st4[2] | st4[3]) & kLeaseLive) != 0)) {  // (wave-uniform)
     uint32_t at4[4], a4[4], z4[4];

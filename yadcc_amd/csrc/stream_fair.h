@@ -62,7 +62,7 @@
 //                  shape (four per thread, 16-byte loads of state and servant: the live unparked leases),
 //                  W's positions (the live rows), and the tick's new requests, whose wants go into
 //                  ask[slot] of the quota's table through QuotaTick::slot, equal slots combined inside
-//                  the wave before the atomic (quota_add's rounds).
+//                  the wave before the atomic (wave_combine of stream_tile.h).
 //   k_fair_level   one workgroup. It walks the table's slots once: held, ask and, by one binary search
 //                  per asker, the override. An override's fixed term goes into the base; a fair asker's
 //                  (h, a) pair goes to the end of a list in HBM (a counter in LDS hands out the places),
@@ -173,8 +173,8 @@ __global__ __launch_bounds__(256) void k_fair_sums(FairRegistry reg, uint32_t r_
   if (b < l_blocks) {
     const uint32_t i0 = (b * blockDim.x + threadIdx.x) * 4;
     unsigned long long n = 0;
-    if (i0 <= L.mask) {  // (the slot count is a multiple of 4)
-      const uint4 st = *reinterpret_cast<const uint4*>(L.state + i0);
+    if (i0 <= L.mask) {  // (the servant column's guard: both loads are issued together)
+      const uint4 st = lease_states4(L, i0);
       const uint4 sv = *reinterpret_cast<const uint4*>(L.servant + i0);
       // (a zombie still holds its slot; a parked lease — its servant expired in this tick — is gone once the tick ends)
       n = ((st.x & kLeaseLive) && sv.x < kParkedZombie) + ((st.y & kLeaseLive) && sv.y < kParkedZombie) +
@@ -198,21 +198,13 @@ __global__ __launch_bounds__(256) void k_fair_sums(FairRegistry reg, uint32_t r_
   const uint32_t k = b * blockDim.x + threadIdx.x;
   const uint32_t slot = k < min(*in_n, MT) ? t.slot[k] : kNone;
   const uint32_t want = slot == kNone ? 0u : in_imm ? in_imm[k] + in_pre[k] : 1u;
-  // Equal slots combined inside the wave first (quota_add's rounds): one requestor sending most of a tick
-  // is the normal case. Every lane of the wave gets here.
-  const uint32_t lane = lane_id();
+  // Equal slots combined inside the wave first (wave_combine: every lane of the wave gets here): one
+  // requestor sending most of a tick is the normal case.
   bool active = slot != kNone && slot <= tb.mask && want != 0;
-  unsigned long long todo = __ballot(active);
-  for (uint32_t round = 0; todo && round < kRequestorRounds; ++round) {  // (wave-uniform)
-    const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
-    const uint32_t s0 = (uint32_t)__shfl((int)slot, (int)lead, 64);
-    const bool mine = active && slot == s0;
-    const unsigned long long same = __ballot(mine);
+  active = wave_combine(active, slot, [&](uint32_t s0, bool mine, unsigned long long, bool leads, uint32_t) {
     const uint32_t sum = wave_sum_u32(mine ? want : 0u);
-    if (lane == lead) atomicAdd(&f.ask[s0], sum);
-    active = active && !mine;
-    todo &= ~same;
-  }
+    if (leads) atomicAdd(&f.ask[s0], sum);
+  });
   if (active) atomicAdd(&f.ask[slot], want);
 }
 

@@ -62,28 +62,12 @@ __device__ __forceinline__ int64_t inspect_started(const uint4& r) {
   return (int64_t)((unsigned long long)r.x | ((unsigned long long)r.y << 32));
 }
 
-// lease_insert (lease_table.h) returning the slot it took; kNone never happens under the host's
-// check that |L| plus everything the tick can grant is <= max_leases <= cap / 2.
-__device__ __forceinline__ uint32_t lease_insert_slot(const LeaseCols& L, LeaseState* st, unsigned long long id,
-                                                      int64_t expires, uint32_t servant) {
-  const uint32_t h = lease_home(L, id);
-  for (uint32_t d = 0; d <= L.mask; ++d) {
-    const uint32_t slot = (h + d) & L.mask;
-    if (L.key[slot] != kLeaseEmpty || atomicCAS(&L.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
-    L.expires[slot] = expires;
-    L.servant[slot] = servant;
-    L.state[slot] = kLeaseLive;
-    if (d) atomicMax(&st->max_disp, d);
-    return slot;
-  }
-  return kNone;
-}
-
-// The insert of a granting pass with inspection on: the lease, its record, its servant's count.
+// The insert of a granting pass with inspection on: the lease (lease_file of lease_table.h), its record
+// into the slot it took, its servant's count.
 __device__ __forceinline__ void lease_insert_inspected(const LeaseCols& L, LeaseState* st, const InspectIn& ins,
                                                        unsigned long long id, int64_t expires, uint32_t servant,
                                                        int64_t now, uint32_t j, bool prefetch) {
-  const uint32_t slot = lease_insert_slot(L, st, id, expires, servant);
+  const uint32_t slot = lease_file(L, st, id, expires, servant, kLeaseLive);
   if (slot != kNone) {
     ins.rec[slot] = inspect_rec(now, ins.env[j], ins.ip[j]);
     ins.prefetch[slot] = prefetch ? 1 : 0;
@@ -99,8 +83,8 @@ __global__ __launch_bounds__(256) void k_inspect_fill(uint4* rec, uint8_t* prefe
   prefetch[i] = 0;
 }
 
-// k_lease_rehash's rule (lease_table.h) with the record: thread per slot of `o`. Off the hot path,
-// so one slot per thread and scalar loads.
+// k_lease_rehash (lease_table.h) with the record, which goes into the slot lease_file took: thread per
+// slot of `o`. Off the hot path, so one slot per thread and scalar loads.
 __global__ __launch_bounds__(256) void k_inspect_rehash(LeaseCols o, const LeaseState* ost, const uint4* orec,
                                                         const uint8_t* opre, LeaseCols n, LeaseState* nst, uint4* nrec,
                                                         uint8_t* npre) {
@@ -109,18 +93,11 @@ __global__ __launch_bounds__(256) void k_inspect_rehash(LeaseCols o, const Lease
   if (i <= o.mask) {
     const unsigned long long id = o.key[i];
     if (id != kLeaseEmpty) {
-      const uint32_t h = lease_home(n, id);
-      for (uint32_t d = 0; d <= n.mask; ++d) {
-        const uint32_t slot = (h + d) & n.mask;
-        if (n.key[slot] != kLeaseEmpty || atomicCAS(&n.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
-        n.expires[slot] = o.expires[i];
-        n.servant[slot] = o.servant[i];
-        n.state[slot] = o.state[i];
+      const uint32_t slot = lease_file(n, nst, id, o.expires[i], o.servant[i], o.state[i]);
+      moved = slot != kNone;
+      if (moved) {
         nrec[slot] = orec[i];
         npre[slot] = opre[i];
-        if (d) atomicMax(&nst->max_disp, d);
-        moved = true;
-        break;
       }
     }
   }
@@ -173,11 +150,8 @@ struct InspectPacked {
 __global__ __launch_bounds__(256) void k_inspect_pack(LeaseCols L, const uint4* rec, const uint8_t* pre,
                                                       InspectPacked out, uint32_t* n_packed) {
   const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  uint32_t st4[4] = {0, 0, 0, 0};
-  if (i0 <= L.mask) {  // (cap is a multiple of 4)
-    const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-    st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
-  }
+  const uint4 sv = lease_states4(L, i0);
+  const uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
   unsigned long long m4[4];
   uint32_t total = 0;
 #pragma unroll

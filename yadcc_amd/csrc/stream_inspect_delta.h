@@ -9,8 +9,8 @@
 //                               four columns written at the id's position: the output is in id order without a
 //                               sort. Misses are counted, one atomicAdd per wave.
 //   k_lease_delta_apply_inspect the standby: k_lease_delta_apply_new's twin (stream_delta.h; why a twin: a
-//                               stream without inspection launches what it launched). The thread that wins the
-//                               CAS on a slot stores the lease and then, into the same slot, the record and the
+//                               stream without inspection launches what it launched). The thread whose
+//                               lease_file took a slot then stores, into the same slot, the record and the
 //                               prefetch byte, as lease_insert_inspected does: a stale record a reused slot
 //                               held is overwritten by that store. No second probe, and no atomicAdd into
 //                               ever_assigned: that column is carried whole.
@@ -61,18 +61,10 @@ __global__ __launch_bounds__(256) void k_lease_delta_apply_inspect(LeaseCols L, 
                                                                    uint4* rec, uint8_t* pre) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_ins && i < ins.cap) {
-    const unsigned long long id = ins.id[i];
-    const uint32_t h = lease_home(L, id);
-    for (uint32_t d = 0; d <= L.mask; ++d) {
-      const uint32_t slot = (h + d) & L.mask;
-      if (L.key[slot] != kLeaseEmpty || atomicCAS(&L.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
-      L.expires[slot] = ins.expires[i];
-      L.servant[slot] = ins.servant[i];
-      L.state[slot] = ins.state[i];
+    const uint32_t slot = lease_file(L, st, ins.id[i], ins.expires[i], ins.servant[i], ins.state[i]);
+    if (slot != kNone) {
       rec[slot] = inspect_rec(in.started_at[i], in.env[i], in.ip[i]);
       pre[slot] = in.prefetch[i];
-      if (d) atomicMax(&st->max_disp, d);
-      break;
     }
   }
   if (i == 0) {

@@ -155,21 +155,19 @@ __global__ __launch_bounds__(256) void k_outlook_leases(LeaseCols L, const uint4
     __syncthreads();
   }
   const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i0 <= L.mask) {  // (the slot count is a multiple of 4)
-    const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-    const uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
+  const uint4 sv = lease_states4(L, i0);
+  const uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (!(st4[k] & kLeaseLive)) continue;
-      const uint32_t b = min(rec[i0 + k].z, bins - 1);
-      const bool zombie = (st4[k] & kLeaseZombie) != 0;
-      if (lds) {
-        atomicAdd(&s_hist[b], 1u);
-        if (zombie) atomicAdd(&s_hist[bins + b], 1u);
-      } else {
-        atomicAdd(&hist[b], 1u);
-        if (zombie) atomicAdd(&hist[bins + b], 1u);
-      }
+  for (int k = 0; k < 4; ++k) {
+    if (!(st4[k] & kLeaseLive)) continue;
+    const uint32_t b = min(rec[i0 + k].z, bins - 1);
+    const bool zombie = (st4[k] & kLeaseZombie) != 0;
+    if (lds) {
+      atomicAdd(&s_hist[b], 1u);
+      if (zombie) atomicAdd(&s_hist[bins + b], 1u);
+    } else {
+      atomicAdd(&hist[b], 1u);
+      if (zombie) atomicAdd(&hist[bins + b], 1u);
     }
   }
   if (lds) {

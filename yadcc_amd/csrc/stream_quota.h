@@ -10,8 +10,8 @@
 // stream that never switched the capability on launches none of them:
 //
 //   k_quota_claim   thread per new request: its requestor's slot in a table keyed by the tick's new
-//                   requestor_ips (open addressing, one 64-bit CAS per claim, requestor_index.h's
-//                   word). Whoever claims or finds a slot zeroes its two sums; the tick's counters,
+//                   requestor_ips (open addressing, one 64-bit CAS per claim: requestor_index.h's
+//                   word and requestor_claim). Whoever claims or finds a slot zeroes its two sums; the tick's counters,
 //                   the clip pass's ticket and chain words are reset.
 //   k_quota_loads   one launch over L's slots (k_requestor_leases' shape: four slots per thread) and
 //                   W's positions: a live, attributed lease that is not parked adds 1, an entry of W
@@ -38,7 +38,7 @@
 //                   stays EnvironmentNotFound. Plain stores only.
 //
 // The only wait is lane 0 of a tile's first wave for the release store of ANOTHER workgroup that has
-// drawn its ticket already; nobody spins on a store of a thread of its own wave (book_index.h).
+// drawn its ticket already; nobody spins on a store of a thread of its own wave (slot_probe.h).
 //
 // 32 bits are enough for every sum: an accepted tick has rows(new) <= max_rows <= 2^30, so pre + want
 // < 2^31, and |L| + rows(W) <= max_leases + max_rows < 2^31, so held < 2^31. With cap ==
@@ -99,35 +99,6 @@ struct QuotaDone {
   uint32_t n, rows_clipped, n_refused, tick_no;
 };
 
-__device__ __forceinline__ uint32_t quota_home(const QuotaTable& tb, uint32_t ip) {
-  return (uint32_t)book_index_mix(ip) & tb.mask;
-}
-
-// requestor_claim / requestor_lookup on this table.
-__device__ __forceinline__ uint32_t quota_claim(const QuotaTable& tb, uint32_t ip) {
-  const unsigned long long w = kRequestorOccupied | ip;
-  uint32_t h = quota_home(tb, ip);
-  for (uint32_t it = 0; it <= tb.mask; ++it) {
-    unsigned long long at = __hip_atomic_load(&tb.word[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (at == 0) at = atomicCAS(&tb.word[h], 0ull, w);
-    if (at == 0 || at == w) return h;
-    h = (h + 1) & tb.mask;
-  }
-  return kNone;
-}
-
-__device__ __forceinline__ uint32_t quota_lookup(const QuotaTable& tb, uint32_t ip) {
-  const unsigned long long w = kRequestorOccupied | ip;
-  uint32_t h = quota_home(tb, ip);
-  for (uint32_t it = 0; it <= tb.mask; ++it) {
-    const unsigned long long at = tb.word[h];
-    if (at == w) return h;
-    if (at == 0) break;
-    h = (h + 1) & tb.mask;
-  }
-  return kNone;
-}
-
 // The cap of `ip`: its override, or the default.
 __device__ __forceinline__ uint32_t quota_cap(const QuotaCaps& q, uint32_t ip) {
   const uint32_t n = min(q.hdr[1], q.max);
@@ -148,32 +119,24 @@ __global__ __launch_bounds__(256) void k_quota_claim(const uint32_t* in_ip, cons
   if (k >= MT) return;
   uint32_t h = kNone;
   if (k < min(*in_n, MT)) {
-    h = quota_claim(tb, in_ip[k]);
+    h = requestor_claim(tb.word, tb.mask, in_ip[k]);
     if (h != kNone) tb.held[h] = tb.asked[h] = 0;  // (everybody who shares the slot stores the same)
   }
   t.slot[k] = h;
 }
 
-// `n` for key `ip` per active lane, looked up, equal keys combined inside the wave first
-// (requestor_add's rounds). Every lane of the wave must get here.
+// `n` for key `ip` per active lane, looked up (a miss is skipped), equal keys combined inside the wave
+// first. Every lane of the wave must get here (wave_combine).
 __device__ __forceinline__ void quota_add(const QuotaTable& tb, bool active, uint32_t ip, uint32_t n) {
-  const uint32_t lane = lane_id();
-  unsigned long long todo = __ballot(active);
-  for (uint32_t round = 0; todo && round < kRequestorRounds; ++round) {  // (wave-uniform)
-    const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
-    const uint32_t ip0 = (uint32_t)__shfl((int)ip, (int)lead, 64);
-    const bool mine = active && ip == ip0;
-    const unsigned long long same = __ballot(mine);
+  active = wave_combine(active, ip, [&](uint32_t ip0, bool mine, unsigned long long, bool leads, uint32_t) {
     const uint32_t sum = wave_sum_u32(mine ? n : 0u);
-    if (lane == lead) {
-      const uint32_t h = quota_lookup(tb, ip0);
+    if (leads) {
+      const uint32_t h = requestor_lookup(tb.word, tb.mask, ip0);
       if (h != kNone && sum) atomicAdd(&tb.held[h], sum);
     }
-    active = active && !mine;
-    todo &= ~same;
-  }
+  });
   if (active) {
-    const uint32_t h = quota_lookup(tb, ip);
+    const uint32_t h = requestor_lookup(tb.word, tb.mask, ip);
     if (h != kNone && n) atomicAdd(&tb.held[h], n);
   }
 }
@@ -186,11 +149,8 @@ __global__ __launch_bounds__(256) void k_quota_loads(LeaseCols L, const uint4* r
                                                      uint32_t MW, const LeaseHdr* hdr, QuotaTable tb) {
   if (blockIdx.x < l_blocks) {
     const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    uint32_t st4[4] = {0, 0, 0, 0};
-    if (i0 <= L.mask) {  // (the slot count is a multiple of 4)
-      const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-      st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
-    }
+    const uint4 sv = lease_states4(L, i0);
+    const uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       bool counts = (st4[k] & kLeaseLive) != 0;  // (a zombie still holds its slot)
@@ -238,6 +198,7 @@ __global__ __launch_bounds__(256) void k_quota_clip(const uint32_t* in_ip, const
   const uint32_t want = imm + pre;
   // The wave's groups of equal requestors: lead (the group's first lane), ex (the group's wants in
   // front of this lane), tot (the group's sum). ALU only; at most one round per distinct requestor.
+  // (Not wave_combine: every lane needs its group's prefix, so the rounds go on until no group is left.)
   uint32_t lead = lane, ex = 0, tot = want;
   for (unsigned long long todo = __ballot(active); todo;) {  // (wave-uniform)
     const uint32_t l0 = (uint32_t)__builtin_ctzll(todo);

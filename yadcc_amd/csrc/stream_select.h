@@ -24,8 +24,8 @@
 //
 // Every kernel has k_inspect_pack's shape: ceil(slots / kLeaseTile) workgroups of 256 threads, thread
 // i owns four consecutive slots, `state` read as one uint4 and the other columns as vectors when one
-// of the four is live. Indices: a slot index is < slots by the guard i0 <= L.mask (slots is a
-// multiple of 4); a bin index is a byte; a filter index is < n <= kSelectMaxFilters; a packed
+// of the four is live. Indices: a slot index is < slots by the guard of lease_states4 (slots is a
+// multiple of 4, and beyond the table nothing is live); a bin index is a byte; a filter index is < n <= kSelectMaxFilters; a packed
 // position is guarded by out.cap.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -61,9 +61,7 @@ __host__ __device__ __forceinline__ unsigned long long select_above(unsigned lon
 // pre NULL (inspection off): the sentinels.
 __device__ __forceinline__ uint32_t select_tile(const LeaseCols& L, const uint4* rec, const uint8_t* pre, uint32_t i0,
                                                 uint32_t need, LeaseRow (&row)[4], uint32_t (&st4)[4]) {
-  st4[0] = st4[1] = st4[2] = st4[3] = 0;
-  if (i0 > L.mask) return 0;  // (slots is a multiple of 4)
-  const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
+  const uint4 sv = lease_states4(L, i0);
   st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
   if (!((sv.x | sv.y | sv.z | sv.w) & kLeaseLive)) return 0;
   unsigned long long id4[4] = {0, 0, 0, 0};

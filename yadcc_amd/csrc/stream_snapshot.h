@@ -9,8 +9,8 @@
 //                  append, not a compaction: slot order means nothing across table sizes, the host
 //                  sorts the |L| records by id. |L| records cross the bus, not 2^k slots.
 //   k_lease_load   thread per packed record into the freshly reset table of the restoring stream,
-//                  by lease_insert's rule with the state word stored as given (k_lease_rehash's
-//                  inner loop, fed from packed columns instead of another table's slots).
+//                  by lease_file (lease_table.h) with the state word stored as given (as
+//                  k_lease_rehash, fed from packed columns instead of another table's slots).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,19 +36,17 @@ __global__ __launch_bounds__(256) void k_lease_pack(LeaseCols L, LeasePacked out
   uint32_t st4[4] = {0, 0, 0, 0}, s4[4] = {0, 0, 0, 0};
   unsigned long long k4[4] = {0, 0, 0, 0};
   int64_t e4[4] = {0, 0, 0, 0};
-  if (i0 <= L.mask) {  // (cap is a multiple of 4)
-    const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-    if ((sv.x | sv.y | sv.z | sv.w) & kLeaseLive) {
-      const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(L.key + i0);
-      const ulonglong2 k23 = *reinterpret_cast<const ulonglong2*>(L.key + i0 + 2);
-      const uint4 srv = *reinterpret_cast<const uint4*>(L.servant + i0);
-      const longlong2 e01 = *reinterpret_cast<const longlong2*>(L.expires + i0);
-      const longlong2 e23 = *reinterpret_cast<const longlong2*>(L.expires + i0 + 2);
-      st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
-      s4[0] = srv.x, s4[1] = srv.y, s4[2] = srv.z, s4[3] = srv.w;
-      k4[0] = k01.x, k4[1] = k01.y, k4[2] = k23.x, k4[3] = k23.y;
-      e4[0] = e01.x, e4[1] = e01.y, e4[2] = e23.x, e4[3] = e23.y;
-    }
+  const uint4 sv = lease_states4(L, i0);
+  if ((sv.x | sv.y | sv.z | sv.w) & kLeaseLive) {
+    const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(L.key + i0);
+    const ulonglong2 k23 = *reinterpret_cast<const ulonglong2*>(L.key + i0 + 2);
+    const uint4 srv = *reinterpret_cast<const uint4*>(L.servant + i0);
+    const longlong2 e01 = *reinterpret_cast<const longlong2*>(L.expires + i0);
+    const longlong2 e23 = *reinterpret_cast<const longlong2*>(L.expires + i0 + 2);
+    st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
+    s4[0] = srv.x, s4[1] = srv.y, s4[2] = srv.z, s4[3] = srv.w;
+    k4[0] = k01.x, k4[1] = k01.y, k4[2] = k23.x, k4[3] = k23.y;
+    e4[0] = e01.x, e4[1] = e01.y, e4[2] = e23.x, e4[3] = e23.y;
   }
   // One atomicAdd per wave: the wave's records in (k, lane) order behind the base it drew.
   unsigned long long m4[4];
@@ -86,20 +84,8 @@ __global__ __launch_bounds__(256) void k_lease_load(LeaseCols n, LeaseState* nst
                                                     unsigned long long next_id) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t filed = 0;
-  if (i < count && i < in.cap) {
-    const unsigned long long id = in.id[i];
-    const uint32_t h = lease_home(n, id);
-    for (uint32_t d = 0; d <= n.mask; ++d) {
-      const uint32_t slot = (h + d) & n.mask;
-      if (n.key[slot] != kLeaseEmpty || atomicCAS(&n.key[slot], kLeaseEmpty, id) != kLeaseEmpty) continue;
-      n.expires[slot] = in.expires[i];
-      n.servant[slot] = in.servant[i];
-      n.state[slot] = in.state[i];
-      if (d) atomicMax(&nst->max_disp, d);
-      filed = 1;
-      break;
-    }
-  }
+  if (i < count && i < in.cap)
+    filed = lease_file(n, nst, in.id[i], in.expires[i], in.servant[i], in.state[i]) != kNone ? 1u : 0u;
   if (i == 0) nst->next_id = next_id;
   // One atomic per workgroup.
   __shared__ uint32_t s_cnt;

@@ -2,7 +2,8 @@
 // lease_table.h, wait_lease.h, rpc_stream.h): a pass of ceil(n / 1024) workgroups of 256 threads,
 // thread i of a workgroup owning four consecutive positions, the workgroups ordered by a ticket
 // (not by blockIdx: a workgroup that looks back only ever waits for workgroups that have started)
-// and chained by a decoupled look-back.
+// and chained by a decoupled look-back. Beside them the wave's helpers of the passes over L and W:
+// the wave sum and the combine of equal keys inside a wave (wave_combine).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +15,34 @@ namespace ydc {
 // Sum over the wave of a value per lane (every lane gets it).
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan(v), 63);
+}
+
+constexpr uint32_t kRequestorRounds = 4;  // distinct keys a wave combines before its lanes go alone
+
+// Equal keys combined inside the wave before a global atomic (one requestor that owns most of a table is
+// the normal case, and a plain pass would put an atomic per entry on one address). Round by round the
+// first active lane broadcasts its key, the lanes that hold it are balloted, and
+//   each(key0, mine, same, leads, round)
+// is called by all lanes together: key0 the round's key, `mine` whether this lane holds it, `same` the
+// ballot of those lanes, `leads` true in the one lane that adds for them. The functor may use wave
+// operations (it takes its sums over `mine`), and only the leading lane may write. After
+// kRequestorRounds distinct keys the loop ends — a wave of 64 distinct keys would otherwise loop 64
+// times to save nothing — and the lanes still active are returned: those add for themselves.
+// EVERY LANE OF THE WAVE MUST GET HERE (wave-uniform control flow around the call), active or not.
+template <class Each>
+__device__ __forceinline__ bool wave_combine(bool active, uint32_t key, Each&& each) {
+  const uint32_t lane = lane_id();
+  unsigned long long todo = __ballot(active);
+  for (uint32_t round = 0; todo && round < kRequestorRounds; ++round) {  // (wave-uniform)
+    const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
+    const uint32_t key0 = (uint32_t)__shfl((int)key, (int)lead, 64);
+    const bool mine = active && key == key0;
+    const unsigned long long same = __ballot(mine);
+    each(key0, mine, same, lane == lead, round);
+    active = active && !mine;
+    todo &= ~same;
+  }
+  return active;
 }
 
 // A look-back word: flag (2 bits; 0: not published yet) | payload (62 bits). A payload is two

@@ -12,7 +12,7 @@
 // The table is persistent: open addressing, keyed by requestor, in device memory,
 //   word u64 | slot_time | zombie_time | prefetch_time | wait_time | wait_row_time   (u64 each, SoA)
 // with requestor_index.h's slot word ((1 << 32) | requestor_ip, 0 for a free slot: all 2^32 ids are
-// ordinary keys) and index_home.h's home slot, then linear probing. At least kUsageMinSlots slots, a
+// ordinary keys) and index_home.h's home slot, then linear probing. At least kIndexMinSlots slots, a
 // power of two, at most half full: the host keeps a bound that errs high on the keys the next accrual
 // can meet and files the table again into a larger one between ticks (k_usage_rehash), so a claim
 // always finds room. Should one not, it is counted in `dropped` and the tick ends in an error: an
@@ -28,16 +28,15 @@
 //                   The workgroup that finishes last adds dq to `quanta`, 1 to `ticks` and stores the
 //                   totals to the page-locked result block.
 //   k_usage_find    thread per query; a miss is a row of zeros.
-//   k_usage_fold    one ticket-ordered tile pass (stream_tile.h) over the slots, as k_requestor_fold:
+//   k_usage_fold    one ticket-ordered tile pass over the slots (slot_fold of slot_probe.h), as k_requestor_fold:
 //                   THE ORDER OF THE ROWS IS UNSPECIFIED (the Python wrapper sorts them).
 //   k_usage_load    thread per given row: its key claimed, its five sums added. Duplicates add together.
 //   k_usage_rehash  thread per slot of the old table: the occupied ones filed into the new one.
 //
 // Hot key: one requestor that owns most of L is the normal case, and a plain pass would put 3 |L|
-// 64-bit atomics on three addresses. Equal keys are combined inside the wave first, as requestor_add
-// does: a first-lane broadcast, a ballot of the lanes with that key, and after kRequestorRounds distinct
-// keys the lanes that are left add for themselves. The lead lane multiplies the combined COUNTS by dq
-// once, so a wave issues at most three 64-bit atomics per key for leases and two for W. Over L a thread
+// 64-bit atomics on three addresses. Equal keys are combined inside the wave first (wave_combine of
+// stream_tile.h: after kRequestorRounds distinct keys the lanes that are left add for themselves).
+// The lead lane multiplies the combined COUNTS by dq once, so a wave issues at most three 64-bit atomics per key for leases and two for W. Over L a thread
 // merges its four slots by requestor before the wave combines, and the four waves' first keys meet in
 // LDS, so the hot key takes one set of atomics per workgroup (stream_depart.h's form). All sums are
 // uint64 modulo 2^64 and all additions integer atomics in device memory: the result does not depend
@@ -58,9 +57,8 @@
 namespace ydc {
 
 constexpr uint32_t kUsageCols = 5;  // slot_time | zombie_time | prefetch_time | wait_time | wait_row_time
-constexpr uint32_t kUsageTile = 1024;      // slots per workgroup of the fold (256 x 4)
 constexpr uint32_t kUsageWaitBlocks = 64;  // workgroups of the accrual's stride part at the most
-// (kUsageMinSlots and usage_slots: index_home.h)
+// (kIndexMinSlots and usage_slots: index_home.h)
 
 struct UsageState {
   unsigned long long unattributed, quanta, ticks;
@@ -90,42 +88,14 @@ struct UsageRow {
 };
 static_assert(sizeof(UsageRow) == 48, "ydc_usage_row is 48 bytes");
 
-__device__ __forceinline__ uint32_t usage_home(const UsageTable& tb, uint32_t ip) {
-  return (uint32_t)book_index_mix(ip) & tb.mask;
-}
-
-// The slot of `ip`, claimed if nobody had it (the claim that publishes a new key bumps n_keys).
-// kNone: the table is full.
+// The slot of `ip` (requestor_index.h's claim), claimed if nobody had it: the claim that publishes a new
+// key bumps n_keys. kNone: the table is full, and the addition is counted in `dropped`.
 __device__ __forceinline__ uint32_t usage_claim(const UsageTable& tb, uint32_t ip) {
-  const unsigned long long w = kRequestorOccupied | ip;
-  uint32_t h = usage_home(tb, ip);
-  for (uint32_t it = 0; it <= tb.mask; ++it) {
-    // (a published word never changes: a plain look first, as requestor_claim)
-    unsigned long long at = __hip_atomic_load(&tb.word[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (at == 0) {
-      at = atomicCAS(&tb.word[h], 0ull, w);
-      if (at == 0) {
-        atomicAdd(&tb.st->n_keys, 1u);
-        return h;
-      }
-    }
-    if (at == w) return h;
-    h = (h + 1) & tb.mask;
-  }
-  atomicAdd(&tb.st->dropped, 1u);
-  return kNone;
-}
-
-__device__ __forceinline__ uint32_t usage_lookup(const UsageTable& tb, uint32_t ip) {
-  const unsigned long long w = kRequestorOccupied | ip;
-  uint32_t h = usage_home(tb, ip);
-  for (uint32_t it = 0; it <= tb.mask; ++it) {
-    const unsigned long long at = tb.word[h];
-    if (at == w) return h;
-    if (at == 0) break;
-    h = (h + 1) & tb.mask;
-  }
-  return kNone;
+  bool published;
+  const uint32_t h = requestor_claim(tb.word, tb.mask, ip, &published);
+  if (published) atomicAdd(&tb.st->n_keys, 1u);
+  if (h == kNone) atomicAdd(&tb.st->dropped, 1u);
+  return h;
 }
 
 // Columns col, col + 1, col + 2 of `ip`'s slot gain n | a | b (already multiplied by dq).
@@ -152,28 +122,19 @@ struct UsageLead {
 };
 
 // Per active lane n | a | b entries of key `ip`: n dq | a dq | b dq into columns col, col + 1, col + 2.
-// With `combine` every lane of the wave must get here (wave-uniform control flow around the call).
+// With `combine` every lane of the wave must get here (wave_combine).
 // defer != NULL: the first round's key is not added here but left in *defer for the workgroup to add.
 __device__ __forceinline__ void usage_add(const UsageTable& tb, bool combine, bool active, uint32_t ip, uint32_t col,
                                           uint32_t n, uint32_t a, uint32_t b, unsigned long long dq, UsageLead* defer) {
-  if (combine) {
-    const uint32_t lane = lane_id();
-    unsigned long long todo = __ballot(active);
-    for (uint32_t round = 0; todo && round < kRequestorRounds; ++round) {  // (wave-uniform)
-      const uint32_t lead = (uint32_t)__builtin_ctzll(todo);
-      const uint32_t ip0 = (uint32_t)__shfl((int)ip, (int)lead, 64);
-      const bool mine = active && ip == ip0;
-      const unsigned long long same = __ballot(mine);
+  if (combine)
+    active = wave_combine(active, ip, [&](uint32_t ip0, bool mine, unsigned long long, bool leads, uint32_t round) {
       const unsigned long long sn = wave_sum_wide(mine ? n : 0u), sa = wave_sum_wide(mine ? a : 0u),
                                sb = wave_sum_wide(mine ? b : 0u);
-      if (lane == lead) {
+      if (leads) {
         if (defer && round == 0) *defer = UsageLead{ip0, (uint32_t)sn, (uint32_t)sa, (uint32_t)sb};  // (at most 256 each)
         else usage_add_one(tb, ip0, col, sn * dq, sa * dq, sb * dq);
       }
-      active = active && !mine;
-      todo &= ~same;
-    }
-  }
+    });
   if (active) usage_add_one(tb, ip, col, n * dq, a * dq, b * dq);
 }
 
@@ -200,11 +161,8 @@ __global__ __launch_bounds__(256) void k_usage_accrue(LeaseCols L, const uint4* 
   __shared__ UsageLead s_lead[4];  // (256 threads: four waves)
   if (blockIdx.x < l_blocks) {
     const uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    uint32_t st4[4] = {0, 0, 0, 0};
-    if (i0 <= L.mask) {  // (the slot count is a multiple of 4)
-      const uint4 sv = *reinterpret_cast<const uint4*>(L.state + i0);
-      st4[0] = sv.x, st4[1] = sv.y, st4[2] = sv.z, st4[3] = sv.w;
-    }
+    const uint4 sv = lease_states4(L, i0);
+    const uint32_t st4[4] = {sv.x, sv.y, sv.z, sv.w};
     // The thread's four slots merged by requestor: ng groups of gn leases, gz zombies, gp prefetched.
     uint32_t gip[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0}, gz[4] = {0, 0, 0, 0}, gp[4] = {0, 0, 0, 0};
     uint32_t ng = 0, nobody = 0;
@@ -301,53 +259,19 @@ __global__ __launch_bounds__(256) void k_usage_find(const uint32_t* q, uint32_t 
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t ip = q[i];
-  out[i] = usage_row_at(tb, ip, usage_lookup(tb, ip));
+  out[i] = usage_row_at(tb, ip, requestor_lookup(tb.word, tb.mask, ip));
 }
 
-// The fold's own bookkeeping, cleared by the host in front of the launch; its look-back words follow it.
-struct UsageFoldState {
-  uint32_t ticket;
-  uint32_t n_rows;  // the result: occupied slots
-};
+// The fold's bookkeeping and tile: slot_probe.h's.
+using UsageFoldState = SlotFoldState;
+constexpr uint32_t kUsageTile = kSlotFoldTile;
 
-// ceil(slots / kUsageTile) workgroups of 256 threads, thread i of a workgroup owning four consecutive
-// slots. out: out_cap rows of room (a rank beyond it is counted and not written).
+// slot_fold's grid: ceil(slots / kUsageTile) workgroups of 256 threads. out: out_cap rows of room.
 __global__ __launch_bounds__(256) void k_usage_fold(UsageTable tb, UsageFoldState* fs, unsigned long long* lookback,
                                                     UsageRow* out, uint32_t out_cap) {
-  __shared__ uint32_t lds[17];
-  __shared__ uint32_t s_bid, s_pre;
-  if (threadIdx.x == 0) s_bid = atomicAdd(&fs->ticket, 1u);
-  __syncthreads();
-  const uint32_t bid = s_bid;
-  const uint32_t h0 = bid * kUsageTile + threadIdx.x * 4;
-  unsigned long long w4[4] = {0, 0, 0, 0};
-  if (h0 <= tb.mask) {  // (the slot count is a multiple of 1024)
-    const ulonglong2 w01 = *reinterpret_cast<const ulonglong2*>(tb.word + h0);
-    const ulonglong2 w23 = *reinterpret_cast<const ulonglong2*>(tb.word + h0 + 2);
-    w4[0] = w01.x, w4[1] = w01.y, w4[2] = w23.x, w4[3] = w23.y;
-  }
-  uint32_t n_keep = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) n_keep += w4[i] ? 1u : 0u;
-  uint32_t tot = 0;
-  const uint32_t ex = block_exclusive_scan(n_keep, lds, &tot);
-  if (threadIdx.x < 64) {
-    LbWords<1> agg;
-    agg.w[0] = lb_pack(tot);
-    const LbWords<1> pre = tile_lookback<1>(lookback, bid, threadIdx.x, agg);
-    if (threadIdx.x == 0) {
-      s_pre = lb_lo(pre.w[0]);
-      if (bid == gridDim.x - 1) fs->n_rows = s_pre + tot;
-    }
-  }
-  __syncthreads();
-  uint32_t dst = s_pre + ex;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (!w4[i]) continue;
-    if (dst < out_cap) out[dst] = usage_row_at(tb, (uint32_t)w4[i], h0 + i);
-    ++dst;
-  }
+  slot_fold(tb.word, tb.mask, fs, lookback, out_cap, [&](uint32_t dst, unsigned long long w, uint32_t h) {
+    out[dst] = usage_row_at(tb, (uint32_t)w, h);
+  });
 }
 
 // ceil(max(n, 1) / 256) workgroups. add: what the three totals gain (thread 0's).

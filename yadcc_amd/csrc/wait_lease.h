@@ -169,7 +169,7 @@ __device__ __forceinline__ void commit_pass(WaitCols t, WaitLeaseCols lf, const 
           // (started_at: the clock at the grant, task_dispatcher.cc:133; no prefetch in these modes)
           lease_insert_inspected(L, st, ins, ids[i], expires, r[i], hdr->now, j, false);
         } else {
-          lease_insert(L, st, ids[i], expires, r[i]);
+          lease_file(L, st, ids[i], expires, r[i], kLeaseLive);
         }
       }
     }
